@@ -4,6 +4,7 @@ batch 256 per GPU (BASELINE.json configs[1]: BlazeFace back-camera 256^2 -> Mobi
 
   python bench.py                         # 1 GPU, 200 timed steps after 10 warm-ups
   python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # + the last timed step's outputs as DIR/<name>.npy
   python bench.py --gpus N --steps K --warmup W        # N > 1: starts N ranks ITSELF (launch_ranks below), one per GPU
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W         # ... or runs as one rank of an external launcher (WORLD_SIZE set)
@@ -56,7 +57,7 @@ def cpu_budget():
 
 def launch_ranks(n, argv):
     """`bench.py --gpus N` without an external launcher: start N fresh rank processes of this script (RANK / LOCAL_RANK /
-    WORLD_SIZE / MASTER_* set, rendezvous on 127.0.0.1, GPU_MAX_HW_QUEUES=8 -- see below), relay rank 0's single JSON line
+    WORLD_SIZE / MASTER_* set, rendezvous on 127.0.0.1), relay rank 0's single JSON line
     to this process's stdout and return non-zero if any rank fails or the line does not report n_gpus == N.  The parent
     imports neither torch nor the HIP library and makes NO GPU call (a process that has touched the GPU must not be
     replaced or forked from); children are started with subprocess (fork + exec of a fresh interpreter) and stopped, if
@@ -72,7 +73,6 @@ def launch_ranks(n, argv):
         env = dict(os.environ)
         env.update(RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), LOCAL_WORLD_SIZE=str(n), MASTER_ADDR="127.0.0.1",
                    MASTER_PORT=str(port), BENCH_LAUNCHED_BY="bench.py")
-        env.setdefault("GPU_MAX_HW_QUEUES", "8")
         env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         env.setdefault("OMP_NUM_THREADS", str(max(1, cores // n)))
         procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__)] + list(argv), env=env,
@@ -138,16 +138,9 @@ if __name__ == "__main__" and "WORLD_SIZE" not in os.environ and _requested_gpus
     sys.exit(launch_ranks(_requested_gpus(sys.argv[1:]), sys.argv[1:]))      # before torch / HIP are even imported
 os.environ.setdefault("OMP_NUM_THREADS", str(cpu_budget()))     # (read when torch's thread pools come up)
 
-# The step runs on up to four streams (detector, embedder, cross-rank exchange, RCCL's own).  HIP maps streams onto
-# GPU_MAX_HW_QUEUES hardware queues (default 4) round-robin: with the default, the embedder's stream lands on the detector's
-# queue once the process group exists, and the two networks serialise (4.69 ms per step against 4.15 in the one-GPU RCCL
-# rehearsal).  Per-process runtime knob, read when HIP initialises; only set where the process group exists (with two streams
-# the default mapping is fine: 4.05 ms).
 # how this process came to be (before init_dist fills in defaults): started by launch_ranks, by an external launcher, or alone
 LAUNCH_MODE = ("self-launched (bench.py started the ranks)" if os.environ.get("BENCH_LAUNCHED_BY") == "bench.py" else
                "external launcher (WORLD_SIZE in the environment)" if "WORLD_SIZE" in os.environ else "in-process, one rank")
-if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("BENCH_FORCE_DIST"):
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import torch  # noqa: E402
 
@@ -308,13 +301,16 @@ def run_stub(args):
     os.environ.setdefault("RANK", "0")
     os.environ.setdefault("WORLD_SIZE", "1")
     dist.init_process_group("gloo")
-    dist.barrier()
+
+    def barrier():      # not dist.barrier(): it asks torch for the accelerator, which opens the GPU, and the stub must not
+        dist.all_reduce(torch.zeros(1))
+    barrier()
     t0 = time.perf_counter()
     faces = 0
     for _ in range(args.steps):
         time.sleep(0.001)
         faces += 100 + rank
-    dist.barrier()
+    barrier()
     elapsed, faces_all = reduce_time_and_count(time.perf_counter() - t0, faces, max(world, 2), dist, None, "gloo")
     launch = launch_record(args, world, rank, torch.device("cpu"), dist, "gloo", faces)
     if rank == 0:
@@ -337,6 +333,29 @@ def reduce_time_and_count(elapsed, count, world, dist, dev, backend):
     dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dist.all_reduce(fsum, op=dist.ReduceOp.SUM)
     return float(tmax), float(fsum)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as `path/<name>.npy`, floating point as float32 (float64 stays float64), integers and
+    booleans as float64 (exact).  Past DUMP_LIMIT_BYTES in all, every array keeps the same fixed, seeded sample of its rows,
+    so that two builds run with the same arguments compare output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        host[name] = a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) and a.dtype != np.float64 else np.float64)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        for name, a in host.items():
+            if a.ndim and a.shape[0] > 1:
+                rows = np.random.default_rng(0).choice(a.shape[0], max(1, a.shape[0] * DUMP_LIMIT_BYTES // total), replace=False)
+                host[name] = a[np.sort(rows)]
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -368,8 +387,10 @@ def run_pipeline(args):
                                       lambda R: S.row_inv_norm(R.to(dev)).cpu(), comm=lambda t: t.cpu())
 
     matched = [0]
+    last_out = [None]                           # the result dict of the most recent step (--dump-outputs)
 
     def finish(out):
+        last_out[0] = out
         n = out["n_faces"]
         if multi:
             # two-stream step: the embeddings come from the embedder's stream, and the exchange is queued THERE (its copy into
@@ -507,6 +528,9 @@ def run_pipeline(args):
     t1 = time.perf_counter()
     for p in plans:
         p._timing = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller (FacePipeline.step): face count, crop records, embeddings, filter result
+        dump_outputs(args.dump_outputs, {k: v for k, v in last_out[0].items() if k != "done"})
 
     elapsed, faces_all = reduce_time_and_count(t1 - t0, faces, world if not multi else max(world, 2), dist, dev, backend)
     launch = launch_record(args, world, rank, dev, dist, backend, faces)
@@ -704,6 +728,8 @@ def run_c5(args):
     if dist is not None:
         dist.barrier()
     t1 = time.perf_counter()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"best": best, "arg": arg, "keep": keep})
     nr = nr_local * world
     elapsed, rows_all = reduce_time_and_count(t1 - t0, M * args.steps, world, dist, dev, backend)
     launch = launch_record(args, world, rank, dev, dist, backend, M * args.steps)
@@ -778,6 +804,9 @@ def main():
     ap.add_argument("--box-px", type=float, default=W.BOX_PX,
                     help="synthetic detector's box size (model-input pixels); sets how candidates cluster in the NMS")
     ap.add_argument("--gallery-rows", type=int, default=125_000, help="c5: gallery rows per rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, float32 "
+                         "or float64, at most 64 MB in all; the inputs are seeded, so runs with the same arguments compare")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 20 if args.workload == "c5" else 200

@@ -279,3 +279,28 @@ def test_bench_launcher_fails_loudly():
     assert r.returncode == 3 and r.stdout.strip() == "" and "rank 1 failed" in r.stderr
     r = _run_bench({"BENCH_STUB_STEP": "1", "WORLD_SIZE": "1", "RANK": "0"}, "--gpus", "2", "--steps", "2")
     assert r.returncode != 0 and r.stdout.strip() == "" and "--gpus 2 but WORLD_SIZE = 1" in r.stderr
+
+
+def test_bench_dump_outputs_dtypes_and_size_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs writes every array as <name>.npy: floating point as float32 (float64 kept), integers and
+    booleans as float64, exactly.  Past the size cap every array keeps the same seeded sample of its rows, run after run."""
+    import bench
+    n = 300
+    arrays = {"n_faces": n, "emb": torch.randn(n, 64), "arg": torch.arange(n, dtype=torch.int32) * 7,
+              "keep": torch.arange(n) % 3 == 0, "best": torch.rand(n, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    full = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in arrays}
+    assert {k: a.dtype for k, a in full.items()} == {"n_faces": np.float64, "emb": np.float32, "arg": np.float64,
+                                                     "keep": np.float64, "best": np.float64}
+    assert int(full["n_faces"]) == n and np.array_equal(full["emb"], arrays["emb"].numpy())
+    assert np.array_equal(full["arg"], np.arange(n) * 7) and np.array_equal(full["keep"], np.arange(n) % 3 == 0)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 40_000)
+    for d in ("cut1", "cut2"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    cut = {k: np.load(tmp_path / "cut1" / f"{k}.npy") for k in arrays}
+    assert sum(a.nbytes for a in cut.values()) <= 40_000 and 0 < len(cut["arg"]) < n
+    rows = (cut["arg"] / 7).astype(np.int64)
+    assert np.all(np.diff(rows) > 0)
+    for k in ("emb", "arg", "keep", "best"):
+        np.testing.assert_array_equal(cut[k], full[k][rows])
+        np.testing.assert_array_equal(cut[k], np.load(tmp_path / "cut2" / f"{k}.npy"))

@@ -543,3 +543,28 @@ def test_bench_gpus_2_self_launch_on_one_gpu(dev):
     assert len(per_rank) == 2 and all(4 * 256 <= n <= 4 * 256 * 4 for n in per_rank)         # ~2 faces per frame, 4 steps each
     assert abs(rec["value"] * rec["ms_per_step"] * 4e-3 - sum(per_rank)) <= 1.0                # whole-job faces / max-rank time
     assert rec["config"]["frames_per_step_per_gpu"] == 256 and "gloo" in rec["launch"]["backend"]
+
+
+def test_bench_dump_outputs(dev, tmp_path):
+    """`python bench.py --dump-outputs DIR`: the result of the last timed step as .npy files -- face count, crop records,
+    embeddings and the cosine filter's answer for them, which must be the oracle's answer on the dumped embeddings."""
+    import subprocess
+    import sys
+    from conftest import ROOT
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--no-cpu-baseline", "--no-other-configs", "--no-fp32-leg", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert json.loads(r.stdout.strip().splitlines()[-1])["steps"] == 3
+    d = {k: np.load(tmp_path / f"{k}.npy") for k in ("n_faces", "info", "emb", "items", "best", "arg", "keep")}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    n = int(d["n_faces"])
+    assert 256 <= n <= 256 * 4
+    assert d["info"].shape == (n, 7) and d["items"].shape == (n, 9) and d["emb"].shape == (n, 512)
+    assert d["best"].shape == d["arg"].shape == d["keep"].shape == (n,)
+    np.testing.assert_allclose(np.linalg.norm(d["emb"], axis=1), 1.0, atol=1e-5)
+    best, _, keep, s = similarity_ref.cosine_filter(d["emb"], W.make_reference(10000, "cpu").numpy(), 0.3)
+    assert np.abs(d["best"] - best).max() < 1e-5
+    assert np.abs(s[np.arange(n), d["arg"].astype(np.int64)] - best).max() < 1e-5           # an argmax, up to rounding
+    clear = np.abs(best - 0.3) > 1e-5
+    np.testing.assert_array_equal(d["keep"][clear], keep[clear].astype(np.float64))

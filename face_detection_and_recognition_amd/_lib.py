@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfacepath.so")
 
 FP_OK = 0
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 # fp_op_kind
 OP_CONV, OP_DWCONV, OP_MAXPOOL, OP_UPSAMPLE2X, OP_COPY, OP_L2NORM, OP_BLAZEBLOCK, OP_DWPW, OP_YSTEM = 1, 2, 3, 4, 5, 6, 7, 8, 9
@@ -68,6 +68,22 @@ class FpJpegInfo(C.Structure):
                 ("quant", (C.c_uint16 * 64) * 3)]
 
 
+class FpJpegHuff(C.Structure):
+    """Mirror of struct fp_jpeg_huff."""
+    _fields_ = [("look", C.c_uint16 * 512), ("maxcode", C.c_int32 * 18), ("valoff", C.c_int32 * 18), ("vals", C.c_uint8 * 256)]
+
+
+class FpJpegScan(C.Structure):
+    """Mirror of struct fp_jpeg_scan (ABI 12)."""
+    _fields_ = [("data_off", C.c_int64), ("data_len", C.c_int64), ("n_coefs", C.c_int64), ("coef_off", C.c_int64 * 3),
+                ("blocks_w", C.c_int32 * 3), ("mcux", C.c_int32), ("mcuy", C.c_int32), ("restart_interval", C.c_int32),
+                ("blocks_per_mcu", C.c_int32), ("ncomp", C.c_int32), ("slot_comp", C.c_uint8 * 8), ("slot_tab", C.c_uint8 * 8),
+                ("slot_dy", C.c_uint8 * 8), ("slot_dx", C.c_uint8 * 8), ("hs", C.c_int32 * 3), ("vs", C.c_int32 * 3),
+                ("dc", FpJpegHuff * 3), ("ac", FpJpegHuff * 3)]
+
+
+JPEG_DECODE_ON_HOST = 1          # fp_jpeg_entropy_decode_device status: decode this image with fp_jpeg_entropy_decode
+
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
@@ -114,6 +130,11 @@ SIGNATURES = {
     "fp_jpeg_entropy_decode": (_I, [_P, _SZ, C.POINTER(FpJpegInfo), _P]),
     "fp_jpeg_workspace_bytes": (_SZ, [C.POINTER(FpJpegInfo)]),
     "fp_jpeg_reconstruct": (_I, [_P, C.POINTER(FpJpegInfo), _P, _SZ, _P, _I, _P]),
+    "fp_jpeg_scan_prepare": (_I, [_P, _SZ, C.POINTER(FpJpegInfo), C.POINTER(FpJpegScan)]),
+    "fp_jpeg_entropy_workspace_bytes": (_SZ, [C.POINTER(FpJpegScan), _I, _I, _I]),
+    "fp_jpeg_entropy_decode_device": (_I, [_P, C.POINTER(FpJpegScan), C.POINTER(_I64), _I, _P, C.POINTER(_I64), _P, _P, _SZ, _I,
+                                           _I, _P]),
+    "fp_jpeg_entropy_decode_emulate": (_I, [_P, _SZ, C.POINTER(FpJpegScan), _P, _I, _I, C.POINTER(C.c_int32)]),
     "fp_tracker_step": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _F, _F, _P, _P, _P]),
 }
 

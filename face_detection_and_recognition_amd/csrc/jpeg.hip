@@ -262,6 +262,7 @@ struct Scan {
 };
 
 int read_sos(const unsigned char* s, unsigned len, const fp_jpeg_info& info, const Frame& fr, Scan& sc) {
+  if (len < 3) return FP_ERR_INVALID_ARG;        // an empty segment body: s[0] would lie behind it
   sc.ns = s[0];
   if (sc.ns < 1 || sc.ns > info.ncomp || len != 6u + 2u * sc.ns) return FP_ERR_INVALID_ARG;
   for (int i = 0; i < sc.ns; ++i) {
@@ -695,6 +696,74 @@ int fp_jpeg_entropy_decode(const uint8_t* data, size_t n, const fp_jpeg_info* in
   delete[] dc;
   if (rc) return rc;
   return scans > 0 ? FP_OK : FP_ERR_INVALID_ARG;
+}
+
+int fp_jpeg_scan_prepare(const uint8_t* data, size_t n, fp_jpeg_info* info, fp_jpeg_scan* scan) {
+  if (!data || !info || !scan) return FP_ERR_INVALID_ARG;
+  Huff* dc = new Huff[8];
+  Huff* ac = dc + 4;
+  memset(dc, 0, 8 * sizeof(Huff));
+  Frame fr;
+  memset(scan, 0, sizeof(*scan));
+  const long pos = parse_headers(data, n, *info, fr, dc, ac);
+  int rc = pos < 0 ? (int)pos : FP_OK;
+  unsigned len = 0;
+  Scan sc;
+  if (!rc && info->progressive) rc = FP_ERR_UNSUPPORTED;
+  if (!rc && (size_t)pos + 2 > n) rc = FP_ERR_INVALID_ARG;
+  if (!rc) {
+    len = be16(data + pos);
+    if (len < 2 || (size_t)pos + len > n) rc = FP_ERR_INVALID_ARG;
+  }
+  if (!rc) rc = read_sos(data + pos + 2, len, *info, fr, sc);
+  if (!rc && sc.ns != info->ncomp) rc = FP_ERR_UNSUPPORTED;     // the first scan must carry every component
+  for (int i = 0; !rc && i < sc.ns; ++i) {
+    for (int j = 0; j < i; ++j)
+      if (sc.ci[j] == sc.ci[i]) rc = FP_ERR_UNSUPPORTED;
+    if (!rc && (!dc[sc.td[i]].present || !ac[sc.ta[i]].present)) rc = FP_ERR_INVALID_ARG;   // decode_scan's check
+  }
+  const size_t off = (size_t)pos + len;
+  long nblocks = 0;
+  for (int c = 0; !rc && c < info->ncomp; ++c) nblocks += (long)info->blocks_w[c] * info->blocks_h[c];
+  if (!rc && (n - off > (size_t)FP_JPEG_DEV_MAX_BYTES || nblocks > FP_JPEG_DEV_MAX_BLOCKS)) rc = FP_ERR_UNSUPPORTED;
+  if (!rc) {
+    scan->data_off = (int64_t)off;
+    scan->data_len = (int64_t)(n - off);
+    scan->n_coefs = info->n_coefs;
+    scan->mcux = info->mcux;
+    scan->mcuy = info->mcuy;
+    scan->restart_interval = info->restart_interval;
+    scan->ncomp = info->ncomp;
+    int slot = 0;
+    for (int i = 0; i < sc.ns; ++i) {
+      const int c = sc.ci[i];
+      scan->coef_off[c] = info->coef_off[c];
+      scan->blocks_w[c] = info->blocks_w[c];
+      scan->hs[c] = info->hs[c];
+      scan->vs[c] = info->vs[c];
+      for (int v = 0; v < info->vs[c]; ++v)
+        for (int h = 0; h < info->hs[c]; ++h) {
+          scan->slot_comp[slot] = (uint8_t)c;
+          scan->slot_tab[slot] = (uint8_t)i;
+          scan->slot_dy[slot] = (uint8_t)v;
+          scan->slot_dx[slot] = (uint8_t)h;
+          ++slot;
+        }
+      const Huff* src[2] = {&dc[sc.td[i]], &ac[sc.ta[i]]};
+      fp_jpeg_huff* dst[2] = {&scan->dc[i], &scan->ac[i]};
+      for (int t = 0; t < 2; ++t) {
+        memcpy(dst[t]->look, src[t]->look, sizeof(dst[t]->look));
+        memcpy(dst[t]->vals, src[t]->vals, sizeof(dst[t]->vals));
+        for (int l = 0; l < 18; ++l) {
+          dst[t]->maxcode[l] = l >= 1 && l <= 16 ? src[t]->maxcode[l] : -1;
+          dst[t]->valoff[l] = l >= 1 && l <= 16 ? src[t]->valptr[l] - src[t]->mincode[l] : 0;
+        }
+      }
+    }
+    scan->blocks_per_mcu = slot;
+  }
+  delete[] dc;
+  return rc;
 }
 
 size_t fp_jpeg_workspace_bytes(const fp_jpeg_info* info) {

@@ -69,13 +69,14 @@ def read_and_preprocess_img(img_path: str, in_size=(160, 160), dct_method: str =
     return preprocess_tf_standardize(t, in_size)[0]
 
 
-def embed_images(model, paths, batch_size=32, preprocess="mobile_facenet"):
+def embed_images(model, paths, batch_size=32, preprocess="mobile_facenet", entropy="host"):
     """Decode (Huffman stage on a host thread pool, the rest on the device: modules/utils/jpeg.py), then resize + normalise and
     embed on device, batch by batch.  preprocess:
     "mobile_facenet" = cv2-style resize of the whole image to 112x112, (x - 127.5) / 127.5, BGR
     (fde/modules/mobile_facenet/utils.py:13-17); "tf_standardize" = the reference filter's own TF preprocess
     (filter_faces_using_reference.py:60-68: RGB, [0,1], bilinear resize, per-image standardisation) at the network's
-    112x112 input size."""
+    112x112 input size.  entropy="device": the Huffman stage of the sequential JPEGs on the device as well
+    (modules/utils/jpeg.py imread_batch)."""
     if preprocess not in ("mobile_facenet", "tf_standardize"):
         raise ValueError(f"unknown preprocess {preprocess!r}")
     dev = model._device()
@@ -84,7 +85,7 @@ def embed_images(model, paths, batch_size=32, preprocess="mobile_facenet"):
     for i in range(0, len(paths), batch_size):
         chunk = paths[i:i + batch_size]
         plan = model.plan_for(len(chunk))
-        decoded = imread_batch(chunk, dev)       # (B, H, W, 3) when the sizes agree, else a list
+        decoded = imread_batch(chunk, dev, entropy=entropy)   # (B, H, W, 3) when the sizes agree, else a list
         for j in range(len(chunk)):              # images differ in size: one resize launch per image
             img = decoded[j].unsqueeze(0)
             if preprocess == "tf_standardize":

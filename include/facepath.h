@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define FP_ABI_VERSION 11
+#define FP_ABI_VERSION 12
 
 typedef enum fp_status {
   FP_OK = 0,
@@ -292,7 +292,8 @@ typedef struct fp_op {
  *            [32] scale, [32] bias;  [2 slabs][3 planes][32 co][32 k] stem_3 (k: stem_2b's 32 channels, then the pooled map's);  [32] scale,
  *            [32] bias (scale = 1 where the BatchNorm is folded into the conv).
  * ABI history: 1 = round-1 ops; 2 = fp_ext / *_U8 ops (never shipped in a VERDICT-ed tree); 3 = fp_op.flags, row-padded
- * views; 4 = fp_op.Cmid / reserved0, FP_OP_DWBLOCK, FP_OP_BLAZEPAIR; 5 = FP_OPF_SPLIT3; 6 = FP_OP_BLAZECHAIN; 7 = FP_OPF_IN_UP2; 8 = FP_OP_BLAZEPAIR with stride 2; 9 = FP_OPF_OUT_DW, fp_debug_reload_env; 10 = FP_OP_SHUFDOWN, FP_OP_SHUFUNIT, FP_OP_YSTEM2; 11 = FP_OPF_SPLIT3 on FP_OP_STEM_U8.
+ * views; 4 = fp_op.Cmid / reserved0, FP_OP_DWBLOCK, FP_OP_BLAZEPAIR; 5 = FP_OPF_SPLIT3; 6 = FP_OP_BLAZECHAIN; 7 = FP_OPF_IN_UP2; 8 = FP_OP_BLAZEPAIR with stride 2; 9 = FP_OPF_OUT_DW, fp_debug_reload_env; 10 = FP_OP_SHUFDOWN, FP_OP_SHUFUNIT, FP_OP_YSTEM2; 11 = FP_OPF_SPLIT3 on FP_OP_STEM_U8;
+ * 12 = device Huffman decoding of sequential JPEG scans (fp_jpeg_scan, fp_jpeg_scan_prepare, fp_jpeg_entropy_decode_device, section 7).
  */
 
 /* Validates every op against arena_floats / weight_floats, then launches them in order. */
@@ -561,6 +562,19 @@ int fp_tracker_step(float* feats, int* bboxes, int* count, int cap, int D, const
  * (progressive: spectral selection and successive approximation), 8-bit, Huffman, any number of scans, 1 or 3 components, luma
  * sampling 1x1 / 2x1 / 2x2 with 1x1 chroma, restart intervals.  Everything else (arithmetic, lossless, 12-bit, CMYK, other
  * sampling layouts): FP_ERR_UNSUPPORTED, the caller decodes those on the host.
+ *
+ * ABI 12: the Huffman stage of SEQUENTIAL files on the DEVICE as well (csrc/jpegdec.hip), for a whole batch in one call.
+ * fp_jpeg_scan_prepare (host) parses the headers into an fp_jpeg_scan descriptor; it takes SOF0 / SOF1 files whose first scan
+ * is interleaved over every component (a single scan for gray files), with or without restart intervals, up to
+ * FP_JPEG_DEV_MAX_BYTES of scan data and FP_JPEG_DEV_MAX_BLOCKS blocks, and returns FP_ERR_UNSUPPORTED for everything else
+ * (progressive files among them).  fp_jpeg_entropy_decode_device splits every scan without regard to restart markers
+ * into subsequences of sub_bits bits, decodes each from a guessed codeword boundary, re-decodes each from its predecessor's
+ * exit until a whole pass reproduces every exit (at most max_rounds passes: the decodes are then proven to be the serial
+ * decode's), places the blocks by a prefix sum of the block counts and writes them.  The result, for every image it reports
+ * FP_OK or FP_ERR_INVALID_ARG for, equals fp_jpeg_entropy_decode's status and coefficients bit for bit, damaged files
+ * included.  FP_JPEG_DECODE_ON_HOST: the device did not decide this image (a second scan or another segment behind the
+ * first scan, fill bytes 0xff 0xff inside the scan, no proof within max_rounds): run fp_jpeg_entropy_decode on it.
+ * fp_jpeg_entropy_decode_emulate runs the same phases serially on the CPU from the same per-subsequence code.
  */
 typedef struct fp_jpeg_info {
   int32_t width, height, ncomp, restart_interval;
@@ -587,6 +601,55 @@ size_t fp_jpeg_workspace_bytes(const fp_jpeg_info* info);
  */
 int fp_jpeg_reconstruct(const int16_t* coefs, const fp_jpeg_info* info, uint8_t* workspace, size_t ws_bytes, uint8_t* out,
                         int bgr, void* stream);
+
+#define FP_JPEG_DECODE_ON_HOST 1                 /* device status: decode this image with fp_jpeg_entropy_decode */
+#define FP_JPEG_DEV_MAX_BYTES (64ll << 20)       /* scan data of one file the device path takes */
+#define FP_JPEG_DEV_MAX_BLOCKS (1 << 20)         /* 8 x 8 blocks of one image the device path takes */
+
+/* One canonical Huffman table in the device decoder's lookup form. */
+typedef struct fp_jpeg_huff {
+  uint16_t look[512];      /* the next 9 bits -> code length << 8 | symbol; 0 = the code is longer than 9 bits */
+  int32_t maxcode[18];     /* largest code of each length (-1: none of that length) */
+  int32_t valoff[18];      /* a code of length l is symbol vals[code + valoff[l]] */
+  uint8_t vals[256];
+} fp_jpeg_huff;
+
+/* The first scan of a sequential file, as fp_jpeg_entropy_decode_device reads it. */
+typedef struct fp_jpeg_scan {
+  int64_t data_off;        /* byte offset of the entropy-coded data in the file (behind the SOS header) */
+  int64_t data_len;        /* bytes from there to the end of the file */
+  int64_t n_coefs;         /* = fp_jpeg_info.n_coefs */
+  int64_t coef_off[3];     /* = fp_jpeg_info.coef_off */
+  int32_t blocks_w[3];     /* = fp_jpeg_info.blocks_w */
+  int32_t mcux, mcuy;      /* MCUs per row / column */
+  int32_t restart_interval;   /* MCUs per restart segment, 0 = none */
+  int32_t blocks_per_mcu;  /* 1 .. 6 */
+  int32_t ncomp;
+  uint8_t slot_comp[8];    /* per block slot of an MCU, in decode order: component */
+  uint8_t slot_tab[8];     /* ... its tables: dc[slot_tab] / ac[slot_tab] */
+  uint8_t slot_dy[8];      /* ... its block row / column inside the MCU */
+  uint8_t slot_dx[8];
+  int32_t hs[3], vs[3];    /* blocks of each component per MCU */
+  fp_jpeg_huff dc[3], ac[3];  /* the tables of the scan's components, in scan order */
+} fp_jpeg_scan;
+
+/* HOST.  Headers of a file -> info (as fp_jpeg_parse) and scan.  FP_ERR_UNSUPPORTED: not for the device path (see above). */
+int fp_jpeg_scan_prepare(const uint8_t* data, size_t n, fp_jpeg_info* info, fp_jpeg_scan* scan);
+/* Bytes of device workspace fp_jpeg_entropy_decode_device needs for these n files (scans: HOST). */
+size_t fp_jpeg_entropy_workspace_bytes(const fp_jpeg_scan* scans, int n, int sub_bits, int max_rounds);
+/*
+ * DEVICE.  files: device, file i at files + file_off[i]; scans, file_off, coef_off: HOST arrays of n; coefs: device int16, image i
+ * at coefs + coef_off[i] (scans[i].n_coefs values, zeroed here first); status: device int32 [n], FP_OK / FP_ERR_INVALID_ARG /
+ * FP_JPEG_DECODE_ON_HOST; workspace: device, 16-byte aligned, fp_jpeg_entropy_workspace_bytes.  sub_bits (>= 32, a multiple of
+ * 8): subsequence length; max_rounds (>= 1): synchronisation passes.  Copies the descriptors into the workspace before it returns.
+ */
+int fp_jpeg_entropy_decode_device(const uint8_t* files, const fp_jpeg_scan* scans, const int64_t* file_off, int n, int16_t* coefs,
+                                  const int64_t* coef_off, int32_t* status, void* workspace, size_t ws_bytes, int sub_bits,
+                                  int max_rounds, void* stream);
+/* HOST.  The device algorithm run serially on one file: returns the status the device would report, coefs (HOST, n_coefs) as
+ * the device would write them; rounds (may be NULL) = synchronisation passes until the proof (max_rounds + 1: none). */
+int fp_jpeg_entropy_decode_emulate(const uint8_t* data, size_t n, const fp_jpeg_scan* scan, int16_t* coefs, int sub_bits,
+                                   int max_rounds, int32_t* rounds);
 
 #ifdef __cplusplus
 }

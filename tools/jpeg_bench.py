@@ -1,5 +1,6 @@
-"""Decode rate of the JPEG front end (modules/utils/jpeg.py) against Pillow on the host: 256 synthetic 576 x 1024 4:2:0 frames.
-    python tools/jpeg_bench.py [n_frames] [threads]"""
+"""Decode rate of the JPEG front end (modules/utils/jpeg.py) against Pillow on the host: 256 synthetic 576 x 1024 4:2:0 frames,
+then the host and the device Huffman stage (entropy="host" / "device") alternated on the frames and on 1024 small crops.
+    python tools/jpeg_bench.py [n_frames] [threads] [repeats]"""
 import io
 import os
 import sys
@@ -15,6 +16,7 @@ from PIL import Image  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 threads = int(sys.argv[2]) if len(sys.argv) > 2 else 16
+repeats = int(sys.argv[3]) if len(sys.argv) > 3 else 3
 dev = torch.device("cuda:0")
 rng = np.random.default_rng(0)
 datas = []
@@ -54,3 +56,43 @@ t0 = time.perf_counter()
 for _ in range(20):
     J.entropy_decode(datas[0])
 print(f"host half alone (one thread): {(time.perf_counter() - t0) / 20 * 1e3:.2f} ms per frame")
+
+
+def alternate(label, files, repeats):
+    """entropy="host" and entropy="device" decode_jpeg_batch, alternated, `repeats` times each (after one warm-up of each)."""
+    fns = (("host Huffman", lambda: J.decode_jpeg_batch(files, dev, threads=threads)),
+           ("device Huffman", lambda: J.decode_jpeg_batch(files, dev, threads=threads, entropy="device")))
+    for _, fn in fns:
+        fn()
+    torch.cuda.synchronize()
+    rates = {name: [] for name, _ in fns}
+    for _ in range(repeats):
+        for name, fn in fns:
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            rates[name].append(len(files) / (time.perf_counter() - t0))
+    for name, r in rates.items():
+        print(f"{label}, {name} + device reconstruction: {' '.join(f'{x:.0f}' for x in r)} frames/s (median {np.median(r):.0f})")
+
+
+alternate(f"{n} frames", datas, repeats)
+res = J.device_entropy_decode(datas, dev)
+torch.cuda.synchronize()
+t0 = time.perf_counter()
+for _ in range(5):
+    res = J.device_entropy_decode(datas, dev)
+torch.cuda.synchronize()
+dt = (time.perf_counter() - t0) / 5
+print(f"device Huffman stage alone ({n} frames, prepare + pack + copy + decode + status read-back): {dt * 1e3:.1f} ms = "
+      f"{n / dt:.0f} frames/s, {sum(r is None for r in res)} left to the host")
+crops = []
+for i in range(16):
+    h, w = 120 + 8 * i, 104 + 4 * i
+    img = np.clip(np.cumsum(np.cumsum(rng.normal(0, 2.5, (h, w, 3)), 0), 1) * 0.2 + rng.normal(128, 20, (h, w, 3)), 0, 255).astype(np.uint8)
+    b = io.BytesIO()
+    Image.fromarray(img).save(b, "JPEG", quality=90, subsampling=2)
+    crops.append(b.getvalue())
+crops = [crops[i % 16] for i in range(1024)]
+print(f"1024 crops {min(len(c) for c in crops) / 1024:.1f}-{max(len(c) for c in crops) / 1024:.1f} KiB")
+alternate("1024 crops", crops, repeats)

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfacepath.so")
 
 FP_OK = 0
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 # fp_op_kind
 OP_CONV, OP_DWCONV, OP_MAXPOOL, OP_UPSAMPLE2X, OP_COPY, OP_L2NORM, OP_BLAZEBLOCK, OP_DWPW, OP_YSTEM = 1, 2, 3, 4, 5, 6, 7, 8, 9
@@ -82,7 +82,16 @@ class FpJpegScan(C.Structure):
                 ("dc", FpJpegHuff * 3), ("ac", FpJpegHuff * 3)]
 
 
+class FpJpegEncItem(C.Structure):
+    """Mirror of struct fp_jpeg_enc_item (ABI 13)."""
+    _fields_ = [("src_off", C.c_int64), ("src_h", C.c_int32), ("src_w", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32),
+                ("x1", C.c_int32), ("y1", C.c_int32)]
+
+
 JPEG_DECODE_ON_HOST = 1          # fp_jpeg_entropy_decode_device status: decode this image with fp_jpeg_entropy_decode
+JPEG_444, JPEG_422, JPEG_420 = 0, 1, 2   # fp_jpeg_encode_* subsampling (Pillow's numbering)
+JPEG_ENC_BYTES_PER_BLOCK = 416   # worst-case scan bytes of one 8 x 8 block, stuffing included
+JPEG_ENC_HEADER_BYTES = 623      # what fp_jpeg_encode_headers writes
 
 _P = C.c_void_p
 _I = C.c_int
@@ -135,6 +144,10 @@ SIGNATURES = {
     "fp_jpeg_entropy_decode_device": (_I, [_P, C.POINTER(FpJpegScan), C.POINTER(_I64), _I, _P, C.POINTER(_I64), _P, _P, _SZ, _I,
                                            _I, _P]),
     "fp_jpeg_entropy_decode_emulate": (_I, [_P, _SZ, C.POINTER(FpJpegScan), _P, _I, _I, C.POINTER(C.c_int32)]),
+    "fp_jpeg_encode_workspace_bytes": (_I, [C.POINTER(FpJpegEncItem), _I, _I, C.POINTER(_SZ), C.POINTER(_SZ)]),
+    "fp_jpeg_encode_headers": (_I, [_I, _I, _I, _I, _P, _SZ]),
+    "fp_jpeg_encode_device": (_I, [_P, C.POINTER(FpJpegEncItem), _I, _I, _I, _I, _P, _SZ, _P, _SZ, _P, _P]),
+    "fp_jpeg_encode_emulate": (_I, [_P, C.POINTER(FpJpegEncItem), _I, _I, _I, _I, _P, _SZ, C.POINTER(_I64)]),
     "fp_tracker_step": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _F, _F, _P, _P, _P]),
 }
 

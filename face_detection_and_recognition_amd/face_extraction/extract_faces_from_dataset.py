@@ -4,6 +4,13 @@
   extract_face_feat_conf_area_list(pipe, frames)  :270-307  (here: a whole batch of frames per call, on device)
   save_extracted_faces(...)                       :311-363  (same annot dict, zero-padded feature vector, np.save)
 
+Face crops as JPEG files (:346-349, cv2.imwrite): extract_face_feat_conf_area_list(..., save_face=True) encodes every crop of the
+batch on the device in one call (modules/utils/jpeg.py encode_crops, byte-identical to cv2.imwrite's libjpeg-turbo output at
+quality 95) and keeps each frame's files in FrameFacesObj.face_jpegs; save_extracted_faces(..., save_face=True,
+faces_save_dir=...) writes them under the reference's file names.  The reference saves faces unless --noface is given; here
+save_face defaults to False, so a caller that does not ask for crops gets exactly the feature files as before.  The
+directory follows the reference's driver (:395-409): <target>/faces/<class_name> for images, .../<media_root> for videos.
+
 The reference walks a dataset one frame at a time through a Net wrapper; this module is the SURVEY 8(f) rank-1
 "next" row: the same composition driven by pipeline.FacePipeline, so detection, cropping and embedding of all frames
 of a media item are three device-resident stages.  Directory walking / video decoding stay with the caller."""
@@ -27,11 +34,14 @@ class FrameFacesObj:
     areas: List[float]
     boxes: np.ndarray
     feats: List[np.ndarray] = field(default_factory=list)
+    face_jpegs: List[bytes] = field(default_factory=list)   # save_face=True: each face's JPEG file (None: an empty crop)
 
 
-def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=None) -> List[FrameFacesObj]:
+def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=None, save_face=False,
+                                     quality=95) -> List[FrameFacesObj]:
     """frames: (B, H, W, 3) u8 BGR (numpy or CUDA tensor).  One FacePipeline step (no similarity filter needed);
-    returns per-frame records with boxes (orig pixels, rounded), confs, area fractions and embeddings."""
+    returns per-frame records with boxes (orig pixels, rounded), confs, area fractions and embeddings.  save_face: also
+    encode every face crop (the reference's image[y:yh, x:xw]) to a JPEG file of that quality, in one device call."""
     if isinstance(frames, np.ndarray):
         frames = torch.from_numpy(np.ascontiguousarray(frames))
     frames = frames.to(pipe.dev)
@@ -40,6 +50,10 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
     n = res["n_faces"]
     emb = res["emb"].cpu().numpy()
     info = res["info"].cpu().numpy()
+    jpegs = None
+    if save_face:
+        from ..modules.utils.jpeg import encode_crops
+        jpegs = encode_crops(frames.contiguous(), res["items"], n, quality=quality)
     out = [FrameFacesObj(frame_nums[i] if frame_nums is not None else i,
                          times_sec[i] if times_sec is not None else 0.0, [], [], np.zeros((0, 4), np.float32))
            for i in range(B)]
@@ -51,6 +65,8 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
         out[f].confs.append(float(conf))
         out[f].areas.append(float(area))     # BlazeFace: fraction (inference.py:40-46); YOLO: percent (onnx_utils.py:331)
         out[f].feats.append(emb[k])
+        if jpegs is not None:
+            out[f].face_jpegs.append(jpegs[k])
     for f in range(B):
         if boxes[f]:
             out[f].boxes = np.asarray(boxes[f], dtype=np.float32)
@@ -58,9 +74,17 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
 
 
 def save_extracted_faces(frames_faces_obj_list, media_root, class_name, feats_save_dir, face_feature_size,
-                         class2label_dict, save_feat=True):
-    """:311-363 without the cv2.imwrite branch: annot dict {media_id, frames_info, class_name, label, feature}
-    with the feature vector zero-padded to MAX_N_FRAME_FROM_VID * MAX_N_FACES_PER_FRAME * face_feature_size."""
+                         class2label_dict, save_feat=True, save_face=False, faces_save_dir=None):
+    """:311-363: annot dict {media_id, frames_info, class_name, label, feature} with the feature vector zero-padded to
+    MAX_N_FRAME_FROM_VID * MAX_N_FACES_PER_FRAME * face_feature_size.  save_face: also write each frame's face_jpegs
+    (extract_face_feat_conf_area_list(..., save_face=True)) into faces_save_dir as
+    frame_{frame_num}_sec_{time_sec}_conf_{round(conf, 3), '.' -> '_'}_area_{area}.jpg, the reference's names (a later
+    face with the same name overwrites an earlier one, as there).  An empty crop, which the reference cannot write, is
+    skipped."""
+    if save_face:
+        if faces_save_dir is None:
+            raise ValueError("save_face=True needs faces_save_dir")
+        os.makedirs(faces_save_dir, exist_ok=True)
     annot = {"media_id": media_root, "frames_info": []}
     feats_list, total = [], 0
     for fr in frames_faces_obj_list:
@@ -70,6 +94,15 @@ def save_extracted_faces(frames_faces_obj_list, media_root, class_name, feats_sa
             feats_list.extend(feats)
         annot["frames_info"].append({"frame_num": fr.frame_num, "time_sec": fr.time_sec, "confs": fr.confs,
                                      "areas": fr.areas})
+        if save_face:
+            if len(fr.face_jpegs) != len(fr.confs):
+                raise ValueError(f"frame {fr.frame_num}: no JPEG crops (extract with save_face=True)")
+            for data, conf, area in zip(fr.face_jpegs, fr.confs, fr.areas):
+                if data is None:
+                    continue
+                conf = str(round(conf, 3)).replace('.', '_')
+                with open(f"{faces_save_dir}/frame_{fr.frame_num}_sec_{fr.time_sec}_conf_{conf}_area_{area}.jpg", "wb") as f:
+                    f.write(data)
         total += len(fr.confs)
     os.makedirs(feats_save_dir, exist_ok=True)
     annot["class_name"] = class_name

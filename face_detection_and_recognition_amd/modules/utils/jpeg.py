@@ -12,6 +12,13 @@ fde/face_extraction/extract_faces_from_dataset.py:393-420).
                                               what the decoder does not take (CMYK / arithmetic-coded JPEGs, PNG, ...) is
                                               decoded by Pillow on the host -- file I/O, not the hot path -- and uploaded
 
+    encode_jpeg_batch(images, ...)            JPEG ENCODE (csrc/jpegenc.hip): a list of (h, w, 3) u8 device images -> list of JPEG
+                                              files (bytes), byte-identical to libjpeg-turbo's default compressor -- cv2.imwrite /
+                                              Pillow's save(quality=q, subsampling=s) -- in one device call per batch
+    encode_crops(frames, items, n, ...)       the same for the pipeline's crop records over its device frames, without cutting the
+                                              crops out first
+    imwrite(path, image, quality=95)          cv2.imwrite for one device image
+
 JpegUnsupported is raised by the first two for files outside csrc/jpeg.hip's scope (arithmetic-coded, lossless, 12-bit,
 CMYK, sampling layouts other than 4:4:4 / 4:2:2 / 4:2:0).  All 1048 JPEG files of the reference's tree are inside it."""
 import ctypes as C
@@ -240,3 +247,147 @@ def imread_batch(paths, device, bgr=True, threads=8, entropy="host"):
     if frames and all(f.shape == frames[0].shape for f in frames):
         return torch.stack(frames)
     return frames
+
+
+# ---- encode ----------------------------------------------------------------------------------------------------------
+
+_SUBSAMPLING = {"4:4:4": L.JPEG_444, "4:2:2": L.JPEG_422, "4:2:0": L.JPEG_420,
+                L.JPEG_444: L.JPEG_444, L.JPEG_422: L.JPEG_422, L.JPEG_420: L.JPEG_420}
+_headers = {}
+
+
+def _subsampling(s):
+    if s not in _SUBSAMPLING:
+        raise JpegUnsupported(f"subsampling {s!r}: the encoder takes '4:4:4', '4:2:2' or '4:2:0' (or Pillow's 0, 1, 2)")
+    return _SUBSAMPLING[s]
+
+
+def encode_headers(w, h, quality=95, subsampling="4:2:0"):
+    """The headers of a w x h file (SOI .. SOS, fp_jpeg_encode_headers): they depend on nothing else."""
+    key = (w, h, quality, _subsampling(subsampling))
+    hdr = _headers.get(key)
+    if hdr is None:
+        buf = (C.c_uint8 * L.JPEG_ENC_HEADER_BYTES)()
+        rc = L.load().fp_jpeg_encode_headers(w, h, quality, key[3], buf, len(buf))
+        if rc < 0:
+            L.check(rc, "fp_jpeg_encode_headers")
+        hdr = bytes(buf[:rc])
+        if len(_headers) < 4096:
+            _headers[key] = hdr
+    return hdr
+
+
+def _encode_items(src, items, quality, subsampling, bgr, emulate=False):
+    """fp_jpeg_enc_item list over the u8 buffer `src` (a device tensor; a host numpy array for emulate=True) -> files."""
+    lib = L.load()
+    sub = _subsampling(subsampling)
+    n = len(items)
+    if n == 0:
+        return []
+    if not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise L.FacepathError(f"quality {quality!r}: must be an int in 1 .. 100")
+    arr = (L.FpJpegEncItem * n)(*items)
+    ws_bytes, out_bytes = C.c_size_t(), C.c_size_t()
+    rc = lib.fp_jpeg_encode_workspace_bytes(arr, n, sub, C.byref(ws_bytes), C.byref(out_bytes))
+    if rc == FP_ERR_UNSUPPORTED:
+        raise JpegUnsupported("a crop the encoder does not take (a side over 65535, or too many blocks in the batch)")
+    L.check(rc, "fp_jpeg_encode_workspace_bytes")
+    if emulate:
+        out = np.empty((out_bytes.value,), np.uint8)
+        offs = (C.c_int64 * (n + 1))()
+        L.check(lib.fp_jpeg_encode_emulate(src.ctypes.data, arr, n, quality, sub, 1 if bgr else 0, out.ctypes.data,
+                                           out_bytes.value, offs), "fp_jpeg_encode_emulate")
+        offs = list(offs)
+        data = out[:offs[n]].tobytes()
+    else:
+        device = src.device
+        ws = torch.empty((ws_bytes.value,), dtype=torch.uint8, device=device)
+        out = torch.empty((out_bytes.value,), dtype=torch.uint8, device=device)
+        offs_dev = torch.empty((n + 1,), dtype=torch.int64, device=device)
+        L.check(lib.fp_jpeg_encode_device(L.ptr(src), arr, n, quality, sub, 1 if bgr else 0, L.ptr(ws), ws_bytes.value,
+                                          L.ptr(out), out_bytes.value, L.ptr(offs_dev), L.current_stream(device)),
+                "fp_jpeg_encode_device")
+        offs = offs_dev.cpu().tolist()                      # (synchronises)
+        data = out[:offs[n]].cpu().numpy().tobytes()        # one copy of the batch's compressed bytes
+    files = []
+    for i, it in enumerate(items):
+        w = min(it.x1, it.src_w) - max(it.x0, 0)
+        h = min(it.y1, it.src_h) - max(it.y0, 0)
+        files.append(encode_headers(w, h, quality, sub) + data[offs[i]:offs[i + 1]] + b"\xff\xd9")
+    return files
+
+
+def encode_jpeg_batch(images, quality=95, subsampling="4:2:0", bgr=True):
+    """List of (h, w, 3) u8 tensors on one HIP device (BGR, cv2's order, unless bgr=False) -> list of JPEG files (bytes), one
+    device call for the batch.  Each file equals cv2.imwrite's (libjpeg-turbo, quality 95, 4:2:0 by default) byte for byte."""
+    if not images:
+        return []
+    device = images[0].device
+    if device.type != "cuda":
+        raise L.FacepathError("encode_jpeg_batch encodes on a HIP device; there is no CPU path")
+    items, flat, off = [], [], 0
+    for im in images:
+        if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or im.device != device:
+            raise L.FacepathError("encode_jpeg_batch takes (h, w, 3) uint8 tensors on one device")
+        h, w = int(im.shape[0]), int(im.shape[1])
+        if h < 1 or w < 1:
+            raise L.FacepathError(f"encode_jpeg_batch: an empty image ({h} x {w})")
+        items.append(L.FpJpegEncItem(off, h, w, 0, 0, w, h))
+        flat.append(im.reshape(-1))
+        off += h * w * 3
+    src = torch.cat(flat) if len(flat) > 1 else flat[0].contiguous()
+    return _encode_items(src, items, quality, subsampling, bgr)
+
+
+def crop_items(frames, items, n):
+    """The pipeline's crop records (fp_resize_item rows from fp_dets_to_crops, items[:n]) over frames (B, H, W, 3) ->
+    fp_jpeg_enc_item list; None for a crop that is empty after the clamp (the reference's slice of it is empty)."""
+    B, H, W, _ = frames.shape
+    rows = items[:n].cpu().tolist() if n else []
+    out = []
+    for src_image, sx, sy, sw, sh, *_ in rows:
+        if not 0 <= src_image < B:
+            raise L.FacepathError(f"crop record of frame {src_image} outside the batch of {B}")
+        it = L.FpJpegEncItem(src_image * H * W * 3, H, W, sx, sy, sx + sw, sy + sh)
+        empty = min(it.x1, W) <= max(it.x0, 0) or min(it.y1, H) <= max(it.y0, 0)
+        out.append(None if empty else it)
+    return out
+
+
+def encode_crops(frames, items, n, quality=95, subsampling="4:2:0", bgr=True):
+    """The first n crop records of a FacePipeline step (res["items"]) over its device frames (B, H, W, 3) u8 -> one JPEG file
+    per face (bytes; None for a crop that is empty after the clamp), encoded straight from the frames in one device call."""
+    if frames.device.type != "cuda" or frames.dtype != torch.uint8 or frames.dim() != 4 or not frames.is_contiguous():
+        raise L.FacepathError("encode_crops takes contiguous (B, H, W, 3) uint8 frames on a HIP device")
+    recs = crop_items(frames, items, n)
+    take = [it for it in recs if it is not None]
+    files = iter(_encode_items(frames, take, quality, subsampling, bgr))
+    return [None if it is None else next(files) for it in recs]
+
+
+def imwrite(path, image, quality=95, bgr=True):
+    """cv2.imwrite(path, image) with cv2's default JPEG settings (quality 95, 4:2:0) for one (h, w, 3) u8 device image
+    (a numpy array is uploaded to the current HIP device).  Returns True, as cv2.imwrite does."""
+    if isinstance(image, np.ndarray):
+        image = torch.from_numpy(np.ascontiguousarray(image)).to(torch.device("cuda", torch.cuda.current_device()))
+    data = encode_jpeg_batch([image], quality=quality, bgr=bgr)[0]
+    with open(path, "wb") as f:
+        f.write(data)
+    return True
+
+
+def encode_jpeg_batch_emulate(images, quality=95, subsampling="4:2:0", bgr=True):
+    """encode_jpeg_batch on host numpy images through fp_jpeg_encode_emulate: the device's phases run serially on the CPU
+    (tests and debugging; the same bytes)."""
+    items, flat, off = [], [], 0
+    for im in images:
+        im = np.ascontiguousarray(im, dtype=np.uint8)
+        if im.ndim != 3 or im.shape[2] != 3:
+            raise L.FacepathError("encode_jpeg_batch_emulate takes (h, w, 3) uint8 arrays")
+        h, w = im.shape[:2]
+        items.append(L.FpJpegEncItem(off, h, w, 0, 0, w, h))
+        flat.append(im.reshape(-1))
+        off += im.size
+    if not items:
+        return []
+    return _encode_items(np.concatenate(flat), items, quality, subsampling, bgr, emulate=True)

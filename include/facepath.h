@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define FP_ABI_VERSION 12
+#define FP_ABI_VERSION 13
 
 typedef enum fp_status {
   FP_OK = 0,
@@ -293,7 +293,8 @@ typedef struct fp_op {
  *            [32] bias (scale = 1 where the BatchNorm is folded into the conv).
  * ABI history: 1 = round-1 ops; 2 = fp_ext / *_U8 ops (never shipped in a VERDICT-ed tree); 3 = fp_op.flags, row-padded
  * views; 4 = fp_op.Cmid / reserved0, FP_OP_DWBLOCK, FP_OP_BLAZEPAIR; 5 = FP_OPF_SPLIT3; 6 = FP_OP_BLAZECHAIN; 7 = FP_OPF_IN_UP2; 8 = FP_OP_BLAZEPAIR with stride 2; 9 = FP_OPF_OUT_DW, fp_debug_reload_env; 10 = FP_OP_SHUFDOWN, FP_OP_SHUFUNIT, FP_OP_YSTEM2; 11 = FP_OPF_SPLIT3 on FP_OP_STEM_U8;
- * 12 = device Huffman decoding of sequential JPEG scans (fp_jpeg_scan, fp_jpeg_scan_prepare, fp_jpeg_entropy_decode_device, section 7).
+ * 12 = device Huffman decoding of sequential JPEG scans (fp_jpeg_scan, fp_jpeg_scan_prepare, fp_jpeg_entropy_decode_device, section 7);
+ * 13 = baseline JPEG encoding of crop batches (fp_jpeg_enc_item, fp_jpeg_encode_device, section 8).
  */
 
 /* Validates every op against arena_floats / weight_floats, then launches them in order. */
@@ -650,6 +651,55 @@ int fp_jpeg_entropy_decode_device(const uint8_t* files, const fp_jpeg_scan* scan
  * the device would write them; rounds (may be NULL) = synchronisation passes until the proof (max_rounds + 1: none). */
 int fp_jpeg_entropy_decode_emulate(const uint8_t* data, size_t n, const fp_jpeg_scan* scan, int16_t* coefs, int sub_bits,
                                    int max_rounds, int32_t* rounds);
+
+/* ------------------------------------------------------------------------- */
+/* 8. JPEG encode (the face crops the reference's driver saves)                */
+/* ------------------------------------------------------------------------- */
+
+/*
+ * ABI 13.  Baseline (SOF0) encoding of a batch of 8-bit RGB / BGR crops, byte-identical to libjpeg-turbo's default compressor
+ * (jpeg_set_defaults + jpeg_set_quality(quality, TRUE): islow DCT, the Annex K tables scaled by quality, standard Huffman
+ * tables, no restart markers, no Huffman optimisation) -- what cv2.imwrite writes for the reference's face crops
+ * (fde/face_extraction/extract_faces_from_dataset.py:311-363) and Pillow's save(quality=q, subsampling=s).  csrc/jpegenc.hip.
+ * A file = fp_jpeg_encode_headers (host: SOI, JFIF APP0, 2 x DQT, SOF0, 4 x DHT, SOS) + the image's scan data
+ * + EOI (FF D9).  Subsampling 4:4:4, 4:2:2, 4:2:0 (the default of both); quality 1 .. 100; crops of 1 .. 65535 pixels a side.
+ *
+ * Item i encodes src[src_off + y * src_w * 3 + x * 3 ...] (3 bytes per pixel, packed rows) over the rectangle clamped the
+ * way the reference slices it, image[max(y0, 0):min(y1, src_h), max(x0, 0):min(x1, src_w)].  An empty rectangle after the
+ * clamp: FP_ERR_INVALID_ARG; subsampling outside 0 .. 2, a side over 65535 or more than 2^31 - 1 blocks: FP_ERR_UNSUPPORTED.
+ *
+ * Sizing: one 8 x 8 block codes to at most 22 (DC) + 63 x 26 (AC) = 1660 bits, 208 bytes; byte stuffing at most doubles
+ * that.  So n_blocks x FP_JPEG_ENC_BYTES_PER_BLOCK bytes hold the scan data of any batch, whatever the pixels; the call needs
+ * no host sync to size its output.
+ */
+#define FP_JPEG_444 0
+#define FP_JPEG_422 1
+#define FP_JPEG_420 2
+#define FP_JPEG_ENC_BYTES_PER_BLOCK 416
+#define FP_JPEG_ENC_HEADER_BYTES 623   /* what fp_jpeg_encode_headers writes, for every size, quality and subsampling */
+
+typedef struct fp_jpeg_enc_item {
+  int64_t src_off;          /* byte offset of the source image's pixel (0, 0) in src */
+  int32_t src_h, src_w;     /* the source image's size (pixels) */
+  int32_t x0, y0, x1, y1;   /* the crop, [y0, y1) x [x0, x1), clamped to the source image */
+} fp_jpeg_enc_item;
+
+/* HOST.  Checks the batch (items: HOST) and sizes it: *ws_bytes of device workspace, *out_bytes of output
+ * (= n_blocks * FP_JPEG_ENC_BYTES_PER_BLOCK).  FP_OK or the refusal's status. */
+int fp_jpeg_encode_workspace_bytes(const fp_jpeg_enc_item* items, int n, int subsampling, size_t* ws_bytes, size_t* out_bytes);
+/* HOST.  The headers of a width x height file (FP_JPEG_ENC_HEADER_BYTES bytes into out): returns that count or a status < 0. */
+int fp_jpeg_encode_headers(int width, int height, int quality, int subsampling, uint8_t* out, size_t cap);
+/*
+ * DEVICE.  src: device u8; items: HOST array of n; workspace: device, 16-byte aligned, fp_jpeg_encode_workspace_bytes; out: device,
+ * >= out_bytes.  Writes the scan data (stuffed, last byte padded with 1-bits) of image i at out + out_off[i], images back to back,
+ * out_off[n] = the total (out_off: device int64 [n + 1]).  bgr = 1: the pixels are B, G, R (cv2's order).  Copies the
+ * descriptors into the workspace before it returns.
+ */
+int fp_jpeg_encode_device(const uint8_t* src, const fp_jpeg_enc_item* items, int n, int quality, int subsampling, int bgr,
+                          void* workspace, size_t ws_bytes, uint8_t* out, size_t out_cap, int64_t* out_off, void* stream);
+/* HOST.  The device's phases run serially on host memory (src, out, out_off: HOST); the same bytes. */
+int fp_jpeg_encode_emulate(const uint8_t* src, const fp_jpeg_enc_item* items, int n, int quality, int subsampling, int bgr,
+                           uint8_t* out, size_t out_cap, int64_t* out_off);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfacepath.so")
 
 FP_OK = 0
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 # fp_op_kind
 OP_CONV, OP_DWCONV, OP_MAXPOOL, OP_UPSAMPLE2X, OP_COPY, OP_L2NORM, OP_BLAZEBLOCK, OP_DWPW, OP_YSTEM = 1, 2, 3, 4, 5, 6, 7, 8, 9
@@ -57,6 +57,15 @@ class FpResizeItem(C.Structure):
     """Mirror of struct fp_resize_item."""
     _fields_ = [("src_image", C.c_int32), ("sx", C.c_int32), ("sy", C.c_int32), ("sw", C.c_int32), ("sh", C.c_int32),
                 ("dx", C.c_int32), ("dy", C.c_int32), ("dw", C.c_int32), ("dh", C.c_int32)]
+
+
+class FpFrameDesc(C.Structure):
+    """Mirror of struct fp_frame_desc (ABI 14): one frame of a ragged batch (byte offset of pixel (0, 0), size)."""
+    _fields_ = [("off", C.c_int64), ("h", C.c_int32), ("w", C.c_int32)]
+
+
+FRAME_MIN_W, FRAME_MAX_W, FRAME_MAX_H = 3, 32767, 65535   # fp_frame_desc sizes the ragged kernels take
+RAGGED_U8, RAGGED_F32_LUT = 0, 1                           # fp_resize_ragged output modes
 
 
 class FpJpegInfo(C.Structure):
@@ -120,6 +129,9 @@ SIGNATURES = {
     "fp_letterbox_tables": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "fp_dets_to_crops": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I,
                                 _P, _P, _P, _P]),
+    "fp_resize_ragged": (_I, [_P, _SZ, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
+    "fp_dets_to_crops_ragged": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P,
+                                       _P]),
     "fp_blaze_decode": (_I, [_P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P]),
     "fp_blaze_weighted_nms": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P]),
     "fp_yolo_decode": (_I, [_P, _I, _I, _I, _I, _F, C.POINTER(_F), _P, _I64, _I64, _P]),

@@ -98,28 +98,9 @@ __global__ __launch_bounds__(256) void resize_normalize_rows_kernel(ResizeRowsAr
   it.sh = min(max(it.sh, 1), p.fh - it.sy);
   const bool item_ok = it.dw > 0 && it.dh > 0 && it.src_image >= 0 && it.src_image < p.n_frames;
   lut[tid] = p.lut[tid];
-  for (int i = tid; i < p.cw + q.rpb; i += 256) {
-    fp_lb_tap t = {0, 0};
-    if (i < p.cw) {
-      if (item_ok && i >= it.dx && i < it.dx + it.dw) {
-        int s0, s1, a0, a1;
-        fp_lb_coef(i - it.dx, (double)it.sw / (double)it.dw, it.sw, s0, s1, a0, a1);
-        const int off0 = (it.sx + s0) * 3, off1 = (it.sx + s1) * 3;
-        const int base = min(off0, p.fw * 3 - 8);              // the 8-byte window never leaves the frame row
-        t.a = base;
-        t.b = (off0 - base) | ((off1 - base) << 3) | (a0 << 6) | (a1 << 18) | FP_LB_VALID;
-      }
-    } else {
-      const int y = y0 + (i - p.cw);
-      if (item_ok && y >= it.dy && y < it.dy + it.dh) {
-        int s0, s1, b0, b1;
-        fp_lb_coef(y - it.dy, (double)it.sh / (double)it.dh, it.sh, s0, s1, b0, b1);
-        t.a = (it.sy + s0) | ((it.sy + s1) << 16);
-        t.b = b0 | (b1 << 12) | FP_LB_VALID;
-      }
-    }
-    tabs[i] = t;
-  }
+  for (int i = tid; i < p.cw + q.rpb; i += 256)
+    tabs[i] = i < p.cw ? fp_lb_xtap(i, it.sx, it.sw, it.dx, item_ok ? it.dw : 0, p.fw)
+                       : fp_lb_ytap(y0 + (i - p.cw), it.sy, it.sh, it.dy, item_ok ? it.dh : 0);
   __syncthreads();
   const uint8_t* frame = p.frames + (long)(item_ok ? it.src_image : 0) * p.fh * p.fw * 3;
   const long row_bytes = (long)p.fw * 3;
@@ -181,6 +162,148 @@ extern "C" int fp_resize_normalize(const uint8_t* frames, int n_frames, int fram
 }
 
 // ---------------------------------------------------------------------------------------------
+// Ragged batches (ABI 14): fp_resize_normalize over frames of different sizes packed back to back in one buffer, each
+// item's src_image selecting an fp_frame_desc (byte offset, h, w) instead of frames + i * H * W * 3.  Same workgroup
+// shape as resize_normalize_rows_kernel -- one workgroup per (item, band of canvas rows), taps built in LDS by the same
+// fp_lb_xtap / fp_lb_ytap -- so the work of an item depends on its canvas, not on its frame.  Two outputs:
+//   U8 = false: fp32 NHWC (4 channels) through the LUT, optional R/B swap -- bit for bit fp_resize_normalize;
+//   U8 = true : u8 NHWC (3 channels, frame order, no LUT): the canvas the detectors' u8 plans read as a frame.
+namespace {
+
+struct RaggedArgs {
+  const uint8_t* frames;
+  const fp_frame_desc* descs;
+  const fp_resize_item* items;
+  void* canvas;
+  const float* lut;
+  uint64_t frames_bytes;
+  int n_frames, ch, cw, pad_value, swap_rb, rpb, bpi;
+  fp_divisor cw_div;
+};
+
+struct __attribute__((aligned(4))) u32x3 {
+  unsigned x, y, z;
+};
+
+template <bool U8>
+__global__ __launch_bounds__(256) void resize_ragged_kernel(RaggedArgs p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  float* lut = (float*)smem_raw;                                     // [256] (fp32 output only)
+  fp_lb_tap* tabs = (fp_lb_tap*)(smem_raw + (U8 ? 0 : 1024));        // [cw] column taps, [rpb] row taps
+  const int tid = threadIdx.x;
+  const int item = blockIdx.x / p.bpi, y0 = (blockIdx.x - item * p.bpi) * p.rpb;
+  fp_resize_item it = p.items[item];
+  // descriptors live in device memory: a frame outside the limits or the buffer makes its items pad colour (no load
+  // outside the buffer); the limits are the ones the tap fields and the 8-byte windows need (letterbox.h)
+  fp_frame_desc d = {0, 1, 3};
+  bool item_ok = it.src_image >= 0 && it.src_image < p.n_frames;
+  if (item_ok) {
+    d = p.descs[it.src_image];
+    item_ok = d.off >= 0 && d.h >= 1 && d.h <= FP_FRAME_MAX_H && d.w >= FP_FRAME_MIN_W && d.w <= FP_FRAME_MAX_W &&
+              (uint64_t)d.off + (uint64_t)d.h * (uint64_t)d.w * 3u <= p.frames_bytes;
+    if (!item_ok) d = fp_frame_desc{0, 1, 3};
+  }
+  it.sx = min(max(it.sx, 0), d.w - 1);
+  it.sy = min(max(it.sy, 0), d.h - 1);
+  it.sw = min(max(it.sw, 1), d.w - it.sx);
+  it.sh = min(max(it.sh, 1), d.h - it.sy);
+  item_ok = item_ok && it.dw > 0 && it.dh > 0;
+  if (!U8) lut[tid] = p.lut[tid];
+  for (int i = tid; i < p.cw + p.rpb; i += 256)
+    tabs[i] = i < p.cw ? fp_lb_xtap(i, it.sx, it.sw, it.dx, item_ok ? it.dw : 0, d.w)
+                       : fp_lb_ytap(y0 + (i - p.cw), it.sy, it.sh, it.dy, item_ok ? it.dh : 0);
+  __syncthreads();
+  const uint8_t* frame = p.frames + (item_ok ? d.off : 0);            // pad pixels load (and ignore) its first 8 bytes
+  const long row_bytes = (long)d.w * 3;
+  const int rows = min(p.rpb, p.ch - y0);
+  const int npx = rows * p.cw;
+  const long px0 = ((long)item * p.ch + y0) * p.cw;                   // first canvas pixel of the band
+  if (!U8) {
+    float* out = (float*)p.canvas + px0 * 4;
+    // four pixels per thread and pass: the eight window loads are issued before the first pixel is finished
+    for (int i0 = tid; i0 < npx; i0 += 4 * 256) {
+      fp_lb_raw raw[4];
+      fp_lb_tap xt[4], yt[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = min(i0 + 256 * k, npx - 1);
+        const int r = (int)fp_fastdiv((unsigned)i, p.cw_div), x = i - r * p.cw;
+        xt[k] = tabs[x];
+        yt[k] = tabs[p.cw + r];
+        raw[k] = fp_lb_issue(frame, row_bytes, xt[k], yt[k]);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = i0 + 256 * k;
+        if (i < npx) *(f32x4*)(out + (long)i * 4) = fp_lb_finish(raw[k], xt[k], yt[k], lut, p.pad_value, p.swap_rb);
+      }
+    }
+  } else {
+    // four consecutive pixels per thread and pass = 12 bytes = three whole dwords when the band starts dword-aligned
+    uint8_t* out = (uint8_t*)p.canvas + px0 * 3;
+    const bool aligned = ((uintptr_t)out & 3) == 0;
+    for (int g = tid; 4 * g < npx; g += 256) {
+      fp_lb_raw raw[4];
+      fp_lb_tap xt[4], yt[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = min(4 * g + k, npx - 1);
+        const int r = (int)fp_fastdiv((unsigned)i, p.cw_div), x = i - r * p.cw;
+        xt[k] = tabs[x];
+        yt[k] = tabs[p.cw + r];
+        raw[k] = fp_lb_issue(frame, row_bytes, xt[k], yt[k]);
+      }
+      int v[4][3];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) fp_lb_rgb(raw[k], xt[k], yt[k], p.pad_value, v[k]);
+      if (aligned && 4 * g + 4 <= npx) {
+        u32x3 w;
+        w.x = (unsigned)v[0][0] | (unsigned)v[0][1] << 8 | (unsigned)v[0][2] << 16 | (unsigned)v[1][0] << 24;
+        w.y = (unsigned)v[1][1] | (unsigned)v[1][2] << 8 | (unsigned)v[2][0] << 16 | (unsigned)v[2][1] << 24;
+        w.z = (unsigned)v[2][2] | (unsigned)v[3][0] << 8 | (unsigned)v[3][1] << 16 | (unsigned)v[3][2] << 24;
+        *(u32x3*)(out + 12L * g) = w;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (4 * g + k < npx)
+            for (int c = 0; c < 3; ++c) out[12L * g + 3 * k + c] = (uint8_t)v[k][c];
+      }
+    }
+  }
+}
+
+}  // namespace
+
+// Arguments checked by fp_resize_ragged (capi.cpp).
+int fp_launch_resize_ragged(const uint8_t* frames, size_t frames_bytes, const fp_frame_desc* descs, int n_frames,
+                            const fp_resize_item* items, int n_items, void* canvas, int canvas_h, int canvas_w, int mode,
+                            const float* lut256, int pad_value, int swap_rb, hipStream_t s) {
+  RaggedArgs a;
+  a.frames = frames;
+  a.descs = descs;
+  a.items = items;
+  a.canvas = canvas;
+  a.lut = lut256;
+  a.frames_bytes = frames_bytes;
+  a.n_frames = n_frames;
+  a.ch = canvas_h;
+  a.cw = canvas_w;
+  a.pad_value = pad_value;
+  a.swap_rb = swap_rb;
+  a.rpb = (int)min((long)canvas_h, max(1L, 8192L / canvas_w));       // ~8 k pixels per workgroup
+  a.bpi = (int)fp_ceil_div(canvas_h, a.rpb);
+  a.cw_div = fp_make_divisor((unsigned)canvas_w);
+  if ((long)n_items * a.bpi >= (1L << 31)) return FP_ERR_UNSUPPORTED;
+  const bool u8 = mode == FP_RAGGED_U8;
+  const size_t lds = (u8 ? 0 : 1024) + (size_t)(canvas_w + a.rpb) * sizeof(fp_lb_tap);
+  const dim3 grid((unsigned)((long)n_items * a.bpi));
+  if (u8) hipLaunchKernelGGL(resize_ragged_kernel<true>, grid, dim3(256), lds, s, a);
+  else hipLaunchKernelGGL(resize_ragged_kernel<false>, grid, dim3(256), lds, s, a);
+  FP_CHECK_LAUNCH();
+  return FP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Tap tables of ONE resize geometry (letterbox.h) for the stems that read u8 frames directly.
 namespace {
 
@@ -193,26 +316,9 @@ struct LbTableArgs {
 __global__ __launch_bounds__(256) void letterbox_tables_kernel(LbTableArgs p) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < p.cw) {
-    fp_lb_tap t = {0, 0};
-    if (p.dw > 0 && i >= p.dx && i < p.dx + p.dw) {
-      int s0, s1, a0, a1;
-      fp_lb_coef(i - p.dx, (double)p.sw / (double)p.dw, p.sw, s0, s1, a0, a1);
-      const int off0 = (p.sx + s0) * 3, off1 = (p.sx + s1) * 3;
-      const int base = min(off0, p.fw * 3 - 8);        // the 8-byte window never leaves the frame row
-      t.a = base;
-      t.b = (off0 - base) | ((off1 - base) << 3) | (a0 << 6) | (a1 << 18) | FP_LB_VALID;
-    }
-    p.xtab[i] = t;
+    p.xtab[i] = fp_lb_xtap(i, p.sx, p.sw, p.dx, p.dw, p.fw);
   } else if (i < p.cw + p.ch) {
-    const int y = i - p.cw;
-    fp_lb_tap t = {0, 0};
-    if (p.dh > 0 && y >= p.dy && y < p.dy + p.dh) {
-      int s0, s1, b0, b1;
-      fp_lb_coef(y - p.dy, (double)p.sh / (double)p.dh, p.sh, s0, s1, b0, b1);
-      t.a = (p.sy + s0) | ((p.sy + s1) << 16);
-      t.b = b0 | (b1 << 12) | FP_LB_VALID;
-    }
-    p.ytab[y] = t;
+    p.ytab[i - p.cw] = fp_lb_ytap(i - p.cw, p.sy, p.sh, p.dy, p.dh);
   } else if (i == p.cw + p.ch) {
     const fp_lb_tap t = {p.pad_value, p.swap_rb};     // trailer: pad colour (u8 value), swap R/B
     p.xtab[i] = t;

@@ -76,11 +76,9 @@ __device__ __forceinline__ fp_lb_raw fp_lb_issue(const uint8_t* frame, long row_
   return r;
 }
 
-// raw windows -> normalised RGB(+0) pixel.  lut: 256 floats (LDS or global); pad: the pad colour as a u8 value.
+// raw windows -> the pixel's three u8 channels in frame order (pad: every channel = pad).
 // All products fit 24-bit operands (weights <= 2048, taps <= 255, row sums <= 522240 >> 4), hence the mul24 forms.
-__device__ __forceinline__ f32x4 fp_lb_finish(const fp_lb_raw& r, const fp_lb_tap& xt, const fp_lb_tap& yt,
-                                              const float* lut, int pad, int swap_rb) {
-  int v[3];
+__device__ __forceinline__ void fp_lb_rgb(const fp_lb_raw& r, const fp_lb_tap& xt, const fp_lb_tap& yt, int pad, int v[3]) {
   if ((xt.b & FP_LB_VALID) && (yt.b & FP_LB_VALID)) {
     const unsigned sh0 = xt.b & 7u, sh1 = ((unsigned)xt.b >> 3) & 7u;
     const unsigned a0 = ((unsigned)xt.b >> 6) & 0xfffu, a1 = ((unsigned)xt.b >> 18) & 0xfffu;
@@ -99,10 +97,44 @@ __device__ __forceinline__ f32x4 fp_lb_finish(const fp_lb_raw& r, const fp_lb_ta
   } else {
     v[0] = v[1] = v[2] = pad;
   }
+}
+
+// raw windows -> normalised RGB(+0) pixel.  lut: 256 floats (LDS or global); pad: the pad colour as a u8 value.
+__device__ __forceinline__ f32x4 fp_lb_finish(const fp_lb_raw& r, const fp_lb_tap& xt, const fp_lb_tap& yt,
+                                              const float* lut, int pad, int swap_rb) {
+  int v[3];
+  fp_lb_rgb(r, xt, yt, pad, v);
   f32x4 o;
   o[0] = lut[swap_rb ? v[2] : v[0]];
   o[1] = lut[v[1]];
   o[2] = lut[swap_rb ? v[0] : v[2]];
   o[3] = 0.f;
   return o;
+}
+
+// Table entries (the format above) of one resize geometry: source rectangle (sx, sy, sw, sh) of a frame fw pixels wide
+// -> destination rectangle (dx, dy, dw, dh).  Canvas column i / row y outside the destination: { 0, 0 } (not valid).
+// Shared by fp_letterbox_tables, fp_resize_normalize's tabled kernel and the ragged resize (image.hip).
+__device__ __forceinline__ fp_lb_tap fp_lb_xtap(int i, int sx, int sw, int dx, int dw, int fw) {
+  fp_lb_tap t = {0, 0};
+  if (dw > 0 && i >= dx && i < dx + dw) {
+    int s0, s1, a0, a1;
+    fp_lb_coef(i - dx, (double)sw / (double)dw, sw, s0, s1, a0, a1);
+    const int off0 = (sx + s0) * 3, off1 = (sx + s1) * 3;
+    const int base = min(off0, fw * 3 - 8);        // the 8-byte window never leaves the frame row
+    t.a = base;
+    t.b = (off0 - base) | ((off1 - base) << 3) | (a0 << 6) | (a1 << 18) | FP_LB_VALID;
+  }
+  return t;
+}
+
+__device__ __forceinline__ fp_lb_tap fp_lb_ytap(int y, int sy, int sh, int dy, int dh) {
+  fp_lb_tap t = {0, 0};
+  if (dh > 0 && y >= dy && y < dy + dh) {
+    int s0, s1, b0, b1;
+    fp_lb_coef(y - dy, (double)sh / (double)dh, sh, s0, s1, b0, b1);
+    t.a = (sy + s0) | ((sy + s1) << 16);
+    t.b = b0 | (b1 << 12) | FP_LB_VALID;
+  }
+  return t;
 }

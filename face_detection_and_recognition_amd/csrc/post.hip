@@ -407,10 +407,24 @@ struct CropArgs {
   fp_resize_item* items;
   float* info;
   int* n_faces;
+  const fp_frame_desc* descs;   // ragged batch (ABI 14): per-frame orig_w / orig_h (descs) and gain, pad_x, pad_y (geom [B][3]);
+  const float* geom;            // nullptr: the scalars above hold for every frame
 };
 
-__device__ __forceinline__ bool crop_one(const CropArgs& p, const float* d, float& x1, float& y1, float& x2,
-                                         float& y2, float& conf, float& perc) {
+// The scale_coords / clamp geometry of one frame.
+struct FrameGeom {
+  int orig_w, orig_h;
+  float gain, pad_x, pad_y;
+};
+
+__device__ __forceinline__ FrameGeom frame_geom(const CropArgs& p, int f) {
+  if (!p.descs) return FrameGeom{p.orig_w, p.orig_h, p.gain, p.pad_x, p.pad_y};
+  const fp_frame_desc d = p.descs[f];
+  return FrameGeom{d.w, d.h, p.geom[3 * f], p.geom[3 * f + 1], p.geom[3 * f + 2]};
+}
+
+__device__ __forceinline__ bool crop_one(const CropArgs& p, const FrameGeom& g, const float* d, float& x1, float& y1,
+                                         float& x2, float& y2, float& conf, float& perc) {
   if (p.fmt == 0) {
     conf = d[16];
     if (!(conf > p.det_thres)) return false;
@@ -428,10 +442,10 @@ __device__ __forceinline__ bool crop_one(const CropArgs& p, const float* d, floa
     perc = (100.f * area) / (float)(p.in_w * p.in_h);
     if (!(perc > p.area_thres)) return false;
   }
-  x1 = (x1 - p.pad_x) / p.gain; x2 = (x2 - p.pad_x) / p.gain;
-  y1 = (y1 - p.pad_y) / p.gain; y2 = (y2 - p.pad_y) / p.gain;
-  x1 = fminf(fmaxf(x1, 0.f), (float)p.orig_w); x2 = fminf(fmaxf(x2, 0.f), (float)p.orig_w);
-  y1 = fminf(fmaxf(y1, 0.f), (float)p.orig_h); y2 = fminf(fmaxf(y2, 0.f), (float)p.orig_h);
+  x1 = (x1 - g.pad_x) / g.gain; x2 = (x2 - g.pad_x) / g.gain;
+  y1 = (y1 - g.pad_y) / g.gain; y2 = (y2 - g.pad_y) / g.gain;
+  x1 = fminf(fmaxf(x1, 0.f), (float)g.orig_w); x2 = fminf(fmaxf(x2, 0.f), (float)g.orig_w);
+  y1 = fminf(fmaxf(y1, 0.f), (float)g.orig_h); y2 = fminf(fmaxf(y2, 0.f), (float)g.orig_h);
   x1 = rintf(x1); y1 = rintf(y1); x2 = rintf(x2); y2 = rintf(y2);
   return true;
 }
@@ -446,12 +460,15 @@ __global__ __launch_bounds__(256) void dets_to_crops_kernel(CropArgs p) {
     const int f = f0 + tid;
     int n = 0, cnt = 0;
     const float* D = nullptr;
+    FrameGeom g{1, 1, 1.f, 0.f, 0.f};
     if (f < p.B) {
+      g = frame_geom(p, f);
       n = min(max(p.counts[f], 0), p.max_dets);
+      if (g.orig_w <= 0 || g.orig_h <= 0 || !(g.gain > 0.f)) n = 0;   // a ragged frame with no usable geometry: no faces
       D = p.dets + (long)f * p.max_dets * p.row;
       for (int i = 0; i < n; ++i) {
         float x1, y1, x2, y2, c, pc;
-        if (crop_one(p, D + (long)i * p.row, x1, y1, x2, y2, c, pc)) ++cnt;
+        if (crop_one(p, g, D + (long)i * p.row, x1, y1, x2, y2, c, pc)) ++cnt;
       }
     }
     scan[tid] = cnt;
@@ -465,10 +482,10 @@ __global__ __launch_bounds__(256) void dets_to_crops_kernel(CropArgs p) {
     int slot = base_s + scan[tid] - cnt;
     for (int i = 0; i < n; ++i) {
       float x1, y1, x2, y2, c, pc;
-      if (!crop_one(p, D + (long)i * p.row, x1, y1, x2, y2, c, pc)) continue;
+      if (!crop_one(p, g, D + (long)i * p.row, x1, y1, x2, y2, c, pc)) continue;
       if (slot < p.max_faces) {
         int x = (int)x1 + p.tx, y = (int)y1 + p.ty, xw = (int)x2 + p.bx, yh = (int)y2 + p.by;
-        x = max(x, 0); y = max(y, 0); xw = min(xw, p.orig_w); yh = min(yh, p.orig_h);
+        x = max(x, 0); y = max(y, 0); xw = min(xw, g.orig_w); yh = min(yh, g.orig_h);
         fp_resize_item it;
         it.src_image = f;
         it.sx = x; it.sy = y; it.sw = xw - x; it.sh = yh - y;
@@ -572,10 +589,24 @@ int fp_dets_to_crops(const float* dets, const int32_t* counts, int B, int max_de
     return FP_ERR_INVALID_ARG;
   if ((fmt == 0 && row_floats < 17) || (fmt == 1 && row_floats < 5) || fmt < 0 || fmt > 1) return FP_ERR_INVALID_ARG;
   CropArgs a{dets, counts, B, max_dets, row_floats, fmt, in_w, in_h, orig_w, orig_h, det_thres, area_thres, gain,
-             pad_x, pad_y, off_tx, off_ty, off_bx, off_by, dst_w, dst_h, max_faces, items, face_info, n_faces};
+             pad_x, pad_y, off_tx, off_ty, off_bx, off_by, dst_w, dst_h, max_faces, items, face_info, n_faces,
+             nullptr, nullptr};
   hipLaunchKernelGGL(dets_to_crops_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
   FP_CHECK_LAUNCH();
   return FP_OK;
 }
 
 }  // extern "C"
+
+// Arguments checked by fp_dets_to_crops_ragged (capi.cpp).
+int fp_launch_dets_to_crops_ragged(const float* dets, const int32_t* counts, int B, int max_dets, int row_floats, int fmt,
+                                   int in_w, int in_h, const fp_frame_desc* descs, const float* geom, float det_thres,
+                                   float area_thres, int off_tx, int off_ty, int off_bx, int off_by, int dst_w, int dst_h,
+                                   int max_faces, fp_resize_item* items, float* face_info, int32_t* n_faces, hipStream_t s) {
+  CropArgs a{dets, counts, B, max_dets, row_floats, fmt, in_w, in_h, 0, 0, det_thres, area_thres, 0.f,
+             0.f, 0.f, off_tx, off_ty, off_bx, off_by, dst_w, dst_h, max_faces, items, face_info, n_faces,
+             descs, geom};
+  hipLaunchKernelGGL(dets_to_crops_kernel, dim3(1), dim3(256), 0, s, a);
+  FP_CHECK_LAUNCH();
+  return FP_OK;
+}

@@ -2,6 +2,7 @@
 (face_detection_and_extraction/face_extraction/extract_faces_from_dataset.py:270-365).
 
   extract_face_feat_conf_area_list(pipe, frames)  :270-307  (here: a whole batch of frames per call, on device)
+  extract_faces_from_images(pipe, paths)          :400-407  (image media items of any size, batch by batch)
   save_extracted_faces(...)                       :311-363  (same annot dict, zero-padded feature vector, np.save)
 
 Face crops as JPEG files (:346-349, cv2.imwrite): extract_face_feat_conf_area_list(..., save_face=True) encodes every crop of the
@@ -21,6 +22,8 @@ from typing import List
 import numpy as np
 import torch
 
+from ..frames import RaggedFrames
+
 MAX_N_FACES_PER_FRAME = 3      # extract_faces_from_dataset.py:38
 MAX_N_FRAME_FROM_VID = 15      # :40
 
@@ -39,13 +42,24 @@ class FrameFacesObj:
 
 def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=None, save_face=False,
                                      quality=95) -> List[FrameFacesObj]:
-    """frames: (B, H, W, 3) u8 BGR (numpy or CUDA tensor).  One FacePipeline step (no similarity filter needed);
-    returns per-frame records with boxes (orig pixels, rounded), confs, area fractions and embeddings.  save_face: also
-    encode every face crop (the reference's image[y:yh, x:xw]) to a JPEG file of that quality, in one device call."""
+    """frames: (B, H, W, 3) u8 BGR (numpy or CUDA tensor), a RaggedFrames, or a list of (h, w, 3) frames.  One FacePipeline
+    step (no similarity filter needed); returns per-frame records with boxes (each frame's own pixels, rounded), confs,
+    area fractions and embeddings.  A list whose frames share one size is stacked and takes the uniform path; otherwise it
+    is packed into a RaggedFrames.  save_face: also encode every face crop (the reference's image[y:yh, x:xw]) to a JPEG
+    file of that quality, in one device call."""
+    if isinstance(frames, (list, tuple)):
+        if not frames:
+            return []
+        if all(tuple(f.shape) == tuple(frames[0].shape) for f in frames):
+            frames = torch.stack([(torch.from_numpy(np.ascontiguousarray(f)) if isinstance(f, np.ndarray) else f).to(pipe.dev)
+                                  for f in frames])
+        else:
+            frames = RaggedFrames.from_list(frames, pipe.dev)
     if isinstance(frames, np.ndarray):
         frames = torch.from_numpy(np.ascontiguousarray(frames))
-    frames = frames.to(pipe.dev)
-    B, H, W, _ = frames.shape
+    if not isinstance(frames, RaggedFrames):
+        frames = frames.to(pipe.dev).contiguous()
+    B = len(frames)
     res = pipe.step(frames)                   # detect -> crops -> embed (+ the exact re-run on a detector overflow)
     n = res["n_faces"]
     emb = res["emb"].cpu().numpy()
@@ -53,7 +67,7 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
     jpegs = None
     if save_face:
         from ..modules.utils.jpeg import encode_crops
-        jpegs = encode_crops(frames.contiguous(), res["items"], n, quality=quality)
+        jpegs = encode_crops(frames, res["items"], n, quality=quality)
     out = [FrameFacesObj(frame_nums[i] if frame_nums is not None else i,
                          times_sec[i] if times_sec is not None else 0.0, [], [], np.zeros((0, 4), np.float32))
            for i in range(B)]
@@ -70,6 +84,23 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
     for f in range(B):
         if boxes[f]:
             out[f].boxes = np.asarray(boxes[f], dtype=np.float32)
+    return out
+
+
+def extract_faces_from_images(pipe, paths, batch_size=256, entropy="host", save_face=False, quality=95) -> List[FrameFacesObj]:
+    """The reference's image media items (:400-407: one photo per item, any size, recorded as FrameFacesObj(1, 1, ...)) for a
+    whole list of files: decode batch_size files at a time (modules/utils/jpeg.py imread_batch; entropy as there), then one
+    pipeline step per batch -- frames of different sizes as one RaggedFrames.  Returns one record per path, in order; pass
+    each to save_extracted_faces under its file's media_root."""
+    from ..modules.utils.jpeg import imread_batch
+    out = []
+    for i in range(0, len(paths), int(batch_size)):
+        chunk = paths[i:i + int(batch_size)]
+        frames = imread_batch(chunk, pipe.dev, entropy=entropy)     # (B, H, W, 3) when the sizes agree, else a list
+        recs = extract_face_feat_conf_area_list(pipe, frames, save_face=save_face, quality=quality)
+        for r in recs:
+            r.frame_num, r.time_sec = 1, 1
+        out.extend(recs)
     return out
 
 

@@ -7,7 +7,8 @@ import torch
 
 from ... import _lib as L
 from ..models.base import Model
-from ..utils.image import bind_letterbox, letterbox_batch
+from ...frames import RaggedFrames
+from ..utils.image import bind_letterbox, letterbox_batch, letterbox_ragged
 from .blazeface import BlazeFace, generate_anchors
 
 MODEL_IN_SIZES = {"back": (256, 256), "front": (128, 128)}
@@ -57,9 +58,24 @@ class BlazeFaceModel(Model):
         return self.predict_batch(cv2_img[None])[0]
 
     def raw_batch(self, frames):
-        """frames: (B, H, W, 3) u8 BGR (numpy or CUDA tensor) -> device dets (B, 896, 17) [ymin,xmin,...], counts (B,)."""
+        """frames: (B, H, W, 3) u8 BGR (numpy or CUDA tensor) or a RaggedFrames -> device dets (B, 896, 17)
+        [ymin,xmin,...], counts (B,)."""
         net = self.net
         dev = net._device()
+        if isinstance(frames, RaggedFrames):
+            # frames of different sizes: one letterbox launch into a u8 canvas of the input size, then the u8 plan of that
+            # size (identity taps: the stem's staging returns the canvas bytes), or the fp32 plan input directly
+            ih, iw = net.input_hw
+            B = len(frames)
+            if BlazeFace.FUSE_LETTERBOX:
+                plan = net.plan_for(B, frame_hw=(ih, iw))
+                bind_letterbox(plan, letterbox_ragged(frames, (iw, ih)), net._preprocess_lut(), pad_value=125, swap_rb=True)
+            else:
+                plan = net.plan_for(B)
+                letterbox_ragged(frames, (iw, ih), net._preprocess_lut(), plan.input, pad_value=125, swap_rb=True)
+            plan.run()
+            net.last_plan = plan
+            return net.postprocess(plan.r, plan.c)
         if isinstance(frames, np.ndarray):
             frames = torch.from_numpy(np.ascontiguousarray(frames))
         frames = frames.to(dev)

@@ -5,6 +5,7 @@ import numpy as np
 import torch
 
 from ... import _lib as L
+from ...frames import RaggedFrames, resize_ragged
 
 
 def mfn_lut(device):
@@ -13,7 +14,11 @@ def mfn_lut(device):
 
 
 def crops_to_input(frames_u8, items, n_items, canvas, lut):
-    """frames_u8 (B,H,W,3) u8 CUDA; items int32 CUDA (n,9) fp_resize_item rows; canvas (n,112,112,C) fp32."""
+    """frames_u8 (B,H,W,3) u8 CUDA or a RaggedFrames; items int32 CUDA (n,9) fp_resize_item rows; canvas (n,112,112,C) fp32
+    (C = 4 for a RaggedFrames)."""
+    if isinstance(frames_u8, RaggedFrames):
+        resize_ragged(frames_u8, items, n_items, canvas, lut, pad_value=0, swap_rb=False)
+        return
     lib = L.load()
     B, H, W, _ = frames_u8.shape
     L.check(lib.fp_resize_normalize(L.ptr(frames_u8), B, H, W, L.ptr(items), int(n_items), L.ptr(canvas),

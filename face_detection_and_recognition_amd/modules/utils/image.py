@@ -49,6 +49,34 @@ def letterbox_batch(frames_u8, new_size, lut, canvas, pad_value=125, swap_rb=Fal
     return canvas
 
 
+def letterbox_items(frames, new_size):
+    """The fp_resize_item rows (device int32, (B, 9)) of pad_resize_image for every frame of a RaggedFrames: frame i's
+    whole image into its own letterbox rectangle of a new_w x new_h canvas (built once per batch and size)."""
+    new_w, new_h = new_size
+
+    def make():
+        rows = []
+        for i, (h, w) in enumerate(frames.sizes):
+            sw, sh, left, top = letterbox_geometry(w, h, new_w, new_h)
+            rows.append([i, 0, 0, w, h, left, top, sw, sh])
+        return torch.tensor(rows, dtype=torch.int32, device=frames.device)
+    return frames.cached(("letterbox", new_w, new_h), make)
+
+
+def letterbox_ragged(frames, new_size, lut=None, canvas=None, pad_value=125, swap_rb=False):
+    """pad_resize_image of every frame of a RaggedFrames in one launch (fp_resize_ragged).  lut None: returns a new
+    (B, new_h, new_w, 3) u8 canvas -- frames of one size, which a detector's u8 plan reads with identity taps, so the R/B
+    swap and the normalisation still happen once, in its stem.  Else: fills `canvas` (B, new_h, new_w, 4) fp32 through the
+    LUT, bit-identical to letterbox_batch on each frame."""
+    from ...frames import resize_ragged
+    new_w, new_h = new_size
+    B = len(frames)
+    if lut is None:
+        canvas = torch.empty((B, new_h, new_w, 3), dtype=torch.uint8, device=frames.device)
+    assert canvas.shape[0] == B and canvas.shape[1] == new_h and canvas.shape[2] == new_w
+    return resize_ragged(frames, letterbox_items(frames, new_size), B, canvas, lut, pad_value, swap_rb)
+
+
 def bind_letterbox(plan, frames_u8, lut, pad_value=125, swap_rb=False):
     """Point a plan whose first op reads u8 frames (FP_OP_*_U8) at a batch: external buffers [frames, tap tables, LUT].
     The tap tables of the plan's (frame size -> canvas size) letterbox are computed once per plan on the device

@@ -12,6 +12,7 @@ import torch
 
 from . import _lib as L
 from . import similarity as S
+from .frames import RaggedFrames
 from .modules.mobile_facenet.utils import crops_to_input, mfn_lut
 from .modules.utils.image import letterbox_geometry
 
@@ -26,6 +27,11 @@ def scale_coords_params(in_size, orig_size):
     gain = min(ih / h, iw / w)
     pad_x, pad_y = (iw - w * gain) / 2, (ih - h * gain) / 2
     return np.float32(gain), np.float32(pad_x), np.float32(pad_y)
+
+
+def ragged_scale_coords_params(in_size, sizes):
+    """(B, 3) float32 host array: scale_coords_params of every (h, w) in sizes, row = (gain, pad_x, pad_y)."""
+    return np.array([scale_coords_params(in_size, (w, h)) for h, w in sizes], dtype=np.float32).reshape(-1, 3)
 
 
 class FacePipeline:
@@ -65,7 +71,7 @@ class FacePipeline:
 
     # -- stages ----------------------------------------------------------------------------------
     def detect(self, frames, max_det=-1, beside=False):
-        """frames (B, H, W, 3) u8 BGR on device -> (dets, counts, overflow or None).  max_det: -1 = the detector's
+        """frames (B, H, W, 3) u8 BGR on device or a RaggedFrames -> (dets, counts, overflow or None).  max_det: -1 = the detector's
         default cap, None = uncapped (the exact re-run after an overflow).  beside: the detector's kernels will run
         beside the embedder's on the other stream (step_overlapped with two_streams)."""
         if self._co_net is not None:      # selects the plan (blazeface.py plan_for): several pipelines may share one detector
@@ -74,18 +80,29 @@ class FacePipeline:
         return out if len(out) == 3 else (out[0], out[1], None)
 
     def crops(self, frames, dets, counts):
-        """Device-side B7 + crop arithmetic -> (items, info, n_faces tensor)."""
+        """Device-side B7 + crop arithmetic -> (items, info, n_faces tensor).  frames: (B, H, W, 3) or a RaggedFrames
+        (each frame's boxes in its own pixels: per-frame scale_coords values, the same fp32 numbers as a frame alone)."""
         lib = L.load()
-        B, H, W, _ = frames.shape
+        B = len(frames) if isinstance(frames, RaggedFrames) else frames.shape[0]
         cap = B * self.max_faces_per_frame
         items = torch.empty((cap, 9), dtype=torch.int32, device=self.dev)
         info = torch.empty((cap, 7), dtype=torch.float32, device=self.dev)
         nf = torch.empty((1,), dtype=torch.int32, device=self.dev)
         iw, ih = self.det.input_size
-        gain, px, py = scale_coords_params((iw, ih), (W, H))
         fmt = getattr(self.det, "dets_fmt", 0)
         row = dets.shape[-1]
         tx, ty, bx, by = FACE_OFFSETS
+        if isinstance(frames, RaggedFrames):
+            geom = frames.cached(("scale_coords", iw, ih), lambda: torch.from_numpy(ragged_scale_coords_params(
+                (iw, ih), frames.sizes)).to(self.dev))
+            L.check(lib.fp_dets_to_crops_ragged(L.ptr(dets), L.ptr(counts), B, dets.shape[1], row, fmt, iw, ih,
+                                                L.ptr(frames.descs), L.ptr(geom), float(self.det.det_thres),
+                                                float(self.det.bbox_area_thres), tx, ty, bx, by, 112, 112, cap,
+                                                L.ptr(items), L.ptr(info), L.ptr(nf), L.current_stream(self.dev)),
+                    "fp_dets_to_crops_ragged")
+            return items, info, nf
+        _, H, W, _ = frames.shape
+        gain, px, py = scale_coords_params((iw, ih), (W, H))
         L.check(lib.fp_dets_to_crops(L.ptr(dets), L.ptr(counts), B, dets.shape[1], row, fmt, iw, ih, W, H,
                                      float(self.det.det_thres), float(self.det.bbox_area_thres), float(gain),
                                      float(px), float(py), tx, ty, bx, by, 112, 112, cap, L.ptr(items), L.ptr(info),
@@ -220,7 +237,8 @@ class FacePipeline:
 
     # -- whole step ------------------------------------------------------------------------------
     def step(self, frames, beside=False):
-        """One pass over a batch of frames.  Returns dict(n_faces, info, emb, best, arg, keep).
+        """One pass over a batch of frames ((B, H, W, 3) u8 BGR on device, or a RaggedFrames of different sizes).
+        Returns dict(n_faces, info, emb, best, arg, keep).
         ``emb`` is a copy (the embedder's output lives in its plan arena and the next step overwrites it).
         beside: use the detector plan of the two-stream steps (measurement: bench.py's per-op probe pass)."""
         dets, counts, over = self.detect(frames, beside=beside)

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from .. import similarity as S
+from ..frames import RaggedFrames
 from ..modules.mobile_facenet.utils import crops_to_input, mfn_lut
 
 
@@ -86,16 +87,17 @@ def embed_images(model, paths, batch_size=32, preprocess="mobile_facenet", entro
         chunk = paths[i:i + batch_size]
         plan = model.plan_for(len(chunk))
         decoded = imread_batch(chunk, dev, entropy=entropy)   # (B, H, W, 3) when the sizes agree, else a list
-        for j in range(len(chunk)):              # images differ in size: one resize launch per image
-            img = decoded[j].unsqueeze(0)
-            if preprocess == "tf_standardize":
-                rgb = img.flip(-1).contiguous()
+        if preprocess == "tf_standardize":
+            for j in range(len(chunk)):
+                rgb = decoded[j].unsqueeze(0).flip(-1).contiguous()
                 plan.input[j, ..., :3].copy_(preprocess_tf_standardize(rgb, (112, 112))[0])
                 plan.input[j, ..., 3:].zero_()
-                continue
-            h, w = img.shape[1:3]
-            item = torch.tensor([[0, 0, 0, w, h, 0, 0, 112, 112]], dtype=torch.int32, device=dev)
-            crops_to_input(img, item, 1, plan.input[j:j + 1], lut)
+        else:
+            # every image, whatever its size, resized into its own 112 x 112 canvas in one launch (fp_resize_ragged)
+            frames = RaggedFrames.from_list(list(decoded), dev)
+            items = torch.tensor([[j, 0, 0, w, h, 0, 0, 112, 112] for j, (h, w) in enumerate(frames.sizes)],
+                                 dtype=torch.int32, device=dev)
+            crops_to_input(frames, items, len(chunk), plan.input, lut)
         plan.run()
         feats.append(plan.out.clone())
     return torch.cat(feats) if feats else torch.zeros((0, model.embedding_size), device=dev)

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define FP_ABI_VERSION 13
+#define FP_ABI_VERSION 14
 
 typedef enum fp_status {
   FP_OK = 0,
@@ -294,7 +294,9 @@ typedef struct fp_op {
  * ABI history: 1 = round-1 ops; 2 = fp_ext / *_U8 ops (never shipped in a VERDICT-ed tree); 3 = fp_op.flags, row-padded
  * views; 4 = fp_op.Cmid / reserved0, FP_OP_DWBLOCK, FP_OP_BLAZEPAIR; 5 = FP_OPF_SPLIT3; 6 = FP_OP_BLAZECHAIN; 7 = FP_OPF_IN_UP2; 8 = FP_OP_BLAZEPAIR with stride 2; 9 = FP_OPF_OUT_DW, fp_debug_reload_env; 10 = FP_OP_SHUFDOWN, FP_OP_SHUFUNIT, FP_OP_YSTEM2; 11 = FP_OPF_SPLIT3 on FP_OP_STEM_U8;
  * 12 = device Huffman decoding of sequential JPEG scans (fp_jpeg_scan, fp_jpeg_scan_prepare, fp_jpeg_entropy_decode_device, section 7);
- * 13 = baseline JPEG encoding of crop batches (fp_jpeg_enc_item, fp_jpeg_encode_device, section 8).
+ * 13 = baseline JPEG encoding of crop batches (fp_jpeg_enc_item, fp_jpeg_encode_device, section 8);
+ * 14 = ragged batches: frames of different sizes in one packed buffer (fp_frame_desc, fp_resize_ragged,
+ * fp_dets_to_crops_ragged, section 2).
  */
 
 /* Validates every op against arena_floats / weight_floats, then launches them in order. */
@@ -408,6 +410,54 @@ int fp_dets_to_crops(const float* dets, const int32_t* counts, int B, int max_de
                      float gain, float pad_x, float pad_y, int off_tx, int off_ty, int off_bx, int off_by,
                      int dst_w, int dst_h, int max_faces,
                      fp_resize_item* items, float* face_info, int32_t* n_faces, void* stream);
+
+/*
+ * Ragged batches (ABI 14): frames of DIFFERENT sizes (u8 BGR, HWC, rows packed) back to back in one buffer, each described
+ * by an fp_frame_desc in device memory.  frame i = frames[descs[i].off ...], descs[i].h x descs[i].w pixels.  The frames
+ * the reference's dataset driver reads (one photo per media item, fde/face_extraction/extract_faces_from_dataset.py:380-405)
+ * are of any size; these entry points take a whole batch of them in one launch.
+ */
+typedef struct fp_frame_desc {
+  int64_t off;        /* byte offset of the frame's pixel (0, 0) in the packed buffer */
+  int32_t h, w;       /* the frame's size (pixels) */
+} fp_frame_desc;
+
+#define FP_FRAME_MIN_W 3        /* a frame row holds the 8-byte tap window of the resize (csrc/letterbox.h) */
+#define FP_FRAME_MAX_W 32767
+#define FP_FRAME_MAX_H 65535
+#define FP_RAGGED_U8 0          /* fp_resize_ragged output: u8 canvas, 3 channels in frame order, no LUT, no R/B swap */
+#define FP_RAGGED_F32_LUT 1     /* fp_resize_ragged output: fp32 canvas, 4 channels, lut256[value] (+ swap_rb), 4th = 0 */
+
+/*
+ * fp_resize_normalize over a ragged batch: item i resizes its source rectangle of frame items[i].src_image (an index into
+ * descs) into the destination rectangle of canvas i, pad_value elsewhere.  Every output value equals what
+ * fp_resize_normalize computes on the same source rectangle of the same frame (FP_RAGGED_F32_LUT: bit for bit; FP_RAGGED_U8:
+ * the u8 value before the LUT).  One workgroup per (item, band of canvas rows): the work of an item depends on its canvas,
+ * not on its frame.  canvas: [n_items][canvas_h][canvas_w][canvas_c], canvas_c = 3 (u8, lut256 unused, swap_rb = 0) or
+ * 4 (fp32, 16-byte aligned, lut256 = 256 device floats); canvas_w <= 4096, canvas_h <= 65535.
+ * Refusals before any launch: NULL pointers, sizes out of range, a canvas_c or swap_rb the mode does not take, frames_bytes
+ * < 9 (FP_ERR_INVALID_ARG); a misaligned fp32 canvas (FP_ERR_ALIGNMENT).
+ * Trust boundary: descs and items are device memory the host does not read.  The kernel clamps each source rectangle to its
+ * frame and writes pad_value for an item whose descriptor is outside [FP_FRAME_MIN_W, FP_FRAME_MAX_W] x [1, FP_FRAME_MAX_H]
+ * or whose frame does not end inside frames_bytes, so it never loads outside the buffer; that the descriptors describe the
+ * frames the caller meant (no overlap, the right sizes) is the caller's contract.
+ */
+int fp_resize_ragged(const uint8_t* frames, size_t frames_bytes, const fp_frame_desc* descs /*device*/, int n_frames,
+                     const fp_resize_item* items /*device*/, int n_items, void* canvas, int canvas_h, int canvas_w,
+                     int canvas_c, int mode, const float* lut256 /*device, 256 floats; FP_RAGGED_F32_LUT only*/,
+                     int pad_value, int swap_rb, void* stream);
+
+/*
+ * fp_dets_to_crops over a ragged batch: frame f's orig_w / orig_h come from descs[f] (w, h) and its scale_coords values
+ * from geom[f] = (gain, pad_x, pad_y) fp32 (device, B x 3; the caller computes them per frame as for fp_dets_to_crops).
+ * Same kernel body, same rows, same order.  A frame whose descriptor has h or w <= 0 or whose gain is not > 0 contributes
+ * no faces.  Refusals as fp_dets_to_crops (FP_ERR_INVALID_ARG before any launch).
+ */
+int fp_dets_to_crops_ragged(const float* dets, const int32_t* counts, int B, int max_dets, int row_floats, int fmt,
+                            int in_w, int in_h, const fp_frame_desc* descs /*device, B*/, const float* geom /*device, B x 3*/,
+                            float det_thres, float area_thres, int off_tx, int off_ty, int off_bx, int off_by,
+                            int dst_w, int dst_h, int max_faces,
+                            fp_resize_item* items, float* face_info, int32_t* n_faces, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* 3. BlazeFace post-processing                                                */

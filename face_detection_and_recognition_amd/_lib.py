@@ -44,7 +44,7 @@ class FpOp(C.Structure):
         ("in_off", C.c_int64), ("out_off", C.c_int64), ("res_off", C.c_int64),
         ("w_off", C.c_int64), ("scale_off", C.c_int64), ("bias_off", C.c_int64), ("slope_off", C.c_int64),
         ("act2", C.c_int32), ("flags", C.c_int32),
-        ("Cmid", C.c_int32), ("reserved0", C.c_int32),
+        ("Cmid", C.c_int32), ("row_lo", C.c_int16), ("row_end", C.c_int16),
     ]
 
 

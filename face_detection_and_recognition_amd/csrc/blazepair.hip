@@ -15,7 +15,9 @@
 //   * the shortcut + bias of block 1 are parked in the ring slot the row will occupy, and the epilogue updates them in
 //     place, so there is no shortcut tile; block 2's output tile reuses the A tile: 66 KiB of LDS per workgroup, two
 //     workgroups per CU;
-//   * a band needs y1 rows y0 - 1 .. y0 + R: R + 2 block-1 rows for R output rows (R = 64: 3 % recomputed).
+//   * a band needs y1 rows y0 - 1 .. y0 + R: R + 2 block-1 rows for R output rows (R = 64: 3 % recomputed);
+//   * with a row window (facepath.h "Row windows") the bands cover only the window's rows; y1 rows outside the window but
+//     inside the image are computed from x like any other (the caller keeps x right there), only rows -1 and H are zero.
 // Bytes per pair: x once (+ the band halos) and y2 once -- half of what two launches move; the instruction count per
 // pixel is the same as two blazeblock_wp launches (fp32 MFMAs and VALU share the SIMD's ALU: tools/lab/coexec_lab.hip).
 #include "common.h"
@@ -39,7 +41,8 @@ struct BlazePairArgs {
   const float* bd;    // [2][C]
   const float* wp;    // [2] packed [C/4][32][4]
   const float* bp;    // [2][C]
-  int H, R, bands;    // bands per image (H / R)
+  int H, R, bands;    // bands per image
+  int lo, span;       // band b starts at output row lo + min(b R, span): the row window (facepath.h) is rows lo .. lo + span + R - 1
   int nbands;         // N * bands
   int in_rp, out_rp;  // row pitch, floats
   long in_ns, out_ns;
@@ -101,7 +104,7 @@ __global__ __launch_bounds__(256, 2) void blazepair_kernel(BlazePairArgs p) {
   const int bi = min((int)blockIdx.x * NSUB + sub, p.nbands - 1);
   const bool live = (int)blockIdx.x * NSUB + sub < p.nbands;
   const unsigned img = __builtin_amdgcn_readfirstlane(fp_fastdiv((unsigned)bi, p.bands_div));
-  const int y0 = __builtin_amdgcn_readfirstlane((bi - (int)img * p.bands) * p.R);   // wave-uniform: the row tests below are scalar branches
+  const int y0 = __builtin_amdgcn_readfirstlane(p.lo + min((bi - (int)img * p.bands) * p.R, p.span));   // wave-uniform: the row tests below are scalar branches
   const long in_rb = (long)p.in_rp * 4, out_rb = (long)p.out_rp * 4;
   const char* inb = (const char*)p.in + fp_uniform(((long)img * p.in_ns + (long)(x0 - 1) * C) * 4);    // (row 0, column x0 - 1)
   char* outb = (char*)p.out + fp_uniform(((long)img * p.out_ns + (long)x0 * C) * 4);                   // (row 0, column x0)
@@ -337,8 +340,19 @@ int fp_launch_blazepair(const fp_op& op, const float* weights, float* arena, hip
   a.wp = weights + op.slope_off;
   a.bp = weights + op.bias_off;
   a.H = op.H;
-  a.R = fp_blazepair_band_rows(op);
-  a.bands = op.H / a.R;
+  if (op.row_end > 0) {
+    // a row window: bands over its rows only, as many as fill whole rounds of the 512 workgroup slots (two per CU)
+    const int rows = op.row_end - op.row_lo, nsub = 4 / (op.W / 32);
+    a.bands = fp_window_bands(rows, op.N, nsub, 512, 1, 2, 2, 8);
+    a.R = fp_ceil_div(rows, a.bands);
+    a.lo = op.row_lo;
+    a.span = rows - a.R;
+  } else {
+    a.R = fp_blazepair_band_rows(op);
+    a.bands = op.H / a.R;
+    a.lo = 0;
+    a.span = op.H - a.R;
+  }
   a.nbands = op.N * a.bands;
   a.in_rp = (op.W + 1) * C;
   a.out_rp = (op.OW + ((op.flags & FP_OPF_OUT_ROWPAD) ? 1 : 0)) * C;

@@ -28,7 +28,8 @@ struct BlazePairS2Args {
   const float* bd;    // [2][C]
   const float* wp;    // block 1: packed [C/4][32][4]; block 2 behind it: packed [C/4][Npad2][4], Npad2 = 32 (C2 = 24) / 64 (C2 = 48)
   const float* bp;    // [C] then [C2]
-  int H, R, bands;    // R = output rows of y2 per band, bands per image ((H / 2) / R)
+  int H, R, bands;    // R = output rows of y2 per band, bands per image
+  int lo, span;       // band b starts at y2 row lo + min(b R, span): the row window (facepath.h) is y2 rows lo .. lo + span + R - 1
   int nbands;         // N * bands
   int in_rp, out_rp;  // row pitch, floats
   long in_ns, out_ns;
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(256, 2) void blazepair_s2_kernel(BlazePairS2Args p)
   const int bi = min((int)blockIdx.x * NSUB + sub, p.nbands - 1);
   const bool live = (int)blockIdx.x * NSUB + sub < p.nbands;
   const unsigned img = __builtin_amdgcn_readfirstlane(fp_fastdiv((unsigned)bi, p.bands_div));
-  const int yo0 = __builtin_amdgcn_readfirstlane((bi - (int)img * p.bands) * p.R);
+  const int yo0 = __builtin_amdgcn_readfirstlane(p.lo + min((bi - (int)img * p.bands) * p.R, p.span));
   const int ya = 2 * yo0;                                  // first y1 row of the band
   const long in_rb = (long)p.in_rp * 4, out_rb = (long)p.out_rp * 4;
   const char* inb = (const char*)p.in + fp_uniform(((long)img * p.in_ns + (long)(x0 - 1) * C) * 4);           // (row 0, column x0 - 1)
@@ -319,8 +320,20 @@ int fp_launch_blazepair_s2(const fp_op& op, const float* weights, float* arena, 
   a.wp = weights + op.slope_off;
   a.bp = weights + op.bias_off;
   a.H = op.H;
-  a.R = fp_blazepair_s2_band_rows(op);
-  a.bands = op.OH / a.R;
+  if (op.row_end > 0) {
+    // a row window of y2 rows: bands over its rows only, as many as fill whole rounds of the 512 workgroup slots (a band of
+    // R rows of y2 takes 2 R + 1 steps)
+    const int rows = op.row_end - op.row_lo, nsub = 4 / (op.W / 32);
+    a.bands = fp_window_bands(rows, op.N, nsub, 512, 2, 1, 2, 4);
+    a.R = fp_ceil_div(rows, a.bands);
+    a.lo = op.row_lo;
+    a.span = rows - a.R;
+  } else {
+    a.R = fp_blazepair_s2_band_rows(op);
+    a.bands = op.OH / a.R;
+    a.lo = 0;
+    a.span = op.OH - a.R;
+  }
   a.nbands = op.N * a.bands;
   a.in_rp = (op.W + 1) * 24;
   a.out_rp = (op.OW + ((op.flags & FP_OPF_OUT_ROWPAD) ? 1 : 0)) * op.Cout;

@@ -100,7 +100,12 @@ static int validate_op(const fp_op& op, size_t weight_floats, size_t arena_float
   const int Cout = (op.kind == FP_OP_CONV || op.kind == FP_OP_BLAZEBLOCK || op.kind == FP_OP_DWPW ||
                     op.kind == FP_OP_DWBLOCK || op.kind == FP_OP_BLAZEPAIR || op.kind == FP_OP_BLAZECHAIN || op.kind == FP_OP_YSTEM ||
                     op.kind == FP_OP_SHUFDOWN || op.kind == FP_OP_SHUFUNIT || op.kind == FP_OP_YSTEM2 || ext_in) ? op.Cout : op.Cin;
-  if (op.reserved0 != 0 || (op.kind != FP_OP_DWBLOCK && op.kind != FP_OP_BLAZECHAIN && op.kind != FP_OP_SHUFDOWN && op.kind != FP_OP_SHUFUNIT && op.Cmid != 0)) return FP_ERR_INVALID_ARG;
+  if (op.kind != FP_OP_DWBLOCK && op.kind != FP_OP_BLAZECHAIN && op.kind != FP_OP_SHUFDOWN && op.kind != FP_OP_SHUFUNIT && op.Cmid != 0) return FP_ERR_INVALID_ARG;
+  if (op.row_lo != 0 || op.row_end != 0) {
+    // a row window (facepath.h "Row windows"): only the kernels that take one, never empty, inside the output map
+    if (!(op.kind == FP_OP_BLAZEPAIR || (op.kind == FP_OP_STEM_U8 && fp_stem_u8_band_eligible(op)))) return FP_ERR_UNSUPPORTED;
+    if (op.row_lo < 0 || op.row_end <= op.row_lo || op.row_end > OH) return FP_ERR_INVALID_ARG;
+  }
   if (Cout <= 0 || op.out_cmul < 1 || op.in_ld < op.Cin) return FP_ERR_INVALID_ARG;
   // row-padded views (facepath.h FP_OPF_*): which ops take them, and their extent including the pads
   if (op.flags & ~(FP_OPF_IN_ROWPAD | FP_OPF_OUT_ROWPAD | FP_OPF_IN_C3 | FP_OPF_SPLIT3 | FP_OPF_IN_DW | FP_OPF_IN_UP2 | FP_OPF_OUT_DW))

@@ -86,6 +86,21 @@ __device__ __forceinline__ long fp_uniform(long v) {
 }
 
 static inline int fp_ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Bands per image for a launch over a row window of `rows` output rows of N images (facepath.h "Row windows"): a workgroup
+// takes `per_wg` bands, `slots` workgroups run at once on the device, and a band of R rows costs step_mul * R + halo steps.
+// Minimises (rounds of slots) x (steps per band) over bmin .. rows / min_rows bands (at least bmin); ties keep fewer bands.
+// A band of ceil(rows / bands) rows: the last one is moved up to end at the window's end, overlapping its neighbour.
+static inline int fp_window_bands(int rows, int N, int per_wg, int slots, int step_mul, int halo, int bmin, int min_rows) {
+  int best = bmin;
+  long best_cost = -1;
+  for (int b = bmin; b == bmin || b <= rows / min_rows; ++b) {
+    const long rounds = fp_ceil_div(fp_ceil_div((long)N * b, per_wg), slots);
+    const long cost = rounds * ((long)step_mul * fp_ceil_div(rows, b) + halo);
+    if (best_cost < 0 || cost < best_cost) best = b, best_cost = cost;
+  }
+  return best;
+}
 static inline long fp_round_up(long a, long b) { return (a + b - 1) / b * b; }
 
 // launchers implemented in the .hip files, called by the plan executor (capi.cpp)

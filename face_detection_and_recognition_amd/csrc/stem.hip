@@ -355,7 +355,8 @@ int fp_launch_stem_u8(const fp_op& op, const float* weights, float* arena, const
 // pixel is RESAMPLED 2.5 times (~70 VALU instructions each, and fp32 MFMAs do not hide VALU work: tools/lab/coexec_lab).
 // Here a workgroup owns a band of R consecutive output rows of one image and keeps the canvas rows in an 8-row LDS ring:
 // output row oy reads ring rows 2oy-1 .. 2oy+3 while the two rows the NEXT output row adds (2oy+4, 2oy+5) are resampled
-// into the ring -- one resample per canvas pixel (+ 3 rows per band), one workgroup barrier per output row.
+// into the ring -- one resample per canvas pixel (+ 3 rows per band), one workgroup barrier per output row.  With a row
+// window (facepath.h "Row windows") the bands cover the window's rows only (both band kernels).
 //   * wave w owns output pixels 32w .. 32w+31 of the row; the 5x5 weights of its MFMAs live in registers;
 //   * D^T = W^T x A^T (operands swapped), so a lane ends up with 16-byte channel pieces of ITS pixel: bias + ReLU on
 //     float4s, three ds_write_b128 into the wave's private output tile, three coalesced 16-byte global stores;
@@ -376,6 +377,7 @@ struct StemBandArgs {
   long frame_bytes, row_bytes, out_ns;
   int frame_h, frame_w, out_rp;   // out_rp: output row pitch in floats ((OW + 1) * 24 row-padded, OW * 24 dense)
   int R, bands;                   // rows per band, bands per image
+  int lo, span;                   // band b starts at output row lo + min(b R, span): the row window (facepath.h) is rows lo .. lo + span + R - 1
 };
 
 constexpr int SB_W = 256, SB_OW = 128, SB_C = 24, SB_WP = 260, SB_KQ = 13;   // ring row: columns -1 .. 258 (zero borders)
@@ -407,7 +409,7 @@ __global__ __launch_bounds__(256, 3) void stem5_u8_band_kernel(StemBandArgs p) {
   for (int j = 0; j < 3; ++j) bias4[j] = *(const f32x4*)(p.bias + 8 * j + 4 * h);
 
   const int img = blockIdx.x / p.bands, band = blockIdx.x - img * p.bands;
-  const int oy0 = band * p.R;
+  const int oy0 = p.lo + min(band * p.R, p.span);
   const uint8_t* frame = p.frames + (long)img * p.frame_bytes;
   float* outi = p.out + (long)img * p.out_ns;
   __syncthreads();
@@ -563,7 +565,7 @@ __global__ __launch_bounds__(256, 3) void stem5_u8_x6_kernel(StemBandArgs p) {
   for (int nt = 0; nt < 2; ++nt) bias4[nt] = (nt == 0 || q < 2) ? *(const f32x4*)(p.bias + 16 * nt + 4 * q) : z4;
 
   const int img = blockIdx.x / p.bands, band = blockIdx.x - img * p.bands;
-  const int oy0 = band * p.R;
+  const int oy0 = p.lo + min(band * p.R, p.span);
   const uint8_t* frame = p.frames + (long)img * p.frame_bytes;
   float* outi = p.out + (long)img * p.out_ns;
   __syncthreads();
@@ -682,8 +684,19 @@ int fp_launch_stem_u8_band(const fp_op& op, const float* weights, float* arena, 
 #ifndef FP_STEM_BAND_ROWS
 #define FP_STEM_BAND_ROWS 16
 #endif
-  a.R = FP_STEM_BAND_ROWS;
-  a.bands = SB_OW / a.R;
+  if (op.row_end > 0) {
+    // a row window: bands over its rows only, as many as fill whole rounds of the 768 workgroup slots (three per CU)
+    const int rows = op.row_end - op.row_lo;
+    a.bands = fp_window_bands(rows, op.N, 1, 768, 1, 1, 1, 4);
+    a.R = fp_ceil_div(rows, a.bands);
+    a.lo = op.row_lo;
+    a.span = rows - a.R;
+  } else {
+    a.R = FP_STEM_BAND_ROWS;
+    a.bands = SB_OW / a.R;
+    a.lo = 0;
+    a.span = SB_OW - a.R;
+  }
   if (op.flags & FP_OPF_SPLIT3) {
     const size_t lds6 = (size_t)3 * SX_PL * 2 + 256 * 4 + 8 * (size_t)(2 * SB_W);
     hipLaunchKernelGGL(stem5_u8_x6_kernel, dim3(op.N * a.bands), dim3(256), lds6, s, a);

@@ -15,6 +15,24 @@ import torch.nn as nn
 from ... import _lib as L
 from ...plan import Buf, CompiledPlan, PlanBuilder, PlanCache, View, cpad, switch_key
 from ..params import ConvParams, _NoCompute, npy
+from ..utils.image import letterbox_geometry
+
+
+def _dirty_rows(d, rf, OH):
+    """Output rows [lo, hi] of an OH-row map that depend on input rows d = [lo, hi] (None: every row).  rf = (stride, a, b):
+    output row y reads input rows stride * y + a .. stride * y + b."""
+    if d is None:
+        return None
+    s, a, b = rf
+    return max(0, -((b - d[0]) // s)), min(OH - 1, (d[1] - a) // s)
+
+
+# receptive fields (stride, first input row, last input row) of output row y, blazeface.py:12-68,118-120,195
+RF_STEM = (2, -1, 3)          # F.pad(1, 2, 1, 2) + 5 x 5 stride 2
+RF_BLOCK1 = (1, -1, 1)        # stride-1 BlazeBlock: 3 x 3, padding 1
+RF_BLOCK2 = (2, 0, 2)         # stride-2 BlazeBlock / FinalBlazeBlock: F.pad(0, 2, 0, 2) + 3 x 3 stride 2
+RF_PAIR = (1, -2, 2)          # two stride-1 blocks
+RF_PAIR_S2 = (2, -1, 3)       # a stride-1 block + a stride-2 block
 
 
 class BlazeBlock(_NoCompute):
@@ -59,14 +77,15 @@ class BlazeBlock(_NoCompute):
                 other.kernel_size == 3 and other.stride == 2 and other.in_channels == 24 and
                 pb.blazepair_s2_supported(x, other.out_channels))
 
-    def emit_pair_s2(self, other, pb, x, out_rowpad=False):
-        y = (pb.new_buf_rowpad if out_rowpad else pb.new_buf)(x.H // 2, x.W // 2, other.out_channels)
+    def emit_pair_s2(self, other, pb, x, out_rowpad=False, dedicated=False):
+        y = pb.new_buf_rowpad(x.H // 2, x.W // 2, other.out_channels, dedicated) if out_rowpad else \
+            pb.new_buf(x.H // 2, x.W // 2, other.out_channels)
         pb.blazepair_s2(x, [(npy(b.convs[0].weight), npy(b.convs[0].bias), npy(b.convs[1].weight), npy(b.convs[1].bias))
                             for b in (self, other)], y.view())
         return y
 
-    def emit_pair(self, other, pb, x, out_rowpad=False):
-        y = (pb.new_buf_rowpad if out_rowpad else pb.new_buf)(x.H, x.W, 24)
+    def emit_pair(self, other, pb, x, out_rowpad=False, dedicated=False):
+        y = pb.new_buf_rowpad(x.H, x.W, 24, dedicated) if out_rowpad else pb.new_buf(x.H, x.W, 24)
         pb.blazepair(x, [(npy(b.convs[0].weight), npy(b.convs[0].bias), npy(b.convs[1].weight), npy(b.convs[1].bias))
                          for b in (self, other)], y.view())
         return y
@@ -256,6 +275,10 @@ class BlazeFace(nn.Module):
         return (256, 256) if self.back_model else (128, 128)
 
     FUSE_LETTERBOX = True    # class-wide switch: False keeps the stand-alone letterbox kernel (A/B parity tests)
+    # class-wide switch: on a letterboxed frame (u8 plans, back model, batch >= 16) the stem and the pair kernels of the 128 x 128
+    # and 64 x 64 stages compute only the rows that depend on the frame's content (row windows, include/facepath.h); the
+    # rest, which only the pad colour reaches, is left from the plan's unrestricted runs (CompiledPlan).  False: every row
+    ROW_WINDOW = os.environ.get("FP_BLAZE_ROW_WINDOW", "1") == "1"
 
     def _emit(self, N, frame_hw=None):
         """Emit the op list for batch N (host only, no GPU needed).  frame_hw = (frame_h, frame_w): the stem reads u8
@@ -285,34 +308,64 @@ class BlazeFace(nn.Module):
                 return False
             return i < len(blocks) and isinstance(blocks[i], BlazeBlock) and blocks[i].wants_rowpad_input(h, w)
 
+        # Row windows: `dirty` = the rows [lo, hi] of the current map that depend on the frame's content (None: all of them).
+        # The letterbox puts the content in canvas rows top .. top + sh - 1; every conv is local, so every other row of every
+        # map is the same in each frame.  An op whose kernel takes a window and whose output rows are not all dirty writes a
+        # dedicated buffer and gets its dirty rows as its window (PlanBuilder.window).
+        dirty = None
+        if frame_hw is not None and BlazeFace.ROW_WINDOW and self.back_model and N >= 16:
+            _, sh, _, top = letterbox_geometry(frame_hw[1], frame_hw[0], W, H)
+            if 0 < sh < H:
+                dirty = (top, top + sh - 1)
+
+        def windowed(d, OH):      # True: an op with these dirty output rows gets a window
+            return d is not None and OH in (128, 64) and d != (0, OH - 1)
+
         # F.pad(x, (1, 2, 1, 2)) + 5x5 stride-2 conv + ReLU (blazeface.py:118-120,195)
-        x = (pb.new_buf_rowpad if rowpad_for(0, H // 2, W // 2) else pb.new_buf)(H // 2, W // 2, 24)
+        dirty = _dirty_rows(dirty, RF_STEM, H // 2)
+        win = windowed(dirty, H // 2) and rowpad_for(0, H // 2, W // 2)
+        x = pb.new_buf_rowpad(H // 2, W // 2, 24, win) if rowpad_for(0, H // 2, W // 2) else pb.new_buf(H // 2, W // 2, 24)
         if frame_hw is None:
             pb.conv(inp.view(), npy(stem.weight), x.view(), stride=2, pad=(1, 1), bias=npy(stem.bias), act=L.ACT_RELU)
         else:
             split = BlazeFace.STEM_X6 and PlanBuilder.X6 and (H, W) == (256, 256) and N >= 16
             pb.stem_u8((H, W, frame_hw[0], frame_hw[1], 0), npy(stem.weight), x.view(), pad=(1, 1), bias=npy(stem.bias),
                        act=L.ACT_RELU, split=split)
+            if win:
+                pb.window(dirty[0], dirty[1] + 1)
         i = 0
         while i < len(blocks):
             blk = blocks[i]
             nchain = chain_len(i, x.H, x.W)
             if nchain and pb.blazechain_supported(x.view()):
+                dirty = None        # 16 x 16: past the windowed stages
                 y = pb.new_buf(16, 16, 96)
                 pb.blazechain(x.view(), [(npy(b.convs[0].weight), npy(b.convs[0].bias), npy(b.convs[1].weight), npy(b.convs[1].bias))
                                          for b in blocks[i:i + nchain]], y.view())
                 i += nchain - 1
             elif (isinstance(blk, BlazeBlock) and i + 1 < len(blocks) and isinstance(blocks[i + 1], BlazeBlock) and
                     blk.pairs_with(blocks[i + 1], pb, x.view())):
-                y = blk.emit_pair(blocks[i + 1], pb, x.view(), out_rowpad=rowpad_for(i + 2, x.H, x.W))
+                dirty = _dirty_rows(dirty, RF_PAIR, x.H)
+                rp = rowpad_for(i + 2, x.H, x.W)
+                win = windowed(dirty, x.H) and rp
+                y = blk.emit_pair(blocks[i + 1], pb, x.view(), out_rowpad=rp, dedicated=win)
+                if win:
+                    pb.window(dirty[0], dirty[1] + 1)
                 i += 1
             elif isinstance(blk, BlazeBlock) and i + 1 < len(blocks) and blk.pairs_with_s2(blocks[i + 1], pb, x.view()):
-                y = blk.emit_pair_s2(blocks[i + 1], pb, x.view(), out_rowpad=rowpad_for(i + 2, x.H // 2, x.W // 2))
+                dirty = _dirty_rows(dirty, RF_PAIR_S2, x.H // 2)
+                rp = rowpad_for(i + 2, x.H // 2, x.W // 2)
+                win = windowed(dirty, x.H // 2) and rp
+                y = blk.emit_pair_s2(blocks[i + 1], pb, x.view(), out_rowpad=rp, dedicated=win)
+                if win:
+                    pb.window(dirty[0], dirty[1] + 1)
                 i += 1
             elif isinstance(blk, BlazeBlock):
                 oh, ow = (x.H // 2, x.W // 2) if blk.stride == 2 else (x.H, x.W)
+                dirty = _dirty_rows(dirty, RF_BLOCK2 if blk.stride == 2 else RF_BLOCK1, oh)
                 y = blk.emit(pb, x.view(), out_rowpad=blk.fused(pb, x.view()) and rowpad_for(i + 1, oh, ow))
             else:
+                dirty = None
                 y = blk.emit(pb, x.view())
             pb.free(x)
             x = y

@@ -92,6 +92,8 @@ def bind_letterbox(plan, frames_u8, lut, pad_value=125, swap_rb=False):
                                              int(bool(swap_rb)), L.ptr(t), L.current_stream(frames_u8.device)),
                 "fp_letterbox_tables")
         plan.tables = (key, t)
+        if hasattr(plan, "invalidate_windows"):   # new pad colour: the rows outside a row window change (CompiledPlan)
+            plan.invalidate_windows()
     plan.set_ext([frames_u8, plan.tables[1], lut])
     return plan
 

@@ -37,6 +37,7 @@ class Buf:
     size: int    # floats, whole batch
     ns_: int = -1   # per-image stride override (e.g. a head writing into a [B, 896, 16] tensor)
     rowpad: bool = False   # row-padded layout (include/facepath.h): off = pixel (0, 0) of image 0, row pitch (W+1)*C
+    dedicated: bool = False   # the output of ONE row-windowed op: never recycled (rows outside the window keep their values)
 
     @property
     def ld(self):
@@ -181,6 +182,7 @@ class PlanBuilder:
         self.rowpad_end = 0
         self.has_rowpad = False
         self._placed = False
+        self.windows = []       # [(op index, row_lo, row_end)]: the row windows of window() (applied by CompiledPlan)
 
     # ---- memory ----
     def new_buf(self, H, W, C):
@@ -189,24 +191,25 @@ class PlanBuilder:
         self.peak = max(self.peak, self.arena.top)
         return Buf(H, W, C, off, size)
 
-    def new_buf_rowpad(self, H, W, C):
+    def new_buf_rowpad(self, H, W, C, dedicated=False):
         """A buffer in the row-padded layout of include/facepath.h (one zero pixel after every row, a zero row above and
         below every image): 3x3 windows read it without bounds checks.  The pads must stay zero for the life of the
         plan, so these buffers live in a region of their own behind the recycled arena (no op ever writes there except
         through a row-padded view: a recycled block would carry another tensor's data into the pads), free() keeps
         them for the next row-padded buffer of the same shape, and the arena of such a plan starts zeroed.  Offsets are
-        relative to that region until finish() places it."""
+        relative to that region until finish() places it.  dedicated: a buffer of its own that free() never hands out
+        again (the output of a row-windowed op, window())."""
         assert not self._placed, "plan already finished"
         C = cpad(C)
         pool = self.rowpad_free.setdefault((H, W, C), [])
-        if pool:
+        if pool and not dedicated:
             return pool.pop()
         ns = ((H + 2) * (W + 1) + 1) * C
         base = self.rowpad_top
         self.rowpad_end = base + self.N * ns           # exact end of the region (the arena size is exact too)
         self.rowpad_top += round_up(self.N * ns, 64)
         self.has_rowpad = True
-        buf = Buf(H, W, C, base + (W + 2) * C, self.N * ns, ns_=ns, rowpad=True)
+        buf = Buf(H, W, C, base + (W + 2) * C, self.N * ns, ns_=ns, rowpad=True, dedicated=dedicated)
         self.rowpad_bufs.append(buf)
         return buf
 
@@ -222,6 +225,8 @@ class PlanBuilder:
         return Buf(H, W, 0, 0, 0)
 
     def free(self, buf):
+        if buf.dedicated:
+            return
         if buf.rowpad:
             self.rowpad_free.setdefault((buf.H, buf.W, buf.C), []).append(buf)
         else:
@@ -236,6 +241,13 @@ class PlanBuilder:
             self.wchunks.append(np.zeros(pad, dtype=np.float32))
         self.w_floats += arr.size + pad
         return off
+
+    def window(self, lo, end):
+        """Give the last emitted op the output row window [lo, end) (include/facepath.h "Row windows").  Its output must be a
+        dedicated buffer: the rows outside the window are left as the plan's unrestricted runs wrote them."""
+        op = self.ops[-1]
+        assert 0 <= lo < end <= op.OH and (lo, end) != (0, op.OH)
+        self.windows.append((len(self.ops) - 1, int(lo), int(end)))
 
     # ---- op emission ----
     def _base(self, kind, x, out, OH, OW):
@@ -1112,6 +1124,45 @@ class CompiledPlan:
         self.lib = L.load()
         L.check(self.lib.fp_plan_validate(self.ops, self.n_ops, self.weights.numel(), self.arena_floats),
                 "fp_plan_validate")
+        # Row windows (PlanBuilder.window): a windowed op writes only its window, so the rows outside it must already hold
+        # what an unrestricted run writes there.  They do not depend on the frames, but they do depend on the kernels that
+        # wrote them (the stem's kernel follows the batch) and on the pad colour / LUT behind the tap tables.  So a run is
+        # windowed only if an unrestricted run of at least as many images, with the same kernels and external tables, came
+        # before it; any other run is unrestricted and becomes the new record.  `prime_runs` counts those.
+        self.windows = list(getattr(builder, "windows", ()))
+        self.prime_runs = 0
+        self._primed = None         # (n, key) of the last unrestricted run
+        self._win_key = {}          # n -> (windowed kernels, windows valid at n)
+        self._win_on = True
+        self._set_windows(False)
+
+    def _set_windows(self, on):
+        if on != self._win_on:
+            for i, lo, end in self.windows:
+                self.ops[i].row_lo, self.ops[i].row_end = (lo, end) if on else (0, 0)
+            self._win_on = on
+
+    def _window_choice(self, n):
+        """(names of the kernels the windowed ops launch at batch n, whether the library accepts the windows at n)"""
+        if n not in self._win_key:
+            self._set_windows(True)
+            ok = self.lib.fp_plan_validate(self.ops, self.n_ops, self.weights.numel(), self.arena_floats) == 0
+            self._win_key[n] = (tuple(self.kernel_name(i) for i, _, _ in self.windows), ok)
+        return self._win_key[n]
+
+    def invalidate_windows(self):
+        """The next run is unrestricted (the caller changed something the rows outside the windows depend on)."""
+        self._primed = None
+
+    def _prepare_windows(self):
+        n = self.n_run
+        names, ok = self._window_choice(n)
+        key = (names, tuple(t.data_ptr() for t in self._ext_keep[1:]))    # kernels; tap tables + LUT (external buffer 0 = the frames)
+        on = ok and self._primed is not None and self._primed[1] == key and n <= self._primed[0]
+        self._set_windows(on)
+        if not on:
+            self._primed = (n, key)
+            self.prime_runs += 1
 
     def buf_tensor(self, buf, N):
         """A torch view [N, H, W, C] of an arena buffer (no copy)."""
@@ -1145,6 +1196,8 @@ class CompiledPlan:
     def run(self, n=None):
         if n is not None:
             self.set_batch(n)
+        if self.windows:
+            self._prepare_windows()
         if self._timing is not None:
             return self.run_timed(*self._timing)
         rc = self.lib.fp_plan_run_ext(self.ops, self.n_ops, L.ptr(self.weights), self.weights.numel(),
@@ -1205,6 +1258,11 @@ class CompiledPlan:
               op.res_mode in (L.RES_ADD_BEFORE_ACT, L.RES_ADD_AFTER_ACT, L.RES_SHUFFLE2)):
             b_res = oh * ow * op.res_C * 4                       # a residual that is not the op's own input (the block
                                                                  # ops' shortcut is their input: read once)
+        if op.row_end > 0:      # a row window (the last run's): its rows are written, and the input rows they reach are read
+            if k == L.OP_BLAZEPAIR:
+                lo, end = (op.row_lo - 2, op.row_end + 2) if op.stride == 1 else (2 * op.row_lo - 1, 2 * op.row_end + 2)
+                b_in = b_in * (min(op.H, end) - max(0, lo)) // op.H
+            b_out = b_out * (op.row_end - op.row_lo) // oh
         return n * (b_in + b_out + b_res)
 
     def flops(self, i, n=None):

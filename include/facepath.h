@@ -135,8 +135,23 @@ typedef struct fp_op {
   int32_t act2;                    /* fused ops: activation of the SECOND conv's output (DWPW: FP_ACT_NONE / FP_ACT_SILU) */
   int32_t flags;                   /* FP_OPF_* bits (0 for dense tensors) */
   int32_t Cmid;                    /* ABI 4.  DWBLOCK: channels of the expanded tensor (Depth_Wise `groups`); BLAZECHAIN: number of blocks; 0 elsewhere */
-  int32_t reserved0;               /* ABI 4.  must be 0 */
+  int16_t row_lo, row_end;         /* output row window [row_lo, row_end); 0, 0: the whole map.  See "Row windows" (these two
+                                      halves were ABI 4's reserved0, which had to be 0: the layout and every existing caller are
+                                      unchanged) */
 } fp_op;
+
+/*
+ * Row windows.  An op with row_end > 0 computes output rows row_lo .. row_end - 1 of every image and MAY leave
+ * every other output row as it was: the caller guarantees that those rows already hold what the op would write there
+ * (BlazeFace on letterboxed frames: the rows whose receptive field holds only the canvas pad are the same in every
+ * frame, so one unrestricted run leaves them right for the plan's life).  Rows outside the window are still READ where a
+ * window row's receptive field reaches them.  0 <= row_lo < row_end <= OH; an empty or out-of-range window is
+ * FP_ERR_INVALID_ARG.  Only these ops take a window (anything else with row_end > 0: FP_ERR_UNSUPPORTED):
+ *   FP_OP_STEM_U8 on the 5x5 band kernels (fp_stem_u8_band_eligible: BlazeFace-back's stem, N >= 16) and
+ *   FP_OP_BLAZEPAIR (stride 1 and 2).
+ * A windowed launch spreads the window's rows over its bands (band heights are chosen to fill whole rounds of workgroup
+ * slots); bands may overlap by a few rows, which are then written twice with the same values.
+ */
 
 /*
  * Row-padded activation layout (ABI 3).  A tensor in this layout keeps one ZERO pixel after every image row, one zero

@@ -438,13 +438,11 @@ size_t fp_blazeblock_lds_bytes(int Cin, int Cout) {
   return 4 * (a + (size_t)TM * (Cin + 4) + (size_t)Kpad * Npad + (size_t)10 * Cin);
 }
 
-bool fp_blazeblock_fixed24(const fp_op& op) { return op.Cin == 24 && op.Cout == 24; }
-
-int fp_launch_blazeblock(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
+int fp_launch_blazeblock(const fp_op& op, const fp_launch& L) {
   // op fields: w_off = depthwise weights [9][Cin], scale_off = depthwise bias, slope_off = packed pointwise
   // weights, bias_off = pointwise bias; res_C = channels of the shortcut (= logical Cin).
   if (op.KH != 3 || op.KW != 3 || (op.stride != 1 && op.stride != 2)) return FP_ERR_UNSUPPORTED;
-  if (op.flags & FP_OPF_IN_ROWPAD) return fp_launch_blazeblock_rowpad(op, weights, arena, s);   // blazewp.hip
+  if (op.flags & FP_OPF_IN_ROWPAD) return fp_launch_blazeblock_rowpad(op, L);   // blazewp.hip
   if (op.Cin % 4 || op.Cout % 4 || op.in_ld % 4 || op.in_off % 4 || op.in_ns % 4 || op.out_off % 4) return FP_ERR_ALIGNMENT;
   const bool out_rowpad = (op.flags & FP_OPF_OUT_ROWPAD) != 0;
   if (op.out_cmul != 1 || op.out_ld != op.Cout || (!out_rowpad && op.out_ns != (int64_t)op.OH * op.OW * op.Cout))
@@ -454,6 +452,9 @@ int fp_launch_blazeblock(const fp_op& op, const float* weights, float* arena, hi
   if (op.Cout > 128 || op.res_C > op.Cin || op.OW % 4) return FP_ERR_UNSUPPORTED;
   const size_t lds = fp_blazeblock_lds_bytes(op.Cin, op.Cout);
   if (lds > FP_BLAZEBLOCK_MAX_LDS) return FP_ERR_UNSUPPORTED;  // the planner emits the unfused pair for wider blocks
+  const float* weights = L.weights;
+  float* arena = L.arena;
+  const hipStream_t s = L.s;
   BlazeArgs a;
   a.in = arena + op.in_off;
   a.out = arena + op.out_off;
@@ -483,7 +484,8 @@ int fp_launch_blazeblock(const fp_op& op, const float* weights, float* arena, hi
     int G = 256 * per_cu;
     if (G > a.ntiles) G = a.ntiles;
     if (plds <= 64 * 1024) {
-      const bool w24 = fp_blazeblock_fixed24(op);
+      const bool w24 = op.Cin == 24 && op.Cout == 24;   // instantiated with compile-time widths
+      if (fp_dry_run(L, "blazeblock_persist_kernel<%d, %s>", op.stride, w24 ? "24, 24" : "0, 0")) return FP_OK;
       if (op.stride == 1) {
         if (w24) hipLaunchKernelGGL((blazeblock_persist_kernel<1, 24, 24>), dim3(G), dim3(256), plds, s, a);
         else hipLaunchKernelGGL((blazeblock_persist_kernel<1, 0, 0>), dim3(G), dim3(256), plds, s, a);
@@ -495,6 +497,8 @@ int fp_launch_blazeblock(const fp_op& op, const float* weights, float* arena, hi
       return FP_OK;
     }
   }
+  if (a.Npad > 4 * 32) return FP_ERR_UNSUPPORTED;
+  if (fp_dry_run(L, "blazeblock_kernel<%d>", a.Npad / 32)) return FP_OK;
   dim3 grid((unsigned)a.ntiles), block(256);
 #define FP_BB_CASE(NBV)                                                                                     \
   case NBV:                                                                                                 \
@@ -508,7 +512,6 @@ int fp_launch_blazeblock(const fp_op& op, const float* weights, float* arena, hi
     FP_BB_CASE(2)
     FP_BB_CASE(3)
     FP_BB_CASE(4)
-    default: return FP_ERR_UNSUPPORTED;
   }
 #undef FP_BB_CASE
   FP_CHECK_LAUNCH();

@@ -78,8 +78,7 @@ __global__ __launch_bounds__(512, 1) void blazechain96_kernel(ChainArgs p) {
                                        (lds_ptr)((unsigned char*)(par + (b & 1) * PARP) + wave * 1024), 16, 0, 0);
   };
 
-  // persistent over images: the launcher may start fewer workgroups than images (FP_CHAIN_GRID / co-scheduled plans: a
-  // workgroup owns its CU's LDS, so a capped grid leaves the other CUs to whatever runs beside this kernel)
+  // persistent over images: correct for any grid of at most N workgroups (the launcher starts one per image)
   for (int img_i = blockIdx.x; img_i < p.N; img_i += gridDim.x) {
   const float* in = p.in + fp_uniform((long)img_i * p.in_ns);
   float* out = p.out + fp_uniform((long)img_i * p.out_ns);
@@ -204,7 +203,7 @@ __global__ __launch_bounds__(512, 1) void blazechain96_kernel(ChainArgs p) {
 }  // namespace
 
 // A run of Cmid (1..16) stride-1 96 -> 96 BlazeBlocks on a dense 16 x 16 map (include/facepath.h, BLAZECHAIN).
-bool fp_blazechain_supported(const fp_op& op) {
+static bool blazechain_supported(const fp_op& op) {
   if (op.kind != FP_OP_BLAZECHAIN || op.flags != FP_OPF_SPLIT3) return false;
   if (op.stride != 1 || op.KH != 3 || op.KW != 3 || op.pad_t != 1 || op.pad_l != 1) return false;
   if (op.Cin != C || op.Cout != C || op.in_ld != C || op.out_ld != C || op.out_cmul != 1) return false;
@@ -216,25 +215,23 @@ bool fp_blazechain_supported(const fp_op& op) {
 
 int64_t fp_blazechain_w_floats(const fp_op& op) { return (int64_t)op.Cmid * BLK_F; }
 
-int fp_launch_blazechain(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
-  if (!fp_blazechain_supported(op)) return FP_ERR_UNSUPPORTED;
+int fp_launch_blazechain(const fp_op& op, const fp_launch& L) {
+  if (!blazechain_supported(op)) return FP_ERR_UNSUPPORTED;
+  if (fp_dry_run(L, "blazechain96_kernel")) return FP_OK;
   ChainArgs a;
-  a.in = arena + op.in_off;
-  a.out = arena + op.out_off;
-  a.w = weights + op.w_off;
+  a.in = L.arena + op.in_off;
+  a.out = L.arena + op.out_off;
+  a.w = L.weights + op.w_off;
   a.in_ns = op.in_ns;
   a.out_ns = op.out_ns;
   a.nblk = op.Cmid;
   a.N = op.N;
-  int grid = op.N;
-  const int cap = fp_get_knobs().chain_grid;           // lab: cap the number of workgroups (= CUs this kernel occupies)
-  if (cap > 0 && cap < grid) grid = cap;
   const hipError_t ae = hipFuncSetAttribute((const void*)blazechain96_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
   if (ae != hipSuccess) {
     fp_set_hip_error(ae);
     return FP_ERR_LAUNCH;
   }
-  hipLaunchKernelGGL(blazechain96_kernel, dim3(grid), dim3(512), LDS_BYTES, s, a);
+  hipLaunchKernelGGL(blazechain96_kernel, dim3(op.N), dim3(512), LDS_BYTES, L.s, a);
   FP_CHECK_LAUNCH();
   return FP_OK;
 }

@@ -285,16 +285,16 @@ __global__ __launch_bounds__(256, 2) void blazepair_kernel(BlazePairArgs p) {
 }
 
 template <int W>
-int launch_pair(const BlazePairArgs& a, hipStream_t s) {
+int launch_pair(const BlazePairArgs& a, const fp_launch& L) {
   constexpr int C = 24, NSUB = 4 / (W / 32);
-  size_t lds = 4 * ((size_t)2 * 10 * C + 64 + (size_t)NSUB * 4 * (W + 2) * C + 4 * (size_t)32 * (C + 4));
-  if ((size_t)fp_get_knobs().pair_lds_min > lds) lds = (size_t)fp_get_knobs().pair_lds_min;      // lab knob, 0 in the product
+  if (fp_dry_run(L, "blazepair_kernel<%d>", W)) return FP_OK;
+  const size_t lds = 4 * ((size_t)2 * 10 * C + 64 + (size_t)NSUB * 4 * (W + 2) * C + 4 * (size_t)32 * (C + 4));
   const hipError_t ae = hipFuncSetAttribute((const void*)blazepair_kernel<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (ae != hipSuccess) {
     fp_set_hip_error(ae);
     return FP_ERR_LAUNCH;
   }
-  hipLaunchKernelGGL((blazepair_kernel<W>), dim3(fp_ceil_div(a.nbands, NSUB)), dim3(256), lds, s, a);
+  hipLaunchKernelGGL((blazepair_kernel<W>), dim3(fp_ceil_div(a.nbands, NSUB)), dim3(256), lds, L.s, a);
   FP_CHECK_LAUNCH();
   return FP_OK;
 }
@@ -306,7 +306,7 @@ int launch_pair(const BlazePairArgs& a, hipStream_t s) {
 #ifndef FP_PAIR_MAX_ROWS
 #define FP_PAIR_MAX_ROWS 64
 #endif
-int fp_blazepair_band_rows(const fp_op& op) {
+static int blazepair_band_rows(const fp_op& op) {
   const int nsub = 4 / (op.W / 32);
   int best = 0;
   for (int r = 8; r <= FP_PAIR_MAX_ROWS && 2 * r <= op.H; r += 4) {      // at least two bands per image (the kernel's band index math)
@@ -317,7 +317,7 @@ int fp_blazepair_band_rows(const fp_op& op) {
 }
 
 // Two stride-1 24 -> 24 blocks on a row-padded 128- or 64-pixel-wide map (include/facepath.h, BLAZEPAIR).
-bool fp_blazepair_supported(const fp_op& op) {
+static bool blazepair_supported(const fp_op& op) {
   if (op.kind != FP_OP_BLAZEPAIR || !(op.flags & FP_OPF_IN_ROWPAD)) return false;
   if (op.stride != 1 || op.KH != 3 || op.KW != 3 || op.pad_t != 1 || op.pad_l != 1) return false;
   if (op.Cin != 24 || op.Cout != 24 || op.in_ld != 24 || op.out_ld != 24 || op.out_cmul != 1) return false;
@@ -325,12 +325,14 @@ bool fp_blazepair_supported(const fp_op& op) {
   if (op.in_off % 4 || op.out_off % 4 || op.in_ns % 4 || op.out_ns % 4) return false;
   if (op.w_off % 4 || op.scale_off % 4 || op.slope_off % 4 || op.bias_off % 4) return false;
   if (op.res_mode != FP_RES_ADD_BEFORE_ACT || op.act != FP_ACT_RELU) return false;
-  const int r = fp_blazepair_band_rows(op);
+  const int r = blazepair_band_rows(op);
   return r > 0 && op.H / r >= 2;
 }
 
-int fp_launch_blazepair(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
-  if (!fp_blazepair_supported(op)) return FP_ERR_UNSUPPORTED;
+int fp_launch_blazepair(const fp_op& op, const fp_launch& L) {
+  if (!blazepair_supported(op)) return FP_ERR_UNSUPPORTED;
+  const float* weights = L.weights;
+  float* arena = L.arena;
   constexpr int C = 24;
   BlazePairArgs a;
   a.in = arena + op.in_off;
@@ -348,7 +350,7 @@ int fp_launch_blazepair(const fp_op& op, const float* weights, float* arena, hip
     a.lo = op.row_lo;
     a.span = rows - a.R;
   } else {
-    a.R = fp_blazepair_band_rows(op);
+    a.R = blazepair_band_rows(op);
     a.bands = op.H / a.R;
     a.lo = 0;
     a.span = op.H - a.R;
@@ -359,5 +361,5 @@ int fp_launch_blazepair(const fp_op& op, const float* weights, float* arena, hip
   a.in_ns = op.in_ns;
   a.out_ns = op.out_ns;
   a.bands_div = fp_make_divisor((unsigned)a.bands);
-  return op.W == 128 ? launch_pair<128>(a, s) : launch_pair<64>(a, s);
+  return op.W == 128 ? launch_pair<128>(a, L) : launch_pair<64>(a, L);
 }

@@ -269,8 +269,9 @@ __global__ __launch_bounds__(256, 2) void blazepair_s2_kernel(BlazePairS2Args p)
 }
 
 template <int W, int C2>
-int launch_pair_s2(const BlazePairS2Args& a, hipStream_t s) {
+int launch_pair_s2(const BlazePairS2Args& a, const fp_launch& L) {
   constexpr int C = 24, NSUB = 4 / (W / 32), NS2 = W / 64;
+  if (fp_dry_run(L, "blazepair_s2_kernel<%d, %d>", W, C2)) return FP_OK;
   const size_t lds = 4 * ((size_t)2 * 10 * C + 96 + (size_t)NSUB * 4 * (W + 2) * C + 4 * (size_t)32 * (C + 4) +
                           (C2 > C ? (size_t)NSUB * NS2 * 32 * C2 : 0));
   const hipError_t ae = hipFuncSetAttribute((const void*)blazepair_s2_kernel<W, C2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -278,7 +279,7 @@ int launch_pair_s2(const BlazePairS2Args& a, hipStream_t s) {
     fp_set_hip_error(ae);
     return FP_ERR_LAUNCH;
   }
-  hipLaunchKernelGGL((blazepair_s2_kernel<W, C2>), dim3(fp_ceil_div(a.nbands, NSUB)), dim3(256), lds, s, a);
+  hipLaunchKernelGGL((blazepair_s2_kernel<W, C2>), dim3(fp_ceil_div(a.nbands, NSUB)), dim3(256), lds, L.s, a);
   FP_CHECK_LAUNCH();
   return FP_OK;
 }
@@ -287,7 +288,7 @@ int launch_pair_s2(const BlazePairS2Args& a, hipStream_t s) {
 
 // Output rows of y2 per band: the largest divisor of OH that is <= 32 and leaves at least 512 workgroups (two per CU), never
 // below 4 (a band computes 2 R + 1 rows of y1 for its R rows of y2).
-int fp_blazepair_s2_band_rows(const fp_op& op) {
+static int blazepair_s2_band_rows(const fp_op& op) {
   const int nsub = 4 / (op.W / 32);
   int best = 0;
   for (int r = 4; r <= 32 && 2 * r <= op.OH; r += 4) {    // at least two bands per image
@@ -299,7 +300,7 @@ int fp_blazepair_s2_band_rows(const fp_op& op) {
 
 // A stride-1 24 -> 24 block and the stride-2 24 -> 24 / 48 block behind it on a row-padded 128- or 64-pixel-wide map
 // (include/facepath.h, BLAZEPAIR with stride = 2).
-bool fp_blazepair_s2_supported(const fp_op& op) {
+static bool blazepair_s2_supported(const fp_op& op) {
   if (op.kind != FP_OP_BLAZEPAIR || !(op.flags & FP_OPF_IN_ROWPAD) || (op.flags & ~(FP_OPF_IN_ROWPAD | FP_OPF_OUT_ROWPAD))) return false;
   if (op.stride != 2 || op.KH != 3 || op.KW != 3 || op.pad_t != 0 || op.pad_l != 0) return false;
   if (op.Cin != 24 || (op.Cout != 24 && op.Cout != 48) || op.in_ld != 24 || op.out_ld != op.Cout || op.out_cmul != 1) return false;
@@ -307,11 +308,13 @@ bool fp_blazepair_s2_supported(const fp_op& op) {
   if (op.in_off % 4 || op.out_off % 4 || op.in_ns % 4 || op.out_ns % 4) return false;
   if (op.w_off % 4 || op.scale_off % 4 || op.slope_off % 4 || op.bias_off % 4) return false;
   if (op.res_mode != FP_RES_POOL2_BEFORE_ACT || op.act != FP_ACT_RELU) return false;
-  return fp_blazepair_s2_band_rows(op) > 0;
+  return blazepair_s2_band_rows(op) > 0;
 }
 
-int fp_launch_blazepair_s2(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
-  if (!fp_blazepair_s2_supported(op)) return FP_ERR_UNSUPPORTED;
+int fp_launch_blazepair_s2(const fp_op& op, const fp_launch& L) {
+  if (!blazepair_s2_supported(op)) return FP_ERR_UNSUPPORTED;
+  const float* weights = L.weights;
+  float* arena = L.arena;
   BlazePairS2Args a;
   a.in = arena + op.in_off;
   a.out = arena + op.out_off;
@@ -329,7 +332,7 @@ int fp_launch_blazepair_s2(const fp_op& op, const float* weights, float* arena, 
     a.lo = op.row_lo;
     a.span = rows - a.R;
   } else {
-    a.R = fp_blazepair_s2_band_rows(op);
+    a.R = blazepair_s2_band_rows(op);
     a.bands = op.OH / a.R;
     a.lo = 0;
     a.span = op.OH - a.R;
@@ -339,7 +342,7 @@ int fp_launch_blazepair_s2(const fp_op& op, const float* weights, float* arena, 
   a.out_rp = (op.OW + ((op.flags & FP_OPF_OUT_ROWPAD) ? 1 : 0)) * op.Cout;
   a.in_ns = op.in_ns;
   a.out_ns = op.out_ns;
-  a.bands_div = fp_make_divisor((unsigned)a.bands);      // >= 2 by fp_blazepair_s2_band_rows
-  if (op.Cout == 24) return op.W == 128 ? launch_pair_s2<128, 24>(a, s) : launch_pair_s2<64, 24>(a, s);
-  return op.W == 128 ? launch_pair_s2<128, 48>(a, s) : launch_pair_s2<64, 48>(a, s);
+  a.bands_div = fp_make_divisor((unsigned)a.bands);      // >= 2 by blazepair_s2_band_rows
+  if (op.Cout == 24) return op.W == 128 ? launch_pair_s2<128, 24>(a, L) : launch_pair_s2<64, 24>(a, L);
+  return op.W == 128 ? launch_pair_s2<128, 48>(a, L) : launch_pair_s2<64, 48>(a, L);
 }

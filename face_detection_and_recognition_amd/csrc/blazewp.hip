@@ -418,7 +418,7 @@ __global__ __launch_bounds__(256, C <= 48 ? 2 : 1) void blazeblock_wps_kernel(Bl
 }  // namespace
 
 // Wave-private kernel: stride 1, 24 -> 24 with the full shortcut, rows that split into 32-pixel tiles, row-padded input.
-bool fp_blazeblock_wp_eligible(const fp_op& op) {
+static bool blazeblock_wp_eligible(const fp_op& op) {
   return op.kind == FP_OP_BLAZEBLOCK && (op.flags & FP_OPF_IN_ROWPAD) && op.stride == 1 && op.KH == 3 && op.KW == 3 &&
          op.Cin == 24 && op.Cout == 24 && op.res_C == 24 && op.in_ld == 24 && op.out_ld == 24 && op.out_cmul == 1 &&
          op.OH == op.H && op.OW == op.W && op.OW % 32 == 0 && op.OW >= 64 && op.OH % 4 == 0 && op.OH >= 8 &&
@@ -427,7 +427,7 @@ bool fp_blazeblock_wp_eligible(const fp_op& op) {
 }
 
 // Wide blocks on small maps: stride 1, C -> C with C = 48 or 96, 16- or 32-pixel-wide maps, row-padded input.
-bool fp_blazeblock_wps_eligible(const fp_op& op) {
+static bool blazeblock_wps_eligible(const fp_op& op) {
   return op.kind == FP_OP_BLAZEBLOCK && (op.flags & FP_OPF_IN_ROWPAD) && op.stride == 1 && op.KH == 3 && op.KW == 3 &&
          (op.Cin == 48 || op.Cin == 96) && op.Cout == op.Cin && op.res_C == op.Cin && op.in_ld == op.Cin &&
          op.out_ld == op.Cin && op.out_cmul == 1 && op.OH == op.H && op.OW == op.W && (op.W == 16 || op.W == 32) &&
@@ -436,7 +436,11 @@ bool fp_blazeblock_wps_eligible(const fp_op& op) {
 }
 
 template <int C>
-static int launch_blazeblock_wps(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
+static int launch_blazeblock_wps(const fp_op& op, const fp_launch& L) {
+  if (fp_dry_run(L, "blazeblock_wps_kernel<%d>", C)) return FP_OK;
+  const float* weights = L.weights;
+  float* arena = L.arena;
+  const hipStream_t s = L.s;
   constexpr int NPAD = (C + 31) / 32 * 32;
   BlazeWpsArgs a;
   a.in = arena + op.in_off;
@@ -468,10 +472,14 @@ static int launch_blazeblock_wps(const fp_op& op, const float* weights, float* a
   return FP_OK;
 }
 
-static int launch_blazeblock_wp(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
+static int launch_blazeblock_wp(const fp_op& op, const fp_launch& L) {
   // R = 8 (7.5 instead of 9 window loads per row) measured the same within noise on 128 x 128 maps and 6 % faster on
   // 64 x 64 ones, against twice the code: R = 4 everywhere
   constexpr int C = 24, R = 4;
+  if (fp_dry_run(L, "blazeblock_wp_kernel<%d, %d>", C, R)) return FP_OK;
+  const float* weights = L.weights;
+  float* arena = L.arena;
+  const hipStream_t s = L.s;
   BlazeWpArgs a;
   a.in = arena + op.in_off;
   a.out = arena + op.out_off;
@@ -497,11 +505,9 @@ static int launch_blazeblock_wp(const fp_op& op, const float* weights, float* ar
   return FP_OK;
 }
 
-// Row-padded input: dispatch to the kernel that takes the shape (FP_ERR_UNSUPPORTED otherwise; fp_plan_validate checks
-// the same predicates on the host).
-int fp_launch_blazeblock_rowpad(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
-  if (fp_blazeblock_wp_eligible(op)) return launch_blazeblock_wp(op, weights, arena, s);
-  if (fp_blazeblock_wps_eligible(op))
-    return op.Cin == 48 ? launch_blazeblock_wps<48>(op, weights, arena, s) : launch_blazeblock_wps<96>(op, weights, arena, s);
+// Row-padded input: dispatch to the kernel that takes the shape (FP_ERR_UNSUPPORTED otherwise).
+int fp_launch_blazeblock_rowpad(const fp_op& op, const fp_launch& L) {
+  if (blazeblock_wp_eligible(op)) return launch_blazeblock_wp(op, L);
+  if (blazeblock_wps_eligible(op)) return op.Cin == 48 ? launch_blazeblock_wps<48>(op, L) : launch_blazeblock_wps<96>(op, L);
   return FP_ERR_UNSUPPORTED;
 }

@@ -1,5 +1,6 @@
 // capi.cpp — plan validation + executor and the small ABI utilities of libfacepath.so.
 // Compiled by hipcc as host code; kernels live in the .hip files.
+#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -14,24 +15,53 @@ void fp_set_hip_error(hipError_t e) {
   g_hip_err[sizeof(g_hip_err) - 1] = 0;
 }
 
-static int env_int(const char* name) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : 0;
-}
 static fp_knobs read_knobs() {
   fp_knobs k;
-  k.chain_grid = env_int("FP_CHAIN_GRID");
   k.resize_per_pixel = getenv("FP_RESIZE_PER_PIXEL") != nullptr;
-  k.x6_quarter14 = env_int("FP_X6_QUARTER14");
-  k.x6_spec14 = env_int("FP_X6_SPEC14");
-  k.pwx6_small_maxk = env_int("FP_PWX6_SMALL_MAXK");
-  k.pair_lds_min = env_int("FP_PAIR_LDS_MIN");
-  k.x6_lds_min = env_int("FP_X6_LDS_MIN");
-  k.shuf_ldsw = env_int("FP_SHUF_LDSW");
   return k;
 }
 static fp_knobs g_knobs = read_knobs();
 const fp_knobs& fp_get_knobs() { return g_knobs; }
+
+bool fp_dry_run(const fp_launch& L, const char* fmt, ...) {
+  if (!L.dry) return false;
+  if (L.name) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(L.name, FP_KERNEL_NAME_MAX, fmt, ap);
+    va_end(ap);
+  }
+  return true;
+}
+
+static int launch_op(const fp_op& op, const fp_launch& L) {
+  switch (op.kind) {
+    case FP_OP_CONV: return fp_launch_conv(op, L);
+    case FP_OP_DWCONV: return fp_launch_dwconv(op, L);
+    case FP_OP_MAXPOOL: return fp_launch_maxpool(op, L);
+    case FP_OP_UPSAMPLE2X: return fp_launch_upsample2x(op, L);
+    case FP_OP_COPY: return fp_launch_copy(op, L);
+    case FP_OP_L2NORM: return fp_launch_l2norm(op, L);
+    case FP_OP_BLAZEBLOCK: return fp_launch_blazeblock(op, L);
+    case FP_OP_DWPW: return (op.flags & FP_OPF_SPLIT3) ? fp_launch_dwpwx6(op, L) : fp_launch_dwpw(op, L);
+    case FP_OP_DWBLOCK: return (op.flags & FP_OPF_SPLIT3) ? fp_launch_dwblock_x6(op, L) : fp_launch_dwblock(op, L);
+    case FP_OP_BLAZEPAIR: return op.stride == 2 ? fp_launch_blazepair_s2(op, L) : fp_launch_blazepair(op, L);
+    case FP_OP_BLAZECHAIN: return fp_launch_blazechain(op, L);
+    case FP_OP_SHUFDOWN: return fp_launch_shufdown(op, L);
+    case FP_OP_SHUFUNIT: return fp_launch_shufunit(op, L);
+    case FP_OP_YSTEM2: return fp_launch_ystem2(op, L);
+    case FP_OP_YSTEM: return fp_launch_ystem(op, L);
+    case FP_OP_YSTEM_U8: return fp_launch_ystem_u8(op, L);
+    case FP_OP_STEM_U8: return fp_launch_stem_u8(op, L);
+    default: return FP_ERR_UNSUPPORTED;
+  }
+}
+
+// The launcher's dry run (common.h fp_launch): its status, and with `name` the kernel instance it would launch.
+static int dry_run(const fp_op& op, char* name) {
+  const fp_launch L = {nullptr, nullptr, nullptr, 0, nullptr, true, name};
+  return launch_op(op, L);
+}
 
 extern "C" {
 
@@ -102,8 +132,9 @@ static int validate_op(const fp_op& op, size_t weight_floats, size_t arena_float
                     op.kind == FP_OP_SHUFDOWN || op.kind == FP_OP_SHUFUNIT || op.kind == FP_OP_YSTEM2 || ext_in) ? op.Cout : op.Cin;
   if (op.kind != FP_OP_DWBLOCK && op.kind != FP_OP_BLAZECHAIN && op.kind != FP_OP_SHUFDOWN && op.kind != FP_OP_SHUFUNIT && op.Cmid != 0) return FP_ERR_INVALID_ARG;
   if (op.row_lo != 0 || op.row_end != 0) {
-    // a row window (facepath.h "Row windows"): only the kernels that take one, never empty, inside the output map
-    if (!(op.kind == FP_OP_BLAZEPAIR || (op.kind == FP_OP_STEM_U8 && fp_stem_u8_band_eligible(op)))) return FP_ERR_UNSUPPORTED;
+    // a row window (facepath.h "Row windows"): only the kernels that take one (of the u8 stems, the launcher refuses it
+    // outside the band kernel), never empty, inside the output map
+    if (op.kind != FP_OP_BLAZEPAIR && op.kind != FP_OP_STEM_U8) return FP_ERR_UNSUPPORTED;
     if (op.row_lo < 0 || op.row_end <= op.row_lo || op.row_end > OH) return FP_ERR_INVALID_ARG;
   }
   if (Cout <= 0 || op.out_cmul < 1 || op.in_ld < op.Cin) return FP_ERR_INVALID_ARG;
@@ -113,14 +144,12 @@ static int validate_op(const fp_op& op, size_t weight_floats, size_t arena_float
   if (op.flags & FP_OPF_OUT_DW) {
     // Mobile-FaceNet's conv1 + conv2_dw (facepath.h): the conv's slopes are followed by the depthwise block's [12][Cout]
     if (op.kind != FP_OP_CONV) return FP_ERR_INVALID_ARG;
-    if (!fp_stemdw_supported(op)) return FP_ERR_UNSUPPORTED;
     if (!span_ok(op.slope_off, 13 * (int64_t)op.Cout, weight_floats)) return FP_ERR_BOUNDS;
     if (!span_ok(op.w_off, fp_stemdw_w_floats(op), weight_floats)) return FP_ERR_BOUNDS;
   }
   if (op.flags & FP_OPF_IN_UP2) {
     // channels [0, res_C) come from the res view at half resolution (facepath.h): only the split-MFMA pointwise kernel reads that
     if (op.kind != FP_OP_CONV || !(op.flags & FP_OPF_SPLIT3)) return FP_ERR_INVALID_ARG;
-    if (!fp_pwx6_eligible(op) && !fp_convx6_eligible(op)) return FP_ERR_UNSUPPORTED;
     const int64_t up_ext = (int64_t)(op.N - 1) * op.res_ns + ((int64_t)op.res_H * op.res_W - 1) * op.res_ld + op.res_C;
     if (!span_ok(op.res_off, up_ext, arena_floats)) return FP_ERR_BOUNDS;
   }
@@ -128,24 +157,25 @@ static int validate_op(const fp_op& op, size_t weight_floats, size_t arena_float
   if ((op.flags & FP_OPF_SPLIT3) && op.kind != FP_OP_DWBLOCK && op.kind != FP_OP_CONV && op.kind != FP_OP_DWPW && op.kind != FP_OP_BLAZECHAIN &&
       op.kind != FP_OP_SHUFDOWN && op.kind != FP_OP_SHUFUNIT && op.kind != FP_OP_YSTEM2 && op.kind != FP_OP_STEM_U8)
     return FP_ERR_INVALID_ARG;
-  if ((op.flags & FP_OPF_SPLIT3) && op.kind == FP_OP_STEM_U8 && !fp_stem_u8_band_eligible(op)) return FP_ERR_UNSUPPORTED;
-  if ((op.flags & FP_OPF_SPLIT3) && op.kind == FP_OP_DWPW && !fp_dwpwx6_eligible(op)) return FP_ERR_UNSUPPORTED;
-  if ((op.flags & FP_OPF_SPLIT3) && op.kind == FP_OP_CONV && !(op.flags & FP_OPF_OUT_DW) && !fp_pwx6_eligible(op) && !fp_convx6_eligible(op))
-    return FP_ERR_UNSUPPORTED;
   if ((op.flags & FP_OPF_IN_C3) && (op.Cin != 4 || (op.kind != FP_OP_CONV && op.kind != FP_OP_YSTEM)))
     return FP_ERR_INVALID_ARG;
   const bool in_rp = (op.flags & FP_OPF_IN_ROWPAD) != 0, out_rp = (op.flags & FP_OPF_OUT_ROWPAD) != 0;
-  if (in_rp && !fp_blazeblock_wp_eligible(op) && !fp_blazeblock_wps_eligible(op) && !fp_blazepair_supported(op) &&
-      !fp_blazepair_s2_supported(op))
-    return FP_ERR_UNSUPPORTED;
+  if (in_rp && op.kind != FP_OP_BLAZEBLOCK && op.kind != FP_OP_BLAZEPAIR) return FP_ERR_UNSUPPORTED;
   if (out_rp && !(op.kind == FP_OP_BLAZEBLOCK || op.kind == FP_OP_BLAZEPAIR || op.kind == FP_OP_STEM_U8 || op.kind == FP_OP_COPY ||
-                  (op.kind == FP_OP_CONV && fp_stem_eligible(op))))
+                  op.kind == FP_OP_CONV))
     return FP_ERR_UNSUPPORTED;
   if (out_rp && (op.out_cmul != 1 || op.out_ld != Cout)) return FP_ERR_UNSUPPORTED;
-  // a row-padded COPY exists only in its 16-byte form (copy4_kernel); the scalar copy would fail at launch
-  if (out_rp && op.kind == FP_OP_COPY &&
-      (op.Cin % 4 || op.in_ld % 4 || op.out_ld % 4 || op.in_off % 4 || op.out_off % 4 || op.in_ns % 4 || op.out_ns % 4))
-    return FP_ERR_UNSUPPORTED;
+  if (op.kind == FP_OP_CONV || op.kind == FP_OP_DWCONV || op.kind == FP_OP_MAXPOOL || op.kind == FP_OP_BLAZEBLOCK ||
+      op.kind == FP_OP_DWPW || op.kind == FP_OP_DWBLOCK || op.kind == FP_OP_BLAZEPAIR || op.kind == FP_OP_BLAZECHAIN ||
+      op.kind == FP_OP_YSTEM || op.kind == FP_OP_SHUFDOWN || op.kind == FP_OP_SHUFUNIT || op.kind == FP_OP_YSTEM2 || ext_in) {
+    if (op.KH <= 0 || op.KW <= 0 || op.stride <= 0 || op.pad_t < 0 || op.pad_l < 0) return FP_ERR_INVALID_ARG;
+    // every output pixel must have at least its first tap row/col addressable without overflow of int math
+    if ((int64_t)(OH - 1) * op.stride - op.pad_t >= op.H || (int64_t)(OW - 1) * op.stride - op.pad_l >= op.W)
+      return FP_ERR_INVALID_ARG;
+  }
+  // what the kernel itself requires: the launcher's checks, in a dry run
+  const int rc = dry_run(op, nullptr);
+  if (rc != FP_OK) return rc;
   // input extent
   if (in_rp) {
     const int64_t lead = (int64_t)(op.W + 2) * op.in_ld;
@@ -169,14 +199,6 @@ static int validate_op(const fp_op& op, size_t weight_floats, size_t arena_float
   }
   if (op.in_ns < 0 || op.out_ns < 0) return FP_ERR_INVALID_ARG;
 
-  if (op.kind == FP_OP_CONV || op.kind == FP_OP_DWCONV || op.kind == FP_OP_MAXPOOL || op.kind == FP_OP_BLAZEBLOCK ||
-      op.kind == FP_OP_DWPW || op.kind == FP_OP_DWBLOCK || op.kind == FP_OP_BLAZEPAIR || op.kind == FP_OP_BLAZECHAIN ||
-      op.kind == FP_OP_YSTEM || op.kind == FP_OP_SHUFDOWN || op.kind == FP_OP_SHUFUNIT || op.kind == FP_OP_YSTEM2 || ext_in) {
-    if (op.KH <= 0 || op.KW <= 0 || op.stride <= 0 || op.pad_t < 0 || op.pad_l < 0) return FP_ERR_INVALID_ARG;
-    // every output pixel must have at least its first tap row/col addressable without overflow of int math
-    if ((int64_t)(OH - 1) * op.stride - op.pad_t >= op.H || (int64_t)(OW - 1) * op.stride - op.pad_l >= op.W)
-      return FP_ERR_INVALID_ARG;
-  }
   if (op.kind == FP_OP_CONV || op.kind == FP_OP_BLAZEBLOCK || op.kind == FP_OP_STEM_U8) {
     int64_t wext;
     if (op.kind != FP_OP_BLAZEBLOCK) {
@@ -208,20 +230,16 @@ static int validate_op(const fp_op& op, size_t weight_floats, size_t arena_float
     if (op.act != FP_ACT_NONE && op.act != FP_ACT_PRELU) return FP_ERR_INVALID_ARG;
     // bias_off: optional [Cout4] PReLU slopes of the projection output
     if (op.bias_off >= 0 && !span_ok(op.bias_off, (op.Cout + 3) / 4 * 4, weight_floats)) return FP_ERR_BOUNDS;
-    if (op.bias_off >= 0 && op.res_mode != FP_RES_NONE) return FP_ERR_UNSUPPORTED;
     if (op.act2 != FP_ACT_NONE && op.act2 != FP_ACT_SILU) return FP_ERR_INVALID_ARG;
   } else if (op.kind == FP_OP_SHUFDOWN) {
-    // one parameter block at w_off (facepath.h SHUFDOWN); the shapes the kernel exists for are fp_shufdown_supported's
-    if (!fp_shufdown_supported(op)) return FP_ERR_UNSUPPORTED;
+    // one parameter block at w_off (facepath.h SHUFDOWN)
     if (!span_ok(op.w_off, fp_shufdown_w_floats(op), weight_floats)) return FP_ERR_BOUNDS;
   } else if (op.kind == FP_OP_YSTEM2) {
     // parameter block at w_off, the pooled map in the res view (facepath.h YSTEM2)
-    if (!fp_ystem2_supported(op)) return FP_ERR_UNSUPPORTED;
     if (!span_ok(op.w_off, fp_ystem2_w_floats(op), weight_floats)) return FP_ERR_BOUNDS;
     const int64_t res_ext = (int64_t)(op.N - 1) * op.res_ns + ((int64_t)op.OH * op.OW - 1) * op.res_ld + op.res_C;
     if (!span_ok(op.res_off, res_ext, arena_floats)) return FP_ERR_BOUNDS;
   } else if (op.kind == FP_OP_SHUFUNIT) {
-    if (!fp_shufunit_supported(op)) return FP_ERR_UNSUPPORTED;
     if (!span_ok(op.w_off, fp_shufunit_w_floats(op), weight_floats)) return FP_ERR_BOUNDS;
   } else if (op.act2 != FP_ACT_NONE) {
     return FP_ERR_INVALID_ARG;
@@ -229,7 +247,6 @@ static int validate_op(const fp_op& op, size_t weight_floats, size_t arena_float
   if (op.kind == FP_OP_BLAZEPAIR) {
     // both blocks' parameters back to back (facepath.h BLAZEPAIR)
     // stride 2: the second block is the stride-2 block behind a stride-1 block (24 -> 24 or 24 -> 48; blazepairs2.hip)
-    if (op.stride == 2 ? !fp_blazepair_s2_supported(op) : !fp_blazepair_supported(op)) return FP_ERR_UNSUPPORTED;
     const int64_t pw2 = op.stride == 2 && op.Cout == 48 ? 2 * 768 : 768, c2 = op.stride == 2 ? op.Cout : 24;
     if (!span_ok(op.w_off, 2 * 9 * 24, weight_floats) || !span_ok(op.scale_off, 2 * 24, weight_floats) ||
         !span_ok(op.slope_off, 768 + pw2, weight_floats) || !span_ok(op.bias_off, 24 + c2, weight_floats))
@@ -237,15 +254,13 @@ static int validate_op(const fp_op& op, size_t weight_floats, size_t arena_float
   }
   if (op.kind == FP_OP_BLAZECHAIN) {
     // Cmid blocks back to back at w_off, each [1280 fp32 parameters][3 slabs of split 1x1 weights] (facepath.h BLAZECHAIN)
-    if (!fp_blazechain_supported(op)) return FP_ERR_UNSUPPORTED;
     if (!span_ok(op.w_off, fp_blazechain_w_floats(op), weight_floats)) return FP_ERR_BOUNDS;
   }
   if (op.kind == FP_OP_DWBLOCK) {
     // w_off: expand packed as CONV (K = Cin, Npad = Cmid); scale_off: [15][Cmid]; slope_off: project packed as CONV
-    // (K = Cmid, Npad = Cout) + [Cout] scale + [Cout] bias.  The shapes the kernel exists for are fp_dwblock_supported's.
+    // (K = Cmid, Npad = Cout) + [Cout] scale + [Cout] bias.
     // FP_OPF_SPLIT3: both weight matrices as three bf16 planes (1.5 floats per weight), see facepath.h
     const bool x6 = (op.flags & FP_OPF_SPLIT3) != 0;
-    if (!(x6 ? fp_dwblock_x6_supported(op) : fp_dwblock_supported(op))) return FP_ERR_UNSUPPORTED;
     if (!span_ok(op.w_off, x6 ? fp_dwblock_x6_we_floats(op) : (int64_t)op.Cin * op.Cmid, weight_floats)) return FP_ERR_BOUNDS;
     if (!span_ok(op.scale_off, 15 * (int64_t)op.Cmid, weight_floats)) return FP_ERR_BOUNDS;
     if ((op.flags & FP_OPF_IN_DW) && !span_ok(op.bias_off, 12 * (int64_t)op.Cin, weight_floats)) return FP_ERR_BOUNDS;
@@ -262,8 +277,6 @@ static int validate_op(const fp_op& op, size_t weight_floats, size_t arena_float
     const int64_t res_ext = (int64_t)(op.N - 1) * op.res_ns + ((int64_t)(op.OH / 2) * (op.OW / 2) - 1) * op.res_ld + op.res_C;
     if (!span_ok(op.res_off, res_ext, arena_floats)) return FP_ERR_BOUNDS;
   }
-  if (op.kind == FP_OP_STEM_U8 && (op.Cin != 3 || op.res_H <= 0 || op.res_W < 3 || !fp_stem_u8_shape_ok(op)))
-    return FP_ERR_UNSUPPORTED;
   if (op.kind == FP_OP_CONV || op.kind == FP_OP_DWCONV || op.kind == FP_OP_STEM_U8) {
     if (op.scale_off >= 0 && !span_ok(op.scale_off, Cout, weight_floats)) return FP_ERR_BOUNDS;
     if (op.bias_off >= 0 && !span_ok(op.bias_off, Cout, weight_floats)) return FP_ERR_BOUNDS;
@@ -287,128 +300,15 @@ static int validate_op(const fp_op& op, size_t weight_floats, size_t arena_float
     const int64_t res_ext = (int64_t)(op.N - 1) * op.res_ns + ((int64_t)rh * rw - 1) * op.res_ld + op.res_C;
     if (!span_ok(op.res_off, res_ext, arena_floats)) return FP_ERR_BOUNDS;
   }
-  switch (op.kind) {
-    case FP_OP_CONV:
-    case FP_OP_DWCONV:
-    case FP_OP_MAXPOOL:
-    case FP_OP_UPSAMPLE2X:
-    case FP_OP_COPY:
-    case FP_OP_L2NORM:
-    case FP_OP_BLAZEBLOCK:
-    case FP_OP_DWPW:
-    case FP_OP_DWBLOCK:
-    case FP_OP_BLAZEPAIR:
-    case FP_OP_BLAZECHAIN:
-    case FP_OP_YSTEM:
-    case FP_OP_YSTEM_U8:
-    case FP_OP_STEM_U8:
-    case FP_OP_SHUFDOWN:
-    case FP_OP_SHUFUNIT:
-    case FP_OP_YSTEM2:
-      return FP_OK;
-    default:
-      return FP_ERR_UNSUPPORTED;
-  }
+  return FP_OK;
 }
 
-// Name of the HIP kernel an op launches (the family rocprofv3's kernel trace shows), for measurement tools.
+// Name of the HIP kernel an op launches (the family rocprofv3's kernel trace shows), for measurement tools: the
+// launcher's own choice, "?" for an op it refuses.
 const char* fp_op_kernel_name(const fp_op* op) {
-  static thread_local char buf[64];
-  if (!op) return "?";
-  switch (op->kind) {
-    case FP_OP_CONV: {
-      if (op->flags & FP_OPF_OUT_DW) return (op->flags & FP_OPF_SPLIT3) ? "stemdw_kernel<true>" : "stemdw_kernel<false>";
-      if (op->flags & FP_OPF_SPLIT3) {
-        if (fp_pwx6_eligible(*op))
-          snprintf(buf, sizeof(buf), "pwx6_kernel<%d, %d, %s>", op->Cout == 48 ? 3 : op->Cout == 64 ? 4 : 8, fp_pwx6_mt(*op),
-                   (op->flags & FP_OPF_IN_UP2) ? "true" : "false");
-        else snprintf(buf, sizeof(buf), "convx6_kernel<%d>", fp_convx6_nt16(*op));
-        return buf;
-      }
-      if (fp_pws_eligible(*op)) { snprintf(buf, sizeof(buf), "pws_kernel<%d, %d>", op->Cin, op->Cin == 64 ? 12 : 8); return buf; }
-      if (fp_stem_eligible(*op)) {
-        snprintf(buf, sizeof(buf), "stem_conv_kernel<%d, %d, false>", op->KH, (int)fp_round_up(op->Cout, 32) / 32);
-        return buf;
-      }
-      if (fp_conv3_eligible(*op)) {
-        snprintf(buf, sizeof(buf), "conv3_kernel<%d, %d, %s>", fp_conv3_nb(*op), op->stride, fp_conv3_t16(*op) ? "true" : "false");
-        return buf;
-      }
-      int nb, vec, pwd;
-      fp_conv_variant(*op, &nb, &vec, &pwd);
-      snprintf(buf, sizeof(buf), "conv_igemm_kernel<%d, %s, %s>", nb, vec ? "true" : "false", pwd ? "true" : "false");
-      return buf;
-    }
-    case FP_OP_DWCONV:
-      if (op->KH == 3 && (op->stride == 1 || op->stride == 2)) snprintf(buf, sizeof(buf), "dwconv3_row_kernel<%d>", op->stride);
-      else snprintf(buf, sizeof(buf), "dwconv_kernel<%d>", op->KH);
-      return buf;
-    case FP_OP_MAXPOOL: return "maxpool_kernel";
-    case FP_OP_UPSAMPLE2X: return "upsample2x_kernel";
-    case FP_OP_COPY:
-      return (op->out_cmul == 1 && op->Cin % 4 == 0 && op->in_ld % 4 == 0 && op->out_ld % 4 == 0 && op->in_off % 4 == 0 &&
-              op->out_off % 4 == 0 && op->in_ns % 4 == 0 && op->out_ns % 4 == 0) ? "copy4_kernel" : "copy_kernel";
-    case FP_OP_L2NORM: return "l2norm_kernel";
-    case FP_OP_BLAZEBLOCK:
-      if (op->flags & FP_OPF_IN_ROWPAD) {
-        if (fp_blazeblock_wp_eligible(*op)) return "blazeblock_wp_kernel<24, 4>";
-        snprintf(buf, sizeof(buf), "blazeblock_wps_kernel<%d>", op->Cin);
-        return buf;
-      }
-      if (fp_round_up(op->Cin, 8) <= 32 && fp_round_up(op->Cout, 32) == 32 &&
-          fp_ceil_div((long)op->N * op->OH * op->OW, 128) >= 2048)
-        snprintf(buf, sizeof(buf), "blazeblock_persist_kernel<%d, %s>", op->stride, fp_blazeblock_fixed24(*op) ? "24, 24" : "0, 0");
-      else
-        snprintf(buf, sizeof(buf), "blazeblock_kernel<%d>", (int)fp_round_up(op->Cout, 32) / 32);
-      return buf;
-    case FP_OP_DWPW:
-      if (op->flags & FP_OPF_SPLIT3) { snprintf(buf, sizeof(buf), "dwpwx6_kernel<%d, 4, %d>", op->Cout / 16, op->stride); return buf; }
-      if (fp_dwpw_persistent(*op)) {
-        snprintf(buf, sizeof(buf), fp_dwpw_wave_private(*op) ? "dwpw_wp_kernel<%d, %d, 4>" : "dwpw_persist_kernel<%d, %d>",
-                 (int)fp_round_up(op->Cout, 32) / 32, op->stride);
-        return buf;
-      }
-      snprintf(buf, sizeof(buf), "dwpw_kernel<%d, %d, %d>", (int)fp_round_up(op->Cout, 32) / 32,
-               (op->OW % 4 == 0) ? 4 : (op->OW % 2 == 0) ? 2 : 1, op->stride);
-      return buf;
-    case FP_OP_BLAZECHAIN:
-      snprintf(buf, sizeof(buf), "blazechain96_kernel");
-      return buf;
-    case FP_OP_BLAZEPAIR:
-      if (op->stride == 2) {
-        snprintf(buf, sizeof(buf), "blazepair_s2_kernel<%d, %d>", op->W, op->Cout);
-        return buf;
-      }
-      snprintf(buf, sizeof(buf), "blazepair_kernel<%d>", op->W);
-      return buf;
-    case FP_OP_DWBLOCK:
-      if (op->flags & FP_OPF_SPLIT3) {
-        if (op->stride == 2)
-          snprintf(buf, sizeof(buf), "dwblock_x6d_kernel<%d, %d, %d, %d, %s>", op->Cin, op->Cmid, op->Cout, op->H,
-                   (op->flags & FP_OPF_IN_DW) ? "true" : "false");
-        else if (op->Cin == 128 && op->H == 7) snprintf(buf, sizeof(buf), "dwblock_x6q_kernel<%d>", op->H);
-        else snprintf(buf, sizeof(buf), "dwblock_x6_kernel<%d, %d>", op->Cin, op->H);
-        return buf;
-      }
-      snprintf(buf, sizeof(buf), "dwblock_kernel<%d, %d, %d, %d>", op->Cin, op->H, op->H == 28 ? 7 : op->H, op->H == 7 ? 3 : 1);
-      return buf;
-    case FP_OP_SHUFDOWN:
-      snprintf(buf, sizeof(buf), "shufdown_x6_kernel<%d, %d, %s>", op->Cin / 32, op->Cmid, fp_get_knobs().shuf_ldsw ? "true" : "false");
-      return buf;
-    case FP_OP_SHUFUNIT:
-      snprintf(buf, sizeof(buf), "shufunit_x6_kernel<%d>", op->Cmid);
-      return buf;
-    case FP_OP_YSTEM2: return "ystem2_x6_kernel";
-    case FP_OP_STEM_U8:
-      if (fp_stem_u8_band_eligible(*op)) return (op->flags & FP_OPF_SPLIT3) ? "stem5_u8_x6_kernel" : "stem5_u8_band_kernel";
-      snprintf(buf, sizeof(buf), "stem_conv_kernel<%d, %d, true>", op->KH, (int)fp_round_up(op->Cout, 32) / 32);
-      return buf;
-    case FP_OP_YSTEM:
-    case FP_OP_YSTEM_U8:
-      snprintf(buf, sizeof(buf), "ystem_kernel<%d, %s>", fp_ystem_nb2(*op), op->kind == FP_OP_YSTEM_U8 ? "true" : "false");
-      return buf;
-    default: return "?";
-  }
+  static thread_local char buf[FP_KERNEL_NAME_MAX];
+  if (!op || dry_run(*op, buf) != FP_OK) return "?";
+  return buf;
 }
 
 int fp_plan_validate(const fp_op* ops, int n_ops, size_t weight_floats, size_t arena_floats) {
@@ -420,42 +320,35 @@ int fp_plan_validate(const fp_op* ops, int n_ops, size_t weight_floats, size_t a
   return FP_OK;
 }
 
-static int launch_op(const fp_op& op, const float* weights, float* arena, const fp_ext* ext, int n_ext, hipStream_t s) {
-  switch (op.kind) {
-    case FP_OP_CONV: return fp_launch_conv(op, weights, arena, s);
-    case FP_OP_DWCONV: return fp_launch_dwconv(op, weights, arena, s);
-    case FP_OP_MAXPOOL: return fp_launch_maxpool(op, arena, s);
-    case FP_OP_UPSAMPLE2X: return fp_launch_upsample2x(op, arena, s);
-    case FP_OP_COPY: return fp_launch_copy(op, arena, s);
-    case FP_OP_L2NORM: return fp_launch_l2norm(op, arena, s);
-    case FP_OP_BLAZEBLOCK: return fp_launch_blazeblock(op, weights, arena, s);
-    case FP_OP_DWPW:
-      return (op.flags & FP_OPF_SPLIT3) ? fp_launch_dwpwx6(op, weights, arena, s) : fp_launch_dwpw(op, weights, arena, s);
-    case FP_OP_DWBLOCK:
-      return (op.flags & FP_OPF_SPLIT3) ? fp_launch_dwblock_x6(op, weights, arena, s) : fp_launch_dwblock(op, weights, arena, s);
-    case FP_OP_BLAZEPAIR: return op.stride == 2 ? fp_launch_blazepair_s2(op, weights, arena, s) : fp_launch_blazepair(op, weights, arena, s);
-    case FP_OP_BLAZECHAIN: return fp_launch_blazechain(op, weights, arena, s);
-    case FP_OP_SHUFDOWN: return fp_launch_shufdown(op, weights, arena, s);
-    case FP_OP_SHUFUNIT: return fp_launch_shufunit(op, weights, arena, s);
-    case FP_OP_YSTEM2: return fp_launch_ystem2(op, weights, arena, s);
-    case FP_OP_YSTEM: return fp_launch_ystem(op, weights, arena, s);
-    case FP_OP_YSTEM_U8: return fp_launch_ystem_u8(op, weights, arena, ext, n_ext, s);
-    case FP_OP_STEM_U8: return fp_launch_stem_u8(op, weights, arena, ext, n_ext, s);
-    default: return FP_ERR_UNSUPPORTED;
+struct fp_timer {
+  int n;
+  hipEvent_t* start;
+  hipEvent_t* stop;
+  unsigned char* used;
+};
+
+// The plan executor: validates every op, then launches them in order.  With a timer, the ops op_mask selects are
+// bracketed by its events.
+static int run_plan(const fp_op* ops, int n_ops, size_t weight_floats, size_t arena_floats, const fp_launch& L, fp_timer* t,
+                    const unsigned char* op_mask) {
+  int rc = fp_plan_validate(ops, n_ops, weight_floats, arena_floats);
+  if (rc != FP_OK) return rc;
+  for (int i = 0; i < n_ops; ++i) {
+    const bool timed = t && op_mask[i];
+    if (t) t->used[i] = op_mask[i];
+    if (timed) (void)hipEventRecord(t->start[i], L.s);
+    rc = launch_op(ops[i], L);
+    if (rc != FP_OK) return rc;
+    if (timed) (void)hipEventRecord(t->stop[i], L.s);
   }
+  return FP_OK;
 }
 
 int fp_plan_run_ext(const fp_op* ops, int n_ops, const float* weights, size_t weight_floats, float* arena,
                     size_t arena_floats, const fp_ext* ext, int n_ext, void* stream) {
   if (!weights || !arena || n_ext < 0 || (n_ext > 0 && !ext)) return FP_ERR_INVALID_ARG;
-  int rc = fp_plan_validate(ops, n_ops, weight_floats, arena_floats);
-  if (rc != FP_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  for (int i = 0; i < n_ops; ++i) {
-    rc = launch_op(ops[i], weights, arena, ext, n_ext, s);
-    if (rc != FP_OK) return rc;
-  }
-  return FP_OK;
+  const fp_launch L = {weights, arena, ext, n_ext, (hipStream_t)stream, false, nullptr};
+  return run_plan(ops, n_ops, weight_floats, arena_floats, L, nullptr, nullptr);
 }
 
 int fp_plan_run(const fp_op* ops, int n_ops, const float* weights, size_t weight_floats, float* arena,
@@ -498,13 +391,6 @@ int fp_dets_to_crops_ragged(const float* dets, const int32_t* counts, int B, int
                                         face_info, n_faces, (hipStream_t)stream);
 }
 
-struct fp_timer {
-  int n;
-  hipEvent_t* start;
-  hipEvent_t* stop;
-  unsigned char* used;
-};
-
 int fp_timer_create(int n_ops, void** out) {
   if (!out || n_ops <= 0) return FP_ERR_INVALID_ARG;
   fp_timer* t = new fp_timer;
@@ -541,17 +427,8 @@ int fp_plan_run_timed_ext(const fp_op* ops, int n_ops, const float* weights, siz
                           const unsigned char* op_mask) {
   fp_timer* t = (fp_timer*)timer;
   if (!weights || !arena || !t || !op_mask || t->n < n_ops || n_ext < 0 || (n_ext > 0 && !ext)) return FP_ERR_INVALID_ARG;
-  int rc = fp_plan_validate(ops, n_ops, weight_floats, arena_floats);
-  if (rc != FP_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  for (int i = 0; i < n_ops; ++i) {
-    t->used[i] = op_mask[i];
-    if (op_mask[i]) (void)hipEventRecord(t->start[i], s);
-    rc = launch_op(ops[i], weights, arena, ext, n_ext, s);
-    if (rc != FP_OK) return rc;
-    if (op_mask[i]) (void)hipEventRecord(t->stop[i], s);
-  }
-  return FP_OK;
+  const fp_launch L = {weights, arena, ext, n_ext, (hipStream_t)stream, false, nullptr};
+  return run_plan(ops, n_ops, weight_floats, arena_floats, L, t, op_mask);
 }
 
 int fp_plan_run_timed(const fp_op* ops, int n_ops, const float* weights, size_t weight_floats, float* arena,

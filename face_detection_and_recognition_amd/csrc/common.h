@@ -25,17 +25,10 @@ __device__ __forceinline__ float fp_silu(float x) {
   return x * __builtin_amdgcn_rcpf(1.0f + e);
 }
 
-// Lab / test knobs of the launchers, taken from the environment ONCE when the library is loaded (a launch never calls
-// getenv); fp_debug_reload_env() (facepath.h) re-reads them.  0 = the product path for every knob.
+// Test knob of the launchers, taken from the environment ONCE when the library is loaded (a launch never calls getenv);
+// fp_debug_reload_env() (facepath.h) re-reads it.
 struct fp_knobs {
-  int chain_grid;        // FP_CHAIN_GRID: cap on blazechain96_kernel's workgroups (lab)
   int resize_per_pixel;  // FP_RESIZE_PER_PIXEL: fp_resize_normalize takes the per-pixel kernel (the tabled kernel's reference in tests)
-  int x6_quarter14;      // FP_X6_QUARTER14: 14 x 14 Depth_Wise blocks as 7 x 7 tiles (lab)
-  int x6_spec14;         // FP_X6_SPEC14: the wave-specialised 14 x 14 form (lab)
-  int pwx6_small_maxk;   // FP_PWX6_SMALL_MAXK: K at or below which pwx6 takes its small tiles (lab)
-  int pair_lds_min;      // FP_PAIR_LDS_MIN: blazepair kernels request at least this much LDS (lab: > 80 KiB = one workgroup per CU)
-  int x6_lds_min;        // FP_X6_LDS_MIN: the same for the dwblock_x6 / x6d kernels (lab)
-  int shuf_ldsw;         // FP_SHUF_LDSW: shufdown_x6_kernel in its eight-wave, weights-in-LDS form (lab)
 };
 const fp_knobs& fp_get_knobs();
 
@@ -103,66 +96,69 @@ static inline int fp_window_bands(int rows, int N, int per_wg, int slots, int st
 }
 static inline long fp_round_up(long a, long b) { return (a + b - 1) / b * b; }
 
-// launchers implemented in the .hip files, called by the plan executor (capi.cpp)
-int fp_launch_conv(const fp_op& op, const float* weights, float* arena, hipStream_t s);
-int fp_launch_dwconv(const fp_op& op, const float* weights, float* arena, hipStream_t s);
-int fp_launch_maxpool(const fp_op& op, float* arena, hipStream_t s);
-int fp_launch_upsample2x(const fp_op& op, float* arena, hipStream_t s);
-int fp_launch_copy(const fp_op& op, float* arena, hipStream_t s);
-int fp_launch_l2norm(const fp_op& op, float* arena, hipStream_t s);
-int fp_launch_blazeblock(const fp_op& op, const float* weights, float* arena, hipStream_t s);
-bool fp_blazeblock_wp_eligible(const fp_op& op);   // row-padded input: the wave-private kernel takes it (24 -> 24)
-bool fp_blazeblock_wps_eligible(const fp_op& op);  // ... its small-map form for the 48- and 96-channel blocks
-int fp_launch_blazeblock_rowpad(const fp_op& op, const float* weights, float* arena, hipStream_t s);   // blazewp.hip
-bool fp_blazeblock_fixed24(const fp_op& op);   // persistent BlazeBlock instantiated with compile-time 24 -> 24 widths
-int fp_launch_dwpw(const fp_op& op, const float* weights, float* arena, hipStream_t s);
-bool fp_dwpwx6_eligible(const fp_op& op);   // DWPW with FP_OPF_SPLIT3: depthwise on the VALU, 1x1 on the split MFMA (dwpwx6.hip)
-long fp_dwpwx6_w_floats(const fp_op& op);
-int fp_launch_dwpwx6(const fp_op& op, const float* weights, float* arena, hipStream_t s);
-bool fp_dwpw_persistent(const fp_op& op);   // true: dwpw_persist_kernel / dwpw_wp_kernel, false: dwpw_kernel
-bool fp_dwpw_wave_private(const fp_op& op); // true: dwpw_wp_kernel (projection weights resident in LDS)
-bool fp_blazepair_supported(const fp_op& op);   // two stride-1 24 -> 24 BlazeBlocks in one kernel (blazepair.hip)
-int fp_blazepair_band_rows(const fp_op& op);
-int fp_launch_blazepair(const fp_op& op, const float* weights, float* arena, hipStream_t s);
-bool fp_blazepair_s2_supported(const fp_op& op);   // a stride-1 24 -> 24 block + the stride-2 block behind it (blazepairs2.hip)
-int fp_blazepair_s2_band_rows(const fp_op& op);
-int fp_launch_blazepair_s2(const fp_op& op, const float* weights, float* arena, hipStream_t s);
-bool fp_blazechain_supported(const fp_op& op);  // a run of stride-1 96 -> 96 BlazeBlocks on a 16 x 16 map in one kernel (blazechain.hip)
-int64_t fp_blazechain_w_floats(const fp_op& op);
-int fp_launch_blazechain(const fp_op& op, const float* weights, float* arena, hipStream_t s);
-bool fp_dwblock_supported(const fp_op& op); // whole Depth_Wise block shapes dwblock.hip is instantiated for
-int fp_launch_dwblock(const fp_op& op, const float* weights, float* arena, hipStream_t s);
-bool fp_dwblock_x6_supported(const fp_op& op);   // DWBLOCK with FP_OPF_SPLIT3: bf16x6 split-MFMA kernel (dwblockx6.hip)
-long fp_dwblock_x6_we_floats(const fp_op& op);   // floats behind w_off / slope_off of such an op
-long fp_dwblock_x6_wp_floats(const fp_op& op);
-int fp_launch_dwblock_x6(const fp_op& op, const float* weights, float* arena, hipStream_t s);
-bool fp_shufdown_supported(const fp_op& op);     // FP_OP_SHUFDOWN: a whole stride-2 ShuffleV2Block (shufdown.hip)
-long fp_shufdown_w_floats(const fp_op& op);
-int fp_launch_shufdown(const fp_op& op, const float* weights, float* arena, hipStream_t s);
-bool fp_shufunit_supported(const fp_op& op);     // FP_OP_SHUFUNIT: a whole stride-1 ShuffleV2Block (shufdown.hip)
-long fp_shufunit_w_floats(const fp_op& op);
-int fp_launch_shufunit(const fp_op& op, const float* weights, float* arena, hipStream_t s);
-bool fp_ystem2_supported(const fp_op& op);       // FP_OP_YSTEM2: stem_2b + cat + stem_3 of YOLOv5-face's StemBlock (ystem2.hip)
-long fp_ystem2_w_floats(const fp_op& op);
-int fp_launch_ystem2(const fp_op& op, const float* weights, float* arena, hipStream_t s);
-bool fp_pwx6_eligible(const fp_op& op);     // CONV with FP_OPF_SPLIT3: pointwise conv on the bf16x6 split-MFMA kernel (pwx6.hip)
-long fp_pwx6_w_floats(const fp_op& op);
-int fp_pwx6_mt(const fp_op& op);
-bool fp_convx6_eligible(const fp_op& op);   // ... the general form: 3x3 pad 1 stride 1 / 2, widths padded to 32 / 16 (convx6_kernel)
-long fp_convx6_w_floats(const fp_op& op);
-int fp_convx6_nt16(const fp_op& op);
-int fp_launch_convx6(const fp_op& op, const float* weights, float* arena, hipStream_t s);
-int fp_launch_pwx6(const fp_op& op, const float* weights, float* arena, hipStream_t s);
-bool fp_pws_eligible(const fp_op& op);      // pointwise K = 64 convs that take the wave-private streaming kernel
-int fp_launch_pws(const fp_op& op, const float* weights, float* arena, hipStream_t s);
-bool fp_stem_eligible(const fp_op& op);     // KxK stride-2 convs on a 4-float-pixel image (network stems)
-int fp_launch_stem(const fp_op& op, const float* weights, float* arena, hipStream_t s);
-bool fp_stemdw_supported(const fp_op& op);   // CONV + FP_OPF_OUT_DW: Mobile-FaceNet's conv1 + conv2_dw in one kernel (stemdw.hip)
+// What a plan-op launcher is given (capi.cpp).  A launcher alone decides whether it takes an op and which kernel
+// instance runs it.  With `dry` set it makes every check and that choice exactly as a launch would, writes the
+// instance's name to `name` (when not null, FP_KERNEL_NAME_MAX bytes) and returns FP_OK before any HIP call and without
+// touching the weights, the arena or `ext`: fp_plan_validate and fp_op_kernel_name are such dry runs.
+#define FP_KERNEL_NAME_MAX 64
+struct fp_launch {
+  const float* weights;
+  float* arena;
+  const fp_ext* ext;
+  int n_ext;
+  hipStream_t s;
+  bool dry;
+  char* name;
+};
+// In a dry run: record the kernel's name (printf format) and return true, the launcher then returns FP_OK.
+bool fp_dry_run(const fp_launch& L, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+
+// launchers implemented in the .hip files, one per op family, dispatched by the plan executor (capi.cpp)
+int fp_launch_conv(const fp_op& op, const fp_launch& L);
+int fp_launch_dwconv(const fp_op& op, const fp_launch& L);
+int fp_launch_maxpool(const fp_op& op, const fp_launch& L);
+int fp_launch_upsample2x(const fp_op& op, const fp_launch& L);
+int fp_launch_copy(const fp_op& op, const fp_launch& L);
+int fp_launch_l2norm(const fp_op& op, const fp_launch& L);
+int fp_launch_blazeblock(const fp_op& op, const fp_launch& L);
+int fp_launch_blazeblock_rowpad(const fp_op& op, const fp_launch& L);   // blazewp.hip
+int fp_launch_dwpw(const fp_op& op, const fp_launch& L);
+int fp_launch_dwpwx6(const fp_op& op, const fp_launch& L);   // DWPW with FP_OPF_SPLIT3 (dwpwx6.hip)
+int fp_launch_blazepair(const fp_op& op, const fp_launch& L);
+int fp_launch_blazepair_s2(const fp_op& op, const fp_launch& L);
+int fp_launch_blazechain(const fp_op& op, const fp_launch& L);
+int fp_launch_dwblock(const fp_op& op, const fp_launch& L);
+int fp_launch_dwblock_x6(const fp_op& op, const fp_launch& L);   // DWBLOCK with FP_OPF_SPLIT3 (dwblockx6.hip)
+int fp_launch_shufdown(const fp_op& op, const fp_launch& L);
+int fp_launch_shufunit(const fp_op& op, const fp_launch& L);
+int fp_launch_ystem2(const fp_op& op, const fp_launch& L);
+int fp_launch_ystem(const fp_op& op, const fp_launch& L);
+int fp_launch_ystem_u8(const fp_op& op, const fp_launch& L);
+int fp_launch_stem_u8(const fp_op& op, const fp_launch& L);
+// ... and the kernels fp_launch_conv dispatches to, with the predicates that pick them
+int fp_launch_stemdw(const fp_op& op, const fp_launch& L);   // FP_OPF_OUT_DW (stemdw.hip)
+bool fp_pwx6_eligible(const fp_op& op);   // FP_OPF_SPLIT3 pointwise: pwx6_kernel, else convx6_kernel (pwx6.hip)
+int fp_launch_pwx6(const fp_op& op, const fp_launch& L);
+int fp_launch_convx6(const fp_op& op, const fp_launch& L);
+bool fp_pws_eligible(const fp_op& op);    // pointwise K = 64 / 128 convs on the wave-private streaming kernel (pws.hip)
+int fp_launch_pws(const fp_op& op, const fp_launch& L);
+bool fp_stem_eligible(const fp_op& op);   // KxK stride-2 convs on a 4-float-pixel image, network stems (stem.hip)
+int fp_launch_stem(const fp_op& op, const fp_launch& L);
+bool fp_conv3_eligible(const fp_op& op);  // dense 3x3 pad-1 convs on the LDS-image kernel (conv3.hip)
+int fp_launch_conv3(const fp_op& op, const fp_launch& L);
+
+// floats of the weight blob behind an op's offsets (the span checks of fp_plan_validate)
 long fp_stemdw_w_floats(const fp_op& op);
-int fp_launch_stemdw(const fp_op& op, const float* weights, float* arena, hipStream_t s);
-bool fp_stem_u8_shape_ok(const fp_op& op);
-bool fp_stem_u8_band_eligible(const fp_op& op);   // BlazeFace's 5x5 stem on u8 frames, band kernel (canvas rows in an LDS ring)
-int fp_launch_stem_u8(const fp_op& op, const float* weights, float* arena, const fp_ext* ext, int n_ext, hipStream_t s);
+long fp_convx6_w_floats(const fp_op& op);
+long fp_dwpwx6_w_floats(const fp_op& op);
+int64_t fp_blazechain_w_floats(const fp_op& op);
+long fp_dwblock_x6_we_floats(const fp_op& op);   // behind w_off / slope_off of a DWBLOCK with FP_OPF_SPLIT3
+long fp_dwblock_x6_wp_floats(const fp_op& op);
+long fp_shufdown_w_floats(const fp_op& op);
+long fp_shufunit_w_floats(const fp_op& op);
+long fp_ystem2_w_floats(const fp_op& op);
+int fp_ystem_nb2(const fp_op& op);   // 16-channel column blocks of ystem_kernel's packed stem_1 weights
+
 // ragged batches (facepath.h section 2): launchers behind the argument checks of capi.cpp
 int fp_launch_resize_ragged(const uint8_t* frames, size_t frames_bytes, const fp_frame_desc* descs, int n_frames,
                             const fp_resize_item* items, int n_items, void* canvas, int canvas_h, int canvas_w, int mode,
@@ -171,11 +167,3 @@ int fp_launch_dets_to_crops_ragged(const float* dets, const int32_t* counts, int
                                    int in_w, int in_h, const fp_frame_desc* descs, const float* geom, float det_thres,
                                    float area_thres, int off_tx, int off_ty, int off_bx, int off_by, int dst_w, int dst_h,
                                    int max_faces, fp_resize_item* items, float* face_info, int32_t* n_faces, hipStream_t s);
-int fp_launch_ystem(const fp_op& op, const float* weights, float* arena, hipStream_t s);
-int fp_ystem_nb2(const fp_op& op);
-int fp_launch_ystem_u8(const fp_op& op, const float* weights, float* arena, const fp_ext* ext, int n_ext, hipStream_t s);
-bool fp_conv3_eligible(const fp_op& op);    // dense 3x3 pad-1 convs that take the LDS-image kernel (conv3.hip)
-int fp_conv3_nb(const fp_op& op);
-bool fp_conv3_t16(const fp_op& op);        // conv3 with 16-column n tiles (16x16x4 MFMA)
-int fp_launch_conv3(const fp_op& op, const float* weights, float* arena, hipStream_t s);
-void fp_conv_variant(const fp_op& op, int* nb, int* vec, int* pwd);  // conv_igemm template arguments for an op

@@ -705,7 +705,7 @@ static bool conv_vec_epilogue(const fp_op& op) {
 #ifndef FP_PWD_NB2_MAX_K
 #define FP_PWD_NB2_MAX_K 0
 #endif
-void fp_conv_variant(const fp_op& op, int* nb, int* vec, int* pwd) {
+static void conv_variant(const fp_op& op, int* nb, int* vec, int* pwd) {
   *vec = ((op.Cin % 4 == 0) && (op.in_ld % 4 == 0) && (op.in_off % 4 == 0) && (op.in_ns % 4 == 0)) ? 1 : 0;
   const long HWl = (long)op.H * op.W;
   bool pw = *vec && conv_vec_epilogue(op) && op.KH == 1 && op.KW == 1 && op.stride == 1 && op.pad_t == 0 &&
@@ -722,13 +722,15 @@ void fp_conv_variant(const fp_op& op, int* nb, int* vec, int* pwd) {
   else *nb = 4;  // partial last tile (guarded in-kernel)
 }
 
-int fp_launch_conv(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
-  if (op.flags & FP_OPF_OUT_DW) return fp_launch_stemdw(op, weights, arena, s);
-  if (op.flags & FP_OPF_SPLIT3)
-    return fp_pwx6_eligible(op) ? fp_launch_pwx6(op, weights, arena, s) : fp_launch_convx6(op, weights, arena, s);
-  if (fp_pws_eligible(op)) return fp_launch_pws(op, weights, arena, s);
-  if (fp_stem_eligible(op)) return fp_launch_stem(op, weights, arena, s);
-  if (fp_conv3_eligible(op)) return fp_launch_conv3(op, weights, arena, s);
+int fp_launch_conv(const fp_op& op, const fp_launch& L) {
+  if (op.flags & FP_OPF_OUT_DW) return fp_launch_stemdw(op, L);
+  if (op.flags & FP_OPF_SPLIT3) return fp_pwx6_eligible(op) ? fp_launch_pwx6(op, L) : fp_launch_convx6(op, L);
+  if (fp_stem_eligible(op)) return fp_launch_stem(op, L);
+  if (op.flags & FP_OPF_OUT_ROWPAD) return FP_ERR_UNSUPPORTED;   // of the convs, only the stem kernel writes row-padded output
+  if (fp_pws_eligible(op)) return fp_launch_pws(op, L);
+  if (fp_conv3_eligible(op)) return fp_launch_conv3(op, L);
+  const float* weights = L.weights;
+  float* arena = L.arena;
   ConvArgs a;
   a.in = arena + op.in_off;
   a.out = arena + op.out_off;
@@ -749,18 +751,20 @@ int fp_launch_conv(const fp_op& op, const float* weights, float* arena, hipStrea
   a.Npad = (int)fp_round_up(op.Cout, 32);
   a.OHW = op.OH * op.OW;
   a.M = (long)op.N * a.OHW;
-  if (a.act == FP_ACT_PRELU && !a.slope) return FP_ERR_INVALID_ARG;
+  if (a.act == FP_ACT_PRELU && op.slope_off < 0) return FP_ERR_INVALID_ARG;
   if (a.M >= (1L << 31)) return FP_ERR_UNSUPPORTED;  // 32-bit row decode in the kernel
   a.res_C4 = (int)fp_round_up(op.res_C, 4);
   const bool ve = conv_vec_epilogue(op);
   a.vec_epi = ve ? 1 : 0;
   if (op.res_mode == FP_RES_SHUFFLE2 && (!ve || op.res_C < op.Cout)) return FP_ERR_UNSUPPORTED;
   int NB, vec_i, pwd_i;
-  fp_conv_variant(op, &NB, &vec_i, &pwd_i);
+  conv_variant(op, &NB, &vec_i, &pwd_i);
   const bool vec = vec_i != 0, pwd = pwd_i != 0;
   a.ntiles_n = fp_ceil_div(a.Npad, NB * 32);
   const long nblocks = (long)fp_ceil_div(a.M, BM) * a.ntiles_n;
   if (nblocks >= (1L << 31)) return FP_ERR_UNSUPPORTED;
+  if (fp_dry_run(L, "conv_igemm_kernel<%d, %s, %s>", NB, vec ? "true" : "false", pwd ? "true" : "false")) return FP_OK;
+  const hipStream_t s = L.s;
   dim3 grid((unsigned)nblocks);
   dim3 block(256);
 #define FP_CONV_CASE(NBV)                                                                      \
@@ -780,11 +784,13 @@ int fp_launch_conv(const fp_op& op, const float* weights, float* arena, hipStrea
   return FP_OK;
 }
 
-int fp_launch_dwconv(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
+int fp_launch_dwconv(const fp_op& op, const fp_launch& L) {
   if (op.Cin % 4 || op.in_ld % 4 || op.out_ld % 4 || op.in_off % 4 || op.out_off % 4 || op.in_ns % 4 || op.out_ns % 4 ||
       op.out_cmul != 1)
     return FP_ERR_ALIGNMENT;
   if (op.KH != op.KW) return FP_ERR_UNSUPPORTED;
+  const float* weights = L.weights;
+  float* arena = L.arena;
   DwArgs a;
   a.in = arena + op.in_off;
   a.out = arena + op.out_off;
@@ -797,10 +803,12 @@ int fp_launch_dwconv(const fp_op& op, const float* weights, float* arena, hipStr
   a.in_ld = op.in_ld; a.out_ld = op.out_ld; a.in_ns = op.in_ns; a.out_ns = op.out_ns;
   a.act = op.act; a.OHW = op.OH * op.OW; a.C4 = op.Cin / 4;
   a.total = (long)op.N * a.OHW * a.C4;
-  if (a.act == FP_ACT_PRELU && !a.slope) return FP_ERR_INVALID_ARG;
+  if (a.act == FP_ACT_PRELU && op.slope_off < 0) return FP_ERR_INVALID_ARG;
   if (a.total >= (1L << 31)) return FP_ERR_UNSUPPORTED;  // 32-bit item decode in the kernel
+  const hipStream_t s = L.s;
   dim3 grid((unsigned)fp_ceil_div(a.total, 256)), block(256);
   if (op.KH == 3 && (op.stride == 1 || op.stride == 2)) {
+    if (fp_dry_run(L, "dwconv3_row_kernel<%d>", op.stride)) return FP_OK;
     const int OWG = (op.OW + 3) / 4;
     const long items = (long)op.N * op.OH * OWG * a.C4;
     dim3 g2((unsigned)fp_ceil_div(items, 256));
@@ -809,11 +817,12 @@ int fp_launch_dwconv(const fp_op& op, const float* weights, float* arena, hipStr
     FP_CHECK_LAUNCH();
     return FP_OK;
   }
+  if (op.KH != 3 && op.KH != 5 && op.KH != 7) return FP_ERR_UNSUPPORTED;
+  if (fp_dry_run(L, "dwconv_kernel<%d>", op.KH)) return FP_OK;
   switch (op.KH) {
     case 3: hipLaunchKernelGGL((dwconv_kernel<3>), grid, block, 0, s, a); break;
     case 5: hipLaunchKernelGGL((dwconv_kernel<5>), grid, block, 0, s, a); break;
-    case 7: hipLaunchKernelGGL((dwconv_kernel<7>), grid, block, 0, s, a); break;
-    default: return FP_ERR_UNSUPPORTED;
+    default: hipLaunchKernelGGL((dwconv_kernel<7>), grid, block, 0, s, a); break;
   }
   FP_CHECK_LAUNCH();
   return FP_OK;
@@ -833,12 +842,14 @@ static int fill_pool_args(const fp_op& op, float* arena, PoolArgs& a) {
   return FP_OK;
 }
 
-int fp_launch_maxpool(const fp_op& op, float* arena, hipStream_t s) {
+int fp_launch_maxpool(const fp_op& op, const fp_launch& L) {
   PoolArgs a;
-  int rc = fill_pool_args(op, arena, a);
+  int rc = fill_pool_args(op, L.arena, a);
   if (rc) return rc;
   const dim3 grid((unsigned)fp_ceil_div(a.total, 256)), block(256);
   const bool small = a.total < (1L << 31);
+  if (fp_dry_run(L, small && (a.K == 2 || a.K == 3 || a.K == 5) ? "maxpool_kernel" : "maxpool_generic_kernel")) return FP_OK;
+  const hipStream_t s = L.s;
   if (small && a.K == 2) hipLaunchKernelGGL(maxpool_kernel<2>, grid, block, 0, s, a);
   else if (small && a.K == 3) hipLaunchKernelGGL(maxpool_kernel<3>, grid, block, 0, s, a);
   else if (small && a.K == 5) hipLaunchKernelGGL(maxpool_kernel<5>, grid, block, 0, s, a);
@@ -847,20 +858,21 @@ int fp_launch_maxpool(const fp_op& op, float* arena, hipStream_t s) {
   return FP_OK;
 }
 
-int fp_launch_upsample2x(const fp_op& op, float* arena, hipStream_t s) {
+int fp_launch_upsample2x(const fp_op& op, const fp_launch& L) {
   PoolArgs a;
-  int rc = fill_pool_args(op, arena, a);
+  int rc = fill_pool_args(op, L.arena, a);
   if (rc) return rc;
   if (op.OH != 2 * op.H || op.OW != 2 * op.W) return FP_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(upsample2x_kernel, dim3((unsigned)fp_ceil_div(a.total, 256)), dim3(256), 0, s, a);
+  if (fp_dry_run(L, "upsample2x_kernel")) return FP_OK;
+  hipLaunchKernelGGL(upsample2x_kernel, dim3((unsigned)fp_ceil_div(a.total, 256)), dim3(256), 0, L.s, a);
   FP_CHECK_LAUNCH();
   return FP_OK;
 }
 
-int fp_launch_copy(const fp_op& op, float* arena, hipStream_t s) {
+int fp_launch_copy(const fp_op& op, const fp_launch& L) {
   CopyArgs a;
-  a.in = arena + op.in_off;
-  a.out = arena + op.out_off;
+  a.in = L.arena + op.in_off;
+  a.out = L.arena + op.out_off;
   a.C = op.Cin; a.in_ld = op.in_ld; a.out_ld = op.out_ld; a.out_cmul = op.out_cmul;
   a.HW = op.H * op.W; a.in_ns = op.in_ns; a.out_ns = op.out_ns;
   a.W = op.W; a.out_rowpad = (op.flags & FP_OPF_OUT_ROWPAD) != 0;
@@ -868,21 +880,24 @@ int fp_launch_copy(const fp_op& op, float* arena, hipStream_t s) {
                   op.out_off % 4 == 0 && op.in_ns % 4 == 0 && op.out_ns % 4 == 0;
   if (v4) {
     a.total = (long)op.N * a.HW * (a.C / 4);
-    hipLaunchKernelGGL(copy4_kernel, dim3((unsigned)fp_ceil_div(a.total, 256)), dim3(256), 0, s, a);
+    if (fp_dry_run(L, "copy4_kernel")) return FP_OK;
+    hipLaunchKernelGGL(copy4_kernel, dim3((unsigned)fp_ceil_div(a.total, 256)), dim3(256), 0, L.s, a);
     FP_CHECK_LAUNCH();
     return FP_OK;
   }
   if (a.out_rowpad) return FP_ERR_UNSUPPORTED;   // the scalar form has no row-padded output
   a.total = (long)op.N * a.HW * a.C;
-  hipLaunchKernelGGL(copy_kernel, dim3((unsigned)fp_ceil_div(a.total, 256)), dim3(256), 0, s, a);
+  if (fp_dry_run(L, "copy_kernel")) return FP_OK;
+  hipLaunchKernelGGL(copy_kernel, dim3((unsigned)fp_ceil_div(a.total, 256)), dim3(256), 0, L.s, a);
   FP_CHECK_LAUNCH();
   return FP_OK;
 }
 
-int fp_launch_l2norm(const fp_op& op, float* arena, hipStream_t s) {
+int fp_launch_l2norm(const fp_op& op, const fp_launch& L) {
   const long M = (long)op.N * op.H * op.W;
-  hipLaunchKernelGGL(l2norm_kernel, dim3((unsigned)fp_ceil_div(M, 4)), dim3(256), 0, s, arena + op.in_off,
-                     arena + op.out_off, M, op.Cin, (long)op.in_ld, (long)op.out_ld);
+  if (fp_dry_run(L, "l2norm_kernel")) return FP_OK;
+  hipLaunchKernelGGL(l2norm_kernel, dim3((unsigned)fp_ceil_div(M, 4)), dim3(256), 0, L.s, L.arena + op.in_off,
+                     L.arena + op.out_off, M, op.Cin, (long)op.in_ld, (long)op.out_ld);
   FP_CHECK_LAUNCH();
   return FP_OK;
 }

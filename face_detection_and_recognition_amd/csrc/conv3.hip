@@ -321,19 +321,25 @@ bool fp_conv3_eligible(const fp_op& op) {
 // summarised in DESIGN.md section 6): 48 -> 48 @ 80 x 80 1070 -> 636 us and 64 -> 64 @ 80 x 80 1282 -> 1041 us (117
 // TFLOP/s) against the 32 x 32 x 2 tiles; 24 -> 24 (2 tiles), 92 -> 92 (6 tiles) and the stride-2 128 -> 128 (8 tiles)
 // are 3-20 % slower that way and stay on 32-column tiles.
-bool fp_conv3_t16(const fp_op& op) {
+static bool conv3_t16(const fp_op& op) {
   if (op.stride != 1 || op.Cout > 112) return false;
   if (op.Cout > 32 && op.Cout <= 64) return true;                           // 3 or 4 tiles of 16
   return fp_round_up(op.Cout, 16) < fp_round_up(op.Cout, 32);               // a whole idle 16-column tile otherwise
 }
 
-int fp_conv3_nb(const fp_op& op) {
-  if (fp_conv3_t16(op)) return (int)fp_round_up(op.Cout, 16) / 16;          // 1, 3, 4, 5 or 7 tiles of 16
+static int conv3_nb(const fp_op& op) {
+  if (conv3_t16(op)) return (int)fp_round_up(op.Cout, 16) / 16;          // 1, 3, 4, 5 or 7 tiles of 16
   const int nblk = (int)fp_round_up(op.Cout, 32) / 32;
   return nblk >= 4 ? 4 : nblk;   // wider outputs run as several 128-column chunks (grid.y)
 }
 
-int fp_launch_conv3(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
+int fp_launch_conv3(const fp_op& op, const fp_launch& L) {
+  const int NB = conv3_nb(op);
+  const bool t16 = conv3_t16(op);
+  if (fp_dry_run(L, "conv3_kernel<%d, %d, %s>", NB, op.stride, t16 ? "true" : "false")) return FP_OK;
+  const float* weights = L.weights;
+  float* arena = L.arena;
+  const hipStream_t s = L.s;
   Conv3Args a;
   a.in = arena + op.in_off;
   a.out = arena + op.out_off;
@@ -348,8 +354,6 @@ int fp_launch_conv3(const fp_op& op, const float* weights, float* arena, hipStre
   a.in_ns = op.in_ns; a.out_ns = op.out_ns; a.res_ns = op.res_ns;
   a.tiles_x = fp_ceil_div(op.OW, TW);
   a.tiles_per_img = a.tiles_x * fp_ceil_div(op.OH, TH);
-  const int NB = fp_conv3_nb(op);
-  const bool t16 = fp_conv3_t16(op);
   const dim3 grid((unsigned)((long)op.N * a.tiles_per_img), (unsigned)(t16 ? fp_ceil_div((int)fp_round_up(op.Cout, 16), NB * 16) : fp_ceil_div(a.Npad, NB * 32))), block(256);
   hipError_t ae = hipSuccess;
 #define FP_CONV3_CASE(NBV, SV, T16V)                                                                               \

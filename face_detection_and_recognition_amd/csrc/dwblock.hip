@@ -402,10 +402,11 @@ __global__ __launch_bounds__(512, 1) void dwblock_kernel(DwBlockArgs p) {
 }
 
 template <int C, int HW, int RB, int NIMG>
-int launch_variant(const DwBlockArgs& a, hipStream_t s) {
+int launch_variant(const DwBlockArgs& a, const fp_launch& L) {
   using K = DwbCfg<C, HW, RB, NIMG>;
   static_assert(K::LDS_FLOATS * 4 <= 160 * 1024, "one workgroup per CU");
   constexpr int lds = K::LDS_FLOATS * 4;
+  if (fp_dry_run(L, "dwblock_kernel<%d, %d, %d, %d>", C, HW, RB, NIMG)) return FP_OK;
   const hipError_t ae = hipFuncSetAttribute((const void*)dwblock_kernel<C, HW, RB, NIMG>,
                                             hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (ae != hipSuccess) {
@@ -413,7 +414,7 @@ int launch_variant(const DwBlockArgs& a, hipStream_t s) {
     return FP_ERR_LAUNCH;
   }
   const int tiles = fp_ceil_div(a.N, NIMG) * K::NBAND;
-  hipLaunchKernelGGL((dwblock_kernel<C, HW, RB, NIMG>), dim3(tiles), dim3(512), lds, s, a);
+  hipLaunchKernelGGL((dwblock_kernel<C, HW, RB, NIMG>), dim3(tiles), dim3(512), lds, L.s, a);
   FP_CHECK_LAUNCH();
   return FP_OK;
 }
@@ -421,7 +422,7 @@ int launch_variant(const DwBlockArgs& a, hipStream_t s) {
 }  // namespace
 
 // Shapes the kernel is instantiated for (include/facepath.h, DWBLOCK).
-bool fp_dwblock_supported(const fp_op& op) {
+static bool dwblock_supported(const fp_op& op) {
   if (op.kind != FP_OP_DWBLOCK) return false;
   if (op.stride != 1 || op.KH != 3 || op.KW != 3 || op.pad_t != 1 || op.pad_l != 1) return false;
   if (op.OH != op.H || op.OW != op.W || op.H != op.W || op.Cout != op.Cin || op.out_cmul != 1) return false;
@@ -438,18 +439,18 @@ bool fp_dwblock_supported(const fp_op& op) {
   return true;
 }
 
-int fp_launch_dwblock(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
-  if (!fp_dwblock_supported(op)) return FP_ERR_UNSUPPORTED;
+int fp_launch_dwblock(const fp_op& op, const fp_launch& L) {
+  if (!dwblock_supported(op)) return FP_ERR_UNSUPPORTED;
   DwBlockArgs a;
   memset(&a, 0, sizeof(a));
-  a.in = arena + op.in_off;
-  a.out = arena + op.out_off;
-  a.we = weights + op.w_off;
-  a.par = weights + op.scale_off;
-  a.wp = weights + op.slope_off;
+  a.in = L.arena + op.in_off;
+  a.out = L.arena + op.out_off;
+  a.we = L.weights + op.w_off;
+  a.par = L.weights + op.scale_off;
+  a.wp = L.weights + op.slope_off;
   a.N = op.N;
   a.has_res = op.res_mode == FP_RES_ADD_AFTER_ACT;
-  if (op.Cin == 128 && op.H == 14) return launch_variant<128, 14, 14, 1>(a, s);
-  if (op.Cin == 128 && op.H == 7) return launch_variant<128, 7, 7, 3>(a, s);
-  return launch_variant<64, 28, 7, 1>(a, s);
+  if (op.Cin == 128 && op.H == 14) return launch_variant<128, 14, 14, 1>(a, L);
+  if (op.Cin == 128 && op.H == 7) return launch_variant<128, 7, 7, 3>(a, L);
+  return launch_variant<64, 28, 7, 1>(a, L);
 }

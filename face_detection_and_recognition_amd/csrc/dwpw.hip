@@ -849,7 +849,7 @@ static size_t dwpw_persist_lds(int NB, int G) {
 
 // Persistent pipelined kernel over tiles of 32 2x2 patches, 2 resident workgroups per CU.  Cout = 128 at stride 2
 // (a 5x5 window + 4 accumulators per lane) spills and measured slower than the per-tile kernel: left to that one.
-bool fp_dwpw_persistent(const fp_op& op) {
+static bool dwpw_persistent(const fp_op& op) {
   if (op.act2 != FP_ACT_NONE || op.res_mode == FP_RES_SHUFFLE2) return false;   // the per-tile kernel owns those epilogues
   const int NB = (int)fp_round_up(op.Cout, 32) / 32;
   if (!(NB == 2 || (NB == 4 && op.stride == 1))) return false;
@@ -863,8 +863,8 @@ bool fp_dwpw_persistent(const fp_op& op) {
 
 // The persistent shapes whose whole packed projection matrix (G x Npad floats) fits 64 KB of LDS take the wave-private
 // kernel: every Mobile-FaceNet block on the 56 x 56 and 28 x 28 maps (the 14 x 14 blocks have 128 KB of it).
-bool fp_dwpw_wave_private(const fp_op& op) {
-  return fp_dwpw_persistent(op) && (size_t)op.Cin * fp_round_up(op.Cout, 32) * 4 <= 64 * 1024 &&
+static bool dwpw_wave_private(const fp_op& op) {
+  return dwpw_persistent(op) && (size_t)op.Cin * fp_round_up(op.Cout, 32) * 4 <= 64 * 1024 &&
          (unsigned long long)op.N * (unsigned long long)op.in_ns * 4ull < (1ull << 32);   // 32-bit byte offsets
 }
 
@@ -872,7 +872,7 @@ bool fp_dwpw_wave_private(const fp_op& op) {
 static unsigned long long* g_dwpw_stamps = nullptr;
 #endif
 
-int fp_launch_dwpw(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
+int fp_launch_dwpw(const fp_op& op, const fp_launch& L) {
   // op: KH = KW = 3, pad 1, stride 1|2, Cin = G (multiple of 64), Cout multiple of 4 and <= 128;
   // w_off -> depthwise block, slope_off -> pointwise block; act = FP_ACT_PRELU when the depthwise has a PReLU;
   // res_mode = FP_RES_ADD_AFTER_ACT for the residual variant.
@@ -890,6 +890,9 @@ int fp_launch_dwpw(const fp_op& op, const float* weights, float* arena, hipStrea
     return FP_ERR_UNSUPPORTED;
   if (shuffle && op.out_ld < 2 * op.Cout) return FP_ERR_INVALID_ARG;
   if (op.act2 != FP_ACT_NONE && op.act2 != FP_ACT_SILU) return FP_ERR_UNSUPPORTED;
+  const float* weights = L.weights;
+  float* arena = L.arena;
+  const hipStream_t s = L.s;
   DwPwArgs a;
   a.in = arena + op.in_off;
   a.out = arena + op.out_off;
@@ -897,7 +900,7 @@ int fp_launch_dwpw(const fp_op& op, const float* weights, float* arena, hipStrea
   a.dwp = weights + op.w_off;
   a.pwp = weights + op.slope_off;
   a.oslope = op.bias_off >= 0 ? weights + op.bias_off : nullptr;   // output PReLU (never together with a residual)
-  if (a.oslope && (has_res || op.bias_off % 4)) return FP_ERR_UNSUPPORTED;
+  if (op.bias_off >= 0 && (has_res || op.bias_off % 4)) return FP_ERR_UNSUPPORTED;
   a.N = op.N; a.H = op.H; a.W = op.W; a.OH = op.OH; a.OW = op.OW; a.G = op.Cin; a.Cout = op.Cout; a.stride = op.stride;
   a.in_ld = op.in_ld; a.out_ld = op.out_ld; a.res_ld = op.res_ld; a.in_ns = op.in_ns;
   a.Npad = (int)fp_round_up(op.Cout, 32);
@@ -914,7 +917,9 @@ int fp_launch_dwpw(const fp_op& op, const float* weights, float* arena, hipStrea
 #endif
   const int NB = a.Npad / 32;
   const int P = (op.OW % 4 == 0) ? 4 : (op.OW % 2 == 0) ? 2 : 1;
-  if (fp_dwpw_persistent(op)) {
+  if (dwpw_persistent(op)) {
+    const bool wp = dwpw_wave_private(op);
+    if (fp_dry_run(L, wp ? "dwpw_wp_kernel<%d, %d, 4>" : "dwpw_persist_kernel<%d, %d>", NB, op.stride)) return FP_OK;
     const size_t plds = dwpw_persist_lds(NB, a.G);
     {
       DwPwArgs b = a;
@@ -928,7 +933,7 @@ int fp_launch_dwpw(const fp_op& op, const float* weights, float* arena, hipStrea
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds);                         \
     hipLaunchKernelGGL((dwpw_persist_kernel<NBV, SV>), dim3(nblk), dim3(256), plds, s, b);                      \
   } while (0)
-      if (fp_dwpw_wave_private(op)) {
+      if (wp) {
         // whole projection matrix resident in LDS: the wave-private kernel, 4 waves per workgroup, 2 workgroups per CU
         // (6 waves x 2 -- three per SIMD -- needs <= 168 VGPRs: the NB = 2 form spills 92 bytes there and runs 2x slower)
         constexpr int NWv = 4;
@@ -955,6 +960,7 @@ int fp_launch_dwpw(const fp_op& op, const float* weights, float* arena, hipStrea
       return FP_OK;
     }
   }
+  if (fp_dry_run(L, "dwpw_kernel<%d, %d, %d>", NB, P, op.stride)) return FP_OK;
   dim3 grid((unsigned)a.ntiles), block(256);
   const size_t lds = 4 * ((size_t)TM * LDT + (size_t)KCH * NB * 32 + 12 * KCH);
 #define FP_DWPW_LAUNCH(NBV, PV, SV)                                                                        \
@@ -974,8 +980,7 @@ int fp_launch_dwpw(const fp_op& op, const float* weights, float* arena, hipStrea
     case 1: FP_DWPW_S(1) break;
     case 2: FP_DWPW_S(2) break;
     case 3: FP_DWPW_S(3) break;
-    case 4: FP_DWPW_S(4) break;
-    default: return FP_ERR_UNSUPPORTED;
+    default: FP_DWPW_S(4) break;   // NB <= 4: Cout <= 128 above
   }
 #undef FP_DWPW_S
 #undef FP_DWPW_P

@@ -223,16 +223,17 @@ __global__ __launch_bounds__(256, 2) void dwpwx6_kernel(DwPwX6Args p) {
 }
 
 template <int NT, int S>
-int launch(const DwPwX6Args& a, hipStream_t s) {
+int launch(const DwPwX6Args& a, const fp_launch& L) {
   const int lds = 3 * APL * 2 + 3 * NT * 16 * 32 * 2 + 12 * a.G * 4;
   const long tiles = (a.M + TM - 1) / TM;
   if (tiles >= (1L << 31)) return FP_ERR_UNSUPPORTED;
+  if (fp_dry_run(L, "dwpwx6_kernel<%d, 4, %d>", NT, S)) return FP_OK;
   const hipError_t ae = hipFuncSetAttribute((const void*)dwpwx6_kernel<NT, 4, S>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (ae != hipSuccess) {
     fp_set_hip_error(ae);
     return FP_ERR_LAUNCH;
   }
-  hipLaunchKernelGGL((dwpwx6_kernel<NT, 4, S>), dim3((unsigned)tiles), dim3(256), lds, s, a);
+  hipLaunchKernelGGL((dwpwx6_kernel<NT, 4, S>), dim3((unsigned)tiles), dim3(256), lds, L.s, a);
   FP_CHECK_LAUNCH();
   return FP_OK;
 }
@@ -240,7 +241,7 @@ int launch(const DwPwX6Args& a, hipStream_t s) {
 }  // namespace
 
 // FP_OP_DWPW with FP_OPF_SPLIT3: G a multiple of 32 (<= 256), Cout 64 or 128, OW a multiple of 4, dense output rows.
-bool fp_dwpwx6_eligible(const fp_op& op) {
+static bool dwpwx6_eligible(const fp_op& op) {
   if (op.kind != FP_OP_DWPW || !(op.flags & FP_OPF_SPLIT3) || (op.flags & ~FP_OPF_SPLIT3)) return false;
   if (op.KH != 3 || op.KW != 3 || op.pad_t != 1 || op.pad_l != 1 || (op.stride != 1 && op.stride != 2)) return false;
   if (op.OH != (op.H + 2 - 3) / op.stride + 1 || op.OW != (op.W + 2 - 3) / op.stride + 1 || op.OW % 4) return false;
@@ -259,8 +260,10 @@ bool fp_dwpwx6_eligible(const fp_op& op) {
 
 long fp_dwpwx6_w_floats(const fp_op& op) { return (long)op.Cin * op.Cout * 3 / 2 + 2L * op.Cout; }
 
-int fp_launch_dwpwx6(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
-  if (!fp_dwpwx6_eligible(op)) return FP_ERR_UNSUPPORTED;
+int fp_launch_dwpwx6(const fp_op& op, const fp_launch& L) {
+  if (!dwpwx6_eligible(op)) return FP_ERR_UNSUPPORTED;
+  const float* weights = L.weights;
+  float* arena = L.arena;
   DwPwX6Args a;
   memset(&a, 0, sizeof(a));
   a.in = arena + op.in_off;
@@ -275,6 +278,6 @@ int fp_launch_dwpwx6(const fp_op& op, const float* weights, float* arena, hipStr
   a.act2 = op.act2; a.res_mode = op.res_mode;
   a.in_ns = op.in_ns;
   a.M = (long)op.N * a.OHW;
-  if (op.Cout == 64) return op.stride == 1 ? launch<4, 1>(a, s) : launch<4, 2>(a, s);
-  return op.stride == 1 ? launch<8, 1>(a, s) : launch<8, 2>(a, s);
+  if (op.Cout == 64) return op.stride == 1 ? launch<4, 1>(a, L) : launch<4, 2>(a, L);
+  return op.stride == 1 ? launch<8, 1>(a, L) : launch<8, 2>(a, L);
 }

@@ -181,7 +181,11 @@ bool fp_pws_eligible(const fp_op& op) {
   return true;
 }
 
-int fp_launch_pws(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
+int fp_launch_pws(const fp_op& op, const fp_launch& L) {
+  if (fp_dry_run(L, "pws_kernel<%d, %d>", op.Cin, op.Cin == 64 ? 12 : 8)) return FP_OK;
+  const float* weights = L.weights;
+  float* arena = L.arena;
+  const hipStream_t s = L.s;
   PwsArgs a;
   a.in = arena + op.in_off;
   a.out = arena + op.out_off;

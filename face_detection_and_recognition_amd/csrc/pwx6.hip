@@ -242,10 +242,6 @@ __global__ __launch_bounds__(256, MT_ == 4 ? 2 : 3) void pwx6_kernel(PwX6Args p)
 }
 
 // rounds of workgroups the large tiles need (512 slots): below 8, and with a last round less than 70 % full -> small tiles
-// K at or below which the small tiles are taken regardless of the round count (0 = never): with two or four K slabs a tile is
-// one HBM round trip + its MFMAs, and three co-resident workgroups with every slab of A in flight hide more of it than two.
-static int pwx6_small_maxk() { return fp_get_knobs().pwx6_small_maxk; }
-
 bool pwx6_small_tiles(long M, int nchunk) {
   const double rounds = (double)((M + BM - 1) / BM * nchunk) / 512.0;
   const double frac = rounds - (double)(long)rounds;
@@ -253,14 +249,16 @@ bool pwx6_small_tiles(long M, int nchunk) {
 }
 
 template <int NT16>
-int launch(const PwX6Args& a, hipStream_t s) {
+int launch(const PwX6Args& a, bool up, const fp_launch& L) {
   constexpr int lds = 2 * 3 * NT16 * 16 * 32 * 2;
   const long nchunk = a.N / (NT16 * 16);
   const long big = (a.M + BM - 1) / BM * nchunk;
   if (2 * big >= (1L << 31)) return FP_ERR_UNSUPPORTED;
-  const bool up = a.up != nullptr;
   // (the large-tile form with the second set of row pointers of an FP_OPF_IN_UP2 op needs 257 registers at 128-column chunks)
-  if (pwx6_small_tiles(a.M, (int)nchunk) || (up && NT16 == 8) || a.K <= pwx6_small_maxk()) {
+  const bool small = pwx6_small_tiles(a.M, (int)nchunk) || (up && NT16 == 8);
+  if (fp_dry_run(L, "pwx6_kernel<%d, %d, %s>", NT16, small ? 2 : 4, up ? "true" : "false")) return FP_OK;
+  const hipStream_t s = L.s;
+  if (small) {
     const long tiles = (a.M + BM / 2 - 1) / (BM / 2) * nchunk;
     if (up) hipLaunchKernelGGL((pwx6_kernel<NT16, 2, true>), dim3((unsigned)tiles), dim3(256), lds, s, a);
     else hipLaunchKernelGGL((pwx6_kernel<NT16, 2, false>), dim3((unsigned)tiles), dim3(256), lds, s, a);
@@ -467,11 +465,12 @@ __global__ __launch_bounds__(256, 2) void convx6_kernel(ConvX6Args p) {
 }
 
 template <int NT16>
-int launch_conv(const ConvX6Args& a, hipStream_t s) {
+int launch_conv(const ConvX6Args& a, const fp_launch& L) {
   constexpr int lds = 2 * 3 * NT16 * 16 * 32 * 2;
   const long tiles = (a.M + BM - 1) / BM * (a.Npad / (NT16 * 16));
   if (tiles >= (1L << 31)) return FP_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL((convx6_kernel<NT16>), dim3((unsigned)tiles), dim3(256), lds, s, a);
+  if (fp_dry_run(L, "convx6_kernel<%d>", NT16)) return FP_OK;
+  hipLaunchKernelGGL((convx6_kernel<NT16>), dim3((unsigned)tiles), dim3(256), lds, L.s, a);
   FP_CHECK_LAUNCH();
   return FP_OK;
 }
@@ -523,17 +522,10 @@ bool fp_pwx6_eligible(const fp_op& op) {
   return true;
 }
 
-long fp_pwx6_w_floats(const fp_op& op) { return (long)op.Cin * op.Cout * 3 / 2; }
-
-// 16-row tiles per wave the launcher will pick for this op at its current batch (kernel-name reporting)
-int fp_pwx6_mt(const fp_op& op) {
-  const int nt = chunk_tiles(op.Cout);
-  if ((nt == 8 && (op.flags & FP_OPF_IN_UP2)) || op.Cin <= pwx6_small_maxk()) return 2;
-  return nt && pwx6_small_tiles((long)op.N * op.H * op.W, op.Cout / (nt * 16)) ? 2 : 4;
-}
-
-int fp_launch_pwx6(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
+int fp_launch_pwx6(const fp_op& op, const fp_launch& L) {
   if (!fp_pwx6_eligible(op)) return FP_ERR_UNSUPPORTED;
+  const float* weights = L.weights;
+  float* arena = L.arena;
   PwX6Args a;
   memset(&a, 0, sizeof(a));
   a.in = arena + op.in_off;
@@ -562,10 +554,11 @@ int fp_launch_pwx6(const fp_op& op, const float* weights, float* arena, hipStrea
     a.hw_div = fp_make_divisor((unsigned)a.HW);
     a.w_div = fp_make_divisor((unsigned)op.W);
   }
+  const bool up = (op.flags & FP_OPF_IN_UP2) != 0;
   switch (chunk_tiles(op.Cout)) {
-    case 3: return launch<3>(a, s);
-    case 4: return launch<4>(a, s);
-    default: return launch<8>(a, s);
+    case 3: return launch<3>(a, up, L);
+    case 4: return launch<4>(a, up, L);
+    default: return launch<8>(a, up, L);
   }
 }
 
@@ -577,7 +570,7 @@ static bool convx6_shape(const fp_op& op) {
   return k3 || k1;
 }
 
-bool fp_convx6_eligible(const fp_op& op) {
+static bool convx6_eligible(const fp_op& op) {
   if (op.kind != FP_OP_CONV || !(op.flags & FP_OPF_SPLIT3) || (op.flags & ~(FP_OPF_SPLIT3 | FP_OPF_IN_UP2))) return false;
   if (op.flags & FP_OPF_IN_UP2) {
     if (op.KH != 1 || op.res_mode != FP_RES_NONE || op.res_C % 8 || op.res_C <= 0 || op.res_C >= op.Cin) return false;
@@ -602,12 +595,6 @@ bool fp_convx6_eligible(const fp_op& op) {
   return true;
 }
 
-int fp_convx6_nt16(const fp_op& op) {
-  int nt16, npad;
-  general_tiles(op.Cout, &nt16, &npad);
-  return nt16;
-}
-
 long fp_convx6_w_floats(const fp_op& op) {
   int nt16, npad;
   general_tiles(op.Cout, &nt16, &npad);
@@ -615,8 +602,10 @@ long fp_convx6_w_floats(const fp_op& op) {
   return slabs * 3 * npad * 32 / 2;
 }
 
-int fp_launch_convx6(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
-  if (!fp_convx6_eligible(op)) return FP_ERR_UNSUPPORTED;
+int fp_launch_convx6(const fp_op& op, const fp_launch& L) {
+  if (!convx6_eligible(op)) return FP_ERR_UNSUPPORTED;
+  const float* weights = L.weights;
+  float* arena = L.arena;
   ConvX6Args a;
   memset(&a, 0, sizeof(a));
   a.in = arena + op.in_off;
@@ -645,9 +634,9 @@ int fp_launch_convx6(const fp_op& op, const float* weights, float* arena, hipStr
   int nt16;
   general_tiles(op.Cout, &nt16, &a.Npad);
   switch (nt16) {
-    case 2: return launch_conv<2>(a, s);
-    case 3: return launch_conv<3>(a, s);
-    case 4: return launch_conv<4>(a, s);
-    default: return launch_conv<6>(a, s);
+    case 2: return launch_conv<2>(a, L);
+    case 3: return launch_conv<3>(a, L);
+    case 4: return launch_conv<4>(a, L);
+    default: return launch_conv<6>(a, L);
   }
 }

@@ -285,7 +285,7 @@ static void stem_fill(const fp_op& op, const float* weights, float* arena, StemA
 }
 
 template <bool U8>
-static int stem_launch(const fp_op& op, const StemArgs& a, hipStream_t s) {
+static int stem_launch(const fp_op& op, const StemArgs& a, const fp_launch& L) {
   const size_t lds = stem_lds_bytes(a.rows_max, a.Wp, a.Kpad, a.Npad, op.Cout, U8 ? op.H + op.W : 0);
   int per_cu = (int)(160 * 1024 / lds);   // resident workgroups per CU by LDS (registers allow 3)
   const int cap = 3;
@@ -293,6 +293,9 @@ static int stem_launch(const fp_op& op, const StemArgs& a, hipStream_t s) {
   int grid = 256 * per_cu;
   if (grid > a.ntiles) grid = a.ntiles;
   const int NB = a.Npad / 32;
+  if ((op.KH != 3 && op.KH != 5) || (NB != 1 && NB != 2)) return FP_ERR_UNSUPPORTED;
+  if (fp_dry_run(L, "stem_conv_kernel<%d, %d, %s>", op.KH, NB, U8 ? "true" : "false")) return FP_OK;
+  const hipStream_t s = L.s;
   hipError_t ae = hipSuccess;
 #define FP_STEM_CASE(KSV, NBV)                                                                                       \
   {                                                                                                                  \
@@ -304,8 +307,7 @@ static int stem_launch(const fp_op& op, const StemArgs& a, hipStream_t s) {
   if (op.KH == 3 && NB == 1) FP_STEM_CASE(3, 1)
   else if (op.KH == 3 && NB == 2) FP_STEM_CASE(3, 2)
   else if (op.KH == 5 && NB == 1) FP_STEM_CASE(5, 1)
-  else if (op.KH == 5 && NB == 2) FP_STEM_CASE(5, 2)
-  else return FP_ERR_UNSUPPORTED;
+  else FP_STEM_CASE(5, 2)
 #undef FP_STEM_CASE
   if (ae != hipSuccess) {
     fp_set_hip_error(ae);
@@ -315,38 +317,42 @@ static int stem_launch(const fp_op& op, const StemArgs& a, hipStream_t s) {
   return FP_OK;
 }
 
-int fp_launch_stem(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
+int fp_launch_stem(const fp_op& op, const fp_launch& L) {
   StemArgs a;
-  stem_fill(op, weights, arena, a);
-  a.in = arena + op.in_off;
-  return stem_launch<false>(op, a, s);
+  stem_fill(op, L.weights, L.arena, a);
+  a.in = L.arena + op.in_off;
+  return stem_launch<false>(op, a, L);
 }
 
-bool fp_stem_u8_band_eligible(const fp_op& op);
-int fp_launch_stem_u8_band(const fp_op& op, const float* weights, float* arena, const fp_ext* ext, hipStream_t s);
+static bool stem_u8_band_eligible(const fp_op& op);
+static int launch_stem_u8_band(const fp_op& op, const fp_launch& L);
 
 // FP_OP_STEM_U8 (include/facepath.h): the same conv with the H x W input resampled from u8 frames while it is staged.
-bool fp_stem_u8_shape_ok(const fp_op& op) { return op.H + op.W <= 2048 && stem_shape_ok(op, op.H + op.W); }
-
-int fp_launch_stem_u8(const fp_op& op, const float* weights, float* arena, const fp_ext* ext, int n_ext, hipStream_t s) {
+// The ext buffers are checked at launch only: a dry run has none.
+int fp_launch_stem_u8(const fp_op& op, const fp_launch& L) {
+  const fp_ext* ext = L.ext;
   const long e = op.in_off;
-  if (e < 0 || e + 2 >= n_ext || !ext) return FP_ERR_INVALID_ARG;
+  if (!L.dry && (e < 0 || e + 2 >= L.n_ext || !ext)) return FP_ERR_INVALID_ARG;
   const int fh = op.res_H, fw = op.res_W;
-  if (op.Cin != 3 || fh <= 0 || fw < 3 || !fp_stem_u8_shape_ok(op)) return FP_ERR_UNSUPPORTED;
-  if (ext[e].bytes < (size_t)op.N * fh * fw * 3 || ext[e + 1].bytes < (size_t)(op.H + op.W + 2) * 8 ||
-      ext[e + 2].bytes < 256 * sizeof(float) || !ext[e].ptr || !ext[e + 1].ptr || !ext[e + 2].ptr)
+  if (op.Cin != 3 || fh <= 0 || fw < 3 || op.H + op.W > 2048 || !stem_shape_ok(op, op.H + op.W)) return FP_ERR_UNSUPPORTED;
+  if (!L.dry && (ext[e].bytes < (size_t)op.N * fh * fw * 3 || ext[e + 1].bytes < (size_t)(op.H + op.W + 2) * 8 ||
+                 ext[e + 2].bytes < 256 * sizeof(float) || !ext[e].ptr || !ext[e + 1].ptr || !ext[e + 2].ptr))
     return FP_ERR_BOUNDS;
-  if (fp_stem_u8_band_eligible(op)) return fp_launch_stem_u8_band(op, weights, arena, ext, s);
+  if (stem_u8_band_eligible(op)) return launch_stem_u8_band(op, L);
+  // a row window and the split-MFMA form exist in the band kernel only
+  if (op.row_end || (op.flags & FP_OPF_SPLIT3)) return FP_ERR_UNSUPPORTED;
   StemArgs a;
-  stem_fill(op, weights, arena, a);
-  a.frames = (const uint8_t*)ext[e].ptr;
-  a.tabs = (const fp_lb_tap*)ext[e + 1].ptr;
-  a.lut = (const float*)ext[e + 2].ptr;
+  stem_fill(op, L.weights, L.arena, a);
+  if (!L.dry) {
+    a.frames = (const uint8_t*)ext[e].ptr;
+    a.tabs = (const fp_lb_tap*)ext[e + 1].ptr;
+    a.lut = (const float*)ext[e + 2].ptr;
+  }
   a.row_bytes = (long)fw * 3;
   a.frame_bytes = (long)fh * fw * 3;
   a.frame_h = fh;
   a.frame_w = fw;
-  return stem_launch<true>(op, a, s);
+  return stem_launch<true>(op, a, L);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -660,13 +666,19 @@ __global__ __launch_bounds__(256, 3) void stem5_u8_x6_kernel(StemBandArgs p) {
 
 }  // namespace
 
-bool fp_stem_u8_band_eligible(const fp_op& op) {
+static bool stem_u8_band_eligible(const fp_op& op) {
   return op.kind == FP_OP_STEM_U8 && op.KH == 5 && op.KW == 5 && op.stride == 2 && op.pad_t == 1 && op.pad_l == 1 &&
          op.H == SB_W && op.W == SB_W && op.OH == SB_OW && op.OW == SB_OW && op.Cout == SB_C && op.out_ld == SB_C &&
          op.scale_off < 0 && op.bias_off >= 0 && op.act == FP_ACT_RELU && op.res_mode == FP_RES_NONE && op.N >= 16;
 }
 
-int fp_launch_stem_u8_band(const fp_op& op, const float* weights, float* arena, const fp_ext* ext, hipStream_t s) {
+static int launch_stem_u8_band(const fp_op& op, const fp_launch& L) {
+  const bool x6 = (op.flags & FP_OPF_SPLIT3) != 0;
+  if (fp_dry_run(L, x6 ? "stem5_u8_x6_kernel" : "stem5_u8_band_kernel")) return FP_OK;
+  const float* weights = L.weights;
+  float* arena = L.arena;
+  const fp_ext* ext = L.ext;
+  const hipStream_t s = L.s;
   const long e = op.in_off;
   StemBandArgs a;
   a.out = arena + op.out_off;
@@ -697,7 +709,7 @@ int fp_launch_stem_u8_band(const fp_op& op, const float* weights, float* arena, 
     a.lo = 0;
     a.span = SB_OW - a.R;
   }
-  if (op.flags & FP_OPF_SPLIT3) {
+  if (x6) {
     const size_t lds6 = (size_t)3 * SX_PL * 2 + 256 * 4 + 8 * (size_t)(2 * SB_W);
     hipLaunchKernelGGL(stem5_u8_x6_kernel, dim3(op.N * a.bands), dim3(256), lds6, s, a);
     FP_CHECK_LAUNCH();

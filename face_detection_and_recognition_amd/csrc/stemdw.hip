@@ -282,7 +282,7 @@ __global__ __launch_bounds__(256, 2) void stemdw_kernel(StemDwArgs p) {
 }  // namespace
 
 // Mobile-FaceNet's conv1 with conv2_dw behind it: FP_OP_CONV + FP_OPF_OUT_DW on a dense 112 x 112 four-float-pixel image.
-bool fp_stemdw_supported(const fp_op& op) {
+static bool stemdw_supported(const fp_op& op) {
   if (op.kind != FP_OP_CONV || !(op.flags & FP_OPF_OUT_DW) || !(op.flags & FP_OPF_IN_C3)) return false;
   if (op.flags & ~(FP_OPF_OUT_DW | FP_OPF_IN_C3 | FP_OPF_SPLIT3)) return false;
   if (op.H != SD_H || op.W != SD_H || op.OH != SD_OH || op.OW != SD_OH || op.Cin != 4 || op.Cout != SD_C) return false;
@@ -297,8 +297,13 @@ bool fp_stemdw_supported(const fp_op& op) {
 // floats behind w_off: the packed fp32 weights (40 x 64), or with FP_OPF_SPLIT3 three bf16 planes [4][3][16][32]
 long fp_stemdw_w_floats(const fp_op& op) { return (op.flags & FP_OPF_SPLIT3) ? 4 * 3 * 16 * 32 / 2 : 40 * 64; }
 
-int fp_launch_stemdw(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
-  if (!fp_stemdw_supported(op)) return FP_ERR_UNSUPPORTED;
+int fp_launch_stemdw(const fp_op& op, const fp_launch& L) {
+  if (!stemdw_supported(op)) return FP_ERR_UNSUPPORTED;
+  const bool x6 = (op.flags & FP_OPF_SPLIT3) != 0;
+  if (fp_dry_run(L, x6 ? "stemdw_kernel<true>" : "stemdw_kernel<false>")) return FP_OK;
+  const float* weights = L.weights;
+  float* arena = L.arena;
+  const hipStream_t s = L.s;
   StemDwArgs a;
   a.in = arena + op.in_off;
   a.out = arena + op.out_off;
@@ -310,7 +315,6 @@ int fp_launch_stemdw(const fp_op& op, const float* weights, float* arena, hipStr
   a.in_ns = op.in_ns;
   a.out_ns = op.out_ns;
   a.N = op.N;
-  const bool x6 = (op.flags & FP_OPF_SPLIT3) != 0;
   const hipError_t ae = hipFuncSetAttribute(x6 ? (const void*)stemdw_kernel<true> : (const void*)stemdw_kernel<false>,
                                             hipFuncAttributeMaxDynamicSharedMemorySize, SD_LDS);
   if (ae != hipSuccess) {

@@ -292,8 +292,10 @@ static int ystem_fill(const fp_op& op, const float* weights, float* arena, YStem
 }
 
 template <bool U8>
-static int ystem_launch(const fp_op& op, const YStemArgs& a, hipStream_t s) {
+static int ystem_launch(const fp_op& op, const YStemArgs& a, const fp_launch& L) {
   const int nb2 = fp_ystem_nb2(op);
+  if (fp_dry_run(L, "ystem_kernel<%d, %s>", nb2, U8 ? "true" : "false")) return FP_OK;
+  const hipStream_t s = L.s;
   const size_t lds = ystem_lds_bytes(nb2, U8 ? op.H + op.W : 0);
   int grid = 512;                             // two workgroups per CU (LDS ~63 KiB each), persistent
   if (grid > a.ntiles) grid = a.ntiles;
@@ -313,37 +315,42 @@ static int ystem_launch(const fp_op& op, const YStemArgs& a, hipStream_t s) {
   return FP_OK;
 }
 
-int fp_launch_ystem(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
+int fp_launch_ystem(const fp_op& op, const fp_launch& L) {
   if (op.Cin != 4 || op.in_ld != 4 || op.in_off % 4 || op.in_ns % 4) return FP_ERR_UNSUPPORTED;
   if (op.res_H != op.OH / 2 || op.res_W != op.OW / 2) return FP_ERR_UNSUPPORTED;
   YStemArgs a;
-  const int rc = ystem_fill(op, weights, arena, a);
+  const int rc = ystem_fill(op, L.weights, L.arena, a);
   if (rc != FP_OK) return rc;
-  a.in = arena + op.in_off;
+  a.in = L.arena + op.in_off;
   a.c4 = (op.flags & FP_OPF_IN_C3) ? 0 : 1;
-  return ystem_launch<false>(op, a, s);
+  return ystem_launch<false>(op, a, L);
 }
 
-// FP_OP_YSTEM_U8: the same op reading the u8 frames through the letterbox tap tables (include/facepath.h).
-int fp_launch_ystem_u8(const fp_op& op, const float* weights, float* arena, const fp_ext* ext, int n_ext, hipStream_t s) {
+// FP_OP_YSTEM_U8: the same op reading the u8 frames through the letterbox tap tables (include/facepath.h).  The ext
+// buffers are checked at launch only: a dry run has none.
+int fp_launch_ystem_u8(const fp_op& op, const fp_launch& L) {
+  const fp_ext* ext = L.ext;
   const long e = op.in_off;
-  if (e < 0 || e + 2 >= n_ext || !ext) return FP_ERR_INVALID_ARG;
+  if (!L.dry && (e < 0 || e + 2 >= L.n_ext || !ext)) return FP_ERR_INVALID_ARG;
   const int fh = op.res_H, fw = op.res_W;
   if (op.Cin != 3 || fh <= 0 || fw < 3) return FP_ERR_INVALID_ARG;
-  if (ext[e].bytes < (size_t)op.N * fh * fw * 3 || ext[e + 1].bytes < (size_t)(op.H + op.W + 2) * 8 || op.H + op.W > 2048 ||
-      ext[e + 2].bytes < 256 * sizeof(float) || !ext[e].ptr || !ext[e + 1].ptr || !ext[e + 2].ptr)
+  if (op.H + op.W > 2048) return FP_ERR_BOUNDS;
+  if (!L.dry && (ext[e].bytes < (size_t)op.N * fh * fw * 3 || ext[e + 1].bytes < (size_t)(op.H + op.W + 2) * 8 ||
+                 ext[e + 2].bytes < 256 * sizeof(float) || !ext[e].ptr || !ext[e + 1].ptr || !ext[e + 2].ptr))
     return FP_ERR_BOUNDS;
   YStemArgs a;
-  const int rc = ystem_fill(op, weights, arena, a);
+  const int rc = ystem_fill(op, L.weights, L.arena, a);
   if (rc != FP_OK) return rc;
-  a.frames = (const uint8_t*)ext[e].ptr;
-  a.xtab = (const fp_lb_tap*)ext[e + 1].ptr;
-  a.ytab = a.xtab + op.W;
-  a.lut = (const float*)ext[e + 2].ptr;
+  if (!L.dry) {
+    a.frames = (const uint8_t*)ext[e].ptr;
+    a.xtab = (const fp_lb_tap*)ext[e + 1].ptr;
+    a.ytab = a.xtab + op.W;
+    a.lut = (const float*)ext[e + 2].ptr;
+  }
   a.row_bytes = (long)fw * 3;
   a.frame_bytes = (long)fh * fw * 3;
   a.frame_h = fh;
   a.frame_w = fw;
   a.c4 = 0;
-  return ystem_launch<true>(op, a, s);
+  return ystem_launch<true>(op, a, L);
 }

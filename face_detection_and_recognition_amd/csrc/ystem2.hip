@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256, 2) void ystem2_x6_kernel(YStem2Args p) {
 }  // namespace
 
 // FP_OP_YSTEM2: in = a (H x W even, 16 channels), res = the pooled map (OH x OW, 32 channels), out 32 channels, 3x3 stride 2 pad 1.
-bool fp_ystem2_supported(const fp_op& op) {
+static bool ystem2_supported(const fp_op& op) {
   if (op.kind != FP_OP_YSTEM2 || op.flags != FP_OPF_SPLIT3) return false;
   if (op.Cin != 16 || op.Cout != 32 || op.res_C != 32 || op.Cmid != 0) return false;
   if (op.KH != 3 || op.KW != 3 || op.stride != 2 || op.pad_t != 1 || op.pad_l != 1) return false;
@@ -217,14 +217,15 @@ bool fp_ystem2_supported(const fp_op& op) {
 
 long fp_ystem2_w_floats(const fp_op&) { return YS2::TOTAL; }
 
-int fp_launch_ystem2(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
-  if (!fp_ystem2_supported(op)) return FP_ERR_UNSUPPORTED;
+int fp_launch_ystem2(const fp_op& op, const fp_launch& L) {
+  if (!ystem2_supported(op)) return FP_ERR_UNSUPPORTED;
+  if (fp_dry_run(L, "ystem2_x6_kernel")) return FP_OK;
   YStem2Args a;
   memset(&a, 0, sizeof(a));
-  a.a = arena + op.in_off;
-  a.pool = arena + op.res_off;
-  a.out = arena + op.out_off;
-  a.w = weights + op.w_off;
+  a.a = L.arena + op.in_off;
+  a.pool = L.arena + op.res_off;
+  a.out = L.arena + op.out_off;
+  a.w = L.weights + op.w_off;
   a.H = op.H; a.W = op.W; a.OH = op.OH; a.OW = op.OW;
   a.a_ld = op.in_ld; a.p_ld = op.res_ld; a.out_ld = op.out_ld;
   a.a_ns = op.in_ns; a.p_ns = op.res_ns; a.out_ns = op.out_ns;
@@ -237,7 +238,7 @@ int fp_launch_ystem2(const fp_op& op, const float* weights, float* arena, hipStr
     return FP_ERR_LAUNCH;
   }
   const int grid = a.ntiles < 512 ? a.ntiles : 512;       // persistent: two workgroups per CU, contiguous runs of tiles
-  hipLaunchKernelGGL(ystem2_x6_kernel, dim3((unsigned)grid), dim3(256), YS2::LDS_BYTES, s, a);
+  hipLaunchKernelGGL(ystem2_x6_kernel, dim3((unsigned)grid), dim3(256), YS2::LDS_BYTES, L.s, a);
   FP_CHECK_LAUNCH();
   return FP_OK;
 }

@@ -51,9 +51,8 @@ const char* fp_last_hip_error(void);
  */
 int fp_selftest(void);
 /*
- * Lab / test knobs (FP_CHAIN_GRID, FP_RESIZE_PER_PIXEL, FP_X6_QUARTER14, FP_X6_SPEC14, FP_PWX6_SMALL_MAXK) are read from
- * the environment ONCE, when the library is loaded; no launch calls getenv.  This re-reads them (tests that switch a
- * knob at run time call it after changing the environment).  Not for production use: it is the library's only
+ * The test knob FP_RESIZE_PER_PIXEL is read from the environment ONCE, when the library is loaded; no launch calls
+ * getenv.  This re-reads it (tests that switch it at run time call this after changing the environment).  Not for production use: it is the library's only
  * process-wide mutable state, and it must not be called while another thread is launching.
  */
 void fp_debug_reload_env(void);
@@ -335,7 +334,12 @@ int fp_plan_run_ext(const fp_op* ops /*host*/, int n_ops,
                     float* arena, size_t arena_floats,
                     const fp_ext* ext /*host*/, int n_ext, void* stream);
 
-/* Validation only (no GPU needed): same checks as fp_plan_run. */
+/*
+ * Validation only (no GPU needed): the checks fp_plan_run makes before its first launch, which end with each op's
+ * launcher deciding, without launching, whether it takes the op.  A plan that validates is refused at launch only for
+ * an fp_ext buffer it is given at run time (the frame, tap-table and LUT sizes of FP_OP_STEM_U8 / FP_OP_YSTEM_U8) or a
+ * HIP error.
+ */
 int fp_plan_validate(const fp_op* ops /*host*/, int n_ops, size_t weight_floats, size_t arena_floats);
 
 /*
@@ -356,7 +360,8 @@ int fp_plan_run_timed_ext(const fp_op* ops /*host*/, int n_ops,
                           const fp_ext* ext /*host*/, int n_ext,
                           void* stream, void* timer, const unsigned char* op_mask /*host, n_ops*/);
 int fp_timer_accumulate(void* timer, float* ms_accum /*host, n_ops*/, int n_ops);
-/* Name of the HIP kernel family an op launches (as rocprofv3's kernel trace shows it); thread-local buffer. */
+/* Name of the HIP kernel instance an op launches (as rocprofv3's kernel trace shows it), the launcher's own choice; "?" for
+ * an op its launcher refuses.  Thread-local buffer. */
 const char* fp_op_kernel_name(const fp_op* op /*host*/);
 
 /* ------------------------------------------------------------------------- */

@@ -615,3 +615,52 @@ def test_upsample_fold_plan_and_validation(lib):
     finally:
         Model.FOLD_UPSAMPLE = True
     assert names_u.count("upsample2x_kernel") == 2 and not any(n.endswith("true>") and n.startswith("pwx6") for n in names_u)
+
+
+def test_validate_refuses_what_the_launchers_refuse(lib):
+    """fp_plan_validate ends with the launcher's own checks (a dry run, csrc/common.h fp_launch): an op it accepts is one
+    the launcher launches, and an op the launcher would refuse half-way through a plan is refused up front with the
+    launcher's status."""
+    from face_detection_and_recognition_amd.modules.mobile_facenet.mobile_facenet import Depth_Wise
+    from face_detection_and_recognition_amd.modules.yolov5_face.yolo import Model
+
+    def emit(cls, attr, value, make):
+        old = getattr(cls, attr)
+        setattr(cls, attr, value)
+        try:
+            return make().finish()
+        finally:
+            setattr(cls, attr, old)
+
+    def rc_after(plan, pick, edit):
+        ops, weights, arena = plan
+        arr = (L.FpOp * len(ops))(*ops)
+        assert lib.fp_plan_validate(arr, len(ops), weights.size, arena) == 0
+        idx = [i for i, op in enumerate(ops) if pick(op)]
+        assert idx
+        for i in idx:
+            edit(arr[i])
+        return lib.fp_plan_validate(arr, len(ops), weights.size, arena)
+
+    def named(prefix):
+        return lambda op: lib.fp_op_kernel_name(ctypes.byref(op)).decode().startswith(prefix)
+
+    def shift(field, by):
+        return lambda op: setattr(op, field, getattr(op, field) + by)
+
+    # fp32 Depth_Wise blocks: dwpw_kernel reads 16-byte pixels
+    mfn = emit(Depth_Wise, "X6", False, lambda: MobileFaceNet(512)._emit(64)[0])
+    assert rc_after(mfn, named("dwpw_kernel<"), shift("in_off", 1)) == -5                  # FP_ERR_ALIGNMENT
+    # dense BlazeBlocks: the output image stride must be the dense one
+    bf = emit(BlazeBlock, "ROWPAD", False, lambda: BlazeFace(True)._emit(32)[0])
+    assert rc_after(bf, lambda op: op.kind == L.OP_BLAZEBLOCK, shift("out_ns", -4)) == -3  # FP_ERR_UNSUPPORTED
+    # unfused depthwise convs: 16-byte aligned views
+    bf = emit(BlazeBlock, "FUSE", False, lambda: BlazeFace(False)._emit(8)[0])
+    assert rc_after(bf, lambda op: op.kind == L.OP_DWCONV, shift("in_off", 1)) == -5
+    # stand-alone 2x upsampling: the output map is twice the input's
+    yolo = emit(Model, "FOLD_UPSAMPLE", False, lambda: Model("yolov5n")._emit(1, 640, 640)[0])
+    assert rc_after(yolo, lambda op: op.kind == L.OP_UPSAMPLE2X, shift("OH", -2)) == -1    # FP_ERR_INVALID_ARG
+    # an op a launcher refuses has no kernel name
+    op = mfn[0][[i for i, o in enumerate(mfn[0]) if named("dwpw_kernel<")(o)][0]]
+    op.in_off += 1
+    assert lib.fp_op_kernel_name(ctypes.byref(op)).decode() == "?"

@@ -13,6 +13,7 @@
 #include <vector>
 
 void fp_set_hip_error(hipError_t e) { fprintf(stderr, "hip error: %s\n", hipGetErrorString(e)); }
+bool fp_dry_run(const fp_launch&, const char*, ...) { return false; }   // (capi.cpp is not linked into the lab binary)
 
 int main(int argc, char** argv) {
   const int HW = argc > 1 ? atoi(argv[1]) : 28, G = argc > 2 ? atoi(argv[2]) : 128, Cout = argc > 3 ? atoi(argv[3]) : 64;
@@ -36,6 +37,7 @@ int main(int argc, char** argv) {
   op.out_off = in_elems; op.out_ld = Cout; op.out_ns = (long)OHW * OHW * Cout; op.out_cmul = 1;
   op.res_off = in_elems + out_elems; op.res_ld = Cout; op.res_ns = op.out_ns; op.res_C = Cout;
   op.w_off = 0; op.slope_off = dw_elems; op.bias_off = -1; op.scale_off = -1;
+  const fp_launch L = {weights, arena, nullptr, 0, 0, false, nullptr};
   unsigned long long* stamps;
   const size_t ns = 4 * 4 * FP_DWPW_NUNIT * FP_DWPW_NSTAMP;
   hipMalloc(&stamps, ns * 8);
@@ -44,9 +46,9 @@ int main(int argc, char** argv) {
   hipEventCreate(&e0); hipEventCreate(&e1);
   g_dwpw_stamps = nullptr;
   int rc = 0;
-  for (int i = 0; i < 3; ++i) rc |= fp_launch_dwpw(op, weights, arena, 0);
+  for (int i = 0; i < 3; ++i) rc |= fp_launch_dwpw(op, L);
   hipEventRecord(e0);
-  for (int i = 0; i < 10; ++i) rc |= fp_launch_dwpw(op, weights, arena, 0);
+  for (int i = 0; i < 10; ++i) rc |= fp_launch_dwpw(op, L);
   hipEventRecord(e1);
   hipEventSynchronize(e1);
   float ms;
@@ -54,7 +56,7 @@ int main(int argc, char** argv) {
   printf("dwpw %dx%d G=%d Cout=%d s%d: %.1f us per launch rc=%d err=%s\n", HW, HW, G, Cout, stride, ms * 100, rc,
          hipGetErrorString(hipGetLastError()));
   g_dwpw_stamps = stamps;
-  fp_launch_dwpw(op, weights, arena, 0);
+  fp_launch_dwpw(op, L);
   hipDeviceSynchronize();
   std::vector<unsigned long long> h(ns);
   hipMemcpy(h.data(), stamps, ns * 8, hipMemcpyDeviceToHost);

@@ -66,6 +66,7 @@ class FpFrameDesc(C.Structure):
 
 FRAME_MIN_W, FRAME_MAX_W, FRAME_MAX_H = 3, 32767, 65535   # fp_frame_desc sizes the ragged kernels take
 RAGGED_U8, RAGGED_F32_LUT = 0, 1                           # fp_resize_ragged output modes
+ALIGN_SIZE, ALIGN_DEGENERATE = 112, 1                      # fp_align_warp canvas side, fp_dets_to_crops_aligned flag
 
 
 class FpJpegInfo(C.Structure):
@@ -132,6 +133,15 @@ SIGNATURES = {
     "fp_resize_ragged": (_I, [_P, _SZ, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
     "fp_dets_to_crops_ragged": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P,
                                        _P]),
+    "fp_dets_to_crops_aligned": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I,
+                                        _P, _P, _P, _P, _P, _P, _P]),
+    "fp_dets_to_crops_aligned_ragged": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P,
+                                               _P, _P, _P, _P, _P, _P]),
+    "fp_dets_to_crops_aligned_emulate": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P,
+                                                _P, _P, _P, _P, _P]),
+    "fp_align_warp": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P]),
+    "fp_align_warp_ragged": (_I, [_P, _SZ, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P]),
+    "fp_align_emulate": (_I, [_P, _SZ, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P]),
     "fp_blaze_decode": (_I, [_P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P]),
     "fp_blaze_weighted_nms": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P]),
     "fp_yolo_decode": (_I, [_P, _I, _I, _I, _I, _F, C.POINTER(_F), _P, _I64, _I64, _P]),

@@ -41,12 +41,14 @@ class FrameFacesObj:
 
 
 def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=None, save_face=False,
-                                     quality=95) -> List[FrameFacesObj]:
+                                     quality=95, align=False) -> List[FrameFacesObj]:
     """frames: (B, H, W, 3) u8 BGR (numpy or CUDA tensor), a RaggedFrames, or a list of (h, w, 3) frames.  One FacePipeline
     step (no similarity filter needed); returns per-frame records with boxes (each frame's own pixels, rounded), confs,
     area fractions and embeddings.  A list whose frames share one size is stacked and takes the uniform path; otherwise it
     is packed into a RaggedFrames.  save_face: also encode every face crop (the reference's image[y:yh, x:xw]) to a JPEG
-    file of that quality, in one device call."""
+    file of that quality, in one device call.  align: embed each face warped onto the five-point template
+    (FacePipeline(align=True) for this call, modules/utils/align.py); with save_face the files are then the 112 x 112
+    aligned faces the embedder saw (as u8), under the same names."""
     if isinstance(frames, (list, tuple)):
         if not frames:
             return []
@@ -60,14 +62,26 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
     if not isinstance(frames, RaggedFrames):
         frames = frames.to(pipe.dev).contiguous()
     B = len(frames)
-    res = pipe.step(frames)                   # detect -> crops -> embed (+ the exact re-run on a detector overflow)
+    if align and not pipe.align:
+        pipe.align = True
+        try:
+            res = pipe.step(frames)
+        finally:
+            pipe.align = False
+    else:
+        res = pipe.step(frames)               # detect -> crops -> embed (+ the exact re-run on a detector overflow)
     n = res["n_faces"]
     emb = res["emb"].cpu().numpy()
     info = res["info"].cpu().numpy()
     jpegs = None
     if save_face:
-        from ..modules.utils.jpeg import encode_crops
-        jpegs = encode_crops(frames, res["items"], n, quality=quality)
+        from ..modules.utils.jpeg import encode_crops, encode_jpeg_batch
+        if "align_M" in res:
+            from ..modules.utils.align import warp_u8
+            faces = warp_u8(frames, res["align_M"], res["info"], res["align_flags"], res["items"], n)
+            jpegs = encode_jpeg_batch(list(faces), quality=quality)
+        else:
+            jpegs = encode_crops(frames, res["items"], n, quality=quality)
     out = [FrameFacesObj(frame_nums[i] if frame_nums is not None else i,
                          times_sec[i] if times_sec is not None else 0.0, [], [], np.zeros((0, 4), np.float32))
            for i in range(B)]
@@ -87,17 +101,18 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
     return out
 
 
-def extract_faces_from_images(pipe, paths, batch_size=256, entropy="host", save_face=False, quality=95) -> List[FrameFacesObj]:
+def extract_faces_from_images(pipe, paths, batch_size=256, entropy="host", save_face=False, quality=95,
+                              align=False) -> List[FrameFacesObj]:
     """The reference's image media items (:400-407: one photo per item, any size, recorded as FrameFacesObj(1, 1, ...)) for a
     whole list of files: decode batch_size files at a time (modules/utils/jpeg.py imread_batch; entropy as there), then one
     pipeline step per batch -- frames of different sizes as one RaggedFrames.  Returns one record per path, in order; pass
-    each to save_extracted_faces under its file's media_root."""
+    each to save_extracted_faces under its file's media_root.  align: as extract_face_feat_conf_area_list."""
     from ..modules.utils.jpeg import imread_batch
     out = []
     for i in range(0, len(paths), int(batch_size)):
         chunk = paths[i:i + int(batch_size)]
         frames = imread_batch(chunk, pipe.dev, entropy=entropy)     # (B, H, W, 3) when the sizes agree, else a list
-        recs = extract_face_feat_conf_area_list(pipe, frames, save_face=save_face, quality=quality)
+        recs = extract_face_feat_conf_area_list(pipe, frames, save_face=save_face, quality=quality, align=align)
         for r in recs:
             r.frame_num, r.time_sec = 1, 1
         out.extend(recs)

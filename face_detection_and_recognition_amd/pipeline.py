@@ -14,6 +14,7 @@ from . import _lib as L
 from . import similarity as S
 from .frames import RaggedFrames
 from .modules.mobile_facenet.utils import crops_to_input, mfn_lut
+from .modules.utils import align as A
 from .modules.utils.image import letterbox_geometry
 
 FACE_OFFSETS = (-6, -1, 4, 5)   # tx, ty, bx, by  (extract_faces_from_dataset.py:285-287)
@@ -36,7 +37,9 @@ def ragged_scale_coords_params(in_size, sizes):
 
 class FacePipeline:
     """detector: a BlazeFaceModel or YOLOV5FaceModel (HIP); embedder: a HIP MobileFaceNet;
-    reference: (Nr, E) CUDA tensor of reference embeddings for the cosine filter (or None)."""
+    reference: (Nr, E) CUDA tensor of reference embeddings for the cosine filter (or None).
+    align: feed the embedder each face warped onto the five-point template (modules/utils/align.py) instead of its
+    stretched box crop; step results then also carry lmarks, align_M and align_flags."""
 
     # embed(): a batch a little above a multiple of ROUND_CROPS crops is run as that multiple + the remainder on a side stream
     ROUND_CROPS = 512     # crops whose tiles fill whole rounds of workgroups in every Depth_Wise kernel (2 / 4 / 7 tiles per crop, 512 slots)
@@ -44,8 +47,9 @@ class FacePipeline:
     TAIL_CAP = 128        # capacity of the remainder's plan
 
     def __init__(self, detector, embedder, reference=None, tau=0.3, max_faces_per_frame=8, bucket=8, two_streams=False,
-                 split_tail=True):
+                 split_tail=True, align=False):
         self.det = detector
+        self.align = bool(align)
         self.emb = embedder
         self.tau = float(tau)
         self.max_faces_per_frame = int(max_faces_per_frame)
@@ -81,7 +85,12 @@ class FacePipeline:
 
     def crops(self, frames, dets, counts):
         """Device-side B7 + crop arithmetic -> (items, info, n_faces tensor).  frames: (B, H, W, 3) or a RaggedFrames
-        (each frame's boxes in its own pixels: per-frame scale_coords values, the same fp32 numbers as a frame alone)."""
+        (each frame's boxes in its own pixels: per-frame scale_coords values, the same fp32 numbers as a frame alone).
+        With align: (items, info, n_faces, al), al = dict(lmarks, M, flags) of fp_dets_to_crops_aligned."""
+        out = self._crops(frames, dets, counts)
+        return out if self.align else out[:3]
+
+    def _crops(self, frames, dets, counts):
         lib = L.load()
         B = len(frames) if isinstance(frames, RaggedFrames) else frames.shape[0]
         cap = B * self.max_faces_per_frame
@@ -92,29 +101,54 @@ class FacePipeline:
         fmt = getattr(self.det, "dets_fmt", 0)
         row = dets.shape[-1]
         tx, ty, bx, by = FACE_OFFSETS
+        al = A.alloc(cap, self.dev) if self.align else None
+        if al is not None and (fmt == 1 and row < 15):
+            raise L.FacepathError(f"align=True needs detector rows with landmarks (got {row} columns)")
         if isinstance(frames, RaggedFrames):
             geom = frames.cached(("scale_coords", iw, ih), lambda: torch.from_numpy(ragged_scale_coords_params(
                 (iw, ih), frames.sizes)).to(self.dev))
+            if al is not None:
+                L.check(lib.fp_dets_to_crops_aligned_ragged(
+                    L.ptr(dets), L.ptr(counts), B, dets.shape[1], row, fmt, iw, ih, L.ptr(frames.descs), L.ptr(geom),
+                    float(self.det.det_thres), float(self.det.bbox_area_thres), tx, ty, bx, by, 112, 112, cap, L.ptr(items),
+                    L.ptr(info), L.ptr(nf), L.ptr(al["lmarks"]), L.ptr(al["M"]), L.ptr(al["flags"]),
+                    L.current_stream(self.dev)), "fp_dets_to_crops_aligned_ragged")
+                return items, info, nf, al
             L.check(lib.fp_dets_to_crops_ragged(L.ptr(dets), L.ptr(counts), B, dets.shape[1], row, fmt, iw, ih,
                                                 L.ptr(frames.descs), L.ptr(geom), float(self.det.det_thres),
                                                 float(self.det.bbox_area_thres), tx, ty, bx, by, 112, 112, cap,
                                                 L.ptr(items), L.ptr(info), L.ptr(nf), L.current_stream(self.dev)),
                     "fp_dets_to_crops_ragged")
-            return items, info, nf
+            return items, info, nf, None
         _, H, W, _ = frames.shape
         gain, px, py = scale_coords_params((iw, ih), (W, H))
+        if al is not None:
+            L.check(lib.fp_dets_to_crops_aligned(L.ptr(dets), L.ptr(counts), B, dets.shape[1], row, fmt, iw, ih, W, H,
+                                                 float(self.det.det_thres), float(self.det.bbox_area_thres), float(gain),
+                                                 float(px), float(py), tx, ty, bx, by, 112, 112, cap, L.ptr(items),
+                                                 L.ptr(info), L.ptr(nf), L.ptr(al["lmarks"]), L.ptr(al["M"]),
+                                                 L.ptr(al["flags"]), L.current_stream(self.dev)), "fp_dets_to_crops_aligned")
+            return items, info, nf, al
         L.check(lib.fp_dets_to_crops(L.ptr(dets), L.ptr(counts), B, dets.shape[1], row, fmt, iw, ih, W, H,
                                      float(self.det.det_thres), float(self.det.bbox_area_thres), float(gain),
                                      float(px), float(py), tx, ty, bx, by, 112, 112, cap, L.ptr(items), L.ptr(info),
                                      L.ptr(nf), L.current_stream(self.dev)), "fp_dets_to_crops")
-        return items, info, nf
+        return items, info, nf, None
 
-    def embed(self, frames, items, n_faces):
+    def _to_input(self, frames, items, n, canvas, al, info, start=0):
+        """The embedder input of faces start .. start + n: the box crops (crops_to_input), or with al the aligned faces."""
+        if al is None:
+            crops_to_input(frames, items[start:] if start else items, n, canvas, self.lut)
+        else:
+            A.warp(frames, al["M"][start:], info[start:], al["flags"][start:], items[start:], n, out_f32=canvas, lut=self.lut)
+
+    def embed(self, frames, items, n_faces, al=None, info=None):
         """Crop + resize + normalise into the embedder's input, run Mobile-FaceNet.  -> (n_faces, E), a view into the
         embedder plan's arena.  ONE plan (arena sized for the largest batch seen, in steps of 256 crops) serves every
         face count: it runs on the first n_pad = n_faces rounded up to `bucket` images (8 keeps the 14x14 layers'
         row count a multiple of the 32-row MFMA tiles the streaming 1x1 kernels need), so at most bucket - 1 crops of
-        work are padding and a varying face count neither builds new plans nor pins new arenas."""
+        work are padding and a varying face count neither builds new plans nor pins new arenas.
+        al / info: the aligned crops' outputs (crops() with align): the input is the aligned faces (fp_align_warp)."""
         if n_faces == 0:
             return torch.zeros((0, self.emb.embedding_size), device=self.dev)
         n_pad = (n_faces + self.bucket - 1) // self.bucket * self.bucket
@@ -124,14 +158,14 @@ class FacePipeline:
         self.emb_key, self.emb_n_pad = (cap, n_pad), n_pad     # the plan itself stays owned by the embedder's LRU cache
         main = n_pad // self.ROUND_CROPS * self.ROUND_CROPS
         if self.split_tail and main and 0 < n_pad - main <= self.TAIL_MAX and main < n_faces:
-            return self._embed_split(frames, items, n_faces, n_pad, main, plan)
-        crops_to_input(frames, items, n_faces, plan.input, self.lut)
+            return self._embed_split(frames, items, n_faces, n_pad, main, plan, al, info)
+        self._to_input(frames, items, n_faces, plan.input, al, info)
         if n_pad > n_faces:
             plan.input[n_faces:n_pad].zero_()    # padding crops: defined inputs (every op is per-image, their rows are dropped)
         plan.run(n=n_pad)
         return plan.out[:n_faces]
 
-    def _embed_split(self, frames, items, n_faces, n_pad, main, plan):
+    def _embed_split(self, frames, items, n_faces, n_pad, main, plan, al=None, info=None):
         """~528 crops are 1056 band tiles of a 14 x 14 Depth_Wise kernel on 512 workgroup slots: two full rounds and a third
         with 32 tiles, in EVERY launch (28 x 28: 2112 tiles, 56 x 56: 3696) -- the last 16 crops cost 0.25 ms of a 2.3 ms
         forward.  The first `main` crops (whole rounds in every kernel) run on the current stream, the remainder as its own
@@ -147,13 +181,16 @@ class FacePipeline:
             self.tail_stream.wait_event(ready)           # items / frames are complete (and the tail plan's previous consumer is done)
             frames.record_stream(self.tail_stream)
             items.record_stream(self.tail_stream)
-            crops_to_input(frames, items[main:], rem, tail.input, self.lut)
+            if al is not None:
+                for t in (info, al["M"], al["flags"]):
+                    t.record_stream(self.tail_stream)
+            self._to_input(frames, items, rem, tail.input, al, info, start=main)
             if rem_pad > rem:
                 tail.input[rem:rem_pad].zero_()
             tail.run(n=rem_pad)
             done = torch.cuda.Event()
             done.record(self.tail_stream)
-        crops_to_input(frames, items, main, plan.input, self.lut)
+        self._to_input(frames, items, main, plan.input, al, info)
         plan.run(n=main)
         cur.wait_event(done)
         return torch.cat([plan.out[:main], tail.out[:rem]])
@@ -173,7 +210,7 @@ class FacePipeline:
         last one.  Same kernels, same numbers as step(); a detector overflow (more survivors than the cap in some frame)
         falls back to the exact un-capped re-run for that batch."""
         dets, counts, over = self.detect(frames, beside=self.emb_stream is not None)
-        items, info, nf = self.crops(frames, dets, counts)
+        items, info, nf, al = self._crops(frames, dets, counts)
         # two pinned count buffers, used alternately: at most one batch is pending while the previous one's is read
         if getattr(self, "_host_counts", None) is None:
             self._host_counts, self._host_k = [torch.empty((2,), dtype=torch.int32).pin_memory() for _ in range(2)], 0
@@ -185,7 +222,7 @@ class FacePipeline:
             host[1] = 0
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.dev))
-        prev, self._pending = getattr(self, "_pending", None), (frames, items, info, host, ev)
+        prev, self._pending = getattr(self, "_pending", None), (frames, items, info, host, ev, al)
         return None if prev is None else self._finish(prev)
 
     def flush(self):
@@ -194,18 +231,18 @@ class FacePipeline:
         return None if prev is None else self._finish(prev)
 
     def _finish(self, pending):
-        frames, items, info, host, ev = pending
+        frames, items, info, host, ev, al = pending
         ev.synchronize()
         n, n_over = int(host[0]), int(host[1])
         if n_over:                              # > MAX_DET survivors in some frame: exact re-run without a cap
             dets, counts, _ = self.detect(frames, max_det=None)
-            items, info, nf = self.crops(frames, dets, counts)
+            items, info, nf, al = self._crops(frames, dets, counts)
             n = int(nf.item())
         cap = items.shape[0]
         if n > cap:
             raise L.FacepathError(f"{n} faces in the batch exceed max_faces_per_frame*B = {cap}")
         if self.emb_stream is None:
-            emb = self.embed(frames, items, n)
+            emb = self.embed(frames, items, n, al, info)
             res = self.filter(emb)
             out = dict(n_faces=n, info=info[:n], emb=emb.clone(), items=items[:n])
         else:
@@ -214,9 +251,9 @@ class FacePipeline:
             if getattr(self, "_emb_done", None) is not None:
                 main.wait_event(self._emb_done)            # (results of the batch before are complete for the caller)
             with torch.cuda.stream(self.emb_stream):
-                for t in (frames, items, info):
+                for t in (frames, items, info) + (() if al is None else tuple(al.values())):
                     t.record_stream(self.emb_stream)
-                emb = self.embed(frames, items, n)
+                emb = self.embed(frames, items, n, al, info)
                 res = self.filter(emb)
                 out = dict(n_faces=n, info=info[:n], emb=emb.clone(), items=items[:n])
                 # allocated on the side stream, consumed by the caller on the main stream (after `done`): tell the caching
@@ -226,9 +263,15 @@ class FacePipeline:
                 self._emb_done = torch.cuda.Event()
                 self._emb_done.record(self.emb_stream)
             out["done"] = self._emb_done                   # the caller waits for this event before it reads the results
+        self._add_align(out, al, n)
         if res is not None:
             out.update(best=res[0], arg=res[1], keep=res[2])
         return out
+
+    @staticmethod
+    def _add_align(out, al, n):
+        if al is not None:
+            out.update(lmarks=al["lmarks"][:n], align_M=al["M"][:n], align_flags=al["flags"][:n])
 
     def filter(self, emb):
         if self.reference is None or emb.shape[0] == 0:
@@ -242,7 +285,7 @@ class FacePipeline:
         ``emb`` is a copy (the embedder's output lives in its plan arena and the next step overwrites it).
         beside: use the detector plan of the two-stream steps (measurement: bench.py's per-op probe pass)."""
         dets, counts, over = self.detect(frames, beside=beside)
-        items, info, nf = self.crops(frames, dets, counts)
+        items, info, nf, al = self._crops(frames, dets, counts)
         # the one host sync of the step: the face count (sizes the embedder batch) and the detector's overflow flag
         if over is None:
             n, n_over = int(nf.item()), 0
@@ -250,14 +293,15 @@ class FacePipeline:
             n, n_over = torch.stack([nf[0], over.sum().to(torch.int32)]).tolist()
         if n_over:                              # > MAX_DET survivors in some frame: exact re-run without a cap
             dets, counts, _ = self.detect(frames, max_det=None)
-            items, info, nf = self.crops(frames, dets, counts)
+            items, info, nf, al = self._crops(frames, dets, counts)
             n = int(nf.item())
         cap = items.shape[0]
         if n > cap:
             raise L.FacepathError(f"{n} faces in the batch exceed max_faces_per_frame*B = {cap}")
-        emb = self.embed(frames, items, n)
+        emb = self.embed(frames, items, n, al, info)
         res = self.filter(emb)
         out = dict(n_faces=n, info=info[:n], emb=emb.clone(), items=items[:n])
+        self._add_align(out, al, n)
         if res is not None:
             out.update(best=res[0], arg=res[1], keep=res[2])
         return out

@@ -727,6 +727,78 @@ int fp_jpeg_entropy_decode_emulate(const uint8_t* data, size_t n, const fp_jpeg_
 /* ------------------------------------------------------------------------- */
 
 /*
+ * Face alignment (csrc/align.hip).  The embedder's input as a similarity warp of the frame onto the ArcFace 112 x 112
+ * five-point template (38.2946, 51.6963) (73.5318, 51.5014) (56.0252, 71.7366) (41.5493, 92.3655) (70.7299, 92.2041)
+ * instead of the stretched box crop.  All additive: fp_dets_to_crops and fp_resize_* are unchanged.
+ *
+ * fp_dets_to_crops_aligned / _ragged take fp_dets_to_crops' / _ragged's arguments and write the same items, face_info and
+ * n_faces bit for bit, plus, per face (device memory, max_faces rows):
+ *   lmarks[10]: landmarks in frame pixels, fp32, in numpy's float32 operation order.  fmt 0 (BlazeFace; row_floats >= 17):
+ *               keypoints 0..3 (x, y) * (in_w, in_h), - pad, / gain, round half-to-even, not clipped (bbox_lmarks of
+ *               get_dets_bboxes_confs_lmarks_areas), slots 8 and 9 = 0.  fmt 1 (YOLOv5-face; row_floats >= 15): columns
+ *               5..14 - pad, / gain, clamped to [0, w] / [0, h], not rounded (scale_coords_landmarks).
+ *   M[6]:       the least-squares similarity frame -> template (a, -b, tx, b, a, ty), fp64 (Umeyama's estimate in closed
+ *               form).  fmt 1: landmark i -> template point i; fmt 0: keypoints 0, 1, 2, 3 -> points 0, 1, 2 and the
+ *               midpoint of 3 and 4.
+ *   flags:      FP_ALIGN_DEGENERATE when the centred landmarks' sum of squares is < 1 px^2 (or the fit is not finite);
+ *               M is then 0 and the face's embedder input is its box crop.
+ * Refusals before any launch: those of fp_dets_to_crops, a NULL lmarks / M / flags, fmt 1 with row_floats < 15
+ * (FP_ERR_INVALID_ARG); M not 8-byte aligned (FP_ERR_ALIGNMENT).
+ */
+#define FP_ALIGN_SIZE 112
+#define FP_ALIGN_DEGENERATE 1
+
+int fp_dets_to_crops_aligned(const float* dets, const int32_t* counts, int B, int max_dets, int row_floats, int fmt,
+                             int in_w, int in_h, int orig_w, int orig_h, float det_thres, float area_thres,
+                             float gain, float pad_x, float pad_y, int off_tx, int off_ty, int off_bx, int off_by,
+                             int dst_w, int dst_h, int max_faces,
+                             fp_resize_item* items, float* face_info, int32_t* n_faces,
+                             float* lmarks, double* M, int32_t* flags, void* stream);
+int fp_dets_to_crops_aligned_ragged(const float* dets, const int32_t* counts, int B, int max_dets, int row_floats, int fmt,
+                                    int in_w, int in_h, const fp_frame_desc* descs /*device, B*/,
+                                    const float* geom /*device, B x 3*/, float det_thres, float area_thres,
+                                    int off_tx, int off_ty, int off_bx, int off_by, int dst_w, int dst_h, int max_faces,
+                                    fp_resize_item* items, float* face_info, int32_t* n_faces,
+                                    float* lmarks, double* M, int32_t* flags, void* stream);
+/* HOST.  fp_dets_to_crops_aligned_ragged run serially on host memory (every pointer HOST); the same values. */
+int fp_dets_to_crops_aligned_emulate(const float* dets, const int32_t* counts, int B, int max_dets, int row_floats, int fmt,
+                                     int in_w, int in_h, const fp_frame_desc* descs, const float* geom, float det_thres,
+                                     float area_thres, int off_tx, int off_ty, int off_bx, int off_by, int dst_w, int dst_h,
+                                     int max_faces, fp_resize_item* items, float* face_info, int32_t* n_faces,
+                                     float* lmarks, double* M, int32_t* flags);
+
+/*
+ * The embedder's input of n faces: canvas k = face k warped by M[k] (frame -> template) out of frame (int)face_info[k][0]
+ * (cv2.warpAffine's convention: output pixel (x, y), 0 <= x, y < 112, samples the frame at M^-1 (x, y), no half-pixel
+ * shift), bilinear in fp32 over the u8 BGR frame, taps outside the frame 0 (BORDER_CONSTANT 0).  A face whose flags carry
+ * FP_ALIGN_DEGENERATE gets the box crop of items[k] instead, bit for bit what fp_resize_normalize / fp_resize_ragged
+ * make of it (pad 0, no R/B swap).  Outputs (either may be NULL, not both; device):
+ *   out_u8  [n][112][112][3]: the value rounded half-to-even, clamped to [0, 255], channels in frame order;
+ *   out_f32 [n][112][112][out_c], out_c = 3 or 4 (4: 16-byte aligned, the 4th channel 0): lut256[u8] (256 device floats).
+ * M, face_info, flags and items are device memory the host does not read: a frame index outside the batch, a descriptor
+ * outside the limits of fp_resize_ragged or a non-invertible M gives a canvas of 0s, never a load outside the frames.
+ * Refusals before any launch: NULL pointers, n < 0, n_frames <= 0, sizes out of range, out_c not 3 / 4, no output
+ * (FP_ERR_INVALID_ARG); M not 8-byte aligned, face_info / flags / items not 4-byte aligned, a misaligned out_f32
+ * (FP_ERR_ALIGNMENT).  fp_align_warp: frames [n_frames][frame_h][frame_w][3], frame_h <= 65535, frame_w <= 32767;
+ * fp_align_warp_ragged: a ragged batch (section 2, the trust boundary of fp_resize_ragged).
+ */
+int fp_align_warp(const uint8_t* frames, int n_frames, int frame_h, int frame_w, const double* M /*device, n x 6*/,
+                  const float* face_info /*device, n x 7*/, const int32_t* flags /*device, n*/,
+                  const fp_resize_item* items /*device, n*/, int n, uint8_t* out_u8, float* out_f32, int out_c,
+                  const float* lut256, void* stream);
+int fp_align_warp_ragged(const uint8_t* frames, size_t frames_bytes, const fp_frame_desc* descs /*device*/, int n_frames,
+                         const double* M, const float* face_info, const int32_t* flags, const fp_resize_item* items, int n,
+                         uint8_t* out_u8, float* out_f32, int out_c, const float* lut256, void* stream);
+/*
+ * HOST.  The device's estimate and per-pixel code run serially on host memory (every pointer HOST).  lmarks non-NULL
+ * (n x 10, fmt as above): M and flags are computed from them; NULL: M and flags are inputs.  out_u8 non-NULL: the u8
+ * canvases of fp_align_warp_ragged over frames described by descs (a uniform batch is n_frames equal descriptors).
+ */
+int fp_align_emulate(const uint8_t* frames, size_t frames_bytes, const fp_frame_desc* descs, int n_frames, const float* lmarks,
+                     int fmt, double* M, const float* face_info, int32_t* flags, const fp_resize_item* items, int n,
+                     uint8_t* out_u8);
+
+/*
  * ABI 13.  Baseline (SOF0) encoding of a batch of 8-bit RGB / BGR crops, byte-identical to libjpeg-turbo's default compressor
  * (jpeg_set_defaults + jpeg_set_quality(quality, TRUE): islow DCT, the Annex K tables scaled by quality, standard Huffman
  * tables, no restart markers, no Huffman optimisation) -- what cv2.imwrite writes for the reference's face crops

@@ -16,6 +16,7 @@ ABI_VERSION = 14
 # fp_op_kind
 OP_CONV, OP_DWCONV, OP_MAXPOOL, OP_UPSAMPLE2X, OP_COPY, OP_L2NORM, OP_BLAZEBLOCK, OP_DWPW, OP_YSTEM = 1, 2, 3, 4, 5, 6, 7, 8, 9
 OP_YSTEM_U8, OP_STEM_U8, OP_DWBLOCK, OP_BLAZEPAIR, OP_BLAZECHAIN, OP_SHUFDOWN, OP_SHUFUNIT, OP_YSTEM2 = 10, 11, 12, 13, 14, 15, 16, 17
+OP_EMBED_HEAD = 18
 # fp_act
 ACT_NONE, ACT_RELU, ACT_PRELU, ACT_SILU = 0, 1, 2, 3
 # fp_res_mode
@@ -26,6 +27,7 @@ OPF_IN_DW = 16                         # DWBLOCK: a depthwise Conv_block in fron
 OPF_IN_UP2 = 32                        # CONV (split pointwise): leading input channels = a half-size map upsampled 2x (nearest)
 OPF_OUT_DW = 64                        # CONV (Mobile-FaceNet stem): a depthwise 3x3 Conv_block behind the conv, in the same kernel
 OPF_SPLIT3 = 8                         # GEMM weights packed as three bf16 planes (bf16x6 split-MFMA kernels)
+OPF_OUT_L2 = 128                       # EMBED_HEAD: every output row L2-normalised (F.normalize)
 
 
 class FpOp(C.Structure):

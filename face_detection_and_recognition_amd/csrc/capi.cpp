@@ -53,6 +53,7 @@ static int launch_op(const fp_op& op, const fp_launch& L) {
     case FP_OP_YSTEM: return fp_launch_ystem(op, L);
     case FP_OP_YSTEM_U8: return fp_launch_ystem_u8(op, L);
     case FP_OP_STEM_U8: return fp_launch_stem_u8(op, L);
+    case FP_OP_EMBED_HEAD: return fp_launch_embed_head(op, L);
     default: return FP_ERR_UNSUPPORTED;
   }
 }
@@ -129,7 +130,8 @@ static int validate_op(const fp_op& op, size_t weight_floats, size_t arena_float
   const bool ext_in = op.kind == FP_OP_YSTEM_U8 || op.kind == FP_OP_STEM_U8;   // input in an external buffer (checked at launch)
   const int Cout = (op.kind == FP_OP_CONV || op.kind == FP_OP_BLAZEBLOCK || op.kind == FP_OP_DWPW ||
                     op.kind == FP_OP_DWBLOCK || op.kind == FP_OP_BLAZEPAIR || op.kind == FP_OP_BLAZECHAIN || op.kind == FP_OP_YSTEM ||
-                    op.kind == FP_OP_SHUFDOWN || op.kind == FP_OP_SHUFUNIT || op.kind == FP_OP_YSTEM2 || ext_in) ? op.Cout : op.Cin;
+                    op.kind == FP_OP_SHUFDOWN || op.kind == FP_OP_SHUFUNIT || op.kind == FP_OP_YSTEM2 || op.kind == FP_OP_EMBED_HEAD ||
+                    ext_in) ? op.Cout : op.Cin;
   if (op.kind != FP_OP_DWBLOCK && op.kind != FP_OP_BLAZECHAIN && op.kind != FP_OP_SHUFDOWN && op.kind != FP_OP_SHUFUNIT && op.Cmid != 0) return FP_ERR_INVALID_ARG;
   if (op.row_lo != 0 || op.row_end != 0) {
     // a row window (facepath.h "Row windows"): only the kernels that take one (of the u8 stems, the launcher refuses it
@@ -139,8 +141,10 @@ static int validate_op(const fp_op& op, size_t weight_floats, size_t arena_float
   }
   if (Cout <= 0 || op.out_cmul < 1 || op.in_ld < op.Cin) return FP_ERR_INVALID_ARG;
   // row-padded views (facepath.h FP_OPF_*): which ops take them, and their extent including the pads
-  if (op.flags & ~(FP_OPF_IN_ROWPAD | FP_OPF_OUT_ROWPAD | FP_OPF_IN_C3 | FP_OPF_SPLIT3 | FP_OPF_IN_DW | FP_OPF_IN_UP2 | FP_OPF_OUT_DW))
+  if (op.flags & ~(FP_OPF_IN_ROWPAD | FP_OPF_OUT_ROWPAD | FP_OPF_IN_C3 | FP_OPF_SPLIT3 | FP_OPF_IN_DW | FP_OPF_IN_UP2 | FP_OPF_OUT_DW |
+                   FP_OPF_OUT_L2))
     return FP_ERR_INVALID_ARG;
+  if ((op.flags & FP_OPF_OUT_L2) && op.kind != FP_OP_EMBED_HEAD) return FP_ERR_INVALID_ARG;
   if (op.flags & FP_OPF_OUT_DW) {
     // Mobile-FaceNet's conv1 + conv2_dw (facepath.h): the conv's slopes are followed by the depthwise block's [12][Cout]
     if (op.kind != FP_OP_CONV) return FP_ERR_INVALID_ARG;
@@ -283,6 +287,12 @@ static int validate_op(const fp_op& op, size_t weight_floats, size_t arena_float
     if (op.slope_off >= 0 && !span_ok(op.slope_off, Cout, weight_floats)) return FP_ERR_BOUNDS;
     if (op.act == FP_ACT_PRELU && op.slope_off < 0) return FP_ERR_INVALID_ARG;
     if (op.act < FP_ACT_NONE || op.act > FP_ACT_SILU) return FP_ERR_INVALID_ARG;
+  }
+  if (op.kind == FP_OP_EMBED_HEAD) {
+    // [Cout][Cin] Linear weight, optional [Cout] affine (facepath.h EMBED_HEAD)
+    if (!span_ok(op.w_off, (int64_t)op.Cout * op.Cin, weight_floats)) return FP_ERR_BOUNDS;
+    if (op.scale_off >= 0 && !span_ok(op.scale_off, Cout, weight_floats)) return FP_ERR_BOUNDS;
+    if (op.bias_off >= 0 && !span_ok(op.bias_off, Cout, weight_floats)) return FP_ERR_BOUNDS;
   }
   if ((op.kind == FP_OP_CONV || op.kind == FP_OP_BLAZEBLOCK || op.kind == FP_OP_DWPW || op.kind == FP_OP_DWBLOCK) &&
       op.res_mode != FP_RES_NONE) {

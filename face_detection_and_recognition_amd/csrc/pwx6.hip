@@ -277,12 +277,14 @@ int launch(const PwX6Args& a, bool up, const fp_launch& L) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// convx6_kernel: the same scheme for dense 3x3 convs (pad 1, stride 1 / 2: YOLOv5-face's Bottleneck.cv2 and downsampling
-// Convs, y5/models/common.py:35-56,76-88) and for pointwise convs whose widths are not multiples of 32 / 16 (the in-tree
-// yolov5s widths 92, 184, 360).  Rows are OUTPUT pixels; the K loop runs over (tap, 32-channel slab); a lane's A fragment
-// for a slab is 8 consecutive channels of input pixel (oy*s + dy - pad, ox*s + dx - pad) -- two 16-byte loads straight from
-// global memory (the nine taps of a pixel hit L1 / L2), zero outside the image or beyond Cin -- split in registers as
-// above.  Weight slabs [tap * CS + cs][3][Npad][32] with zero rows / columns in the padding; outputs beyond Cout are not stored.
+// convx6_kernel: the same scheme for dense KH x KW convs (KH, KW in 1..7, padding below the window size, stride 1 / 2):
+// YOLOv5-face's Bottleneck.cv2 and downsampling Convs (3x3 pad 1, y5/models/common.py:35-56,76-88), pointwise convs whose widths
+// are not multiples of 32 / 16 (the in-tree yolov5s widths 92, 184, 360), and Inception-ResNet-v1's unpadded 3x3 and 1x7 / 7x1 /
+// 1x3 / 3x1 windows.  Rows are OUTPUT pixels, flattened over the images; the K loop runs over (tap, 32-channel slab) with
+// tap = dy * KW + dx; a lane's A fragment for a slab is 8 consecutive channels of input pixel (oy*s + dy - pad_t, ox*s + dx -
+// pad_l) -- two 16-byte loads straight from global memory (the taps of a pixel hit L1 / L2), zero outside the image or beyond
+// Cin -- split in registers as above.  Weight slabs [tap * CS + cs][3][Npad][32] with zero rows / columns in the padding;
+// outputs beyond Cout are not stored.
 struct ConvX6Args {
   const float* in;
   float* out;
@@ -292,7 +294,8 @@ struct ConvX6Args {
   const float* bias;
   const float* slope;
   long M;
-  int H, W, OH, OW, Cin, Cout, Npad, KH, stride, pad;
+  int H, W, OH, OW, Cin, Cout, Npad, KH, KW, stride, pad_t, pad_l;
+  int kw_rcp;                // ceil(65536 / KW): dy = (tap * kw_rcp) >> 16 for every tap < 4096 / KW
   int in_ld, out_ld, res_ld, res_C, act, res_mode;
   long in_ns;
   // FP_OPF_IN_UP2 (1x1 only): channels [0, up_C) of input pixel (y, x) come from pixel (y / 2, x / 2) of `up` (up_C % 8 == 0:
@@ -300,9 +303,11 @@ struct ConvX6Args {
   const float* up;
   long up_ns;
   int up_ld, up_C, W2;
-  // flat: Cin < 32 (a multiple of 8): K runs over the flattened (tap, channel) index in slabs of 32 -- two taps of a 16-channel
-  // input per slab (YOLOv5n-face's stem_2b, 3x3 stride 2 on 16 channels: K = 144 in 5 slabs instead of 9 half-empty ones)
+  // flat: Cin < 32 (a multiple of 4), 3x3: K runs over the flattened (tap, channel) index in slabs of 32 -- two taps of a
+  // 16-channel input per slab (YOLOv5n-face's stem_2b, 3x3 stride 2 on 16 channels: K = 144 in 5 slabs instead of 9 half-empty
+  // ones); each 16-byte half of a lane's eight k finds its own tap (a 4-channel image: two pixels per lane)
   int flat;
+  int c3;                    // FP_OPF_IN_C3 (flat, Cin = 4): the fourth channel of a pixel is not read (zero weights, any value)
   fp_divisor div_cin;
   fp_divisor div_ohw, div_ow;
 };
@@ -322,7 +327,8 @@ __global__ __launch_bounds__(256, 2) void convx6_kernel(ConvX6Args p) {
   const long row0 = (long)(vb / nchunk) * BM + wave * (MT * 16);
   const int c0 = chunk * NC;
   const int CS = (p.Cin + 31) / 32;
-  const int NSL = p.flat ? (p.KH * p.KH * p.Cin + 31) / 32 : p.KH * p.KH * CS;   // slabs: (tap, channel slab), or 32 flattened k
+  const int NTAP = p.KH * p.KW;
+  const int NSL = p.flat ? (NTAP * p.Cin + 31) / 32 : NTAP * CS;   // slabs: (tap, channel slab), or 32 flattened k
   const f32x4 z = {0.f, 0.f, 0.f, 0.f};
 
   auto stage = [&](int sl) {
@@ -339,9 +345,9 @@ __global__ __launch_bounds__(256, 2) void convx6_kernel(ConvX6Args p) {
     }
   };
 
-  // this lane's output pixels: tile t -> row row0 + 16 t + l15 -> (n, oy, ox); kept as the float offset of input pixel
-  // (oy*s - pad, ox*s - pad) of image n (may point outside the image: only dereferenced for valid taps) + iy0 / ix0
-  int nimg[MT], iyx[MT];   // image index; (iy0 << 16) | (ix0 & 0xffff) with iy0 / ix0 = oy*s - pad / ox*s - pad (two ints, not
+  // this lane's output pixels: tile t -> row row0 + 16 t + l15 -> (n, oy, ox); kept as the image index and the input pixel
+  // (oy*s - pad_t, ox*s - pad_l) of the window's first tap (may lie outside the image: only dereferenced for valid taps)
+  int nimg[MT], iyx[MT];   // image index; (iy0 << 16) | (ix0 & 0xffff) with iy0 / ix0 = oy*s - pad_t / ox*s - pad_l (two ints, not
                            // a 64-bit address + two coordinates per tile: the 128-accumulator form has no registers to spare)
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
@@ -351,26 +357,33 @@ __global__ __launch_bounds__(256, 2) void convx6_kernel(ConvX6Args p) {
     const unsigned rem = (unsigned)r - n * (unsigned)(p.OH * p.OW);
     const unsigned oy = fp_fastdiv(rem, p.div_ow), ox = rem - oy * p.OW;
     nimg[t] = (int)n;
-    iyx[t] = (((int)oy * p.stride - p.pad) << 16) | (((int)ox * p.stride - p.pad) & 0xffff);
+    iyx[t] = (((int)oy * p.stride - p.pad_t) << 16) | (((int)ox * p.stride - p.pad_l) & 0xffff);
   }
   f32x4 araw[MT][2];
   auto load_a = [&](int sl) {
-    int tap, cs, k0;
-    bool k_lo, k_hi;
-    if (p.flat) {                      // per-lane tap: this lane's eight k are channels k0 .. k0 + 7 of tap (32 sl + 8 q) / Cin
-      const unsigned kf = 32u * sl + 8u * q;
-      tap = (int)fp_fastdiv(kf, p.div_cin);
-      k0 = (int)kf - tap * p.Cin;
-      cs = 0;
-      k_lo = k_hi = tap < p.KH * p.KH;
-    } else {
-      tap = sl / CS;
-      cs = sl - tap * CS;
-      k0 = 32 * cs + 8 * q;
-      k_lo = k0 < p.Cin;
-      k_hi = k0 + 4 < p.Cin;
+    if (p.flat) {                      // per-half tap: channels k0 .. k0 + 3 of tap (32 sl + 8 q + 4 h) / Cin
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const unsigned kf = 32u * sl + 8u * q + 4u * h;
+        const int tap = (int)fp_fastdiv(kf, p.div_cin);
+        const int k0 = (int)kf - tap * p.Cin;
+        const bool kv = tap < NTAP;
+        const int dy = (tap * p.kw_rcp) >> 16, dx = tap - dy * p.KW;
+#pragma unroll
+        for (int t = 0; t < MT; ++t) {
+          const int iy = (iyx[t] >> 16) + dy, ix = (int)(short)(iyx[t] & 0xffff) + dx;
+          const bool ok = kv && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
+          const float* src = p.in + ((long)nimg[t] * p.in_ns + (long)((iy * p.W + ix) * p.in_ld + k0));
+          araw[t][h] = ok ? *(const f32x4*)src : z;
+          if (p.c3) araw[t][h][3] = 0.f;
+        }
+      }
+      return;
     }
-    const int dy = (tap >= p.KH) + (tap >= 2 * p.KH), dx = tap - dy * p.KH;     // KH in {1, 3}
+    const int tap = sl / CS, cs = sl - tap * CS;
+    const int k0 = 32 * cs + 8 * q;
+    const bool k_lo = k0 < p.Cin, k_hi = k0 + 4 < p.Cin;
+    const int dy = (tap * p.kw_rcp) >> 16, dx = tap - dy * p.KW;
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
       const int iy = (iyx[t] >> 16) + dy, ix = (int)(short)(iyx[t] & 0xffff) + dx;
@@ -562,24 +575,27 @@ int fp_launch_pwx6(const fp_op& op, const fp_launch& L) {
   }
 }
 
-// The general form (convx6_kernel): 3x3 pad 1 stride 1 / 2, or pointwise with widths that pwx6_kernel does not take.
+// The general form (convx6_kernel): KH x KW windows, KH and KW in 1..7, 0 <= pad_t < KH and 0 <= pad_l < KW on both sides of the
+// map, stride 1 / 2 -- or pointwise with widths that pwx6_kernel does not take.
 static bool convx6_shape(const fp_op& op) {
-  const bool k3 = op.KH == 3 && op.KW == 3 && op.pad_t == 1 && op.pad_l == 1 && (op.stride == 1 || op.stride == 2) &&
-                  op.OH == (op.H + 2 - 3) / op.stride + 1 && op.OW == (op.W + 2 - 3) / op.stride + 1;
-  const bool k1 = op.KH == 1 && op.KW == 1 && op.stride == 1 && !op.pad_t && !op.pad_l && op.OH == op.H && op.OW == op.W;
-  return k3 || k1;
+  if (op.KH < 1 || op.KH > 7 || op.KW < 1 || op.KW > 7 || op.pad_t < 0 || op.pad_t >= op.KH || op.pad_l < 0 || op.pad_l >= op.KW)
+    return false;
+  if ((op.stride != 1 && op.stride != 2) || op.H + 2 * op.pad_t < op.KH || op.W + 2 * op.pad_l < op.KW) return false;
+  return op.OH == (op.H + 2 * op.pad_t - op.KH) / op.stride + 1 && op.OW == (op.W + 2 * op.pad_l - op.KW) / op.stride + 1;
 }
 
 static bool convx6_eligible(const fp_op& op) {
-  if (op.kind != FP_OP_CONV || !(op.flags & FP_OPF_SPLIT3) || (op.flags & ~(FP_OPF_SPLIT3 | FP_OPF_IN_UP2))) return false;
+  if (op.kind != FP_OP_CONV || !(op.flags & FP_OPF_SPLIT3) || (op.flags & ~(FP_OPF_SPLIT3 | FP_OPF_IN_UP2 | FP_OPF_IN_C3)))
+    return false;
   if (op.flags & FP_OPF_IN_UP2) {
-    if (op.KH != 1 || op.res_mode != FP_RES_NONE || op.res_C % 8 || op.res_C <= 0 || op.res_C >= op.Cin) return false;
+    if (op.KH != 1 || op.KW != 1 || op.stride != 1 || op.res_mode != FP_RES_NONE || op.res_C % 8 || op.res_C <= 0 || op.res_C >= op.Cin) return false;
     if (op.H % 2 || op.W % 2 || op.res_H != op.H / 2 || op.res_W != op.W / 2) return false;
     if (op.res_ld % 4 || op.res_off % 4 || op.res_ns % 4 || op.res_ld < op.res_C || op.res_ns < (long)op.res_H * op.res_W * op.res_ld)
       return false;
   }
-  // Cin >= 32, or 8 / 16 / 24 channels under a 3x3 (K flattened over taps and channels)
-  const bool flat = op.Cin < 32 && op.KH == 3 && op.Cin % 8 == 0 && op.Cin >= 8 && !(op.flags & FP_OPF_IN_UP2);
+  // Cin >= 32, or a multiple of 4 below 32 under a 3x3 (K flattened over taps and channels); FP_OPF_IN_C3 only there, on 4 channels
+  const bool flat = op.Cin < 32 && op.KH == 3 && op.KW == 3 && op.Cin % 4 == 0 && !(op.flags & FP_OPF_IN_UP2);
+  if ((op.flags & FP_OPF_IN_C3) && (!flat || op.Cin != 4)) return false;
   if (!convx6_shape(op) || op.Cin % 4 || (op.Cin < 32 && !flat) || op.Cout % 4 || op.Cout < 32 || op.out_cmul != 1) return false;
   const long OHW = (long)op.OH * op.OW;
   if (op.in_ns < (long)op.H * op.W * op.in_ld || op.out_ns != OHW * op.out_ld) return false;
@@ -617,12 +633,14 @@ int fp_launch_convx6(const fp_op& op, const fp_launch& L) {
   a.slope = op.slope_off >= 0 ? weights + op.slope_off : nullptr;
   a.M = (long)op.N * op.OH * op.OW;
   a.H = op.H; a.W = op.W; a.OH = op.OH; a.OW = op.OW; a.Cin = op.Cin; a.Cout = op.Cout;
-  a.KH = op.KH; a.stride = op.stride; a.pad = op.pad_t;
+  a.KH = op.KH; a.KW = op.KW; a.stride = op.stride; a.pad_t = op.pad_t; a.pad_l = op.pad_l;
+  a.kw_rcp = (65536 + op.KW - 1) / op.KW;
   a.in_ld = op.in_ld; a.out_ld = op.out_ld; a.res_ld = op.res_ld; a.res_C = op.res_C; a.act = op.act; a.res_mode = op.res_mode;
   a.in_ns = op.in_ns;
   a.div_ohw = fp_make_divisor((unsigned)(op.OH * op.OW));
   a.div_ow = fp_make_divisor((unsigned)op.OW);
   a.flat = op.Cin < 32;
+  a.c3 = (op.flags & FP_OPF_IN_C3) != 0;
   a.div_cin = fp_make_divisor((unsigned)(op.Cin >= 2 ? op.Cin : 2));
   if (op.flags & FP_OPF_IN_UP2) {
     a.up = arena + op.res_off;

@@ -335,3 +335,12 @@ class MobileFaceNet(nn.Module):
         plan = self.plan_for(n)
         plan.run()
         return plan.out
+
+    # ---- what FacePipeline asks an embedder ----
+    input_size = (112, 112)
+    swap_rb = False      # crops in BGR, as mobile_facenet/utils.py:13-17 feeds them
+
+    def input_lut(self, device):
+        """Per-value input LUT of the pipeline's crops: (x - 127.5) / 127.5 (utils.mfn_lut)."""
+        from .utils import mfn_lut
+        return mfn_lut(device)

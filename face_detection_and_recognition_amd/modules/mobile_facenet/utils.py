@@ -13,16 +13,16 @@ def mfn_lut(device):
     return torch.from_numpy(((np.arange(256, dtype=np.uint8) - 127.5) / 127.5).astype(np.float32)).to(device)
 
 
-def crops_to_input(frames_u8, items, n_items, canvas, lut):
-    """frames_u8 (B,H,W,3) u8 CUDA or a RaggedFrames; items int32 CUDA (n,9) fp_resize_item rows; canvas (n,112,112,C) fp32
-    (C = 4 for a RaggedFrames)."""
+def crops_to_input(frames_u8, items, n_items, canvas, lut, swap_rb=False):
+    """frames_u8 (B,H,W,3) u8 CUDA or a RaggedFrames; items int32 CUDA (n,9) fp_resize_item rows; canvas (n,h,w,C) fp32
+    (C = 4 for a RaggedFrames; h x w = the embedder's input, 112 x 112 for Mobile-FaceNet); swap_rb: RGB crops (FaceNet)."""
     if isinstance(frames_u8, RaggedFrames):
-        resize_ragged(frames_u8, items, n_items, canvas, lut, pad_value=0, swap_rb=False)
+        resize_ragged(frames_u8, items, n_items, canvas, lut, pad_value=0, swap_rb=swap_rb)
         return
     lib = L.load()
     B, H, W, _ = frames_u8.shape
     L.check(lib.fp_resize_normalize(L.ptr(frames_u8), B, H, W, L.ptr(items), int(n_items), L.ptr(canvas),
-                                    canvas.shape[1], canvas.shape[2], canvas.shape[3], L.ptr(lut), 0, 0,
+                                    canvas.shape[1], canvas.shape[2], canvas.shape[3], L.ptr(lut), 0, int(bool(swap_rb)),
                                     L.current_stream(frames_u8.device)), "fp_resize_normalize")
 
 

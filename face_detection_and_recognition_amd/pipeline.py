@@ -13,7 +13,7 @@ import torch
 from . import _lib as L
 from . import similarity as S
 from .frames import RaggedFrames
-from .modules.mobile_facenet.utils import crops_to_input, mfn_lut
+from .modules.mobile_facenet.utils import crops_to_input
 from .modules.utils import align as A
 from .modules.utils.image import letterbox_geometry
 
@@ -36,7 +36,8 @@ def ragged_scale_coords_params(in_size, sizes):
 
 
 class FacePipeline:
-    """detector: a BlazeFaceModel or YOLOV5FaceModel (HIP); embedder: a HIP MobileFaceNet;
+    """detector: a BlazeFaceModel or YOLOV5FaceModel (HIP); embedder: a HIP MobileFaceNet or InceptionResnetV1 (FaceNet):
+    the crops are resized to its ``input_size``, in its channel order (``swap_rb``), through its ``input_lut``;
     reference: (Nr, E) CUDA tensor of reference embeddings for the cosine filter (or None).
     align: feed the embedder each face warped onto the five-point template (modules/utils/align.py) instead of its
     stretched box crop; step results then also carry lmarks, align_M and align_flags."""
@@ -55,7 +56,12 @@ class FacePipeline:
         self.max_faces_per_frame = int(max_faces_per_frame)
         self.bucket = int(bucket)
         self.dev = embedder._device()
-        self.lut = mfn_lut(self.dev)
+        self.in_w, self.in_h = embedder.input_size
+        self.swap_rb = bool(embedder.swap_rb)
+        self.lut = embedder.input_lut(self.dev)
+        if self.align and (self.in_w, self.in_h) != (L.ALIGN_SIZE, L.ALIGN_SIZE):
+            raise ValueError(f"align=True warps faces onto the {L.ALIGN_SIZE} x {L.ALIGN_SIZE} template; the embedder takes "
+                             f"{self.in_w} x {self.in_h}")
         # step_overlapped with two_streams: embed + filter of batch k run on a SIDE stream beside the detector of batch
         # k + 1 (the split-MFMA embedder kernels are matrix-core bound, the BlazeFace kernels vector-ALU / HBM bound, and
         # every kernel's last, partly empty round of workgroups is filled by the other stream's work)
@@ -116,7 +122,7 @@ class FacePipeline:
                 return items, info, nf, al
             L.check(lib.fp_dets_to_crops_ragged(L.ptr(dets), L.ptr(counts), B, dets.shape[1], row, fmt, iw, ih,
                                                 L.ptr(frames.descs), L.ptr(geom), float(self.det.det_thres),
-                                                float(self.det.bbox_area_thres), tx, ty, bx, by, 112, 112, cap,
+                                                float(self.det.bbox_area_thres), tx, ty, bx, by, self.in_w, self.in_h, cap,
                                                 L.ptr(items), L.ptr(info), L.ptr(nf), L.current_stream(self.dev)),
                     "fp_dets_to_crops_ragged")
             return items, info, nf, None
@@ -131,19 +137,19 @@ class FacePipeline:
             return items, info, nf, al
         L.check(lib.fp_dets_to_crops(L.ptr(dets), L.ptr(counts), B, dets.shape[1], row, fmt, iw, ih, W, H,
                                      float(self.det.det_thres), float(self.det.bbox_area_thres), float(gain),
-                                     float(px), float(py), tx, ty, bx, by, 112, 112, cap, L.ptr(items), L.ptr(info),
+                                     float(px), float(py), tx, ty, bx, by, self.in_w, self.in_h, cap, L.ptr(items), L.ptr(info),
                                      L.ptr(nf), L.current_stream(self.dev)), "fp_dets_to_crops")
         return items, info, nf, None
 
     def _to_input(self, frames, items, n, canvas, al, info, start=0):
         """The embedder input of faces start .. start + n: the box crops (crops_to_input), or with al the aligned faces."""
         if al is None:
-            crops_to_input(frames, items[start:] if start else items, n, canvas, self.lut)
+            crops_to_input(frames, items[start:] if start else items, n, canvas, self.lut, swap_rb=self.swap_rb)
         else:
             A.warp(frames, al["M"][start:], info[start:], al["flags"][start:], items[start:], n, out_f32=canvas, lut=self.lut)
 
     def embed(self, frames, items, n_faces, al=None, info=None):
-        """Crop + resize + normalise into the embedder's input, run Mobile-FaceNet.  -> (n_faces, E), a view into the
+        """Crop + resize + normalise into the embedder's input, run the embedder.  -> (n_faces, E), a view into the
         embedder plan's arena.  ONE plan (arena sized for the largest batch seen, in steps of 256 crops) serves every
         face count: it runs on the first n_pad = n_faces rounded up to `bucket` images (8 keeps the 14x14 layers'
         row count a multiple of the 32-row MFMA tiles the streaming 1x1 kernels need), so at most bucket - 1 crops of

@@ -183,6 +183,8 @@ class PlanBuilder:
         self.has_rowpad = False
         self._placed = False
         self.windows = []       # [(op index, row_lo, row_end)]: the row windows of window() (applied by CompiledPlan)
+        self.x6_all = False     # True: every conv the split-MFMA kernels accept runs there, whatever the size policy says
+                                # (pwx6_ok policy=False; set by the network that emits the plan: Inception-ResNet-v1)
 
     # ---- memory ----
     def new_buf(self, H, W, C):
@@ -312,26 +314,33 @@ class PlanBuilder:
         return per, (nt + per - 1) // per * per * 16
 
     @classmethod
-    def pwx6_ok(cls, x, out, kh, kw, stride, pad, res, res_mode):
-        """Mirror of fp_pwx6_eligible / fp_convx6_eligible (csrc/pwx6.hip) + the size policy above."""
+    def pwx6_ok(cls, x, out, kh, kw, stride, pad, res, res_mode, policy=True):
+        """Mirror of fp_pwx6_eligible / fp_convx6_eligible (csrc/pwx6.hip) + (policy) the size policy above, which applies to
+        the 1x1 and 3x3-pad-1 shapes only: the other windows (KH, KW in 1..7, 0 <= pad < window, stride 1 / 2) take the split
+        kernel whenever it accepts them.  policy=False: the kernels' own eligibility alone."""
         if not cls.X6 or out.cmul != 1 or x.buf.rowpad or out.buf.rowpad:
             return False
-        k3 = (kh, kw) == (3, 3) and tuple(pad) == (1, 1) and stride in (1, 2) and \
-            (out.H, out.W) == ((x.H + 2 - 3) // stride + 1, (x.W + 2 - 3) // stride + 1)
-        k1 = (kh, kw, stride) == (1, 1, 1) and tuple(pad) == (0, 0) and (out.H, out.W) == (x.H, x.W)
-        if k1:
+        pt, pl = pad
+        if not (1 <= kh <= 7 and 1 <= kw <= 7 and 0 <= pt < kh and 0 <= pl < kw and stride in (1, 2) and
+                x.H + 2 * pt >= kh and x.W + 2 * pl >= kw and
+                (out.H, out.W) == ((x.H + 2 * pt - kh) // stride + 1, (x.W + 2 * pl - kw) // stride + 1)):
+            return False
+        k3 = (kh, kw, pt, pl) == (3, 3, 1, 1)
+        k1 = (kh, kw, stride, pt, pl) == (1, 1, 1, 0, 0)
+        if x.C < 32 and (kh, kw) != (3, 3):      # the flat form (K over (tap, channel)) is 3x3 only
+            return False
+        if policy and k1:
             if not cls.PW_X6_MIN_K or x.C < cls.PW_X6_MIN_K:
                 return False
-        elif k3:
+        elif policy and k3:
             flat = cls.CONV3_X6_FLAT and x.C in (8, 16, 24)      # K flattened over (tap, channel): csrc/pwx6.hip convx6_kernel
             if not cls.CONV3_X6_MIN_K or (x.C < cls.CONV3_X6_MIN_K and not flat):
                 return False
-        else:
+        if policy and (k1 or k3) and x.C < 128 and out.H * out.W < cls.X6_SMALL_K_MIN_PIXELS:
             return False
-        if x.C < 128 and out.H * out.W < cls.X6_SMALL_K_MIN_PIXELS:
-            return False
-        fast = k1 and x.C % 32 == 0 and (out.C in (48, 64) or out.C % 128 == 0) and x.buf.ns == x.H * x.W * x.buf.ld
-        if x.C % 4 or out.C % 4 or out.C < (32 if k3 and x.C < 32 else 48) or (not fast and (out.H * out.W < 2 or out.W < 2)):   # (32 outputs: a third of the three-tile chunk would be padding)
+        fast = k1 and x.C % 32 == 0 and x.C >= 64 and (out.C in (48, 64) or out.C % 128 == 0) and x.buf.ns == x.H * x.W * x.buf.ld
+        min_cout = 48 if policy and (k1 or k3) and x.C >= 32 else 32   # (32 outputs: a third of the three-tile chunk would be padding)
+        if x.C % 4 or out.C % 4 or out.C < min_cout or (not fast and (out.H * out.W < 2 or out.W < 2)):
             return False
         ohw = out.H * out.W
         if x.buf.ns < x.H * x.W * x.buf.ld or x.buf.ns % 4 or x.buf.ld % 4 or (x.buf.off + x.coff) % 4:
@@ -402,7 +411,7 @@ class PlanBuilder:
             w3 = split3_bf16(flat).reshape(3, cout // 16, 16, 32).transpose(1, 0, 2, 3)
             op.w_off = self.add_weight(np.ascontiguousarray(w3).reshape(-1).view(np.float32))
             op.flags |= L.OPF_SPLIT3
-        elif self.pwx6_ok(x, out, kh, kw, stride, pad, res, res_mode) and not (op.flags & ~L.OPF_IN_UP2):
+        elif self.pwx6_ok(x, out, kh, kw, stride, pad, res, res_mode, policy=not self.x6_all) and not (op.flags & ~L.OPF_IN_UP2):
             # three bf16 planes [tap * CS + cs][3][Npad][32] (include/facepath.h, FP_OPF_SPLIT3 on FP_OP_CONV): K runs
             # over (tap, 32-channel slab), zero rows / columns in the padding of Cin to 32 and Cout to whole chunks
             cs = (x.C + 31) // 32
@@ -1023,6 +1032,26 @@ class PlanBuilder:
         self.alg_bytes.append(0)
         return out
 
+    def embed_head(self, x, w, out, scale=None, bias=None, normalize=False):
+        """Embedding head as ONE op (FP_OP_EMBED_HEAD, csrc/embedhead.hip): mean over x's H x W pixels -> Linear (w: [D, C], no
+        bias) -> x*scale + bias (BatchNorm1d) -> with normalize, F.normalize.  out: a View of a 1 x 1 buffer, D channels."""
+        d, c = w.shape
+        assert c <= x.C and out.C >= d and (out.H, out.W) == (1, 1) and out.cmul == 1 and x.up is None
+        op = self._base(L.OP_EMBED_HEAD, x, out, 1, 1)
+        op.Cout = d
+        wp = np.zeros((d, x.C), np.float32)
+        wp[:, :c] = np.asarray(w, np.float32)
+        op.w_off = self.add_weight(wp)
+        if scale is not None:
+            op.scale_off = self.add_weight(pad_vec(scale, d))
+        if bias is not None:
+            op.bias_off = self.add_weight(pad_vec(bias, d))
+        if normalize:
+            op.flags |= L.OPF_OUT_L2
+        self.ops.append(op)
+        self.alg_bytes.append(4 * self.N * (x.H * x.W * c + d))
+        return out
+
     def finish(self):
         if not self._placed:   # the row-padded region goes behind the recycled arena: relocate its views once
             self._placed = True
@@ -1246,7 +1275,7 @@ class CompiledPlan:
             if op.flags & L.OPF_IN_UP2:                          # the leading res_C channels come from the half-size map
                 b_in = op.H * op.W * (op.Cin - op.res_C) * 4 + op.res_H * op.res_W * op.res_C * 4
         cout = op.Cout if k in (L.OP_CONV, L.OP_BLAZEBLOCK, L.OP_DWPW, L.OP_DWBLOCK, L.OP_BLAZEPAIR, L.OP_BLAZECHAIN, L.OP_YSTEM, L.OP_YSTEM_U8,
-                                L.OP_STEM_U8, L.OP_SHUFDOWN, L.OP_SHUFUNIT, L.OP_YSTEM2) else op.Cin
+                                L.OP_STEM_U8, L.OP_SHUFDOWN, L.OP_SHUFUNIT, L.OP_YSTEM2, L.OP_EMBED_HEAD) else op.Cin
         oh, ow = (op.H, op.W) if k in (L.OP_COPY, L.OP_L2NORM) else (op.OH, op.OW)
         b_out = oh * ow * cout * 4 * (2 if op.res_mode == L.RES_SHUFFLE2 else 1)
         b_res = 0
@@ -1289,6 +1318,8 @@ class CompiledPlan:
             f = opix * (2 * op.Cmid * op.Cmid + 9 * op.Cmid)
         elif k == L.OP_YSTEM2:
             f = opix * (9 * op.Cin * op.Cout + 2 * op.Cout * op.Cout)
+        elif k == L.OP_EMBED_HEAD:  # the Linear (the mean and the affine are epilogue-class)
+            f = op.Cin * op.Cout
         elif k == L.OP_SHUFDOWN:   # branch1: dw + 1x1; branch2: 1x1 at full resolution, dw, 1x1
             f = opix * (9 * op.Cin + op.Cin * op.Cmid) + op.H * op.W * op.Cin * op.Cmid + opix * (9 * op.Cmid + op.Cmid * op.Cmid)
         else:

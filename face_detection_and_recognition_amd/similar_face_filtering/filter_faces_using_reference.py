@@ -1,8 +1,10 @@
 """filter_faces_using_reference on MI355X (similar_face_filtering/filter_faces_using_reference.py).
 
 Same functions, flags (--ud --rd --td -m -b -r) and directory contract.  The feature extractor is a HIP
-network (Mobile-FaceNet 112x112 by default; the reference's TF/Keras FaceNet SavedModel is an external download and
-TensorFlow is not a dependency of this build); the filter arithmetic runs in csrc/sim.hip:
+network: Mobile-FaceNet 112x112 by default, or with --net facenet the reference's own network, Inception-ResNet-v1 at 160x160
+(modules/facenet), un-normalised as the reference's Bottleneck_BatchNorm output, from a state dict (-m; a Keras SavedModel
+is converted to that layout elsewhere: TensorFlow is not a dependency of this build); the filter arithmetic runs in
+csrc/sim.hip:
   reference-exact default   --metric l2_mean : mean of <= R reference embeddings, thres = max distance to the mean,
                                                keep iff ||e - mean|| <= thres            (:71-100, :183-197)
   batched cosine filter     --metric cosine  : keep iff max_j cos(e, ref_j) >= --tau     
@@ -18,7 +20,7 @@ import torch
 
 from .. import similarity as S
 from ..frames import RaggedFrames
-from ..modules.mobile_facenet.utils import crops_to_input, mfn_lut
+from ..modules.mobile_facenet.utils import crops_to_input
 
 
 def _fix_path_for_globbing(dir: str) -> str:
@@ -73,15 +75,16 @@ def read_and_preprocess_img(img_path: str, in_size=(160, 160), dct_method: str =
 def embed_images(model, paths, batch_size=32, preprocess="mobile_facenet", entropy="host"):
     """Decode (Huffman stage on a host thread pool, the rest on the device: modules/utils/jpeg.py), then resize + normalise and
     embed on device, batch by batch.  preprocess:
-    "mobile_facenet" = cv2-style resize of the whole image to 112x112, (x - 127.5) / 127.5, BGR
-    (fde/modules/mobile_facenet/utils.py:13-17); "tf_standardize" = the reference filter's own TF preprocess
-    (filter_faces_using_reference.py:60-68: RGB, [0,1], bilinear resize, per-image standardisation) at the network's
-    112x112 input size.  entropy="device": the Huffman stage of the sequential JPEGs on the device as well
+    "mobile_facenet" = cv2-style resize of the whole image to the network's input size through its input LUT in its channel
+    order (Mobile-FaceNet: 112x112, (x - 127.5) / 127.5, BGR, fde/modules/mobile_facenet/utils.py:13-17); "tf_standardize" =
+    the reference filter's own TF preprocess (filter_faces_using_reference.py:60-68: RGB, [0,1], bilinear resize, per-image
+    standardisation) at the network's input size (FaceNet: 160x160, the reference's own pairing).  entropy="device": the Huffman stage of the sequential JPEGs on the device as well
     (modules/utils/jpeg.py imread_batch)."""
     if preprocess not in ("mobile_facenet", "tf_standardize"):
         raise ValueError(f"unknown preprocess {preprocess!r}")
     dev = model._device()
-    lut = mfn_lut(dev)
+    lut = model.input_lut(dev)
+    iw, ih = model.input_size
     feats = []
     for i in range(0, len(paths), batch_size):
         chunk = paths[i:i + batch_size]
@@ -90,14 +93,14 @@ def embed_images(model, paths, batch_size=32, preprocess="mobile_facenet", entro
         if preprocess == "tf_standardize":
             for j in range(len(chunk)):
                 rgb = decoded[j].unsqueeze(0).flip(-1).contiguous()
-                plan.input[j, ..., :3].copy_(preprocess_tf_standardize(rgb, (112, 112))[0])
+                plan.input[j, ..., :3].copy_(preprocess_tf_standardize(rgb, (ih, iw))[0])
                 plan.input[j, ..., 3:].zero_()
         else:
-            # every image, whatever its size, resized into its own 112 x 112 canvas in one launch (fp_resize_ragged)
+            # every image, whatever its size, resized into its own input-size canvas in one launch (fp_resize_ragged)
             frames = RaggedFrames.from_list(list(decoded), dev)
-            items = torch.tensor([[j, 0, 0, w, h, 0, 0, 112, 112] for j, (h, w) in enumerate(frames.sizes)],
+            items = torch.tensor([[j, 0, 0, w, h, 0, 0, iw, ih] for j, (h, w) in enumerate(frames.sizes)],
                                  dtype=torch.int32, device=dev)
-            crops_to_input(frames, items, len(chunk), plan.input, lut)
+            crops_to_input(frames, items, len(chunk), plan.input, lut, swap_rb=model.swap_rb)
         plan.run()
         feats.append(plan.out.clone())
     return torch.cat(feats) if feats else torch.zeros((0, model.embedding_size), device=dev)
@@ -115,22 +118,45 @@ def get_ref_mean_vec_and_thres_from_imgs(model, ref_class_path: str, max_ref_img
 
 
 def get_parsed_args(argv=None):
-    """:103-124 plus --metric/--tau/--device."""
+    """:103-124 plus --net/--metric/--tau/--preprocess/--device."""
     parser = argparse.ArgumentParser()
     parser.add_argument('--ud', '--unfiltered_data_path', dest="unfiltered_data_path", type=str, required=True)
     parser.add_argument('--rd', '--reference_data_path', dest="reference_data_path", type=str, required=True)
     parser.add_argument('--td', '--target_data_path', dest="target_data_path", type=str, default="data/faces_filtered")
-    parser.add_argument('-m', '--savedmodel_path', type=str, default="weights/mobile_facenet/mobile_facenet.pth",
-                        help='Mobile-FaceNet state_dict (.pth). (default: %(default)s)')
+    parser.add_argument('--net', choices=["mobile_facenet", "facenet"], default="mobile_facenet",
+                        help='mobile_facenet: Mobile-FaceNet 112x112, unit 512-d embeddings; facenet: Inception-ResNet-v1 160x160, '
+                             'the reference\'s un-normalised embeddings (D from last_linear.weight). (default: %(default)s)')
+    parser.add_argument('-m', '--savedmodel_path', type=str, default=None,
+                        help='state_dict (.pth / .pt) of the --net network. (default: weights/mobile_facenet/mobile_facenet.pth, '
+                             'weights/facenet/facenet.pt)')
     parser.add_argument('-b', '--batch_size', type=int, default=32)
     parser.add_argument('-r', '--ref_img_per_class', type=int, default=32)
     parser.add_argument('--metric', choices=["l2_mean", "cosine"], default="l2_mean")
     parser.add_argument('--tau', type=float, default=0.3)
-    parser.add_argument('--preprocess', choices=["mobile_facenet", "tf_standardize"], default="mobile_facenet",
-                        help='mobile_facenet: (x - 127.5)/127.5 BGR at 112x112 (mobile_facenet/utils.py:13-17); tf_standardize: '
-                             'the reference filter\'s read_and_preprocess_img (:60-68) at 112x112. (default: %(default)s)')
+    parser.add_argument('--preprocess', choices=["mobile_facenet", "tf_standardize"], default=None,
+                        help='mobile_facenet: the network\'s crop preprocess ((x - 127.5)/127.5 BGR at 112x112 for Mobile-FaceNet, '
+                             'mobile_facenet/utils.py:13-17); tf_standardize: the reference filter\'s read_and_preprocess_img (:60-68) at '
+                             'the network\'s input size. (default: mobile_facenet with --net mobile_facenet, tf_standardize with facenet)')
     parser.add_argument('-d', '--device', default="cuda")
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    if args.preprocess is None:
+        args.preprocess = "tf_standardize" if args.net == "facenet" else "mobile_facenet"
+    if args.savedmodel_path is None:
+        args.savedmodel_path = "weights/facenet/facenet.pt" if args.net == "facenet" else "weights/mobile_facenet/mobile_facenet.pth"
+    return args
+
+
+def load_model(args):
+    """The --net network with the -m state dict, on the device."""
+    sd = torch.load(args.savedmodel_path, weights_only=True)
+    if getattr(args, "net", "mobile_facenet") == "facenet":
+        from ..modules.facenet.inception_resnet_v1 import InceptionResnetV1
+        model = InceptionResnetV1(int(sd["last_linear.weight"].shape[0]), normalize=False)
+    else:
+        from ..modules.mobile_facenet.mobile_facenet import MobileFaceNet
+        model = MobileFaceNet(512)
+    model.load_state_dict(sd)
+    return model.to(args.device.replace("hip", "cuda"))
 
 
 def filter_class(model, ref_class_path, unfiltered_class_path, clean_dir, unclean_dir, args):
@@ -157,10 +183,7 @@ def filter_class(model, ref_class_path, unfiltered_class_path, clean_dir, unclea
 def main(argv=None):
     args = get_parsed_args(argv)
     print(args)
-    from ..modules.mobile_facenet.mobile_facenet import MobileFaceNet
-    model = MobileFaceNet(512)
-    model.load_state_dict(torch.load(args.savedmodel_path, weights_only=True))
-    model = model.to(args.device.replace("hip", "cuda"))
+    model = load_model(args)
     ref_class_paths = glob.glob(_fix_path_for_globbing(args.reference_data_path))
     unfiltered_class_paths = glob.glob(_fix_path_for_globbing(args.unfiltered_data_path))
     if len(unfiltered_class_paths) != len(ref_class_paths):

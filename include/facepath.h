@@ -88,9 +88,12 @@ enum fp_op_kind {
                            SiLU) -> cat with the pooled stem_1 map -> stem_3 (1x1, 2c -> c, SiLU); stem_2b's output never reaches HBM.  See "YSTEM2" */
   FP_OP_SHUFUNIT = 16,  /* ABI 10.  a WHOLE stride-1 ShuffleV2Block (y5/models/common.py:127-176): x1, x2 = x.chunk(2); branch2(x2) = 1x1 + BN
                            + SiLU -> dw3x3 + BN -> 1x1 + BN + SiLU; out = channel_shuffle(cat(x1, branch2)) in one kernel.  See "SHUFUNIT" */
-  FP_OP_SHUFDOWN = 15   /* ABI 10.  a WHOLE stride-2 ShuffleV2Block (y5/models/common.py:127-176) in one kernel: branch1 = dw3x3 s2 + BN
+  FP_OP_SHUFDOWN = 15,  /* ABI 10.  a WHOLE stride-2 ShuffleV2Block (y5/models/common.py:127-176) in one kernel: branch1 = dw3x3 s2 + BN
                            -> 1x1 + BN + SiLU, branch2 = 1x1 + BN + SiLU -> dw3x3 s2 + BN -> 1x1 + BN + SiLU, cat + channel_shuffle(2)
                            as the store pattern; nothing but x and the shuffled output touches HBM.  See "SHUFDOWN" */
+  FP_OP_EMBED_HEAD = 18 /* (appended at ABI 14) an embedding head in one kernel: mean over the H x W pixels of each image -> Linear Cin -> Cout
+                           (no bias) -> per-channel affine (BatchNorm1d) -> with FP_OPF_OUT_L2, x / max(||x||_2, 1e-12) (F.normalize).
+                           Inception-ResNet-v1's avgpool_1a + last_linear + last_bn (+ normalize).  See "EMBED_HEAD" */
 };
 
 enum fp_act { FP_ACT_NONE = 0, FP_ACT_RELU = 1, FP_ACT_PRELU = 2, FP_ACT_SILU = 3 };
@@ -225,6 +228,10 @@ typedef struct fp_op {
  *                (csrc/stemdw.hip).
  */
 #define FP_OPF_OUT_DW 64
+/*
+ * FP_OPF_OUT_L2 (appended at ABI 14) : FP_OP_EMBED_HEAD only: each output row is L2-normalised (F.normalize, eps 1e-12).
+ */
+#define FP_OPF_OUT_L2 128
 
 /*
  * Weight blob layouts (packed by the host side, see
@@ -305,6 +312,11 @@ typedef struct fp_op {
  *            Parameter block at w_off: [5 slabs][3 planes][32 co][32 k] stem_2b with k = (ky*3 + kx)*16 + c (zero for k >= 144);
  *            [32] scale, [32] bias;  [2 slabs][3 planes][32 co][32 k] stem_3 (k: stem_2b's 32 channels, then the pooled map's);  [32] scale,
  *            [32] bias (scale = 1 where the BatchNorm is folded into the conv).
+ *   EMBED_HEAD : in = an NHWC map (H x W x Cin, any in_ld / in_ns), OH = OW = 1, out = [N][Cout] rows (out_ns per image, out_cmul 1),
+ *            KH = KW = stride = 1, no padding, act = FP_ACT_NONE, res_mode = FP_RES_NONE.  w_off -> [Cout][Cin] fp32 Linear weight
+ *            (row-major, torch's [out, in]); scale_off / bias_off -> [Cout] affine (-1: 1 / 0); flags: FP_OPF_OUT_L2 or 0.
+ *            fp32 arithmetic: the mean sums the pixels in order and divides by H * W; each image's result does not depend on the
+ *            batch.  Cin <= 2048, Cout <= 1024.
  * ABI history: 1 = round-1 ops; 2 = fp_ext / *_U8 ops (never shipped in a VERDICT-ed tree); 3 = fp_op.flags, row-padded
  * views; 4 = fp_op.Cmid / reserved0, FP_OP_DWBLOCK, FP_OP_BLAZEPAIR; 5 = FP_OPF_SPLIT3; 6 = FP_OP_BLAZECHAIN; 7 = FP_OPF_IN_UP2; 8 = FP_OP_BLAZEPAIR with stride 2; 9 = FP_OPF_OUT_DW, fp_debug_reload_env; 10 = FP_OP_SHUFDOWN, FP_OP_SHUFUNIT, FP_OP_YSTEM2; 11 = FP_OPF_SPLIT3 on FP_OP_STEM_U8;
  * 12 = device Huffman decoding of sequential JPEG scans (fp_jpeg_scan, fp_jpeg_scan_prepare, fp_jpeg_entropy_decode_device, section 7);

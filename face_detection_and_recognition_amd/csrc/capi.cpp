@@ -177,6 +177,12 @@ static int validate_op(const fp_op& op, size_t weight_floats, size_t arena_float
     if ((int64_t)(OH - 1) * op.stride - op.pad_t >= op.H || (int64_t)(OW - 1) * op.stride - op.pad_l >= op.W)
       return FP_ERR_INVALID_ARG;
   }
+  if (op.kind == FP_OP_YSTEM2) {
+    // the pooled map (the res view) first: a view outside the arena is a bounds error before the launcher compares it with
+    // the output (it refuses an output that aliases either input)
+    const int64_t res_ext = (int64_t)(op.N - 1) * op.res_ns + ((int64_t)op.OH * op.OW - 1) * op.res_ld + op.res_C;
+    if (!span_ok(op.res_off, res_ext, arena_floats)) return FP_ERR_BOUNDS;
+  }
   // what the kernel itself requires: the launcher's checks, in a dry run
   const int rc = dry_run(op, nullptr);
   if (rc != FP_OK) return rc;
@@ -239,10 +245,8 @@ static int validate_op(const fp_op& op, size_t weight_floats, size_t arena_float
     // one parameter block at w_off (facepath.h SHUFDOWN)
     if (!span_ok(op.w_off, fp_shufdown_w_floats(op), weight_floats)) return FP_ERR_BOUNDS;
   } else if (op.kind == FP_OP_YSTEM2) {
-    // parameter block at w_off, the pooled map in the res view (facepath.h YSTEM2)
+    // parameter block at w_off (facepath.h YSTEM2); the pooled map's view is checked before the dry run
     if (!span_ok(op.w_off, fp_ystem2_w_floats(op), weight_floats)) return FP_ERR_BOUNDS;
-    const int64_t res_ext = (int64_t)(op.N - 1) * op.res_ns + ((int64_t)op.OH * op.OW - 1) * op.res_ld + op.res_C;
-    if (!span_ok(op.res_off, res_ext, arena_floats)) return FP_ERR_BOUNDS;
   } else if (op.kind == FP_OP_SHUFUNIT) {
     if (!span_ok(op.w_off, fp_shufunit_w_floats(op), weight_floats)) return FP_ERR_BOUNDS;
   } else if (op.act2 != FP_ACT_NONE) {

@@ -96,6 +96,16 @@ static inline int fp_window_bands(int rows, int N, int per_wg, int slots, int st
 }
 static inline long fp_round_up(long a, long b) { return (a + b - 1) / b * b; }
 
+// True if two NHWC views of the arena may share a float: each is (offset, per-image stride, pixels, pixel stride, channels)
+// over N images.  Plans lay the arena out image-major, so views with the same image stride overlap only if one image's
+// extents do; otherwise the whole-batch extents are compared.
+static inline bool fp_views_overlap(int N, long off_a, long ns_a, long hw_a, long ld_a, long c_a, long off_b, long ns_b,
+                                    long hw_b, long ld_b, long c_b) {
+  const long img_a = (hw_a - 1) * ld_a + c_a, img_b = (hw_b - 1) * ld_b + c_b;   // exact extents of one image
+  if (ns_a == ns_b) return off_a < off_b + img_b && off_b < off_a + img_a;
+  return off_a < off_b + (long)(N - 1) * ns_b + img_b && off_b < off_a + (long)(N - 1) * ns_a + img_a;
+}
+
 // What a plan-op launcher is given (capi.cpp).  A launcher alone decides whether it takes an op and which kernel
 // instance runs it.  With `dry` set it makes every check and that choice exactly as a launch would, writes the
 // instance's name to `name` (when not null, FP_KERNEL_NAME_MAX bytes) and returns FP_OK before any HIP call and without

@@ -13,7 +13,8 @@
 //     four row tiles (24 MFMAs per 3 ds_read_b128);
 //   * operands swapped (D^T = W^T A^T): a lane ends up with 4 consecutive channels of ONE pixel -- 16-byte epilogue
 //     (scale / bias, residual, ReLU / PReLU / SiLU, ShuffleV2's interleaved store) straight from the accumulators.
-// Eligibility (fp_pwx6_eligible) mirrors plan.py's PlanBuilder.pwx6_ok: the op carries FP_OPF_SPLIT3 and split weights.
+// Eligibility (fp_pwx6_eligible): the op carries FP_OPF_SPLIT3 and split weights; plan.py emits that form only where the launcher
+// takes it (PlanBuilder.probe).
 #include <stdlib.h>
 #include <string.h>
 

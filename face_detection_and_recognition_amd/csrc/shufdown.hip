@@ -543,14 +543,9 @@ static bool shufunit_supported(const fp_op& op) {
   if (op.in_ld < op.Cin || op.out_ld < op.Cout || op.in_ns < (long)op.H * op.W * op.in_ld || op.out_ns < (long)op.OH * op.OW * op.out_ld) return false;
   if (op.act != FP_ACT_SILU || op.act2 != FP_ACT_SILU || op.res_mode != FP_RES_NONE) return false;
   // in place is not possible: a tile reads its neighbours' pixels (halo, x1) after they may have been written
-  // (plans lay the arena out image-major: every image has the same stride and the views are regions inside it)
-  const long in_img = ((long)op.H * op.W - 1) * op.in_ld + op.Cin, out_img = ((long)op.OH * op.OW - 1) * op.out_ld + op.Cout;   // exact extents of the views
-  if (op.in_ns == op.out_ns) {
-    if (op.in_off < op.out_off + out_img && op.out_off < op.in_off + in_img) return false;
-  } else {
-    const long in_hi = op.in_off + (long)(op.N - 1) * op.in_ns + in_img, out_hi = op.out_off + (long)(op.N - 1) * op.out_ns + out_img;
-    if (op.in_off < out_hi && op.out_off < in_hi) return false;
-  }
+  if (fp_views_overlap(op.N, op.in_off, op.in_ns, (long)op.H * op.W, op.in_ld, op.Cin, op.out_off, op.out_ns, (long)op.OH * op.OW,
+                       op.out_ld, op.Cout))
+    return false;
   const long tiles = (long)op.N * ((op.OH + 7) / 8) * ((op.OW + 15) / 16);
   return tiles > 0 && tiles < (1L << 31);
 }

@@ -211,6 +211,11 @@ static bool ystem2_supported(const fp_op& op) {
   if (op.in_ld < 16 || op.out_ld < 32 || op.in_ns < (long)op.H * op.W * op.in_ld || op.out_ns < (long)op.OH * op.OW * op.out_ld ||
       op.res_ns < (long)op.OH * op.OW * op.res_ld) return false;
   if (op.act != FP_ACT_SILU || op.act2 != FP_ACT_SILU || op.res_mode != FP_RES_NONE) return false;
+  // the output may not alias either input: a tile reads its neighbours' input pixels (halo) after they may have been written
+  const long ohw = (long)op.OH * op.OW;
+  if (fp_views_overlap(op.N, op.in_off, op.in_ns, (long)op.H * op.W, op.in_ld, op.Cin, op.out_off, op.out_ns, ohw, op.out_ld, op.Cout) ||
+      fp_views_overlap(op.N, op.res_off, op.res_ns, ohw, op.res_ld, op.res_C, op.out_off, op.out_ns, ohw, op.out_ld, op.Cout))
+    return false;
   const long tiles = (long)op.N * ((op.OH + 3) / 4) * ((op.OW + 15) / 16);
   return tiles > 0 && tiles < (1L << 31);
 }

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from ... import _lib as L
-from ...plan import Buf, CompiledPlan, PlanBuilder, PlanCache, View, cpad, switch_key
+from ...plan import Buf, CompiledPlan, PlanBuilder, PlanCache, View, switch_key
 from ..params import ConvParams, _NoCompute, npy
 from ..utils.image import letterbox_geometry
 
@@ -60,74 +60,66 @@ class BlazeBlock(_NoCompute):
         return self.kernel_size == 3 and self.stride == 1 and self.in_channels == 96 and self.out_channels == 96
 
     def pairs_with(self, other, pb, x):
-        """True if self followed by `other`, fed the row-padded view x, runs as one FP_OP_BLAZEPAIR."""
-        ok = lambda b: (isinstance(b, BlazeBlock) and b.kernel_size == 3 and b.stride == 1 and b.in_channels == 24 and
-                        b.out_channels == 24)
-        return (BlazeBlock.FUSE and BlazeBlock.ROWPAD and BlazeBlock.PAIR and ok(self) and ok(other) and
-                pb.blazepair_supported(x))
+        """True if self followed by `other`, fed the row-padded view x, runs as one FP_OP_BLAZEPAIR: two stride-1 24 -> 24
+        blocks (PAIR) whose op the launcher takes."""
+        return BlazeBlock.PAIR and self._pair_taken(other, 1, pb, x)
 
     PAIR_S2 = os.environ.get("FP_BLAZE_PAIR_S2", "1") == "1"   # class-wide switch: the single stride-1 24 -> 24 block that ends a stage and
                                                                 # the stride-2 block behind it as ONE op (csrc/blazepairs2.hip)
 
     def pairs_with_s2(self, other, pb, x):
         """True if self (stride 1, 24 -> 24) followed by the stride-2 block `other`, fed the row-padded view x, runs as one
-        FP_OP_BLAZEPAIR with stride = 2."""
-        return (BlazeBlock.FUSE and BlazeBlock.ROWPAD and BlazeBlock.PAIR_S2 and isinstance(other, BlazeBlock) and
-                self.kernel_size == 3 and self.stride == 1 and self.in_channels == 24 and self.out_channels == 24 and
-                other.kernel_size == 3 and other.stride == 2 and other.in_channels == 24 and
-                pb.blazepair_s2_supported(x, other.out_channels))
+        FP_OP_BLAZEPAIR with stride = 2 (PAIR_S2, and the launcher takes the op)."""
+        return BlazeBlock.PAIR_S2 and self._pair_taken(other, 2, pb, x)
+
+    def _pair_taken(self, other, stride, pb, x):
+        """self a stride-1 24 -> 24 block, `other` a 3 x 3 block of this stride on 24 channels (24 -> 24 at stride 1): the pair
+        the FP_OP_BLAZEPAIR packers take, and the launcher takes its op on x."""
+        if not (BlazeBlock.FUSE and BlazeBlock.ROWPAD and isinstance(other, BlazeBlock) and self.kernel_size == 3 and
+                self.stride == 1 and self.in_channels == self.out_channels == 24 and other.kernel_size == 3 and
+                other.stride == stride and other.in_channels == 24 and (stride == 2 or other.out_channels == 24)):
+            return False
+        out = pb.new_buf(x.H // stride, x.W // stride, other.out_channels, peek=True)
+        return pb.probe(pb.blazepair_op(x, out.view(), stride)) is not None
+
+    def _pair_params(self, other):
+        return [(npy(b.convs[0].weight), npy(b.convs[0].bias), npy(b.convs[1].weight), npy(b.convs[1].bias))
+                for b in (self, other)]
 
     def emit_pair_s2(self, other, pb, x, out_rowpad=False, dedicated=False):
         y = pb.new_buf_rowpad(x.H // 2, x.W // 2, other.out_channels, dedicated) if out_rowpad else \
             pb.new_buf(x.H // 2, x.W // 2, other.out_channels)
-        pb.blazepair_s2(x, [(npy(b.convs[0].weight), npy(b.convs[0].bias), npy(b.convs[1].weight), npy(b.convs[1].bias))
-                            for b in (self, other)], y.view())
+        emitted = pb.blazepair_s2(x, self._pair_params(other), y.view())
+        assert emitted is not None, "pairs_with_s2 said the launcher takes this pair"
         return y
 
     def emit_pair(self, other, pb, x, out_rowpad=False, dedicated=False):
         y = pb.new_buf_rowpad(x.H, x.W, 24, dedicated) if out_rowpad else pb.new_buf(x.H, x.W, 24)
-        pb.blazepair(x, [(npy(b.convs[0].weight), npy(b.convs[0].bias), npy(b.convs[1].weight), npy(b.convs[1].bias))
-                         for b in (self, other)], y.view())
+        emitted = pb.blazepair(x, self._pair_params(other), y.view())
+        assert emitted is not None, "pairs_with said the launcher takes this pair"
         return y
 
-    def wide_ok(self, H, W):
-        """True if this block on an H x W map runs on the small-map wave-private kernel (csrc/blazewp.hip
-        fp_blazeblock_wps_eligible: stride 1, 48 -> 48 or 96 -> 96, 16- or 32-pixel-wide maps, row-padded input)."""
-        return (BlazeBlock.FUSE and BlazeBlock.ROWPAD and self.kernel_size == 3 and self.stride == 1 and
-                self.in_channels == self.out_channels and self.in_channels in (48, 96) and W in (16, 32) and
-                (H * W) % 32 == 0 and H * W >= 64)
+    def _takes(self, pb, x):
+        """True if the launcher takes this block as one FP_OP_BLAZEBLOCK on view x."""
+        OH, OW = (x.H // 2, x.W // 2) if self.stride == 2 else (x.H, x.W)
+        out = pb.new_buf(OH, OW, self.out_channels, peek=True)
+        return (self.kernel_size == 3 and
+                pb.probe(pb.blazeblock_op(x, out.view(), self.in_channels, self.stride)) is not None)
+
+    def reads_rowpad(self, pb, H, W):
+        """True if this block, fed an H x W map, reads it row-padded: the launcher takes it on a row-padded input (the
+        wave-private kernels, csrc/blazewp.hip)."""
+        return (BlazeBlock.FUSE and BlazeBlock.ROWPAD and
+                self._takes(pb, pb.new_buf_rowpad(H, W, self.in_channels, peek=True).view()))
 
     def fused(self, pb, x):
         """True if emit() takes the fused FP_OP_BLAZEBLOCK path for input view x."""
-        if self.wide_ok(x.H, x.W) and x.coff == 0:
-            return True
-        OW = x.W // 2 if self.stride == 2 else x.W
-        return (BlazeBlock.FUSE and self.kernel_size == 3 and x.coff == 0 and OW % 4 == 0 and
-                pb.blazeblock_lds_bytes(x.C, cpad(self.out_channels)) <= 80 * 1024)
-
-    def wants_rowpad_input(self, H, W):
-        """True if this block, fed an H x W map, runs on a wave-private kernel that reads a row-padded input
-        (csrc/blazewp.hip fp_blazeblock_wp_eligible: stride 1, 24 -> 24, rows of whole 32-pixel tiles; or wide_ok)."""
-        if self.wide_ok(H, W):
-            return True
-        return (BlazeBlock.FUSE and BlazeBlock.ROWPAD and self.kernel_size == 3 and self.stride == 1 and
-                self.in_channels == 24 and self.out_channels == 24 and W % 32 == 0 and W >= 64 and H % 4 == 0 and H >= 8)
+        return BlazeBlock.FUSE and x.coff == 0 and (self.reads_rowpad(pb, x.H, x.W) or self._takes(pb, x))
 
     def emit(self, pb, x, out_rowpad=False):
         """out_rowpad: write the output in the row-padded layout (the next block asked for it); only the fused path
         can."""
         dw, pw = self.convs[0], self.convs[1]
-        if self.wide_ok(x.H, x.W) and x.coff == 0:
-            tmp = None
-            if not x.buf.rowpad:   # dense producer (the unfused stride-2 block before a 96-channel stage): one copy
-                tmp = pb.new_buf_rowpad(x.H, x.W, x.C)
-                pb.copy(x, tmp.view())
-                x = tmp.view()
-            y = (pb.new_buf_rowpad if out_rowpad else pb.new_buf)(x.H, x.W, self.out_channels)
-            pb.blazeblock(x, npy(dw.weight), npy(dw.bias), npy(pw.weight), npy(pw.bias), y.view(), 1)
-            if tmp is not None:
-                pb.free(tmp)
-            return y
         if self.stride == 2:
             # h = F.pad(x, (0, 2, 0, 2)); dw stride 2, padding 0 (blazeface.py:38-39)
             OH, OW, pad = x.H // 2, x.W // 2, (0, 0)
@@ -136,8 +128,17 @@ class BlazeBlock(_NoCompute):
             OH, OW, pad = x.H, x.W, (1, 1)
             res_mode = L.RES_ADD_BEFORE_ACT
         if self.fused(pb, x):
+            tmp = None
+            if not x.buf.rowpad and not self._takes(pb, x):
+                # only a row-padded kernel takes the block, and its producer wrote a dense map (the unfused stride-2 block
+                # before a 96-channel stage): one copy
+                tmp = pb.new_buf_rowpad(x.H, x.W, x.C)
+                pb.copy(x, tmp.view())
+                x = tmp.view()
             y = (pb.new_buf_rowpad if out_rowpad else pb.new_buf)(OH, OW, self.out_channels)
             pb.blazeblock(x, npy(dw.weight), npy(dw.bias), npy(pw.weight), npy(pw.bias), y.view(), self.stride)
+            if tmp is not None:
+                pb.free(tmp)
             return y
         assert not out_rowpad and not x.buf.rowpad
         t = pb.new_buf(OH, OW, self.in_channels)
@@ -306,7 +307,7 @@ class BlazeFace(nn.Module):
         def rowpad_for(i, h, w):   # should the input of blocks[i] (an h x w map) be row-padded?
             if chain_len(i, h, w):     # the chain kernel reads a dense map
                 return False
-            return i < len(blocks) and isinstance(blocks[i], BlazeBlock) and blocks[i].wants_rowpad_input(h, w)
+            return i < len(blocks) and isinstance(blocks[i], BlazeBlock) and blocks[i].reads_rowpad(pb, h, w)
 
         # Row windows: `dirty` = the rows [lo, hi] of the current map that depend on the frame's content (None: all of them).
         # The letterbox puts the content in canvas rows top .. top + sh - 1; every conv is local, so every other row of every
@@ -337,12 +338,15 @@ class BlazeFace(nn.Module):
         while i < len(blocks):
             blk = blocks[i]
             nchain = chain_len(i, x.H, x.W)
-            if nchain and pb.blazechain_supported(x.view()):
-                dirty = None        # 16 x 16: past the windowed stages
-                y = pb.new_buf(16, 16, 96)
-                pb.blazechain(x.view(), [(npy(b.convs[0].weight), npy(b.convs[0].bias), npy(b.convs[1].weight), npy(b.convs[1].bias))
-                                         for b in blocks[i:i + nchain]], y.view())
-                i += nchain - 1
+            y = None
+            if nchain:
+                c = pb.new_buf(16, 16, 96, peek=True)
+                if pb.blazechain(x.view(), [(npy(b.convs[0].weight), npy(b.convs[0].bias), npy(b.convs[1].weight),
+                                             npy(b.convs[1].bias)) for b in blocks[i:i + nchain]], c.view()) is not None:
+                    dirty, y = None, pb.take(c)        # 16 x 16: past the windowed stages
+                    i += nchain - 1
+            if y is not None:
+                pass
             elif (isinstance(blk, BlazeBlock) and i + 1 < len(blocks) and isinstance(blocks[i + 1], BlazeBlock) and
                     blk.pairs_with(blocks[i + 1], pb, x.view())):
                 dirty = _dirty_rows(dirty, RF_PAIR, x.H)

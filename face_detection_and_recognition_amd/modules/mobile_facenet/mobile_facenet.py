@@ -121,36 +121,25 @@ class Depth_Wise(_NoCompute, metaclass=_X6Switch):
     def emit(self, pb, x, expanded=None, in_dw=None):
         """expanded: the output of self.conv when the caller has already produced it (fused into the previous
         depthwise Conv_block, see MobileFaceNet._emit); x is then only the residual source.  in_dw: a depthwise
-        Conv_block that precedes this block and is computed inside its kernel (FP_OPF_IN_DW: conv2_dw + conv_23)."""
+        Conv_block that precedes this block and is computed inside its kernel (FP_OPF_IN_DW: conv2_dw + conv_23); None
+        (nothing emitted) if no kernel takes the block in that form."""
         dw, pj, ex = self.conv_dw, self.project, self.conv
         shapes = Depth_Wise.BLOCK_SHAPES
         if shapes is None:
             shapes = getattr(pb, "dwblock_shapes", None)
         if shapes is None:
             shapes = Depth_Wise.block_policy(pb.N)
-        if (Depth_Wise.FUSE and Depth_Wise.X6 and expanded is None and dw.k == 3 and dw.p == 1 and
-                (ex.in_c, x.H) in pb.DWBLOCK_X6_SHAPES and pb.dwblock_supported(x, ex.in_c, ex.out_c, pj.out_c, dw.s)):
-            y = pb.new_buf(x.H, x.W, pj.out_c)
-            pb.dwblock(x, npy(ex.conv.weight), _affine(ex.bn), npy(ex.prelu.weight),
-                       npy(dw.conv.weight), _affine(dw.bn), npy(dw.prelu.weight),
-                       npy(pj.conv.weight), _affine(pj.bn), y.view(), self.residual, split=True)
-            return y
-        if (Depth_Wise.FUSE and Depth_Wise.X6 and expanded is None and dw.k == 3 and dw.p == 1 and not self.residual and
-                pb.dwblock_x6d_supported(x, ex.in_c, ex.out_c, pj.out_c, dw.s)):
-            y = pb.new_buf(x.H // 2, x.W // 2, pj.out_c)
-            pb.dwblock(x, npy(ex.conv.weight), _affine(ex.bn), npy(ex.prelu.weight),
-                       npy(dw.conv.weight), _affine(dw.bn), npy(dw.prelu.weight),
-                       npy(pj.conv.weight), _affine(pj.bn), y.view(), False, split=True, stride=2,
-                       in_dw=None if in_dw is None else (npy(in_dw.conv.weight), _affine(in_dw.bn), npy(in_dw.prelu.weight)))
-            return y
-        assert in_dw is None
-        if (Depth_Wise.FUSE and expanded is None and x.H in shapes and dw.k == 3 and dw.p == 1 and
-                pb.dwblock_supported(x, ex.in_c, ex.out_c, pj.out_c, dw.s)):
-            y = pb.new_buf(x.H, x.W, pj.out_c)
-            pb.dwblock(x, npy(ex.conv.weight), _affine(ex.bn), npy(ex.prelu.weight),
-                       npy(dw.conv.weight), _affine(dw.bn), npy(dw.prelu.weight),
-                       npy(pj.conv.weight), _affine(pj.bn), y.view(), self.residual)
-            return y
+        if Depth_Wise.FUSE and expanded is None and dw.k == 3 and dw.p == 1:
+            # the whole block as one op: the split kernel wherever it takes the block, the fp32 one on the map sizes of `shapes`
+            y = pb.new_buf(x.H // dw.s, x.W // dw.s, pj.out_c, peek=True)
+            if pb.dwblock(x, npy(ex.conv.weight), _affine(ex.bn), npy(ex.prelu.weight),
+                          npy(dw.conv.weight), _affine(dw.bn), npy(dw.prelu.weight),
+                          npy(pj.conv.weight), _affine(pj.bn), y.view(), self.residual, stride=dw.s,
+                          in_dw=None if in_dw is None else (npy(in_dw.conv.weight), _affine(in_dw.bn), npy(in_dw.prelu.weight)),
+                          fp32=x.H in shapes) is not None:
+                return pb.take(y)
+        if in_dw is not None:
+            return None
         a = expanded if expanded is not None else self.conv.emit(pb, x)
         if (Depth_Wise.FUSE and dw.k == 3 and dw.p == 1 and dw.groups % 64 == 0 and pj.out_c % 4 == 0 and
                 pj.out_c <= 128):
@@ -240,32 +229,29 @@ class MobileFaceNet(nn.Module):
         stem_dw = False
         if (Depth_Wise.FUSE and MobileFaceNet.STEM_DW and c1.groups == 1 and (c1.k, c1.s, c1.p) == (3, 2, 1) and
                 (c2.k, c2.s, c2.p) == (3, 1, 1) and c2.groups == c2.in_c == c2.out_c == c1.out_c):
-            y = pb.new_buf(H // 2, W // 2, c1.out_c)
-            if pb.stem_dw_ok(inp.view(), npy(c1.conv.weight), y.view(), 2, (1, 1), L.ACT_PRELU, L.RES_NONE):
-                # conv1 + conv2_dw in ONE kernel (FP_OPF_OUT_DW, csrc/stemdw.hip): conv1's 56 x 56 x 64 rows stay in LDS, the
-                # depthwise conv runs on them there; conv_23 below then runs in its plain form (no FP_OPF_IN_DW prologue)
-                s1, b1 = _affine(c1.bn)
-                pb.conv(inp.view(), npy(c1.conv.weight), y.view(), stride=2, pad=(1, 1), scale=s1, bias=b1,
-                        slope=npy(c1.prelu.weight), act=L.ACT_PRELU,
-                        out_dw=(npy(c2.conv.weight), _affine(c2.bn), npy(c2.prelu.weight)))
-                x, stem_dw = y, True
-            else:
-                pb.free(y)
+            # conv1 + conv2_dw in ONE kernel (FP_OPF_OUT_DW, csrc/stemdw.hip): conv1's 56 x 56 x 64 rows stay in LDS, the
+            # depthwise conv runs on them there; conv_23 below then runs in its plain form (no FP_OPF_IN_DW prologue)
+            y = pb.new_buf(H // 2, W // 2, c1.out_c, peek=True)
+            s1, b1 = _affine(c1.bn)
+            stem_dw = pb.conv(inp.view(), npy(c1.conv.weight), y.view(), stride=2, pad=(1, 1), scale=s1, bias=b1,
+                              slope=npy(c1.prelu.weight), act=L.ACT_PRELU,
+                              out_dw=(npy(c2.conv.weight), _affine(c2.bn), npy(c2.prelu.weight))) is not None
+            if stem_dw:
+                x = pb.take(y)
         if not stem_dw:
             x = c1.emit(pb, inp.view())
-        if stem_dw:
-            y = c23.emit(pb, x.view()); pb.free(x); x = y
-        elif (Depth_Wise.FUSE and Depth_Wise.X6 and MobileFaceNet.X6_CONV23 and c23.conv_dw.s == 2 and not c23.residual and
-                x.H == x.W and c2.out_c == c23.conv.in_c and
-                (c23.conv.in_c, c23.conv.out_c, c23.project.out_c, x.H) in pb.DWBLOCK_X6D_SHAPES):
-            # conv2_dw + ALL of conv_23 (expand -> dw stride 2 -> project) as one split-MFMA kernel: conv2_dw is formed in
-            # the kernel's prologue from an LDS image of conv1's rows (FP_OPF_IN_DW); neither its output (424 MB at 528
-            # crops) nor the 128-channel 56x56 tensor (848 MB) ever exists
-            if MobileFaceNet.X6_CONV2_IN and c2.k == 3 and c2.s == 1 and c2.p == 1 and c2.groups == c2.in_c == c2.out_c:
-                y = c23.emit(pb, x.view(), in_dw=c2); pb.free(x); x = y
-            else:
+        # conv2_dw + ALL of conv_23 (expand -> dw stride 2 -> project) as one split-MFMA kernel where it takes them: conv2_dw
+        # is formed in the kernel's prologue from an LDS image of conv1's rows (FP_OPF_IN_DW); neither its output (424 MB
+        # at 528 crops) nor the 128-channel 56x56 tensor (848 MB) ever exists
+        conv2_in = (not stem_dw and Depth_Wise.FUSE and Depth_Wise.X6 and MobileFaceNet.X6_CONV23 and
+                    MobileFaceNet.X6_CONV2_IN and c2.k == 3 and c2.s == 1 and c2.p == 1 and c2.groups == c2.in_c == c2.out_c)
+        y = c23.emit(pb, x.view(), in_dw=c2) if conv2_in else None
+        if y is not None:
+            pb.free(x); x = y
+        elif stem_dw or (Depth_Wise.FUSE and Depth_Wise.X6 and MobileFaceNet.X6_CONV23 and not MobileFaceNet.X6_CONV2_IN):
+            if not stem_dw:      # conv2_dw as a launch of its own, then conv_23 (as one op where the launcher takes it)
                 y = c2.emit(pb, x.view()); pb.free(x); x = y
-                y = c23.emit(pb, x.view()); pb.free(x); x = y
+            y = c23.emit(pb, x.view()); pb.free(x); x = y
         elif Depth_Wise.FUSE and c2.k == 3 and c2.s == 1 and c2.p == 1 and c2.groups % 64 == 0 and not c23.residual:
             # conv2_dw (dw3x3 + BN + PReLU) -> conv_23.conv (1x1 + BN + PReLU) as ONE dw->pw kernel: the 64-channel
             # 56x56 tensor between them (873 MB at N = 1088) never goes to HBM
@@ -317,7 +303,7 @@ class MobileFaceNet(nn.Module):
         if Depth_Wise.FUSE and Depth_Wise.X6:
             # every stride-1 block takes the split whole-block kernel before `shapes` is consulted (Depth_Wise.emit): the op
             # list does not depend on it, so ONE capacity = ONE plan and one arena whatever n_run is
-            shapes = tuple(h for h in shapes if (128 if h < 28 else 64, h) not in PlanBuilder.DWBLOCK_X6_SHAPES)
+            shapes = ()
         key = (N, shapes, switch_key(PlanBuilder, Depth_Wise, MobileFaceNet))
         return self._plans.get(key, lambda cache: self._build(N, cache, block_shapes=shapes))
 

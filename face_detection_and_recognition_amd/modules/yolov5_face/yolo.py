@@ -158,10 +158,10 @@ class StemBlock(_NoCompute):
                      cat.view(c, c), u8=u8)
             s2b, s3 = self.stem_2b, self.stem_3
             y = pb.new_buf(H1 // 2, W1 // 2, c).view() if out is None else out
+            # stem_2b -> cat -> stem_3 in one kernel (FP_OP_YSTEM2) where the launcher takes it: stem_2b's output never reaches HBM
             if (StemBlock.FUSE_TAIL and c == 32 and s2b.act and s3.act and s2b.k == 3 and s2b.s == 2 and s2b.p == 1 and
-                    pb.ystem2_supported(a.view(0, c // 2), cat.view(c, c), y)):
-                # stem_2b -> cat -> stem_3 in one kernel (FP_OP_YSTEM2): stem_2b's output never reaches HBM
-                pb.ystem2(a.view(0, c // 2), cat.view(c, c), npy(s2b.conv.weight), self._sb(s2b), npy(s3.conv.weight), self._sb(s3), y)
+                    pb.ystem2(a.view(0, c // 2), cat.view(c, c), npy(s2b.conv.weight), self._sb(s2b), npy(s3.conv.weight),
+                              self._sb(s3), y) is not None):
                 pb.free(a)
                 pb.free(cat)
                 return y
@@ -274,8 +274,8 @@ class ShuffleV2Block(_NoCompute):
                                      ConvParams(bf, bf, 1, 1, 0, bias=False), BNParams(bf, eps=1e-3), _Tag())
 
     FUSE = True   # class-wide switch: False emits the unfused DWCONV + CONV pairs (A/B parity tests)
-    FUSE_DOWN = True   # the whole stride-2 block as one FP_OP_SHUFDOWN where csrc/shufdown.hip has the shape (32 -> 128 channels)
-    FUSE_UNIT = True   # the whole stride-1 block as one FP_OP_SHUFUNIT where it has the width (128 channels)
+    FUSE_DOWN = True   # the whole stride-2 block as one FP_OP_SHUFDOWN where the launcher takes it (csrc/shufdown.hip)
+    FUSE_UNIT = True   # the whole stride-1 block as one FP_OP_SHUFUNIT where the launcher takes it
 
     def emit(self, pb, x, out=None):
         """out: optional View (C = oup) the block writes into, e.g. a channel slice of a later Concat's buffer."""
@@ -287,15 +287,15 @@ class ShuffleV2Block(_NoCompute):
         # cat + channel_shuffle(2) is the last conv's epilogue (FP_RES_SHUFFLE2): out[2n] = other half, out[2n+1] = conv
         b2 = self.branch2
         fuse2 = ShuffleV2Block.FUSE and self.bf % 64 == 0 and self.bf <= 128     # dw3x3 + 1x1 of branch2 in one kernel
-        if s == 2 and ShuffleV2Block.FUSE and ShuffleV2Block.FUSE_DOWN and pb.shufdown_supported(x, View(ob, oc, self.oup), self.inp, self.bf):
+        if s == 2 and ShuffleV2Block.FUSE and ShuffleV2Block.FUSE_DOWN:
             b1 = self.branch1
-            pb.shufdown(x, npy(b1[0].weight), _bn_sb(b1[1]), npy(b1[2].weight), _bn_sb(b1[3]),
-                        npy(b2[0].weight), _bn_sb(b2[1]), npy(b2[3].weight), _bn_sb(b2[4]), npy(b2[5].weight), _bn_sb(b2[6]),
-                        View(ob, oc, self.oup))
-            return out
-        if s == 1 and ShuffleV2Block.FUSE and ShuffleV2Block.FUSE_UNIT and pb.shufunit_supported(x, View(ob, oc, self.oup), self.bf):
-            pb.shufunit(x, npy(b2[0].weight), _bn_sb(b2[1]), npy(b2[3].weight), _bn_sb(b2[4]), npy(b2[5].weight), _bn_sb(b2[6]),
-                        View(ob, oc, self.oup))
+            if pb.shufdown(x, npy(b1[0].weight), _bn_sb(b1[1]), npy(b1[2].weight), _bn_sb(b1[3]),
+                           npy(b2[0].weight), _bn_sb(b2[1]), npy(b2[3].weight), _bn_sb(b2[4]), npy(b2[5].weight), _bn_sb(b2[6]),
+                           View(ob, oc, self.oup)) is not None:
+                return out
+        if s == 1 and ShuffleV2Block.FUSE and ShuffleV2Block.FUSE_UNIT and \
+                pb.shufunit(x, npy(b2[0].weight), _bn_sb(b2[1]), npy(b2[3].weight), _bn_sb(b2[4]), npy(b2[5].weight),
+                            _bn_sb(b2[6]), View(ob, oc, self.oup)) is not None:
             return out
         if s == 1:
             first = View(x.buf, x.coff, self.bf)                                          # x1 passthrough

@@ -78,16 +78,20 @@ class Arena:
         self.free = []   # sorted list of (off, size)
         self.top = 0
 
-    def alloc(self, size):
+    def place(self, size):
+        """(offset, size) of the block alloc(size) returns next; nothing is allocated."""
         size = round_up(size, 64)
-        for i, (off, sz) in enumerate(self.free):
-            if sz >= size:
+        return next(((off, size) for off, sz in self.free if sz >= size), (self.top, size))
+
+    def alloc(self, size):
+        off, size = self.place(size)
+        for i, (o, sz) in enumerate(self.free):
+            if o == off:
                 if sz == size:
                     self.free.pop(i)
                 else:
                     self.free[i] = (off + size, sz - size)
                 return off, size
-        off = self.top
         self.top += size
         return off, size
 
@@ -184,34 +188,49 @@ class PlanBuilder:
         self._placed = False
         self.windows = []       # [(op index, row_lo, row_end)]: the row windows of window() (applied by CompiledPlan)
         self.x6_all = False     # True: every conv the split-MFMA kernels accept runs there, whatever the size policy says
-                                # (pwx6_ok policy=False; set by the network that emits the plan: Inception-ResNet-v1)
+                                # (x6_policy; set by the network that emits the plan: Inception-ResNet-v1)
 
     # ---- memory ----
-    def new_buf(self, H, W, C):
+    def new_buf(self, H, W, C, peek=False):
+        """peek: the buffer the next new_buf(H, W, C) returns, not allocated (the output of an op that is only probed:
+        take() allocates it)."""
         C = cpad(C)
+        if peek:
+            return Buf(H, W, C, *self.arena.place(self.N * H * W * C))
         off, size = self.arena.alloc(self.N * H * W * C)
         self.peak = max(self.peak, self.arena.top)
         return Buf(H, W, C, off, size)
 
-    def new_buf_rowpad(self, H, W, C, dedicated=False):
+    def take(self, peeked):
+        """Allocate the buffer a peek named (nothing may have been allocated since the peek)."""
+        if peeked.rowpad:
+            buf = self.new_buf_rowpad(peeked.H, peeked.W, peeked.C, peeked.dedicated)
+        else:
+            buf = self.new_buf(peeked.H, peeked.W, peeked.C)
+        assert buf == peeked, (buf, peeked)
+        return buf
+
+    def new_buf_rowpad(self, H, W, C, dedicated=False, peek=False):
         """A buffer in the row-padded layout of include/facepath.h (one zero pixel after every row, a zero row above and
         below every image): 3x3 windows read it without bounds checks.  The pads must stay zero for the life of the
         plan, so these buffers live in a region of their own behind the recycled arena (no op ever writes there except
         through a row-padded view: a recycled block would carry another tensor's data into the pads), free() keeps
         them for the next row-padded buffer of the same shape, and the arena of such a plan starts zeroed.  Offsets are
         relative to that region until finish() places it.  dedicated: a buffer of its own that free() never hands out
-        again (the output of a row-windowed op, window())."""
+        again (the output of a row-windowed op, window()).  peek: as new_buf's."""
         assert not self._placed, "plan already finished"
         C = cpad(C)
-        pool = self.rowpad_free.setdefault((H, W, C), [])
+        pool = self.rowpad_free.get((H, W, C))
         if pool and not dedicated:
-            return pool.pop()
+            return pool[-1] if peek else pool.pop()
         ns = ((H + 2) * (W + 1) + 1) * C
         base = self.rowpad_top
+        buf = Buf(H, W, C, base + (W + 2) * C, self.N * ns, ns_=ns, rowpad=True, dedicated=dedicated)
+        if peek:
+            return buf
         self.rowpad_end = base + self.N * ns           # exact end of the region (the arena size is exact too)
         self.rowpad_top += round_up(self.N * ns, 64)
         self.has_rowpad = True
-        buf = Buf(H, W, C, base + (W + 2) * C, self.N * ns, ns_=ns, rowpad=True, dedicated=dedicated)
         self.rowpad_bufs.append(buf)
         return buf
 
@@ -252,6 +271,21 @@ class PlanBuilder:
         self.windows.append((len(self.ops) - 1, int(lo), int(end)))
 
     # ---- op emission ----
+    @staticmethod
+    def probe(op):
+        """The kernel the op's launcher picks for it (its dry run, fp_op_kernel_name), or None if the launcher refuses it.
+        The launchers alone decide which ops a kernel takes: an emitter fills in every field of a fused or split op, with
+        weight offsets that are multiples of 4 until the weights are packed (add_weight keeps every chunk 16-byte aligned),
+        asks, and emits that form only if the answer is a kernel."""
+        name = L.load().fp_op_kernel_name(C.byref(op)).decode()
+        return None if name == "?" else name
+
+    @staticmethod
+    def _offsets(op, *present):
+        """Provisional weight offsets (0, a multiple of 4) for the weight / scale / bias / slope blocks that are present,
+        -1 for the others."""
+        op.w_off, op.scale_off, op.bias_off, op.slope_off = (0 if p else -1 for p in present)
+
     def _base(self, kind, x, out, OH, OW):
         if x.up is not None and kind != L.OP_CONV:      # only conv() knows how to read a folded upsample
             self.materialise_up(x)
@@ -279,26 +313,46 @@ class PlanBuilder:
                 op.flags |= bit
         return op
 
-    # Pointwise convs with K >= PW_X6_MIN_K input channels on the bf16x6 split-MFMA kernel (csrc/pwx6.hip); 0 = never.
-    # (YOLOv5n-face forward at batch 256: 18.2 ms with 128, 17.0 ms with 64, 17.5 ms with 32.)
-    PW_X6_MIN_K = int(os.environ.get("FP_PW_X6_MIN_K", "64"))         # (the environment variables are lab knobs)
+    # ---- split-MFMA policy: which convs the split kernels (csrc/pwx6.hip) should run when they take them ----
     # Master switch of the bf16x6 split-MFMA kernels (csrc/split.h): False = every GEMM on the fp32 MFMA (the fmaf-chain
     # kernels of rounds 1-3).  Mobile-FaceNet's Depth_Wise.X6 is this attribute.
     X6 = True
-
-    # Dense 3x3 convs (pad 1, stride 1 / 2) with at least this many input channels on the split-MFMA kernel as well
-    # (csrc/pwx6.hip convx6_kernel; widths padded to 32 / 16 inside the weight planes); 0 = never.
+    # Pointwise convs with K >= PW_X6_MIN_K input channels on the split kernel; 0 = never.
+    # (YOLOv5n-face forward at batch 256: 18.2 ms with 128, 17.0 ms with 64, 17.5 ms with 32.)
+    PW_X6_MIN_K = int(os.environ.get("FP_PW_X6_MIN_K", "64"))         # (the environment variables are lab knobs)
+    # Dense 3x3 convs (pad 1, stride 1 / 2) with at least this many input channels on the split kernel as well; 0 = never.
     CONV3_X6_MIN_K = int(os.environ.get("FP_CONV3_X6_MIN_K", "32"))
+    # ... and those on 8 / 16 / 24 input channels, with K flattened over (tap, channel) (YOLOv5n-face's stem_2b, 16 -> 32
+    # stride 2 at 320x320: 945 us on conv_igemm_kernel)
+    CONV3_X6_FLAT = os.environ.get("FP_CONV3_X6_FLAT", "1") == "1"
     X6_SMALL_K_MIN_PIXELS = 400   # below 128 input channels only on maps of at least 20 x 20 (measured on YOLOv5-face; the
                                   # small-map 1x1 convs of BlazeFace stay on the fp32-MFMA kernels)
+    X6_MIN_COUT = 48              # from 32 input channels on, at least 48 outputs (32: a third of the three-tile chunk would
+                                  # be padding)
+    UP2_FOLD = os.environ.get("FP_UP2_FOLD", "1") == "1"   # nn.Upsample + Concat in front of a pointwise conv as operand addressing
 
-    # 3x3 convs on 8 / 16 / 24 input channels on the split kernel with K flattened over (tap, channel) (YOLOv5n-face's stem_2b,
-    # 16 -> 32 stride 2 at 320x320: 945 us on conv_igemm_kernel)
-    CONV3_X6_FLAT = os.environ.get("FP_CONV3_X6_FLAT", "1") == "1"
+    def x6_policy(self, x, out, kh, kw, stride, pad):
+        """True if the size policy above sends this conv to the split kernels (where the launcher takes it).  The policy
+        covers the 1x1 and 3x3-pad-1 shapes; every other window, and every conv of an x6_all plan, goes wherever the
+        launcher takes it."""
+        if not self.X6:
+            return False
+        k1 = (kh, kw, stride, *pad) == (1, 1, 1, 0, 0)
+        k3 = (kh, kw, *pad) == (3, 3, 1, 1)
+        if self.x6_all or not (k1 or k3):
+            return True
+        if k1 and (not self.PW_X6_MIN_K or x.C < self.PW_X6_MIN_K):
+            return False
+        if k3 and (not self.CONV3_X6_MIN_K or
+                   (x.C < self.CONV3_X6_MIN_K and not (self.CONV3_X6_FLAT and x.C in (8, 16, 24)))):
+            return False
+        if x.C < 128 and out.H * out.W < self.X6_SMALL_K_MIN_PIXELS:
+            return False
+        return x.C < 32 or out.C >= self.X6_MIN_COUT
 
     @staticmethod
     def x6_tiles(cout):
-        """(16-column tiles per chunk, padded width) -- mirror of general_tiles (csrc/pwx6.hip)."""
+        """(16-column tiles per chunk, padded width) of the split conv's weight planes: general_tiles (csrc/pwx6.hip)."""
         nt = (cout + 15) // 16
         if nt <= 2:
             per = 2
@@ -313,155 +367,112 @@ class PlanBuilder:
             per = 6 if p6 <= p4 else 4
         return per, (nt + per - 1) // per * per * 16
 
-    @classmethod
-    def pwx6_ok(cls, x, out, kh, kw, stride, pad, res, res_mode, policy=True):
-        """Mirror of fp_pwx6_eligible / fp_convx6_eligible (csrc/pwx6.hip) + (policy) the size policy above, which applies to
-        the 1x1 and 3x3-pad-1 shapes only: the other windows (KH, KW in 1..7, 0 <= pad < window, stride 1 / 2) take the split
-        kernel whenever it accepts them.  policy=False: the kernels' own eligibility alone."""
-        if not cls.X6 or out.cmul != 1 or x.buf.rowpad or out.buf.rowpad:
-            return False
-        pt, pl = pad
-        if not (1 <= kh <= 7 and 1 <= kw <= 7 and 0 <= pt < kh and 0 <= pl < kw and stride in (1, 2) and
-                x.H + 2 * pt >= kh and x.W + 2 * pl >= kw and
-                (out.H, out.W) == ((x.H + 2 * pt - kh) // stride + 1, (x.W + 2 * pl - kw) // stride + 1)):
-            return False
-        k3 = (kh, kw, pt, pl) == (3, 3, 1, 1)
-        k1 = (kh, kw, stride, pt, pl) == (1, 1, 1, 0, 0)
-        if x.C < 32 and (kh, kw) != (3, 3):      # the flat form (K over (tap, channel)) is 3x3 only
-            return False
-        if policy and k1:
-            if not cls.PW_X6_MIN_K or x.C < cls.PW_X6_MIN_K:
-                return False
-        elif policy and k3:
-            flat = cls.CONV3_X6_FLAT and x.C in (8, 16, 24)      # K flattened over (tap, channel): csrc/pwx6.hip convx6_kernel
-            if not cls.CONV3_X6_MIN_K or (x.C < cls.CONV3_X6_MIN_K and not flat):
-                return False
-        if policy and (k1 or k3) and x.C < 128 and out.H * out.W < cls.X6_SMALL_K_MIN_PIXELS:
-            return False
-        fast = k1 and x.C % 32 == 0 and x.C >= 64 and (out.C in (48, 64) or out.C % 128 == 0) and x.buf.ns == x.H * x.W * x.buf.ld
-        min_cout = 48 if policy and (k1 or k3) and x.C >= 32 else 32   # (32 outputs: a third of the three-tile chunk would be padding)
-        if x.C % 4 or out.C % 4 or out.C < min_cout or (not fast and (out.H * out.W < 2 or out.W < 2)):
-            return False
-        ohw = out.H * out.W
-        if x.buf.ns < x.H * x.W * x.buf.ld or x.buf.ns % 4 or x.buf.ld % 4 or (x.buf.off + x.coff) % 4:
-            return False
-        for v in [out] + ([res] if res_mode != L.RES_NONE else []):
-            if v.buf.ns != ohw * v.buf.ld or v.buf.ld % 4 or (v.buf.off + v.coff) % 4:
-                return False
-        if res_mode == L.RES_POOL2_BEFORE_ACT:
-            return False
-        if res_mode != L.RES_NONE and min(res.C, out.C) % 4:
-            return False
-        if res_mode == L.RES_SHUFFLE2 and (res.C < out.C or out.buf.ld < 2 * out.C):
-            return False
-        return True
-
-    UP2_FOLD = os.environ.get("FP_UP2_FOLD", "1") == "1"   # nn.Upsample + Concat in front of a pointwise conv as operand addressing
-
-    def up2_ok(self, x, out, kh, kw, stride, pad, res_mode):
-        """Mirror of the FP_OPF_IN_UP2 clauses of fp_pwx6_eligible / fp_convx6_eligible (csrc/pwx6.hip): x.up can be read in
-        place of the upsampled slice."""
-        u = x.up
-        return (self.UP2_FOLD and u is not None and res_mode == L.RES_NONE and (kh, kw, stride) == (1, 1, 1) and
-                tuple(pad) == (0, 0) and u.C % 8 == 0 and 0 < u.C < x.C and u.cmul == 1 and
-                x.H % 2 == 0 and x.W % 2 == 0 and (u.H, u.W) == (x.H // 2, x.W // 2) and not u.buf.rowpad and
-                u.buf.ld % 4 == 0 and (u.buf.off + u.coff) % 4 == 0 and u.buf.ns % 4 == 0 and
-                u.buf.ns >= u.H * u.W * u.buf.ld and self.pwx6_ok(x, out, kh, kw, stride, pad, None, res_mode))
-
     def materialise_up(self, x):
         """Write the upsampled slice of a view that still carries `up` (a consumer that cannot fold it)."""
         if x.up is not None:
             u, x.up = x.up, None
             self.upsample2x(u, View(x.buf, x.coff, u.C))
 
-    @staticmethod
-    def stem_dw_ok(x, w, out, stride, pad, act, res_mode):
-        """Mirror of fp_stemdw_supported (csrc/stemdw.hip): Mobile-FaceNet's conv1 on a dense 112 x 112 4-float-pixel image."""
-        return (tuple(w.shape) == (64, 3, 3, 3) and stride == 2 and tuple(pad) == (1, 1) and act == L.ACT_PRELU and
-                res_mode == L.RES_NONE and (x.H, x.W, x.C) == (112, 112, 4) and x.buf.ld == 4 and x.coff == 0 and
-                x.up is None and not x.buf.rowpad and (out.H, out.W, out.C) == (56, 56, 64) and out.cmul == 1 and
-                out.coff == 0 and out.buf.ld == 64 and not out.buf.rowpad)
-
-    def conv(self, x, w, out, stride=1, pad=(0, 0), scale=None, bias=None, slope=None,
-             act=L.ACT_NONE, res=None, res_mode=L.RES_NONE, n_convs=1, out_dw=None):
-        """Dense conv (OIHW weight); out is a View whose C >= Cout (extra channels get zeros).
-        out_dw = (weights [C,1,3,3], (scale, bias), PReLU slope) of a depthwise 3x3 stride-1 pad-1 Conv_block computed behind
-        the conv in the same kernel (FP_OPF_OUT_DW: Mobile-FaceNet's conv1 + conv2_dw); `out` then receives ITS output."""
+    @classmethod
+    def conv_weights(cls, w, cin_phys, cout_phys, flags):
+        """The packed weights (at w_off) of a conv op with these flags: OIHW w for cin_phys input and cout_phys output channels."""
         cout, cin, kh, kw = w.shape
-        assert cin <= x.C, (cin, x.C)
-        OH, OW = out.H, out.W
-        fold = x.up is not None and self.up2_ok(x, out, kh, kw, stride, pad, res_mode)
-        if x.up is not None and not fold:
-            self.materialise_up(x)
-        op = self._base(L.OP_CONV, x, out, OH, OW)
-        op.Cout = out.C
-        op.KH, op.KW, op.stride = kh, kw, stride
-        op.pad_t, op.pad_l = pad
-        op.act, op.res_mode = act, res_mode
-        if fold:
-            u = x.up
-            op.flags |= L.OPF_IN_UP2
-            op.res_ld, op.res_ns, op.res_off = u.buf.ld, u.buf.ns, u.buf.off + u.coff
-            op.res_C, op.res_H, op.res_W = u.C, u.H, u.W
-        if out_dw is not None and self.X6:
+        if flags & L.OPF_OUT_DW and flags & L.OPF_SPLIT3:
             # FP_OPF_OUT_DW + FP_OPF_SPLIT3 (csrc/stemdw.hip): K = (tap, channel) flattened into one 32-k slab, three bf16 planes
             # [channel tile of 16][plane][channel][32 k]
             flat = np.zeros((cout, 32), np.float32)
             flat[:, :kh * kw * cin] = np.asarray(w, np.float32).transpose(0, 2, 3, 1).reshape(cout, -1)     # k = (ky*3 + kx)*3 + c
             w3 = split3_bf16(flat).reshape(3, cout // 16, 16, 32).transpose(1, 0, 2, 3)
-            op.w_off = self.add_weight(np.ascontiguousarray(w3).reshape(-1).view(np.float32))
-            op.flags |= L.OPF_SPLIT3
-        elif self.pwx6_ok(x, out, kh, kw, stride, pad, res, res_mode, policy=not self.x6_all) and not (op.flags & ~L.OPF_IN_UP2):
+        elif flags & L.OPF_SPLIT3:
             # three bf16 planes [tap * CS + cs][3][Npad][32] (include/facepath.h, FP_OPF_SPLIT3 on FP_OP_CONV): K runs
             # over (tap, 32-channel slab), zero rows / columns in the padding of Cin to 32 and Cout to whole chunks
-            cs = (x.C + 31) // 32
-            npad = self.x6_tiles(out.C)[1]
-            if x.C < 32:      # flat: k = tap * Cin_phys + channel, slabs of 32 consecutive k, zero rows behind the last tap
-                nsl = (kh * kw * x.C + 31) // 32
+            cs = (cin_phys + 31) // 32
+            npad = cls.x6_tiles(cout_phys)[1]
+            if cin_phys < 32:      # flat: k = tap * Cin_phys + channel, slabs of 32 consecutive k, zero rows behind the last tap
+                nsl = (kh * kw * cin_phys + 31) // 32
                 flat = np.zeros((npad, nsl * 32), np.float32)
-                wt = np.zeros((cout, kh * kw, x.C), np.float32)
+                wt = np.zeros((cout, kh * kw, cin_phys), np.float32)
                 wt[:, :, :cin] = np.asarray(w, np.float32).reshape(cout, cin, kh * kw).transpose(0, 2, 1)
-                flat[:cout, :kh * kw * x.C] = wt.reshape(cout, -1)
+                flat[:cout, :kh * kw * cin_phys] = wt.reshape(cout, -1)
                 w3 = split3_bf16(flat).reshape(3, npad, nsl, 32).transpose(2, 0, 1, 3)       # [slab][plane][n][32]
             else:
                 full = np.zeros((kh * kw, npad, cs * 32), np.float32)
                 full[:, :cout, :cin] = np.asarray(w, np.float32).reshape(cout, cin, kh * kw).transpose(2, 0, 1)
                 w3 = split3_bf16(full).reshape(3, kh * kw, npad, cs, 32).transpose(1, 3, 0, 2, 4)
-            op.w_off = self.add_weight(np.ascontiguousarray(w3).reshape(-1).view(np.float32))
-            op.flags |= L.OPF_SPLIT3
         else:
-            op.w_off = self.add_weight(pack_conv_weight(w, x.C, out.C))
-        if cin == 3 and x.C == 4 and x.buf.ld == 4:   # 3-channel image padded to 16-byte pixels: the pad channel's weights are zero
-            op.flags |= L.OPF_IN_C3
+            return pack_conv_weight(w, cin_phys, cout_phys)
+        return np.ascontiguousarray(w3).reshape(-1).view(np.float32)
+
+    def conv(self, x, w, out, stride=1, pad=(0, 0), scale=None, bias=None, slope=None,
+             act=L.ACT_NONE, res=None, res_mode=L.RES_NONE, n_convs=1, out_dw=None):
+        """Dense conv (OIHW weight); out is a View whose C >= Cout (extra channels get zeros).  On the split kernels
+        (FP_OPF_SPLIT3) when x6_policy says so and the launcher takes the op, reading a folded upsample of x (FP_OPF_IN_UP2)
+        if the launcher takes that too; else on the fp32 kernels.
+        out_dw = (weights [C,1,3,3], (scale, bias), PReLU slope) of a depthwise 3x3 stride-1 pad-1 Conv_block computed behind
+        the conv in the same kernel (FP_OPF_OUT_DW: Mobile-FaceNet's conv1 + conv2_dw); `out` then receives ITS output.  Returns
+        None (nothing emitted) if the launcher refuses that op."""
+        cout, cin, kh, kw = w.shape
+        assert cin <= x.C, (cin, x.C)
+        if res_mode == L.RES_SHUFFLE2:   # out is the dense view of the conv's own Cout channels; 2*Cout are written
+            assert out.cmul == 1 and out.coff + 2 * out.C <= out.buf.ld and res is not None and res.C >= out.C
+        if res_mode != L.RES_NONE:
+            assert res is not None and res.cmul == 1
+
+        def make(flags):
+            op = self._base(L.OP_CONV, x, out, out.H, out.W)
+            op.flags |= flags
+            op.Cout = out.C
+            op.KH, op.KW, op.stride = kh, kw, stride
+            op.pad_t, op.pad_l = pad
+            op.act, op.res_mode = act, res_mode
+            if cin == 3 and x.C == 4 and x.buf.ld == 4:   # 3-channel image padded to 16-byte pixels: the pad channel's weights are zero
+                op.flags |= L.OPF_IN_C3
+            self._offsets(op, True, scale is not None, bias is not None, slope is not None)
+            if flags & L.OPF_IN_UP2:
+                u = x.up
+                assert u.cmul == 1 and not u.buf.rowpad, "the op reads the half-size map as a dense slice"
+                op.res_ld, op.res_ns, op.res_off = u.buf.ld, u.buf.ns, u.buf.off + u.coff
+                op.res_C, op.res_H, op.res_W = u.C, u.H, u.W
+            elif res_mode != L.RES_NONE:
+                op.res_ld, op.res_ns, op.res_off = res.buf.ld, res.buf.ns, res.buf.off + res.coff
+                op.res_C = min(res.C, out.C)
+                op.res_H, op.res_W = res.H, res.W
+            return op
+
+        flags = 0
+        if out_dw is not None:
+            flags = L.OPF_OUT_DW | (L.OPF_SPLIT3 if self.X6 else 0)
+            if self.probe(make(flags)) is None:
+                return None
+        elif self.x6_policy(x, out, kh, kw, stride, pad):
+            if (x.up is not None and self.UP2_FOLD and res_mode == L.RES_NONE and
+                    self.probe(make(L.OPF_SPLIT3 | L.OPF_IN_UP2)) is not None):
+                flags = L.OPF_SPLIT3 | L.OPF_IN_UP2
+            elif self.probe(make(L.OPF_SPLIT3)) is not None:
+                flags = L.OPF_SPLIT3
+        if not flags & L.OPF_IN_UP2:
+            self.materialise_up(x)
+        op = make(flags)
+        op.w_off = self.add_weight(self.conv_weights(w, x.C, out.C, op.flags))
         if scale is not None:
             op.scale_off = self.add_weight(pad_vec(scale, out.C, 0.0))
         if bias is not None:
             op.bias_off = self.add_weight(pad_vec(bias, out.C, 0.0))
         if out_dw is not None:
             # the conv's slopes followed by the depthwise block [12][Cout]: nine taps, BN scale, BN bias, PReLU slope
-            assert self.stem_dw_ok(x, w, out, stride, pad, act, res_mode) and slope is not None
             dw_w, dw_aff, dw_slope = out_dw
             assert tuple(dw_w.shape) == (out.C, 1, 3, 3)
-            op.flags |= L.OPF_OUT_DW
             op.slope_off = self.add_weight(np.concatenate([pad_vec(slope, out.C, 0.0), pack_dw_weight(dw_w, out.C),
                                                            pad_vec(dw_aff[0], out.C), pad_vec(dw_aff[1], out.C),
                                                            pad_vec(dw_slope, out.C)]))
         elif slope is not None:
             op.slope_off = self.add_weight(pad_vec(slope, out.C, 0.0))
-        if res_mode == L.RES_SHUFFLE2:   # out is the dense view of the conv's own Cout channels; 2*Cout are written
-            assert out.cmul == 1 and out.coff + 2 * out.C <= out.buf.ld and res is not None and res.C >= out.C
-        if res_mode != L.RES_NONE:
-            assert res is not None and res.cmul == 1
-            op.res_ld = res.buf.ld
-            op.res_ns = res.buf.ns
-            op.res_off = res.buf.off + res.coff
-            op.res_C = min(res.C, out.C)
-            op.res_H, op.res_W = res.H, res.W
         self.ops.append(op)
         # n_convs > 1: several reference convs on the same input merged into one op (their outputs concatenated): the
         # op-granular model (SURVEY 8d) counts the input once per conv
         # (FP_OPF_OUT_DW: + the depthwise conv's input and output, SURVEY 8d counts every conv)
-        self.alg_bytes.append(4 * self.N * (n_convs * x.H * x.W * cin + OH * OW * cout + (2 * OH * OW * cout if out_dw is not None else 0)))
+        self.alg_bytes.append(4 * self.N * (n_convs * x.H * x.W * cin + out.H * out.W * cout +
+                                            (2 * out.H * out.W * cout if out_dw is not None else 0)))
         return out
 
     def dwconv(self, x, w, out, stride=1, pad=(0, 0), scale=None, bias=None, slope=None, act=L.ACT_NONE):
@@ -483,24 +494,23 @@ class PlanBuilder:
         self.alg_bytes.append(4 * self.N * (x.H * x.W * c + out.H * out.W * c))
         return out
 
-    @staticmethod
-    def blazeblock_lds_bytes(cin_phys, cout_phys):
-        """Mirror of fp_blazeblock_lds_bytes (csrc/blaze.hip): the fused kernel needs <= 64 KiB of LDS."""
-        kpad, npad = round_up(cin_phys, 8), round_up(cout_phys, 32)
-        a = 128 * max(kpad + 4, cout_phys)
-        return 4 * (a + 128 * (cin_phys + 4) + kpad * npad + 10 * cin_phys)
-
-    def blazeblock(self, x, wd, bd, wp, bp, out, stride):
-        """Fused BlazeBlock (blazeface.py:12-47): dw3x3(stride) -> 1x1 -> + shortcut -> ReLU in one kernel."""
-        cin = wd.shape[0]
-        cout = wp.shape[0]
-        assert out.cmul == 1 and out.coff == 0 and out.buf.ld == out.C
+    def blazeblock_op(self, x, out, cin, stride):
+        """The FP_OP_BLAZEBLOCK op of a cin -> out.C block on view x, weights not yet packed (blazeblock(); probe())."""
         op = self._base(L.OP_BLAZEBLOCK, x, out, out.H, out.W)
         op.Cout = out.C
         op.KH = op.KW = 3
         op.stride = stride
         op.pad_t = op.pad_l = 1 if stride == 1 else 0
         op.res_C = min(cin, x.C)
+        self._offsets(op, True, True, True, True)
+        return op
+
+    def blazeblock(self, x, wd, bd, wp, bp, out, stride):
+        """Fused BlazeBlock (blazeface.py:12-47): dw3x3(stride) -> 1x1 -> + shortcut -> ReLU in one kernel."""
+        cin = wd.shape[0]
+        cout = wp.shape[0]
+        assert out.cmul == 1 and out.coff == 0 and out.buf.ld == out.C
+        op = self.blazeblock_op(x, out, cin, stride)
         op.w_off = self.add_weight(pack_dw_weight(wd, x.C))
         op.scale_off = self.add_weight(pad_vec(bd, x.C, 0.0))
         op.slope_off = self.add_weight(pack_conv_weight(wp, x.C, out.C))
@@ -510,25 +520,30 @@ class PlanBuilder:
         self.alg_bytes.append(4 * self.N * (x.H * x.W * cin + opix * cin + opix * cin + opix * cout))
         return out
 
-    @staticmethod
-    def blazepair_supported(x):
-        """Mirror of fp_blazepair_supported (csrc/blazepair.hip): a row-padded 24-channel map, 128 or 64 pixels wide."""
-        return (x.buf.rowpad and x.coff == 0 and x.C == 24 and x.buf.ld == 24 and x.W in (128, 64) and x.H % 8 == 0 and
-                x.H >= 64)
+    def blazepair_op(self, x, out, stride):
+        """The FP_OP_BLAZEPAIR op of two BlazeBlocks on the row-padded view x, the second of stride `stride`, weights not yet
+        packed (blazepair(), blazepair_s2(); probe())."""
+        op = self._base(L.OP_BLAZEPAIR, x, out, out.H, out.W)
+        op.Cout = out.C
+        op.KH = op.KW = 3
+        op.stride = stride
+        op.pad_t = op.pad_l = 1 if stride == 1 else 0
+        op.act, op.res_C = L.ACT_RELU, 24
+        op.res_mode = L.RES_ADD_BEFORE_ACT if stride == 1 else L.RES_POOL2_BEFORE_ACT
+        op.res_ld, op.res_ns, op.res_off, op.res_H, op.res_W = op.in_ld, op.in_ns, op.in_off, x.H, x.W
+        self._offsets(op, True, True, True, True)
+        return op
 
     def blazepair(self, x, blocks, out):
         """Two consecutive stride-1 24 -> 24 BlazeBlocks (blazeface.py:12-47) as ONE op (FP_OP_BLAZEPAIR): blocks =
-        ((dw_w, dw_b, pw_w, pw_b), (dw_w, dw_b, pw_w, pw_b)); the tensor between them never reaches HBM."""
-        assert self.blazepair_supported(x) and len(blocks) == 2 and out.C == 24 and out.coff == 0 and out.buf.ld == 24
-        op = self._base(L.OP_BLAZEPAIR, x, out, out.H, out.W)
-        op.Cout = 24
-        op.KH = op.KW = 3
-        op.stride = 1
-        op.pad_t = op.pad_l = 1
-        op.act, op.res_mode, op.res_C = L.ACT_RELU, L.RES_ADD_BEFORE_ACT, 24
-        op.res_ld, op.res_ns, op.res_off, op.res_H, op.res_W = op.in_ld, op.in_ns, op.in_off, x.H, x.W
+        ((dw_w, dw_b, pw_w, pw_b), (dw_w, dw_b, pw_w, pw_b)); the tensor between them never reaches HBM.  None (nothing
+        emitted) if the launcher refuses the op (csrc/blazepair.hip: a row-padded map 128 or 64 pixels wide)."""
+        assert len(blocks) == 2
         for wd, bd, wp, bp in blocks:
             assert wd.shape == (24, 1, 3, 3) and wp.shape[:2] == (24, 24)
+        op = self.blazepair_op(x, out, 1)
+        if self.probe(op) is None:
+            return None
         op.w_off = self.add_weight(np.concatenate([pack_dw_weight(b[0], 24) for b in blocks]))
         op.scale_off = self.add_weight(np.concatenate([pad_vec(b[1], 24) for b in blocks]))
         op.slope_off = self.add_weight(np.concatenate([pack_conv_weight(b[2], 24, 24) for b in blocks]))
@@ -538,29 +553,18 @@ class PlanBuilder:
         self.alg_bytes.append(2 * 4 * self.N * pix * 24 * 4)      # two blocks, four tensor passes each
         return out
 
-    @staticmethod
-    def blazepair_s2_supported(x, cout2):
-        """Mirror of fp_blazepair_s2_supported (csrc/blazepairs2.hip): a row-padded 24-channel map, 128 or 64 pixels wide, in
-        front of a stride-1 24 -> 24 block followed by a stride-2 24 -> 24 / 48 block."""
-        return (x.buf.rowpad and x.coff == 0 and x.C == 24 and x.buf.ld == 24 and x.W in (128, 64) and x.H % 8 == 0 and
-                x.H >= 16 and cout2 in (24, 48))      # H / 2 output rows in bands of a multiple of 4, at least two bands
-
     def blazepair_s2(self, x, blocks, out):
         """A stride-1 24 -> 24 BlazeBlock and the STRIDE-2 BlazeBlock behind it (blazeface.py:12-47) as ONE op (FP_OP_BLAZEPAIR
         with stride = 2): blocks = ((dw_w, dw_b, pw_w, pw_b) of the stride-1 block, the same of the stride-2 block); the
-        full-size tensor between them never reaches HBM, `out` is the half-size map (dense or row-padded, ld = its channels)."""
-        cout2 = blocks[1][2].shape[0]
-        assert self.blazepair_s2_supported(x, cout2) and len(blocks) == 2
-        assert out.C == cout2 and out.coff == 0 and out.buf.ld == cout2 and (out.H, out.W) == (x.H // 2, x.W // 2)
-        op = self._base(L.OP_BLAZEPAIR, x, out, out.H, out.W)
-        op.Cout = cout2
-        op.KH = op.KW = 3
-        op.stride = 2
-        op.pad_t = op.pad_l = 0
-        op.act, op.res_mode, op.res_C = L.ACT_RELU, L.RES_POOL2_BEFORE_ACT, 24
-        op.res_ld, op.res_ns, op.res_off, op.res_H, op.res_W = op.in_ld, op.in_ns, op.in_off, x.H, x.W
+        full-size tensor between them never reaches HBM, `out` is the half-size map (dense or row-padded, ld = its channels).
+        None (nothing emitted) if the launcher refuses the op (csrc/blazepairs2.hip)."""
         (wd1, bd1, wp1, bp1), (wd2, bd2, wp2, bp2) = blocks
-        assert wd1.shape == (24, 1, 3, 3) and wp1.shape[:2] == (24, 24) and wd2.shape == (24, 1, 3, 3) and wp2.shape[:2] == (cout2, 24)
+        cout2 = wp2.shape[0]
+        assert wd1.shape == (24, 1, 3, 3) and wp1.shape[:2] == (24, 24) and wd2.shape == (24, 1, 3, 3) and wp2.shape[1] == 24
+        assert out.C == cout2
+        op = self.blazepair_op(x, out, 2)
+        if self.probe(op) is None:
+            return None
         op.w_off = self.add_weight(np.concatenate([pack_dw_weight(wd1, 24), pack_dw_weight(wd2, 24)]))
         op.scale_off = self.add_weight(np.concatenate([pad_vec(bd1, 24), pad_vec(bd2, 24)]))
         op.slope_off = self.add_weight(np.concatenate([pack_conv_weight(wp1, 24, 24), pack_conv_weight(wp2, 24, cout2)]))
@@ -571,29 +575,27 @@ class PlanBuilder:
         self.alg_bytes.append(4 * self.N * (pix * 24 * 4 + pix * 24 + opix * 24 + opix * 24 + opix * cout2))
         return out
 
-    @staticmethod
-    def blazechain_supported(x):
-        """Mirror of fp_blazechain_supported (csrc/blazechain.hip): a dense 96-channel 16 x 16 map."""
-        return (not x.buf.rowpad and x.coff == 0 and x.C == 96 and x.buf.ld == 96 and x.cmul == 1 and x.H == 16 and x.W == 16)
-
     def blazechain(self, x, blocks, out):
         """A run of stride-1 96 -> 96 BlazeBlocks on the 16 x 16 map (blazeface.py:12-47,146-152) as ONE op
         (FP_OP_BLAZECHAIN): blocks = ((dw_w, dw_b, pw_w, pw_b), ...); the tensors between them never reach HBM.  The 1x1
-        weights go in as three bf16 planes (split3_bf16), one slab per 32 input channels: include/facepath.h BLAZECHAIN."""
-        assert self.blazechain_supported(x) and 1 <= len(blocks) <= 16
-        assert out.C == 96 and out.coff == 0 and out.buf.ld == 96 and not out.buf.rowpad and (out.H, out.W) == (16, 16)
-        op = self._base(L.OP_BLAZECHAIN, x, out, 16, 16)
-        op.Cout = 96
+        weights go in as three bf16 planes (split3_bf16), one slab per 32 input channels: include/facepath.h BLAZECHAIN.
+        None (nothing emitted) if the launcher refuses the op (csrc/blazechain.hip)."""
+        for wd, bd, wp, bp in blocks:
+            assert wd.shape == (96, 1, 3, 3) and wp.shape[:2] == (96, 96)
+        op = self._base(L.OP_BLAZECHAIN, x, out, out.H, out.W)
+        op.Cout = out.C
         op.KH = op.KW = 3
         op.stride = 1
         op.pad_t = op.pad_l = 1
         op.act, op.res_mode, op.res_C = L.ACT_RELU, L.RES_ADD_BEFORE_ACT, 96
-        op.res_ld, op.res_ns, op.res_off, op.res_H, op.res_W = op.in_ld, op.in_ns, op.in_off, 16, 16
+        op.res_ld, op.res_ns, op.res_off, op.res_H, op.res_W = op.in_ld, op.in_ns, op.in_off, x.H, x.W
         op.Cmid = len(blocks)
         op.flags |= L.OPF_SPLIT3
+        self._offsets(op, True, False, False, False)
+        if self.probe(op) is None:
+            return None
         chunks = []
         for wd, bd, wp, bp in blocks:
-            assert wd.shape == (96, 1, 3, 3) and wp.shape[:2] == (96, 96)
             par = np.zeros(1280, np.float32)
             par[:864] = pack_dw_weight(wd, 96)
             par[864:960] = pad_vec(bd, 96)
@@ -607,33 +609,16 @@ class PlanBuilder:
         return out
 
     DWPW_X6 = os.environ.get("FP_DWPW_X6", "1") == "1"    # the dw -> 1x1 op with its 1x1 on the split MFMA (csrc/dwpwx6.hip)
-
-    @classmethod
-    def dwpwx6_ok(cls, x, out, G, stride, res, shuffle, out_slope, out_act):
-        """Mirror of fp_dwpwx6_eligible (csrc/dwpwx6.hip)."""
-        if not (cls.X6 and cls.DWPW_X6) or out_slope is not None or out_act not in (L.ACT_NONE, L.ACT_SILU) or stride not in (1, 2):
-            return False
-        if G % 32 or G > 256 or out.C not in (64, 128) or out.W % 4 or out.cmul != 1 or x.buf.rowpad or out.buf.rowpad:
-            return False
-        if out.C != 128:      # measured on YOLOv5n-face (256 images): 128 -> 128 at 40x40 278 -> 246 us, 80x80 stride 2 367 / 298 ->
-            return False      # 345 / 248; 64 -> 64 at 80x80 420 -> 440 (the depthwise phase, not the 1x1, bounds the narrow form)
-        ohw = out.H * out.W
-        if x.buf.ld % 4 or (x.buf.off + x.coff) % 4 or x.buf.ns % 4 or x.buf.ns < x.H * x.W * x.buf.ld:
-            return False
-        for v in [out] + ([res] if res is not None else []):
-            if v.buf.ld % 4 or (v.buf.off + v.coff) % 4 or v.buf.ns != ohw * v.buf.ld:
-                return False
-        if res is not None and min(res.C, out.C) % 4:
-            return False
-        if shuffle and (res.C < out.C or out.buf.ld < 2 * out.C):
-            return False
-        return True
+    # ... for 128 outputs only: measured on YOLOv5n-face (256 images): 128 -> 128 at 40x40 278 -> 246 us, 80x80 stride 2
+    # 367 / 298 -> 345 / 248; 64 -> 64 at 80x80 420 -> 440 (the depthwise phase, not the 1x1, bounds the narrow form)
+    DWPW_X6_COUT = 128
 
     def dwpw(self, x, dw_w, dw_scale, dw_bias, dw_slope, pw_w, pw_scale, pw_bias, out, stride, res=None,
              out_slope=None, out_act=L.ACT_NONE, shuffle=False):
         """Fused Depth_Wise tail (mobile_facenet.py:72-85): dw3x3 stride s (+BN affine, +PReLU) -> 1x1 (+BN affine)
         [+ res], or -- with out_slope -- a depthwise Conv_block followed by a 1x1 Conv_block (BN + PReLU on both:
-        conv2_dw -> conv_23.conv, mobile_facenet.py:117-118,70).  x has G (multiple of 64) channels."""
+        conv2_dw -> conv_23.conv, mobile_facenet.py:117-118,70).  x has G (multiple of 64) channels.  The 1x1 runs on the
+        split MFMA (FP_OPF_SPLIT3) when DWPW_X6 and DWPW_X6_COUT allow it and the launcher takes the op."""
         G = dw_w.shape[0]
         cout, cin = pw_w.shape[0], pw_w.shape[1]
         assert cin == G == x.C and G % 64 == 0 and out.cmul == 1
@@ -643,14 +628,29 @@ class PlanBuilder:
             assert res is not None and res.C >= out.C and out.coff + 2 * out.C <= out.buf.ld
         else:
             assert out.coff == 0 and out.buf.ld == out.C or out_act != L.ACT_NONE
-        op = self._base(L.OP_DWPW, x, out, out.H, out.W)
-        split = self.dwpwx6_ok(x, out, G, stride, res, shuffle, out_slope, out_act)
-        op.act2 = out_act
-        op.Cout = out.C
-        op.KH = op.KW = 3
-        op.stride = stride
-        op.pad_t = op.pad_l = 1
-        op.act = L.ACT_PRELU if dw_slope is not None else L.ACT_NONE
+        assert res is None or (res.cmul == 1 and out_slope is None)
+
+        def make(flags):
+            op = self._base(L.OP_DWPW, x, out, out.H, out.W)
+            op.flags |= flags
+            op.act2 = out_act
+            op.Cout = out.C
+            op.KH = op.KW = 3
+            op.stride = stride
+            op.pad_t = op.pad_l = 1
+            op.act = L.ACT_PRELU if dw_slope is not None else L.ACT_NONE
+            op.w_off, op.slope_off, op.bias_off = 0, 0, 0 if out_slope is not None else -1
+            if res is not None:
+                op.res_mode = L.RES_SHUFFLE2 if shuffle else L.RES_ADD_AFTER_ACT
+                op.res_ld, op.res_ns = res.buf.ld, res.buf.ns
+                op.res_off = res.buf.off + res.coff
+                op.res_C = min(res.C, out.C)
+                op.res_H, op.res_W = res.H, res.W
+            return op
+
+        split = (self.X6 and self.DWPW_X6 and out.C == self.DWPW_X6_COUT and
+                 self.probe(make(L.OPF_SPLIT3)) is not None)
+        op = make(L.OPF_SPLIT3 if split else 0)
         slope = dw_slope if dw_slope is not None else np.zeros(G, np.float32)
         op.w_off = self.add_weight(np.concatenate([pack_dw_weight(dw_w, G), pad_vec(dw_scale, G), pad_vec(dw_bias, G),
                                                    pad_vec(slope, G)]))
@@ -660,69 +660,53 @@ class PlanBuilder:
             full = np.zeros((out.C, G), np.float32)
             full[:cout] = np.asarray(pw_w, np.float32).reshape(cout, G)
             w3 = split3_bf16(full).reshape(3, out.C, G // 32, 32).transpose(2, 0, 1, 3)
-            op.flags |= L.OPF_SPLIT3
             op.slope_off = self.add_weight(np.concatenate([np.ascontiguousarray(w3).reshape(-1).view(np.float32),
                                                            pad_vec(pw_scale, c4), pad_vec(pw_bias, c4)]))
         else:
             op.slope_off = self.add_weight(np.concatenate([pack_conv_weight(pw_w, G, out.C), pad_vec(pw_scale, c4),
                                                            pad_vec(pw_bias, c4)]))
         if out_slope is not None:
-            assert res is None
             op.bias_off = self.add_weight(pad_vec(out_slope, c4))
-        if res is not None:
-            assert res.cmul == 1
-            op.res_mode = L.RES_SHUFFLE2 if shuffle else L.RES_ADD_AFTER_ACT
-            op.res_ld, op.res_ns = res.buf.ld, res.buf.ns
-            op.res_off = res.buf.off + res.coff
-            op.res_C = min(res.C, out.C)
-            op.res_H, op.res_W = res.H, res.W
         self.ops.append(op)
         opix = out.H * out.W
         self.alg_bytes.append(4 * self.N * (x.H * x.W * G + opix * G + opix * G + opix * cout))
         return out
 
-    # shapes csrc/dwblock.hip is instantiated for: (block width, map size); Cmid = 2 * width
-    DWBLOCK_SHAPES = ((128, 14), (128, 7), (64, 28))
-
-    @classmethod
-    def dwblock_supported(cls, x, cin, cmid, cout, stride):
-        """Mirror of fp_dwblock_supported (csrc/dwblock.hip): stride-1 Depth_Wise blocks on a dense square map."""
-        return (stride == 1 and cin == cout and cmid == 2 * cin and x.H == x.W and (cin, x.H) in cls.DWBLOCK_SHAPES and
-                x.coff == 0 and x.C == cin and x.buf.ld == cin and x.buf.ns == x.H * x.W * cin and not x.buf.rowpad)
-
-    # shapes csrc/dwblockx6.hip (bf16x6 split MFMA, OPF_SPLIT3) is instantiated for
-    DWBLOCK_X6_SHAPES = ((128, 14), (128, 7), (64, 28))
-    # ... and its stride-2 form (dwblock_x6d_kernel): (Cin, Cmid, Cout, input map size)
-    DWBLOCK_X6D_SHAPES = ((64, 256, 128, 28), (128, 512, 128, 14), (64, 128, 64, 56))
-
-    @classmethod
-    def dwblock_x6d_supported(cls, x, cin, cmid, cout, stride):
-        return (stride == 2 and x.H == x.W and (cin, cmid, cout, x.H) in cls.DWBLOCK_X6D_SHAPES and x.coff == 0 and x.C == cin and
-                x.buf.ld == cin and x.buf.ns == x.H * x.W * cin and not x.buf.rowpad)
-
-    def dwblock(self, x, e_w, e_aff, e_slope, dw_w, dw_aff, dw_slope, pw_w, pw_aff, out, residual, split=False, stride=1,
-                in_dw=None):
-        """A whole Depth_Wise block (mobile_facenet.py:67-88) as ONE op (FP_OP_DWBLOCK, csrc/dwblock.hip): 1x1 expand
-        + BN + PReLU -> dw3x3 (stride 1) + BN + PReLU -> 1x1 project + BN [+ x]; the expanded tensor stays in LDS.
-        *_aff = (scale, bias) of the eval-mode BatchNorm."""
+    def dwblock(self, x, e_w, e_aff, e_slope, dw_w, dw_aff, dw_slope, pw_w, pw_aff, out, residual, stride=1, in_dw=None,
+                fp32=True):
+        """A whole Depth_Wise block (mobile_facenet.py:67-88) as ONE op (FP_OP_DWBLOCK): 1x1 expand + BN + PReLU -> dw3x3
+        (stride) + BN + PReLU -> 1x1 project + BN [+ x]; the expanded tensor stays in LDS.  *_aff = (scale, bias) of the
+        eval-mode BatchNorm.  The split form (FP_OPF_SPLIT3, csrc/dwblockx6.hip) when X6 is on and the launcher takes it,
+        else the fp32 form (csrc/dwblock.hip) if the caller's policy allows it (`fp32`) and the launcher takes it, else None
+        (nothing emitted)."""
         cmid, cin = e_w.shape[0], e_w.shape[1]
         cout = pw_w.shape[0]
-        if stride == 1:
-            assert self.dwblock_supported(x, cin, cmid, cout, 1)
-        else:   # stride-2 blocks exist only in the split-MFMA form
-            assert split and not residual and self.dwblock_x6d_supported(x, cin, cmid, cout, stride)
-        assert dw_w.shape == (cmid, 1, 3, 3) and pw_w.shape[1] == cmid and (out.H, out.W) == (x.H // stride, x.W // stride)
-        assert out.coff == 0 and out.C == cout and out.buf.ld == cout and out.cmul == 1 and not out.buf.rowpad
-        op = self._base(L.OP_DWBLOCK, x, out, out.H, out.W)
-        op.Cout, op.Cmid = cout, cmid
-        op.KH = op.KW = 3
-        op.stride = stride
-        op.pad_t = op.pad_l = 1
-        op.act = L.ACT_PRELU
+        assert dw_w.shape == (cmid, 1, 3, 3) and pw_w.shape[1] == cmid
+        assert out.coff == 0 and out.C == cout
+
+        def make(flags):
+            op = self._base(L.OP_DWBLOCK, x, out, out.H, out.W)
+            op.flags |= flags
+            op.Cout, op.Cmid = cout, cmid
+            op.KH = op.KW = 3
+            op.stride = stride
+            op.pad_t = op.pad_l = 1
+            op.act = L.ACT_PRELU
+            self._offsets(op, True, True, in_dw is not None, True)
+            if residual:
+                op.res_mode = L.RES_ADD_AFTER_ACT
+                op.res_ld, op.res_ns, op.res_off = op.in_ld, op.in_ns, op.in_off
+                op.res_C, op.res_H, op.res_W = cin, x.H, x.W
+            return op
+
+        in_flag = L.OPF_IN_DW if in_dw is not None else 0
+        forms = ([L.OPF_SPLIT3] if self.X6 else []) + ([0] if fp32 else [])
+        split = next((f for f in forms if self.probe(make(f | in_flag)) is not None), None)
+        if split is None:
+            return None
+        op = make(split | in_flag)
         if split:
             # three bf16 planes per matrix, in the fragment order of dwblock_x6_kernel (include/facepath.h, DWBLOCK)
-            assert stride == 2 or (cin, x.H) in self.DWBLOCK_X6_SHAPES
-            op.flags |= L.OPF_SPLIT3
             R = cmid // 32
             e3 = split3_bf16(np.asarray(e_w, np.float32).reshape(cmid, cin))            # [3][g][k]
             e3 = e3.reshape(3, R, 32, cin // 32, 32).transpose(1, 0, 3, 2, 4)            # [R][3][ks][g'][k']
@@ -737,50 +721,29 @@ class PlanBuilder:
                 pad_vec(dw_aff[0], cmid), pad_vec(dw_aff[1], cmid), pad_vec(dw_slope, cmid)]
         op.scale_off = self.add_weight(np.concatenate(rows))
         op.slope_off = self.add_weight(np.concatenate([wp, pad_vec(pw_aff[0], cout), pad_vec(pw_aff[1], cout)]))
-        if residual:
-            op.res_mode = L.RES_ADD_AFTER_ACT
-            op.res_ld, op.res_ns, op.res_off = op.in_ld, op.in_ns, op.in_off
-            op.res_C, op.res_H, op.res_W = cin, x.H, x.W
-        self.ops.append(op)
         pix, opix = x.H * x.W, out.H * out.W
         extra = 0
         if in_dw is not None:
             # OPF_IN_DW: a depthwise 3x3 stride-1 Conv_block (weights [C,1,3,3], (scale, bias), PReLU slope) in front of the
             # block, computed in the kernel's prologue (conv2_dw + conv_23 of Mobile-FaceNet); parameters [12][Cin] at bias_off
             iw, iaff, islope = in_dw
-            assert split and stride == 2 and (cin, cmid, cout, x.H) == (64, 128, 64, 56) and iw.shape == (cin, 1, 3, 3)
-            op.flags |= L.OPF_IN_DW
+            assert iw.shape == (cin, 1, 3, 3)
             op.bias_off = self.add_weight(np.concatenate([pack_dw_weight(iw, cin), pad_vec(iaff[0], cin), pad_vec(iaff[1], cin),
                                                           pad_vec(islope, cin)]))
             extra = pix * 2 * cin
+        self.ops.append(op)
         # the three convs of the block (+ the depthwise conv in front), each input once + output once
         self.alg_bytes.append(4 * self.N * (extra + pix * (cin + cmid) + (pix + opix) * cmid + opix * (cmid + cout)))
         return out
-
-    # shapes csrc/shufdown.hip is instantiated for: (Cin, branch width)
-    SHUFDOWN_SHAPES = ((32, 64),)
-
-    @classmethod
-    def shufdown_supported(cls, x, out, cin, cb):
-        """Mirror of fp_shufdown_supported (csrc/shufdown.hip): a whole stride-2 ShuffleV2Block as one op."""
-        if not cls.X6 or (cin, cb) not in cls.SHUFDOWN_SHAPES or x.C != cin or out.C != 2 * cb or out.cmul != 1:
-            return False
-        if x.H % 2 or x.W % 2 or (out.H, out.W) != (x.H // 2, x.W // 2) or x.buf.rowpad or out.buf.rowpad:
-            return False
-        for v in (x, out):
-            if v.buf.ld % 4 or (v.buf.off + v.coff) % 4 or v.buf.ns % 4 or v.buf.ns < v.H * v.W * v.buf.ld:
-                return False
-        return True
 
     def shufdown(self, x, b1_dw, b1_dw_aff, b1_pw, b1_pw_aff, pw1, pw1_aff, dw2, dw2_aff, pw2, pw2_aff, out):
         """A whole stride-2 ShuffleV2Block (y5/models/common.py:127-176) as ONE op (FP_OP_SHUFDOWN, csrc/shufdown.hip):
         branch1 = dw3x3 s2 + BN -> 1x1 + BN + SiLU, branch2 = 1x1 + BN + SiLU -> dw3x3 s2 + BN -> 1x1 + BN + SiLU,
         out[2c] = branch1[c], out[2c + 1] = branch2[c].  *_aff = (scale, bias) of the eval-mode BatchNorm.  The parameter block's
-        layout is facepath.h "SHUFDOWN"."""
+        layout is facepath.h "SHUFDOWN".  None (nothing emitted) if X6 is off or the launcher refuses the op."""
         cin, cb = x.C, pw1.shape[0]
-        assert self.shufdown_supported(x, out, cin, cb)
         assert b1_dw.shape == (cin, 1, 3, 3) and b1_pw.shape[:2] == (cb, cin) and pw1.shape[:2] == (cb, cin)
-        assert dw2.shape == (cb, 1, 3, 3) and pw2.shape[:2] == (cb, cb)
+        assert dw2.shape == (cb, 1, 3, 3) and pw2.shape[:2] == (cb, cb) and out.C == 2 * cb
         op = self._base(L.OP_SHUFDOWN, x, out, out.H, out.W)
         op.Cout, op.Cmid = 2 * cb, cb
         op.KH = op.KW = 3
@@ -788,6 +751,9 @@ class PlanBuilder:
         op.pad_t = op.pad_l = 1
         op.act = op.act2 = L.ACT_SILU
         op.flags |= L.OPF_SPLIT3
+        self._offsets(op, True, False, False, False)
+        if not self.X6 or self.probe(op) is None:
+            return None
         ks, r = cin // 32, cb // 32
 
         def planes(a):
@@ -807,28 +773,13 @@ class PlanBuilder:
         self.alg_bytes.append(4 * self.N * ((pix + opix) * cin + opix * (cin + cb) + pix * (cin + cb) + (pix + opix) * cb + opix * 2 * cb))
         return out
 
-    # branch widths csrc/shufdown.hip's stride-1 kernel (shufunit_x6_kernel) is instantiated for
-    SHUFUNIT_WIDTHS = (64,)
-
-    @classmethod
-    def shufunit_supported(cls, x, out, cb):
-        """Mirror of fp_shufunit_supported (csrc/shufdown.hip): a whole stride-1 ShuffleV2Block as one op."""
-        if not cls.X6 or cb not in cls.SHUFUNIT_WIDTHS or x.C != 2 * cb or out.C != 2 * cb or out.cmul != 1 or x.buf is out.buf:
-            return False
-        if (out.H, out.W) != (x.H, x.W) or x.buf.rowpad or out.buf.rowpad:
-            return False
-        for v in (x, out):
-            if v.buf.ld % 4 or (v.buf.off + v.coff) % 4 or v.buf.ns % 4 or v.buf.ns < v.H * v.W * v.buf.ld:
-                return False
-        return True
-
     def shufunit(self, x, pw1, pw1_aff, dw2, dw2_aff, pw2, pw2_aff, out):
         """A whole stride-1 ShuffleV2Block (y5/models/common.py:127-176) as ONE op (FP_OP_SHUFUNIT, csrc/shufdown.hip):
         x1, x2 = x.chunk(2); branch2(x2) = 1x1 + BN + SiLU -> dw3x3 + BN -> 1x1 + BN + SiLU; out[2c] = x1[c], out[2c + 1] = branch2[c].
-        The parameter block's layout is facepath.h "SHUFUNIT"."""
+        The parameter block's layout is facepath.h "SHUFUNIT".  None (nothing emitted) if X6 is off or the launcher refuses
+        the op."""
         cb = pw1.shape[0]
-        assert self.shufunit_supported(x, out, cb)
-        assert pw1.shape[:2] == (cb, cb) and dw2.shape == (cb, 1, 3, 3) and pw2.shape[:2] == (cb, cb)
+        assert pw1.shape[:2] == (cb, cb) and dw2.shape == (cb, 1, 3, 3) and pw2.shape[:2] == (cb, cb) and out.C == 2 * cb
         op = self._base(L.OP_SHUFUNIT, x, out, out.H, out.W)
         op.Cout, op.Cmid = 2 * cb, cb
         op.KH = op.KW = 3
@@ -836,6 +787,9 @@ class PlanBuilder:
         op.pad_t = op.pad_l = 1
         op.act = op.act2 = L.ACT_SILU
         op.flags |= L.OPF_SPLIT3
+        self._offsets(op, True, False, False, False)
+        if not self.X6 or self.probe(op) is None:
+            return None
         ks = r = cb // 32
 
         def planes(a):
@@ -956,24 +910,13 @@ class PlanBuilder:
         self.alg_bytes.append(4 * self.N * (H * W * 3 + H1 * W1 * c1 + H1 * W1 * c1 + H1 * W1 * c2))
         return a_out
 
-    @classmethod
-    def ystem2_supported(cls, a, pool, out):
-        """Mirror of fp_ystem2_supported (csrc/ystem2.hip): stem_2b + cat + stem_3 of YOLOv5n-face's StemBlock (c = 32) as one op."""
-        if not cls.X6 or a.C != 16 or pool.C != 32 or out.C != 32 or out.cmul != 1 or a.H % 2 or a.W % 2:
-            return False
-        if (out.H, out.W) != (a.H // 2, a.W // 2) or (pool.H, pool.W) != (out.H, out.W):
-            return False
-        for v in (a, pool, out):
-            if v.buf.rowpad or v.buf.ld % 4 or (v.buf.off + v.coff) % 4 or v.buf.ns % 4 or v.buf.ns < v.H * v.W * v.buf.ld:
-                return False
-        return out.buf is not a.buf and out.buf is not pool.buf
-
     def ystem2(self, a, pool, w2b, aff2b, w3, aff3, out):
         """The tail of YOLOv5-face's StemBlock (y5/models/common.py:58-73) as ONE op (FP_OP_YSTEM2, csrc/ystem2.hip):
-        out = stem_3(cat(stem_2b(a), pool)), both convs + (BN) + SiLU.  *_aff = (scale or None, bias).  Layout: facepath.h "YSTEM2"."""
-        assert self.ystem2_supported(a, pool, out) and w2b.shape == (32, 16, 3, 3) and w3.shape[:2] == (32, 64)
+        out = stem_3(cat(stem_2b(a), pool)), both convs + (BN) + SiLU.  *_aff = (scale or None, bias).  Layout: facepath.h "YSTEM2".
+        None (nothing emitted) if X6 is off or the launcher refuses the op."""
+        assert w2b.shape == (32, 16, 3, 3) and w3.shape[:2] == (32, 64) and pool.cmul == 1
         op = self._base(L.OP_YSTEM2, a, out, out.H, out.W)
-        op.Cout = 32
+        op.Cout = out.C
         op.KH = op.KW = 3
         op.stride = 2
         op.pad_t = op.pad_l = 1
@@ -981,7 +924,10 @@ class PlanBuilder:
         op.flags |= L.OPF_SPLIT3
         op.res_ld, op.res_ns = pool.buf.ld, pool.buf.ns
         op.res_off = pool.buf.off + pool.coff
-        op.res_C, op.res_H, op.res_W = 32, pool.H, pool.W
+        op.res_C, op.res_H, op.res_W = pool.C, pool.H, pool.W
+        self._offsets(op, True, False, False, False)
+        if not self.X6 or self.probe(op) is None:
+            return None
 
         def planes(x):
             return np.ascontiguousarray(x).reshape(-1).view(np.float32)

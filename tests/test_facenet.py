@@ -203,9 +203,18 @@ def _window_op(cin, cout, kh, kw, pt, pl, stride, H, W):
     return pb, x, out, op
 
 
-def test_validator_and_mirror_agree(lib):
-    """fp_plan_validate (the launchers' eligibility, csrc/pwx6.hip) and PlanBuilder.pwx6_ok(policy=False) accept and refuse the
-    same split-MFMA convs over a grid of windows, paddings, strides and widths."""
+def test_conv_splits_exactly_where_the_launcher_takes_it(lib, monkeypatch):
+    """With x6_all, PlanBuilder.conv emits FP_OPF_SPLIT3 over a grid of windows, paddings, strides and widths exactly when
+    fp_plan_validate (the launchers' eligibility, csrc/pwx6.hip) accepts the split op, and the fp32 form otherwise.  The
+    weights are not packed here (their layouts are the parity tests' business): conv_weights is stubbed."""
+    monkeypatch.setattr(PlanBuilder, "conv_weights", classmethod(lambda cls, *a: np.zeros(4, np.float32)))
+
+    def emits_split(pb, x, out, cin, cout, kh, kw, stride, pad):
+        pb.x6_all = True
+        w = np.broadcast_to(np.float32(0), (cout, cin, kh, kw))
+        pb.conv(x, w, out, stride=stride, pad=pad, act=L.ACT_RELU)
+        return bool(pb.ops[-1].flags & L.OPF_SPLIT3)
+
     big = 1 << 40
     seen = {True: 0, False: 0}
     grid = itertools.product((32, 80, 128, 896), (32, 80, 96, 384), range(1, 9), range(1, 9), (1, 2), ((17, 17), (8, 8), (3, 3)))
@@ -219,8 +228,8 @@ def test_validator_and_mirror_agree(lib):
                     continue
                 pb, x, out, op = built
                 c_ok = lib.fp_plan_validate(ctypes.byref(op), 1, big, big) == 0
-                py_ok = PlanBuilder.pwx6_ok(x, out, kh, kw, stride, (pt, pl), None, L.RES_NONE, policy=False)
-                assert c_ok == py_ok, (cin, cout, kh, kw, pt, pl, stride, H, W, c_ok)
+                assert emits_split(pb, x, out, cin, cout, kh, kw, stride, (pt, pl)) == c_ok, \
+                    (cin, cout, kh, kw, pt, pl, stride, H, W, c_ok)
                 if pt >= kh or pl >= kw or kh > 7 or kw > 7:
                     assert not c_ok
                 seen[c_ok] += 1
@@ -232,7 +241,7 @@ def test_validator_and_mirror_agree(lib):
         op.Cin = op.in_ld = cin
         op.in_ns = 81 * cin
         assert lib.fp_plan_validate(ctypes.byref(op), 1, big, big) != 0
-        assert not PlanBuilder.pwx6_ok(x, out, kh, kw, 1, (0, 0), None, L.RES_NONE, policy=False)
+        assert not emits_split(pb, x, out, cin, 64, kh, kw, 1, (0, 0))
 
 
 def test_embed_head_validation(lib):

@@ -401,10 +401,10 @@ def test_blazechain_run_of_blocks_in_one_kernel_vs_oracle(dev, nblk, n):
         pb = PlanBuilder(n)
         inp = pb.new_buf(16, 16, 96)
         if chain:
-            assert pb.blazechain_supported(inp.view()) and all(b.chains() for b in blks)
+            assert all(b.chains() for b in blks)
             y = pb.new_buf(16, 16, 96)
-            pb.blazechain(inp.view(), [(npy(b.convs[0].weight), npy(b.convs[0].bias), npy(b.convs[1].weight), npy(b.convs[1].bias))
-                                       for b in blks], y.view())
+            assert pb.blazechain(inp.view(), [(npy(b.convs[0].weight), npy(b.convs[0].bias), npy(b.convs[1].weight),
+                                               npy(b.convs[1].bias)) for b in blks], y.view()) is not None
         else:
             y = inp
             for b in blks:

@@ -156,7 +156,8 @@ def test_shufflev2_block_ops_validation(lib):
             assert rc_with(stride=2) in (-3, -1)
         else:
             assert rc_with(H=23) in (-3, -1) and rc_with(stride=1) in (-3, -1)
-    # the stem's tail (FP_OP_YSTEM2): emitted behind FP_OP_YSTEM for c = 32, refused for other shapes / a missing pooled view
+    # the stem's tail (FP_OP_YSTEM2): emitted behind FP_OP_YSTEM for c = 32, refused for other shapes / a missing pooled view /
+    # an output that aliases either input
     stem = Y.StemBlock(3, 32, 3, 2)
     pb = PlanBuilder(2)
     stem.emit(pb, pb.new_buf(48, 64, 4).view())
@@ -170,6 +171,7 @@ def test_shufflev2_block_ops_validation(lib):
         return lib.fp_plan_validate((L.FpOp * 1)(op), 1, len(weights), arena)
     assert rc2() == 0 and rc2(res_C=16) == -3 and rc2(Cout=48) in (-3, -2, -1) and rc2(flags=0) == -3 and rc2(res_H=5) == -3
     assert rc2(w_off=len(weights) - 64) == -2 and rc2(res_off=arena - 64) == -2
+    assert rc2(out_off=pb.ops[1].in_off) == -3 and rc2(out_off=pb.ops[1].res_off) == -3   # an output that aliases an input
     for c in (24, 16):                                                   # other widths keep the two convs
         pb = PlanBuilder(2)
         Y.StemBlock(3, c, 3, 2).emit(pb, pb.new_buf(48, 64, 4).view())

@@ -1,9 +1,11 @@
 """The plans of the existing networks do not move (CPU).
 
 tests/golden/plan_digests.json holds, for BlazeFace front / back (fp32 canvas and u8 frames), YOLOv5n / s / n-0.5 (fp32 canvas
-and u8 frames) and Mobile-FaceNet at three batch sizes with the split-MFMA kernels on and off, a SHA-256 over every field of
-every fp_op the network emits plus the kernel family fp_op_kernel_name reports for it.  It was recorded before the split conv
-kernel learnt rectangular windows (csrc/pwx6.hip), so any change of op, field or kernel choice in those networks fails here.
+and u8 frames) Mobile-FaceNet and FaceNet (128-d and 512-d heads) at three batch sizes with the split-MFMA kernels on and off, a SHA-256
+over every field of every fp_op the network emits plus the kernel family fp_op_kernel_name reports for it, a SHA-256 of the
+packed weight blob and the arena size (floats) builder.finish() returns.  The op digests were recorded before the split conv
+kernel learnt rectangular windows (csrc/pwx6.hip), so any change of op, field, kernel choice, weight packing or arena layout
+in those networks fails here.
 
 Regenerate (only when a plan change is intended): python tests/test_plan_digests.py --write
 """
@@ -27,6 +29,7 @@ FRAME_HW = (576, 1024)
 def _networks():
     import torch
     from face_detection_and_recognition_amd.modules.blazeface.blazeface import BlazeFace
+    from face_detection_and_recognition_amd.modules.facenet.inception_resnet_v1 import InceptionResnetV1
     from face_detection_and_recognition_amd.modules.mobile_facenet.mobile_facenet import MobileFaceNet
     from face_detection_and_recognition_amd.modules.yolov5_face.yolo import Model
 
@@ -43,20 +46,24 @@ def _networks():
         nets[cfg + "_u8"] = lambda n, net=net: net._emit(n, 640, 640, frame_hw=FRAME_HW)[0]
     mfn = MobileFaceNet(512)
     nets["mobile_facenet"] = lambda n: mfn._emit(n)[0]
+    for d in (128, 512):
+        fn = InceptionResnetV1(d)
+        nets[f"facenet{d}"] = lambda n, fn=fn: fn._emit(n)[0]
     return nets
 
 
 def plan_digest(builder):
-    """(number of ops, SHA-256 over every fp_op field and the kernel name of every op)"""
+    """{n_ops, sha256 over every fp_op field and the kernel name of every op, weights_sha256, arena_floats}"""
     from face_detection_and_recognition_amd import _lib as L
     lib = L.load()
-    ops, _, _ = builder.finish()
+    ops, weights, arena_floats = builder.finish()
     h = hashlib.sha256()
     for op in ops:
         fields = [str(getattr(op, f)) for f, _ in L.FpOp._fields_]
         name = lib.fp_op_kernel_name(ctypes.byref(op)).decode()
         h.update((",".join(fields) + "|" + name + "\n").encode())
-    return len(ops), h.hexdigest()
+    return {"n_ops": len(ops), "sha256": h.hexdigest(), "weights_sha256": hashlib.sha256(weights.tobytes()).hexdigest(),
+            "arena_floats": int(arena_floats)}
 
 
 def compute_digests():
@@ -68,8 +75,7 @@ def compute_digests():
             for n in BATCHES:
                 for x6 in (True, False):
                     PlanBuilder.X6 = x6
-                    n_ops, digest = plan_digest(emit(n))
-                    out[f"{name}/N={n}/X6={int(x6)}"] = {"n_ops": n_ops, "sha256": digest}
+                    out[f"{name}/N={n}/X6={int(x6)}"] = plan_digest(emit(n))
     finally:
         PlanBuilder.X6 = saved
     return out

@@ -11,12 +11,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfacepath.so")
 
 FP_OK = 0
+FP_ERR_INVALID_ARG = -1
 ABI_VERSION = 14
 
 # fp_op_kind
 OP_CONV, OP_DWCONV, OP_MAXPOOL, OP_UPSAMPLE2X, OP_COPY, OP_L2NORM, OP_BLAZEBLOCK, OP_DWPW, OP_YSTEM = 1, 2, 3, 4, 5, 6, 7, 8, 9
 OP_YSTEM_U8, OP_STEM_U8, OP_DWBLOCK, OP_BLAZEPAIR, OP_BLAZECHAIN, OP_SHUFDOWN, OP_SHUFUNIT, OP_YSTEM2 = 10, 11, 12, 13, 14, 15, 16, 17
 OP_EMBED_HEAD = 18
+OP_POOL_LRN, OP_CLS_HEAD = 19, 20
 # fp_act
 ACT_NONE, ACT_RELU, ACT_PRELU, ACT_SILU = 0, 1, 2, 3
 # fp_res_mode
@@ -172,6 +174,8 @@ SIGNATURES = {
     "fp_jpeg_encode_headers": (_I, [_I, _I, _I, _I, _P, _SZ]),
     "fp_jpeg_encode_device": (_I, [_P, C.POINTER(FpJpegEncItem), _I, _I, _I, _I, _P, _SZ, _P, _SZ, _P, _P]),
     "fp_jpeg_encode_emulate": (_I, [_P, C.POINTER(FpJpegEncItem), _I, _I, _I, _I, _P, _SZ, C.POINTER(_I64)]),
+    "fp_attr_crop_items": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "fp_attr_crop_items_emulate": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     "fp_tracker_step": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _F, _F, _P, _P, _P]),
 }
 

@@ -54,6 +54,8 @@ static int launch_op(const fp_op& op, const fp_launch& L) {
     case FP_OP_YSTEM_U8: return fp_launch_ystem_u8(op, L);
     case FP_OP_STEM_U8: return fp_launch_stem_u8(op, L);
     case FP_OP_EMBED_HEAD: return fp_launch_embed_head(op, L);
+    case FP_OP_POOL_LRN: return fp_launch_pool_lrn(op, L);
+    case FP_OP_CLS_HEAD: return fp_launch_cls_head(op, L);
     default: return FP_ERR_UNSUPPORTED;
   }
 }
@@ -131,8 +133,11 @@ static int validate_op(const fp_op& op, size_t weight_floats, size_t arena_float
   const int Cout = (op.kind == FP_OP_CONV || op.kind == FP_OP_BLAZEBLOCK || op.kind == FP_OP_DWPW ||
                     op.kind == FP_OP_DWBLOCK || op.kind == FP_OP_BLAZEPAIR || op.kind == FP_OP_BLAZECHAIN || op.kind == FP_OP_YSTEM ||
                     op.kind == FP_OP_SHUFDOWN || op.kind == FP_OP_SHUFUNIT || op.kind == FP_OP_YSTEM2 || op.kind == FP_OP_EMBED_HEAD ||
-                    ext_in) ? op.Cout : op.Cin;
-  if (op.kind != FP_OP_DWBLOCK && op.kind != FP_OP_BLAZECHAIN && op.kind != FP_OP_SHUFDOWN && op.kind != FP_OP_SHUFUNIT && op.Cmid != 0) return FP_ERR_INVALID_ARG;
+                    op.kind == FP_OP_CLS_HEAD || ext_in) ? op.Cout : op.Cin;
+  if (op.kind != FP_OP_DWBLOCK && op.kind != FP_OP_BLAZECHAIN && op.kind != FP_OP_SHUFDOWN && op.kind != FP_OP_SHUFUNIT &&
+      op.kind != FP_OP_POOL_LRN && op.Cmid != 0)
+    return FP_ERR_INVALID_ARG;
+  if (op.kind == FP_OP_POOL_LRN && op.Cout != op.Cin) return FP_ERR_INVALID_ARG;
   if (op.row_lo != 0 || op.row_end != 0) {
     // a row window (facepath.h "Row windows"): only the kernels that take one (of the u8 stems, the launcher refuses it
     // outside the band kernel), never empty, inside the output map
@@ -171,7 +176,8 @@ static int validate_op(const fp_op& op, size_t weight_floats, size_t arena_float
   if (out_rp && (op.out_cmul != 1 || op.out_ld != Cout)) return FP_ERR_UNSUPPORTED;
   if (op.kind == FP_OP_CONV || op.kind == FP_OP_DWCONV || op.kind == FP_OP_MAXPOOL || op.kind == FP_OP_BLAZEBLOCK ||
       op.kind == FP_OP_DWPW || op.kind == FP_OP_DWBLOCK || op.kind == FP_OP_BLAZEPAIR || op.kind == FP_OP_BLAZECHAIN ||
-      op.kind == FP_OP_YSTEM || op.kind == FP_OP_SHUFDOWN || op.kind == FP_OP_SHUFUNIT || op.kind == FP_OP_YSTEM2 || ext_in) {
+      op.kind == FP_OP_YSTEM || op.kind == FP_OP_SHUFDOWN || op.kind == FP_OP_SHUFUNIT || op.kind == FP_OP_YSTEM2 ||
+      op.kind == FP_OP_POOL_LRN || ext_in) {
     if (op.KH <= 0 || op.KW <= 0 || op.stride <= 0 || op.pad_t < 0 || op.pad_l < 0) return FP_ERR_INVALID_ARG;
     // every output pixel must have at least its first tap row/col addressable without overflow of int math
     if ((int64_t)(OH - 1) * op.stride - op.pad_t >= op.H || (int64_t)(OW - 1) * op.stride - op.pad_l >= op.W)
@@ -297,6 +303,16 @@ static int validate_op(const fp_op& op, size_t weight_floats, size_t arena_float
     if (!span_ok(op.w_off, (int64_t)op.Cout * op.Cin, weight_floats)) return FP_ERR_BOUNDS;
     if (op.scale_off >= 0 && !span_ok(op.scale_off, Cout, weight_floats)) return FP_ERR_BOUNDS;
     if (op.bias_off >= 0 && !span_ok(op.bias_off, Cout, weight_floats)) return FP_ERR_BOUNDS;
+  }
+  if (op.kind == FP_OP_POOL_LRN && op.Cmid) {
+    // [alpha, beta, k, unused] (facepath.h POOL_LRN)
+    if (!span_ok(op.w_off, 4, weight_floats)) return FP_ERR_BOUNDS;
+  }
+  if (op.kind == FP_OP_CLS_HEAD) {
+    // [Cout][Cin] weight, optional [Cout] bias, optional logits view at res_off (facepath.h CLS_HEAD)
+    if (!span_ok(op.w_off, (int64_t)op.Cout * op.Cin, weight_floats)) return FP_ERR_BOUNDS;
+    if (op.bias_off >= 0 && !span_ok(op.bias_off, Cout, weight_floats)) return FP_ERR_BOUNDS;
+    if (op.res_off >= 0 && !span_ok(op.res_off, (int64_t)(op.N - 1) * op.res_ns + Cout, arena_floats)) return FP_ERR_BOUNDS;
   }
   if ((op.kind == FP_OP_CONV || op.kind == FP_OP_BLAZEBLOCK || op.kind == FP_OP_DWPW || op.kind == FP_OP_DWBLOCK) &&
       op.res_mode != FP_RES_NONE) {

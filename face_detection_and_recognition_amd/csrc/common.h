@@ -131,6 +131,8 @@ int fp_launch_upsample2x(const fp_op& op, const fp_launch& L);
 int fp_launch_copy(const fp_op& op, const fp_launch& L);
 int fp_launch_l2norm(const fp_op& op, const fp_launch& L);
 int fp_launch_embed_head(const fp_op& op, const fp_launch& L);   // embedhead.hip
+int fp_launch_pool_lrn(const fp_op& op, const fp_launch& L);     // lrn.hip
+int fp_launch_cls_head(const fp_op& op, const fp_launch& L);     // clshead.hip
 int fp_launch_blazeblock(const fp_op& op, const fp_launch& L);
 int fp_launch_blazeblock_rowpad(const fp_op& op, const fp_launch& L);   // blazewp.hip
 int fp_launch_dwpw(const fp_op& op, const fp_launch& L);

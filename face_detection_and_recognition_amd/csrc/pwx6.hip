@@ -278,10 +278,11 @@ int launch(const PwX6Args& a, bool up, const fp_launch& L) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// convx6_kernel: the same scheme for dense KH x KW convs (KH, KW in 1..7, padding below the window size, stride 1 / 2):
+// convx6_kernel: the same scheme for dense KH x KW convs (KH, KW in 1..7, padding below the window size, stride 1 / 2 / 4):
 // YOLOv5-face's Bottleneck.cv2 and downsampling Convs (3x3 pad 1, y5/models/common.py:35-56,76-88), pointwise convs whose widths
 // are not multiples of 32 / 16 (the in-tree yolov5s widths 92, 184, 360), and Inception-ResNet-v1's unpadded 3x3 and 1x7 / 7x1 /
-// 1x3 / 3x1 windows.  Rows are OUTPUT pixels, flattened over the images; the K loop runs over (tap, 32-channel slab) with
+// 1x3 / 3x1 windows, and Levi-Hassner's conv1 (7x7 stride 4 on the 4-float-pixel image, flat), 5x5 / 3x3 pad 2 / 1 and fc6 (a 7x7
+// valid window on the 7x7 map: 1 x 1 outputs, one row per image).  Rows are OUTPUT pixels, flattened over the images; the K loop runs over (tap, 32-channel slab) with
 // tap = dy * KW + dx; a lane's A fragment for a slab is 8 consecutive channels of input pixel (oy*s + dy - pad_t, ox*s + dx -
 // pad_l) -- two 16-byte loads straight from global memory (the taps of a pixel hit L1 / L2), zero outside the image or beyond
 // Cin -- split in registers as above.  Weight slabs [tap * CS + cs][3][Npad][32] with zero rows / columns in the padding;
@@ -354,9 +355,9 @@ __global__ __launch_bounds__(256, 2) void convx6_kernel(ConvX6Args p) {
   for (int t = 0; t < MT; ++t) {
     long r = row0 + 16 * t + l15;
     r = r < p.M ? r : p.M - 1;
-    const unsigned n = fp_fastdiv((unsigned)r, p.div_ohw);
+    const unsigned n = p.OH * p.OW == 1 ? (unsigned)r : fp_fastdiv((unsigned)r, p.div_ohw);   // 1 x 1 maps: a row per image
     const unsigned rem = (unsigned)r - n * (unsigned)(p.OH * p.OW);
-    const unsigned oy = fp_fastdiv(rem, p.div_ow), ox = rem - oy * p.OW;
+    const unsigned oy = p.OW == 1 ? rem : fp_fastdiv(rem, p.div_ow), ox = rem - oy * p.OW;
     nimg[t] = (int)n;
     iyx[t] = (((int)oy * p.stride - p.pad_t) << 16) | (((int)ox * p.stride - p.pad_l) & 0xffff);
   }
@@ -577,11 +578,11 @@ int fp_launch_pwx6(const fp_op& op, const fp_launch& L) {
 }
 
 // The general form (convx6_kernel): KH x KW windows, KH and KW in 1..7, 0 <= pad_t < KH and 0 <= pad_l < KW on both sides of the
-// map, stride 1 / 2 -- or pointwise with widths that pwx6_kernel does not take.
+// map, stride 1 / 2 / 4 -- or pointwise with widths that pwx6_kernel does not take.
 static bool convx6_shape(const fp_op& op) {
   if (op.KH < 1 || op.KH > 7 || op.KW < 1 || op.KW > 7 || op.pad_t < 0 || op.pad_t >= op.KH || op.pad_l < 0 || op.pad_l >= op.KW)
     return false;
-  if ((op.stride != 1 && op.stride != 2) || op.H + 2 * op.pad_t < op.KH || op.W + 2 * op.pad_l < op.KW) return false;
+  if ((op.stride != 1 && op.stride != 2 && op.stride != 4) || op.H + 2 * op.pad_t < op.KH || op.W + 2 * op.pad_l < op.KW) return false;
   return op.OH == (op.H + 2 * op.pad_t - op.KH) / op.stride + 1 && op.OW == (op.W + 2 * op.pad_l - op.KW) / op.stride + 1;
 }
 
@@ -594,8 +595,9 @@ static bool convx6_eligible(const fp_op& op) {
     if (op.res_ld % 4 || op.res_off % 4 || op.res_ns % 4 || op.res_ld < op.res_C || op.res_ns < (long)op.res_H * op.res_W * op.res_ld)
       return false;
   }
-  // Cin >= 32, or a multiple of 4 below 32 under a 3x3 (K flattened over taps and channels); FP_OPF_IN_C3 only there, on 4 channels
-  const bool flat = op.Cin < 32 && op.KH == 3 && op.KW == 3 && op.Cin % 4 == 0 && !(op.flags & FP_OPF_IN_UP2);
+  // Cin >= 32, or a multiple of 4 below 32 under a 3x3 or a stride-4 window (K flattened over taps and channels); FP_OPF_IN_C3 only
+  // there, on 4 channels
+  const bool flat = op.Cin < 32 && ((op.KH == 3 && op.KW == 3) || op.stride == 4) && op.Cin % 4 == 0 && !(op.flags & FP_OPF_IN_UP2);
   if ((op.flags & FP_OPF_IN_C3) && (!flat || op.Cin != 4)) return false;
   if (!convx6_shape(op) || op.Cin % 4 || (op.Cin < 32 && !flat) || op.Cout % 4 || op.Cout < 32 || op.out_cmul != 1) return false;
   const long OHW = (long)op.OH * op.OW;
@@ -608,7 +610,8 @@ static bool convx6_eligible(const fp_op& op) {
     if (op.res_ns != OHW * op.res_ld || op.res_ld % 4 || op.res_off % 4 || op.res_C % 4) return false;
     if (op.res_mode == FP_RES_SHUFFLE2 && (op.res_C < op.Cout || op.out_ld < 2 * op.Cout)) return false;
   }
-  if ((long)op.N * OHW >= (1L << 31) || OHW < 2 || op.OW < 2) return false;   // 32-bit row decode by multiply-high (divisors >= 2)
+  // 32-bit row decode by multiply-high (divisors >= 2; a 1 x 1 map or a single column skips that division)
+  if ((long)op.N * OHW >= (1L << 31)) return false;
   return true;
 }
 
@@ -638,8 +641,8 @@ int fp_launch_convx6(const fp_op& op, const fp_launch& L) {
   a.kw_rcp = (65536 + op.KW - 1) / op.KW;
   a.in_ld = op.in_ld; a.out_ld = op.out_ld; a.res_ld = op.res_ld; a.res_C = op.res_C; a.act = op.act; a.res_mode = op.res_mode;
   a.in_ns = op.in_ns;
-  a.div_ohw = fp_make_divisor((unsigned)(op.OH * op.OW));
-  a.div_ow = fp_make_divisor((unsigned)op.OW);
+  a.div_ohw = fp_make_divisor((unsigned)(op.OH * op.OW >= 2 ? op.OH * op.OW : 2));
+  a.div_ow = fp_make_divisor((unsigned)(op.OW >= 2 ? op.OW : 2));
   a.flat = op.Cin < 32;
   a.c3 = (op.flags & FP_OPF_IN_C3) != 0;
   a.div_cin = fp_make_divisor((unsigned)(op.Cin >= 2 ? op.Cin : 2));

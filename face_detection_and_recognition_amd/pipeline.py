@@ -14,6 +14,7 @@ from . import _lib as L
 from . import similarity as S
 from .frames import RaggedFrames
 from .modules.mobile_facenet.utils import crops_to_input
+from .modules.age_gender import age_gender_net as AG
 from .modules.utils import align as A
 from .modules.utils.image import letterbox_geometry
 
@@ -40,7 +41,10 @@ class FacePipeline:
     the crops are resized to its ``input_size``, in its channel order (``swap_rb``), through its ``input_lut``;
     reference: (Nr, E) CUDA tensor of reference embeddings for the cosine filter (or None).
     align: feed the embedder each face warped onto the five-point template (modules/utils/align.py) instead of its
-    stretched box crop; step results then also carry lmarks, align_M and align_flags."""
+    stretched box crop; step results then also carry lmarks, align_M and align_flags.
+    attributes: an AgeGenderNet (modules/age_gender): step results then also carry age_probs (n, 8) and gender_probs (n, 2),
+    one row per face in the order of emb, from the reference's age / gender crops (fp_attr_crop_items); a face whose crop
+    is empty gets NaN rows.  Under two_streams they run on the embedder's side stream."""
 
     # embed(): a batch a little above a multiple of ROUND_CROPS crops is run as that multiple + the remainder on a side stream
     ROUND_CROPS = 512     # crops whose tiles fill whole rounds of workgroups in every Depth_Wise kernel (2 / 4 / 7 tiles per crop, 512 slots)
@@ -48,8 +52,9 @@ class FacePipeline:
     TAIL_CAP = 128        # capacity of the remainder's plan
 
     def __init__(self, detector, embedder, reference=None, tau=0.3, max_faces_per_frame=8, bucket=8, two_streams=False,
-                 split_tail=True, align=False):
+                 split_tail=True, align=False, attributes=None):
         self.det = detector
+        self.attr = attributes
         self.align = bool(align)
         self.emb = embedder
         self.tau = float(tau)
@@ -251,6 +256,7 @@ class FacePipeline:
             emb = self.embed(frames, items, n, al, info)
             res = self.filter(emb)
             out = dict(n_faces=n, info=info[:n], emb=emb.clone(), items=items[:n])
+            self._add_attributes(out, frames, info, n)
         else:
             main = torch.cuda.current_stream(self.dev)
             self.emb_stream.wait_event(ev)                 # the crops of this batch (detector stream)
@@ -262,9 +268,11 @@ class FacePipeline:
                 emb = self.embed(frames, items, n, al, info)
                 res = self.filter(emb)
                 out = dict(n_faces=n, info=info[:n], emb=emb.clone(), items=items[:n])
+                self._add_attributes(out, frames, info, n)
                 # allocated on the side stream, consumed by the caller on the main stream (after `done`): tell the caching
                 # allocator, or it hands the blocks to the next embed / filter while main-stream reads are still queued
-                for t in (out["emb"],) + (tuple(res) if res is not None else ()):
+                attrs = tuple(out[k] for k in ("age_probs", "gender_probs") if k in out)
+                for t in (out["emb"],) + attrs + (tuple(res) if res is not None else ()):
                     t.record_stream(main)
                 self._emb_done = torch.cuda.Event()
                 self._emb_done.record(self.emb_stream)
@@ -273,6 +281,25 @@ class FacePipeline:
         if res is not None:
             out.update(best=res[0], arg=res[1], keep=res[2])
         return out
+
+    ATTR_CAP_STEP = 64    # the attribute plan's capacity grows in steps of this many crops (about 3.8 MB of arena each)
+
+    def attributes_of(self, frames, info, n):
+        """(age_probs (n, 8), gender_probs (n, 2)) of the first n face rows of info: the reference's age / gender crops, both
+        nets in one plan run on the first n rounded up to `bucket` crops.  New tensors; NaN rows for empty crops."""
+        net = self.attr
+        if n == 0:
+            return (torch.zeros((0, net.n_age), device=self.dev), torch.zeros((0, net.n_gender), device=self.dev))
+        items = AG.attr_crop_items(info, n, frames, dst=net.input_size)
+        n_pad = (n + self.bucket - 1) // self.bucket * self.bucket
+        cap = max(getattr(self, "_attr_cap", 0), (n_pad + self.ATTR_CAP_STEP - 1) // self.ATTR_CAP_STEP * self.ATTR_CAP_STEP)
+        self._attr_cap = cap
+        age, gender = AG.run_on_items(net, frames, items, n, n_pad, net.plan_for(cap))
+        return AG.nan_empty(age, items), AG.nan_empty(gender, items)
+
+    def _add_attributes(self, out, frames, info, n):
+        if self.attr is not None:
+            out["age_probs"], out["gender_probs"] = self.attributes_of(frames, info, n)
 
     @staticmethod
     def _add_align(out, al, n):
@@ -307,6 +334,7 @@ class FacePipeline:
         emb = self.embed(frames, items, n, al, info)
         res = self.filter(emb)
         out = dict(n_faces=n, info=info[:n], emb=emb.clone(), items=items[:n])
+        self._add_attributes(out, frames, info, n)
         self._add_align(out, al, n)
         if res is not None:
             out.update(best=res[0], arg=res[1], keep=res[2])

@@ -998,6 +998,43 @@ class PlanBuilder:
         self.alg_bytes.append(4 * self.N * (x.H * x.W * c + d))
         return out
 
+    def pool_lrn(self, x, out, k, stride, pad=0, group=0, size=5, alpha=1e-4, beta=0.75, lrn_k=1.0):
+        """k x k max pool (-inf padding; out.H / out.W as the caller computed them, Caffe's ceil mode included) followed by
+        Caffe's cross-channel LRN within groups of `group` channels (0: no LRN) as ONE op (FP_OP_POOL_LRN, csrc/lrn.hip)."""
+        assert out.C == x.C and out.cmul == 1 and x.up is None
+        op = self._base(L.OP_POOL_LRN, x, out, out.H, out.W)
+        op.Cout = x.C
+        op.KH = op.KW = k
+        op.stride = stride
+        op.pad_t = op.pad_l = pad
+        if group:
+            op.Cmid, op.res_C = group, size
+            op.w_off = self.add_weight(np.array([alpha, beta, lrn_k, 0.0], np.float32))
+        self.ops.append(op)
+        self.alg_bytes.append(0)
+        return out
+
+    def cls_head(self, x, w, bias, out, logits=None):
+        """Linear (w: [D, C], + bias) -> softmax on the row at pixel 0 of every image of x as ONE op (FP_OP_CLS_HEAD,
+        csrc/clshead.hip).  out: a View of a 1 x 1 buffer (D channels) for the probabilities; logits: one for the logits."""
+        d, c = w.shape
+        assert c <= x.C and out.C >= d and (out.H, out.W) == (1, 1) and out.cmul == 1 and x.up is None
+        op = self._base(L.OP_CLS_HEAD, x, out, 1, 1)
+        op.H = op.W = 1
+        op.Cout = d
+        wp = np.zeros((d, x.C), np.float32)
+        wp[:, :c] = np.asarray(w, np.float32)
+        op.w_off = self.add_weight(wp)
+        if bias is not None:
+            op.bias_off = self.add_weight(pad_vec(bias, d))
+        op.res_off = -1
+        if logits is not None:
+            assert logits.cmul == 1 and logits.C >= d
+            op.res_off, op.res_ns, op.res_ld = logits.buf.off + logits.coff, logits.buf.ns, logits.buf.ld
+        self.ops.append(op)
+        self.alg_bytes.append(4 * self.N * (c + d))
+        return out
+
     def finish(self):
         if not self._placed:   # the row-padded region goes behind the recycled arena: relocate its views once
             self._placed = True
@@ -1264,7 +1301,7 @@ class CompiledPlan:
             f = opix * (2 * op.Cmid * op.Cmid + 9 * op.Cmid)
         elif k == L.OP_YSTEM2:
             f = opix * (9 * op.Cin * op.Cout + 2 * op.Cout * op.Cout)
-        elif k == L.OP_EMBED_HEAD:  # the Linear (the mean and the affine are epilogue-class)
+        elif k in (L.OP_EMBED_HEAD, L.OP_CLS_HEAD):  # the Linear (the mean, the affine, the softmax are epilogue-class)
             f = op.Cin * op.Cout
         elif k == L.OP_SHUFDOWN:   # branch1: dw + 1x1; branch2: 1x1 at full resolution, dw, 1x1
             f = opix * (9 * op.Cin + op.Cin * op.Cmid) + op.H * op.W * op.Cin * op.Cmid + opix * (9 * op.Cmid + op.Cmid * op.Cmid)

@@ -69,3 +69,22 @@ def synth_frames(n, h, w, seed, blur=8):
     fine = rng.integers(0, 64, size=(n, h, w, 3), dtype=np.uint8).astype(np.float32)
     out = 0.6 * sm + fine
     return np.clip(out, 0, 255).astype(np.uint8)
+
+
+def synth_age_gender(net, seed):
+    """Seeded weights for an AgeGenderNet (modules/age_gender), in place; returns net.  Every conv / fc weight is
+    N(0, 2 / fan_in) (He: the crops' pixel scale, tens after the mean, carries through the ReLUs, so each LRN divides by
+    (1 + alpha / 5 * sum x^2)^0.75 of about 1.2 - 2 rather than ~1), biases N(0, 0.05), and fc8 N(0, 0.002^2) so that the
+    logits are O(1) and the softmax is not saturated.  The age and the gender net draw different streams."""
+    rng = np.random.default_rng(seed)
+    with torch.no_grad():
+        for sub in (net.age, net.gender):
+            for name in ("conv1", "conv2", "conv3", "fc6", "fc7", "fc8"):
+                p = getattr(sub, name)
+                shape = tuple(p.weight.shape)
+                fan_in = int(np.prod(shape[1:]))
+                std = 0.002 if name == "fc8" else np.sqrt(2.0 / fan_in)
+                p.weight.copy_(torch.from_numpy(rng.normal(0.0, std, shape).astype(np.float32)))
+                p.bias.copy_(torch.from_numpy(rng.normal(0.0, 0.05, tuple(p.bias.shape)).astype(np.float32)))
+    net._plans.clear()
+    return net

@@ -91,9 +91,13 @@ enum fp_op_kind {
   FP_OP_SHUFDOWN = 15,  /* ABI 10.  a WHOLE stride-2 ShuffleV2Block (y5/models/common.py:127-176) in one kernel: branch1 = dw3x3 s2 + BN
                            -> 1x1 + BN + SiLU, branch2 = 1x1 + BN + SiLU -> dw3x3 s2 + BN -> 1x1 + BN + SiLU, cat + channel_shuffle(2)
                            as the store pattern; nothing but x and the shuffled output touches HBM.  See "SHUFDOWN" */
-  FP_OP_EMBED_HEAD = 18 /* (appended at ABI 14) an embedding head in one kernel: mean over the H x W pixels of each image -> Linear Cin -> Cout
+  FP_OP_EMBED_HEAD = 18, /* (appended at ABI 14) an embedding head in one kernel: mean over the H x W pixels of each image -> Linear Cin -> Cout
                            (no bias) -> per-channel affine (BatchNorm1d) -> with FP_OPF_OUT_L2, x / max(||x||_2, 1e-12) (F.normalize).
                            Inception-ResNet-v1's avgpool_1a + last_linear + last_bn (+ normalize).  See "EMBED_HEAD" */
+  FP_OP_POOL_LRN = 19,  /* (appended at ABI 14) max pool (-inf padding, OH/OW given: covers Caffe's ceil mode) followed by Caffe's
+                           cross-channel LRN within channel groups: Levi-Hassner's pool1 + norm1, pool2 + norm2.  See "POOL_LRN" */
+  FP_OP_CLS_HEAD = 20   /* (appended at ABI 14) classifier head: Linear Cin -> Cout (+ bias) on every row, then softmax over the Cout
+                           logits (Levi-Hassner's fc8 + prob).  See "CLS_HEAD" */
 };
 
 enum fp_act { FP_ACT_NONE = 0, FP_ACT_RELU = 1, FP_ACT_PRELU = 2, FP_ACT_SILU = 3 };
@@ -317,6 +321,20 @@ typedef struct fp_op {
  *            (row-major, torch's [out, in]); scale_off / bias_off -> [Cout] affine (-1: 1 / 0); flags: FP_OPF_OUT_L2 or 0.
  *            fp32 arithmetic: the mean sums the pixels in order and divides by H * W; each image's result does not depend on the
  *            batch.  Cin <= 2048, Cout <= 1024.
+ *   POOL_LRN : in = an NHWC map, out = OH x OW x Cin (Cout = Cin), KH x KW max pool (KH, KW in 1 .. 7), stride, pad_t /
+ *            pad_l, -inf outside the map (OH / OW as the caller computed them, Caffe's ceil mode included), then Caffe's / OpenCV's
+ *            LRN ACROSS_CHANNELS on the pooled values: y_c = x_c * (k + alpha / n * sum_{|j - c| <= n / 2} x_j^2)^-beta with
+ *            n = res_C (odd, 1 .. 15) and the sum running over the channel group of c only: groups of Cmid channels
+ *            [g Cmid, (g + 1) Cmid), channels outside the group count as zero (two networks' maps side by side in one tensor
+ *            never mix).  Cmid = 0: no LRN (plain max pool).  w_off -> [4] floats: alpha, beta, k, unused (-1 when Cmid = 0).
+ *            Cin, Cmid, in_ld, out_ld, offsets and image strides multiples of 4, Cin % Cmid == 0, out_cmul = 1, act = FP_ACT_NONE,
+ *            res_mode = FP_RES_NONE.  fp32: the sum of squares in channel order j = c - n/2 .. c + n/2, pow from the device math
+ *            library (powf).
+ *   CLS_HEAD : in = one row of Cin floats per image at (image n, pixel 0) of the input view (H = W = 1, or a map's first
+ *            pixel), OH = OW = 1, out = [N][Cout] probabilities (out_ns per image, out_cmul 1), KH = KW = stride = 1.  w_off ->
+ *            [Cout][Cin] fp32 weight (torch's [out, in]), bias_off -> [Cout] (-1: none).  softmax: p_c = exp(z_c - max z) / sum.
+ *            res_off >= 0: the logits z are written there too (res_ns per image, res_ld ignored).  Cin % 4 == 0, Cin <= 4096,
+ *            Cout <= 64, act = FP_ACT_NONE, res_mode = FP_RES_NONE.  One wave per image, fp32; a row does not depend on the batch.
  * ABI history: 1 = round-1 ops; 2 = fp_ext / *_U8 ops (never shipped in a VERDICT-ed tree); 3 = fp_op.flags, row-padded
  * views; 4 = fp_op.Cmid / reserved0, FP_OP_DWBLOCK, FP_OP_BLAZEPAIR; 5 = FP_OPF_SPLIT3; 6 = FP_OP_BLAZECHAIN; 7 = FP_OPF_IN_UP2; 8 = FP_OP_BLAZEPAIR with stride 2; 9 = FP_OPF_OUT_DW, fp_debug_reload_env; 10 = FP_OP_SHUFDOWN, FP_OP_SHUFUNIT, FP_OP_YSTEM2; 11 = FP_OPF_SPLIT3 on FP_OP_STEM_U8;
  * 12 = device Huffman decoding of sequential JPEG scans (fp_jpeg_scan, fp_jpeg_scan_prepare, fp_jpeg_entropy_decode_device, section 7);
@@ -490,6 +508,27 @@ int fp_dets_to_crops_ragged(const float* dets, const int32_t* counts, int B, int
                             float det_thres, float area_thres, int off_tx, int off_ty, int off_bx, int off_by,
                             int dst_w, int dst_h, int max_faces,
                             fp_resize_item* items, float* face_info, int32_t* n_faces, void* stream);
+
+/*
+ * Crop rectangles of the age / gender nets (Levi-Hassner) from face rows: OpenCVFaceDetAgeGenderModel.__call__ of the
+ * reference (modules/opencv2_dnn/model.py): box = round-half-to-even(info[1..4]) -> int, then
+ *   x0 = max(0, x1 - pad), x_end = min(x2 + pad, W - 1), y0 = max(0, y1 - pad), y_end = min(y2 + pad, H - 1)
+ * (the reference's exclusive ends at W - 1 / H - 1, kept), the crop frame[y0:y_end, x0:x_end] resized to dst_w x dst_h
+ * (cv2 INTER_LINEAR: fp_resize_normalize / fp_resize_ragged with the item written here).
+ * info: [n][info_floats] rows (frame index, x1, y1, x2, y2, ...), e.g. fp_dets_to_crops' info (info_floats = 7).
+ * Frame sizes: descs (device, ragged batch, indexed by the row's frame) or, with descs = NULL, frame_w x frame_h for every
+ * row.  items[i] = {frame, x0, y0, x_end - x0, y_end - y0, 0, 0, dst_w, dst_h}; a crop with zero width or height (the
+ * reference's cv2.resize would raise on it) gets sw = sh = dw = dh = 0: the resize writes pad colour and the caller marks
+ * the face's outputs undefined (AgeGenderNet: NaN probabilities).  A row whose frame index is outside [0, n_frames) is
+ * such an empty item too.  Refusals before any launch: NULL pointers, n < 0, info_floats < 5, pad < 0, dst sizes < 1
+ * (FP_ERR_INVALID_ARG).  fp_attr_crop_items_emulate: the same arithmetic on host arrays (descs host too).
+ */
+int fp_attr_crop_items(const float* info /*device*/, int n, int info_floats, const fp_frame_desc* descs /*device or NULL*/,
+                       int n_frames, int frame_w, int frame_h, int pad, int dst_w, int dst_h,
+                       fp_resize_item* items /*device*/, void* stream);
+int fp_attr_crop_items_emulate(const float* info /*host*/, int n, int info_floats, const fp_frame_desc* descs /*host or NULL*/,
+                               int n_frames, int frame_w, int frame_h, int pad, int dst_w, int dst_h,
+                               fp_resize_item* items /*host*/);
 
 /* ------------------------------------------------------------------------- */
 /* 3. BlazeFace post-processing                                                */

@@ -176,6 +176,16 @@ SIGNATURES = {
     "fp_jpeg_encode_emulate": (_I, [_P, C.POINTER(FpJpegEncItem), _I, _I, _I, _I, _P, _SZ, C.POINTER(_I64)]),
     "fp_attr_crop_items": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "fp_attr_crop_items_emulate": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "fp_pnet_level_images": (_I, [_P, _SZ, _P, _I, _P, _I, _I, _I, _P, _P]),
+    "fp_pnet_threshold": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P]),
+    "fp_mtcnn_scratch_bytes": (_SZ, [_I, _I]),
+    "fp_mtcnn_stage1": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    "fp_mtcnn_cut": (_I, [_P, _SZ, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P]),
+    "fp_mtcnn_stage2": (_I, [_P, _I, _I, _P, _P, _I, _P, _I, _F, _P, _P, _P, _P, _SZ, _P]),
+    "fp_mtcnn_stage3": (_I, [_P, _I, _I, _P, _P, _I, _P, _I, _F, _I, _P, _P, _P, _P, _SZ, _P]),
+    "fp_mtcnn_boxes": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "fp_mtcnn_nms": (_I, [_P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _SZ, _P]),
+    "fp_dets_to_crops_px": (_I, [_P, _P, _I, _I, _I, _P, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "fp_tracker_step": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _F, _F, _P, _P, _P]),
 }
 

@@ -44,6 +44,11 @@ __host__ __device__ __forceinline__ void crop_lmarks(const CropArgs& p, const Fr
     }
     o[8] = 0.f;
     o[9] = 0.f;
+  } else if (p.fmt == 2) {
+    for (int k = 0; k < 5; ++k) {
+      o[2 * k] = fminf(fmaxf(d[4 + 2 * k], 0.f), (float)g.orig_w);
+      o[2 * k + 1] = fminf(fmaxf(d[5 + 2 * k], 0.f), (float)g.orig_h);
+    }
   } else {
     for (int k = 0; k < 5; ++k) {
       float x = (d[5 + 2 * k] - g.pad_x) / g.gain, y = (d[6 + 2 * k] - g.pad_y) / g.gain;
@@ -391,6 +396,24 @@ int fp_dets_to_crops_aligned_ragged(const float* dets, const int32_t* counts, in
   return FP_OK;
 }
 
+int fp_dets_to_crops_px(const float* dets, const int32_t* counts, int B, int max_dets, int row_floats,
+                        const fp_frame_desc* descs, float det_thres, float area_thres, int off_tx, int off_ty, int off_bx,
+                        int off_by, int dst_w, int dst_h, int max_faces, fp_resize_item* items, float* face_info,
+                        int32_t* n_faces, float* lmarks, double* M, int32_t* flags, void* stream) {
+  if (!dets || !counts || !descs || !items || !face_info || !n_faces) return FP_ERR_INVALID_ARG;
+  if (B < 0 || max_dets <= 0 || max_faces <= 0 || dst_w <= 0 || dst_h <= 0 || row_floats < 15) return FP_ERR_INVALID_ARG;
+  const bool align = lmarks || M || flags;
+  if (align && (!lmarks || !M || !flags)) return FP_ERR_INVALID_ARG;
+  if (align && ((uintptr_t)M) % 8) return FP_ERR_ALIGNMENT;
+  CropArgs a{dets, counts, B, max_dets, row_floats, 2, 1, 1, 0, 0, det_thres, area_thres, 1.f,
+             0.f, 0.f, off_tx, off_ty, off_bx, off_by, dst_w, dst_h, max_faces, items, face_info, n_faces,
+             descs, nullptr, lmarks, M, flags};
+  if (align) hipLaunchKernelGGL(dets_to_crops_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(dets_to_crops_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+  FP_CHECK_LAUNCH();
+  return FP_OK;
+}
+
 int fp_dets_to_crops_aligned_emulate(const float* dets, const int32_t* counts, int B, int max_dets, int row_floats, int fmt,
                                      int in_w, int in_h, const fp_frame_desc* descs, const float* geom, float det_thres,
                                      float area_thres, int off_tx, int off_ty, int off_bx, int off_by, int dst_w, int dst_h,
@@ -445,7 +468,7 @@ int fp_align_warp_ragged(const uint8_t* frames, size_t frames_bytes, const fp_fr
 int fp_align_emulate(const uint8_t* frames, size_t frames_bytes, const fp_frame_desc* descs, int n_frames, const float* lmarks,
                      int fmt, double* M, const float* face_info, int32_t* flags, const fp_resize_item* items, int n,
                      uint8_t* out_u8) {
-  if (n < 0 || !M || !flags || (fmt != 0 && fmt != 1)) return FP_ERR_INVALID_ARG;
+  if (n < 0 || !M || !flags || fmt < 0 || fmt > 2) return FP_ERR_INVALID_ARG;
   if (lmarks)
     for (int k = 0; k < n; ++k) flags[k] = align_estimate(lmarks + (long)k * 10, fmt, M + (long)k * 6);
   if (!out_u8) return FP_OK;

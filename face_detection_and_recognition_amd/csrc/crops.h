@@ -7,6 +7,9 @@
 //        column reorder (blazeface/model.py:70) + get_dets_bboxes_confs_lmarks_areas (utils/inference.py:11-58).
 // fmt 1: YOLOv5-face rows (x1,y1,x2,y2,conf@4,...) in model-input pixels: get_bboxes_confs_areas
 //        (yolov5_face/onnx/onnx_utils.py:313-340).
+// fmt 2: MTCNN rows (x1,y1,x2,y2,(x,y) x 5,conf@14) in the FRAME's own pixels (the wrappers' input size is the image): only
+//        fp_dets_to_crops_px passes it (no geom: gain 1, pad 0); the area share is taken of the frame, as fmt 0 takes it of
+//        the model input.  The entry points of fmt 0 / 1 refuse it.
 // Both: conf > det_thres, area filter (fmt 0: 100*(area/total) > thr, info[6] = fraction; fmt 1: (100*area)/total > thr,
 // info[6] = percent -- each in its reference's operation order), scale_coords (utils/image.py:79-99: subtract pad,
 // divide by gain, clip to the frame), round half-to-even, then the crop of
@@ -42,6 +45,7 @@ struct FrameGeom {
 __host__ __device__ __forceinline__ FrameGeom frame_geom(const CropArgs& p, int f) {
   if (!p.descs) return FrameGeom{p.orig_w, p.orig_h, p.gain, p.pad_x, p.pad_y};
   const fp_frame_desc d = p.descs[f];
+  if (!p.geom) return FrameGeom{d.w, d.h, 1.f, 0.f, 0.f};   // fmt 2: rows already in frame pixels
   return FrameGeom{d.w, d.h, p.geom[3 * f], p.geom[3 * f + 1], p.geom[3 * f + 2]};
 }
 
@@ -51,13 +55,20 @@ __host__ __device__ __forceinline__ bool crop_one(const CropArgs& p, const Frame
     conf = d[16];
     if (!(conf > p.det_thres)) return false;
     x1 = d[1] * (float)p.in_w; y1 = d[0] * (float)p.in_h; x2 = d[3] * (float)p.in_w; y2 = d[2] * (float)p.in_h;
+  } else if (p.fmt == 2) {
+    conf = d[14];
+    if (!(conf > p.det_thres)) return false;
+    x1 = d[0]; y1 = d[1]; x2 = d[2]; y2 = d[3];
   } else {
     conf = d[4];
     if (!(conf > p.det_thres)) return false;
     x1 = d[0]; y1 = d[1]; x2 = d[2]; y2 = d[3];
   }
   const float area = (x2 - x1) * (y2 - y1);
-  if (p.fmt == 0) {  // inference.py:40-42: perc = area / total (the FRACTION is reported), filter on 100 * perc
+  if (p.fmt == 2) {  // the wrappers' input size is the frame: inference.py:40-42 with total = the frame's area
+    perc = area / (float)(g.orig_w * g.orig_h);
+    if (!(100.f * perc > p.area_thres)) return false;
+  } else if (p.fmt == 0) {  // inference.py:40-42: perc = area / total (the FRACTION is reported), filter on 100 * perc
     perc = area / (float)(p.in_w * p.in_h);
     if (!(100.f * perc > p.area_thres)) return false;
   } else {           // onnx_utils.py:329-332: perc = 100 * area / total (the PERCENT is reported and compared)

@@ -1,0 +1,47 @@
+"""``python -m face_detection_and_recognition_amd.detect_face_mtcnn -i img.jpg --mt fast --md weights.npz``
+Entry point with the reference's flags (face_detection_and_extraction/detect_face_mtcnn.py).  Images only (the video /
+webcam GUI loops are out of scope); prints the detector's rows (15 numbers each: box, five landmarks, confidence, normalised
+by the image size) and the post-processed detections as JSON.  ``--md synthetic`` runs seeded random weights calibrated on the image (synth.py)."""
+import json
+
+from .modules.mtcnn.model import SLOW_DEFAULTS, SLOW_WEIGHTS, MTCNNFastModel, MTCNNSlowModel
+from .modules.utils.inference import get_dets_bboxes_confs_lmarks_areas, load_image
+from .modules.utils.parser import get_argparse, torch_device
+
+
+def load_model(model_type, model_path, det_thres, bbox_area_thres, device, image=None):
+    net = None
+    if model_path == "synthetic":      # seeded random weights, their heads calibrated on the image itself (synth.synth_mtcnn)
+        from .modules.mtcnn.mtcnn import MTCNN
+        from .synth import synth_mtcnn
+        kw = SLOW_DEFAULTS if model_type == "slow" else dict(min_face_size=40, factor=0.7, thresholds=(0.6, 0.7, 0.8))
+        net = synth_mtcnn(MTCNN(cap=8192, **kw), 0, shares=(0.005, 0.4, 0.5), frames=None if image is None else image[None]).to(device)
+    if model_type == "fast":
+        return MTCNNFastModel(model_path, det_thres, bbox_area_thres, device=device, net=net)
+    if model_type == "slow":
+        return MTCNNSlowModel(det_thres, bbox_area_thres, model_path=model_path, device=device, net=net)
+    raise NotImplementedError(f"{model_type} is not supported")
+
+
+def main(argv=None):
+    parser = get_argparse(description="MTCNN face detection (MI355X HIP path)", conflict_handler='resolve')
+    parser.add_argument("--md", "--model", dest="model", default=SLOW_WEIGHTS,
+                        help="Path to the weights (.npz state dict, .npy port dictionary, .pth) or 'synthetic'. (default: %(default)s)")
+    parser.add_argument("--mt", "--model_type", dest="model_type", default="fast", choices=["fast", "slow"],
+                        help="MTCNN model type, fast or slow (default: %(default)s).")
+    args = parser.parse_args(argv)
+    print("Current Arguments: ", args)
+    image = load_image(args.input_src)
+    net = load_model(args.model_type, args.model, args.det_thres, args.bbox_area_thres, torch_device(args.device), image)
+    h, w = image.shape[:2]
+    dets = net(image)
+    for row in dets:
+        print(" ".join(f"{v:.6f}" for v in row))
+    post = get_dets_bboxes_confs_lmarks_areas(dets.copy(), (w, h), net.input_size, net.det_thres, net.bbox_area_thres)
+    print(json.dumps({"boxes": post.boxes.tolist(), "confs": post.bbox_confs.tolist(),
+                      "areas": post.bbox_areas.tolist(), "landmarks": post.bbox_lmarks.tolist()}))
+    return dets
+
+
+if __name__ == "__main__":
+    main()

@@ -108,11 +108,21 @@ class FacePipeline:
         items = torch.empty((cap, 9), dtype=torch.int32, device=self.dev)
         info = torch.empty((cap, 7), dtype=torch.float32, device=self.dev)
         nf = torch.empty((1,), dtype=torch.int32, device=self.dev)
-        iw, ih = self.det.input_size
         fmt = getattr(self.det, "dets_fmt", 0)
         row = dets.shape[-1]
         tx, ty, bx, by = FACE_OFFSETS
         al = A.alloc(cap, self.dev) if self.align else None
+        if fmt == 2:
+            # rows already in each frame's own pixels (MTCNN: the detector's "input size" is the frame): no scale_coords values
+            descs = frames.descs if isinstance(frames, RaggedFrames) else self._dense_descs(frames)
+            dst = (112, 112) if al is not None else (self.in_w, self.in_h)
+            lm, M, fl = (al["lmarks"], al["M"], al["flags"]) if al is not None else (None, None, None)
+            L.check(lib.fp_dets_to_crops_px(L.ptr(dets), L.ptr(counts), B, dets.shape[1], row, L.ptr(descs),
+                                            float(self.det.det_thres), float(self.det.bbox_area_thres), tx, ty, bx, by, dst[0],
+                                            dst[1], cap, L.ptr(items), L.ptr(info), L.ptr(nf), L.ptr(lm), L.ptr(M), L.ptr(fl),
+                                            L.current_stream(self.dev)), "fp_dets_to_crops_px")
+            return items, info, nf, al
+        iw, ih = self.det.input_size
         if al is not None and (fmt == 1 and row < 15):
             raise L.FacepathError(f"align=True needs detector rows with landmarks (got {row} columns)")
         if isinstance(frames, RaggedFrames):
@@ -145,6 +155,17 @@ class FacePipeline:
                                      float(px), float(py), tx, ty, bx, by, self.in_w, self.in_h, cap, L.ptr(items), L.ptr(info),
                                      L.ptr(nf), L.current_stream(self.dev)), "fp_dets_to_crops")
         return items, info, nf, None
+
+    def _dense_descs(self, frames):
+        """fp_frame_desc rows of a dense (B, H, W, 3) batch (built once per shape)."""
+        B, H, W, _ = frames.shape
+        key = (B, H, W)
+        if getattr(self, "_descs_key", None) != key:
+            d = np.zeros((B, 2), np.int64)
+            d[:, 0] = np.arange(B) * (H * W * 3)
+            d[:, 1] = H | (W << 32)
+            self._descs_key, self._descs = key, torch.from_numpy(d.view(np.uint8)).to(self.dev)
+        return self._descs
 
     def _to_input(self, frames, items, n, canvas, al, info, start=0):
         """The embedder input of faces start .. start + n: the box crops (crops_to_input), or with al the aligned faces."""

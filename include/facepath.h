@@ -894,6 +894,118 @@ int fp_jpeg_encode_device(const uint8_t* src, const fp_jpeg_enc_item* items, int
 int fp_jpeg_encode_emulate(const uint8_t* src, const fp_jpeg_enc_item* items, int n, int quality, int subsampling, int bgr,
                            uint8_t* out, size_t out_cap, int64_t* out_off);
 
+/* ------------------------------------------------------------------------- */
+/* 9. MTCNN (P-Net / R-Net / O-Net cascade, Zhang et al. 2016)                 */
+/* ------------------------------------------------------------------------- */
+/*
+ * Appended in ABI 14 (nothing existing changes).  The procedure is written down in DESIGN.md section 7 ("MTCNN"); the
+ * float64 restatement the tests compare with is tests/mtcnn_restatement.py.
+ *
+ * Stage 1: P-Net runs level by level as a plan of generic ops (conv + PReLU, ceil-mode max pool, a 1x1 conv for both heads)
+ * on groups of equally sized frames.  csrc/pnet.hip holds what surrounds it: fp_pnet_level_images writes a pyramid level of the
+ * group into the plan's input, fp_pnet_threshold turns the head map into 24-byte fp_pnet_cand records of the cells with
+ * p >= t1, handed out by a per-frame atomic counter.  fp_mtcnn_stage1 puts them into (level, cell) order before it uses
+ * them, so the result does not depend on the order of the atomics.  A frame with more than `cap` candidates sets
+ * overflow[frame] = 1 (the host raises); counts[frame] still holds the true number.
+ */
+#define FP_MTCNN_MAX_CAP 8192
+typedef struct fp_pnet_level {
+  double scale;          /* s_k: boxes are generated with it */
+  int32_t lh, lw;        /* level size: ceil(h s), ceil(w s) */
+  int32_t oh, ow;        /* P-Net output map: ceil((l - 2) / 2) - 4 */
+} fp_pnet_level;
+typedef struct fp_pnet_cand {
+  float reg[4];          /* box regression (x1, y1, x2, y2) */
+  float score;           /* face probability */
+  uint32_t key;          /* (level within the frame) << 24 | (y * ow + x) */
+} fp_pnet_cand;
+/*
+ * fp_pnet_level_images: out[i] ([n][lh][lw][4] fp32, 16-byte aligned) = the lh x lw level of frame frame_idx[i] (device int32
+ * [n]; every frame at least lh x lw): each pixel the exact area-weighted mean of its source rectangle (integer arithmetic),
+ * rounded half-to-even to u8, then (v - 127.5) / 128; fourth channel 0.  A frame index or extent outside the tables / the
+ * frames buffer gives zeros.
+ * fp_pnet_threshold: head ([n][oh * ow][ld] fp32, ld >= 8 a multiple of 4: class logits 0, 1, regression 2 .. 5) of the same
+ * frames at level `level` (the level's index within its frame's pyramid): p = softmax(logits)[1]; cells with p >= t1 are
+ * appended to cand[frame] with key = level << 24 | cell.  counts / overflow ([n_frames]) accumulate over calls: the caller zeroes
+ * them before the first level.  Refusals (FP_ERR_INVALID_ARG) before any launch: a NULL or misaligned pointer, sizes out of range,
+ * oh * ow > 2^24, level > 127, cap < 1 or > FP_MTCNN_MAX_CAP.
+ */
+int fp_pnet_level_images(const uint8_t* frames, size_t frames_bytes, const fp_frame_desc* descs /*device*/, int n_frames,
+                         const int32_t* frame_idx /*device*/, int n, int lh, int lw, float* out, void* stream);
+int fp_pnet_threshold(const float* head, int ld, const int32_t* frame_idx /*device*/, int n, int n_frames, int oh, int ow, int level,
+                      float t1, int cap, fp_pnet_cand* cand /*[n_frames][cap]*/, int32_t* counts, int32_t* overflow, void* stream);
+
+/*
+ * The cascade's glue (csrc/mtcnn.hip), one workgroup per frame, fp64 box arithmetic, fp32 IoU without contraction.
+ * NMS everywhere: area (x2 - x1 + 1)(y2 - y1 + 1), intersection with the same + 1, visit by descending score (equal
+ * scores: the lower candidate index wins), drop a box when o > thr against a kept one; o = inter / union, or inter /
+ * min(a_i, a_j) in stage 3.
+ * boxes: [n_frames][cap][4] int32 (x1, y1, x2, y2) + scores [n_frames][cap], in kept order (descending score);
+ * scratch: fp_mtcnn_scratch_bytes(n_frames, cap) bytes.
+ *
+ * fp_mtcnn_stage1: candidates -> (level, cell) order -> boxes q1 = trunc((2 (x, y) + 1) / s), q2 = trunc((2 (x, y) + 12)
+ * / s) -> NMS 0.5 per level -> NMS 0.7 per frame -> b = q + reg (w_q, h_q), squared, truncated; boxes with a side
+ * x2 - x1 + 1 <= 0 are dropped.
+ */
+size_t fp_mtcnn_scratch_bytes(int n_frames, int cap);
+int fp_mtcnn_stage1(const fp_pnet_cand* cand, const int32_t* counts, int n_frames, int cap, const fp_pnet_level* levels,
+                    int n_levels, const int32_t* frame_level0, int32_t* boxes, float* scores, int32_t* out_counts,
+                    void* scratch, size_t scratch_bytes, void* stream);
+/*
+ * fp_mtcnn_cut: candidate i of the flat list (frame f = the one with offs[f] <= i < offs[f + 1], box boxes[f][i - offs[f]])
+ * -> the zero-filled (y2 - y1 + 1) x (x2 - x1 + 1) patch whose pixel (py, px) is frame pixel (y1 - 1 + py, x1 - 1 + px)
+ * where that lies inside the frame, resized to size x size: the area mean when neither axis grows, else linear taps in
+ * "area mode" (sx = floor(dx scale), fx = (dx + 1) - (sx + 1) / scale, fx <= 0 ? 0 : fx - floor(fx)); both in exact integer
+ * arithmetic (the weights are multiples of 1 / patch size), rounded half-to-even to u8.  out: [n][size][size][4] fp32 (v - 127.5) / 128, fourth channel 0; out_u8 (or NULL): [n][size][size][3].
+ */
+int fp_mtcnn_cut(const uint8_t* frames, size_t frames_bytes, const fp_frame_desc* descs, int n_frames, const int32_t* boxes,
+                 int cap, const int32_t* offs /*device [n_frames + 1]*/, int n, int size, float* out, uint8_t* out_u8,
+                 void* stream);
+/*
+ * fp_mtcnn_stage2: rows offs[f] .. offs[f + 1] of prob ([n][prob_ld], face = column 1) and reg ([n][reg_ld], 4 columns)
+ * belong to boxes[f]: keep p >= t2 -> NMS 0.7 -> b = box + reg (w, h), w = x2 - x1 + 1 -> squared, truncated -> out_boxes.
+ */
+int fp_mtcnn_stage2(const int32_t* boxes, int n_frames, int cap, const int32_t* offs, const float* prob, int prob_ld,
+                    const float* reg, int reg_ld, float t2, int32_t* out_boxes, float* out_scores, int32_t* out_counts,
+                    void* scratch, size_t scratch_bytes, void* stream);
+/*
+ * fp_mtcnn_stage3: keep p >= t3; landmarks X = x1 - 1 + w lx, Y = y1 - 1 + h ly (reg columns 4 .. 8 = x, 9 .. 13 = y) on the
+ * input box; b = box + reg (w, h); NMS 0.7 "min".  dets: [n_frames][max_det][15] = (x1, y1, x2, y2, (X, Y) x 5, score) in
+ * frame pixels by descending score; counts[f] = min(found, max_det), overflow[f] = found > max_det.
+ */
+int fp_mtcnn_stage3(const int32_t* boxes, int n_frames, int cap, const int32_t* offs, const float* prob, int prob_ld,
+                    const float* reg, int reg_ld, float t3, int max_det, float* dets, int32_t* counts, int32_t* overflow,
+                    void* scratch, size_t scratch_bytes, void* stream);
+/*
+ * MTCNN rows -> face crops: fp_dets_to_crops_ragged / fp_dets_to_crops_aligned_ragged for rows that are ALREADY in each frame's
+ * own pixels (dets [B][max_dets][row_floats >= 15] = fp_mtcnn_stage3's rows; "fmt 2" of csrc/crops.h).  conf > det_thres, the
+ * box's share of the FRAME (100 * area / (w h) > area_thres; info[6] = the fraction), clip to the frame, round half-to-even,
+ * then the same crop arithmetic, items and face_info.  lmarks / M / flags all NULL: box crops; all given: also the five
+ * landmarks (clipped to the frame), the alignment transform and flags of fp_dets_to_crops_aligned.  Dense batches pass descs
+ * with equal sizes.  fp_align_emulate accepts fmt 2 (five points, as fmt 1).
+ */
+int fp_dets_to_crops_px(const float* dets, const int32_t* counts, int B, int max_dets, int row_floats,
+                        const fp_frame_desc* descs /*device, B*/, float det_thres, float area_thres, int off_tx, int off_ty,
+                        int off_bx, int off_by, int dst_w, int dst_h, int max_faces, fp_resize_item* items, float* face_info,
+                        int32_t* n_faces, float* lmarks, double* M, int32_t* flags, void* stream);
+/*
+ * The box arithmetic of the stages alone (the same device functions the stage kernels call; tests feed it the restatement's
+ * kept boxes): boxes [n][4] fp32 (integers in value), reg [n][reg_ld].  mode 1: b = box + reg (w, h), w = x2 - x1, squared,
+ * truncated -> out_boxes [n][4] int32; mode 2: the same with w = x2 - x1 + 1; mode 3: b = box + reg (w, h), w = x2 - x1 + 1, not
+ * squared, and the landmarks X = x1 - 1 + w lx, Y = y1 - 1 + h ly (reg columns 4 .. 8 = lx, 9 .. 13 = ly) -> out_rows [n][14] fp32
+ * = (x1, y1, x2, y2, (X, Y) x 5).
+ */
+int fp_mtcnn_boxes(const float* boxes, const float* reg, int reg_ld, int n, int mode, int32_t* out_boxes, float* out_rows,
+                   void* stream);
+/*
+ * The NMS of the stages alone (tests feed it the restatement's boxes): segment s = rows seg[s] .. seg[s + 1] of boxes
+ * ([n][4] fp32) / scores; mode 0 = union, 1 = min.  keep_idx[seg[s] + k] = row index (within the whole list) of the k-th
+ * kept box of segment s in visiting order, keep_count[s] their number.  A segment takes at most FP_MTCNN_MAX_CAP rows.
+ */
+int fp_mtcnn_nms(const float* boxes, const float* scores, const int32_t* seg /*device [n_seg + 1]*/, int n_seg, int n,
+                 float thr, int mode, int32_t* keep_idx, int32_t* keep_count, void* scratch, size_t scratch_bytes,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

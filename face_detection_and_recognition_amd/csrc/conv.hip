@@ -185,7 +185,21 @@ __global__ __launch_bounds__(256, PWD ? (NB == 4 ? 3 : 4) : 1) void conv_igemm_k
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
 
+  // Long reductions (K > FLUSH_CHUNKS * 32: the 7x7x384 Linear of the age / gender nets, K = 18816) are summed in blocks: every
+  // FLUSH_CHUNKS chunks the chain's partial sum moves into a second accumulator, so the rounding error grows with the block
+  // length and the number of blocks instead of with K (one chain over 18816 terms measured 1.8e-6 of the output scale against
+  // fp64, five times torch's fp32 conv).  Shorter reductions never flush and keep their bits.  The pointwise-dense instances
+  // are tuned to their register budgets and keep the single chain.
+  constexpr int FLUSH_CHUNKS = 32;
+  f32x16 acc_hi[PWD ? 1 : NB];
   const int nchunks = (p.Kpad + KC - 1) / KC;
+  const bool blocked = !PWD && nchunks > FLUSH_CHUNKS;
+  if (blocked) {
+#pragma unroll
+    for (int nb = 0; nb < (PWD ? 1 : NB); ++nb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc_hi[nb][r] = 0.f;
+  }
   load_chunk(0);
   for (int ch = 0; ch < nchunks; ++ch) {
     store_chunk();
@@ -208,6 +222,14 @@ __global__ __launch_bounds__(256, PWD ? (NB == 4 ? 3 : 4) : 1) void conv_igemm_k
       }
     }
     __syncthreads();
+    if (blocked && (ch % FLUSH_CHUNKS == FLUSH_CHUNKS - 1 || ch + 1 == nchunks)) {
+#pragma unroll
+      for (int nb = 0; nb < (PWD ? 1 : NB); ++nb) {
+        acc_hi[nb] += acc[nb];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[nb][r] = ch + 1 == nchunks ? acc_hi[nb][r] : 0.f;
+      }
+    }
   }
 
   // Epilogue.  C/D map of 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
@@ -675,18 +697,22 @@ __global__ __launch_bounds__(256) void copy4_kernel(CopyArgs p) {
       *(const f32x4*)(p.in + (long)img * p.in_ns + (long)pix * p.in_ld + c4 * 4);
 }
 
-// l2_norm (mobile_facenet.py:30-33): one wave per row, x / sqrt(sum x^2), no epsilon.
-__global__ __launch_bounds__(256) void l2norm_kernel(const float* in, float* out, long M, int D, long in_ld, long out_ld) {
+// l2_norm (mobile_facenet.py:30-33): one wave per row, x / sqrt(sum x^2), no epsilon.  Row m = (image m / HW, pixel m % HW)
+// of a general view (facepath.h: off + n*ns + pix*ld + c), decoded as copy_kernel does.
+__global__ __launch_bounds__(256) void l2norm_kernel(const float* in, float* out, long M, int D, int HW, long in_ld, long out_ld,
+                                                     long in_ns, long out_ns) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
   const int lane = threadIdx.x & 63;
-  const float* x = in + row * in_ld;
+  const long img = row / HW, pix = row - img * HW;
+  const float* x = in + img * in_ns + pix * in_ld;
+  float* y = out + img * out_ns + pix * out_ld;
   float s = 0.f;
   for (int i = lane; i < D; i += 64) s += x[i] * x[i];
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
   const float nrm = sqrtf(s);
-  for (int i = lane; i < D; i += 64) out[row * out_ld + i] = x[i] / nrm;
+  for (int i = lane; i < D; i += 64) y[i] = x[i] / nrm;
 }
 
 }  // namespace
@@ -695,8 +721,10 @@ static bool conv_vec_epilogue(const fp_op& op) {
   bool ve = op.out_cmul == 1 && op.Cout % 4 == 0 && op.out_ld % 4 == 0 && op.out_off % 4 == 0 && op.out_ns % 4 == 0 &&
             (op.scale_off < 0 || op.scale_off % 4 == 0) && (op.bias_off < 0 || op.bias_off % 4 == 0) &&
             (op.slope_off < 0 || op.slope_off % 4 == 0);
+  // the residual is read four channels at a time: every group below Cout must lie inside res_C or outside it ("c >= res_C
+  // adds 0", facepath.h); a residual that ends inside a group takes the scalar epilogue
   if (op.res_mode != FP_RES_NONE)
-    ve = ve && op.res_ld % 4 == 0 && op.res_off % 4 == 0 && op.res_ns % 4 == 0 && fp_round_up(op.res_C, 4) <= op.res_ld;
+    ve = ve && op.res_ld % 4 == 0 && op.res_off % 4 == 0 && op.res_ns % 4 == 0 && (op.res_C % 4 == 0 || op.res_C >= op.Cout);
   return ve;
 }
 
@@ -897,7 +925,8 @@ int fp_launch_l2norm(const fp_op& op, const fp_launch& L) {
   const long M = (long)op.N * op.H * op.W;
   if (fp_dry_run(L, "l2norm_kernel")) return FP_OK;
   hipLaunchKernelGGL(l2norm_kernel, dim3((unsigned)fp_ceil_div(M, 4)), dim3(256), 0, L.s, L.arena + op.in_off,
-                     L.arena + op.out_off, M, op.Cin, (long)op.in_ld, (long)op.out_ld);
+                     L.arena + op.out_off, M, op.Cin, op.H * op.W, (long)op.in_ld, (long)op.out_ld, (long)op.in_ns,
+                     (long)op.out_ns);
   FP_CHECK_LAUNCH();
   return FP_OK;
 }

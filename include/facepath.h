@@ -67,7 +67,8 @@ enum fp_op_kind {
   FP_OP_MAXPOOL = 3,    /* max pool, -inf padding, OH/OW given by caller (covers ceil_mode) */
   FP_OP_UPSAMPLE2X = 4, /* nearest-neighbour 2x */
   FP_OP_COPY = 5,       /* channel-slice copy (concat / chunk / shuffle interleave) */
-  FP_OP_L2NORM = 6,     /* out[m,:] = in[m,:] / ||in[m,:]||_2 over Cin channels (mobile_facenet.py:30-33) */
+  FP_OP_L2NORM = 6,     /* out[m,:] = in[m,:] / ||in[m,:]||_2 over Cin channels (mobile_facenet.py:30-33), no epsilon; row m = pixel
+                           m % (H*W) of image m / (H*W), both views by the general rule (off + n*ns + pix*ld + c, any ns / ld) */
   FP_OP_BLAZEBLOCK = 7, /* fused BlazeBlock: dw3x3 -> 1x1 -> (+shortcut) -> ReLU (blazeface.py:12-47) */
   FP_OP_DWPW = 8,       /* fused Depth_Wise tail: dw3x3(+BN,+PReLU) -> 1x1(+BN) [+x] (mobile_facenet.py:72-85) */
   FP_OP_YSTEM = 9,      /* head of YOLOv5-face's StemBlock (y5/models/common.py:58-73): stem_1 (3x3 s2, SiLU) kept in LDS ->

@@ -280,6 +280,263 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 3) void cosine_x6_kernel(const f
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Top-k search (identify against an enrolled gallery): S = Q G^T with the arithmetic of cosine_x6_kernel (gallery planes
+// from split3_rows_kernel, queries split in registers, fp_mfma_x6, score = acc * qinv[m] * ginv[n]), reduced to the k
+// best columns of every row.  One 64-bit atomicMax cannot carry k candidates, so the grid is (row tile) x (split): a
+// workgroup walks a CONTIGUOUS range of 128-column chunks as one flat, double-buffered pipeline (the next chunk's first
+// slab is staged under the last MFMAs of this one) and keeps a running top-k per row in LDS, as sorted 64-bit keys
+//     key = ord(score) << 32 | ~column        (larger = better: higher score, then LOWER column; 0 = empty slot).
+// The keys of all candidates are distinct and totally ordered, so the k largest are one well-defined set: inserting in any
+// order, in any partition of the columns, gives the same list -- the result does not depend on n_splits, on the order in
+// which lanes insert, or on workgroup scheduling.
+//   * epilogue of a chunk: a lane holds 4 consecutive columns of one row per accumulator; it keeps the row's k-th best
+//     score in a register and compares the maximum of the 4 with it (3 v_max + 1 compare per 4 candidates); only a group
+//     that reaches it takes the insertion path.  A masked column (ginv == 0) or one past N carries a NaN factor: its score
+//     compares false and never enters.
+//   * insertion path: the four lanes that share a row (q = 0..3) take turns -- a lane goes when no lower-q lane of its
+//     row is pending (one ballot) -- and the lists are private to the wave that owns the rows: no barrier, LDS operations
+//     of one wave complete in program order.
+//   * the list leaves the workgroup once, as k keys per (row, split); topk_merge_kernel picks the k largest keys of a
+//     row's n_splits lists (one wave per row) and unpacks them.
+template <int MT>
+__global__ __launch_bounds__(256, 3) void cosine_topk_x6_kernel(const float* __restrict__ Q, const float* __restrict__ qinv,
+                                                                               long M, const unsigned short* __restrict__ G3,
+                                                                               const float* __restrict__ ginv, int N, int Npad, int D,
+                                                                               int k, int n_splits,
+                                                                               unsigned long long* __restrict__ partial) {
+  constexpr int NT16 = 8, NC = 128, SLAB = 3 * NC * 32, XBM = 4 * MT * 16;
+  typedef unsigned long long u64;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  unsigned short* Bl = (unsigned short*)smem_raw;        // [2][3][NC][32]
+  volatile u64* Ls = (volatile u64*)(smem_raw + 2 * SLAB * 2);   // [XBM][LS] running top-k keys, descending
+  const int LS = k | 1;                                  // odd stride: the rows' k-th entries fall in different banks
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, q = lane >> 4;
+  const int nchunk = Npad / NC;
+  const unsigned vb = fp_xcd_block();                    // the splits of one row tile on ONE XCD (query rows from its L2)
+  const int split = vb % (unsigned)n_splits;
+  const long row0 = (long)(vb / (unsigned)n_splits) * XBM + wave * (MT * 16);
+  // chunks [cb, ce) of this split: nchunk = n_splits * base + rem, the first rem splits take one more
+  const int base = nchunk / n_splits, rem = nchunk - base * n_splits;
+  const int cb = split * base + (split < rem ? split : rem);
+  const int nck = base + (split < rem ? 1 : 0);          // >= 1 (the launcher clamps n_splits to nchunk)
+  const int KS = D / 32;
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  const float ninf = -__builtin_huge_valf(), qnan = __builtin_nanf("");
+
+  for (int i = lane; i < MT * 16 * LS; i += 64) Ls[wave * (MT * 16) * LS + i] = 0;
+  u64 lower = 0;                                         // the lanes of my row with a smaller q
+  for (int qq = 0; qq < q; ++qq) lower |= 1ull << (l15 + 16 * qq);
+
+  auto stage = [&](int chunk, int ks, int buf) {
+    unsigned char* dst = (unsigned char*)(Bl + buf * SLAB);
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) {
+      const unsigned char* src = (const unsigned char*)(G3 + ((long)(ks * 3 + pl) * Npad + (long)chunk * NC) * 32) + lane * 16;
+#pragma unroll
+      for (int j = 0; j < NT16 / 4; ++j) {
+        const int c = j * 4 + wave;
+        __builtin_amdgcn_global_load_lds((gbl_ptr)(src + c * 1024), (lds_ptr)(dst + (pl * NC * 32 + c * 512) * 2), 16, 0, 0);
+      }
+    }
+  };
+  const float* Qw = Q + fp_uniform(row0 * D);             // this wave's rows; row0 < M
+  int arow[MT];                                          // 32-bit offsets: at most 64 rows x D floats
+  float thr[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    long r = row0 + 16 * t + l15;
+    r = r < M ? r : M - 1;
+    arow[t] = (int)(r - row0) * D + 8 * q;
+    thr[t] = ninf;
+  }
+  f32x4 araw[MT][2];
+  auto load_a = [&](int ks) {
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {
+      araw[t][0] = *(const f32x4*)(Qw + arow[t] + 32 * ks);
+      araw[t][1] = *(const f32x4*)(Qw + arow[t] + 32 * ks + 4);
+    }
+  };
+  f32x4 acc[MT][NT16];
+#pragma unroll
+  for (int t = 0; t < MT; ++t)
+#pragma unroll
+    for (int n = 0; n < NT16; ++n) acc[t][n] = z;
+
+  const int steps = nck * KS;
+  int ks = 0, chunk = cb;                                // of the step being computed
+  stage(cb, 0, 0);
+  load_a(0);
+  for (int s = 0; s < steps; ++s) {
+    fp_frag3 af[MT];
+#pragma unroll
+    for (int t = 0; t < MT; ++t) af[t] = fp_split8(araw[t][0], araw[t][1]);
+    __syncthreads();
+    if (s + 1 < steps) {
+      const bool last = ks + 1 == KS;
+      stage(last ? chunk + 1 : chunk, last ? 0 : ks + 1, (s + 1) & 1);
+      load_a(last ? 0 : ks + 1);
+    }
+    const unsigned short* Bc = Bl + (s & 1) * SLAB + (l15 * 32 + 8 * q);
+    fp_frag3 bf[2];
+    auto ldb = [&](int n, fp_frag3& b) {
+      b.h = *(const u32x4*)(Bc + n * 512);
+      b.m = *(const u32x4*)(Bc + NC * 32 + n * 512);
+      b.l = *(const u32x4*)(Bc + 2 * NC * 32 + n * 512);
+    };
+    ldb(0, bf[0]);
+#pragma unroll
+    for (int n = 0; n < NT16; ++n) {
+      if (n + 1 < NT16) ldb(n + 1, bf[(n + 1) & 1]);
+      const fp_frag3& b = bf[n & 1];
+#pragma unroll
+      for (int t = 0; t < MT; ++t) acc[t][n] = fp_mfma_x6(b.h, b.m, b.l, af[t].h, af[t].m, af[t].l, acc[t][n]);
+    }
+    if (++ks < KS) continue;
+    ks = 0;
+
+    // epilogue of a chunk: lane = query row 16 t + l15, gallery columns c0 + 16 n + 4 q + i
+    const int c0 = chunk * NC;
+    ++chunk;
+    float gi[MT];
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {
+      const long m = row0 + 16 * t + l15;
+      gi[t] = m < M ? qinv[m] : qnan;
+    }
+#pragma unroll
+    for (int n = 0; n < NT16; ++n) {
+      const int colb = c0 + 16 * n + 4 * q;
+      f32x4 rn;
+      if (colb + 3 < N) {
+        rn = *(const f32x4*)(ginv + colb);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) rn[i] = colb + i < N ? ginv[colb + i] : 0.f;
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) rn[i] = rn[i] == 0.f ? qnan : rn[i];      // masked / padding: never a candidate
+#pragma unroll
+      for (int t = 0; t < MT; ++t) {
+        volatile u64* Lr = Ls + (wave * (MT * 16) + 16 * t + l15) * LS;
+        f32x4 sv;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sv[i] = acc[t][n][i] * gi[t] * rn[i];
+        acc[t][n] = z;
+        // fmaxf drops NaNs: the maximum of the valid candidates (NaN if none is)
+        const float mx = fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3]));
+        if (__ballot(mx >= thr[t]) == 0) continue;       // the common case: nothing in this group reaches the k-th best
+#pragma unroll 1
+        for (int i = 0; i < 4; ++i) {
+          const float v = i == 0 ? sv[0] : i == 1 ? sv[1] : i == 2 ? sv[2] : sv[3];
+          bool pend = v >= thr[t];
+          const u64 key = ((u64)f2ord(v) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)(colb + i));
+          for (;;) {
+            const u64 mask = __ballot(pend);
+            if (!mask) break;
+            if (pend && !(mask & lower)) {               // my turn: no lower-q lane of my row is waiting
+              pend = false;
+              if (key > Lr[k - 1]) {
+                int j = k - 1;
+                while (j > 0) {
+                  const u64 p = Lr[j - 1];
+                  if (p > key) break;
+                  Lr[j] = p;
+                  --j;
+                }
+                Lr[j] = key;
+              }
+            }
+            __builtin_amdgcn_wave_barrier();
+          }
+        }
+        const u64 kth = Lr[k - 1];
+        thr[t] = kth ? ord2f((unsigned)(kth >> 32)) : ninf;
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {                         // other lanes of the row may have raised it
+      const u64 kth = Ls[(wave * (MT * 16) + 16 * t + l15) * LS + k - 1];
+      thr[t] = kth ? ord2f((unsigned)(kth >> 32)) : ninf;
+    }
+  }
+
+  // the lists of this wave's rows -> partial[m][split][0 .. k)
+  __builtin_amdgcn_wave_barrier();
+  for (int i = lane; i < MT * 16 * k; i += 64) {
+    const int r = i / k, j = i - r * k;
+    const long m = row0 + r;
+    if (m < M) partial[(m * n_splits + split) * k + j] = Ls[(wave * (MT * 16) + r) * LS + j];
+  }
+}
+
+// One wave per row: the k largest of the row's n_splits * k keys (all distinct, except empty slots = 0), descending, unpacked.
+__global__ __launch_bounds__(256) void topk_merge_kernel(const unsigned long long* __restrict__ partial, long M, int cnt, int k,
+                                                         float* __restrict__ scores, int* __restrict__ idx) {
+  typedef unsigned long long u64;
+  const long m = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (m >= M) return;
+  const int lane = threadIdx.x & 63;
+  const u64* p = partial + m * cnt;
+  u64 prev = ~0ull, mine = 0;
+  for (int j = 0; j < k; ++j) {
+    u64 best = 0;
+    for (int e = lane; e < cnt; e += 64) {
+      const u64 v = p[e];
+      if (v < prev && v > best) best = v;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const unsigned lo = __shfl_xor((unsigned)best, off), hi = __shfl_xor((unsigned)(best >> 32), off);
+      const u64 o = ((u64)hi << 32) | lo;
+      best = o > best ? o : best;
+    }
+    if (lane == j) mine = best;
+    prev = best;                                         // 0 once the keys run out: every later round finds nothing
+    if (best == 0) break;
+  }
+  if (lane < k) {
+    scores[m * k + lane] = mine ? ord2f((unsigned)(mine >> 32)) : -__builtin_huge_valf();
+    idx[m * k + lane] = mine ? (int)(0xFFFFFFFFu - (unsigned)(mine & 0xFFFFFFFFull)) : -1;
+  }
+}
+
+// fp_topk_vote: one thread per row of a (M, k) top-k result.
+__global__ __launch_bounds__(256) void topk_vote_kernel(const float* __restrict__ scores, const int* __restrict__ idx, long M, int k,
+                                                        const int* __restrict__ labels, int N, float tau, int mode,
+                                                        int* __restrict__ out_label, float* __restrict__ out_score,
+                                                        int* __restrict__ out_votes) {
+  const long m = (long)blockIdx.x * 256 + threadIdx.x;
+  if (m >= M) return;
+  const float* s = scores + m * k;
+  const int* ix = idx + m * k;
+  auto passes = [&](int j) { return ix[j] >= 0 && ix[j] < N && s[j] >= tau; };
+  int wl = -1, wv = 0;
+  float wbest = s[0], wsum = 0.f;
+  if (mode == 0) {
+    if (passes(0)) wl = labels[ix[0]], wv = 1;
+  } else {
+    for (int j = 0; j < k; ++j) {
+      if (!passes(j)) continue;
+      const int lab = labels[ix[j]];
+      bool first = true;
+      for (int i = 0; i < j; ++i) first = first && !(passes(i) && labels[ix[i]] == lab);
+      if (!first) continue;                              // counted at the label's first candidate (its best score: rows are descending)
+      int v = 0;
+      float sum = 0.f;
+      for (int i = j; i < k; ++i)
+        if (passes(i) && labels[ix[i]] == lab) ++v, sum += s[i];
+      if (wl < 0 || v > wv || (v == wv && (sum > wsum || (sum == wsum && lab < wl)))) wl = lab, wv = v, wsum = sum, wbest = s[j];
+    }
+  }
+  out_label[m] = wl;
+  out_score[m] = wbest;
+  out_votes[m] = wv;
+}
+
 __global__ __launch_bounds__(256) void cosine_finalize_kernel(const unsigned long long* __restrict__ packed, long M,
                                                               float tau, float* __restrict__ best,
                                                               int* __restrict__ arg, unsigned char* __restrict__ keep) {
@@ -437,6 +694,98 @@ int fp_cosine_filter_x6(const float* G, const float* ginv, int64_t M, const void
   return FP_OK;
 }
 
+}  // extern "C"
+
+namespace {
+constexpr int TOPK_NC = 128, TOPK_LDS_B = 2 * 3 * 128 * 32 * 2;
+int topk_num_cus() {
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus = n;
+  }
+  return cus;
+}
+// 128-row tiles (MT = 2).  The 256-row form of cosine_x6_kernel does not fit here: the flat chunk loop and the rows' thresholds
+// on top of its 250 registers spill (checked with tools/kernel_resources.py), and a spill is worse than the smaller tile.
+constexpr int TOPK_ROWS = 128;
+// splits of the column range, from M, k and the CU count, never from N.  slots = workgroups the device holds at once (three per
+// CU while the key lists leave room beside the B slabs, k <= 5, else two).  Row tiles that fill the slots alone are not split
+// (measured, 125 000 rows x 10 000 x 512, k = 5: 7.20 ms unsplit, 7.66 / 8.28 / 9.49 ms at 2 / 4 / 8 splits: every split pays the
+// ramp in which a list fills); fewer tiles are split into TOPK_ROUNDS rounds of the slots (512 rows x 1 000 000: 3.36 ms at 384
+// splits, 3.68 at 64, 3.90 at 768).
+constexpr int TOPK_ROUNDS = 2;
+int topk_auto_splits(int64_t M, int k, int cus) {
+  const long tiles = (M + TOPK_ROWS - 1) / TOPK_ROWS;
+  const long slots = (long)(k <= 5 ? 3 : 2) * cus;
+  if (tiles >= slots) return 1;
+  const long s = (TOPK_ROUNDS * slots + tiles - 1) / (tiles > 0 ? tiles : 1);
+  return (int)(s > 4096 ? 4096 : s);
+}
+}  // namespace
+
+extern "C" {
+
+size_t fp_cosine_topk_workspace(int64_t M, int N, int k, int n_splits) {
+  if (M <= 0 || N <= 0 || k < 1 || k > FP_TOPK_MAX || n_splits < 0) return 0;
+  const size_t nchunk = (size_t)(fp_round_up(N, TOPK_NC) / TOPK_NC);
+  if (n_splits) return (size_t)M * (nchunk < (size_t)n_splits ? nchunk : (size_t)n_splits) * (size_t)k * sizeof(uint64_t);
+  // automatic: a bound on M * n_splits that grows with M and k whatever the choice rounds to -- tiles * n_splits is at most
+  // (workgroups wanted at the smallest k) + tiles, and never above tiles * nchunk
+  const size_t tiles = (size_t)((M + TOPK_ROWS - 1) / TOPK_ROWS);
+  const size_t want = (size_t)TOPK_ROUNDS * 3 * topk_num_cus() + tiles;
+  const size_t lists = tiles * nchunk < want ? tiles * nchunk : want;
+  return lists * TOPK_ROWS * (size_t)k * sizeof(uint64_t);
+}
+
+int fp_cosine_topk_x6(const float* Q, const float* qinv, int64_t M, const void* G3, const float* ginv, int N, int D, int k,
+                      int n_splits, float* scores, int32_t* idx, void* workspace, size_t ws_bytes, void* stream) {
+  if (!Q || !qinv || !G3 || !ginv || !scores || !idx || !workspace) return FP_ERR_INVALID_ARG;
+  if (M < 0 || N <= 0 || D <= 0 || k < 1 || k > FP_TOPK_MAX || n_splits < 0) return FP_ERR_INVALID_ARG;
+  if (D % 32 || ((uintptr_t)Q) % 16 || ((uintptr_t)G3) % 16 || ((uintptr_t)ginv) % 16 || ((uintptr_t)workspace) % 8)
+    return FP_ERR_ALIGNMENT;
+  if (M == 0) return FP_OK;
+  if (ws_bytes < fp_cosine_topk_workspace(M, N, k, n_splits)) return FP_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const int Npad = (int)fp_round_up(N, TOPK_NC);
+  const int nchunk = Npad / TOPK_NC;
+  const int cus = topk_num_cus();
+  int ns = n_splits ? n_splits : topk_auto_splits(M, k, cus);
+  ns = ns > nchunk ? nchunk : ns;
+  const int rows = TOPK_ROWS;
+  const long blocks = (M + rows - 1) / rows * ns;
+  if (blocks >= (1L << 31)) return FP_ERR_UNSUPPORTED;
+  const int lds = TOPK_LDS_B + rows * (k | 1) * 8;        // B slabs + the rows' key lists: 53 KiB at k = 5 (three per CU), 65 KiB at 16 (two)
+  static bool attr_set = false;                          // dynamic LDS above 64 KiB (k > 14) needs the attribute
+  if (!attr_set) {
+    const int mx = TOPK_LDS_B + TOPK_ROWS * (FP_TOPK_MAX | 1) * 8;
+    if (hipFuncSetAttribute((const void*)cosine_topk_x6_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess) {
+      fp_set_hip_error(hipGetLastError());
+      return FP_ERR_LAUNCH;
+    }
+    attr_set = true;
+  }
+  unsigned long long* part = (unsigned long long*)workspace;
+  hipLaunchKernelGGL((cosine_topk_x6_kernel<2>), dim3((unsigned)blocks), dim3(256), lds, s, Q, qinv, (long)M, (const unsigned short*)G3,
+                     ginv, N, Npad, D, k, ns, part);
+  FP_CHECK_LAUNCH();
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)fp_ceil_div(M, 4)), dim3(256), 0, s, (const unsigned long long*)part, (long)M,
+                     ns * k, k, scores, idx);
+  FP_CHECK_LAUNCH();
+  return FP_OK;
+}
+
+int fp_topk_vote(const float* scores, const int32_t* idx, int64_t M, int k, const int32_t* labels, int N, float tau, int mode,
+                 int32_t* out_label, float* out_score, int32_t* out_votes, void* stream) {
+  if (!scores || !idx || !labels || !out_label || !out_score || !out_votes) return FP_ERR_INVALID_ARG;
+  if (M < 0 || N <= 0 || k < 1 || k > FP_TOPK_MAX || (mode != 0 && mode != 1)) return FP_ERR_INVALID_ARG;
+  if (M == 0) return FP_OK;
+  hipLaunchKernelGGL(topk_vote_kernel, dim3((unsigned)fp_ceil_div(M, 256)), dim3(256), 0, (hipStream_t)stream, scores, idx, (long)M, k,
+                     labels, N, tau, mode, out_label, out_score, out_votes);
+  FP_CHECK_LAUNCH();
+  return FP_OK;
+}
 int fp_l2_mean_thres(const float* ref, int R, int D, float* out_mean, float* out_thres, void* stream) {
   if (!ref || !out_mean || !out_thres || R <= 0 || D <= 0) return FP_ERR_INVALID_ARG;
   hipLaunchKernelGGL(l2_mean_thres_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ref, R, D, out_mean, out_thres);

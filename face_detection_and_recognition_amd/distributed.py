@@ -4,7 +4,9 @@ Frames are independent through letterbox -> detect -> NMS -> crop -> embed, so t
 collective.  The similarity stage is the only exchange:
   * cosine filter of a row-sharded gallery against a reference set that was *produced* sharded:
     one all_gather of the (small) reference block, then each rank filters its own gallery rows;
-  * l2_mean mode: all_reduce(sum) of the per-rank partial sums / counts of the reference rows, then local filtering.
+  * l2_mean mode: all_reduce(sum) of the per-rank partial sums / counts of the reference rows, then local filtering;
+  * top-k search of a gallery sharded by rows (sharded_cosine_topk): every rank searches its shard, one all_gather of the
+    (M, k) candidate blocks, the merge keeps the single-rank tie rule.
 """
 import torch
 import torch.distributed as dist
@@ -198,6 +200,34 @@ def sharded_cosine_filter(local_gallery, local_reference, tau, filter_fn, group=
     else:
         full_ref, _ = all_gather_rows(local_reference, group)
     return filter_fn(local_gallery, full_ref, tau)
+
+
+def sharded_cosine_topk(queries, local_gallery, k, topk_fn, group=None):
+    """Top-k search against a gallery sharded by rows: every rank holds a contiguous shard, in rank order, and the same
+    queries (M, D).  topk_fn(queries, local_gallery, k) -> (scores (M, k) descending, idx (M, k) int32 local rows, -inf / -1
+    in unused slots) is the local search (HIP: similarity.cosine_topk).  Two collectives: the shards' row counts and ONE
+    gather of the score and index blocks (packed as int32 bits); nothing is read on the host.  Local indices become global
+    ones (rank r's rows start at the sum of the counts before it), and the merge -- a stable descending sort of the
+    candidates laid out in rank order -- keeps the single-rank tie rule: on equal scores the lower global index first.
+    Every rank returns what one rank searching the concatenated gallery would."""
+    world = dist.get_world_size(group)
+    scores, idx = topk_fn(queries, local_gallery, k)
+    M = scores.shape[0]
+    dev = scores.device
+    counts = torch.empty((world,), dtype=torch.int64, device=dev)
+    dist.all_gather_into_tensor(counts, torch.tensor([local_gallery.shape[0]], dtype=torch.int64, device=dev), group=group)
+    mine = torch.stack([scores.contiguous().view(torch.int32), idx.to(torch.int32).contiguous()])      # (2, M, k)
+    blocks = torch.empty((world * 2,) + tuple(mine.shape[1:]), dtype=torch.int32, device=dev)
+    dist.all_gather_into_tensor(blocks, mine, group=group)
+    blocks = blocks.view((world, 2) + tuple(mine.shape[1:]))
+    offsets = (torch.cumsum(counts, 0) - counts).reshape(world, 1, 1)
+    all_scores = blocks[:, 0].contiguous().view(torch.float32)                                   # (world, M, k)
+    all_idx = blocks[:, 1].to(torch.int64)
+    all_idx = torch.where(all_idx >= 0, all_idx + offsets, all_idx)
+    cand_s = all_scores.permute(1, 0, 2).reshape(M, world * k)                                   # rank-major: ascending global index
+    cand_i = all_idx.permute(1, 0, 2).reshape(M, world * k)                                      # among a rank's equal scores
+    order = torch.sort(cand_s, dim=1, descending=True, stable=True).indices[:, :k]
+    return torch.gather(cand_s, 1, order), torch.gather(cand_i, 1, order).to(torch.int32)
 
 
 def sharded_l2_mean(local_reference, group=None):

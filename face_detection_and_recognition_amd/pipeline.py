@@ -44,7 +44,10 @@ class FacePipeline:
     stretched box crop; step results then also carry lmarks, align_M and align_flags.
     attributes: an AgeGenderNet (modules/age_gender): step results then also carry age_probs (n, 8) and gender_probs (n, 2),
     one row per face in the order of emb, from the reference's age / gender crops (fp_attr_crop_items); a face whose crop
-    is empty gets NaN rows.  Under two_streams they run on the embedder's side stream."""
+    is empty gets NaN rows.  Under two_streams they run on the embedder's side stream.
+    gallery: a FaceGallery (gallery.py): step results then also carry top_scores (n, top_k), top_idx (n, top_k) int32 gallery
+    rows, identity (n,) int32 (-1: nobody enrolled reaches identify_tau; default tau) and identity_score (n,), one row per
+    face in the order of emb, voted by `vote` ("top1" | "majority"); side stream as the attributes."""
 
     # embed(): a batch a little above a multiple of ROUND_CROPS crops is run as that multiple + the remainder on a side stream
     ROUND_CROPS = 512     # crops whose tiles fill whole rounds of workgroups in every Depth_Wise kernel (2 / 4 / 7 tiles per crop, 512 slots)
@@ -52,8 +55,12 @@ class FacePipeline:
     TAIL_CAP = 128        # capacity of the remainder's plan
 
     def __init__(self, detector, embedder, reference=None, tau=0.3, max_faces_per_frame=8, bucket=8, two_streams=False,
-                 split_tail=True, align=False, attributes=None):
+                 split_tail=True, align=False, attributes=None, gallery=None, top_k=5, identify_tau=None, vote="top1"):
         self.det = detector
+        self.gallery, self.top_k, self.vote = gallery, int(top_k), vote
+        self.identify_tau = float(tau if identify_tau is None else identify_tau)
+        if gallery is not None and vote not in S.VOTE_MODES:
+            raise ValueError(f"vote must be one of {sorted(S.VOTE_MODES)}, got {vote!r}")
         self.attr = attributes
         self.align = bool(align)
         self.emb = embedder
@@ -278,6 +285,7 @@ class FacePipeline:
             res = self.filter(emb)
             out = dict(n_faces=n, info=info[:n], emb=emb.clone(), items=items[:n])
             self._add_attributes(out, frames, info, n)
+            self._add_identity(out)
         else:
             main = torch.cuda.current_stream(self.dev)
             self.emb_stream.wait_event(ev)                 # the crops of this batch (detector stream)
@@ -290,9 +298,10 @@ class FacePipeline:
                 res = self.filter(emb)
                 out = dict(n_faces=n, info=info[:n], emb=emb.clone(), items=items[:n])
                 self._add_attributes(out, frames, info, n)
+                self._add_identity(out)
                 # allocated on the side stream, consumed by the caller on the main stream (after `done`): tell the caching
                 # allocator, or it hands the blocks to the next embed / filter while main-stream reads are still queued
-                attrs = tuple(out[k] for k in ("age_probs", "gender_probs") if k in out)
+                attrs = tuple(out[k] for k in ("age_probs", "gender_probs") + self.IDENTITY_KEYS if k in out)
                 for t in (out["emb"],) + attrs + (tuple(res) if res is not None else ()):
                     t.record_stream(main)
                 self._emb_done = torch.cuda.Event()
@@ -321,6 +330,20 @@ class FacePipeline:
     def _add_attributes(self, out, frames, info, n):
         if self.attr is not None:
             out["age_probs"], out["gender_probs"] = self.attributes_of(frames, info, n)
+
+    IDENTITY_KEYS = ("top_scores", "top_idx", "identity", "identity_score")
+
+    def _add_identity(self, out):
+        """The gallery's answer for the step's embeddings (rows in the order of emb); nothing without a gallery."""
+        if self.gallery is None:
+            return
+        k = self.top_k
+        if out["n_faces"] == 0:
+            out.update(top_scores=torch.zeros((0, k), device=self.dev), top_idx=torch.zeros((0, k), dtype=torch.int32, device=self.dev),
+                       identity=torch.zeros((0,), dtype=torch.int32, device=self.dev), identity_score=torch.zeros((0,), device=self.dev))
+            return
+        r = self.gallery.identify(out["emb"], k=k, tau=self.identify_tau, vote=self.vote)
+        out.update(top_scores=r["top_scores"], top_idx=r["top_idx"], identity=r["label"], identity_score=r["score"])
 
     @staticmethod
     def _add_align(out, al, n):
@@ -356,6 +379,7 @@ class FacePipeline:
         res = self.filter(emb)
         out = dict(n_faces=n, info=info[:n], emb=emb.clone(), items=items[:n])
         self._add_attributes(out, frames, info, n)
+        self._add_identity(out)
         self._add_align(out, al, n)
         if res is not None:
             out.update(best=res[0], arg=res[1], keep=res[2])

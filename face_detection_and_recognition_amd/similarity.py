@@ -4,6 +4,7 @@
       (similar_face_filtering/filter_faces_using_reference.py:85-99, 186-189)
   cosine_filter              — batched cosine filter (cosine of
       face_detection_and_extraction/face_extraction/extract_and_label_faces_from_dataset.py:106)
+  cosine_topk / topk_vote    — the k best gallery rows of every query and the identity they vote for (build-defined)
 """
 import torch
 
@@ -62,6 +63,64 @@ def cosine_filter(G, R, tau, ginv=None, rinv=None, r3=None, x6=None):
                                           L.ptr(best), L.ptr(arg), L.ptr(keep), L.ptr(packed), L.current_stream(dev)),
                 "fp_cosine_filter")
     return best, arg, keep.bool()
+
+
+def pad_features(x):
+    """x (M, D) with D zero-padded to the next multiple of 32 (what the split-MFMA kernels take).  Zeros change neither
+    the dot products nor the norms.  Returns x itself when D already is one."""
+    D = x.shape[1]
+    return x if D % 32 == 0 else torch.nn.functional.pad(x, (0, 32 - D % 32)).contiguous()
+
+
+def cosine_topk(Q, G, k, qinv=None, ginv=None, g3=None, n_splits=0):
+    """Q (M, D) queries, G (N, D) gallery -> scores (M, k) fp32 descending, idx (M, k) int32 gallery rows; on equal scores the
+    lower index first.  A gallery row whose ginv is 0 is excluded; slots beyond the valid rows hold -inf / -1.  The M x N
+    score matrix is never materialised, the result is deterministic and does not depend on n_splits (0 = chosen from M and
+    the device; a positive value is clamped to the number of 128-column chunks).  One kernel (bf16 split arithmetic as
+    cosine_filter's x6 form): when D is not a multiple of 32 both operands are zero-padded first.  g3 = split3_rows of the
+    (padded) gallery, computed here when not passed in; G may then be None if ginv is given with it."""
+    Q = pad_features(_f32c(Q))
+    M, D = Q.shape
+    k = int(k)
+    if g3 is None or ginv is None:
+        G = pad_features(_f32c(G))
+        assert G.shape[1] == D
+        ginv = row_inv_norm(G) if ginv is None else ginv
+        g3 = split3_rows(G) if g3 is None else g3
+    N = ginv.shape[0]
+    qinv = row_inv_norm(Q) if qinv is None else qinv
+    assert ginv.dtype == torch.float32 and ginv.is_contiguous() and qinv.dtype == torch.float32 and qinv.is_contiguous()
+    dev = Q.device
+    lib = L.load()
+    scores = torch.empty((M, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((M, k), dtype=torch.int32, device=dev)
+    ws_bytes = lib.fp_cosine_topk_workspace(M, N, k, int(n_splits))
+    ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.int64, device=dev)
+    L.check(lib.fp_cosine_topk_x6(L.ptr(Q), L.ptr(qinv), M, L.ptr(g3), L.ptr(ginv), N, D, k, int(n_splits), L.ptr(scores),
+                                  L.ptr(idx), L.ptr(ws), ws.numel() * 8, L.current_stream(dev)), "fp_cosine_topk_x6")
+    return scores, idx
+
+
+VOTE_MODES = {"top1": 0, "majority": 1}
+
+
+def topk_vote(scores, idx, labels, tau, vote="top1"):
+    """scores / idx (M, k) of cosine_topk, labels (N,) int32 per gallery row -> label (M,) int32 (-1: nobody), score (M,),
+    votes (M,) int32.  top1: the best candidate's label if its score >= tau.  majority: the label with the most candidates
+    >= tau; ties to the larger summed score, then the smaller label."""
+    if vote not in VOTE_MODES:
+        raise ValueError(f"vote must be one of {sorted(VOTE_MODES)}, got {vote!r}")
+    scores, idx, labels = scores.contiguous(), idx.contiguous(), labels.contiguous()
+    assert scores.dtype == torch.float32 and idx.dtype == torch.int32 and labels.dtype == torch.int32
+    M, k = scores.shape
+    dev = scores.device
+    label = torch.empty((M,), dtype=torch.int32, device=dev)
+    score = torch.empty((M,), dtype=torch.float32, device=dev)
+    votes = torch.empty((M,), dtype=torch.int32, device=dev)
+    L.check(L.load().fp_topk_vote(L.ptr(scores), L.ptr(idx), M, k, L.ptr(labels), labels.shape[0], float(tau),
+                                  VOTE_MODES[vote], L.ptr(label), L.ptr(score), L.ptr(votes), L.current_stream(dev)),
+            "fp_topk_vote")
+    return label, score, votes
 
 
 def l2_mean_thres(ref):

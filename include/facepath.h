@@ -629,6 +629,35 @@ int fp_cosine_filter_x6(const float* G, const float* ginv, int64_t M,
                         uint64_t* packed, void* stream);
 
 /*
+ * Top-k cosine search against an enrolled gallery (build-defined; the reference has no counterpart).  S = Q G^T with the
+ * arithmetic of fp_cosine_filter_x6: G3 = fp_split3_rows(G) (D a multiple of 32), score[m][n] = <Q[m], G[n]> * qinv[m] * ginv[n].
+ * Per query row the k largest scores in descending order and their gallery rows: scores [M][k] fp32, idx [M][k] int32; on
+ * equal scores the lower gallery index first.  A gallery row with ginv == 0 is excluded (masking: padding, removed rows);
+ * slots beyond the number of valid rows hold -inf / -1.  S is never materialised: a workgroup keeps a running top-k per row
+ * over a contiguous range of 128-column chunks (one of n_splits ranges) and a second kernel merges the n_splits lists of a
+ * row.  n_splits == 0: chosen from M and the number of CUs; a positive value is honoured, clamped to the number of chunks.
+ * The result is deterministic and the same for every n_splits.  workspace: fp_cosine_topk_workspace(M, N, k, n_splits) bytes
+ * of device memory, 8-byte aligned (M * n_splits * k keys; for n_splits == 0 a bound on what the launcher may choose; 0 for
+ * arguments fp_cosine_topk_x6 refuses; it grows with M, k and n_splits).  1 <= k <= FP_TOPK_MAX.  Refusals: a NULL pointer, k out of range,
+ * N <= 0, n_splits < 0 or a workspace that is too small: FP_ERR_INVALID_ARG; D % 32 or Q / G3 / ginv not 16-byte aligned:
+ * FP_ERR_ALIGNMENT.  M == 0: FP_OK, nothing launched.
+ */
+#define FP_TOPK_MAX 16
+size_t fp_cosine_topk_workspace(int64_t M, int N, int k, int n_splits);
+int fp_cosine_topk_x6(const float* Q, const float* qinv, int64_t M, const void* G3, const float* ginv, int N, int D, int k,
+                      int n_splits, float* scores, int32_t* idx, void* workspace, size_t ws_bytes, void* stream);
+
+/*
+ * Identity of every row of a top-k result (one thread per row).  labels [N] int32: the label of every gallery row.  A
+ * candidate counts when its index is >= 0 and its score >= tau.  mode 0 (top-1): the label of the best candidate if it
+ * counts, else -1.  mode 1 (majority): the label with the most counting candidates; ties go to the larger summed score, then
+ * to the smaller label id; -1 when none counts.  out_score: the best score among the winning label's candidates, or the row's
+ * best score when the label is -1; out_votes: the winner's vote count (0 for -1).
+ */
+int fp_topk_vote(const float* scores, const int32_t* idx, int64_t M, int k, const int32_t* labels, int N, float tau, int mode,
+                 int32_t* out_label, float* out_score, int32_t* out_votes, void* stream);
+
+/*
  * get_ref_mean_vec_and_thres_from_imgs (sff/filter_faces_using_reference.py:71-100):
  * mean over the R reference rows, thres = max_i ||mean - f_i||_2.  out_mean [D], out_thres [1].
  */

@@ -72,6 +72,7 @@ FRAME_MIN_W, FRAME_MAX_W, FRAME_MAX_H = 3, 32767, 65535   # fp_frame_desc sizes 
 RAGGED_U8, RAGGED_F32_LUT = 0, 1                           # fp_resize_ragged output modes
 TOPK_MAX = 16                                              # FP_TOPK_MAX: largest k of fp_cosine_topk_x6
 ALIGN_SIZE, ALIGN_DEGENERATE = 112, 1                      # fp_align_warp canvas side, fp_dets_to_crops_aligned flag
+DETEVAL_MAX_THRS, DETEVAL_MAX_RECS = 31, 1024              # FP_DETEVAL_MAX_*: IoU / recall thresholds fp_det_match / fp_pr_accumulate take
 
 
 class FpJpegInfo(C.Structure):
@@ -191,6 +192,9 @@ SIGNATURES = {
     "fp_mtcnn_nms": (_I, [_P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _SZ, _P]),
     "fp_dets_to_crops_px": (_I, [_P, _P, _I, _I, _I, _P, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "fp_tracker_step": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _F, _F, _P, _P, _P]),
+    "fp_det_match_workspace": (_SZ, [_I64, _I]),
+    "fp_det_match": (_I, [_P, _P, _P, _P, _P, _I, _I64, _I64, _P, _I, _P, _I, _P, _P, _P, _P, _SZ, _P]),
+    "fp_pr_accumulate": (_I, [_P, _P, _P, _P, _I64, _P, _I, _I, _P, _I, _P, _I, _P, _P, _P]),
 }
 
 _lib = None

@@ -1036,6 +1036,50 @@ int fp_mtcnn_nms(const float* boxes, const float* scores, const int32_t* seg /*d
                  float thr, int mode, int32_t* keep_idx, int32_t* keep_count, void* scratch, size_t scratch_bytes,
                  void* stream);
 
+/* ------------------------------------------------------------------------- */
+/* Detector evaluation: COCO-style bbox AP / AR (build-defined)      */
+/* ------------------------------------------------------------------------- */
+
+/*
+ * The published COCO bbox procedure for one category without crowd boxes, restated (pycocotools is not in the reference
+ * tree; face_detection_and_recognition_amd/evaluation.py states the same procedure in numpy fp64 and is the oracle).  All
+ * boxes are xywh fp64; IoU = i / (dw dh + gw gh - i) in fp64 without contraction, 0 when the intersection's width or height
+ * is <= 0.
+ *
+ * fp_det_match: greedy matching of every image's detections against its ground truth, for n_areas area ranges and n_thrs
+ * IoU thresholds in one launch (one workgroup per (image, area range), no host synchronisation).  gt_off / dt_off
+ * [n_images + 1] int32 are CSR offsets into gt_boxes [n_gt][4] / gt_area [n_gt] and dt_boxes [n_dt][4]; an image's
+ * detections are already in descending stable score order and cut to the largest maxDet.  area_rngs [n_areas][2] = (lo, hi):
+ * a GT is ignored in a range when area < lo or area > hi.  Per detection in order, at threshold t: among the GTs that are
+ * not ignored and not yet matched at t, the one with the largest IoU >= min(t, 1 - 1e-10), on equal IoU the LATER one;
+ * failing that the same among the ignored GTs (the detection is then matched AND ignored); a detection left unmatched is
+ * ignored when its own w h lies outside the range.  Outputs: matched / ignored [n_areas][n_thrs][n_dt] uint8, npig
+ * [n_areas] int32 = GTs not ignored (zeroed here, summed with integer atomics).  workspace: fp_det_match_workspace(n_gt,
+ * n_areas) bytes of device memory, 4-byte aligned.  Any number of GTs and detections per image, zero included; the
+ * result does not depend on scheduling.  1 <= n_thrs <= FP_DETEVAL_MAX_THRS.  Refusals: a NULL pointer that is needed,
+ * a count out of range, n_gt or n_dt >= 2^31, a workspace that is too small: FP_ERR_INVALID_ARG; a misaligned array:
+ * FP_ERR_ALIGNMENT.
+ *
+ * fp_pr_accumulate: precision [n_thrs][n_recs][n_areas][n_maxdets] and recall [n_thrs][n_areas][n_maxdets] (fp64), one
+ * workgroup per (threshold, area range, maxDet m) curve.  order [n_dt] int64 = the stable descending score order of the
+ * n_dt detections fp_det_match saw (indices into its flag arrays), rank_sorted [n_dt] int32 = the per-image rank of
+ * order[j].  A curve takes the detections with rank < m that are not ignored, in that order: tp / fp are exact integer
+ * running counts, rc = tp / npig, pr = tp / (fp + tp + 2^-52), pr is replaced by its suffix maximum, and for every
+ * recall threshold r precision = pr at the first index with rc >= r (0 if there is none); recall = the last rc (0
+ * without detections).  npig[a] == 0: the cell's precision and recall are -1.  Every output element is written.
+ * 1 <= n_recs <= FP_DETEVAL_MAX_RECS.
+ */
+#define FP_DETEVAL_MAX_THRS 31
+#define FP_DETEVAL_MAX_RECS 1024
+size_t fp_det_match_workspace(int64_t n_gt, int n_areas);
+int fp_det_match(const double* gt_boxes, const double* gt_area, const int32_t* gt_off, const double* dt_boxes,
+                 const int32_t* dt_off, int n_images, int64_t n_gt, int64_t n_dt, const double* iou_thrs, int n_thrs,
+                 const double* area_rngs, int n_areas, uint8_t* matched, uint8_t* ignored, int32_t* npig, void* workspace,
+                 size_t ws_bytes, void* stream);
+int fp_pr_accumulate(const uint8_t* matched, const uint8_t* ignored, const int64_t* order, const int32_t* rank_sorted,
+                     int64_t n_dt, const int32_t* npig, int n_thrs, int n_areas, const int32_t* max_dets, int n_maxdets,
+                     const double* rec_thrs, int n_recs, double* precision, double* recall, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

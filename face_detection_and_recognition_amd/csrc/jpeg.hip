@@ -8,7 +8,9 @@
 //   host    marker parsing + Huffman decoding (inherently serial per scan) -> quantised DCT coefficients, int16
 //           (fp_jpeg_parse, fp_jpeg_entropy_decode: plain C, no GPU; callers run one thread per image)
 //   device  dequantisation + 8 x 8 inverse DCT (jidctint.c's "islow" integer transform, the library's default), fancy
-//           (triangle-filter) chroma upsampling for 4:2:0 / 4:2:2 (jdsample.c h2v2_fancy_upsample / h2v1_fancy_upsample),
+//           (triangle-filter) chroma upsampling for 4:2:0 / 4:2:2 (jdsample.c h2v2_fancy_upsample / h2v1_fancy_upsample) where
+//           the chroma plane is more than 2 samples wide and plain replication (h2v2_upsample / h2v1_upsample) where it is
+//           not -- jinit_upsampler's rule: fancy only for downsampled_width > 2 --,
 //           YCbCr -> RGB in 16-bit fixed point (jdcolor.c) -> interleaved u8 RGB or BGR frame (fp_jpeg_reconstruct)
 // All three device stages are integer arithmetic restated from the library's published algorithm; the result is compared
 // byte for byte with Pillow's decode (libjpeg-turbo) of the reference's own test images (tests/golden/jpeg, tests/test_jpeg.py).
@@ -104,10 +106,15 @@ struct BitReader {
       if (!marker && p < end) {
         v = *p;
         if (v == 0xff) {
-          const unsigned n = p + 1 < end ? p[1] : 0xd9;
-          if (n == 0) p += 2;                  // stuffed zero
+          // any number of 0xff fill bytes may stand in front of a marker code (B.1.1.2); jdhuff.c's fill_bit_buffer reads
+          // on while it sees 0xff and only then tells a stuffed zero from a marker
+          const unsigned char* q = p + 1;
+          while (q < end && *q == 0xff) ++q;
+          const unsigned n = q < end ? *q : 0xd9;
+          if (n == 0) p = q + 1;               // stuffed zero
           else {
-            marker = (int)n;                   // RSTn / EOI / ...: stop consuming, feed zeros
+            marker = (int)n;                   // RSTn / EOI / ...: stop consuming (p: the 0xff in front of the code), feed zeros
+            p = q - 1;
             v = 0;
           }
         } else {
@@ -558,15 +565,17 @@ __global__ __launch_bounds__(64) void jpeg_idct_kernel(const short* coefs, unsig
   }
 }
 
-// chroma sample for output pixel (oy, ox) by libjpeg's fancy upsampling (jdsample.c); plane row pitch = pitch, the
-// component's true size = cw x ch (edges replicate inside it)
+// chroma sample for output pixel (oy, ox) by libjpeg's upsampling (jdsample.c); plane row pitch = pitch, the component's
+// true size = cw x ch (edges replicate inside it).  jinit_upsampler takes the fancy (triangle) filters only for
+// downsampled_width > 2; a component 1 or 2 samples wide gets plain replication (h2v1_upsample / h2v2_upsample), down as
+// well as across
 __device__ __forceinline__ int chroma_sample(const unsigned char* pl, int pitch, int cw, int ch, int oy, int ox, int hs0, int vs0) {
   if (hs0 == 1) return pl[(long)oy * pitch + ox];                      // 4:4:4 (vs0 == 1 too)
   const int cx = ox >> 1, hodd = ox & 1;
+  if (cw <= 2) return pl[(long)(vs0 == 1 ? oy : oy >> 1) * pitch + cx];   // h2v1_upsample / h2v2_upsample
   if (vs0 == 1) {                                                      // h2v1_fancy_upsample
     const unsigned char* r = pl + (long)oy * pitch;
     const int cur = r[cx];
-    if (cw == 1) return cur;
     if (!hodd) return cx == 0 ? cur : (cur * 3 + r[cx - 1] + 1) >> 2;
     return cx == cw - 1 ? cur : (cur * 3 + r[cx + 1] + 2) >> 2;
   }

@@ -6,7 +6,9 @@
 // after a few symbols (the self-synchronising scheme):
 //   unstuff    one workgroup per image: drops the 0x00 behind each 0xff, cuts the data at the first marker that is not the
 //              next expected RSTn (zero bits follow it, as BitReader::fill feeds them), records where each restart segment
-//              starts, lays the lanes out (jd_unstuff)
+//              starts, lays the lanes out (jd_unstuff).  0xff 0xff in the scan -- fill bytes, which may stand in front of
+//              any marker, an RSTn included (JPEG B.1.1.2) -- ends the device attempt: the image is handed to the host
+//              decoder (FP_JPEG_DECODE_ON_HOST), which skips them as libjpeg does; never refused, never decoded differently
 //   speculate  every lane decodes the symbols that START in its subsequence from state (block slot 0, k = 0) -- exact at a
 //              segment start -- and records its exit (bit offset, slot, k at the first boundary at or past its end) and the
 //              number of DC symbols it decoded (jd_spec)

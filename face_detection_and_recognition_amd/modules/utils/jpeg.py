@@ -81,7 +81,8 @@ def _check_entropy(entropy):
 def device_entropy_decode(datas, device, sub_bits=None, max_rounds=None):
     """The Huffman stage of a batch on the device (fp_jpeg_entropy_decode_device).  Per file: (info, int16 device coefficients)
     when the device decoded it, FP_ERR_INVALID_ARG when it proved the file damaged (fp_jpeg_entropy_decode's status), None for
-    the host path (not a sequential file the device takes, or left undecided by the device)."""
+    the host path (not a sequential file the device takes, or left undecided by the device -- a file with 0xff fill bytes in
+    front of a restart marker among them: the host decoder skips the fill bytes as libjpeg does)."""
     lib = L.load()
     sub_bits = DEVICE_SUB_BITS if sub_bits is None else sub_bits
     max_rounds = DEVICE_MAX_ROUNDS if max_rounds is None else max_rounds

@@ -709,8 +709,10 @@ int fp_tracker_step(float* feats, int* bboxes, int* count, int cap, int D, const
  * (fde/modules/utils/inference.py:68-76, fde/face_extraction/extract_faces_from_dataset.py:393-420) and Pillow return.
  * Split as hardware decoders split it: marker parsing and Huffman decoding on the HOST (serial per scan; plain C, no GPU:
  * fp_jpeg_parse, fp_jpeg_entropy_decode -- run one thread per image), everything after it on the DEVICE
- * (fp_jpeg_reconstruct: dequantisation + the "islow" integer inverse DCT of jidctint.c, fancy chroma upsampling of
- * jdsample.c for 4:2:0 / 4:2:2, YCbCr -> RGB of jdcolor.c, csrc/jpeg.hip).  Accepted: SOF0 / SOF1 (sequential) and SOF2
+ * (fp_jpeg_reconstruct: dequantisation + the "islow" integer inverse DCT of jidctint.c, the chroma upsampling of
+ * jdsample.c for 4:2:0 / 4:2:2 -- fancy (triangle) where the chroma plane is more than 2 samples wide, replication where it
+ * is not, as jinit_upsampler chooses --, YCbCr -> RGB of jdcolor.c, csrc/jpeg.hip).  Any number of 0xff fill bytes may stand
+ * in front of a marker, RSTn inside a scan included.  Accepted: SOF0 / SOF1 (sequential) and SOF2
  * (progressive: spectral selection and successive approximation), 8-bit, Huffman, any number of scans, 1 or 3 components, luma
  * sampling 1x1 / 2x1 / 2x2 with 1x1 chroma, restart intervals.  Everything else (arithmetic, lossless, 12-bit, CMYK, other
  * sampling layouts): FP_ERR_UNSUPPORTED, the caller decodes those on the host.

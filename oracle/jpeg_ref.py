@@ -5,9 +5,11 @@ The reference reads frames with cv2.imread (fde/modules/utils/inference.py:68-76
 /root/reference (opencv-python 4.11.0.86 bundles libjpeg-turbo 3.0; cv2 and tensorflow are absent offline).  What IS here is
 Pillow 12.2 with libjpeg-turbo (PIL.features: libjpeg_turbo, jpeglib 6.2 API): `decode_pil` is that library's own output on
 the same bytes -- the pin.  `reconstruct` restates the library's published default algorithm after the entropy decoder
-(jidctint.c jpeg_idct_islow, jdsample.c h2v2_fancy_upsample / h2v1_fancy_upsample, jdcolor.c ycc_rgb_convert) in numpy, so
-that the CPU suite can check the product's host-side Huffman decoder (fp_jpeg_entropy_decode) against Pillow without a GPU,
-and the GPU kernels against both."""
+(jidctint.c jpeg_idct_islow, jdsample.c h2v2_fancy_upsample / h2v1_fancy_upsample -- or h2v2_upsample / h2v1_upsample for a
+chroma plane at most 2 samples wide, jinit_upsampler's choice --, jdcolor.c ycc_rgb_convert) in numpy, so that the CPU suite
+can check the product's host-side Huffman decoder (fp_jpeg_entropy_decode) against Pillow without a GPU, and the GPU kernels
+against both.  The restatement holds by the published rule and by the comparison with Pillow on every geometry the suite
+sweeps (tests/test_jpeg_geometry.py), not by agreeing with the kernel."""
 import io
 
 import numpy as np
@@ -77,13 +79,10 @@ def _planes(info, coefs):
 
 
 def _h2v1_fancy(p):
-    """(h, cw) -> (h, 2 cw): jdsample.c h2v1_fancy_upsample."""
+    """(h, cw) -> (h, 2 cw), cw > 2: jdsample.c h2v1_fancy_upsample."""
     p = p.astype(np.int32)
     cw = p.shape[1]
     out = np.empty((p.shape[0], 2 * cw), np.int32)
-    if cw == 1:
-        out[:, 0] = out[:, 1] = p[:, 0]
-        return out
     left = np.concatenate([p[:, :1], p[:, :-1]], 1)
     right = np.concatenate([p[:, 1:], p[:, -1:]], 1)
     out[:, 0::2] = (p * 3 + left + 1) >> 2
@@ -94,7 +93,7 @@ def _h2v1_fancy(p):
 
 
 def _h2v2_fancy(p):
-    """(ch, cw) -> (2 ch, 2 cw): jdsample.c h2v2_fancy_upsample (edges replicate inside the component)."""
+    """(ch, cw) -> (2 ch, 2 cw), cw > 2: jdsample.c h2v2_fancy_upsample (edges replicate inside the component)."""
     p = p.astype(np.int32)
     ch, cw = p.shape
     above = np.concatenate([p[:1], p[:-1]], 0)
@@ -113,6 +112,16 @@ def _h2v2_fancy(p):
     return out
 
 
+def _upsample(p, v2):
+    """jdsample.c jinit_upsampler: `do_fancy = cinfo->do_fancy_upsampling && cinfo->min_DCT_scaled_size > 1`, then per
+    component h2v1 -> `if (do_fancy && compptr->downsampled_width > 2) h2v1_fancy_upsample else h2v1_upsample`, and the same
+    test for h2v2.  A component 1 or 2 samples wide is replicated (h2v1_upsample / h2v2_upsample), across AND down: the
+    whole method is swapped, not its horizontal half."""
+    if p.shape[1] > 2:
+        return _h2v2_fancy(p) if v2 else _h2v1_fancy(p)
+    return np.repeat(np.repeat(p.astype(np.int32), 2 if v2 else 1, axis=0), 2, axis=1)
+
+
 def reconstruct(info, coefs):
     """fp_jpeg_info (ctypes struct) + quantised coefficients (int16, host) -> (H, W, 3) u8 RGB."""
     H, W = info.height, info.width
@@ -123,10 +132,8 @@ def reconstruct(info, coefs):
     ch = []
     for c in (1, 2):
         p = planes[c][:info.comp_h[c], :info.comp_w[c]]
-        if info.hs[0] == 2 and info.vs[0] == 2:
-            p = _h2v2_fancy(p)
-        elif info.hs[0] == 2:
-            p = _h2v1_fancy(p)
+        if info.hs[0] == 2:
+            p = _upsample(p, info.vs[0] == 2)
         ch.append(p[:H, :W].astype(np.int32) - 128)
     cb, cr = ch
     r = y + ((91881 * cr + 32768) >> 16)

@@ -51,7 +51,9 @@ def _synthetic(rng, w, h, **kw):
 SYNTH = [(w, h, dict(quality=q, subsampling=sub, progressive=prog, **({"restart_marker_blocks": rst} if rst else {})))
          for (w, h) in ((64, 48), (67, 45), (1, 1), (17, 9), (250, 131))
          for sub in (0, 1, 2) for q, rst, prog in ((30, 0, False), (92, 3, False), (40, 0, True), (95, 3, True))] + \
-        [(33, 70, dict(quality=75, gray=True)), (33, 70, dict(quality=75, gray=True, progressive=True)), (8, 8, dict(quality=100, subsampling=2))]
+        [(33, 70, dict(quality=75, gray=True)), (33, 70, dict(quality=75, gray=True, progressive=True)), (8, 8, dict(quality=100, subsampling=2))] + \
+        [(w, h, dict(quality=90, subsampling=sub, progressive=prog))          # chroma planes 1 and 2 samples wide: replicated
+         for (w, h) in ((2, 5), (3, 16), (4, 3)) for sub in (0, 1, 2) for prog in (False, True)]
 
 
 def test_pillow_still_decodes_the_fixtures_as_recorded():
@@ -114,7 +116,9 @@ def test_jpeg_host_half_mutation_fuzz_under_asan_ubsan(tmp_path):
     with AddressSanitizer + UndefinedBehaviorSanitizer (CPU only, no device code) and feeds it truncated / bit-flipped / 0xff- and
     zero-stuffed variants of 50 small files (4:4:4 / 4:2:2 / 4:2:0 / gray, restart intervals, progressive), each input in an
     exact-size heap block: any read or write outside it, any shift or overflow the language leaves undefined, aborts the run.
-    (1.5 M inputs of the same campaign ran clean when the decoder was written; this is the 40 k regression slice.)"""
+    (1.5 M inputs of the same campaign ran clean when the decoder was written; this is the 40 k regression slice.)  Fixed seed in
+    front of each file's mutations: the sequential seeds with restart markers, two 0xff fill bytes in front of every RSTn, must
+    decode to the coefficients of the file without them."""
     import shutil
     import subprocess
     if not (os.path.exists("/opt/rocm/bin/hipcc") and os.path.exists("/opt/rocm/lib/llvm/bin/clang++") and shutil.which("nm")):
@@ -123,7 +127,7 @@ def test_jpeg_host_half_mutation_fuzz_under_asan_ubsan(tmp_path):
     for attempt in range(2):
         r = subprocess.run([os.path.join(ROOT, "tools", "fuzz", "run_jpeg_fuzz.sh"), "800", "3"], capture_output=True, text=True,
                            timeout=600, env=env)
-        report = "Sanitizer" in r.stderr or "runtime error" in r.stderr
+        report = "Sanitizer" in r.stderr or "runtime error" in r.stderr or "fixed fill-byte seed" in r.stderr
         if r.returncode == 0 or report:
             break
     if r.returncode != 0 and not report:

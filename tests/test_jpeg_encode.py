@@ -21,7 +21,9 @@ from face_detection_and_recognition_amd.modules.utils import jpeg as J
 from oracle import image_ref, jpeg_ref
 from test_jpeg import _host_decode
 
-SIZES = [(1, 1), (7, 9), (8, 8), (9, 8), (15, 17), (16, 16), (17, 16), (37, 53), (63, 65), (112, 112), (250, 17)]  # (h, w)
+SIZES = [(1, 1), (7, 9), (8, 8), (9, 8), (15, 17), (16, 16), (17, 16), (37, 53), (63, 65), (112, 112), (250, 17),  # (h, w)
+         (16, 1), (16, 2), (16, 3), (16, 4), (3, 3), (2, 5)]      # narrow crops: chroma planes 1-3 samples wide
+NARROW_SIZES = SIZES[-6:]
 QUALITIES = [1, 10, 50, 75, 90, 95, 100]
 SUBSAMPLINGS = [0, 1, 2]      # Pillow's numbering: 4:4:4, 4:2:2, 4:2:0
 KINDS = ["noise", "grey", "zero", "full", "checker", "gradient"]
@@ -98,14 +100,17 @@ def test_quality_to_dqt_matches_pillow_for_every_quality():
 
 def test_round_trip_through_the_host_decoder(lib):
     """Each encoded file decodes, through fp_jpeg_parse + fp_jpeg_entropy_decode and the oracle's reconstruction, to the pixels
-    Pillow decodes from Pillow's own file."""
-    for (h, w), q, s, kind in [((37, 53), 95, 2, "noise"), ((63, 65), 75, 1, "gradient"), ((250, 17), 50, 0, "checker"),
-                               ((1, 1), 100, 2, "full"), ((17, 16), 10, 2, "gradient")]:
+    Pillow decodes from the SAME bytes (which are Pillow's own file of the image too): five mixed cases and every narrow size at
+    every subsampling, noise content."""
+    cases = [((37, 53), 95, 2, "noise"), ((63, 65), 75, 1, "gradient"), ((250, 17), 50, 0, "checker"), ((1, 1), 100, 2, "full"),
+             ((17, 16), 10, 2, "gradient")] + [(hw, 90, s, "noise") for hw in NARROW_SIZES for s in SUBSAMPLINGS]
+    for (h, w), q, s, kind in cases:
         img = _content(kind, h, w, 3)
         data = J.encode_jpeg_batch_emulate([img], quality=q, subsampling=s, bgr=False)[0]
+        assert data == _pil(img, q, s), (h, w, q, s)
         rc, info, coefs = _host_decode(lib, data)
         assert rc == 0
-        np.testing.assert_array_equal(jpeg_ref.reconstruct(info, coefs), jpeg_ref.decode_pil(_pil(img, q, s)))
+        np.testing.assert_array_equal(jpeg_ref.reconstruct(info, coefs), jpeg_ref.decode_pil(data), err_msg=str((h, w, q, s)))
 
 
 def test_refusals(lib):

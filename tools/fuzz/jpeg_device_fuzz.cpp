@@ -5,7 +5,9 @@
 // image to the host (FP_JPEG_DECODE_ON_HOST).  A difference prints the input's index and aborts.
 //     jpeg_device_fuzz <iterations per file> <sub_bits> <max_rounds> <files ...>
 // The fixed seed of ADVICE r4 (a file cut at its SOS header + ff da 00 02) runs first: both host entries must return
-// FP_ERR_INVALID_ARG without reading past the buffer.
+// FP_ERR_INVALID_ARG without reading past the buffer.  The fixed fill-byte seed runs in front of each file's mutations: the file
+// with two 0xff in front of every RSTn must decode on the host to the coefficients of the file without them, and the emulator
+// must hand it to the host or agree.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -40,6 +42,47 @@ static int check(const unsigned char* d, size_t len, int sub_bits, int rounds, l
   return 0;
 }
 
+// The fixed fill-byte seed (JPEG B.1.1.2: any number of 0xff may stand in front of a marker): a sequential file with restart
+// markers gets two 0xff in front of every RSTn of its scan.  false: the file has no RSTn to dress (or is progressive).
+static bool fill_byte_variant(const std::vector<unsigned char>& src, std::vector<unsigned char>& out) {
+  size_t p = 2;
+  bool sequential = false;
+  while (p + 4 <= src.size() && src[p] == 0xff && src[p + 1] != 0xda) {
+    if (src[p + 1] == 0xc0 || src[p + 1] == 0xc1) sequential = true;
+    p += 2 + ((size_t)src[p + 2] << 8 | src[p + 3]);
+  }
+  if (!sequential || p + 4 > src.size() || src[p] != 0xff) return false;
+  p += 2 + ((size_t)src[p + 2] << 8 | src[p + 3]);
+  if (p > src.size()) return false;
+  out.assign(src.begin(), src.begin() + p);
+  int hits = 0;
+  for (; p < src.size(); ++p) {                // (in entropy-coded data ff dn is always a marker: a data 0xff is stuffed)
+    if (src[p] == 0xff && p + 1 < src.size() && src[p + 1] >= 0xd0 && src[p + 1] <= 0xd7) out.push_back(0xff), out.push_back(0xff), ++hits;
+    out.push_back(src[p]);
+  }
+  return hits > 0;
+}
+
+static int fill_byte_seed(const std::vector<unsigned char>& src, int sub_bits, int rounds) {
+  std::vector<unsigned char> v;
+  if (!fill_byte_variant(src, v)) return 0;
+  fp_jpeg_info a, b;
+  if (fp_jpeg_parse(src.data(), src.size(), &a) != FP_OK || a.n_coefs > (1L << 24)) return 0;
+  std::vector<int16_t> ca((size_t)a.n_coefs + 1), cb((size_t)a.n_coefs + 1);
+  if (fp_jpeg_entropy_decode(src.data(), src.size(), &a, ca.data()) != FP_OK) return 0;
+  unsigned char* d = (unsigned char*)malloc(v.size());
+  memcpy(d, v.data(), v.size());
+  const int r1 = fp_jpeg_parse(d, v.size(), &b);
+  const int r2 = r1 == FP_OK && b.n_coefs == a.n_coefs ? fp_jpeg_entropy_decode(d, v.size(), &b, cb.data()) : FP_ERR_INVALID_ARG;
+  int bad = r2 != FP_OK || memcmp(ca.data(), cb.data(), (size_t)a.n_coefs * 2) != 0;
+  if (bad) fprintf(stderr, "fixed fill-byte seed: parse %d, entropy_decode %d\n", r1, r2);
+  long n_dev = 0, n_host = 0;
+  if (!bad && check(d, v.size(), sub_bits, rounds, &n_dev, &n_host) == 2) bad = 1;
+  if (!bad && n_dev != 1) fprintf(stderr, "fixed fill-byte seed: fp_jpeg_scan_prepare refused the file\n"), bad = 1;
+  free(d);
+  return bad;
+}
+
 int main(int argc, char** argv) {
   if (argc < 5) return 2;
   const long iters = atol(argv[1]);
@@ -72,6 +115,7 @@ int main(int argc, char** argv) {
         return 1;
       }
     }
+    if (fill_byte_seed(src, sub_bits, rounds)) return 1;
     for (long it = 0; it < iters; ++it) {
       size_t len = src.size();
       const int mode = rnd() % 7;

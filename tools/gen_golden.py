@@ -331,6 +331,52 @@ def gen_jpeg():
     print("jpeg:", {k: v["shape"] for k, v in exp.items()})
 
 
+def gen_jpeg_narrow():
+    """tests/golden/jpeg/narrow: tiny JPEGs that Pillow (libjpeg-turbo's compressor) writes from seeded noise -- nothing of the
+    reference is in them -- at the widths where jdsample.c's jinit_upsampler swaps the fancy chroma upsampler for replication
+    (downsampled_width <= 2) and just above: widths 1-5 at 4:2:2 and 4:2:0, a progressive and a gray file, and one file with
+    two 0xff fill bytes in front of every RSTn (JPEG B.1.1.2).  expected.json: the sha256 of Pillow's decode of each, as in
+    tests/golden/jpeg/expected.json."""
+    import hashlib
+    import io
+    import json
+    from PIL import Image
+    from oracle import jpeg_ref
+    out = os.path.join(OUT, "jpeg", "narrow")
+    os.makedirs(out, exist_ok=True)
+    rng = np.random.default_rng(2024)
+
+    def enc(w, h, gray=False, **kw):
+        img = rng.integers(0, 256, (h, w) if gray else (h, w, 3), dtype=np.uint8)
+        b = io.BytesIO()
+        Image.fromarray(img).save(b, "JPEG", quality=90, **kw)
+        return b.getvalue()
+
+    files = {}
+    for sub, tag in ((1, "422"), (2, "420")):
+        for w in (1, 2, 3, 4, 5):
+            files[f"w{w}_h5_{tag}.jpg"] = enc(w, 5, subsampling=sub)
+    files["w3_h5_420_progressive.jpg"] = enc(3, 5, subsampling=2, progressive=True)
+    files["w3_h5_gray.jpg"] = enc(3, 5, gray=True)
+    d = enc(4, 40, subsampling=2, restart_marker_blocks=1)           # three MCUs: RST0, RST1
+    p = d.index(b"\xff\xda")
+    p += 2 + (d[p + 2] << 8 | d[p + 3])
+    scan = d[p:-2]
+    n = sum(scan.count(bytes([0xFF, 0xD0 + k])) for k in range(8))
+    for k in range(8):                                               # (in entropy-coded data ff dn is always a marker)
+        scan = scan.replace(bytes([0xFF, 0xD0 + k]), bytes([0xFF, 0xFF, 0xFF, 0xD0 + k]))
+    assert n == 2 and jpeg_ref.decode_pil(d[:p] + scan + d[-2:]).tobytes() == jpeg_ref.decode_pil(d).tobytes()
+    files["w4_h40_420_rst1_fill2.jpg"] = d[:p] + scan + d[-2:]
+    exp = {}
+    for name, data in files.items():
+        with open(os.path.join(out, name), "wb") as f:
+            f.write(data)
+        a = jpeg_ref.decode_pil(data)
+        exp[name] = {"shape": list(a.shape), "sha256_rgb": hashlib.sha256(a.tobytes()).hexdigest(), "mean": round(float(a.mean()), 4)}
+    json.dump(exp, open(os.path.join(out, "expected.json"), "w"), indent=1, sort_keys=True)
+    print("jpeg_narrow:", {k: (len(files[k]), v["shape"]) for k, v in exp.items()})
+
+
 def gen_tracker():
     """Face-tracker matching: the reference's own Net.check_if_face_exists / Net.add_face
     (fde/face_extraction/extract_and_label_faces_from_dataset.py:101-121) on seeded feature / box sequences.  The module
@@ -404,6 +450,9 @@ def gen_tracker():
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
+    if sys.argv[1:] == ["jpeg_narrow"]:     # Pillow output of synthetic arrays: needs no reference tree
+        gen_jpeg_narrow()
+        sys.exit(0)
     ns = rh.import_reference()
     which = sys.argv[1:] or ["blazeface", "mobilefacenet", "utils", "similarity", "yolo", "tracker"]
     if "blazeface" in which:

@@ -22,7 +22,7 @@ import torch.nn as nn
 
 from ... import _lib as L
 from ...plan import CompiledPlan, PlanBuilder, PlanCache, switch_key
-from ..params import ConvParams, LinearParams, _NoCompute, npy
+from ..params import ConvParams, LinearParams, PlanCacheMixin, _NoCompute, npy
 
 MEAN_BGR = (78.4263377603, 87.7689143744, 114.895847746)   # the reference's AGE_MEAN_VALUES = GENDER_MEAN_VALUES
 AGE_LIST = ['(0-2)', '(4-6)', '(8-12)', '(15-20)', '(25-32)', '(38-43)', '(48-53)', '(60-100)']
@@ -54,7 +54,7 @@ class LeviHassnerNet(_NoCompute):
         return {name: (tuple(getattr(self, name).weight.shape), tuple(getattr(self, name).bias.shape)) for name in LAYERS}
 
 
-class AgeGenderNet(nn.Module):
+class AgeGenderNet(PlanCacheMixin, nn.Module):
     """Both nets.  ``forward(x)``: (N, 3, 227, 227) float BGR pixel values (0 .. 255, the resized crop, mean NOT subtracted:
     the plan subtracts it) -> (age_probs (N, 8), gender_probs (N, 2)); with ``return_logits`` also the two logit tensors.
     HIP only: on a CPU device plan_for / forward raise."""
@@ -80,21 +80,11 @@ class AgeGenderNet(nn.Module):
                 for name, (w, b) in blobs.items():
                     getattr(sub, name).weight.copy_(torch.from_numpy(w))
                     getattr(sub, name).bias.copy_(torch.from_numpy(b))
-        net._plans.clear()
+        net._invalidate()
         return net
 
     def _device(self):
         return self.age.conv1.weight.device
-
-    def load_state_dict(self, state_dict, strict=True):
-        out = super().load_state_dict(state_dict, strict=strict)
-        self._plans.clear()
-        return out
-
-    def _apply(self, fn, *a, **k):
-        out = super()._apply(fn, *a, **k)
-        self._plans.clear()
-        return out
 
     # ---- plan ----
     def _conv1(self):

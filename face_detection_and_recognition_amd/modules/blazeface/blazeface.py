@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from ... import _lib as L
 from ...plan import Buf, CompiledPlan, PlanBuilder, PlanCache, View, switch_key
-from ..params import ConvParams, _NoCompute, npy
+from ..params import ConvParams, PlanCacheMixin, _NoCompute, npy
 from ..utils.image import letterbox_geometry
 
 
@@ -188,7 +188,7 @@ def generate_anchors(back_model=False):
     return np.asarray(rows, dtype=np.float32)
 
 
-class BlazeFace(nn.Module):
+class BlazeFace(PlanCacheMixin, nn.Module):
     """blazeface.py:71-458.  ``forward(x)`` takes the pre-processed NCHW float batch and returns ``[r, c]``
     with r (b, 896, 16) and c (b, 896, 1); ``predict_on_batch`` returns a list of (k, 17) tensors
     (ymin, xmin, ymax, xmax, 6 keypoints, score)."""
@@ -249,11 +249,6 @@ class BlazeFace(nn.Module):
         self.load_state_dict(torch.load(path, weights_only=True))
         self.eval()
 
-    def load_state_dict(self, *a, **k):
-        out = super().load_state_dict(*a, **k)
-        self._plans.clear()
-        return out
-
     def load_anchors(self, path, use_numpy=False):
         arr = np.load(path).astype(np.float32)
         self.set_anchors(arr)
@@ -264,8 +259,7 @@ class BlazeFace(nn.Module):
         self.anchors = torch.tensor(arr, dtype=torch.float32, device=self._device())
 
     def _apply(self, fn, *a, **k):
-        out = super()._apply(fn, *a, **k)
-        self._plans.clear()
+        out = super()._apply(fn, *a, **k)      # PlanCacheMixin: + _invalidate()
         if self.anchors is not None:
             self.anchors = fn(self.anchors)
         return out

@@ -17,12 +17,8 @@ import torch
 import torch.nn as nn
 
 from ... import _lib as L
-from ...plan import CompiledPlan, PlanBuilder, PlanCache, bn_affine, switch_key
-from ..params import BNParams, ConvParams, LinearParams, _NoCompute, npy
-
-
-def _affine(bn):
-    return bn_affine(npy(bn.weight), npy(bn.bias), npy(bn.running_mean), npy(bn.running_var), bn.eps)
+from ...plan import CompiledPlan, PlanBuilder, PlanCache, switch_key
+from ..params import BNParams, ConvParams, LinearParams, PlanCacheMixin, _NoCompute, bn_sb, npy
 
 
 class _RectConv(_NoCompute):
@@ -50,7 +46,7 @@ class BasicConv2d(_NoCompute):
 
     def emit(self, pb, x, out):
         """x: input View; out: the View (a channel slice, possibly) the ReLU output goes to."""
-        s, b = _affine(self.bn)
+        s, b = bn_sb(self.bn)
         pb.conv(x, npy(self.conv.weight), out, stride=self.stride, pad=self.pad, scale=s, bias=b, act=L.ACT_RELU)
         return out
 
@@ -64,7 +60,7 @@ class BasicConv2d(_NoCompute):
 def _merged_1x1(pb, x, convs, out):
     """Several 1x1 BasicConvs on the same input as ONE op (their outputs side by side in `out`)."""
     w = np.concatenate([npy(c.conv.weight) for c in convs])
-    aff = [_affine(c.bn) for c in convs]
+    aff = [bn_sb(c.bn) for c in convs]
     pb.conv(x, w, out, scale=np.concatenate([a[0] for a in aff]), bias=np.concatenate([a[1] for a in aff]),
             act=L.ACT_RELU, n_convs=len(convs))
 
@@ -193,7 +189,7 @@ class Mixed_7a(_NoCompute):
         return out
 
 
-class InceptionResnetV1(nn.Module):
+class InceptionResnetV1(PlanCacheMixin, nn.Module):
     """Inception-ResNet-v1 (facenet-pytorch's layout and ``state_dict`` keys; ``logits.*`` is not part of it).
     ``forward(x)``: (b, 3, 160, 160) float, RGB, already standardised -> (b, embedding_size), unit rows if ``normalize``."""
 
@@ -230,14 +226,7 @@ class InceptionResnetV1(nn.Module):
         for k, v in own.items():
             if k.endswith("num_batches_tracked"):
                 sd[k] = v
-        out = super().load_state_dict(sd, strict=True)
-        self._plans.clear()
-        return out
-
-    def _apply(self, fn, *a, **k):
-        out = super()._apply(fn, *a, **k)
-        self._plans.clear()
-        return out
+        return super().load_state_dict(sd, strict=True)      # PlanCacheMixin: + _invalidate()
 
     def _emit(self, N):
         """Emit the op list for batch N (host only, no GPU needed)."""
@@ -265,7 +254,7 @@ class InceptionResnetV1(nn.Module):
             x = y
         D = self.embedding_size
         o = pb.new_buf(1, 1, D)
-        s, b = _affine(self.last_bn)
+        s, b = bn_sb(self.last_bn)
         pb.embed_head(x.view(), npy(self.last_linear.weight), o.view(0, D), scale=s, bias=b, normalize=self.normalize)
         return pb, inp, o
 

@@ -7,12 +7,9 @@ import torch
 import torch.nn as nn
 
 from ... import _lib as L
-from ...plan import CompiledPlan, PlanBuilder, PlanCache, bn_affine, switch_key
-from ..params import BNParams, ConvParams, LinearParams, PReLUParams, _NoCompute, npy
-
-
-def _affine(bn):
-    return bn_affine(npy(bn.weight), npy(bn.bias), npy(bn.running_mean), npy(bn.running_var), bn.eps)
+from ...plan import CompiledPlan, PlanBuilder, PlanCache, switch_key
+from ..params import BNParams, ConvParams, LinearParams, PlanCacheMixin, PReLUParams, _NoCompute, npy
+from ..params import bn_sb as _affine      # (the name the parity tests import)
 
 
 def l2_norm(input, axis=1):
@@ -126,7 +123,7 @@ class Depth_Wise(_NoCompute, metaclass=_X6Switch):
         dw, pj, ex = self.conv_dw, self.project, self.conv
         shapes = Depth_Wise.BLOCK_SHAPES
         if shapes is None:
-            shapes = getattr(pb, "dwblock_shapes", None)
+            shapes = pb.dwblock_shapes
         if shapes is None:
             shapes = Depth_Wise.block_policy(pb.N)
         if Depth_Wise.FUSE and expanded is None and dw.k == 3 and dw.p == 1:
@@ -179,7 +176,7 @@ class Flatten(_NoCompute):
     pass
 
 
-class MobileFaceNet(nn.Module):
+class MobileFaceNet(PlanCacheMixin, nn.Module):
     """mobile_facenet.py:104-154.  ``forward(x)``: (b, 3, 112, 112) float in [-1, 1] (BGR, as
     mobile_facenet/utils.py:13-17 feeds it) -> (b, embedding_size) unit-norm embeddings."""
 
@@ -209,21 +206,10 @@ class MobileFaceNet(nn.Module):
     def _device(self):
         return self.linear.weight.device
 
-    def load_state_dict(self, *a, **k):
-        out = super().load_state_dict(*a, **k)
-        self._plans.clear()
-        return out
-
-    def _apply(self, fn, *a, **k):
-        out = super()._apply(fn, *a, **k)
-        self._plans.clear()
-        return out
-
     def _emit(self, N, H=112, W=112, block_shapes=None):
         """Emit the op list for batch N (host only, no GPU needed).  block_shapes: map sizes whose stride-1 Depth_Wise
         blocks become FP_OP_DWBLOCK (None: Depth_Wise.block_policy(N))."""
-        pb = PlanBuilder(N)
-        pb.dwblock_shapes = block_shapes
+        pb = PlanBuilder(N, dwblock_shapes=block_shapes)
         inp = pb.new_buf(H, W, 3)
         c1, c2, c23 = self.conv1, self.conv2_dw, self.conv_23
         stem_dw = False

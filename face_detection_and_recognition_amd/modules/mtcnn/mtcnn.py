@@ -26,7 +26,7 @@ import torch.nn as nn
 from ... import _lib as L
 from ...frames import RaggedFrames
 from ...plan import CompiledPlan, PlanBuilder, PlanCache, switch_key
-from ..params import ConvParams, LinearParams, PReLUParams, _NoCompute, npy
+from ..params import ConvParams, LinearParams, PlanCacheMixin, PReLUParams, _NoCompute, npy
 
 MAX_CAP = 8192                 # FP_MTCNN_MAX_CAP
 LANDMARKS = ("left_eye", "right_eye", "nose", "mouth_left", "mouth_right")
@@ -112,7 +112,7 @@ def check_params(min_face_size, factor):
         raise ValueError(f"factor = {factor} must lie in (0, 1)")
 
 
-class MTCNN(nn.Module):
+class MTCNN(PlanCacheMixin, nn.Module):
     """The three nets and the cascade.  detect_batch runs on a HIP device only."""
 
     def __init__(self, min_face_size=20, factor=0.709, thresholds=(0.6, 0.7, 0.7), cap=4096, bucket=256):
@@ -223,18 +223,8 @@ class MTCNN(nn.Module):
             out[name] = arrs
         return out
 
-    def load_state_dict(self, state_dict, strict=True):
-        out = super().load_state_dict(state_dict, strict=strict)
-        self._invalidate()
-        return out
-
-    def _apply(self, fn, *a, **k):
-        out = super()._apply(fn, *a, **k)
-        self._invalidate()
-        return out
-
     def _invalidate(self):
-        self._plans.clear()
+        super()._invalidate()
         self._tables = {}
         self._pnet_plans = {}
 

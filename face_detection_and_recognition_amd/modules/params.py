@@ -8,6 +8,8 @@ import math
 import torch
 import torch.nn as nn
 
+from ..plan import bn_affine
+
 
 class _NoCompute(nn.Module):
     def forward(self, *a, **k):
@@ -63,3 +65,28 @@ class LinearParams(_NoCompute):
 
 def npy(t):
     return t.detach().cpu().numpy()
+
+
+def bn_sb(bn):
+    """(scale, bias) of an eval-mode BatchNorm (BNParams) as the epilogue affine y = x * scale + bias."""
+    return bn_affine(npy(bn.weight), npy(bn.bias), npy(bn.running_mean), npy(bn.running_var), bn.eps)
+
+
+class PlanCacheMixin:
+    """For a network (in front of nn.Module in its bases) that keeps its compiled plans in ``self._plans`` (plan.PlanCache):
+    the plans hold packed copies of the weights, so whatever replaces or moves the parameters -- load_state_dict, .to() /
+    .cuda() through _apply -- drops them.  A network with more derived state overrides _invalidate().  The mixin holds no
+    parameter, buffer or submodule."""
+
+    def _invalidate(self):
+        self._plans.clear()
+
+    def load_state_dict(self, *a, **k):
+        out = super().load_state_dict(*a, **k)
+        self._invalidate()
+        return out
+
+    def _apply(self, fn, *a, **k):
+        out = super()._apply(fn, *a, **k)
+        self._invalidate()
+        return out

@@ -19,8 +19,8 @@ import torch
 import torch.nn as nn
 
 from ... import _lib as L
-from ...plan import CompiledPlan, PlanBuilder, PlanCache, View, bn_affine, cpad, switch_key
-from ..params import BNParams, ConvParams, _NoCompute, npy
+from ...plan import CompiledPlan, PlanBuilder, PlanCache, View, cpad, switch_key
+from ..params import BNParams, ConvParams, PlanCacheMixin, _NoCompute, bn_sb, npy
 
 # Architecture specs of the reference's in-tree yamls (y5/models/yolov5n.yaml, yolov5s.yaml, yolov5n-0.5.yaml):
 # [from, number, module, args] rows, same meaning as upstream.
@@ -70,10 +70,6 @@ def fuse_conv_and_bn_arrays(w, bn):
     return fw, fb
 
 
-def _bn_sb(bn):
-    return bn_affine(npy(bn.weight), npy(bn.bias), npy(bn.running_mean), npy(bn.running_var), bn.eps)
-
-
 class Conv(_NoCompute):
     """conv(no bias) -> BN -> SiLU; after fuse(): conv(with bias) -> SiLU (common.py:39-55)."""
 
@@ -108,7 +104,7 @@ class Conv(_NoCompute):
         if self.bn is None:
             kw["bias"] = npy(self.conv.bias)
         else:
-            kw["scale"], kw["bias"] = _bn_sb(self.bn)
+            kw["scale"], kw["bias"] = bn_sb(self.bn)
         if res is not None:
             kw.update(res=res, res_mode=L.RES_ADD_AFTER_ACT)
         pb.conv(x, npy(self.conv.weight), out, **kw)
@@ -134,7 +130,7 @@ class StemBlock(_NoCompute):
         """(scale, bias) of a Conv's epilogue: live BatchNorm affine, or (None, folded bias) after fuse()."""
         if conv.bn is None:
             return None, npy(conv.conv.bias)
-        return _bn_sb(conv.bn)
+        return bn_sb(conv.bn)
 
     def fusable(self, H, W):
         """FP_OP_YSTEM handles the block's head (stem_1 -> LDS -> stem_2a + maxpool) for these shapes."""
@@ -230,7 +226,7 @@ class C3(_NoCompute):
             if a.bn is None:
                 kw = dict(bias=np.concatenate([npy(a.conv.bias), npy(b.conv.bias)]))
             else:
-                (s1, b1), (s2, b2) = _bn_sb(a.bn), _bn_sb(b.bn)
+                (s1, b1), (s2, b2) = bn_sb(a.bn), bn_sb(b.bn)
                 kw = dict(scale=np.concatenate([s1, s2]), bias=np.concatenate([b1, b2]))
             pb.conv(x, w, cat.view(0, 2 * c_), act=L.ACT_SILU, n_convs=2, **kw)
             t = cat.view(0, c_)
@@ -289,13 +285,13 @@ class ShuffleV2Block(_NoCompute):
         fuse2 = ShuffleV2Block.FUSE and self.bf % 64 == 0 and self.bf <= 128     # dw3x3 + 1x1 of branch2 in one kernel
         if s == 2 and ShuffleV2Block.FUSE and ShuffleV2Block.FUSE_DOWN:
             b1 = self.branch1
-            if pb.shufdown(x, npy(b1[0].weight), _bn_sb(b1[1]), npy(b1[2].weight), _bn_sb(b1[3]),
-                           npy(b2[0].weight), _bn_sb(b2[1]), npy(b2[3].weight), _bn_sb(b2[4]), npy(b2[5].weight), _bn_sb(b2[6]),
+            if pb.shufdown(x, npy(b1[0].weight), bn_sb(b1[1]), npy(b1[2].weight), bn_sb(b1[3]),
+                           npy(b2[0].weight), bn_sb(b2[1]), npy(b2[3].weight), bn_sb(b2[4]), npy(b2[5].weight), bn_sb(b2[6]),
                            View(ob, oc, self.oup)) is not None:
                 return out
         if s == 1 and ShuffleV2Block.FUSE and ShuffleV2Block.FUSE_UNIT and \
-                pb.shufunit(x, npy(b2[0].weight), _bn_sb(b2[1]), npy(b2[3].weight), _bn_sb(b2[4]), npy(b2[5].weight),
-                            _bn_sb(b2[6]), View(ob, oc, self.oup)) is not None:
+                pb.shufunit(x, npy(b2[0].weight), bn_sb(b2[1]), npy(b2[3].weight), bn_sb(b2[4]), npy(b2[5].weight),
+                            bn_sb(b2[6]), View(ob, oc, self.oup)) is not None:
             return out
         if s == 1:
             first = View(x.buf, x.coff, self.bf)                                          # x1 passthrough
@@ -304,8 +300,8 @@ class ShuffleV2Block(_NoCompute):
         else:
             b1 = self.branch1
             b1out = pb.new_buf(OH, OW, self.bf)
-            sc, bi = _bn_sb(b1[1])
-            sc2, bi2 = _bn_sb(b1[3])
+            sc, bi = bn_sb(b1[1])
+            sc2, bi2 = bn_sb(b1[3])
             if ShuffleV2Block.FUSE and self.inp % 64 == 0 and self.bf <= 128:
                 # branch1: dw3x3 s2 + BN -> 1x1 + BN + SiLU as one FP_OP_DWPW (the depthwise result stays in LDS)
                 pb.dwpw(x, npy(b1[0].weight), sc, bi, None, npy(b1[2].weight), sc2, bi2, b1out.view(), s,
@@ -318,10 +314,10 @@ class ShuffleV2Block(_NoCompute):
             first = b1out.view()
             x2 = x
         t1 = pb.new_buf(x.H, x.W, self.bf)
-        sc, bi = _bn_sb(b2[1])
+        sc, bi = bn_sb(b2[1])
         pb.conv(x2, npy(b2[0].weight), t1.view(), scale=sc, bias=bi, act=L.ACT_SILU)
-        sc, bi = _bn_sb(b2[4])
-        sc2, bi2 = _bn_sb(b2[6])
+        sc, bi = bn_sb(b2[4])
+        sc2, bi2 = bn_sb(b2[6])
         if fuse2:
             # branch2 tail: dw3x3 + BN -> 1x1 + BN + SiLU -> cat + channel_shuffle in one kernel (FP_OP_DWPW with the
             # FP_RES_SHUFFLE2 epilogue): the depthwise tensor never reaches HBM
@@ -417,7 +413,7 @@ class Detect(_NoCompute):
         self.m = nn.ModuleList(ConvParams(x, self.no * self.na, 1, bias=True) for x in ch)
 
 
-class Model(nn.Module):
+class Model(PlanCacheMixin, nn.Module):
     """yolo.py:116-257.  ``forward(x)``: (b, 3, H, W) float in [0, 1], H and W multiples of 32 ->
     ``(z, heads)`` with z (b, sum(3*ny*nx), 16) decoded predictions, like the reference in eval mode."""
 
@@ -449,7 +445,7 @@ class Model(nn.Module):
         for mod in self.model.modules():
             if isinstance(mod, Conv):
                 mod.fuse()
-        self._plans.clear()
+        self._invalidate()
         return self
 
     def float(self):
@@ -460,14 +456,7 @@ class Model(nn.Module):
             for mod in self.model.modules():            # checkpoint of a fused model (Conv without bn)
                 if isinstance(mod, Conv):
                     mod.make_fused_structure()
-        out = super().load_state_dict(sd, *a, **k)
-        self._plans.clear()
-        return out
-
-    def _apply(self, fn, *a, **k):
-        out = super()._apply(fn, *a, **k)
-        self._plans.clear()
-        return out
+        return super().load_state_dict(sd, *a, **k)      # PlanCacheMixin: + _invalidate()
 
     def _device(self):
         return self.model[-1].m[0].weight.device

@@ -157,11 +157,55 @@ def split3_bf16(w):
     return np.stack([h >> 16, m >> 16, l >> 16]).astype(np.uint16)
 
 
+def _f32_blob(planes):
+    """bf16 bit patterns (uint16) in their final order -> the flat fp32-viewed blob the weight array carries (2 per float)."""
+    return np.ascontiguousarray(planes, dtype=np.uint16).reshape(-1).view(np.float32)
+
+
+def _mat(w):
+    """The fp32 matrix [O, I] of a 1x1 conv weight ([O, I, 1, 1]) or a linear weight ([O, I])."""
+    w = np.asarray(w, dtype=np.float32)
+    assert w.shape[2:] in ((), (1, 1)), w.shape
+    return w.reshape(w.shape[:2])
+
+
+def pack_kslab_x6(m):
+    """"k-slab" split-bf16 planes of an fp32 matrix m[n, K], K a multiple of 32: [K / 32][3 planes][n][32], element
+    [slab][plane][n][k'] = piece `plane` of m[n, 32 * slab + k'] (split3_bf16).  The B operand of every split GEMM
+    (include/facepath.h, "FP_OPF_SPLIT3" and the BLAZECHAIN / DWBLOCK / SHUFDOWN / SHUFUNIT / YSTEM2 parameter blocks)."""
+    m = np.asarray(m, dtype=np.float32)
+    n, K = m.shape
+    assert K % 32 == 0, (n, K)
+    return _f32_blob(split3_bf16(m).reshape(3, n, K // 32, 32).transpose(2, 0, 1, 3))
+
+
+def pack_rowblock_x6(m):
+    """"row-block" split-bf16 planes of an fp32 matrix m[g, k], both multiples of 32: [g / 32][3 planes][k / 32][32][32],
+    element [R][plane][ks][g'][k'] = piece `plane` of m[32 * R + g', 32 * ks + k'] (split3_bf16).  The expand matrices,
+    in the fragment order of the whole-block kernels (include/facepath.h, "DWBLOCK", "SHUFDOWN", "SHUFUNIT")."""
+    m = np.asarray(m, dtype=np.float32)
+    g, k = m.shape
+    assert g % 32 == 0 and k % 32 == 0, (g, k)
+    return _f32_blob(split3_bf16(m).reshape(3, g // 32, 32, k // 32, 32).transpose(1, 0, 3, 2, 4))
+
+
 def pad_vec(v, n, fill=0.0):
     v = np.asarray(v, dtype=np.float32).reshape(-1)
     out = np.full((n,), fill, dtype=np.float32)
     out[:v.shape[0]] = v
     return out
+
+
+def affine_rows(aff, c):
+    """(scale, bias) -> the rows [2][c], zero padded."""
+    return np.concatenate([pad_vec(aff[0], c), pad_vec(aff[1], c)])
+
+
+def dw_rows(w, aff, slope, c):
+    """The parameter block [12][c] of a depthwise 3x3 Conv_block: nine taps (pack_dw_weight), BN scale, BN bias, PReLU
+    slope (zeros where there is no PReLU: slope = None)."""
+    return np.concatenate([pack_dw_weight(w, c), affine_rows(aff, c),
+                           np.zeros(c, np.float32) if slope is None else pad_vec(slope, c)])
 
 
 def bn_affine(gamma, beta, mean, var, eps):
@@ -172,8 +216,10 @@ def bn_affine(gamma, beta, mean, var, eps):
 
 
 class PlanBuilder:
-    def __init__(self, N):
+    def __init__(self, N, dwblock_shapes=None):
         self.N = int(N)
+        self.dwblock_shapes = dwblock_shapes   # Mobile-FaceNet: map sizes whose Depth_Wise blocks may take the fp32 whole-block
+                                               # kernel (None: Depth_Wise.block_policy(N))
         self.ops = []
         self.wchunks = []
         self.w_floats = 0
@@ -313,6 +359,38 @@ class PlanBuilder:
                 op.flags |= bit
         return op
 
+    def _base_u8(self, kind, u8, out, OH, OW):
+        """_base for an op that reads u8 frames itself: u8 = (H, W, frame_h, frame_w, ext_index), the H x W letterbox canvas is
+        never materialised (external buffers ext_index .. ext_index + 2 = frames, tap tables, LUT; fp_plan_run_ext)."""
+        H, W, fh, fw, ext_index = u8
+        op = L.FpOp()
+        op.kind, op.N, op.H, op.W, op.OH, op.OW = kind, self.N, H, W, OH, OW
+        op.Cin, op.in_ld, op.in_ns, op.in_off = 3, 3, fh * fw * 3, ext_index
+        op.out_ld, op.out_ns, op.out_off, op.out_cmul = out.buf.ld, out.buf.ns, out.buf.off + out.coff, 1
+        if out.buf.rowpad:
+            op.flags |= L.OPF_OUT_ROWPAD
+        op.w_off = op.scale_off = op.bias_off = op.slope_off = -1
+        return op
+
+    @staticmethod
+    def _set_window(op, k, stride, pad):
+        """The op's window: k = KH = KW or (KH, KW), pad = pad_t = pad_l or (pad_t, pad_l)."""
+        op.KH, op.KW = (k, k) if np.isscalar(k) else k
+        op.stride = stride
+        op.pad_t, op.pad_l = (pad, pad) if np.isscalar(pad) else pad
+
+    @staticmethod
+    def _set_res(op, v, C=None):
+        """The op's second tensor (residual, shortcut, pooled or half-size map) = the View v, C (default: all) of its channels."""
+        op.res_ld, op.res_ns, op.res_off = v.buf.ld, v.buf.ns, v.buf.off + v.coff
+        op.res_C, op.res_H, op.res_W = v.C if C is None else C, v.H, v.W
+
+    def _epilogue(self, op, c, scale=None, bias=None, slope=None):
+        """Append the optional scale / bias / slope vectors (c channels) of a plain epilogue and set the op's three offsets."""
+        for field, v in (("scale_off", scale), ("bias_off", bias), ("slope_off", slope)):
+            if v is not None:
+                setattr(op, field, self.add_weight(pad_vec(v, c)))
+
     # ---- split-MFMA policy: which convs the split kernels (csrc/pwx6.hip) should run when they take them ----
     # Master switch of the bf16x6 split-MFMA kernels (csrc/split.h): False = every GEMM on the fp32 MFMA (the fmaf-chain
     # kernels of rounds 1-3).  Mobile-FaceNet's Depth_Wise.X6 is this attribute.
@@ -377,31 +455,23 @@ class PlanBuilder:
     def conv_weights(cls, w, cin_phys, cout_phys, flags):
         """The packed weights (at w_off) of a conv op with these flags: OIHW w for cin_phys input and cout_phys output channels."""
         cout, cin, kh, kw = w.shape
-        if flags & L.OPF_OUT_DW and flags & L.OPF_SPLIT3:
-            # FP_OPF_OUT_DW + FP_OPF_SPLIT3 (csrc/stemdw.hip): K = (tap, channel) flattened into one 32-k slab, three bf16 planes
-            # [channel tile of 16][plane][channel][32 k]
-            flat = np.zeros((cout, 32), np.float32)
-            flat[:, :kh * kw * cin] = np.asarray(w, np.float32).transpose(0, 2, 3, 1).reshape(cout, -1)     # k = (ky*3 + kx)*3 + c
-            w3 = split3_bf16(flat).reshape(3, cout // 16, 16, 32).transpose(1, 0, 2, 3)
-        elif flags & L.OPF_SPLIT3:
-            # three bf16 planes [tap * CS + cs][3][Npad][32] (include/facepath.h, FP_OPF_SPLIT3 on FP_OP_CONV): K runs
-            # over (tap, 32-channel slab), zero rows / columns in the padding of Cin to 32 and Cout to whole chunks
-            cs = (cin_phys + 31) // 32
-            npad = cls.x6_tiles(cout_phys)[1]
-            if cin_phys < 32:      # flat: k = tap * Cin_phys + channel, slabs of 32 consecutive k, zero rows behind the last tap
-                nsl = (kh * kw * cin_phys + 31) // 32
-                flat = np.zeros((npad, nsl * 32), np.float32)
-                wt = np.zeros((cout, kh * kw, cin_phys), np.float32)
-                wt[:, :, :cin] = np.asarray(w, np.float32).reshape(cout, cin, kh * kw).transpose(0, 2, 1)
-                flat[:cout, :kh * kw * cin_phys] = wt.reshape(cout, -1)
-                w3 = split3_bf16(flat).reshape(3, npad, nsl, 32).transpose(2, 0, 1, 3)       # [slab][plane][n][32]
-            else:
-                full = np.zeros((kh * kw, npad, cs * 32), np.float32)
-                full[:, :cout, :cin] = np.asarray(w, np.float32).reshape(cout, cin, kh * kw).transpose(2, 0, 1)
-                w3 = split3_bf16(full).reshape(3, kh * kw, npad, cs, 32).transpose(1, 3, 0, 2, 4)
-        else:
+        if not flags & L.OPF_SPLIT3:
             return pack_conv_weight(w, cin_phys, cout_phys)
-        return np.ascontiguousarray(w3).reshape(-1).view(np.float32)
+        taps = np.asarray(w, np.float32).reshape(cout, cin, kh * kw).transpose(0, 2, 1)        # [cout][tap][channel]
+        if flags & L.OPF_OUT_DW:
+            # csrc/stemdw.hip: k = tap * 3 + channel in ONE 32-k slab, planes [channel tile of 16][plane][16][32]
+            flat = np.zeros((cout, 32), np.float32)
+            flat[:, :kh * kw * cin] = taps.reshape(cout, -1)
+            return _f32_blob(split3_bf16(flat).reshape(3, cout // 16, 16, 32).transpose(1, 0, 2, 3))
+        # FP_OPF_SPLIT3 on FP_OP_CONV (include/facepath.h): k = tap * pitch + channel with pitch = Cin_phys below 32 channels
+        # (flat) and Cin padded to whole 32-channel slabs from there on (per tap: [tap][slab][3][Npad][32] is the k-slab
+        # layout of that k); zeros behind the last k and in the padding of Cout to whole chunks
+        pitch = cin_phys if cin_phys < 32 else round_up(cin_phys, 32)
+        wt = np.zeros((cout, kh * kw, pitch), np.float32)
+        wt[:, :, :cin] = taps
+        full = np.zeros((cls.x6_tiles(cout_phys)[1], round_up(kh * kw * pitch, 32)), np.float32)
+        full[:cout, :kh * kw * pitch] = wt.reshape(cout, -1)
+        return pack_kslab_x6(full)
 
     def conv(self, x, w, out, stride=1, pad=(0, 0), scale=None, bias=None, slope=None,
              act=L.ACT_NONE, res=None, res_mode=L.RES_NONE, n_convs=1, out_dw=None):
@@ -422,21 +492,16 @@ class PlanBuilder:
             op = self._base(L.OP_CONV, x, out, out.H, out.W)
             op.flags |= flags
             op.Cout = out.C
-            op.KH, op.KW, op.stride = kh, kw, stride
-            op.pad_t, op.pad_l = pad
+            self._set_window(op, (kh, kw), stride, pad)
             op.act, op.res_mode = act, res_mode
             if cin == 3 and x.C == 4 and x.buf.ld == 4:   # 3-channel image padded to 16-byte pixels: the pad channel's weights are zero
                 op.flags |= L.OPF_IN_C3
             self._offsets(op, True, scale is not None, bias is not None, slope is not None)
             if flags & L.OPF_IN_UP2:
-                u = x.up
-                assert u.cmul == 1 and not u.buf.rowpad, "the op reads the half-size map as a dense slice"
-                op.res_ld, op.res_ns, op.res_off = u.buf.ld, u.buf.ns, u.buf.off + u.coff
-                op.res_C, op.res_H, op.res_W = u.C, u.H, u.W
+                assert x.up.cmul == 1 and not x.up.buf.rowpad, "the op reads the half-size map as a dense slice"
+                self._set_res(op, x.up)
             elif res_mode != L.RES_NONE:
-                op.res_ld, op.res_ns, op.res_off = res.buf.ld, res.buf.ns, res.buf.off + res.coff
-                op.res_C = min(res.C, out.C)
-                op.res_H, op.res_W = res.H, res.W
+                self._set_res(op, res, min(res.C, out.C))
             return op
 
         flags = 0
@@ -454,19 +519,10 @@ class PlanBuilder:
             self.materialise_up(x)
         op = make(flags)
         op.w_off = self.add_weight(self.conv_weights(w, x.C, out.C, op.flags))
-        if scale is not None:
-            op.scale_off = self.add_weight(pad_vec(scale, out.C, 0.0))
-        if bias is not None:
-            op.bias_off = self.add_weight(pad_vec(bias, out.C, 0.0))
-        if out_dw is not None:
-            # the conv's slopes followed by the depthwise block [12][Cout]: nine taps, BN scale, BN bias, PReLU slope
-            dw_w, dw_aff, dw_slope = out_dw
-            assert tuple(dw_w.shape) == (out.C, 1, 3, 3)
-            op.slope_off = self.add_weight(np.concatenate([pad_vec(slope, out.C, 0.0), pack_dw_weight(dw_w, out.C),
-                                                           pad_vec(dw_aff[0], out.C), pad_vec(dw_aff[1], out.C),
-                                                           pad_vec(dw_slope, out.C)]))
-        elif slope is not None:
-            op.slope_off = self.add_weight(pad_vec(slope, out.C, 0.0))
+        self._epilogue(op, out.C, scale, bias, slope if out_dw is None else None)
+        if out_dw is not None:     # the conv's slopes followed by the depthwise block
+            assert tuple(out_dw[0].shape) == (out.C, 1, 3, 3)
+            op.slope_off = self.add_weight(np.concatenate([pad_vec(slope, out.C), dw_rows(*out_dw, out.C)]))
         self.ops.append(op)
         # n_convs > 1: several reference convs on the same input merged into one op (their outputs concatenated): the
         # op-granular model counts the input once per conv
@@ -480,16 +536,10 @@ class PlanBuilder:
         assert c <= x.C and out.C == x.C and out.cmul == 1
         op = self._base(L.OP_DWCONV, x, out, out.H, out.W)
         op.Cout = x.C
-        op.KH, op.KW, op.stride = kh, kw, stride
-        op.pad_t, op.pad_l = pad
+        self._set_window(op, (kh, kw), stride, pad)
         op.act = act
         op.w_off = self.add_weight(pack_dw_weight(w, x.C))
-        if scale is not None:
-            op.scale_off = self.add_weight(pad_vec(scale, x.C, 0.0))
-        if bias is not None:
-            op.bias_off = self.add_weight(pad_vec(bias, x.C, 0.0))
-        if slope is not None:
-            op.slope_off = self.add_weight(pad_vec(slope, x.C, 0.0))
+        self._epilogue(op, x.C, scale, bias, slope)
         self.ops.append(op)
         self.alg_bytes.append(4 * self.N * (x.H * x.W * c + out.H * out.W * c))
         return out
@@ -498,9 +548,7 @@ class PlanBuilder:
         """The FP_OP_BLAZEBLOCK op of a cin -> out.C block on view x, weights not yet packed (blazeblock(); probe())."""
         op = self._base(L.OP_BLAZEBLOCK, x, out, out.H, out.W)
         op.Cout = out.C
-        op.KH = op.KW = 3
-        op.stride = stride
-        op.pad_t = op.pad_l = 1 if stride == 1 else 0
+        self._set_window(op, 3, stride, 1 if stride == 1 else 0)
         op.res_C = min(cin, x.C)
         self._offsets(op, True, True, True, True)
         return op
@@ -525,44 +573,20 @@ class PlanBuilder:
         packed (blazepair(), blazepair_s2(); probe())."""
         op = self._base(L.OP_BLAZEPAIR, x, out, out.H, out.W)
         op.Cout = out.C
-        op.KH = op.KW = 3
-        op.stride = stride
-        op.pad_t = op.pad_l = 1 if stride == 1 else 0
-        op.act, op.res_C = L.ACT_RELU, 24
+        self._set_window(op, 3, stride, 1 if stride == 1 else 0)
+        op.act = L.ACT_RELU
         op.res_mode = L.RES_ADD_BEFORE_ACT if stride == 1 else L.RES_POOL2_BEFORE_ACT
-        op.res_ld, op.res_ns, op.res_off, op.res_H, op.res_W = op.in_ld, op.in_ns, op.in_off, x.H, x.W
+        self._set_res(op, x, 24)      # the shortcut view IS the input view
         self._offsets(op, True, True, True, True)
         return op
 
-    def blazepair(self, x, blocks, out):
-        """Two consecutive stride-1 24 -> 24 BlazeBlocks (blazeface.py:12-47) as ONE op (FP_OP_BLAZEPAIR): blocks =
-        ((dw_w, dw_b, pw_w, pw_b), (dw_w, dw_b, pw_w, pw_b)); the tensor between them never reaches HBM.  None (nothing
-        emitted) if the launcher refuses the op (csrc/blazepair.hip: a row-padded map 128 or 64 pixels wide)."""
-        assert len(blocks) == 2
-        for wd, bd, wp, bp in blocks:
-            assert wd.shape == (24, 1, 3, 3) and wp.shape[:2] == (24, 24)
-        op = self.blazepair_op(x, out, 1)
-        if self.probe(op) is None:
-            return None
-        op.w_off = self.add_weight(np.concatenate([pack_dw_weight(b[0], 24) for b in blocks]))
-        op.scale_off = self.add_weight(np.concatenate([pad_vec(b[1], 24) for b in blocks]))
-        op.slope_off = self.add_weight(np.concatenate([pack_conv_weight(b[2], 24, 24) for b in blocks]))
-        op.bias_off = self.add_weight(np.concatenate([pad_vec(b[3], 24) for b in blocks]))
-        self.ops.append(op)
-        pix = out.H * out.W
-        self.alg_bytes.append(2 * 4 * self.N * pix * 24 * 4)      # SURVEY 8(d): two blocks, four tensor passes each
-        return out
-
-    def blazepair_s2(self, x, blocks, out):
-        """A stride-1 24 -> 24 BlazeBlock and the STRIDE-2 BlazeBlock behind it (blazeface.py:12-47) as ONE op (FP_OP_BLAZEPAIR
-        with stride = 2): blocks = ((dw_w, dw_b, pw_w, pw_b) of the stride-1 block, the same of the stride-2 block); the
-        full-size tensor between them never reaches HBM, `out` is the half-size map (dense or row-padded, ld = its channels).
-        None (nothing emitted) if the launcher refuses the op (csrc/blazepairs2.hip)."""
+    def _blazepair(self, x, blocks, out, stride, alg_bytes):
+        """blazepair() / blazepair_s2(): the second block has this stride and wp2.shape[0] outputs (24 at stride 1)."""
         (wd1, bd1, wp1, bp1), (wd2, bd2, wp2, bp2) = blocks
         cout2 = wp2.shape[0]
         assert wd1.shape == (24, 1, 3, 3) and wp1.shape[:2] == (24, 24) and wd2.shape == (24, 1, 3, 3) and wp2.shape[1] == 24
-        assert out.C == cout2
-        op = self.blazepair_op(x, out, 2)
+        assert cout2 == 24 if stride == 1 else out.C == cout2
+        op = self.blazepair_op(x, out, stride)
         if self.probe(op) is None:
             return None
         op.w_off = self.add_weight(np.concatenate([pack_dw_weight(wd1, 24), pack_dw_weight(wd2, 24)]))
@@ -570,25 +594,37 @@ class PlanBuilder:
         op.slope_off = self.add_weight(np.concatenate([pack_conv_weight(wp1, 24, 24), pack_conv_weight(wp2, 24, cout2)]))
         op.bias_off = self.add_weight(np.concatenate([pad_vec(bp1, 24), pad_vec(bp2, cout2)]))
         self.ops.append(op)
-        pix, opix = x.H * x.W, out.H * out.W
-        # the stride-1 block's four tensor passes + the stride-2 block's (input, dw output, 1x1 input, output)
-        self.alg_bytes.append(4 * self.N * (pix * 24 * 4 + pix * 24 + opix * 24 + opix * 24 + opix * cout2))
+        self.alg_bytes.append(alg_bytes)
         return out
+
+    def blazepair(self, x, blocks, out):
+        """Two consecutive stride-1 24 -> 24 BlazeBlocks (blazeface.py:12-47) as ONE op (FP_OP_BLAZEPAIR): blocks =
+        ((dw_w, dw_b, pw_w, pw_b), (dw_w, dw_b, pw_w, pw_b)); the tensor between them never reaches HBM.  None (nothing
+        emitted) if the launcher refuses the op (csrc/blazepair.hip: a row-padded map 128 or 64 pixels wide)."""
+        pix = out.H * out.W
+        return self._blazepair(x, blocks, out, 1, 2 * 4 * self.N * pix * 24 * 4)      # SURVEY 8(d): two blocks, four tensor passes each
+
+    def blazepair_s2(self, x, blocks, out):
+        """A stride-1 24 -> 24 BlazeBlock and the STRIDE-2 BlazeBlock behind it (blazeface.py:12-47) as ONE op (FP_OP_BLAZEPAIR
+        with stride = 2): blocks = ((dw_w, dw_b, pw_w, pw_b) of the stride-1 block, the same of the stride-2 block); the
+        full-size tensor between them never reaches HBM, `out` is the half-size map (dense or row-padded, ld = its channels).
+        None (nothing emitted) if the launcher refuses the op (csrc/blazepairs2.hip)."""
+        pix, opix, cout2 = x.H * x.W, out.H * out.W, blocks[1][2].shape[0]
+        # SURVEY 8(d): the stride-1 block's four tensor passes + the stride-2 block's (input, dw output, 1x1 input, output)
+        return self._blazepair(x, blocks, out, 2, 4 * self.N * (pix * 24 * 4 + pix * 24 + opix * 24 + opix * 24 + opix * cout2))
 
     def blazechain(self, x, blocks, out):
         """A run of stride-1 96 -> 96 BlazeBlocks on the 16 x 16 map (blazeface.py:12-47,146-152) as ONE op
         (FP_OP_BLAZECHAIN): blocks = ((dw_w, dw_b, pw_w, pw_b), ...); the tensors between them never reach HBM.  The 1x1
-        weights go in as three bf16 planes (split3_bf16), one slab per 32 input channels: include/facepath.h BLAZECHAIN.
+        weights go in as k-slab planes (pack_kslab_x6): include/facepath.h BLAZECHAIN.
         None (nothing emitted) if the launcher refuses the op (csrc/blazechain.hip)."""
         for wd, bd, wp, bp in blocks:
             assert wd.shape == (96, 1, 3, 3) and wp.shape[:2] == (96, 96)
         op = self._base(L.OP_BLAZECHAIN, x, out, out.H, out.W)
         op.Cout = out.C
-        op.KH = op.KW = 3
-        op.stride = 1
-        op.pad_t = op.pad_l = 1
-        op.act, op.res_mode, op.res_C = L.ACT_RELU, L.RES_ADD_BEFORE_ACT, 96
-        op.res_ld, op.res_ns, op.res_off, op.res_H, op.res_W = op.in_ld, op.in_ns, op.in_off, x.H, x.W
+        self._set_window(op, 3, 1, 1)
+        op.act, op.res_mode = L.ACT_RELU, L.RES_ADD_BEFORE_ACT
+        self._set_res(op, x, 96)
         op.Cmid = len(blocks)
         op.flags |= L.OPF_SPLIT3
         self._offsets(op, True, False, False, False)
@@ -600,9 +636,7 @@ class PlanBuilder:
             par[:864] = pack_dw_weight(wd, 96)
             par[864:960] = pad_vec(bd, 96)
             par[960:1056] = pad_vec(bp, 96)
-            w3 = split3_bf16(np.asarray(wp, np.float32).reshape(96, 96))          # [3][cout][cin]
-            w3 = w3.reshape(3, 96, 3, 32).transpose(2, 0, 1, 3)                    # [slab][plane][cout][32]
-            chunks += [par, np.ascontiguousarray(w3).reshape(-1).view(np.float32)]
+            chunks += [par, pack_kslab_x6(_mat(wp))]
         op.w_off = self.add_weight(np.concatenate(chunks))
         self.ops.append(op)
         self.alg_bytes.append(len(blocks) * 4 * self.N * 256 * 96 * 4)     # four tensor passes per block
@@ -618,7 +652,8 @@ class PlanBuilder:
         """Fused Depth_Wise tail (mobile_facenet.py:72-85): dw3x3 stride s (+BN affine, +PReLU) -> 1x1 (+BN affine)
         [+ res], or -- with out_slope -- a depthwise Conv_block followed by a 1x1 Conv_block (BN + PReLU on both:
         conv2_dw -> conv_23.conv, mobile_facenet.py:117-118,70).  x has G (multiple of 64) channels.  The 1x1 runs on the
-        split MFMA (FP_OPF_SPLIT3) when DWPW_X6 and DWPW_X6_COUT allow it and the launcher takes the op."""
+        split MFMA (FP_OPF_SPLIT3, its weights as k-slab planes: csrc/dwpwx6.hip) when DWPW_X6 and DWPW_X6_COUT allow it and
+        the launcher takes the op."""
         G = dw_w.shape[0]
         cout, cin = pw_w.shape[0], pw_w.shape[1]
         assert cin == G == x.C and G % 64 == 0 and out.cmul == 1
@@ -635,36 +670,26 @@ class PlanBuilder:
             op.flags |= flags
             op.act2 = out_act
             op.Cout = out.C
-            op.KH = op.KW = 3
-            op.stride = stride
-            op.pad_t = op.pad_l = 1
+            self._set_window(op, 3, stride, 1)
             op.act = L.ACT_PRELU if dw_slope is not None else L.ACT_NONE
             op.w_off, op.slope_off, op.bias_off = 0, 0, 0 if out_slope is not None else -1
             if res is not None:
                 op.res_mode = L.RES_SHUFFLE2 if shuffle else L.RES_ADD_AFTER_ACT
-                op.res_ld, op.res_ns = res.buf.ld, res.buf.ns
-                op.res_off = res.buf.off + res.coff
-                op.res_C = min(res.C, out.C)
-                op.res_H, op.res_W = res.H, res.W
+                self._set_res(op, res, min(res.C, out.C))
             return op
 
         split = (self.X6 and self.DWPW_X6 and out.C == self.DWPW_X6_COUT and
                  self.probe(make(L.OPF_SPLIT3)) is not None)
         op = make(L.OPF_SPLIT3 if split else 0)
-        slope = dw_slope if dw_slope is not None else np.zeros(G, np.float32)
-        op.w_off = self.add_weight(np.concatenate([pack_dw_weight(dw_w, G), pad_vec(dw_scale, G), pad_vec(dw_bias, G),
-                                                   pad_vec(slope, G)]))
-        c4 = round_up(out.C, 4)
+        op.w_off = self.add_weight(dw_rows(dw_w, (dw_scale, dw_bias), dw_slope, G))
         if split:
-            # the 1x1 as three bf16 planes [G / 32][3][N][32] (csrc/dwpwx6.hip), then [N] BN scale, [N] BN bias
             full = np.zeros((out.C, G), np.float32)
-            full[:cout] = np.asarray(pw_w, np.float32).reshape(cout, G)
-            w3 = split3_bf16(full).reshape(3, out.C, G // 32, 32).transpose(2, 0, 1, 3)
-            op.slope_off = self.add_weight(np.concatenate([np.ascontiguousarray(w3).reshape(-1).view(np.float32),
-                                                           pad_vec(pw_scale, c4), pad_vec(pw_bias, c4)]))
+            full[:cout] = _mat(pw_w)
+            wp = pack_kslab_x6(full)
         else:
-            op.slope_off = self.add_weight(np.concatenate([pack_conv_weight(pw_w, G, out.C), pad_vec(pw_scale, c4),
-                                                           pad_vec(pw_bias, c4)]))
+            wp = pack_conv_weight(pw_w, G, out.C)
+        c4 = round_up(out.C, 4)
+        op.slope_off = self.add_weight(np.concatenate([wp, affine_rows((pw_scale, pw_bias), c4)]))
         if out_slope is not None:
             op.bias_off = self.add_weight(pad_vec(out_slope, c4))
         self.ops.append(op)
@@ -678,7 +703,9 @@ class PlanBuilder:
         (stride) + BN + PReLU -> 1x1 project + BN [+ x]; the expanded tensor stays in LDS.  *_aff = (scale, bias) of the
         eval-mode BatchNorm.  The split form (FP_OPF_SPLIT3, csrc/dwblockx6.hip) when X6 is on and the launcher takes it,
         else the fp32 form (csrc/dwblock.hip) if the caller's policy allows it (`fp32`) and the launcher takes it, else None
-        (nothing emitted)."""
+        (nothing emitted).
+        in_dw = (weights [Cin,1,3,3], (scale, bias), PReLU slope) of a depthwise 3x3 stride-1 Conv_block in front of the block,
+        computed in the kernel's prologue (FP_OPF_IN_DW: conv2_dw + conv_23 of Mobile-FaceNet); its dw_rows go to bias_off."""
         cmid, cin = e_w.shape[0], e_w.shape[1]
         cout = pw_w.shape[0]
         assert dw_w.shape == (cmid, 1, 3, 3) and pw_w.shape[1] == cmid
@@ -688,15 +715,12 @@ class PlanBuilder:
             op = self._base(L.OP_DWBLOCK, x, out, out.H, out.W)
             op.flags |= flags
             op.Cout, op.Cmid = cout, cmid
-            op.KH = op.KW = 3
-            op.stride = stride
-            op.pad_t = op.pad_l = 1
+            self._set_window(op, 3, stride, 1)
             op.act = L.ACT_PRELU
             self._offsets(op, True, True, in_dw is not None, True)
             if residual:
                 op.res_mode = L.RES_ADD_AFTER_ACT
-                op.res_ld, op.res_ns, op.res_off = op.in_ld, op.in_ns, op.in_off
-                op.res_C, op.res_H, op.res_W = cin, x.H, x.W
+                self._set_res(op, x, cin)
             return op
 
         in_flag = L.OPF_IN_DW if in_dw is not None else 0
@@ -705,36 +729,44 @@ class PlanBuilder:
         if split is None:
             return None
         op = make(split | in_flag)
-        if split:
-            # three bf16 planes per matrix, in the fragment order of dwblock_x6_kernel (include/facepath.h, DWBLOCK)
-            R = cmid // 32
-            e3 = split3_bf16(np.asarray(e_w, np.float32).reshape(cmid, cin))            # [3][g][k]
-            e3 = e3.reshape(3, R, 32, cin // 32, 32).transpose(1, 0, 3, 2, 4)            # [R][3][ks][g'][k']
-            p3 = split3_bf16(np.asarray(pw_w, np.float32).reshape(cout, cmid))           # [3][co][g]
-            p3 = p3.reshape(3, cout, R, 32).transpose(2, 0, 1, 3)                        # [R][3][co][g']
-            op.w_off = self.add_weight(np.ascontiguousarray(e3).reshape(-1).view(np.float32))
-            wp = np.ascontiguousarray(p3).reshape(-1).view(np.float32)
+        if split:      # include/facepath.h, DWBLOCK: the expand matrix in row blocks, the projection in k-slabs
+            op.w_off = self.add_weight(pack_rowblock_x6(_mat(e_w)))
+            wp = pack_kslab_x6(_mat(pw_w))
         else:
             op.w_off = self.add_weight(pack_conv_weight(e_w, cin, cmid))
             wp = pack_conv_weight(pw_w, cmid, cout)
-        rows = [pad_vec(e_aff[0], cmid), pad_vec(e_aff[1], cmid), pad_vec(e_slope, cmid), pack_dw_weight(dw_w, cmid),
-                pad_vec(dw_aff[0], cmid), pad_vec(dw_aff[1], cmid), pad_vec(dw_slope, cmid)]
-        op.scale_off = self.add_weight(np.concatenate(rows))
-        op.slope_off = self.add_weight(np.concatenate([wp, pad_vec(pw_aff[0], cout), pad_vec(pw_aff[1], cout)]))
+        op.scale_off = self.add_weight(np.concatenate([affine_rows(e_aff, cmid), pad_vec(e_slope, cmid),
+                                                       dw_rows(dw_w, dw_aff, dw_slope, cmid)]))
+        op.slope_off = self.add_weight(np.concatenate([wp, affine_rows(pw_aff, cout)]))
         pix, opix = x.H * x.W, out.H * out.W
         extra = 0
         if in_dw is not None:
-            # OPF_IN_DW: a depthwise 3x3 stride-1 Conv_block (weights [C,1,3,3], (scale, bias), PReLU slope) in front of the
-            # block, computed in the kernel's prologue (conv2_dw + conv_23 of Mobile-FaceNet); parameters [12][Cin] at bias_off
-            iw, iaff, islope = in_dw
-            assert iw.shape == (cin, 1, 3, 3)
-            op.bias_off = self.add_weight(np.concatenate([pack_dw_weight(iw, cin), pad_vec(iaff[0], cin), pad_vec(iaff[1], cin),
-                                                          pad_vec(islope, cin)]))
+            assert in_dw[0].shape == (cin, 1, 3, 3)
+            op.bias_off = self.add_weight(dw_rows(*in_dw, cin))
             extra = pix * 2 * cin
         self.ops.append(op)
         # the three convs of the block (+ the depthwise conv in front), each input once + output once
         self.alg_bytes.append(4 * self.N * (extra + pix * (cin + cmid) + (pix + opix) * cmid + opix * (cmid + cout)))
         return out
+
+    def _shuf_op(self, kind, x, out, cb, stride):
+        """The FP_OP_SHUFDOWN / FP_OP_SHUFUNIT op with branch width cb, weights not yet packed; None if X6 is off or the
+        launcher refuses it."""
+        op = self._base(kind, x, out, out.H, out.W)
+        op.Cout, op.Cmid = 2 * cb, cb
+        self._set_window(op, 3, stride, 1)
+        op.act = op.act2 = L.ACT_SILU
+        op.flags |= L.OPF_SPLIT3
+        self._offsets(op, True, False, False, False)
+        return op if self.X6 and self.probe(op) is not None else None
+
+    @staticmethod
+    def _shuf_branch2(pw1, pw1_aff, dw2, dw2_aff, pw2, pw2_aff):
+        """Branch 2 of a ShuffleV2Block in its parameter block (facepath.h "SHUFUNIT"; the tail of "SHUFDOWN"): the first 1x1
+        in row blocks + affine, the depthwise taps + affine, the second 1x1 in k-slabs + affine."""
+        cb = pw1.shape[0]
+        return [pack_rowblock_x6(_mat(pw1)), affine_rows(pw1_aff, cb), pack_dw_weight(dw2, cb), affine_rows(dw2_aff, cb),
+                pack_kslab_x6(_mat(pw2)), affine_rows(pw2_aff, cb)]
 
     def shufdown(self, x, b1_dw, b1_dw_aff, b1_pw, b1_pw_aff, pw1, pw1_aff, dw2, dw2_aff, pw2, pw2_aff, out):
         """A whole stride-2 ShuffleV2Block (y5/models/common.py:127-176) as ONE op (FP_OP_SHUFDOWN, csrc/shufdown.hip):
@@ -744,29 +776,11 @@ class PlanBuilder:
         cin, cb = x.C, pw1.shape[0]
         assert b1_dw.shape == (cin, 1, 3, 3) and b1_pw.shape[:2] == (cb, cin) and pw1.shape[:2] == (cb, cin)
         assert dw2.shape == (cb, 1, 3, 3) and pw2.shape[:2] == (cb, cb) and out.C == 2 * cb
-        op = self._base(L.OP_SHUFDOWN, x, out, out.H, out.W)
-        op.Cout, op.Cmid = 2 * cb, cb
-        op.KH = op.KW = 3
-        op.stride = 2
-        op.pad_t = op.pad_l = 1
-        op.act = op.act2 = L.ACT_SILU
-        op.flags |= L.OPF_SPLIT3
-        self._offsets(op, True, False, False, False)
-        if not self.X6 or self.probe(op) is None:
+        op = self._shuf_op(L.OP_SHUFDOWN, x, out, cb, 2)
+        if op is None:
             return None
-        ks, r = cin // 32, cb // 32
-
-        def planes(a):
-            return np.ascontiguousarray(a).reshape(-1).view(np.float32)
-        w_b1 = split3_bf16(np.asarray(b1_pw, np.float32).reshape(cb, cin)).reshape(3, cb, ks, 32).transpose(2, 0, 1, 3)   # [ks][3][co][k']
-        w_1 = split3_bf16(np.asarray(pw1, np.float32).reshape(cb, cin)).reshape(3, r, 32, ks, 32).transpose(1, 0, 3, 2, 4)  # [r][3][ks][g'][k']
-        w_2 = split3_bf16(np.asarray(pw2, np.float32).reshape(cb, cb)).reshape(3, cb, r, 32).transpose(2, 0, 1, 3)           # [r][3][co][g']
-        blob = [pack_dw_weight(b1_dw, cin), pad_vec(b1_dw_aff[0], cin), pad_vec(b1_dw_aff[1], cin),
-                planes(w_b1), pad_vec(b1_pw_aff[0], cb), pad_vec(b1_pw_aff[1], cb),
-                planes(w_1), pad_vec(pw1_aff[0], cb), pad_vec(pw1_aff[1], cb),
-                pack_dw_weight(dw2, cb), pad_vec(dw2_aff[0], cb), pad_vec(dw2_aff[1], cb),
-                planes(w_2), pad_vec(pw2_aff[0], cb), pad_vec(pw2_aff[1], cb)]
-        op.w_off = self.add_weight(np.concatenate(blob))
+        blob = [pack_dw_weight(b1_dw, cin), affine_rows(b1_dw_aff, cin), pack_kslab_x6(_mat(b1_pw)), affine_rows(b1_pw_aff, cb)]
+        op.w_off = self.add_weight(np.concatenate(blob + self._shuf_branch2(pw1, pw1_aff, dw2, dw2_aff, pw2, pw2_aff)))
         self.ops.append(op)
         pix, opix = x.H * x.W, out.H * out.W
         # the five convs of the block, each input once + output once
@@ -780,26 +794,10 @@ class PlanBuilder:
         the op."""
         cb = pw1.shape[0]
         assert pw1.shape[:2] == (cb, cb) and dw2.shape == (cb, 1, 3, 3) and pw2.shape[:2] == (cb, cb) and out.C == 2 * cb
-        op = self._base(L.OP_SHUFUNIT, x, out, out.H, out.W)
-        op.Cout, op.Cmid = 2 * cb, cb
-        op.KH = op.KW = 3
-        op.stride = 1
-        op.pad_t = op.pad_l = 1
-        op.act = op.act2 = L.ACT_SILU
-        op.flags |= L.OPF_SPLIT3
-        self._offsets(op, True, False, False, False)
-        if not self.X6 or self.probe(op) is None:
+        op = self._shuf_op(L.OP_SHUFUNIT, x, out, cb, 1)
+        if op is None:
             return None
-        ks = r = cb // 32
-
-        def planes(a):
-            return np.ascontiguousarray(a).reshape(-1).view(np.float32)
-        w_1 = split3_bf16(np.asarray(pw1, np.float32).reshape(cb, cb)).reshape(3, r, 32, ks, 32).transpose(1, 0, 3, 2, 4)   # [r][3][ks][g'][k']
-        w_2 = split3_bf16(np.asarray(pw2, np.float32).reshape(cb, cb)).reshape(3, cb, r, 32).transpose(2, 0, 1, 3)           # [r][3][co][g']
-        blob = [planes(w_1), pad_vec(pw1_aff[0], cb), pad_vec(pw1_aff[1], cb),
-                pack_dw_weight(dw2, cb), pad_vec(dw2_aff[0], cb), pad_vec(dw2_aff[1], cb),
-                planes(w_2), pad_vec(pw2_aff[0], cb), pad_vec(pw2_aff[1], cb)]
-        op.w_off = self.add_weight(np.concatenate(blob))
+        op.w_off = self.add_weight(np.concatenate(self._shuf_branch2(pw1, pw1_aff, dw2, dw2_aff, pw2, pw2_aff)))
         self.ops.append(op)
         pix = x.H * x.W
         self.alg_bytes.append(4 * self.N * pix * 6 * cb)     # SURVEY 8(d): three convs of cb channels, input once + output once each
@@ -818,31 +816,22 @@ class PlanBuilder:
                     k = 16 * (ky % 2) + 3 * kx + c
                     for co in range(24):
                         full[ky // 2, co // 16, co % 16, k] = w[co, c, ky, kx]
-        planes = split3_bf16(full)                                      # [3 planes][slab][nt][16][32]
-        blob = np.ascontiguousarray(planes.transpose(1, 2, 0, 3, 4))    # [slab][nt][plane][16][32]
-        return blob.reshape(-1).view(np.float32)
+        return _f32_blob(split3_bf16(full).transpose(1, 2, 0, 3, 4))    # [3 planes][slab][nt][16][32] -> [slab][nt][plane][16][32]
 
     def stem_u8(self, u8, w, out, pad=(0, 0), scale=None, bias=None, slope=None, act=L.ACT_NONE, split=False):
         """First conv of a network reading u8 frames itself (FP_OP_STEM_U8): KxK (3 or 5) stride 2, Cout <= 64, dense
         output buffer.  u8 = (H, W, frame_h, frame_w, ext_index): the H x W letterbox canvas is resampled from the
-        frames while the conv's input tile is staged (external buffers ext_index..+2 = frames, tap tables, LUT).
+        frames while the conv's input tile is staged (_base_u8).
         w is the [Cout, 3, K, K] weight; it is packed for a 4-channel pixel like the fp32-canvas form."""
-        H, W, fh, fw, ext_index = u8
+        H, W = u8[:2]
         cout, cin, kh, kw = w.shape
         assert cin == 3 and kh == kw and kh in (3, 5) and out.cmul == 1 and out.coff == 0 and out.buf.ld == out.C
         assert out.C <= 64 and H + W <= 2048
-        op = L.FpOp()
-        op.kind, op.N, op.H, op.W, op.OH, op.OW = L.OP_STEM_U8, self.N, H, W, out.H, out.W
-        op.Cin, op.in_ld, op.in_ns, op.in_off = 3, 3, fh * fw * 3, ext_index
-        op.Cout, op.out_ld, op.out_ns, op.out_off, op.out_cmul = out.C, out.buf.ld, out.buf.ns, out.buf.off, 1
-        if out.buf.rowpad:
-            op.flags |= L.OPF_OUT_ROWPAD
-        op.KH = op.KW = kh
-        op.stride = 2
-        op.pad_t, op.pad_l = pad
+        op = self._base_u8(L.OP_STEM_U8, u8, out, out.H, out.W)
+        op.Cout = out.C
+        self._set_window(op, kh, 2, pad)
         op.act = act
-        op.res_H, op.res_W = fh, fw
-        op.w_off = op.scale_off = op.bias_off = op.slope_off = -1
+        op.res_H, op.res_W = u8[2:4]
         if split:
             # BlazeFace's 5x5 stem on the bf16 matrix cores (FP_OPF_SPLIT3, stem5_u8_x6_kernel): the band form's shape only
             assert (kh, H, W, out.H, out.W, cout) == (5, 256, 256, 128, 128, 24) and pad == (1, 1) and scale is None
@@ -851,12 +840,7 @@ class PlanBuilder:
             op.w_off = self.add_weight(self.pack_stem5_x6(w))
         else:
             op.w_off = self.add_weight(pack_conv_weight(w, 4, out.C))
-        if scale is not None:
-            op.scale_off = self.add_weight(pad_vec(scale, out.C, 0.0))
-        if bias is not None:
-            op.bias_off = self.add_weight(pad_vec(bias, out.C, 0.0))
-        if slope is not None:
-            op.slope_off = self.add_weight(pad_vec(slope, out.C, 0.0))
+        self._epilogue(op, out.C, scale, bias, slope)
         self.ops.append(op)
         self.alg_bytes.append(4 * self.N * (H * W * 3 + out.H * out.W * cout))
         return out
@@ -864,7 +848,8 @@ class PlanBuilder:
     def ystem(self, x, w1, scale1, bias1, w2, scale2, bias2, a_out, pool_out, u8=None):
         """Head of YOLOv5-face's StemBlock (common.py:58-73) as ONE op: stem_1 (3x3 s2 p1, SiLU) stays in LDS,
         stem_2a (1x1, SiLU) -> a_out, maxpool2x2(stem_1) -> pool_out (a channel slice of stem_3's concat buffer).
-        scale1 / scale2 = None when the BatchNorm is folded into the conv (Model.fuse())."""
+        scale1 / scale2 = None when the BatchNorm is folded into the conv (Model.fuse()).
+        u8 = (H, W, frame_h, frame_w, ext_index): the op reads the u8 frames itself (FP_OP_YSTEM_U8, _base_u8) and x is None."""
         c1, c2 = w1.shape[0], w2.shape[0]
         assert w1.shape[2:] == (3, 3) and w2.shape[1] == c1 and w2.shape[2:] == (1, 1)
         assert c1 <= 32 and a_out.C <= 32 and pool_out.C >= c1 and pool_out.cmul == 1 and a_out.cmul == 1
@@ -875,36 +860,24 @@ class PlanBuilder:
             if w1.shape[1] == 3:   # 3-channel image in 16-byte pixels: the pad channel's weights are zero
                 op.flags |= L.OPF_IN_C3
         else:
-            # u8 = (H, W, frame_h, frame_w, ext_index): the H x W canvas is never materialised; the op reads the frames
-            # (external buffers ext_index .. ext_index + 2: frames, tap tables, LUT) through fp_plan_run_ext
             assert x is None
-            H, W, fh, fw, ext_index = u8
-            op = L.FpOp()
-            op.kind, op.N, op.H, op.W, op.OH, op.OW = L.OP_YSTEM_U8, self.N, H, W, H // 2, W // 2
-            op.Cin, op.in_ld, op.in_ns, op.in_off = 3, 3, fh * fw * 3, ext_index
-            op.out_ld, op.out_ns, op.out_off, op.out_cmul = a_out.buf.ld, a_out.buf.ns, a_out.buf.off + a_out.coff, 1
-            op.w_off = op.scale_off = op.bias_off = op.slope_off = -1
+            H, W = u8[:2]
+            op = self._base_u8(L.OP_YSTEM_U8, u8, a_out, H // 2, W // 2)
         H1, W1 = H // 2, W // 2
         assert H % 4 == 0 and W % 4 == 0 and (a_out.H, a_out.W) == (H1, W1) and (pool_out.H, pool_out.W) == (H1 // 2, W1 // 2)
         op.Cout = a_out.C
-        op.KH = op.KW = 3
-        op.stride = 2
-        op.pad_t = op.pad_l = 1
+        self._set_window(op, 3, 2, 1)
         op.act = L.ACT_SILU
-        op.res_ld, op.res_ns = pool_out.buf.ld, pool_out.buf.ns
-        op.res_off = pool_out.buf.off + pool_out.coff
-        op.res_C = cpad(c1)
-        op.res_H, op.res_W = (pool_out.H, pool_out.W) if u8 is None else (u8[2], u8[3])
+        self._set_res(op, pool_out, cpad(c1))
+        if u8 is not None:
+            op.res_H, op.res_W = u8[2:4]      # the frames' size
         op.w_off = self.add_weight(pack_conv_weight(w1, 4, cpad(c1)))
-        if scale1 is not None:
-            op.scale_off = self.add_weight(pad_vec(scale1, 32, 0.0))
-        op.bias_off = self.add_weight(pad_vec(bias1, 32, 0.0))
+        self._epilogue(op, 32, scale1, bias1)
         nb2 = (a_out.C + 15) // 16
         wq = np.zeros((32, nb2 * 16), np.float32)                       # [k][n], zero padded
         wq[:c1, :c2] = np.asarray(w2, np.float32).reshape(c2, c1).T
         blob = [np.ascontiguousarray(wq.reshape(2, 4, 4, nb2 * 16).transpose(0, 1, 3, 2)).reshape(-1),  # [j][g][n][e]
-                pad_vec(scale2 if scale2 is not None else np.ones(c2, np.float32), nb2 * 16, 0.0),
-                pad_vec(bias2, nb2 * 16, 0.0)]
+                affine_rows((scale2 if scale2 is not None else np.ones(c2, np.float32), bias2), nb2 * 16)]
         op.slope_off = self.add_weight(np.concatenate(blob))
         self.ops.append(op)
         self.alg_bytes.append(4 * self.N * (H * W * 3 + H1 * W1 * c1 + H1 * W1 * c1 + H1 * W1 * c2))
@@ -917,28 +890,19 @@ class PlanBuilder:
         assert w2b.shape == (32, 16, 3, 3) and w3.shape[:2] == (32, 64) and pool.cmul == 1
         op = self._base(L.OP_YSTEM2, a, out, out.H, out.W)
         op.Cout = out.C
-        op.KH = op.KW = 3
-        op.stride = 2
-        op.pad_t = op.pad_l = 1
+        self._set_window(op, 3, 2, 1)
         op.act = op.act2 = L.ACT_SILU
         op.flags |= L.OPF_SPLIT3
-        op.res_ld, op.res_ns = pool.buf.ld, pool.buf.ns
-        op.res_off = pool.buf.off + pool.coff
-        op.res_C, op.res_H, op.res_W = pool.C, pool.H, pool.W
+        self._set_res(op, pool)
         self._offsets(op, True, False, False, False)
         if not self.X6 or self.probe(op) is None:
             return None
 
-        def planes(x):
-            return np.ascontiguousarray(x).reshape(-1).view(np.float32)
-
         def aff(sb):
-            return [np.ones(32, np.float32) if sb[0] is None else pad_vec(sb[0], 32), pad_vec(sb[1], 32)]
+            return affine_rows((np.ones(32, np.float32) if sb[0] is None else sb[0], sb[1]), 32)
         k2 = np.zeros((32, 160), np.float32)                                    # k = (ky*3 + kx)*16 + c, padded to five slabs
         k2[:, :144] = np.asarray(w2b, np.float32).transpose(0, 2, 3, 1).reshape(32, 144)
-        p2 = split3_bf16(k2).reshape(3, 32, 5, 32).transpose(2, 0, 1, 3)        # [slab][3][co][k']
-        p3 = split3_bf16(np.asarray(w3, np.float32).reshape(32, 64)).reshape(3, 32, 2, 32).transpose(2, 0, 1, 3)
-        op.w_off = self.add_weight(np.concatenate([planes(p2)] + aff(aff2b) + [planes(p3)] + aff(aff3)))
+        op.w_off = self.add_weight(np.concatenate([pack_kslab_x6(k2), aff(aff2b), pack_kslab_x6(_mat(w3)), aff(aff3)]))
         self.ops.append(op)
         pix, opix = a.H * a.W, out.H * out.W
         self.alg_bytes.append(4 * self.N * (pix * 16 + opix * 32 + opix * 64 + opix * 32))   # the two convs
@@ -948,9 +912,7 @@ class PlanBuilder:
         assert out.C == x.C
         op = self._base(L.OP_MAXPOOL, x, out, out.H, out.W)
         op.Cout = x.C
-        op.KH = op.KW = k
-        op.stride = stride
-        op.pad_t = op.pad_l = pad
+        self._set_window(op, k, stride, pad)
         self.ops.append(op)
         self.alg_bytes.append(0)
         return out
@@ -988,10 +950,7 @@ class PlanBuilder:
         wp = np.zeros((d, x.C), np.float32)
         wp[:, :c] = np.asarray(w, np.float32)
         op.w_off = self.add_weight(wp)
-        if scale is not None:
-            op.scale_off = self.add_weight(pad_vec(scale, d))
-        if bias is not None:
-            op.bias_off = self.add_weight(pad_vec(bias, d))
+        self._epilogue(op, d, scale, bias)
         if normalize:
             op.flags |= L.OPF_OUT_L2
         self.ops.append(op)
@@ -1004,9 +963,7 @@ class PlanBuilder:
         assert out.C == x.C and out.cmul == 1 and x.up is None
         op = self._base(L.OP_POOL_LRN, x, out, out.H, out.W)
         op.Cout = x.C
-        op.KH = op.KW = k
-        op.stride = stride
-        op.pad_t = op.pad_l = pad
+        self._set_window(op, k, stride, pad)
         if group:
             op.Cmid, op.res_C = group, size
             op.w_off = self.add_weight(np.array([alpha, beta, lrn_k, 0.0], np.float32))
@@ -1131,7 +1088,7 @@ class CompiledPlan:
             torch.from_numpy(weights).to(self.device)
         self.arena_floats = int(arena_floats)
         # row-padded buffers rely on pads that nobody ever writes: start from zeros
-        alloc = torch.zeros if getattr(builder, "has_rowpad", False) else torch.empty
+        alloc = torch.zeros if builder.has_rowpad else torch.empty
         self.arena = alloc(self.arena_floats, dtype=torch.float32, device=self.device)
         self.lib = L.load()
         L.check(self.lib.fp_plan_validate(self.ops, self.n_ops, self.weights.numel(), self.arena_floats),
@@ -1141,7 +1098,7 @@ class CompiledPlan:
         # wrote them (the stem's kernel follows the batch) and on the pad colour / LUT behind the tap tables.  So a run is
         # windowed only if an unrestricted run of at least as many images, with the same kernels and external tables, came
         # before it; any other run is unrestricted and becomes the new record.  `prime_runs` counts those.
-        self.windows = list(getattr(builder, "windows", ()))
+        self.windows = list(builder.windows)
         self.prime_runs = 0
         self._primed = None         # (n, key) of the last unrestricted run
         self._win_key = {}          # n -> (windowed kernels, windows valid at n)

@@ -1,10 +1,24 @@
-// align.hip — five-point face alignment between detection and embedding (gfx950).  Build with -ffp-contract=off (as
-// post.hip): the landmarks follow numpy's float32 operation order and the host emulator must reproduce the device's
-// estimate and samples bit for bit.
+// align.hip — detections -> per-face crop rectangles, and five-point face alignment between detection and embedding
+// (gfx950).  Build with -ffp-contract=off: boxes and landmarks follow numpy's operation order for float32 inputs and must
+// not be contracted into fmas, and the host emulator must reproduce the device's records, estimate and samples bit for bit.
 //
-// 1. fp_dets_to_crops_aligned / _ragged: fp_dets_to_crops' kernel (crops.h, the same rows in the same order) that also
-//    writes, per face, its landmarks in frame pixels, the least-squares similarity onto the ArcFace 112 x 112 template
-//    (Umeyama's estimate, closed form in 2-D, fp64) and a flag for a degenerate landmark set.
+// 1. fp_dets_to_crops and its five siblings (_ragged, _aligned, _aligned_ragged, _px, _aligned_emulate): one kernel, one
+//    argument check (check_crops) and one launcher (launch_crops); an entry point fills the fields that differ.
+//      fmt 0: BlazeFaceModel rows (ymin,xmin,ymax,xmax,...,score@16), normalised to the model input:
+//             column reorder (blazeface/model.py:70) + get_dets_bboxes_confs_lmarks_areas (utils/inference.py:11-58).
+//      fmt 1: YOLOv5-face rows (x1,y1,x2,y2,conf@4,...) in model-input pixels: get_bboxes_confs_areas
+//             (yolov5_face/onnx/onnx_utils.py:313-340).
+//      fmt 2: MTCNN rows (x1,y1,x2,y2,(x,y) x 5,conf@14) in the FRAME's own pixels (the wrappers' input size is the image):
+//             only fp_dets_to_crops_px passes it (no geom: gain 1, pad 0); the area share is taken of the frame, as fmt 0
+//             takes it of the model input.  The entry points of fmt 0 / 1 refuse it.
+//    All: conf > det_thres, area filter (fmt 0: 100*(area/total) > thr, info[6] = fraction; fmt 1: (100*area)/total > thr,
+//    info[6] = percent -- each in its reference's operation order), scale_coords (utils/image.py:79-99: subtract pad,
+//    divide by gain, clip to the frame), round half-to-even, then the crop of
+//    face_extraction/extract_faces_from_dataset.py:289-303: int(), offsets (tx,ty,bx,by), clamp to the frame.
+//    Faces are emitted in (frame, detection) order.
+//    With lmarks / M / flags (the aligned entry points) each face also gets its landmarks in frame pixels, the least-squares
+//    similarity onto the ArcFace 112 x 112 template (Umeyama's estimate, closed form in 2-D, fp64) and a flag for a
+//    degenerate landmark set.
 //      fmt 0 (BlazeFace, bbox_lmarks of get_dets_bboxes_confs_lmarks_areas, utils/inference.py:11-58): keypoint * [iw, ih],
 //            - pad, / gain, round half-to-even, no clip.  Keypoints 0..3 (eyes, nose tip, mouth centre) -> template points
 //            0, 1, 2 and the midpoint of 3 and 4; the ears are unused.
@@ -19,9 +33,92 @@
 #include <math.h>
 
 #include "common.h"
-#include "crops.h"
 
 namespace {
+
+struct CropArgs {
+  const float* dets;
+  const int* counts;
+  int B, max_dets, row, fmt, in_w, in_h, orig_w, orig_h;
+  float det_thres, area_thres, gain, pad_x, pad_y;
+  int tx, ty, bx, by, dst_w, dst_h, max_faces;
+  fp_resize_item* items;
+  float* info;
+  int* n_faces;
+  const fp_frame_desc* descs;   // ragged batch (ABI 14): per-frame orig_w / orig_h (descs) and gain, pad_x, pad_y (geom [B][3]);
+  const float* geom;            // nullptr: the scalars above hold for every frame
+  float* lmarks;                // aligned entry points only: [max_faces][10] landmarks in frame pixels,
+  double* M;                    // [max_faces][6] frame -> template similarity,
+  int* flags;                   // [max_faces] FP_ALIGN_* flags
+};
+
+// The scale_coords / clamp geometry of one frame.
+struct FrameGeom {
+  int orig_w, orig_h;
+  float gain, pad_x, pad_y;
+};
+
+__host__ __device__ __forceinline__ FrameGeom frame_geom(const CropArgs& p, int f) {
+  if (!p.descs) return FrameGeom{p.orig_w, p.orig_h, p.gain, p.pad_x, p.pad_y};
+  const fp_frame_desc d = p.descs[f];
+  if (!p.geom) return FrameGeom{d.w, d.h, 1.f, 0.f, 0.f};   // fmt 2: rows already in frame pixels
+  return FrameGeom{d.w, d.h, p.geom[3 * f], p.geom[3 * f + 1], p.geom[3 * f + 2]};
+}
+
+// Detection rows of frame f to look at: none for a (ragged) frame with no usable geometry.
+__host__ __device__ __forceinline__ int frame_dets(const CropArgs& p, const FrameGeom& g, int f) {
+  if (g.orig_w <= 0 || g.orig_h <= 0 || !(g.gain > 0.f)) return 0;
+  return min(max(p.counts[f], 0), p.max_dets);
+}
+
+__host__ __device__ __forceinline__ bool crop_one(const CropArgs& p, const FrameGeom& g, const float* d, float& x1,
+                                                  float& y1, float& x2, float& y2, float& conf, float& perc) {
+  if (p.fmt == 0) {
+    conf = d[16];
+    if (!(conf > p.det_thres)) return false;
+    x1 = d[1] * (float)p.in_w; y1 = d[0] * (float)p.in_h; x2 = d[3] * (float)p.in_w; y2 = d[2] * (float)p.in_h;
+  } else if (p.fmt == 2) {
+    conf = d[14];
+    if (!(conf > p.det_thres)) return false;
+    x1 = d[0]; y1 = d[1]; x2 = d[2]; y2 = d[3];
+  } else {
+    conf = d[4];
+    if (!(conf > p.det_thres)) return false;
+    x1 = d[0]; y1 = d[1]; x2 = d[2]; y2 = d[3];
+  }
+  const float area = (x2 - x1) * (y2 - y1);
+  if (p.fmt == 2) {  // the wrappers' input size is the frame: inference.py:40-42 with total = the frame's area
+    perc = area / (float)(g.orig_w * g.orig_h);
+    if (!(100.f * perc > p.area_thres)) return false;
+  } else if (p.fmt == 0) {  // inference.py:40-42: perc = area / total (the FRACTION is reported), filter on 100 * perc
+    perc = area / (float)(p.in_w * p.in_h);
+    if (!(100.f * perc > p.area_thres)) return false;
+  } else {           // onnx_utils.py:329-332: perc = 100 * area / total (the PERCENT is reported and compared)
+    perc = (100.f * area) / (float)(p.in_w * p.in_h);
+    if (!(perc > p.area_thres)) return false;
+  }
+  x1 = (x1 - g.pad_x) / g.gain; x2 = (x2 - g.pad_x) / g.gain;
+  y1 = (y1 - g.pad_y) / g.gain; y2 = (y2 - g.pad_y) / g.gain;
+  x1 = fminf(fmaxf(x1, 0.f), (float)g.orig_w); x2 = fminf(fmaxf(x2, 0.f), (float)g.orig_w);
+  y1 = fminf(fmaxf(y1, 0.f), (float)g.orig_h); y2 = fminf(fmaxf(y2, 0.f), (float)g.orig_h);
+  x1 = rintf(x1); y1 = rintf(y1); x2 = rintf(x2); y2 = rintf(y2);
+  return true;
+}
+
+// The record every entry point writes (fp_dets_to_crops' items / info).
+__host__ __device__ __forceinline__ void crop_emit_box(const CropArgs& p, const FrameGeom& g, int f, int slot, float x1,
+                                                       float y1, float x2, float y2, float c, float pc) {
+  int x = (int)x1 + p.tx, y = (int)y1 + p.ty, xw = (int)x2 + p.bx, yh = (int)y2 + p.by;
+  x = max(x, 0); y = max(y, 0); xw = min(xw, g.orig_w); yh = min(yh, g.orig_h);
+  fp_resize_item it;
+  it.src_image = f;
+  it.sx = x; it.sy = y; it.sw = xw - x; it.sh = yh - y;
+  it.dx = 0; it.dy = 0; it.dw = p.dst_w; it.dh = p.dst_h;
+  if (it.sw <= 0 || it.sh <= 0) { it.dw = 0; it.dh = 0; }  // empty crop: canvas becomes pad colour
+  p.items[slot] = it;
+  float* o = p.info + (long)slot * 7;
+  o[0] = (float)f; o[1] = x1; o[2] = y1; o[3] = x2; o[4] = y2; o[5] = c; o[6] = pc;
+}
 
 constexpr int AL = FP_ALIGN_SIZE;
 // ArcFace 112 x 112 five-point template (x, y): left eye, right eye, nose tip, left / right mouth corner
@@ -98,13 +195,115 @@ __host__ __device__ int align_estimate(const float* lm, int fmt, double* M) {
   return 0;
 }
 
-template <>
-__host__ __device__ __forceinline__ void crop_emit<true>(const CropArgs& p, const FrameGeom& g, int f, const float* d, int slot,
-                                                         float x1, float y1, float x2, float y2, float c, float pc) {
+// Writes the crop record of a face crop_one accepted into slot `slot` (< max_faces); with ALIGN also its landmarks,
+// alignment transform and flags.
+template <bool ALIGN>
+__host__ __device__ __forceinline__ void crop_emit(const CropArgs& p, const FrameGeom& g, int f, const float* d, int slot,
+                                                   float x1, float y1, float x2, float y2, float c, float pc) {
   crop_emit_box(p, g, f, slot, x1, y1, x2, y2, c, pc);
-  float* lm = p.lmarks + (long)slot * 10;
-  crop_lmarks(p, g, d, lm);
-  p.flags[slot] = align_estimate(lm, p.fmt, p.M + (long)slot * 6);
+  if (ALIGN) {
+    float* lm = p.lmarks + (long)slot * 10;
+    crop_lmarks(p, g, d, lm);
+    p.flags[slot] = align_estimate(lm, p.fmt, p.M + (long)slot * 6);
+  }
+}
+
+// The faces among the first n rows of frame f, in order, into slots slot, slot + 1, ... (written while < max_faces, counted
+// beyond): the kernel's emit pass and the whole of the host emulator.  Returns the slot after the frame's last face.
+template <bool ALIGN>
+__host__ __device__ int crop_frame(const CropArgs& p, const FrameGeom& g, int f, int n, int slot) {
+  const float* D = p.dets + (long)f * p.max_dets * p.row;
+  for (int i = 0; i < n; ++i) {
+    float x1, y1, x2, y2, c, pc;
+    if (!crop_one(p, g, D + (long)i * p.row, x1, y1, x2, y2, c, pc)) continue;
+    if (slot < p.max_faces) crop_emit<ALIGN>(p, g, f, D + (long)i * p.row, slot, x1, y1, x2, y2, c, pc);
+    ++slot;
+  }
+  return slot;
+}
+
+// One workgroup over all frames: a per-frame count pass, a block scan, then each frame's faces in order.
+template <bool ALIGN>
+__global__ __launch_bounds__(256) void dets_to_crops_kernel(CropArgs p) {
+  __shared__ int scan[256];
+  __shared__ int base_s;
+  const int tid = threadIdx.x;
+  if (tid == 0) base_s = 0;
+  __syncthreads();
+  for (int f0 = 0; f0 < p.B; f0 += 256) {
+    const int f = f0 + tid;
+    int n = 0, cnt = 0;
+    FrameGeom g{1, 1, 1.f, 0.f, 0.f};
+    if (f < p.B) {
+      g = frame_geom(p, f);
+      n = frame_dets(p, g, f);
+      const float* D = p.dets + (long)f * p.max_dets * p.row;
+      for (int i = 0; i < n; ++i) {
+        float x1, y1, x2, y2, c, pc;
+        if (crop_one(p, g, D + (long)i * p.row, x1, y1, x2, y2, c, pc)) ++cnt;
+      }
+    }
+    scan[tid] = cnt;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {  // inclusive Hillis-Steele scan over the 256 frames of this chunk
+      int v = tid >= off ? scan[tid - off] : 0;
+      __syncthreads();
+      scan[tid] += v;
+      __syncthreads();
+    }
+    crop_frame<ALIGN>(p, g, f, n, base_s + scan[tid] - cnt);   // n = 0 past the last frame
+    __syncthreads();
+    if (tid == 255) base_s += scan[255];
+    __syncthreads();
+  }
+  if (tid == 0) p.n_faces[0] = base_s;  // may exceed max_faces: the host checks and raises
+}
+
+// What an entry point asks of its arguments beyond the checks all six share.
+enum CropFrames { CROPS_DENSE, CROPS_RAGGED, CROPS_PX };   // frame geometry: orig_* / gain scalars, descs + geom, descs alone
+struct CropForm {
+  CropFrames frames;
+  int fmt_lo, fmt_hi;   // row formats taken
+  int min_row1;         // least row_floats of fmt 1 (15: rows with landmarks), fmt 0 needs 17, fmt 2 15
+  bool align;           // lmarks / M / flags are required (CROPS_PX: all three or none)
+};
+
+// Everything the host can see, before any launch; FP_ERR_INVALID_ARG for the shared arguments comes before FP_ERR_ALIGNMENT,
+// and that before the frame geometry of the dense and ragged forms.
+int check_crops(const CropArgs& a, const CropForm& form) {
+  if (!a.dets || !a.counts || !a.items || !a.info || !a.n_faces) return FP_ERR_INVALID_ARG;
+  if (form.align && (!a.lmarks || !a.M || !a.flags)) return FP_ERR_INVALID_ARG;
+  if (form.frames == CROPS_PX && !a.descs) return FP_ERR_INVALID_ARG;
+  if (a.B < 0 || a.max_dets <= 0 || a.max_faces <= 0 || a.in_w <= 0 || a.in_h <= 0 || a.dst_w <= 0 || a.dst_h <= 0)
+    return FP_ERR_INVALID_ARG;
+  if (a.fmt < form.fmt_lo || a.fmt > form.fmt_hi) return FP_ERR_INVALID_ARG;
+  if (a.row < (a.fmt == 0 ? 17 : a.fmt == 1 ? form.min_row1 : 15)) return FP_ERR_INVALID_ARG;
+  if ((a.lmarks || a.M || a.flags) && (!a.lmarks || !a.M || !a.flags)) return FP_ERR_INVALID_ARG;
+  if (a.M && ((uintptr_t)a.M) % 8) return FP_ERR_ALIGNMENT;
+  if (form.frames == CROPS_DENSE && (a.orig_w <= 0 || a.orig_h <= 0 || !(a.gain > 0.f))) return FP_ERR_INVALID_ARG;
+  if (form.frames == CROPS_RAGGED && (!a.descs || !a.geom)) return FP_ERR_INVALID_ARG;
+  return FP_OK;
+}
+
+int launch_crops(const CropArgs& a, hipStream_t s) {
+  if (a.lmarks) hipLaunchKernelGGL(dets_to_crops_kernel<true>, dim3(1), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(dets_to_crops_kernel<false>, dim3(1), dim3(256), 0, s, a);
+  FP_CHECK_LAUNCH();
+  return FP_OK;
+}
+
+// The arguments all six entry points pass on as they are; everything else starts at 0 / nullptr and is assigned by name.
+CropArgs crop_args(const float* dets, const int32_t* counts, int B, int max_dets, int row_floats, int fmt, int in_w, int in_h,
+                   float det_thres, float area_thres, int off_tx, int off_ty, int off_bx, int off_by, int dst_w, int dst_h,
+                   int max_faces, fp_resize_item* items, float* face_info, int32_t* n_faces) {
+  CropArgs a{};
+  a.dets = dets; a.counts = counts; a.B = B; a.max_dets = max_dets; a.row = row_floats;
+  a.fmt = fmt; a.in_w = in_w; a.in_h = in_h;
+  a.det_thres = det_thres; a.area_thres = area_thres;
+  a.tx = off_tx; a.ty = off_ty; a.bx = off_bx; a.by = off_by;
+  a.dst_w = dst_w; a.dst_h = dst_h; a.max_faces = max_faces;
+  a.items = items; a.info = face_info; a.n_faces = n_faces;
+  return a;
 }
 
 // ------------------------------------------------------------------------------------------------ warp
@@ -347,36 +546,43 @@ int check_warp(const WarpArgs& a) {
   return FP_OK;
 }
 
-int check_crops(const float* dets, const int32_t* counts, int B, int max_dets, int row_floats, int fmt, int in_w, int in_h,
-                int dst_w, int dst_h, int max_faces, const void* items, const void* info, const void* nf, const float* lmarks,
-                const double* M, const int32_t* flags) {
-  if (!dets || !counts || !items || !info || !nf || !lmarks || !M || !flags) return FP_ERR_INVALID_ARG;
-  if (B < 0 || max_dets <= 0 || max_faces <= 0 || in_w <= 0 || in_h <= 0 || dst_w <= 0 || dst_h <= 0)
-    return FP_ERR_INVALID_ARG;
-  if ((fmt == 0 && row_floats < 17) || (fmt == 1 && row_floats < 15) || fmt < 0 || fmt > 1) return FP_ERR_INVALID_ARG;
-  if (((uintptr_t)M) % 8) return FP_ERR_ALIGNMENT;
-  return FP_OK;
-}
-
 }  // namespace
 
 extern "C" {
+
+int fp_dets_to_crops(const float* dets, const int32_t* counts, int B, int max_dets, int row_floats, int fmt, int in_w,
+                     int in_h, int orig_w, int orig_h, float det_thres, float area_thres, float gain, float pad_x,
+                     float pad_y, int off_tx, int off_ty, int off_bx, int off_by, int dst_w, int dst_h, int max_faces,
+                     fp_resize_item* items, float* face_info, int32_t* n_faces, void* stream) {
+  CropArgs a = crop_args(dets, counts, B, max_dets, row_floats, fmt, in_w, in_h, det_thres, area_thres, off_tx, off_ty, off_bx,
+                         off_by, dst_w, dst_h, max_faces, items, face_info, n_faces);
+  a.orig_w = orig_w; a.orig_h = orig_h; a.gain = gain; a.pad_x = pad_x; a.pad_y = pad_y;
+  const int rc = check_crops(a, CropForm{CROPS_DENSE, 0, 1, 5, false});
+  return rc != FP_OK ? rc : launch_crops(a, (hipStream_t)stream);
+}
+
+int fp_dets_to_crops_ragged(const float* dets, const int32_t* counts, int B, int max_dets, int row_floats, int fmt,
+                            int in_w, int in_h, const fp_frame_desc* descs, const float* geom, float det_thres,
+                            float area_thres, int off_tx, int off_ty, int off_bx, int off_by, int dst_w, int dst_h,
+                            int max_faces, fp_resize_item* items, float* face_info, int32_t* n_faces, void* stream) {
+  CropArgs a = crop_args(dets, counts, B, max_dets, row_floats, fmt, in_w, in_h, det_thres, area_thres, off_tx, off_ty, off_bx,
+                         off_by, dst_w, dst_h, max_faces, items, face_info, n_faces);
+  a.descs = descs; a.geom = geom;
+  const int rc = check_crops(a, CropForm{CROPS_RAGGED, 0, 1, 5, false});
+  return rc != FP_OK ? rc : launch_crops(a, (hipStream_t)stream);
+}
 
 int fp_dets_to_crops_aligned(const float* dets, const int32_t* counts, int B, int max_dets, int row_floats, int fmt, int in_w,
                              int in_h, int orig_w, int orig_h, float det_thres, float area_thres, float gain, float pad_x,
                              float pad_y, int off_tx, int off_ty, int off_bx, int off_by, int dst_w, int dst_h, int max_faces,
                              fp_resize_item* items, float* face_info, int32_t* n_faces, float* lmarks, double* M,
                              int32_t* flags, void* stream) {
-  int rc = check_crops(dets, counts, B, max_dets, row_floats, fmt, in_w, in_h, dst_w, dst_h, max_faces, items, face_info,
-                       n_faces, lmarks, M, flags);
-  if (rc != FP_OK) return rc;
-  if (orig_w <= 0 || orig_h <= 0 || !(gain > 0.f)) return FP_ERR_INVALID_ARG;
-  CropArgs a{dets, counts, B, max_dets, row_floats, fmt, in_w, in_h, orig_w, orig_h, det_thres, area_thres, gain,
-             pad_x, pad_y, off_tx, off_ty, off_bx, off_by, dst_w, dst_h, max_faces, items, face_info, n_faces,
-             nullptr, nullptr, lmarks, M, flags};
-  hipLaunchKernelGGL(dets_to_crops_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
-  FP_CHECK_LAUNCH();
-  return FP_OK;
+  CropArgs a = crop_args(dets, counts, B, max_dets, row_floats, fmt, in_w, in_h, det_thres, area_thres, off_tx, off_ty, off_bx,
+                         off_by, dst_w, dst_h, max_faces, items, face_info, n_faces);
+  a.orig_w = orig_w; a.orig_h = orig_h; a.gain = gain; a.pad_x = pad_x; a.pad_y = pad_y;
+  a.lmarks = lmarks; a.M = M; a.flags = flags;
+  const int rc = check_crops(a, CropForm{CROPS_DENSE, 0, 1, 15, true});
+  return rc != FP_OK ? rc : launch_crops(a, (hipStream_t)stream);
 }
 
 int fp_dets_to_crops_aligned_ragged(const float* dets, const int32_t* counts, int B, int max_dets, int row_floats, int fmt,
@@ -384,34 +590,24 @@ int fp_dets_to_crops_aligned_ragged(const float* dets, const int32_t* counts, in
                                     float area_thres, int off_tx, int off_ty, int off_bx, int off_by, int dst_w, int dst_h,
                                     int max_faces, fp_resize_item* items, float* face_info, int32_t* n_faces,
                                     float* lmarks, double* M, int32_t* flags, void* stream) {
-  int rc = check_crops(dets, counts, B, max_dets, row_floats, fmt, in_w, in_h, dst_w, dst_h, max_faces, items, face_info,
-                       n_faces, lmarks, M, flags);
-  if (rc != FP_OK) return rc;
-  if (!descs || !geom) return FP_ERR_INVALID_ARG;
-  CropArgs a{dets, counts, B, max_dets, row_floats, fmt, in_w, in_h, 0, 0, det_thres, area_thres, 0.f,
-             0.f, 0.f, off_tx, off_ty, off_bx, off_by, dst_w, dst_h, max_faces, items, face_info, n_faces,
-             descs, geom, lmarks, M, flags};
-  hipLaunchKernelGGL(dets_to_crops_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
-  FP_CHECK_LAUNCH();
-  return FP_OK;
+  CropArgs a = crop_args(dets, counts, B, max_dets, row_floats, fmt, in_w, in_h, det_thres, area_thres, off_tx, off_ty, off_bx,
+                         off_by, dst_w, dst_h, max_faces, items, face_info, n_faces);
+  a.descs = descs; a.geom = geom;
+  a.lmarks = lmarks; a.M = M; a.flags = flags;
+  const int rc = check_crops(a, CropForm{CROPS_RAGGED, 0, 1, 15, true});
+  return rc != FP_OK ? rc : launch_crops(a, (hipStream_t)stream);
 }
 
 int fp_dets_to_crops_px(const float* dets, const int32_t* counts, int B, int max_dets, int row_floats,
                         const fp_frame_desc* descs, float det_thres, float area_thres, int off_tx, int off_ty, int off_bx,
                         int off_by, int dst_w, int dst_h, int max_faces, fp_resize_item* items, float* face_info,
                         int32_t* n_faces, float* lmarks, double* M, int32_t* flags, void* stream) {
-  if (!dets || !counts || !descs || !items || !face_info || !n_faces) return FP_ERR_INVALID_ARG;
-  if (B < 0 || max_dets <= 0 || max_faces <= 0 || dst_w <= 0 || dst_h <= 0 || row_floats < 15) return FP_ERR_INVALID_ARG;
-  const bool align = lmarks || M || flags;
-  if (align && (!lmarks || !M || !flags)) return FP_ERR_INVALID_ARG;
-  if (align && ((uintptr_t)M) % 8) return FP_ERR_ALIGNMENT;
-  CropArgs a{dets, counts, B, max_dets, row_floats, 2, 1, 1, 0, 0, det_thres, area_thres, 1.f,
-             0.f, 0.f, off_tx, off_ty, off_bx, off_by, dst_w, dst_h, max_faces, items, face_info, n_faces,
-             descs, nullptr, lmarks, M, flags};
-  if (align) hipLaunchKernelGGL(dets_to_crops_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(dets_to_crops_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
-  FP_CHECK_LAUNCH();
-  return FP_OK;
+  CropArgs a = crop_args(dets, counts, B, max_dets, row_floats, 2, 1, 1, det_thres, area_thres, off_tx, off_ty, off_bx, off_by,
+                         dst_w, dst_h, max_faces, items, face_info, n_faces);
+  a.descs = descs;                                // no geom: the rows are in each frame's own pixels
+  a.lmarks = lmarks; a.M = M; a.flags = flags;    // all three or none
+  const int rc = check_crops(a, CropForm{CROPS_PX, 2, 2, 15, false});
+  return rc != FP_OK ? rc : launch_crops(a, (hipStream_t)stream);
 }
 
 int fp_dets_to_crops_aligned_emulate(const float* dets, const int32_t* counts, int B, int max_dets, int row_floats, int fmt,
@@ -419,25 +615,16 @@ int fp_dets_to_crops_aligned_emulate(const float* dets, const int32_t* counts, i
                                      float area_thres, int off_tx, int off_ty, int off_bx, int off_by, int dst_w, int dst_h,
                                      int max_faces, fp_resize_item* items, float* face_info, int32_t* n_faces,
                                      float* lmarks, double* M, int32_t* flags) {
-  int rc = check_crops(dets, counts, B, max_dets, row_floats, fmt, in_w, in_h, dst_w, dst_h, max_faces, items, face_info,
-                       n_faces, lmarks, M, flags);
+  CropArgs a = crop_args(dets, counts, B, max_dets, row_floats, fmt, in_w, in_h, det_thres, area_thres, off_tx, off_ty, off_bx,
+                         off_by, dst_w, dst_h, max_faces, items, face_info, n_faces);
+  a.descs = descs; a.geom = geom;
+  a.lmarks = lmarks; a.M = M; a.flags = flags;
+  const int rc = check_crops(a, CropForm{CROPS_RAGGED, 0, 1, 15, true});
   if (rc != FP_OK) return rc;
-  if (!descs || !geom) return FP_ERR_INVALID_ARG;
-  CropArgs p{dets, counts, B, max_dets, row_floats, fmt, in_w, in_h, 0, 0, det_thres, area_thres, 0.f,
-             0.f, 0.f, off_tx, off_ty, off_bx, off_by, dst_w, dst_h, max_faces, items, face_info, n_faces,
-             descs, geom, lmarks, M, flags};
   int slot = 0;
   for (int f = 0; f < B; ++f) {   // dets_to_crops_kernel's order: frame by frame, each frame's detections in order
-    const FrameGeom g = frame_geom(p, f);
-    int n = min(max(counts[f], 0), max_dets);
-    if (g.orig_w <= 0 || g.orig_h <= 0 || !(g.gain > 0.f)) n = 0;
-    const float* D = dets + (long)f * max_dets * row_floats;
-    for (int i = 0; i < n; ++i) {
-      float x1, y1, x2, y2, c, pc;
-      if (!crop_one(p, g, D + (long)i * row_floats, x1, y1, x2, y2, c, pc)) continue;
-      if (slot < max_faces) crop_emit<true>(p, g, f, D + (long)i * row_floats, slot, x1, y1, x2, y2, c, pc);
-      ++slot;
-    }
+    const FrameGeom g = frame_geom(a, f);
+    slot = crop_frame<true>(a, g, f, frame_dets(a, g, f), slot);
   }
   n_faces[0] = slot;
   return FP_OK;

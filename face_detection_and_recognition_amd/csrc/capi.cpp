@@ -386,41 +386,6 @@ int fp_plan_run(const fp_op* ops, int n_ops, const float* weights, size_t weight
   return fp_plan_run_ext(ops, n_ops, weights, weight_floats, arena, arena_floats, nullptr, 0, stream);
 }
 
-// Ragged batches (facepath.h section 2): every argument the host can see is checked here, before any launch; the
-// descriptors and items are device memory, bounded inside the kernels.
-int fp_resize_ragged(const uint8_t* frames, size_t frames_bytes, const fp_frame_desc* descs, int n_frames,
-                     const fp_resize_item* items, int n_items, void* canvas, int canvas_h, int canvas_w, int canvas_c,
-                     int mode, const float* lut256, int pad_value, int swap_rb, void* stream) {
-  if (!frames || !descs || !items || !canvas) return FP_ERR_INVALID_ARG;
-  if (frames_bytes < 3 * FP_FRAME_MIN_W || n_frames <= 0 || n_items < 0) return FP_ERR_INVALID_ARG;
-  if (canvas_h <= 0 || canvas_h > 65535 || canvas_w <= 0 || canvas_w > 4096) return FP_ERR_INVALID_ARG;
-  if (pad_value < 0 || pad_value > 255 || (swap_rb != 0 && swap_rb != 1)) return FP_ERR_INVALID_ARG;
-  if (mode == FP_RAGGED_U8) {
-    if (canvas_c != 3 || swap_rb) return FP_ERR_INVALID_ARG;
-  } else if (mode == FP_RAGGED_F32_LUT) {
-    if (canvas_c != 4 || !lut256) return FP_ERR_INVALID_ARG;
-    if (((uintptr_t)canvas) % 16) return FP_ERR_ALIGNMENT;
-  } else {
-    return FP_ERR_INVALID_ARG;
-  }
-  if (n_items == 0) return FP_OK;
-  return fp_launch_resize_ragged(frames, frames_bytes, descs, n_frames, items, n_items, canvas, canvas_h, canvas_w, mode,
-                                 lut256, pad_value, swap_rb, (hipStream_t)stream);
-}
-
-int fp_dets_to_crops_ragged(const float* dets, const int32_t* counts, int B, int max_dets, int row_floats, int fmt,
-                            int in_w, int in_h, const fp_frame_desc* descs, const float* geom, float det_thres,
-                            float area_thres, int off_tx, int off_ty, int off_bx, int off_by, int dst_w, int dst_h,
-                            int max_faces, fp_resize_item* items, float* face_info, int32_t* n_faces, void* stream) {
-  if (!dets || !counts || !descs || !geom || !items || !face_info || !n_faces) return FP_ERR_INVALID_ARG;
-  if (B < 0 || max_dets <= 0 || max_faces <= 0 || in_w <= 0 || in_h <= 0 || dst_w <= 0 || dst_h <= 0)
-    return FP_ERR_INVALID_ARG;
-  if ((fmt == 0 && row_floats < 17) || (fmt == 1 && row_floats < 5) || fmt < 0 || fmt > 1) return FP_ERR_INVALID_ARG;
-  return fp_launch_dets_to_crops_ragged(dets, counts, B, max_dets, row_floats, fmt, in_w, in_h, descs, geom, det_thres,
-                                        area_thres, off_tx, off_ty, off_bx, off_by, dst_w, dst_h, max_faces, items,
-                                        face_info, n_faces, (hipStream_t)stream);
-}
-
 int fp_timer_create(int n_ops, void** out) {
   if (!out || n_ops <= 0) return FP_ERR_INVALID_ARG;
   fp_timer* t = new fp_timer;

@@ -171,12 +171,3 @@ long fp_shufdown_w_floats(const fp_op& op);
 long fp_shufunit_w_floats(const fp_op& op);
 long fp_ystem2_w_floats(const fp_op& op);
 int fp_ystem_nb2(const fp_op& op);   // 16-channel column blocks of ystem_kernel's packed stem_1 weights
-
-// ragged batches (facepath.h section 2): launchers behind the argument checks of capi.cpp
-int fp_launch_resize_ragged(const uint8_t* frames, size_t frames_bytes, const fp_frame_desc* descs, int n_frames,
-                            const fp_resize_item* items, int n_items, void* canvas, int canvas_h, int canvas_w, int mode,
-                            const float* lut256, int pad_value, int swap_rb, hipStream_t s);
-int fp_launch_dets_to_crops_ragged(const float* dets, const int32_t* counts, int B, int max_dets, int row_floats, int fmt,
-                                   int in_w, int in_h, const fp_frame_desc* descs, const float* geom, float det_thres,
-                                   float area_thres, int off_tx, int off_ty, int off_bx, int off_by, int dst_w, int dst_h,
-                                   int max_faces, fp_resize_item* items, float* face_info, int32_t* n_faces, hipStream_t s);

@@ -274,10 +274,24 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(RaggedArgs p) {
 
 }  // namespace
 
-// Arguments checked by fp_resize_ragged (capi.cpp).
-int fp_launch_resize_ragged(const uint8_t* frames, size_t frames_bytes, const fp_frame_desc* descs, int n_frames,
-                            const fp_resize_item* items, int n_items, void* canvas, int canvas_h, int canvas_w, int mode,
-                            const float* lut256, int pad_value, int swap_rb, hipStream_t s) {
+// Ragged batches (facepath.h section 2): every argument the host can see is checked here, before the launch; the
+// descriptors and items are device memory, bounded inside the kernel.
+extern "C" int fp_resize_ragged(const uint8_t* frames, size_t frames_bytes, const fp_frame_desc* descs, int n_frames,
+                                const fp_resize_item* items, int n_items, void* canvas, int canvas_h, int canvas_w, int canvas_c,
+                                int mode, const float* lut256, int pad_value, int swap_rb, void* stream) {
+  if (!frames || !descs || !items || !canvas) return FP_ERR_INVALID_ARG;
+  if (frames_bytes < 3 * FP_FRAME_MIN_W || n_frames <= 0 || n_items < 0) return FP_ERR_INVALID_ARG;
+  if (canvas_h <= 0 || canvas_h > 65535 || canvas_w <= 0 || canvas_w > 4096) return FP_ERR_INVALID_ARG;
+  if (pad_value < 0 || pad_value > 255 || (swap_rb != 0 && swap_rb != 1)) return FP_ERR_INVALID_ARG;
+  if (mode == FP_RAGGED_U8) {
+    if (canvas_c != 3 || swap_rb) return FP_ERR_INVALID_ARG;
+  } else if (mode == FP_RAGGED_F32_LUT) {
+    if (canvas_c != 4 || !lut256) return FP_ERR_INVALID_ARG;
+    if (((uintptr_t)canvas) % 16) return FP_ERR_ALIGNMENT;
+  } else {
+    return FP_ERR_INVALID_ARG;
+  }
+  if (n_items == 0) return FP_OK;
   RaggedArgs a;
   a.frames = frames;
   a.descs = descs;
@@ -297,8 +311,8 @@ int fp_launch_resize_ragged(const uint8_t* frames, size_t frames_bytes, const fp
   const bool u8 = mode == FP_RAGGED_U8;
   const size_t lds = (u8 ? 0 : 1024) + (size_t)(canvas_w + a.rpb) * sizeof(fp_lb_tap);
   const dim3 grid((unsigned)((long)n_items * a.bpi));
-  if (u8) hipLaunchKernelGGL(resize_ragged_kernel<true>, grid, dim3(256), lds, s, a);
-  else hipLaunchKernelGGL(resize_ragged_kernel<false>, grid, dim3(256), lds, s, a);
+  if (u8) hipLaunchKernelGGL(resize_ragged_kernel<true>, grid, dim3(256), lds, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(resize_ragged_kernel<false>, grid, dim3(256), lds, (hipStream_t)stream, a);
   FP_CHECK_LAUNCH();
   return FP_OK;
 }

@@ -8,7 +8,6 @@
 // 64-wide wavefront shuffles.  Every loop is bounded by the candidate count (the reference's
 // weighted NMS never terminates on a degenerate box; here such a box is emitted alone and removed).
 #include "common.h"
-#include "crops.h"
 
 namespace {
 
@@ -387,9 +386,6 @@ __global__ __launch_bounds__(256) void yolo_nms_kernel(const float* __restrict__
   if (tid == 0) out_count[b] = nout;
 }
 
-
-// Detections -> per-face crop rectangles: crops.h (shared with the aligned entry points of align.hip).
-
 }  // namespace
 
 extern "C" {
@@ -465,34 +461,4 @@ int fp_yolo_w_nms(const float* pred, int B, int n_rows, float conf_thres, float 
                          overflow, scratch, scratch_bytes, stream);
 }
 
-int fp_dets_to_crops(const float* dets, const int32_t* counts, int B, int max_dets, int row_floats, int fmt, int in_w,
-                     int in_h, int orig_w, int orig_h, float det_thres, float area_thres, float gain, float pad_x,
-                     float pad_y, int off_tx, int off_ty, int off_bx, int off_by, int dst_w, int dst_h, int max_faces,
-                     fp_resize_item* items, float* face_info, int32_t* n_faces, void* stream) {
-  if (!dets || !counts || !items || !face_info || !n_faces) return FP_ERR_INVALID_ARG;
-  if (B < 0 || max_dets <= 0 || max_faces <= 0 || in_w <= 0 || in_h <= 0 || orig_w <= 0 || orig_h <= 0 ||
-      dst_w <= 0 || dst_h <= 0 || !(gain > 0.f))
-    return FP_ERR_INVALID_ARG;
-  if ((fmt == 0 && row_floats < 17) || (fmt == 1 && row_floats < 5) || fmt < 0 || fmt > 1) return FP_ERR_INVALID_ARG;
-  CropArgs a{dets, counts, B, max_dets, row_floats, fmt, in_w, in_h, orig_w, orig_h, det_thres, area_thres, gain,
-             pad_x, pad_y, off_tx, off_ty, off_bx, off_by, dst_w, dst_h, max_faces, items, face_info, n_faces,
-             nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipLaunchKernelGGL(dets_to_crops_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
-  FP_CHECK_LAUNCH();
-  return FP_OK;
-}
-
 }  // extern "C"
-
-// Arguments checked by fp_dets_to_crops_ragged (capi.cpp).
-int fp_launch_dets_to_crops_ragged(const float* dets, const int32_t* counts, int B, int max_dets, int row_floats, int fmt,
-                                   int in_w, int in_h, const fp_frame_desc* descs, const float* geom, float det_thres,
-                                   float area_thres, int off_tx, int off_ty, int off_bx, int off_by, int dst_w, int dst_h,
-                                   int max_faces, fp_resize_item* items, float* face_info, int32_t* n_faces, hipStream_t s) {
-  CropArgs a{dets, counts, B, max_dets, row_floats, fmt, in_w, in_h, 0, 0, det_thres, area_thres, 0.f,
-             0.f, 0.f, off_tx, off_ty, off_bx, off_by, dst_w, dst_h, max_faces, items, face_info, n_faces,
-             descs, geom, nullptr, nullptr, nullptr};
-  hipLaunchKernelGGL(dets_to_crops_kernel<false>, dim3(1), dim3(256), 0, s, a);
-  FP_CHECK_LAUNCH();
-  return FP_OK;
-}

@@ -398,7 +398,7 @@ def dets_to_frame_boxes(detector, dets, counts, frame_sizes):
     input pixels, confidence in column 4) are taken back through the letterbox with the arithmetic of
     modules/utils/image.py scale_coords (subtract the pad, divide by the gain, clip to the frame); dets_fmt 2 (MTCNN) is
     already in frame pixels: gain 1, no pad."""
-    fmt = getattr(detector, "dets_fmt", 0)
+    fmt = detector.dets_fmt
     B, K = int(dets.shape[0]), int(dets.shape[1])
     if len(frame_sizes) != B or tuple(counts.shape) != (B,):
         raise ValueError(f"dets_to_frame_boxes: {B} frames of rows, {len(frame_sizes)} sizes, counts {tuple(counts.shape)}")

@@ -20,9 +20,8 @@ from dataclasses import dataclass, field
 from typing import List
 
 import numpy as np
-import torch
 
-from ..frames import RaggedFrames
+from ..frames import as_frames
 
 MAX_N_FACES_PER_FRAME = 3      # extract_faces_from_dataset.py:38
 MAX_N_FRAME_FROM_VID = 15      # :40
@@ -49,18 +48,9 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
     file of that quality, in one device call.  align: embed each face warped onto the five-point template
     (FacePipeline(align=True) for this call, modules/utils/align.py); with save_face the files are then the 112 x 112
     aligned faces the embedder saw (as u8), under the same names."""
-    if isinstance(frames, (list, tuple)):
-        if not frames:
-            return []
-        if all(tuple(f.shape) == tuple(frames[0].shape) for f in frames):
-            frames = torch.stack([(torch.from_numpy(np.ascontiguousarray(f)) if isinstance(f, np.ndarray) else f).to(pipe.dev)
-                                  for f in frames])
-        else:
-            frames = RaggedFrames.from_list(frames, pipe.dev)
-    if isinstance(frames, np.ndarray):
-        frames = torch.from_numpy(np.ascontiguousarray(frames))
-    if not isinstance(frames, RaggedFrames):
-        frames = frames.to(pipe.dev).contiguous()
+    if isinstance(frames, (list, tuple)) and not frames:
+        return []
+    frames = as_frames(frames, pipe.dev)
     B = len(frames)
     if align and not pipe.align:
         pipe.align = True

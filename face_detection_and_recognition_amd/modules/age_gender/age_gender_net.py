@@ -197,16 +197,14 @@ def attr_crop_items(info, n, frames, dst=(227, 227), pad=ATTR_PAD, out=None):
     """Device: fp_resize_item rows (n, 9) int32 of the age / gender crops of face rows info (n, >= 5: frame, x1, y1, x2, y2)
     of `frames` ((B, H, W, 3) or a RaggedFrames).  An empty crop has dw = dh = 0."""
     import torch
-    from ...frames import RaggedFrames
+    from ...frames import frame_call_args
     lib = L.load()
     dev = info.device
     items = out if out is not None else torch.empty((max(n, 1), 9), dtype=torch.int32, device=dev)
     if n == 0:
         return items[:0]
-    if isinstance(frames, RaggedFrames):
-        descs, nf, fw, fh = L.ptr(frames.descs), len(frames), 0, 0
-    else:
-        descs, nf, fh, fw = None, frames.shape[0], frames.shape[1], frames.shape[2]
+    ragged, fa = frame_call_args(frames)     # ragged: (data, bytes, descs, B); dense: (frames, B, H, W)
+    descs, nf, fh, fw = (fa[2], fa[3], 0, 0) if ragged else (None,) + fa[1:]
     L.check(lib.fp_attr_crop_items(L.ptr(info), int(n), info.shape[1], descs, nf, fw, fh, int(pad), dst[0], dst[1], L.ptr(items),
                                    L.current_stream(dev)), "fp_attr_crop_items")
     return items[:n]

@@ -3,12 +3,10 @@ plus ``predict_batch`` — the batched fast path the reference does not have (it
 import os
 
 import numpy as np
-import torch
 
-from ... import _lib as L
 from ..models.base import Model
-from ...frames import RaggedFrames
-from ..utils.image import bind_letterbox, letterbox_batch, letterbox_ragged
+from ...frames import as_frames
+from ..utils.image import letterbox_plan
 from .blazeface import BlazeFace, generate_anchors
 
 MODEL_IN_SIZES = {"back": (256, 256), "front": (128, 128)}
@@ -61,33 +59,10 @@ class BlazeFaceModel(Model):
         """frames: (B, H, W, 3) u8 BGR (numpy or CUDA tensor) or a RaggedFrames -> device dets (B, 896, 17)
         [ymin,xmin,...], counts (B,)."""
         net = self.net
-        dev = net._device()
-        if isinstance(frames, RaggedFrames):
-            # frames of different sizes: one letterbox launch into a u8 canvas of the input size, then the u8 plan of that
-            # size (identity taps: the stem's staging returns the canvas bytes), or the fp32 plan input directly
-            ih, iw = net.input_hw
-            B = len(frames)
-            if BlazeFace.FUSE_LETTERBOX:
-                plan = net.plan_for(B, frame_hw=(ih, iw))
-                bind_letterbox(plan, letterbox_ragged(frames, (iw, ih)), net._preprocess_lut(), pad_value=125, swap_rb=True)
-            else:
-                plan = net.plan_for(B)
-                letterbox_ragged(frames, (iw, ih), net._preprocess_lut(), plan.input, pad_value=125, swap_rb=True)
-            plan.run()
-            net.last_plan = plan
-            return net.postprocess(plan.r, plan.c)
-        if isinstance(frames, np.ndarray):
-            frames = torch.from_numpy(np.ascontiguousarray(frames))
-        frames = frames.to(dev)
-        B, fh, fw, _ = frames.shape
-        if BlazeFace.FUSE_LETTERBOX and fw >= 3 and fh <= 65535 and frames.dtype == torch.uint8:
-            # pad_resize_image + BGR->RGB + x/127.5-1 (model.py:61,75; blazeface.py:248-250) happen inside the stem conv's
-            # staging (FP_OP_STEM_U8): no fp32 canvas, no letterbox launch
-            plan = net.plan_for(B, frame_hw=(fh, fw))
-            bind_letterbox(plan, frames.contiguous(), net._preprocess_lut(), pad_value=125, swap_rb=True)
-        else:
-            plan = net.plan_for(B)
-            letterbox_batch(frames, self.input_size, net._preprocess_lut(), plan.input, pad_value=125, swap_rb=True)
+        # fused: pad_resize_image + BGR->RGB + x/127.5-1 (model.py:61,75; blazeface.py:248-250) happen inside the stem conv's
+        # staging (FP_OP_STEM_U8): no fp32 canvas, and for a dense batch no letterbox launch
+        plan = letterbox_plan(as_frames(frames, net._device()), self.input_size, net._preprocess_lut(), BlazeFace.FUSE_LETTERBOX,
+                              lambda B, hw: net.plan_for(B, frame_hw=hw), net.plan_for)
         plan.run()
         net.last_plan = plan          # measurement / tests: the plan (and its raw r, c views) of the last batch
         return net.postprocess(plan.r, plan.c)

@@ -4,8 +4,7 @@ BGR kept, NCHW — here the crop, resize and normalisation are one device kernel
 import numpy as np
 import torch
 
-from ... import _lib as L
-from ...frames import RaggedFrames, resize_ragged
+from ...frames import resize_items
 
 
 def mfn_lut(device):
@@ -16,14 +15,7 @@ def mfn_lut(device):
 def crops_to_input(frames_u8, items, n_items, canvas, lut, swap_rb=False):
     """frames_u8 (B,H,W,3) u8 CUDA or a RaggedFrames; items int32 CUDA (n,9) fp_resize_item rows; canvas (n,h,w,C) fp32
     (C = 4 for a RaggedFrames; h x w = the embedder's input, 112 x 112 for Mobile-FaceNet); swap_rb: RGB crops (FaceNet)."""
-    if isinstance(frames_u8, RaggedFrames):
-        resize_ragged(frames_u8, items, n_items, canvas, lut, pad_value=0, swap_rb=swap_rb)
-        return
-    lib = L.load()
-    B, H, W, _ = frames_u8.shape
-    L.check(lib.fp_resize_normalize(L.ptr(frames_u8), B, H, W, L.ptr(items), int(n_items), L.ptr(canvas),
-                                    canvas.shape[1], canvas.shape[2], canvas.shape[3], L.ptr(lut), 0, int(bool(swap_rb)),
-                                    L.current_stream(frames_u8.device)), "fp_resize_normalize")
+    resize_items(frames_u8, items, n_items, canvas, lut, pad_value=0, swap_rb=swap_rb)
 
 
 def inference_onnx_model_mobile_facenet(feature_net, face, face_feat_in_size=(112, 112)):

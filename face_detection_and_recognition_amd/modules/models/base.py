@@ -10,6 +10,7 @@ class Model:
     coordinates normalised to [0, 1] w.r.t. ``input_size`` (base.py:6-31)."""
 
     __slots__ = ["input_size", "det_thres", "bbox_area_thres", "returns_opt_labels"]
+    dets_fmt = 0     # layout of raw_batch rows (fp_dets_to_crops): 0 BlazeFace, 1 YOLOv5-face, 2 MTCNN; subclasses override
 
     def __init__(self, input_size: Tuple[int, int], det_thres: float, bbox_area_thres: float,
                  returns_opt_labels: bool = False):

@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from ... import _lib as L
-from ...frames import RaggedFrames
+from ...frames import as_frames, device_descs, frame_bytes, frame_layout
 from ...plan import CompiledPlan, PlanBuilder, PlanCache, switch_key
 from ..params import ConvParams, LinearParams, PlanCacheMixin, PReLUParams, _NoCompute, npy
 
@@ -387,18 +387,8 @@ class MTCNN(PlanCacheMixin, nn.Module):
     @staticmethod
     def _as_ragged(frames, dev):
         """(data u8, descs, sizes) of a (B, H, W, 3) tensor / numpy array or a RaggedFrames."""
-        if isinstance(frames, RaggedFrames):
-            return frames.data, frames.descs, frames.sizes
-        if isinstance(frames, np.ndarray):
-            frames = torch.from_numpy(np.ascontiguousarray(frames))
-        if frames.dtype != torch.uint8 or frames.ndim != 4 or frames.shape[3] != 3:
-            raise ValueError(f"frames: (B, H, W, 3) uint8 expected, got {tuple(frames.shape)} {frames.dtype}")
-        frames = frames.to(dev).contiguous()
-        B, H, W, _ = frames.shape
-        d = np.zeros((B, 2), np.int64)
-        d[:, 0] = np.arange(B) * (H * W * 3)
-        d[:, 1] = H | (W << 32)
-        return frames.view(-1), torch.from_numpy(d.view(np.uint8)).to(dev), [(H, W)] * B
+        frames = as_frames(frames, dev)
+        return frame_bytes(frames), device_descs(frames), [(h, w) for _, h, w in frame_layout(frames)]
 
     # ---- the stages, one call each (tests drive them alone) ----
     def propose(self, data, descs, sizes, t1=None, cap=None):

@@ -10,7 +10,8 @@ import numpy as np
 import torch
 
 from ... import _lib as L
-from ...frames import RaggedFrames
+from ...frames import frame_call_args, frame_descs, ragged_scale_coords_params
+from ...frames import uniform_descs  # noqa: F401 (re-export)
 
 SIZE = L.ALIGN_SIZE
 DEGENERATE = L.ALIGN_DEGENERATE
@@ -46,15 +47,10 @@ def warp(frames, M, info, flags, items, n, out_u8=None, out_f32=None, lut=None):
         c = out_f32.shape[3]
     if out_u8 is not None:
         assert out_u8.dtype == torch.uint8 and out_u8.is_contiguous() and out_u8.shape[0] >= n
-    if isinstance(frames, RaggedFrames):
-        L.check(lib.fp_align_warp_ragged(L.ptr(frames.data), frames.data.numel(), L.ptr(frames.descs), len(frames), L.ptr(M),
-                                         L.ptr(info), L.ptr(flags), L.ptr(items), int(n), L.ptr(out_u8), L.ptr(out_f32), c,
-                                         L.ptr(lut), L.current_stream(frames.device)), "fp_align_warp_ragged")
-    else:
-        B, H, W, _ = frames.shape
-        L.check(lib.fp_align_warp(L.ptr(frames), B, H, W, L.ptr(M), L.ptr(info), L.ptr(flags), L.ptr(items), int(n),
-                                  L.ptr(out_u8), L.ptr(out_f32), c, L.ptr(lut), L.current_stream(frames.device)),
-                "fp_align_warp")
+    ragged, fa = frame_call_args(frames)
+    name = "fp_align_warp_ragged" if ragged else "fp_align_warp"
+    L.check(getattr(lib, name)(*fa, L.ptr(M), L.ptr(info), L.ptr(flags), L.ptr(items), int(n), L.ptr(out_u8), L.ptr(out_f32), c,
+                               L.ptr(lut), L.current_stream(frames.device)), name)
 
 
 def warp_u8(frames, M, info, flags, items, n):
@@ -69,14 +65,6 @@ def warp_u8(frames, M, info, flags, items, n):
 
 def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p)
-
-
-def uniform_descs(B, H, W):
-    """fp_frame_desc rows of B packed H x W frames (numpy, host)."""
-    d = np.zeros((B, 2), np.int64)
-    d[:, 0] = np.arange(B) * H * W * 3
-    d[:, 1] = H | (W << 32)
-    return d
 
 
 def emulate_estimate(lmarks, fmt):
@@ -100,9 +88,7 @@ def emulate_warp(frames, M, info, flags, items):
         frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
         data = np.concatenate([f.reshape(-1) for f in frames])
         offs = np.concatenate([[0], np.cumsum([f.size for f in frames])[:-1]]).astype(np.int64)
-        descs = np.zeros((len(frames), 2), np.int64)
-        descs[:, 0] = offs
-        descs[:, 1] = [f.shape[0] | (f.shape[1] << 32) for f in frames]
+        descs = frame_descs(offs, [f.shape[:2] for f in frames])
     M = np.ascontiguousarray(M, np.float64)
     info = np.ascontiguousarray(info, np.float32)
     flags = np.ascontiguousarray(flags, np.int32)
@@ -117,13 +103,11 @@ def emulate_warp(frames, M, info, flags, items):
 def emulate_crops(dets, counts, sizes, in_size, fmt, det_thres, area_thres, offsets=(-6, -1, 4, 5), max_faces=None):
     """fp_dets_to_crops_aligned_emulate on host arrays: dets (B, max_dets, row) float32, counts (B,), sizes [(h, w)] ->
     dict(items, info, lmarks, M, flags) of the n faces found."""
-    from ...pipeline import ragged_scale_coords_params
     dets = np.ascontiguousarray(dets, np.float32)
     counts = np.ascontiguousarray(counts, np.int32)
     B, max_dets, row = dets.shape
     cap = max_faces or max(1, B * max_dets)
-    descs = np.zeros((B, 2), np.int64)
-    descs[:, 1] = [h | (w << 32) for h, w in sizes]
+    descs = frame_descs(0, sizes)
     geom = np.ascontiguousarray(ragged_scale_coords_params(in_size, sizes))
     out = dict(items=np.zeros((cap, 9), np.int32), info=np.zeros((cap, 7), np.float32), lmarks=np.zeros((cap, 10), np.float32),
                M=np.zeros((cap, 6), np.float64), flags=np.zeros((cap,), np.int32))

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from ... import _lib as L
+from ...frames import RaggedFrames, resize_items
 
 
 def make_divisible(x, divisor):
@@ -36,17 +37,13 @@ def letterbox_batch(frames_u8, new_size, lut, canvas, pad_value=125, swap_rb=Fal
     """Batched pad_resize_image + normalisation on device.
     frames_u8: (B, H, W, 3) u8 CUDA tensor; canvas: (B, new_h, new_w, C>=3) fp32 CUDA tensor (written);
     lut: (256,) fp32 CUDA tensor (normalisation of each u8 value)."""
-    lib = L.load()
     B, H, W, _ = frames_u8.shape
     new_w, new_h = new_size
     assert canvas.shape[0] == B and canvas.shape[1] == new_h and canvas.shape[2] == new_w
     sw, sh, left, top = letterbox_geometry(W, H, new_w, new_h)
     items = torch.tensor([[i, 0, 0, W, H, left, top, sw, sh] for i in range(B)], dtype=torch.int32,
                          device=frames_u8.device)
-    L.check(lib.fp_resize_normalize(L.ptr(frames_u8), B, H, W, L.ptr(items), B, L.ptr(canvas), new_h, new_w,
-                                    canvas.shape[3], L.ptr(lut), int(pad_value), int(bool(swap_rb)),
-                                    L.current_stream(frames_u8.device)), "fp_resize_normalize")
-    return canvas
+    return resize_items(frames_u8, items, B, canvas, lut, pad_value, swap_rb)
 
 
 def letterbox_items(frames, new_size):
@@ -68,13 +65,12 @@ def letterbox_ragged(frames, new_size, lut=None, canvas=None, pad_value=125, swa
     (B, new_h, new_w, 3) u8 canvas -- frames of one size, which a detector's u8 plan reads with identity taps, so the R/B
     swap and the normalisation still happen once, in its stem.  Else: fills `canvas` (B, new_h, new_w, 4) fp32 through the
     LUT, bit-identical to letterbox_batch on each frame."""
-    from ...frames import resize_ragged
     new_w, new_h = new_size
     B = len(frames)
     if lut is None:
         canvas = torch.empty((B, new_h, new_w, 3), dtype=torch.uint8, device=frames.device)
     assert canvas.shape[0] == B and canvas.shape[1] == new_h and canvas.shape[2] == new_w
-    return resize_ragged(frames, letterbox_items(frames, new_size), B, canvas, lut, pad_value, swap_rb)
+    return resize_items(frames, letterbox_items(frames, new_size), B, canvas, lut, pad_value, swap_rb)
 
 
 def bind_letterbox(plan, frames_u8, lut, pad_value=125, swap_rb=False):
@@ -95,6 +91,24 @@ def bind_letterbox(plan, frames_u8, lut, pad_value=125, swap_rb=False):
         if hasattr(plan, "invalidate_windows"):   # new pad colour: the rows outside a row window change (CompiledPlan)
             plan.invalidate_windows()
     plan.set_ext([frames_u8, plan.tables[1], lut])
+    return plan
+
+
+def letterbox_plan(frames, in_size, lut, fusable, plan_u8, plan_f32, pad_value=125, swap_rb=True):
+    """The plan a detector runs on `frames` ((B, H, W, 3) u8 or a RaggedFrames), filled or bound: the choice both detectors
+    make.  fusable (the detector's own condition) and a frame size the fused stem takes: plan_u8(B, (fh, fw)), whose first op
+    reads u8 frames of fh x fw and letterboxes them in its staging -- a dense batch's frames themselves, a ragged batch's
+    letterbox_ragged u8 canvas of the input size (identity taps; the swap and the normalisation stay in the stem).
+    Otherwise plan_f32(B), its fp32 input letterboxed here through the LUT."""
+    in_w, in_h = in_size
+    ragged = isinstance(frames, RaggedFrames)      # the one fork on the kind of batch outside frames.py: the PLAN differs
+    B = len(frames)
+    fh, fw = (in_h, in_w) if ragged else (frames.shape[1], frames.shape[2])
+    if fusable and fw >= 3 and fh <= 65535 and (ragged or frames.dtype == torch.uint8):
+        src = letterbox_ragged(frames, in_size) if ragged else frames
+        return bind_letterbox(plan_u8(B, (fh, fw)), src, lut, pad_value=pad_value, swap_rb=swap_rb)
+    plan = plan_f32(B)
+    (letterbox_ragged if ragged else letterbox_batch)(frames, in_size, lut, plan.input, pad_value=pad_value, swap_rb=swap_rb)
     return plan
 
 

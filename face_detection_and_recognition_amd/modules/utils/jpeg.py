@@ -344,18 +344,14 @@ def crop_items(frames, items, n):
     """The pipeline's crop records (fp_resize_item rows from fp_dets_to_crops, items[:n]) over frames (B, H, W, 3) or a
     RaggedFrames -> fp_jpeg_enc_item list; None for a crop that is empty after the clamp (the reference's slice of it is
     empty)."""
-    from ...frames import RaggedFrames
-    if isinstance(frames, RaggedFrames):
-        B, geo = len(frames), [(o, h, w) for o, (h, w) in zip(frames.offsets, frames.sizes)]
-    else:
-        B, H, W, _ = frames.shape
-        geo = None
+    from ...frames import frame_layout
+    geo = frame_layout(frames)
     rows = items[:n].cpu().tolist() if n else []
     out = []
     for src_image, sx, sy, sw, sh, *_ in rows:
-        if not 0 <= src_image < B:
-            raise L.FacepathError(f"crop record of frame {src_image} outside the batch of {B}")
-        off, H, W = geo[src_image] if geo is not None else (src_image * H * W * 3, H, W)
+        if not 0 <= src_image < len(geo):
+            raise L.FacepathError(f"crop record of frame {src_image} outside the batch of {len(geo)}")
+        off, H, W = geo[src_image]
         it = L.FpJpegEncItem(off, H, W, sx, sy, sx + sw, sy + sh)
         empty = min(it.x1, W) <= max(it.x0, 0) or min(it.y1, H) <= max(it.y0, 0)
         out.append(None if empty else it)
@@ -366,16 +362,13 @@ def encode_crops(frames, items, n, quality=95, subsampling="4:2:0", bgr=True):
     """The first n crop records of a FacePipeline step (res["items"]) over its device frames (B, H, W, 3) u8 or RaggedFrames
     -> one JPEG file per face (bytes; None for a crop that is empty after the clamp), encoded straight from the frames in one
     device call (a ragged batch: the items address its packed buffer through the frames' descriptors)."""
-    from ...frames import RaggedFrames
-    if isinstance(frames, RaggedFrames):
-        src = frames.data
-    elif frames.device.type != "cuda" or frames.dtype != torch.uint8 or frames.dim() != 4 or not frames.is_contiguous():
+    from ...frames import frame_bytes
+    if isinstance(frames, torch.Tensor) and (frames.device.type != "cuda" or frames.dtype != torch.uint8 or frames.dim() != 4
+                                             or not frames.is_contiguous()):
         raise L.FacepathError("encode_crops takes contiguous (B, H, W, 3) uint8 frames on a HIP device")
-    else:
-        src = frames
     recs = crop_items(frames, items, n)
     take = [it for it in recs if it is not None]
-    files = iter(_encode_items(src, take, quality, subsampling, bgr))
+    files = iter(_encode_items(frame_bytes(frames), take, quality, subsampling, bgr))
     return [None if it is None else next(files) for it in recs]
 
 

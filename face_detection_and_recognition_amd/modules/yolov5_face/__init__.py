@@ -2,9 +2,8 @@
 import numpy as np
 import torch
 
-from ... import _lib as L
-from ...frames import RaggedFrames
-from ..utils.image import bind_letterbox, check_img_size, letterbox_batch, letterbox_ragged
+from ...frames import as_frames
+from ..utils.image import check_img_size, letterbox_plan
 from .general import nms_face_device, non_max_suppression_face
 from .yolo import Model, attempt_load
 
@@ -28,27 +27,10 @@ def preprocess_batch(net, frames_u8, input_size):
     staging and no fp32 canvas exists; otherwise fp_resize_normalize fills the plan's NHWC input.  frames_u8 may also be a
     RaggedFrames (frames of different sizes)."""
     in_w, in_h = tuple(map(check_img_size, input_size))
-    if isinstance(frames_u8, RaggedFrames):
-        # frames of different sizes: one letterbox launch into a u8 canvas of the input size, which the u8 plan of that size
-        # reads with identity taps (the swap and /255 stay in the stem), or straight into the fp32 plan input
-        B = len(frames_u8)
-        if net.letterbox_fusable(in_h, in_w) and in_h + in_w <= 2048:
-            plan = net.plan_for(B, in_h, in_w, frame_hw=(in_h, in_w))
-            bind_letterbox(plan, letterbox_ragged(frames_u8, (in_w, in_h)), yolo_lut(frames_u8.device), pad_value=125,
-                           swap_rb=True)
-            return plan
-        plan = net.plan_for(B, in_h, in_w)
-        letterbox_ragged(frames_u8, (in_w, in_h), yolo_lut(frames_u8.device), plan.input, pad_value=125, swap_rb=True)
-        return plan
-    frames_u8 = frames_u8.contiguous()
-    B, fh, fw, _ = frames_u8.shape
-    if net.letterbox_fusable(in_h, in_w) and fw >= 3 and fh <= 65535 and in_h + in_w <= 2048:
-        plan = net.plan_for(B, in_h, in_w, frame_hw=(fh, fw))
-        bind_letterbox(plan, frames_u8, yolo_lut(frames_u8.device), pad_value=125, swap_rb=True)
-        return plan
-    plan = net.plan_for(B, in_h, in_w)
-    letterbox_batch(frames_u8, (in_w, in_h), yolo_lut(frames_u8.device), plan.input, pad_value=125, swap_rb=True)
-    return plan
+    frames_u8 = as_frames(frames_u8, frames_u8.device)
+    fusable = net.letterbox_fusable(in_h, in_w) and in_h + in_w <= 2048
+    return letterbox_plan(frames_u8, (in_w, in_h), yolo_lut(frames_u8.device), fusable,
+                          lambda B, hw: net.plan_for(B, in_h, in_w, frame_hw=hw), lambda B: net.plan_for(B, in_h, in_w))
 
 
 def inference_pytorch_model_yolov5_face(net, cv2_img, input_size):

@@ -2,9 +2,8 @@
 from typing import Any, Callable, Tuple
 
 import numpy as np
-import torch
 
-from ...frames import RaggedFrames
+from ...frames import as_frames
 from ..models.base import Model
 from . import nms_face_device, preprocess_batch
 from .general import MAX_DET
@@ -38,12 +37,7 @@ class YOLOV5FaceModel(Model):
         overflow[i] != 0: image i had more than max_det survivors and was truncated; the caller re-runs with
         ``max_det=None`` (no cap, as non_max_suppression_face does) -- FacePipeline.step reads the flag in the same
         host transfer as the face count."""
-        dev = self.net._device()
-        if isinstance(frames, np.ndarray):
-            frames = torch.from_numpy(np.ascontiguousarray(frames))
-        if not isinstance(frames, RaggedFrames):
-            frames = frames.to(dev)
-        plan = preprocess_batch(self.net, frames, self.input_size)
+        plan = preprocess_batch(self.net, as_frames(frames, self.net._device()), self.input_size)
         z = self.net.run_plan(plan)
         self.net.last_plan = plan     # measurement / tests: the plan (and its decoded head output plan.z) of the last batch
         out, cnt, _, over = nms_face_device(z, conf_thres=0.4, iou_thres=0.5,

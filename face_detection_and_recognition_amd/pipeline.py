@@ -5,35 +5,19 @@ This is the reference's own composition (face_extraction/extract_faces_from_data
 similarity filter, run for a whole batch of frames at once: every stage is a HIP kernel launched on the
 caller's stream and the only host round trip is reading the number of faces found (it sizes the embedder batch).
 """
-import numpy as np
 import os
 
 import torch
 
 from . import _lib as L
 from . import similarity as S
-from .frames import RaggedFrames
+from .frames import batch_len, dets_to_crops
+from .frames import ragged_scale_coords_params, scale_coords_params  # noqa: F401 (re-exports)
 from .modules.mobile_facenet.utils import crops_to_input
 from .modules.age_gender import age_gender_net as AG
 from .modules.utils import align as A
-from .modules.utils.image import letterbox_geometry
 
 FACE_OFFSETS = (-6, -1, 4, 5)   # tx, ty, bx, by  (extract_faces_from_dataset.py:285-287)
-
-
-def scale_coords_params(in_size, orig_size):
-    """gain / pad of scale_coords (modules/utils/image.py:83-87) as fp32 (numpy promotes python floats to the
-    float32 array dtype)."""
-    iw, ih = in_size
-    w, h = orig_size
-    gain = min(ih / h, iw / w)
-    pad_x, pad_y = (iw - w * gain) / 2, (ih - h * gain) / 2
-    return np.float32(gain), np.float32(pad_x), np.float32(pad_y)
-
-
-def ragged_scale_coords_params(in_size, sizes):
-    """(B, 3) float32 host array: scale_coords_params of every (h, w) in sizes, row = (gain, pad_x, pad_y)."""
-    return np.array([scale_coords_params(in_size, (w, h)) for h, w in sizes], dtype=np.float32).reshape(-1, 3)
 
 
 class FacePipeline:
@@ -109,70 +93,10 @@ class FacePipeline:
         return out if self.align else out[:3]
 
     def _crops(self, frames, dets, counts):
-        lib = L.load()
-        B = len(frames) if isinstance(frames, RaggedFrames) else frames.shape[0]
-        cap = B * self.max_faces_per_frame
-        items = torch.empty((cap, 9), dtype=torch.int32, device=self.dev)
-        info = torch.empty((cap, 7), dtype=torch.float32, device=self.dev)
-        nf = torch.empty((1,), dtype=torch.int32, device=self.dev)
-        fmt = getattr(self.det, "dets_fmt", 0)
-        row = dets.shape[-1]
-        tx, ty, bx, by = FACE_OFFSETS
+        cap = batch_len(frames) * self.max_faces_per_frame
         al = A.alloc(cap, self.dev) if self.align else None
-        if fmt == 2:
-            # rows already in each frame's own pixels (MTCNN: the detector's "input size" is the frame): no scale_coords values
-            descs = frames.descs if isinstance(frames, RaggedFrames) else self._dense_descs(frames)
-            dst = (112, 112) if al is not None else (self.in_w, self.in_h)
-            lm, M, fl = (al["lmarks"], al["M"], al["flags"]) if al is not None else (None, None, None)
-            L.check(lib.fp_dets_to_crops_px(L.ptr(dets), L.ptr(counts), B, dets.shape[1], row, L.ptr(descs),
-                                            float(self.det.det_thres), float(self.det.bbox_area_thres), tx, ty, bx, by, dst[0],
-                                            dst[1], cap, L.ptr(items), L.ptr(info), L.ptr(nf), L.ptr(lm), L.ptr(M), L.ptr(fl),
-                                            L.current_stream(self.dev)), "fp_dets_to_crops_px")
-            return items, info, nf, al
-        iw, ih = self.det.input_size
-        if al is not None and (fmt == 1 and row < 15):
-            raise L.FacepathError(f"align=True needs detector rows with landmarks (got {row} columns)")
-        if isinstance(frames, RaggedFrames):
-            geom = frames.cached(("scale_coords", iw, ih), lambda: torch.from_numpy(ragged_scale_coords_params(
-                (iw, ih), frames.sizes)).to(self.dev))
-            if al is not None:
-                L.check(lib.fp_dets_to_crops_aligned_ragged(
-                    L.ptr(dets), L.ptr(counts), B, dets.shape[1], row, fmt, iw, ih, L.ptr(frames.descs), L.ptr(geom),
-                    float(self.det.det_thres), float(self.det.bbox_area_thres), tx, ty, bx, by, 112, 112, cap, L.ptr(items),
-                    L.ptr(info), L.ptr(nf), L.ptr(al["lmarks"]), L.ptr(al["M"]), L.ptr(al["flags"]),
-                    L.current_stream(self.dev)), "fp_dets_to_crops_aligned_ragged")
-                return items, info, nf, al
-            L.check(lib.fp_dets_to_crops_ragged(L.ptr(dets), L.ptr(counts), B, dets.shape[1], row, fmt, iw, ih,
-                                                L.ptr(frames.descs), L.ptr(geom), float(self.det.det_thres),
-                                                float(self.det.bbox_area_thres), tx, ty, bx, by, self.in_w, self.in_h, cap,
-                                                L.ptr(items), L.ptr(info), L.ptr(nf), L.current_stream(self.dev)),
-                    "fp_dets_to_crops_ragged")
-            return items, info, nf, None
-        _, H, W, _ = frames.shape
-        gain, px, py = scale_coords_params((iw, ih), (W, H))
-        if al is not None:
-            L.check(lib.fp_dets_to_crops_aligned(L.ptr(dets), L.ptr(counts), B, dets.shape[1], row, fmt, iw, ih, W, H,
-                                                 float(self.det.det_thres), float(self.det.bbox_area_thres), float(gain),
-                                                 float(px), float(py), tx, ty, bx, by, 112, 112, cap, L.ptr(items),
-                                                 L.ptr(info), L.ptr(nf), L.ptr(al["lmarks"]), L.ptr(al["M"]),
-                                                 L.ptr(al["flags"]), L.current_stream(self.dev)), "fp_dets_to_crops_aligned")
-            return items, info, nf, al
-        L.check(lib.fp_dets_to_crops(L.ptr(dets), L.ptr(counts), B, dets.shape[1], row, fmt, iw, ih, W, H,
-                                     float(self.det.det_thres), float(self.det.bbox_area_thres), float(gain),
-                                     float(px), float(py), tx, ty, bx, by, self.in_w, self.in_h, cap, L.ptr(items), L.ptr(info),
-                                     L.ptr(nf), L.current_stream(self.dev)), "fp_dets_to_crops")
-        return items, info, nf, None
-
-    def _dense_descs(self, frames):
-        """fp_frame_desc rows of a dense (B, H, W, 3) batch (built once per shape)."""
-        B, H, W, _ = frames.shape
-        key = (B, H, W)
-        if getattr(self, "_descs_key", None) != key:
-            d = np.zeros((B, 2), np.int64)
-            d[:, 0] = np.arange(B) * (H * W * 3)
-            d[:, 1] = H | (W << 32)
-            self._descs_key, self._descs = key, torch.from_numpy(d.view(np.uint8)).to(self.dev)
-        return self._descs
+        dst = (L.ALIGN_SIZE, L.ALIGN_SIZE) if self.align else (self.in_w, self.in_h)
+        return dets_to_crops(frames, dets, counts, self.det, dst, cap, FACE_OFFSETS, al) + (al,)
 
     def _to_input(self, frames, items, n, canvas, al, info, start=0):
         """The embedder input of faces start .. start + n: the box crops (crops_to_input), or with al the aligned faces."""
@@ -255,13 +179,10 @@ class FacePipeline:
             self._host_counts, self._host_k = [torch.empty((2,), dtype=torch.int32).pin_memory() for _ in range(2)], 0
         host = self._host_counts[self._host_k & 1]
         self._host_k += 1
-        both = nf if over is None else torch.stack([nf[0], over.sum().to(torch.int32)])
-        host[:both.numel()].copy_(both, non_blocking=True)
-        if over is None:
-            host[1] = 0
+        self._counts_to_host(nf, over, host)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.dev))
-        prev, self._pending = getattr(self, "_pending", None), (frames, items, info, host, ev, al)
+        prev, self._pending = getattr(self, "_pending", None), (frames, (items, info, nf, al), host, ev)
         return None if prev is None else self._finish(prev)
 
     def flush(self):
@@ -269,10 +190,21 @@ class FacePipeline:
         prev, self._pending = getattr(self, "_pending", None), None
         return None if prev is None else self._finish(prev)
 
-    def _finish(self, pending):
-        frames, items, info, host, ev, al = pending
-        ev.synchronize()
-        n, n_over = int(host[0]), int(host[1])
+    @staticmethod
+    def _counts_to_host(nf, over, host=None):
+        """[faces found, frames whose detections overflowed the detector's cap (0 for a detector without one)] in one host
+        transfer: enqueued into the pinned (2,) `host`, or (host None) read now -- the one host sync of step()."""
+        both = nf if over is None else torch.stack([nf[0], over.sum().to(torch.int32)])
+        if host is None:
+            return (both.tolist() + [0])[:2]
+        host[1] = 0
+        host[:both.numel()].copy_(both, non_blocking=True)
+
+    def _result(self, frames, crops, n, n_over, side=None):
+        """The step's result dict from the crop stage's outputs and the two host counts: the exact re-run after a detector
+        overflow, the cap check, embed, filter, attributes, identity, alignment records.  side = (stream, event the crops are
+        complete at): embed and everything after it run there and the dict carries the event `done` (_finish)."""
+        items, info, _, al = crops
         if n_over:                              # > MAX_DET survivors in some frame: exact re-run without a cap
             dets, counts, _ = self.detect(frames, max_det=None)
             items, info, nf, al = self._crops(frames, dets, counts)
@@ -280,37 +212,48 @@ class FacePipeline:
         cap = items.shape[0]
         if n > cap:
             raise L.FacepathError(f"{n} faces in the batch exceed max_faces_per_frame*B = {cap}")
-        if self.emb_stream is None:
+
+        def tail():
             emb = self.embed(frames, items, n, al, info)
             res = self.filter(emb)
             out = dict(n_faces=n, info=info[:n], emb=emb.clone(), items=items[:n])
             self._add_attributes(out, frames, info, n)
             self._add_identity(out)
+            return out, res
+        if side is None:
+            out, res = tail()
         else:
-            main = torch.cuda.current_stream(self.dev)
-            self.emb_stream.wait_event(ev)                 # the crops of this batch (detector stream)
-            if getattr(self, "_emb_done", None) is not None:
-                main.wait_event(self._emb_done)            # (results of the batch before are complete for the caller)
-            with torch.cuda.stream(self.emb_stream):
-                for t in (frames, items, info) + (() if al is None else tuple(al.values())):
-                    t.record_stream(self.emb_stream)
-                emb = self.embed(frames, items, n, al, info)
-                res = self.filter(emb)
-                out = dict(n_faces=n, info=info[:n], emb=emb.clone(), items=items[:n])
-                self._add_attributes(out, frames, info, n)
-                self._add_identity(out)
-                # allocated on the side stream, consumed by the caller on the main stream (after `done`): tell the caching
-                # allocator, or it hands the blocks to the next embed / filter while main-stream reads are still queued
-                attrs = tuple(out[k] for k in ("age_probs", "gender_probs") + self.IDENTITY_KEYS if k in out)
-                for t in (out["emb"],) + attrs + (tuple(res) if res is not None else ()):
-                    t.record_stream(main)
-                self._emb_done = torch.cuda.Event()
-                self._emb_done.record(self.emb_stream)
-            out["done"] = self._emb_done                   # the caller waits for this event before it reads the results
+            out, res = self._on_side_stream(tail, side, (frames, items, info) + (() if al is None else tuple(al.values())))
         self._add_align(out, al, n)
         if res is not None:
             out.update(best=res[0], arg=res[1], keep=res[2])
         return out
+
+    def _on_side_stream(self, tail, side, inputs):
+        """tail() on the side stream, ordered after the crops' event and before the caller's next use of the main stream."""
+        stream, ev = side
+        main = torch.cuda.current_stream(self.dev)
+        stream.wait_event(ev)                          # the crops of this batch (detector stream)
+        if getattr(self, "_emb_done", None) is not None:
+            main.wait_event(self._emb_done)            # (results of the batch before are complete for the caller)
+        with torch.cuda.stream(stream):
+            for t in inputs:
+                t.record_stream(stream)
+            out, res = tail()
+            # allocated on the side stream, consumed by the caller on the main stream (after `done`): tell the caching
+            # allocator, or it hands the blocks to the next embed / filter while main-stream reads are still queued
+            attrs = tuple(out[k] for k in ("age_probs", "gender_probs") + self.IDENTITY_KEYS if k in out)
+            for t in (out["emb"],) + attrs + (tuple(res) if res is not None else ()):
+                t.record_stream(main)
+            self._emb_done = torch.cuda.Event()
+            self._emb_done.record(stream)
+        out["done"] = self._emb_done                   # the caller waits for this event before it reads the results
+        return out, res
+
+    def _finish(self, pending):
+        frames, crops, host, ev = pending
+        ev.synchronize()
+        return self._result(frames, crops, int(host[0]), int(host[1]), None if self.emb_stream is None else (self.emb_stream, ev))
 
     ATTR_CAP_STEP = 64    # the attribute plan's capacity grows in steps of this many crops (about 3.8 MB of arena each)
 
@@ -362,25 +305,6 @@ class FacePipeline:
         ``emb`` is a copy (the embedder's output lives in its plan arena and the next step overwrites it).
         beside: use the detector plan of the two-stream steps (measurement: bench.py's per-op probe pass)."""
         dets, counts, over = self.detect(frames, beside=beside)
-        items, info, nf, al = self._crops(frames, dets, counts)
-        # the one host sync of the step: the face count (sizes the embedder batch) and the detector's overflow flag
-        if over is None:
-            n, n_over = int(nf.item()), 0
-        else:
-            n, n_over = torch.stack([nf[0], over.sum().to(torch.int32)]).tolist()
-        if n_over:                              # > MAX_DET survivors in some frame: exact re-run without a cap
-            dets, counts, _ = self.detect(frames, max_det=None)
-            items, info, nf, al = self._crops(frames, dets, counts)
-            n = int(nf.item())
-        cap = items.shape[0]
-        if n > cap:
-            raise L.FacepathError(f"{n} faces in the batch exceed max_faces_per_frame*B = {cap}")
-        emb = self.embed(frames, items, n, al, info)
-        res = self.filter(emb)
-        out = dict(n_faces=n, info=info[:n], emb=emb.clone(), items=items[:n])
-        self._add_attributes(out, frames, info, n)
-        self._add_identity(out)
-        self._add_align(out, al, n)
-        if res is not None:
-            out.update(best=res[0], arg=res[1], keep=res[2])
-        return out
+        crops = self._crops(frames, dets, counts)
+        n, n_over = self._counts_to_host(crops[2], over)     # (the face count sizes the embedder batch)
+        return self._result(frames, crops, n, n_over)

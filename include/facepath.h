@@ -1010,7 +1010,7 @@ int fp_mtcnn_stage3(const int32_t* boxes, int n_frames, int cap, const int32_t* 
                     void* scratch, size_t scratch_bytes, void* stream);
 /*
  * MTCNN rows -> face crops: fp_dets_to_crops_ragged / fp_dets_to_crops_aligned_ragged for rows that are ALREADY in each frame's
- * own pixels (dets [B][max_dets][row_floats >= 15] = fp_mtcnn_stage3's rows; "fmt 2" of csrc/crops.h).  conf > det_thres, the
+ * own pixels (dets [B][max_dets][row_floats >= 15] = fp_mtcnn_stage3's rows; "fmt 2" of csrc/align.hip).  conf > det_thres, the
  * box's share of the FRAME (100 * area / (w h) > area_thres; info[6] = the fraction), clip to the frame, round half-to-even,
  * then the same crop arithmetic, items and face_info.  lmarks / M / flags all NULL: box crops; all given: also the five
  * landmarks (clipped to the frame), the alignment transform and flags of fp_dets_to_crops_aligned.  Dense batches pass descs

@@ -344,11 +344,11 @@ def _synth_dets(rng, fmt, B, max_dets, sizes, in_size):
     return dets, counts
 
 
-def _device_crops(lib, dev, dets, counts, frames, in_size, fmt, thr, aligned):
+def _device_crops(lib, dev, dets, counts, frames, in_size, fmt, thr, aligned, cap=None):
     from face_detection_and_recognition_amd.frames import RaggedFrames
     from face_detection_and_recognition_amd.pipeline import ragged_scale_coords_params, scale_coords_params
     B, max_dets, row = dets.shape
-    cap = B * max_dets
+    cap = cap or B * max_dets
     d, c = torch.from_numpy(dets).to(dev), torch.from_numpy(counts).to(dev)
     items = torch.full((cap, 9), -7, dtype=torch.int32, device=dev)
     info = torch.full((cap, 7), -7.0, dtype=torch.float32, device=dev)
@@ -441,6 +441,36 @@ def test_device_equals_emulator_and_crop_records_are_unchanged(lib, dev, fmt):
     for k in ("items", "info", "lmarks", "M", "flags"):
         assert _bits(a[0][k]).tobytes() == _bits(b[0][k]).tobytes(), k
     assert np.array_equal(a[1], b[1])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fmt", [FMT_BLAZE, FMT_YOLO])
+def test_crops_carry_the_slot_across_chunks_of_256_frames(lib, dev, fmt):
+    """300 ragged frames: the kernel walks them in two chunks of 256 and carries the face count from one to the next.  items /
+    info (plain and aligned), lmarks / M / flags and n_faces equal the host emulator's bit for bit; with max_faces below the
+    count n_faces still reports every face and the rows up to the cap are the same."""
+    from face_detection_and_recognition_amd.frames import RaggedFrames
+    rng = np.random.default_rng(40 + fmt)
+    in_size = (256, 256) if fmt == FMT_BLAZE else (640, 640)
+    thr = 0.7 if fmt == FMT_BLAZE else 0.4
+    B, cap = 300, 512
+    sizes = [[(40, 64), (33, 47), (64, 40)][i % 3] for i in range(B)]
+    frames = RaggedFrames.from_list([np.zeros((h, w, 3), np.uint8) for h, w in sizes], dev)
+    dets, counts = _synth_dets(rng, fmt, B, 2, sizes, in_size)
+    emu = A.emulate_crops(dets, counts, sizes, in_size, fmt, thr, 0.12, max_faces=cap)
+    n = emu["info"].shape[0]
+    first = int((emu["info"][:, 0] < 256).sum())
+    assert 0 < first < n < cap, (first, n)                       # faces on both sides of the chunk boundary, none cut
+    for k, want in [(cap, emu), (first + (n - first) // 2, None)]:
+        want = want or A.emulate_crops(dets, counts, sizes, in_size, fmt, thr, 0.12, max_faces=k)
+        assert want["info"].shape[0] == min(n, k)
+        plain = _device_crops(lib, dev, dets, counts, frames, in_size, fmt, thr, False, cap=k)
+        got = _device_crops(lib, dev, dets, counts, frames, in_size, fmt, thr, True, cap=k)
+        assert plain["n"] == got["n"] == n, k                    # the true count, above the cap too
+        for key in ("items", "info"):
+            assert _bits(plain[key]).tobytes() == _bits(want[key]).tobytes(), (k, key)
+        for key in ("items", "info", "lmarks", "M", "flags"):
+            assert _bits(got[key]).tobytes() == _bits(want[key]).tobytes(), (k, key)
 
 
 @pytest.mark.gpu

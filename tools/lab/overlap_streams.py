@@ -32,7 +32,7 @@ def main():
 
     def front(k):
         with torch.cuda.stream(sA):
-            dets, counts = pipe.detect(frames)
+            dets, counts, _ = pipe.detect(frames)
             items, info, nf = pipe.crops(frames, dets, counts)
             hn = torch.empty((1,), dtype=torch.int32).pin_memory()
             hn.copy_(nf, non_blocking=True)

@@ -31,7 +31,7 @@ def main():
     pipe = FacePipeline(det, emb, ref, tau=0.3)
     out = pipe.step(frames)
     print("faces", out["n_faces"], "per frame", out["n_faces"] / B, "keep", int(out["keep"].sum()))
-    dets, counts = pipe.detect(frames)
+    dets, counts, _ = pipe.detect(frames)
     cand, ccount = det.net._last_candidates
     print("candidates/frame", float(ccount.float().mean()), "dets/frame", float(counts.float().mean()))
 

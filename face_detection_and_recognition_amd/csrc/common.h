@@ -161,13 +161,13 @@ bool fp_conv3_eligible(const fp_op& op);  // dense 3x3 pad-1 convs on the LDS-im
 int fp_launch_conv3(const fp_op& op, const fp_launch& L);
 
 // floats of the weight blob behind an op's offsets (the span checks of fp_plan_validate)
-long fp_stemdw_w_floats(const fp_op& op);
-long fp_convx6_w_floats(const fp_op& op);
-long fp_dwpwx6_w_floats(const fp_op& op);
+int64_t fp_stemdw_w_floats(const fp_op& op);
+int64_t fp_convx6_w_floats(const fp_op& op);
+int64_t fp_dwpwx6_w_floats(const fp_op& op);
 int64_t fp_blazechain_w_floats(const fp_op& op);
-long fp_dwblock_x6_we_floats(const fp_op& op);   // behind w_off / slope_off of a DWBLOCK with FP_OPF_SPLIT3
-long fp_dwblock_x6_wp_floats(const fp_op& op);
-long fp_shufdown_w_floats(const fp_op& op);
-long fp_shufunit_w_floats(const fp_op& op);
-long fp_ystem2_w_floats(const fp_op& op);
+int64_t fp_dwblock_x6_we_floats(const fp_op& op);   // behind w_off / slope_off of a DWBLOCK with FP_OPF_SPLIT3
+int64_t fp_dwblock_x6_wp_floats(const fp_op& op);
+int64_t fp_shufdown_w_floats(const fp_op& op);
+int64_t fp_shufunit_w_floats(const fp_op& op);
+int64_t fp_ystem2_w_floats(const fp_op& op);
 int fp_ystem_nb2(const fp_op& op);   // 16-channel column blocks of ystem_kernel's packed stem_1 weights

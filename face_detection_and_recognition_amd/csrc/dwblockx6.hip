@@ -1104,8 +1104,8 @@ static bool dwblock_x6_supported(const fp_op& op) {
 }
 
 // floats of the weight blob behind w_off / slope_off for a split DWBLOCK (capi.cpp bounds checks)
-long fp_dwblock_x6_we_floats(const fp_op& op) { return (long)op.Cmid * op.Cin * 3 / 2; }
-long fp_dwblock_x6_wp_floats(const fp_op& op) { return (long)op.Cmid * op.Cout * 3 / 2 + 2L * op.Cout; }
+int64_t fp_dwblock_x6_we_floats(const fp_op& op) { return (long)op.Cmid * op.Cin * 3 / 2; }
+int64_t fp_dwblock_x6_wp_floats(const fp_op& op) { return (long)op.Cmid * op.Cout * 3 / 2 + 2L * op.Cout; }
 
 int fp_launch_dwblock_x6(const fp_op& op, const fp_launch& L) {
   if (!dwblock_x6_supported(op)) return FP_ERR_UNSUPPORTED;

@@ -258,7 +258,7 @@ static bool dwpwx6_eligible(const fp_op& op) {
   return true;
 }
 
-long fp_dwpwx6_w_floats(const fp_op& op) { return (long)op.Cin * op.Cout * 3 / 2 + 2L * op.Cout; }
+int64_t fp_dwpwx6_w_floats(const fp_op& op) { return (long)op.Cin * op.Cout * 3 / 2 + 2L * op.Cout; }
 
 int fp_launch_dwpwx6(const fp_op& op, const fp_launch& L) {
   if (!dwpwx6_eligible(op)) return FP_ERR_UNSUPPORTED;

@@ -615,7 +615,7 @@ static bool convx6_eligible(const fp_op& op) {
   return true;
 }
 
-long fp_convx6_w_floats(const fp_op& op) {
+int64_t fp_convx6_w_floats(const fp_op& op) {
   int nt16, npad;
   general_tiles(op.Cout, &nt16, &npad);
   const long slabs = op.Cin < 32 ? ((long)op.KH * op.KW * op.Cin + 31) / 32 : (long)op.KH * op.KW * ((op.Cin + 31) / 32);

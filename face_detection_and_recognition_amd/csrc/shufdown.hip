@@ -515,7 +515,7 @@ static bool shufdown_supported(const fp_op& op) {
   return tiles > 0 && tiles < (1L << 31);
 }
 
-long fp_shufdown_w_floats(const fp_op& op) { return op.Cin == 32 && op.Cmid == 64 ? SDCfg<1, 64>::TOTAL : 0; }
+int64_t fp_shufdown_w_floats(const fp_op& op) { return op.Cin == 32 && op.Cmid == 64 ? SDCfg<1, 64>::TOTAL : 0; }
 
 int fp_launch_shufdown(const fp_op& op, const fp_launch& L) {
   if (!shufdown_supported(op)) return FP_ERR_UNSUPPORTED;
@@ -550,7 +550,7 @@ static bool shufunit_supported(const fp_op& op) {
   return tiles > 0 && tiles < (1L << 31);
 }
 
-long fp_shufunit_w_floats(const fp_op& op) { return op.Cmid == 64 ? SUCfg<64>::TOTAL : 0; }
+int64_t fp_shufunit_w_floats(const fp_op& op) { return op.Cmid == 64 ? SUCfg<64>::TOTAL : 0; }
 
 int fp_launch_shufunit(const fp_op& op, const fp_launch& L) {
   if (!shufunit_supported(op)) return FP_ERR_UNSUPPORTED;

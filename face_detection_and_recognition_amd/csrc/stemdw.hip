@@ -295,7 +295,7 @@ static bool stemdw_supported(const fp_op& op) {
 }
 
 // floats behind w_off: the packed fp32 weights (40 x 64), or with FP_OPF_SPLIT3 three bf16 planes [4][3][16][32]
-long fp_stemdw_w_floats(const fp_op& op) { return (op.flags & FP_OPF_SPLIT3) ? 4 * 3 * 16 * 32 / 2 : 40 * 64; }
+int64_t fp_stemdw_w_floats(const fp_op& op) { return (op.flags & FP_OPF_SPLIT3) ? 4 * 3 * 16 * 32 / 2 : 40 * 64; }
 
 int fp_launch_stemdw(const fp_op& op, const fp_launch& L) {
   if (!stemdw_supported(op)) return FP_ERR_UNSUPPORTED;

@@ -220,7 +220,7 @@ static bool ystem2_supported(const fp_op& op) {
   return tiles > 0 && tiles < (1L << 31);
 }
 
-long fp_ystem2_w_floats(const fp_op&) { return YS2::TOTAL; }
+int64_t fp_ystem2_w_floats(const fp_op&) { return YS2::TOTAL; }
 
 int fp_launch_ystem2(const fp_op& op, const fp_launch& L) {
   if (!ystem2_supported(op)) return FP_ERR_UNSUPPORTED;

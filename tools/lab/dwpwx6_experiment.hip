@@ -202,7 +202,7 @@ bool fp_dwpwx6_eligible(const fp_op& op) {
   return pick_tr(op, &rows, &mtp, &sbytes) > 0;
 }
 
-long fp_dwpwx6_w_floats(const fp_op& op) { return (long)op.Cin * op.Cout * 3 / 2 + 2L * op.Cout; }
+int64_t fp_dwpwx6_w_floats(const fp_op& op) { return (long)op.Cin * op.Cout * 3 / 2 + 2L * op.Cout; }
 
 int fp_launch_dwpwx6(const fp_op& op, const float* weights, float* arena, hipStream_t s) {
   if (!fp_dwpwx6_eligible(op)) return FP_ERR_UNSUPPORTED;

@@ -58,11 +58,7 @@ __global__ __launch_bounds__(256) void blazeblock_kernel(BlazeArgs p) {
   // XCD-aware tile order: blocks b, b+8, b+16.. share an XCD (round-robin dispatch), so give each XCD a
   // contiguous range of tiles: vertically adjacent rows (the 3x3 halo) then meet in the same L2.  Bijective
   // for any ntiles (cdna_hip_programming.md T1).
-  int tile;
-  {
-    const int b = blockIdx.x, q = p.ntiles / 8, r = p.ntiles % 8, xcd = b & 7, k = b >> 3;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int tile = (int)fp_xcd_block();          // the grid is p.ntiles blocks
   const long m0 = (long)tile * TM;
 
   // stage the pointwise weights
@@ -280,11 +276,7 @@ __global__ __launch_bounds__(256, S == 1 ? 3 : 2) void blazeblock_persist_kernel
 
   // XCD-aware position of this block inside a window of G tiles (bijective for any G)
   const int G = gridDim.x;
-  int pos;
-  {
-    const int b = blockIdx.x, q = G / 8, rr = G % 8, xcd = b & 7, k = b >> 3;
-    pos = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + k;
-  }
+  const int pos = (int)fp_xcd_block();
 
   // Window loads use 32-bit BYTE offsets from the (wave-uniform, SGPR) tensor base: one address register and one
   // v_add_u32 per load instead of a 64-bit multiply-add each (the launcher checks the tensor is < 4 GiB).

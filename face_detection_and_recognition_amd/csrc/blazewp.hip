@@ -7,8 +7,10 @@
 // 24 -> 24 blocks on 128 x 128 / 64 x 64 maps (55 % of the back model's bytes) and blazeblock_wps_kernel for the
 // 48 -> 48 / 96 -> 96 blocks on 32 x 32 / 16 x 16 maps.  Both give a WAVE a tile of 32 pixels end to end (window ->
 // depthwise -> LDS -> MFMA 1x1 -> shortcut -> ReLU -> store) with no workgroup barrier in the loop; FINDINGS.md findings
-// 14-15 record what that bought and why.
-#include "common.h"
+// 14-15 record what that bought and why.  blazeblock_wp_kernel's depthwise, 1x1, epilogue piece, row loads and staging are the
+// helpers of blazerow.h, shared with the pair kernels (blazepair.hip); blazeblock_wps_kernel has its own MFMA operand order and
+// channel passes.
+#include "blazerow.h"
 
 namespace {
 // ---------------------------------------------------------------------------------------------------------------
@@ -53,37 +55,32 @@ struct BlazeWpArgs {
 template <int C, int R>
 __global__ __launch_bounds__(256, 3) void blazeblock_wp_kernel(BlazeWpArgs p) {
   static_assert(C % 8 == 0 && C <= 32, "one 32-column n tile, K a multiple of 8");
-  constexpr int LDT = C + 4, C4 = C / 4, NIT = 8 * C4, KG = C / 8;
+  constexpr int LDT = C + 4, KG = C / 8;
   constexpr int WAVE_FLOATS = 2 * 32 * LDT + 32 * C;      // A tile, shortcut tile, output tile
   constexpr int NST = (32 * C / 4) / 64;                   // 16-byte stores per lane and row
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Ws = smem;                                        // [10][C] depthwise taps + bias
   float* Bp = Ws + 10 * C;                                 // [32]
   float* Wv = Bp + 32;                                     // 4 wave regions (first used to stage the 1x1 weights)
-  const int tid = threadIdx.x, lane = tid & 63;
+  const int tid = threadIdx.x;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int lr = lane & 31, h = lane >> 5;
+  const BlazeLanes<C> ln(tid);                             // depthwise item / MFMA pixel of this lane (blazerow.h)
+  const int lane = ln.lane, lr = ln.lr, h = ln.h;
 
-  for (int i = tid; i < (10 * C) / 4; i += 256)
-    *(f32x4*)&Ws[i * 4] = (i * 4 < 9 * C) ? *(const f32x4*)(p.wd + i * 4) : *(const f32x4*)(p.bd + (i * 4 - 9 * C));
+  blaze_stage_taps<1, C>(Ws, p.wd, p.bd, tid);
   if (tid < 32) Bp[tid] = tid < C ? p.bp[tid] : 0.f;
-  for (int i = tid; i < KG * 2 * 32; i += 256) *(f32x4*)&Wv[i * 4] = *(const f32x4*)(p.wp + i * 4);
+  blaze_stage_copy(Wv, p.wp, KG * 2 * 32 * 4, tid);
   __syncthreads();
   f32x4 bfrag[KG];                                         // this lane's B fragments: k-quad 2*kq + h, column lr
-#pragma unroll
-  for (int kq = 0; kq < KG; ++kq) bfrag[kq] = *(const f32x4*)&Wv[((kq * 2 + h) * 32 + lr) * 4];
+  blaze_load_bfrag<KG, 32>(bfrag, Wv, h, lr);
   __syncthreads();                                         // staging area becomes the wave regions
 
   float* At = Wv + wv * WAVE_FLOATS;                       // [32][LDT]
   float* St = At + 32 * LDT;                               // [32][LDT]
   float* Ot = St + 32 * LDT;                               // [32][C]
 
-  // depthwise item of this lane: pixels 4g .. 4g+3 of the strip, channels 4c4 .. 4c4+3 (lanes >= NIT repeat item 0
-  // and write nothing)
-  const bool dw_lane = lane < NIT;
-  const int la = dw_lane ? lane : 0;
-  const int g = la / C4, c4 = la - g * C4;
-  const unsigned voff_in = (unsigned)((4 * g * C + 4 * c4) * 4);
+  const int g = ln.g, c4 = ln.c4;
+  const unsigned voff_in = ln.voff_in;
   const unsigned voff_out = (unsigned)lane * 16u;
   const float* wl = &Ws[4 * c4];                           // this lane's taps [k][4] at wl + k*C, bias at k = 9
   const f32x4 pbias = *(const f32x4*)&Bp[4 * c4];          // pointwise bias of this lane's channels: rides the shortcut
@@ -91,11 +88,7 @@ __global__ __launch_bounds__(256, 3) void blazeblock_wp_kernel(BlazeWpArgs p) {
   // XCD-aware order: block b runs on XCD b % 8; each XCD gets a contiguous range of every round's tiles, so the bands
   // above and below a tile (its halo rows) are fetched into the same L2
   const int G = gridDim.x;
-  int pos;
-  {
-    const int b = blockIdx.x, q = G / 8, rr = G % 8, xcd = b & 7, k = b >> 3;
-    pos = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + k;
-  }
+  const int pos = (int)fp_xcd_block();
 
   // byte offsets from p.in / p.out, all scalar: window origin (y0 - 1, x0 - 1) and first output pixel of a tile
   const char* inb = (const char*)p.in;
@@ -123,11 +116,7 @@ __global__ __launch_bounds__(256, 3) void blazeblock_wp_kernel(BlazeWpArgs p) {
   if (t < t_end) {
     locate(t, in_px, out_px);
 #pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
-      const char* rowp = inb + fp_uniform(in_px + ky * in_rb);
-#pragma unroll
-      for (int j = 0; j < 6; ++j) x[ky][j] = *(const f32x4*)(rowp + voff_in + j * C * 4);
-    }
+    for (int ky = 0; ky < 3; ++ky) blaze_load_row<C>(x[ky], inb + fp_uniform(in_px + ky * in_rb), voff_in);
   }
   bool have_prev = false;
   while (t < t_end) {
@@ -139,22 +128,9 @@ __global__ __launch_bounds__(256, 3) void blazeblock_wp_kernel(BlazeWpArgs p) {
       const int s0 = r % 3, s1 = (r + 1) % 3, s2 = (r + 2) % 3;   // ring slots of rows y - 1, y, y + 1 (static: unrolled)
       // ---- depthwise + shortcut -> A, S (this wave's region) ----
       {
-        const f32x4 dbias = *(const f32x4*)(wl + 9 * C);
-        f32x4 acc[4] = {dbias, dbias, dbias, dbias};
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-          const int sl = ky == 0 ? s0 : ky == 1 ? s1 : s2;
-          const f32x4 w0 = *(const f32x4*)(wl + (ky * 3 + 0) * C);
-          const f32x4 w1 = *(const f32x4*)(wl + (ky * 3 + 1) * C);
-          const f32x4 w2 = *(const f32x4*)(wl + (ky * 3 + 2) * C);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {   // three statements: each contracts to one packed FMA on the accumulator
-            acc[q] += x[sl][q] * w0;
-            acc[q] += x[sl][q + 1] * w1;
-            acc[q] += x[sl][q + 2] * w2;
-          }
-        }
-        if (dw_lane) {
+        f32x4 acc[4];
+        blaze_dw3x3<1, C, 1>(acc, x[s0], x[s1], x[s2], wl);
+        if (ln.dw_lane) {
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             *(f32x4*)&At[(4 * g + q) * LDT + 4 * c4] = acc[q];
@@ -170,51 +146,20 @@ __global__ __launch_bounds__(256, 3) void blazeblock_wp_kernel(BlazeWpArgs p) {
       }
       st_px = fp_uniform(out_px + r * out_rb);
       if (r + 1 < R) {                  // row y + 2 replaces row y - 1 in the ring
-        const char* rowp = inb + fp_uniform(in_px + (r + 3) * in_rb);
-#pragma unroll
-        for (int j = 0; j < 6; ++j) x[s0][j] = *(const f32x4*)(rowp + voff_in + j * C * 4);
+        blaze_load_row<C>(x[s0], inb + fp_uniform(in_px + (r + 3) * in_rb), voff_in);
       } else if (tn < t_end) {          // last row of the band: the next tile's first three rows
 #pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-          const char* rowp = inb + fp_uniform(in_nx + ky * in_rb);
-#pragma unroll
-          for (int j = 0; j < 6; ++j) x[ky][j] = *(const f32x4*)(rowp + voff_in + j * C * 4);
-        }
+        for (int ky = 0; ky < 3; ++ky) blaze_load_row<C>(x[ky], inb + fp_uniform(in_nx + ky * in_rb), voff_in);
       }
       // ---- 1x1 on the MFMA pipe ----
-      f32x16 m0, m1;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) m0[i] = 0.f, m1[i] = 0.f;
-      const float* arow = &At[lr * LDT + 4 * h];
-#pragma unroll
-      for (int kq = 0; kq < KG; ++kq) {
-        const f32x4 a = *(const f32x4*)(arow + kq * 8);
-        // operands swapped: D^T = W^T x A^T, so lane (lr, h) holds PIXEL lr and channels (k & 3) + 8*(k >> 2) + 4h --
-        // 16-byte pieces of a row-major pixel: the epilogue is 3 x (b128 read, adds, b128 write) instead of 16 + 16
-        // scalar LDS accesses (csrc/blazepair.hip has the same form)
-        m0 = __builtin_amdgcn_mfma_f32_32x32x2f32(bfrag[kq][0], a[0], m0, 0, 0, 0);
-        FP_MFMA_ORDER();
-        m1 = __builtin_amdgcn_mfma_f32_32x32x2f32(bfrag[kq][1], a[1], m1, 0, 0, 0);
-        FP_MFMA_ORDER();
-        m0 = __builtin_amdgcn_mfma_f32_32x32x2f32(bfrag[kq][2], a[2], m0, 0, 0, 0);
-        FP_MFMA_ORDER();
-        m1 = __builtin_amdgcn_mfma_f32_32x32x2f32(bfrag[kq][3], a[3], m1, 0, 0, 0);
-        FP_MFMA_ORDER();
-      }
+      f32x16 m0, m1;                    // operands swapped: lane (lr, h) holds PIXEL lr, channels 8j + 4h .. + 3 (blazerow.h)
+      blaze_pw_swapped<KG>(&At[lr * LDT + 4 * h], bfrag, m0, m1);
       // ---- shortcut + ReLU -> output tile: pixel lr, channels 8j + 4h .. + 3 ----
       {
         const float* spx = &St[lr * LDT + 4 * h];
         float* opx = &Ot[lr * C + 4 * h];
 #pragma unroll
-        for (int j = 0; j < C / 8; ++j) {
-          const f32x4 sv = *(const f32x4*)(spx + 8 * j);
-          f32x4 v;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = (m0[4 * j + e] + m1[4 * j + e]) + sv[e];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
-          *(f32x4*)(opx + 8 * j) = v;
-        }
+        for (int j = 0; j < C / 8; ++j) *(f32x4*)(opx + 8 * j) = blaze_relu_piece(m0, m1, j, *(const f32x4*)(spx + 8 * j));
       }
       have_prev = true;
     }
@@ -271,8 +216,7 @@ __global__ __launch_bounds__(256, C <= 48 ? 2 : 1) void blazeblock_wps_kernel(Bl
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lr = lane & 31, h = lane >> 5;
 
-  for (int i = tid; i < (10 * C) / 4; i += 256)
-    *(f32x4*)&Ws[i * 4] = (i * 4 < 9 * C) ? *(const f32x4*)(p.wd + i * 4) : *(const f32x4*)(p.bd + (i * 4 - 9 * C));
+  blaze_stage_taps<1, C>(Ws, p.wd, p.bd, tid);
   if (tid < NPAD) Bp[tid] = tid < C ? p.bp[tid] : 0.f;
   for (int i = tid; i < C4T * NPAD; i += 256) *(f32x4*)&Bs[i * 4] = *(const f32x4*)(p.wp + (long)i * 4);
   __syncthreads();                                          // the only workgroup barrier
@@ -294,12 +238,7 @@ __global__ __launch_bounds__(256, C <= 48 ? 2 : 1) void blazeblock_wps_kernel(Bl
   const long in_rb = (long)p.in_rp * 4;
 
   // XCD-aware order of the waves' runs (neighbouring tiles share halo rows: same L2)
-  const int G = gridDim.x;
-  int pos;
-  {
-    const int b = blockIdx.x, q = G / 8, rr = G % 8, xcd = b & 7, k = b >> 3;
-    pos = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + k;
-  }
+  const int pos = (int)fp_xcd_block();
   // byte offsets (scalar) of pixel (y0, 0) of a tile in the input and the output
   auto locate = [&](int t, long& ic, long& oo) {
     const unsigned img = fp_fastdiv((unsigned)t, p.tpi_div), k = (unsigned)t - img * (unsigned)p.tiles_per_img;

@@ -115,7 +115,7 @@ static int spans_dwblock(const fp_op& op, size_t wf, size_t) {
 }
 static int spans_blazepair(const fp_op& op, size_t wf, size_t) {
   // both blocks' parameters back to back (facepath.h BLAZEPAIR)
-  // stride 2: the second block is the stride-2 block behind a stride-1 block (24 -> 24 or 24 -> 48; blazepairs2.hip)
+  // stride 2: the second block is the stride-2 block behind a stride-1 block (24 -> 24 or 24 -> 48; blazepair_s2_kernel in blazepair.hip)
   const int64_t pw2 = op.stride == 2 && op.Cout == 48 ? 2 * 768 : 768, c2 = op.stride == 2 ? op.Cout : 24;
   return span_ok(op.w_off, 2 * 9 * 24, wf) && span_ok(op.scale_off, 2 * 24, wf) && span_ok(op.slope_off, 768 + pw2, wf) &&
                  span_ok(op.bias_off, 24 + c2, wf) ? FP_OK : FP_ERR_BOUNDS;

@@ -65,7 +65,7 @@ class BlazeBlock(_NoCompute):
         return BlazeBlock.PAIR and self._pair_taken(other, 1, pb, x)
 
     PAIR_S2 = os.environ.get("FP_BLAZE_PAIR_S2", "1") == "1"   # class-wide switch: the single stride-1 24 -> 24 block that ends a stage and
-                                                                # the stride-2 block behind it as ONE op (csrc/blazepairs2.hip)
+                                                                # the stride-2 block behind it as ONE op (csrc/blazepair.hip)
 
     def pairs_with_s2(self, other, pb, x):
         """True if self (stride 1, 24 -> 24) followed by the stride-2 block `other`, fed the row-padded view x, runs as one

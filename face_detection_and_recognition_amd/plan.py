@@ -608,7 +608,7 @@ class PlanBuilder:
         """A stride-1 24 -> 24 BlazeBlock and the STRIDE-2 BlazeBlock behind it (blazeface.py:12-47) as ONE op (FP_OP_BLAZEPAIR
         with stride = 2): blocks = ((dw_w, dw_b, pw_w, pw_b) of the stride-1 block, the same of the stride-2 block); the
         full-size tensor between them never reaches HBM, `out` is the half-size map (dense or row-padded, ld = its channels).
-        None (nothing emitted) if the launcher refuses the op (csrc/blazepairs2.hip)."""
+        None (nothing emitted) if the launcher refuses the op (csrc/blazepair.hip)."""
         pix, opix, cout2 = x.H * x.W, out.H * out.W, blocks[1][2].shape[0]
         # SURVEY 8(d): the stride-1 block's four tensor passes + the stride-2 block's (input, dw output, 1x1 input, output)
         return self._blazepair(x, blocks, out, 2, 4 * self.N * (pix * 24 * 4 + pix * 24 + opix * 24 + opix * 24 + opix * cout2))

@@ -287,7 +287,7 @@ typedef struct fp_op {
  *            block's shortcut is its own input).  The two blocks' parameters back to back, each as for BLAZEBLOCK:
  *            w_off -> [2][9][24] taps, scale_off -> [2][24] depthwise bias, slope_off -> [2] packed 1x1 (K = 24,
  *            Npad = 32: 768 floats each), bias_off -> [2][24] 1x1 bias.
- *            With stride = 2 (ABI 8; csrc/blazepairs2.hip) the SECOND block is the stride-2 block that ends a stage
+ *            With stride = 2 (ABI 8; blazepair_s2_kernel in csrc/blazepair.hip) the SECOND block is the stride-2 block that ends a stage
  *            (blazeface.py:34-47: F.pad(0, 2, 0, 2), depthwise stride 2, shortcut = 2 x 2 max pool padded on channels): in = x
  *            as above, out = y2 on the H/2 x W/2 map (dense or FP_OPF_OUT_ROWPAD, out_ld = Cout), Cout = 24 or 48, pad_t =
  *            pad_l = 0, res_mode = FP_RES_POOL2_BEFORE_ACT; parameters as above with the second block's 1x1 packed for its

@@ -328,7 +328,7 @@ def test_blazepair_two_blocks_in_one_kernel_vs_oracle(dev, hw, n, out_rp):
     ((40, 128), 48, 1, False),      # 20 output rows = five bands of four
 ])
 def test_blazepair_s2_stride1_plus_stride2_block_vs_oracle(dev, hw, cout2, n, out_rp):
-    """FP_OP_BLAZEPAIR with stride = 2 (csrc/blazepairs2.hip): a stride-1 24 -> 24 BlazeBlock and the stride-2 block behind it
+    """FP_OP_BLAZEPAIR with stride = 2 (csrc/blazepair.hip): a stride-1 24 -> 24 BlazeBlock and the stride-2 block behind it
     (24 -> 24 / 24 -> 48: F.pad(0, 2, 0, 2), depthwise stride 2, shortcut = channel-padded 2 x 2 max pool) in one kernel, the
     full-size tensor between them in an LDS ring -- against blazeface_ref._blaze_block applied twice (torch fp32 on the CPU;
     blazeface.py:12-47) and against the two separate launches (same arithmetic per block: 2e-6 of scale).  The last output
@@ -377,6 +377,57 @@ def test_blazepair_s2_stride1_plus_stride2_block_vs_oracle(dev, hw, cout2, n, ou
     assert rel_err(outs[True], ref) < 1e-5
     np.testing.assert_allclose(outs[True], ref, rtol=1e-5, atol=2e-5)
     assert rel_err(outs[True], outs[False]) < 2e-6
+
+
+@pytest.mark.parametrize("stride,cout2,win", [
+    (1, 24, (13, 34)),      # 21 rows = two bands of 11 at rows 13 and 23: the second is moved up onto row 23
+    (1, 24, (13, 39)),      # 26 rows = three bands of 9 at rows 13, 22, 30: nine bands in all, the last workgroup's second half idle
+    (2, 24, (5, 18)),       # 13 rows of y2 = three bands of 5 at rows 5, 10, 13; nine bands in all
+    (2, 48, (5, 18)),
+])
+def test_blazepair_row_window_writes_its_rows_only(dev, stride, cout2, win):
+    """FP_OP_BLAZEPAIR under a row window (include/facepath.h "Row windows") at the smallest shape, 64 x 64 with three images: the
+    window touches neither the first nor the last row and its height is no multiple of the band count fp_window_bands picks, so
+    the last band overlaps its neighbour.  The window's rows equal the unwindowed run bit for bit, every row outside it is
+    untouched (or holds what the unwindowed run writes there), and the pads of the row-padded output are still zero."""
+    H = W = 64
+    n, lo, end = 3, win[0], win[1]
+    rng = np.random.default_rng(1300 + stride + cout2 + end)
+    blks = [BlazeBlock(24, 24), BlazeBlock(24, cout2, stride=stride)]
+    for k, b in enumerate(blks):
+        b.load_state_dict(synth_state_dict(b.state_dict(), 1900 + k))
+    x = torch.from_numpy(rng.normal(0, 1, (n, H, W, 24)).astype(np.float32)).to(dev)
+    sentinel = -77.0
+    outs = {}
+    for windowed in (False, True):
+        pb = PlanBuilder(n)
+        inp = pb.new_buf_rowpad(H, W, 24)
+        y = (blks[0].emit_pair if stride == 1 else blks[0].emit_pair_s2)(blks[1], pb, inp.view(), out_rowpad=True)
+        if windowed:
+            pb.ops[-1].row_lo, pb.ops[-1].row_end = lo, end
+        plan = CompiledPlan(pb, dev)
+        assert [plan.kernel_name(i) for i in range(plan.n_ops)] == \
+            ["blazepair_kernel<64>" if stride == 1 else "blazepair_s2_kernel<64, %d>" % cout2]
+        plan.buf_tensor(inp, n).copy_(x)
+        yt = plan.buf_tensor(y, n)
+        assert yt.shape == (n, H // stride, W // stride, cout2) and 0 < lo < end < yt.shape[1]
+        yt.fill_(sentinel)
+        if windowed:
+            yt[:, lo:end] = float("nan")
+        plan.run()
+        torch.cuda.synchronize()
+        outs[windowed] = yt.cpu().numpy()
+        base = y.off - (yt.shape[2] + 2) * cout2      # the pads of the output stay zero (the next block's window reads them)
+        full = plan.arena[base: base + n * y.ns].clone()
+        yt.zero_()
+        assert float(plan.arena[base: base + n * y.ns].abs().max()) == 0.0
+        assert float(full.abs().sum()) > 0
+    ref, got = outs[False], outs[True]
+    assert np.isfinite(ref).all() and float(np.abs(ref).max()) > 0 and not (ref == sentinel).any()
+    np.testing.assert_array_equal(got[:, lo:end].view(np.uint32), ref[:, lo:end].view(np.uint32))
+    for i in range(n):
+        for r in list(range(lo)) + list(range(end, got.shape[1])):
+            assert (got[i, r] == sentinel).all() or np.array_equal(got[i, r].view(np.uint32), ref[i, r].view(np.uint32)), (i, r)
 
 
 @pytest.mark.parametrize("nblk,n", [(7, 5), (2, 3), (1, 2), (7, 260)])

@@ -200,7 +200,7 @@ def test_blazeface_plans_validate_at_any_batch(lib):
 
 
 def test_pair_s2_in_the_blazeface_plan(lib):
-    """FP_OP_BLAZEPAIR with stride = 2 (csrc/blazepairs2.hip): the single stride-1 block that ends each 24-channel stage and the
+    """FP_OP_BLAZEPAIR with stride = 2 (csrc/blazepair.hip): the single stride-1 block that ends each 24-channel stage and the
     stride-2 block behind it are one op; its output feeds the next stage row-padded; the validator checks both blocks'
     parameter spans and rejects shapes the kernel does not exist for."""
     pb = BlazeFace(True)._emit(4, frame_hw=(576, 1024))[0]

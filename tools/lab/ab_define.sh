@@ -1,6 +1,6 @@
 #!/bin/bash
 # Lab (GPU box): A/B of one csrc/*.hip file built with two sets of defines, bench.py's timed step, alternating runs on ONE box.
-#   tools/lab/ab_define.sh blazepair.hip "-DFP_PAIR_DIRECT_STORE=0" "-DFP_PAIR_DIRECT_STORE=1" [rounds]
+#   tools/lab/ab_define.sh stem.hip "-DFP_STEM_ACC2=0" "-DFP_STEM_ACC2=1" [rounds]
 # AB_CMD=<shell command run from the repo root> replaces the bench run (e.g. a plan_profile line filter).
 src=$1; A=$2; B=$3; rounds=${4:-3}
 root="$(cd "$(dirname "$0")/../.." && pwd)"

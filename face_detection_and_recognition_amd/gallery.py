@@ -2,6 +2,7 @@
 with the runner-up candidates (similarity.cosine_topk + similarity.topk_vote, csrc/sim.hip).
 
 Build-defined: the reference stops at the single best cosine score per face; nothing in it searches a gallery.
+FaceGallery.from_clusters enrols what clustering.dbscan_cosine found in unlabelled embeddings.
 """
 import glob
 import os
@@ -100,6 +101,32 @@ class FaceGallery:
             if "removed" in z.files:
                 g.remove(z["removed"])
         return g
+
+    @classmethod
+    def from_clusters(cls, embeddings, labels, names=None, device=None, centroids_only=False):
+        """Enrol the outcome of clustering.dbscan_cosine: every row whose label is >= 0 under its cluster number (noise, -1,
+        is left out), names `cluster_0007` unless given.  centroids_only: one row per cluster instead, its centroid
+        (clustering.cluster_summary)."""
+        emb, lab = torch.as_tensor(embeddings), torch.as_tensor(labels).reshape(-1)
+        if emb.dim() != 2 or lab.shape[0] != emb.shape[0]:
+            raise ValueError(f"{lab.shape[0]} labels for embeddings of shape {tuple(emb.shape)}")
+        if lab.is_floating_point() or lab.dtype == torch.bool:
+            raise ValueError(f"cluster labels must be integers, got {lab.dtype}")
+        keep = lab >= 0
+        if not bool(keep.any()):
+            raise ValueError("no clustered rows: every label is noise (-1)")
+        n_clusters = int(lab.max()) + 1
+        if names is None:
+            names = {c: f"cluster_{c:04d}" for c in range(n_clusters)}
+        if not centroids_only:
+            return cls(emb[keep.to(emb.device)], lab[keep], names, device)
+        from .clustering import cluster_summary
+        if device is None:
+            device = emb.device if emb.is_cuda else "cuda"
+        device = torch.device(str(device).replace("hip", "cuda"))
+        summ = cluster_summary(emb.to(device, torch.float32), lab.to(device))
+        present = summ["sizes"] > 0
+        return cls(summ["centroids"][present], torch.arange(n_clusters, device=device)[present], names, device)
 
     @classmethod
     def from_feature_files(cls, paths_or_dir, feature_size, device="cuda"):

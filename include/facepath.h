@@ -658,6 +658,40 @@ int fp_topk_vote(const float* scores, const int32_t* idx, int64_t M, int k, cons
                  int32_t* out_label, float* out_score, int32_t* out_votes, void* stream);
 
 /*
+ * Cosine DBSCAN: group the N rows of X by identity without labels (build-defined; the reference has no counterpart).  X3 =
+ * fp_split3_rows(X) (D a multiple of 32), xinv = fp_row_inv_norm(X).  Semantics, on which the labels equal scikit-learn's
+ * DBSCAN(metric="precomputed") on the same edge set:
+ *   - a row is live when its xinv is finite and non-zero; a dead row has degree 0, core 0, label -1 and no neighbours;
+ *   - for live i < j: i ~ j iff <X[i], X[j]> * xinv[i] * xinv[j] >= tau, in the arithmetic of fp_cosine_topk_x6 with row i the
+ *     register-split operand and column j from the planes; each unordered pair is evaluated once; NaN compares false;
+ *   - degree[i] = 1 + the number of neighbours (the point counts itself), core[i] = degree[i] >= min_samples;
+ *   - clusters = connected components of the core points under core-core edges, numbered 0 .. C-1 by their smallest row;
+ *   - a live non-core point with a core neighbour (border) takes the smallest cluster number among its core neighbours;
+ *     every other non-core point is noise, label -1.  n_clusters[0] = C.
+ * Two walks of the upper triangle of S = X X^T (S is never stored; one walk when min_samples <= 2), a lock-free union-find in
+ * between, then flatten / rank / label launches.  The result is a function of the edge set only: two runs are bit-identical.
+ * degree [N] int32, core [N] uint8, labels [N] int32, n_clusters [1] int32.  ws: fp_cosine_dbscan_workspace(N, min_samples)
+ * bytes of device memory, 16-byte aligned (0 for arguments the call refuses; grows with N and min_samples).
+ * 1 <= min_samples <= 64, 0 < N < 2^31.  Refusals, before any launch: a NULL pointer, N <= 0, min_samples out of range or a
+ * workspace that is too small: FP_ERR_INVALID_ARG; D % 32 or X / X3 / ws not 16-byte aligned: FP_ERR_ALIGNMENT;
+ * N >= 2^31, or a triangular work list of 2^31 workgroups or more (N above about 33 million rows): FP_ERR_UNSUPPORTED.
+ */
+size_t fp_cosine_dbscan_workspace(int64_t N, int min_samples);
+int fp_cosine_dbscan_x6(const float* X, const float* xinv, const void* X3, int64_t N, int D, float tau, int min_samples,
+                        int32_t* degree, uint8_t* core, int32_t* labels, int32_t* n_clusters, void* ws, size_t ws_bytes,
+                        void* stream);
+
+/*
+ * Centroid and medoid of C clusters.  order: the member rows sorted by (cluster, row); offsets [C + 1]: cluster c owns
+ * order[offsets[c] .. offsets[c + 1]).  centroids [C][D]: the members' normalised rows (X[m] * xinv[m]) summed in that order
+ * and renormalised (an empty cluster: zeros); medoid [C]: the member with the largest cosine to the centroid, the lower row
+ * on equal scores (-1 for an empty cluster).  One workgroup per cluster, no float atomics: two runs are bit-identical.
+ * Any D up to 16000.
+ */
+int fp_cluster_centroids(const float* X, const float* xinv, const int32_t* order, const int32_t* offsets, int C, int D,
+                         float* centroids, int32_t* medoid, void* stream);
+
+/*
  * get_ref_mean_vec_and_thres_from_imgs (sff/filter_faces_using_reference.py:71-100):
  * mean over the R reference rows, thres = max_i ||mean - f_i||_2.  out_mean [D], out_thres [1].
  */

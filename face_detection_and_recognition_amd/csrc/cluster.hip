@@ -17,39 +17,14 @@
 // The result is a function of the edge set: degrees are sums, the root of a component is its minimum, a border point takes the
 // minimum over its complete list -- no arrival order, launch geometry or schedule enters.
 #include "split.h"
+#include "triwalk.h"
 
 namespace {
 
 typedef __attribute__((address_space(3))) void* lds_ptr;
 typedef const __attribute__((address_space(1))) void* gbl_ptr;
 
-constexpr int CL_NC = 128, CL_ROWS = 128, CL_LDS = 2 * 3 * CL_NC * 32 * 2;
 constexpr int CL_MAX_MS = 64;
-
-// ---- the triangular work list --------------------------------------------------------------------------------------
-// Row tile r walks the m = nchunk - r chunks r .. nchunk - 1, cut into ceil(m / P) workgroups of nearly equal, contiguous
-// chunk ranges (at most P each).  Items are numbered by increasing m: tile m = P b + e + 1 (0 <= e < P) has b + 1 groups and
-// the tiles before it hold  P b (b + 1) / 2 + e (b + 1)  groups.
-struct cl_item {
-  int tile, first, count;   // row tile, first chunk, chunks
-};
-__host__ __device__ inline long cl_groups(long nchunk, long P) {
-  const long b = nchunk / P, e = nchunk - b * P;
-  return P * b * (b + 1) / 2 + e * (b + 1);
-}
-__host__ __device__ inline cl_item cl_decode(long v, int nchunk, int P) {
-  long b = (long)((sqrt(1.0 + 8.0 * (double)v / (double)P) - 1.0) * 0.5);
-  while (b > 0 && P * b * (b + 1) / 2 > v) --b;
-  while (P * (b + 1) * (b + 2) / 2 <= v) ++b;
-  const long rem = v - P * b * (b + 1) / 2;
-  const long e = rem / (b + 1), g = rem - e * (b + 1);
-  const long m = P * b + e + 1, base = m / (b + 1), extra = m - base * (b + 1);
-  cl_item it;
-  it.tile = (int)(nchunk - m);
-  it.first = it.tile + (int)(g * base + (g < extra ? g : extra));
-  it.count = (int)(base + (g < extra ? 1 : 0));
-  return it;
-}
 
 // ---- lock-free union-find ------------------------------------------------------------------------------------------
 #define CL_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
@@ -415,16 +390,6 @@ __global__ __launch_bounds__(256) void cluster_centroid_kernel(const float* __re
   }
 }
 
-int cl_num_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus = n;
-  }
-  return cus;
-}
-
 // the workspace: five int32 / fp32 arrays of Npad entries (inv1, inv2, parent, root, rank) and the neighbour lists
 struct cl_ws {
   float *inv1, *inv2;
@@ -466,10 +431,7 @@ int fp_cosine_dbscan_x6(const float* X, const float* xinv, const void* X3, int64
   const cl_ws w = cl_layout(ws, N, min_samples);
   if (ws_bytes < w.bytes) return FP_ERR_INVALID_ARG;
   const int n = (int)N, Npad = (int)fp_round_up(N, CL_NC), nchunk = Npad / CL_NC;
-  // chunks per workgroup: about four rounds of the workgroups the device holds (three per CU), at most 16 chunks each
-  const long total = (long)nchunk * (nchunk + 1) / 2;
-  long P = total / (4L * 3 * cl_num_cus());
-  P = P < 1 ? 1 : P > 16 ? 16 : P;
+  const long P = cl_chunks_per_group(nchunk, 3);   // the walk runs three workgroups per CU
   const long groups = cl_groups(nchunk, P);
   if (groups >= (1L << 31)) return FP_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;

@@ -692,6 +692,31 @@ int fp_cluster_centroids(const float* X, const float* xinv, const int32_t* order
                          float* centroids, int32_t* medoid, void* stream);
 
 /*
+ * Pair histogram: score an embedder on N labelled rows (build-defined; the reference has no counterpart).  The cosine scores of
+ * ALL pairs i < j of live rows are counted into two histograms of nbins equal bins over [lo, hi): genuine (labels[i] ==
+ * labels[j]) and impostor (otherwise).  ROC, TAR at FAR, EER and AUC follow from the 2 x nbins integers on the host.  X3 =
+ * fp_split3_rows(X) (D a multiple of 32), xinv = fp_row_inv_norm(X), labels [N] int32.  Semantics:
+ *   - a row is live when its xinv is finite and non-zero AND its label is >= 0; a row that is not live takes part in no pair;
+ *   - for live i < j: s = <X[i], X[j]> * xinv[i] * xinv[j] in the arithmetic and orientation of fp_cosine_dbscan_x6 (row i the
+ *     register-split operand, column j from the planes); each unordered pair is evaluated once, the diagonal never;
+ *   - bin: scale = (float)(nbins / ((double)hi - lo)) on the host, t = (s - lo) * scale in fp32 as two separately rounded
+ *     operations, b = t < 0 ? 0 : min((int)t, nbins - 1): a score below lo or at or above hi lands in an end bin, so the
+ *     counts total the number of live pairs.  A NaN score (overflow only) is counted nowhere;
+ *   - the counters are integers: two runs are bit-identical whatever the launch geometry.
+ * genuine [nbins], impostor [nbins] int64 on the device: the call zeroes them itself.  Stream-ordered, allocates nothing.
+ * ws: fp_pair_histogram_workspace(N) bytes of device memory, 16-byte aligned (the masked inverse norms and the labels, both
+ * padded to round_up(N, 128); 0 for N <= 0 or N >= 2^31).  N == 0 and N == 1: FP_OK, all zeros (N == 0 reads no input
+ * pointer).  Refusals, before any launch: nbins outside 2 .. FP_PAIRHIST_MAX_BINS, !(lo < hi), lo or hi not finite (or a
+ * range so narrow that scale is not), D <= 0 or D % 32, N < 0, a NULL pointer or a workspace that is too small:
+ * FP_ERR_INVALID_ARG; X / X3 / ws not 16-byte aligned: FP_ERR_ALIGNMENT; N >= 2^31 or a work list of 2^31 workgroups:
+ * FP_ERR_UNSUPPORTED.
+ */
+#define FP_PAIRHIST_MAX_BINS 1024
+size_t fp_pair_histogram_workspace(int64_t N);
+int fp_pair_histogram_x6(const float* X, const float* xinv, const void* X3, const int32_t* labels, int64_t N, int D, float lo,
+                         float hi, int nbins, int64_t* genuine, int64_t* impostor, void* ws, size_t ws_bytes, void* stream);
+
+/*
  * get_ref_mean_vec_and_thres_from_imgs (sff/filter_faces_using_reference.py:71-100):
  * mean over the R reference rows, thres = max_i ||mean - f_i||_2.  out_mean [D], out_thres [1].
  */

@@ -106,6 +106,17 @@ class FpJpegEncItem(C.Structure):
                 ("x1", C.c_int32), ("y1", C.c_int32)]
 
 
+class FpDrawCmd(C.Structure):
+    """Mirror of struct fp_draw_cmd: one 32-byte drawing command (include/facepath.h "Drawing on device frames")."""
+    _fields_ = [("frame", C.c_int32), ("kind", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32),
+                ("y1", C.c_int32), ("b", C.c_uint8), ("g", C.c_uint8), ("r", C.c_uint8), ("a", C.c_uint8), ("arg", C.c_int32)]
+
+
+DRAW_RECT, DRAW_FILL, DRAW_RING, DRAW_GLYPH, DRAW_MOSAIC = 1, 2, 3, 4, 5   # fp_draw_kind
+DRAW_TILE, DRAW_FONT_BYTES = 64, 760                                       # FP_DRAW_TILE, FP_DRAW_FONT_BYTES
+DRAW_MAX_ARG, DRAW_MAX_SCALE, DRAW_MAX_COORD = 4096, 64, 1 << 20           # FP_DRAW_MAX_*
+DRAW_MOSAIC_CELLS = (4, 8, 16, 32)
+
 JPEG_DECODE_ON_HOST = 1          # fp_jpeg_entropy_decode_device status: decode this image with fp_jpeg_entropy_decode
 JPEG_444, JPEG_422, JPEG_420 = 0, 1, 2   # fp_jpeg_encode_* subsampling (Pillow's numbering)
 JPEG_ENC_BYTES_PER_BLOCK = 416   # worst-case scan bytes of one 8 x 8 block, stuffing included
@@ -202,6 +213,9 @@ SIGNATURES = {
     "fp_det_match_workspace": (_SZ, [_I64, _I]),
     "fp_det_match": (_I, [_P, _P, _P, _P, _P, _I, _I64, _I64, _P, _I, _P, _I, _P, _P, _P, _P, _SZ, _P]),
     "fp_pr_accumulate": (_I, [_P, _P, _P, _P, _I64, _P, _I, _I, _P, _I, _P, _I, _P, _P, _P]),
+    "fp_draw": (_I, [_P, _SZ, _P, _I, _P, _P, _I, _P, _I, _P, _P]),
+    "fp_draw_check": (_I, [_SZ, _P, _I, _P, _P, _I, _P, _I]),
+    "fp_draw_emulate": (_I, [_P, _SZ, _P, _I, _P, _P, _I, _P, _I, _P]),
 }
 
 _lib = None

@@ -1,6 +1,8 @@
 """``python -m face_detection_and_recognition_amd.detect_face_blazeface -i img.jpg --md w.pth --mt back``
 Entry point with the reference's flags (face_detection_and_extraction/detect_face_blazeface.py:7-34).  Images
-only (the video / webcam GUI loops are out of scope); prints the post-processed detections as JSON."""
+only (the video / webcam GUI loops are out of scope); prints the post-processed detections as JSON.  ``-o out.jpg`` also
+saves the image with the detections drawn on, ``--anonymize CELL`` pixelates the faces in it first (annotate.py)."""
+import argparse
 import json
 
 from .modules.blazeface.model import BlazeFaceModel
@@ -8,18 +10,26 @@ from .modules.utils.inference import inference_img
 from .modules.utils.parser import get_argparse, torch_device
 
 
-def main(argv=None):
+def build_parser():
     parser = get_argparse(description="Blazeface face detection (MI355X HIP path)", conflict_handler='resolve')
     parser.add_argument("--md", "--model", dest="model", default="weights/blazeface/blazefaceback.pth",
                         help="Path to weight file (.pth). anchors.npy next to it is used when present, "
                              "otherwise the MediaPipe anchors are generated. (default: %(default)s)")
     parser.add_argument("--mt", "--model_type", dest="model_type", default="back", choices=["back", "front"],
                         help="Model type back or front; must match the weight file. (default: %(default)s)")
-    args = parser.parse_args(argv)
+    parser.add_argument("-o", "--output", dest="output", default=argparse.SUPPRESS,
+                        help="Write the image with its detections drawn on (box, landmarks, caption) to this JPEG file.")
+    parser.add_argument("--anonymize", dest="anonymize", type=int, choices=[4, 8, 16, 32], default=argparse.SUPPRESS, metavar="CELL",
+                        help="With -o: pixelate every detected face first, mosaic cells of CELL x CELL pixels (4, 8, 16 or 32).")
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     print("Current Arguments: ", args)
     net = BlazeFaceModel(args.model, args.det_thres, args.bbox_area_thres, args.model_type,
                          torch_device(args.device))
-    post = inference_img(net, args.input_src)
+    post = inference_img(net, args.input_src, save=getattr(args, "output", None), anonymize=getattr(args, "anonymize", 0))
     print(json.dumps({"boxes": post.boxes.tolist(), "confs": post.bbox_confs.tolist(),
                       "areas": post.bbox_areas.tolist(), "landmarks": post.bbox_lmarks.tolist()}))
     return post

@@ -1,11 +1,13 @@
 """``python -m face_detection_and_recognition_amd.detect_face_mtcnn -i img.jpg --mt fast --md weights.npz``
 Entry point with the reference's flags (face_detection_and_extraction/detect_face_mtcnn.py).  Images only (the video /
 webcam GUI loops are out of scope); prints the detector's rows (15 numbers each: box, five landmarks, confidence, normalised
-by the image size) and the post-processed detections as JSON.  ``--md synthetic`` runs seeded random weights calibrated on the image (synth.py)."""
+by the image size) and the post-processed detections as JSON.  ``-o out.jpg`` also saves the image with the detections drawn
+on, ``--anonymize CELL`` pixelates the faces in it first (annotate.py).  ``--md synthetic`` runs seeded random weights calibrated on the image (synth.py)."""
+import argparse
 import json
 
 from .modules.mtcnn.model import SLOW_DEFAULTS, SLOW_WEIGHTS, MTCNNFastModel, MTCNNSlowModel
-from .modules.utils.inference import get_dets_bboxes_confs_lmarks_areas, load_image
+from .modules.utils.inference import get_dets_bboxes_confs_lmarks_areas, load_image, save_annotated
 from .modules.utils.parser import get_argparse, torch_device
 
 
@@ -23,13 +25,21 @@ def load_model(model_type, model_path, det_thres, bbox_area_thres, device, image
     raise NotImplementedError(f"{model_type} is not supported")
 
 
-def main(argv=None):
+def build_parser():
     parser = get_argparse(description="MTCNN face detection (MI355X HIP path)", conflict_handler='resolve')
     parser.add_argument("--md", "--model", dest="model", default=SLOW_WEIGHTS,
                         help="Path to the weights (.npz state dict, .npy port dictionary, .pth) or 'synthetic'. (default: %(default)s)")
     parser.add_argument("--mt", "--model_type", dest="model_type", default="fast", choices=["fast", "slow"],
                         help="MTCNN model type, fast or slow (default: %(default)s).")
-    args = parser.parse_args(argv)
+    parser.add_argument("-o", "--output", dest="output", default=argparse.SUPPRESS,
+                        help="Write the image with its detections drawn on (box, landmarks, caption) to this JPEG file.")
+    parser.add_argument("--anonymize", dest="anonymize", type=int, choices=[4, 8, 16, 32], default=argparse.SUPPRESS, metavar="CELL",
+                        help="With -o: pixelate every detected face first, mosaic cells of CELL x CELL pixels (4, 8, 16 or 32).")
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     print("Current Arguments: ", args)
     image = load_image(args.input_src)
     net = load_model(args.model_type, args.model, args.det_thres, args.bbox_area_thres, torch_device(args.device), image)
@@ -40,6 +50,8 @@ def main(argv=None):
     post = get_dets_bboxes_confs_lmarks_areas(dets.copy(), (w, h), net.input_size, net.det_thres, net.bbox_area_thres)
     print(json.dumps({"boxes": post.boxes.tolist(), "confs": post.bbox_confs.tolist(),
                       "areas": post.bbox_areas.tolist(), "landmarks": post.bbox_lmarks.tolist()}))
+    if getattr(args, "output", None):
+        save_annotated(args.output, image, post, getattr(args, "anonymize", 0), torch_device(args.device))
     return dets
 
 

@@ -1,5 +1,7 @@
 """``python -m face_detection_and_recognition_amd.detect_face_yolov5_face -i img.jpg --md yolov5n-face.pt``
-Entry point with the reference's flags (face_detection_and_extraction/detect_face_yolov5_face.py:13-66)."""
+Entry point with the reference's flags (face_detection_and_extraction/detect_face_yolov5_face.py:13-66).  ``-o out.jpg`` also
+saves the image with the detections drawn on, ``--anonymize CELL`` pixelates the faces in it first (annotate.py)."""
+import argparse
 import json
 import os
 from typing import Tuple
@@ -20,18 +22,26 @@ def load_model(model_path: str, det_thres: float, bbox_area_thres: float, model_
     return YOLOV5FaceModel(net, det_thres, bbox_area_thres, inference_pytorch_model_yolov5_face, model_in_size)
 
 
-def main(argv=None):
+def build_parser():
     parser = get_argparse(description="YOLOv5-face face detection (MI355X HIP path)", conflict_handler='resolve')
     parser.remove_argument("model")
     parser.add_argument("--md", "--model", dest="model", default="weights/yolov5s/yolov5s-face.pt",
                         help='Path to weight file (.pt/.pth state_dict). (default: %(default)s).')
     parser.add_argument("--is", "--input_size", dest="input_size", nargs=2, default=(640, 640),
                         help='Input images are resized to this size (width, height). (default: %(default)s).')
-    args = parser.parse_args(argv)
+    parser.add_argument("-o", "--output", dest="output", default=argparse.SUPPRESS,
+                        help="Write the image with its detections drawn on (box, landmarks, caption) to this JPEG file.")
+    parser.add_argument("--anonymize", dest="anonymize", type=int, choices=[4, 8, 16, 32], default=argparse.SUPPRESS, metavar="CELL",
+                        help="With -o: pixelate every detected face first, mosaic cells of CELL x CELL pixels (4, 8, 16 or 32).")
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     print("Current Arguments: ", args)
     args.input_size = tuple(map(int, args.input_size))
     net = load_model(args.model, args.det_thres, args.bbox_area_thres, args.input_size, args.device)
-    post = inference_img(net, args.input_src)
+    post = inference_img(net, args.input_src, save=getattr(args, "output", None), anonymize=getattr(args, "anonymize", 0))
     print(json.dumps({"boxes": post.boxes.tolist(), "confs": post.bbox_confs.tolist(), "areas": post.bbox_areas.tolist()}))
     return post
 

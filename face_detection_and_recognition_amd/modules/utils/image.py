@@ -1,7 +1,8 @@
 """Image / coordinate helpers with the reference's names
 (face_detection_and_extraction/modules/utils/image.py).  The pixel work (resize, pad, normalise) runs in
 fp_resize_normalize (csrc/image.hip); the per-detection coordinate helpers are the same small numpy host
-arithmetic as the reference (a handful of boxes per image, fp64).  Drawing helpers are out of scope."""
+arithmetic as the reference (a handful of boxes per image, fp64).  draw_bbox_on_image keeps the reference's layout and
+draws it on the device with this build's integer primitives (annotate.py, csrc/draw.hip)."""
 import math
 from typing import Tuple
 
@@ -176,3 +177,21 @@ def calculate_bbox_iou(bbox1, bbox2):
         return 0
     inter = x_diff * y_diff
     return inter / ((bbox1[2] - bbox1[0]) * (bbox1[3] - bbox1[1]) + (bbox2[2] - bbox2[0]) * (bbox2[3] - bbox2[1]) - inter)
+
+
+def draw_bbox_on_image(cv2_img, post_dets, line_thickness: int = None, text_bg_alpha: float = 0.5, anonymize: int = 0):
+    """image.py:146-204: the box, a ring per landmark and the conf_area[label] caption on its bar for every detection of
+    post_dets, drawn IN PLACE.  cv2_img: an (h, w, 3) u8 device tensor, or a numpy image, which is uploaded, drawn on and
+    copied back into the same array.  The layout is the reference's; the pixels are this build's integer primitives, not
+    OpenCV's anti-aliased ones (annotate.py).  anonymize (not in the reference): a mosaic cell, faces are pixelated first."""
+    from ...annotate import draw, post_dets_draw_list
+    h, w = cv2_img.shape[:2]
+    dl = post_dets_draw_list(post_dets, h, w, line_thickness, text_bg_alpha, anonymize)
+    if isinstance(cv2_img, np.ndarray):
+        dev = torch.from_numpy(np.ascontiguousarray(cv2_img)).to(torch.device("cuda", torch.cuda.current_device()))
+        cv2_img[...] = draw(dev.unsqueeze(0), dl)[0].cpu().numpy()
+        return cv2_img
+    if not cv2_img.is_contiguous():
+        raise ValueError("draw_bbox_on_image: a contiguous (h, w, 3) uint8 device tensor expected")
+    draw(cv2_img.unsqueeze(0), dl)
+    return cv2_img

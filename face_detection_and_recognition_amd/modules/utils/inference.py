@@ -1,13 +1,13 @@
 """Inference drivers (face_detection_and_extraction/modules/utils/inference.py).  The GUI loops
-(cv2.imshow / VideoCapture) are out of scope; ``inference_img`` keeps its signature and returns the
-post-processed detections instead of drawing them."""
+(cv2.imshow / VideoCapture) are out of scope; ``inference_img`` keeps its signature, returns the
+post-processed detections and, instead of showing the drawn frame in a window, saves it when asked to (``save``)."""
 import os
 from typing import Any, List, Optional, Tuple
 
 import numpy as np
 
 from ..models.base import Model, PostProcessedDetection
-from .image import scale_coords
+from .image import draw_bbox_on_image, scale_coords
 
 
 def get_dets_bboxes_confs_lmarks_areas(dets: np.ndarray, orig_size: Tuple[int, int], in_size: Tuple[int, int],
@@ -41,8 +41,23 @@ def load_image(path: str, device=None):
     return np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB"))[..., ::-1])
 
 
-def inference_img(net: Model, img, waitKey_val: int = 0) -> PostProcessedDetection:
-    """inference.py:61-93 without the drawing/imshow tail."""
+def save_annotated(path: str, image, post: PostProcessedDetection, anonymize: int = 0, device=None):
+    """The tail of the reference's inference_img with a file in place of the window: draw_bbox_on_image on a device copy of
+    `image` (numpy or device tensor; the caller's frame stays as it is), then imwrite (cv2.imwrite's bytes)."""
+    import torch
+    from .jpeg import imwrite
+    if isinstance(image, np.ndarray):
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        frame = torch.from_numpy(np.ascontiguousarray(image)).to(dev)
+    else:
+        frame = image.contiguous().clone()
+    draw_bbox_on_image(frame, post, anonymize=anonymize)
+    return imwrite(path, frame)
+
+
+def inference_img(net: Model, img, waitKey_val: int = 0, save: Optional[str] = None, anonymize: int = 0) -> PostProcessedDetection:
+    """inference.py:61-93; the drawing / imshow tail becomes: with `save`, the frame with its detections drawn on (faces
+    pixelated first with anonymize = a mosaic cell) is written to that path.  The return value does not depend on it."""
     # a net that takes device frames gets the file decoded ON its device (baseline JPEG: host Huffman + device IDCT / upsampling
     # / colour conversion, byte-identical to cv2.imread's libjpeg-turbo); everything else the host array, as the reference
     dev = net.net._device() if getattr(net, "accepts_device_frames", False) else None
@@ -52,4 +67,7 @@ def inference_img(net: Model, img, waitKey_val: int = 0) -> PostProcessedDetecti
     labels = None
     if net.returns_opt_labels:
         dets, labels = dets
-    return get_dets_bboxes_confs_lmarks_areas(dets, (w, h), net.input_size, net.det_thres, net.bbox_area_thres, labels)
+    post = get_dets_bboxes_confs_lmarks_areas(dets, (w, h), net.input_size, net.det_thres, net.bbox_area_thres, labels)
+    if save:
+        save_annotated(save, image, post, anonymize, dev)
+    return post

@@ -298,6 +298,14 @@ class FacePipeline:
             return None
         return S.cosine_filter(emb, self.reference, self.tau, rinv=self.rinv, r3=self.ref3)
 
+    def annotate(self, frames, result, **kw):
+        """The frames of a finished step with its result drawn on: annotate.annotate_step(frames, result, **kw) (names,
+        anonymize, inplace); names default to the gallery's.  A call of the user's, outside the timed path."""
+        from .annotate import annotate_step
+        if self.gallery is not None:
+            kw.setdefault("names", self.gallery.names)
+        return annotate_step(frames, result, **kw)
+
     # -- whole step ------------------------------------------------------------------------------
     def step(self, frames, beside=False):
         """One pass over a batch of frames ((B, H, W, 3) u8 BGR on device, or a RaggedFrames of different sizes).

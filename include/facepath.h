@@ -1141,6 +1141,64 @@ int fp_pr_accumulate(const uint8_t* matched, const uint8_t* ignored, const int64
                      int64_t n_dt, const int32_t* npig, int n_thrs, int n_areas, const int32_t* max_dets, int n_maxdets,
                      const double* rec_thrs, int n_recs, double* precision, double* recall, void* stream);
 
+/*
+ * Drawing on device frames (build-defined, parity-unpinned against OpenCV; DESIGN §7 "Drawing"): boxes, landmark rings,
+ * captions and pixelated (mosaic) rectangles rasterised in place into u8 BGR frames of either kind of batch (a dense batch is
+ * n_frames equal descriptors).  A draw list is an array of fp_draw_cmd sorted by frame, with cmd_ranges [n_frames + 1]:
+ * frame f owns cmds[cmd_ranges[f] .. cmd_ranges[f + 1]).  The commands of a frame apply IN LIST ORDER, each to the frame as
+ * the commands before it left it; a pixel outside its frame is never touched.  All arithmetic is integer.  With (x, y) a
+ * pixel of the frame and c the command:
+ *   FP_DRAW_RECT    outline of thickness t = arg of the rectangle [x0, x1) x [y0, y1): the pixels of the rectangle grown by
+ *                   t / 2 (floor) on every side that are not in the rectangle shrunk by (t + 1) / 2; 1 <= t <= FP_DRAW_MAX_ARG.
+ *   FP_DRAW_FILL    every pixel of [x0, x1) x [y0, y1).
+ *   FP_DRAW_RING    centre (x0, y0), radius r = arg (x1, y1 unused): (2r - 1)^2 <= 4 (dx^2 + dy^2) < (2r + 1)^2;
+ *                   0 <= r <= FP_DRAW_MAX_ARG (r = 0 sets nothing).
+ *   FP_DRAW_GLYPH   arg = code | scale << 8, code 32 .. 126, 1 <= scale s <= FP_DRAW_MAX_SCALE, cell [x0, x0 + 6s) x [y0, y0 + 8s)
+ *                   (x1, y1 unused): set where bit (0x80 >> (x - x0) / s) of font[(code - 32) * 8 + (y - y0) / s] is 1.
+ *   a pixel these four set becomes dst = (dst * (255 - a) + colour * a + 127) / 255 per channel (a = 255 overwrites).
+ *   FP_DRAW_MOSAIC  cell = arg in {4, 8, 16, 32}, grid anchored at the frame's origin: within each cell, the pixels that lie
+ *                   in [x0, x1) x [y0, y1) and in the frame are replaced by their per-channel mean (sum + cnt / 2) / cnt of
+ *                   the current content.  Colour and alpha unused.
+ * A command whose kind, glyph code, scale, thickness or radius is outside these ranges, whose frame field is not the frame
+ * of its range, or with a coordinate outside [-FP_DRAW_MAX_COORD, FP_DRAW_MAX_COORD] is SKIPPED (by the kernel and by the
+ * emulator alike: commands are device memory the host does not read).
+ *
+ * fp_draw: one workgroup per entry of tiles [n_tiles][3] int32 = (frame, tx, ty), the FP_DRAW_TILE x FP_DRAW_TILE tiles the
+ * commands' bounding boxes touch (the caller built the commands and knows them; a tile that is not listed is not drawn; no
+ * tile twice).  The workgroup holds its tile in LDS, keeps the frame's commands that meet it in order and applies them one
+ * after another, then stores the tile: tiles are disjoint, so the call is race-free without atomics or scratch and two runs are
+ * bit-identical.  font: FP_DRAW_FONT_BYTES bytes of device memory (95 glyphs x 8 row bytes; modules/utils/font6x8.py is the
+ * only copy).  Stream-ordered, allocates nothing.  Refusals before any launch (FP_ERR_INVALID_ARG): a NULL pointer (cmds
+ * may be NULL when n_cmds == 0, tiles when n_tiles == 0), a negative count.  n_tiles == 0: FP_OK, nothing launched.  The
+ * kernel leaves a tile alone whose frame or tile index is outside the batch or whose frame does not lie inside frames_bytes.
+ *
+ * fp_draw_check (HOST arrays): what the host can refuse about lists it built, FP_ERR_INVALID_ARG for: a descriptor outside
+ * 1 .. FP_FRAME_MAX_W x 1 .. FP_FRAME_MAX_H or not inside frames_bytes; cmd_ranges not starting at 0, ending at n_cmds and
+ * non-decreasing; a command whose frame is not its range's; a mosaic cell not in {4, 8, 16, 32}; a tile whose frame or
+ * position is outside the batch; tiles not in strictly ascending (frame, tx, ty) order.
+ * fp_draw_emulate (HOST memory throughout): fp_draw_check, then the same procedure serially, tile by tile.
+ */
+typedef enum fp_draw_kind { FP_DRAW_RECT = 1, FP_DRAW_FILL = 2, FP_DRAW_RING = 3, FP_DRAW_GLYPH = 4, FP_DRAW_MOSAIC = 5 } fp_draw_kind;
+typedef struct fp_draw_cmd {
+  int32_t frame;            /* index into descs */
+  int32_t kind;             /* fp_draw_kind */
+  int32_t x0, y0, x1, y1;   /* inclusive-exclusive, frame pixels; may lie outside the frame */
+  uint8_t b, g, r, a;       /* colour (BGR, the frames' order) and alpha */
+  int32_t arg;              /* thickness / radius / code | scale << 8 / cell */
+} fp_draw_cmd;              /* 32 bytes */
+#define FP_DRAW_TILE 64
+#define FP_DRAW_FONT_BYTES 760
+#define FP_DRAW_MAX_ARG 4096
+#define FP_DRAW_MAX_SCALE 64
+#define FP_DRAW_MAX_COORD (1 << 20)
+int fp_draw(uint8_t* frames, size_t frames_bytes, const fp_frame_desc* descs /*device*/, int n_frames,
+            const fp_draw_cmd* cmds /*device*/, const int32_t* cmd_ranges /*device, n_frames + 1*/, int n_cmds,
+            const int32_t* tiles /*device, n_tiles x 3*/, int n_tiles, const uint8_t* font /*device*/, void* stream);
+int fp_draw_check(size_t frames_bytes, const fp_frame_desc* descs, int n_frames, const fp_draw_cmd* cmds,
+                  const int32_t* cmd_ranges, int n_cmds, const int32_t* tiles, int n_tiles);
+int fp_draw_emulate(uint8_t* frames, size_t frames_bytes, const fp_frame_desc* descs, int n_frames, const fp_draw_cmd* cmds,
+                    const int32_t* cmd_ranges, int n_cmds, const int32_t* tiles, int n_tiles, const uint8_t* font);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,14 +40,17 @@ class FrameFacesObj:
 
 
 def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=None, save_face=False,
-                                     quality=95, align=False) -> List[FrameFacesObj]:
+                                     quality=95, align=False, quality_gate=None) -> List[FrameFacesObj]:
     """frames: (B, H, W, 3) u8 BGR (numpy or CUDA tensor), a RaggedFrames, or a list of (h, w, 3) frames.  One FacePipeline
     step (no similarity filter needed); returns per-frame records with boxes (each frame's own pixels, rounded), confs,
     area fractions and embeddings.  A list whose frames share one size is stacked and takes the uniform path; otherwise it
     is packed into a RaggedFrames.  save_face: also encode every face crop (the reference's image[y:yh, x:xw]) to a JPEG
     file of that quality, in one device call.  align: embed each face warped onto the five-point template
     (FacePipeline(align=True) for this call, modules/utils/align.py); with save_face the files are then the 112 x 112
-    aligned faces the embedder saw (as u8), under the same names."""
+    aligned faces the embedder saw (as u8), under the same names.  quality_gate: a quality.QualityGate; every face is measured
+    (quality.face_quality on the step's items, with its landmarks when the step is aligned) and the faces that fail the gate
+    are left out of the records -- before save_extracted_faces applies the per-frame face cap, so a frame's
+    MAX_N_FACES_PER_FRAME slots go to usable faces.  A gate with a pose term needs align (ValueError otherwise)."""
     if isinstance(frames, (list, tuple)) and not frames:
         return []
     frames = as_frames(frames, pipe.dev)
@@ -63,6 +66,12 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
     n = res["n_faces"]
     emb = res["emb"].cpu().numpy()
     info = res["info"].cpu().numpy()
+    keep = None
+    if quality_gate is not None:
+        from ..quality import face_quality
+        lm = res.get("lmarks")
+        q = face_quality(frames, res["items"], n, lmarks=lm, fmt=None if lm is None else pipe.det.dets_fmt)
+        keep = quality_gate.mask(q).cpu().numpy()
     jpegs = None
     if save_face:
         from ..modules.utils.jpeg import encode_crops, encode_jpeg_batch
@@ -77,6 +86,8 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
            for i in range(B)]
     boxes = [[] for _ in range(B)]
     for k in range(n):
+        if keep is not None and not keep[k]:
+            continue
         f = int(info[k, 0])
         x1, y1, x2, y2, conf, area = info[k, 1:7]
         boxes[f].append([x1, y1, x2, y2])
@@ -92,17 +103,18 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
 
 
 def extract_faces_from_images(pipe, paths, batch_size=256, entropy="host", save_face=False, quality=95,
-                              align=False) -> List[FrameFacesObj]:
+                              align=False, quality_gate=None) -> List[FrameFacesObj]:
     """The reference's image media items (:400-407: one photo per item, any size, recorded as FrameFacesObj(1, 1, ...)) for a
     whole list of files: decode batch_size files at a time (modules/utils/jpeg.py imread_batch; entropy as there), then one
     pipeline step per batch -- frames of different sizes as one RaggedFrames.  Returns one record per path, in order; pass
-    each to save_extracted_faces under its file's media_root.  align: as extract_face_feat_conf_area_list."""
+    each to save_extracted_faces under its file's media_root.  align, quality_gate: as extract_face_feat_conf_area_list."""
     from ..modules.utils.jpeg import imread_batch
     out = []
     for i in range(0, len(paths), int(batch_size)):
         chunk = paths[i:i + int(batch_size)]
         frames = imread_batch(chunk, pipe.dev, entropy=entropy)     # (B, H, W, 3) when the sizes agree, else a list
-        recs = extract_face_feat_conf_area_list(pipe, frames, save_face=save_face, quality=quality, align=align)
+        recs = extract_face_feat_conf_area_list(pipe, frames, save_face=save_face, quality=quality, align=align,
+                                                quality_gate=quality_gate)
         for r in recs:
             r.frame_num, r.time_sec = 1, 1
         out.extend(recs)

@@ -10,6 +10,7 @@ import os
 import torch
 
 from . import _lib as L
+from . import quality as Q
 from . import similarity as S
 from .frames import batch_len, dets_to_crops
 from .frames import ragged_scale_coords_params, scale_coords_params  # noqa: F401 (re-exports)
@@ -31,7 +32,10 @@ class FacePipeline:
     is empty gets NaN rows.  Under two_streams they run on the embedder's side stream.
     gallery: a FaceGallery (gallery.py): step results then also carry top_scores (n, top_k), top_idx (n, top_k) int32 gallery
     rows, identity (n,) int32 (-1: nobody enrolled reaches identify_tau; default tau) and identity_score (n,), one row per
-    face in the order of emb, voted by `vote` ("top1" | "majority"); side stream as the attributes."""
+    face in the order of emb, voted by `vote` ("top1" | "majority"); side stream as the attributes.
+    quality: True or a QualityGate (quality.py): step results then also carry quality, the face_quality dict of the step's items
+    (with align, the pose columns from its landmarks), rows in the order of emb, and, with a gate, quality_keep (n,) bool: its
+    mask, which compacts nothing (as the cosine filter's keep); side stream as the attributes."""
 
     # embed(): a batch a little above a multiple of ROUND_CROPS crops is run as that multiple + the remainder on a side stream
     ROUND_CROPS = 512     # crops whose tiles fill whole rounds of workgroups in every Depth_Wise kernel (2 / 4 / 7 tiles per crop, 512 slots)
@@ -39,8 +43,12 @@ class FacePipeline:
     TAIL_CAP = 128        # capacity of the remainder's plan
 
     def __init__(self, detector, embedder, reference=None, tau=0.3, max_faces_per_frame=8, bucket=8, two_streams=False,
-                 split_tail=True, align=False, attributes=None, gallery=None, top_k=5, identify_tau=None, vote="top1"):
+                 split_tail=True, align=False, attributes=None, gallery=None, top_k=5, identify_tau=None, vote="top1",
+                 quality=None):
         self.det = detector
+        if not (quality is None or quality is True or isinstance(quality, Q.QualityGate)):
+            raise ValueError(f"quality must be None, True or a QualityGate, got {quality!r}")
+        self.quality = quality
         self.gallery, self.top_k, self.vote = gallery, int(top_k), vote
         self.identify_tau = float(tau if identify_tau is None else identify_tau)
         if gallery is not None and vote not in S.VOTE_MODES:
@@ -219,6 +227,8 @@ class FacePipeline:
             out = dict(n_faces=n, info=info[:n], emb=emb.clone(), items=items[:n])
             self._add_attributes(out, frames, info, n)
             self._add_identity(out)
+            if self.quality is not None:
+                self._add_quality(out, frames, items, al, n)
             return out, res
         if side is None:
             out, res = tail()
@@ -243,6 +253,8 @@ class FacePipeline:
             # allocated on the side stream, consumed by the caller on the main stream (after `done`): tell the caching
             # allocator, or it hands the blocks to the next embed / filter while main-stream reads are still queued
             attrs = tuple(out[k] for k in ("age_probs", "gender_probs") + self.IDENTITY_KEYS if k in out)
+            if self.quality is not None:
+                attrs += tuple(out["quality"].values()) + ((out["quality_keep"],) if "quality_keep" in out else ())
             for t in (out["emb"],) + attrs + (tuple(res) if res is not None else ()):
                 t.record_stream(main)
             self._emb_done = torch.cuda.Event()
@@ -287,6 +299,13 @@ class FacePipeline:
             return
         r = self.gallery.identify(out["emb"], k=k, tau=self.identify_tau, vote=self.vote)
         out.update(top_scores=r["top_scores"], top_idx=r["top_idx"], identity=r["label"], identity_score=r["score"])
+
+    def _add_quality(self, out, frames, items, al, n):
+        """The face_quality dict of the step's items (with align: the pose columns from its landmarks) and the gate's mask."""
+        lm = None if al is None else al["lmarks"]
+        out["quality"] = Q.face_quality(frames, items, n, lmarks=lm, fmt=None if al is None else self.det.dets_fmt)
+        if self.quality is not True:
+            out["quality_keep"] = self.quality.mask(out["quality"])
 
     @staticmethod
     def _add_align(out, al, n):

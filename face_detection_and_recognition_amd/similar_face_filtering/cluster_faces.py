@@ -34,6 +34,9 @@ def get_parsed_args(argv=None):
                         help='a face with this many neighbours, itself included, is a core face (1 .. 64)')
     parser.add_argument('--preprocess', choices=["mobile_facenet", "tf_standardize"], default=None,
                         help='(default: mobile_facenet with --net mobile_facenet, tf_standardize with facenet)')
+    parser.add_argument('--best-shot', dest="best_shot", action="store_true",
+                        help='measure every image (quality.face_quality over the whole image), keep the columns in clusters.npz '
+                             'and copy each cluster\'s sharpest usable image to cluster_XXXX/best.jpg')
     parser.add_argument('-d', '--device', default="cuda")
     args = parser.parse_args(argv)
     if args.preprocess is None:
@@ -69,12 +72,52 @@ def group_files(paths, labels, medoid, root, target):
     return list(zip(folders, sizes, rep))
 
 
-def save_clusters(path, paths, labels, core, degree, centroids, medoid):
-    """<td>/clusters.npz: plain arrays, readable without pickle."""
+def save_clusters(path, paths, labels, core, degree, centroids, medoid, quality=None):
+    """<td>/clusters.npz: plain arrays, readable without pickle.  quality: further arrays (--best-shot: quality_<column> per
+    image and best_shot per cluster)."""
     np.savez(path, paths=np.array([str(p) for p in paths], dtype=np.str_), labels=np.asarray(labels, np.int32),
              core=np.asarray(core, bool), degree=np.asarray(degree, np.int32), centroids=np.asarray(centroids, np.float32),
-             medoid=np.asarray(medoid, np.int32))
+             medoid=np.asarray(medoid, np.int32), **(quality or {}))
     return path
+
+
+QUALITY_COLUMNS = ("flags", "step", "mean", "contrast", "dark_frac", "bright_frac", "sharpness", "side")
+
+
+def image_quality(paths, device, batch_size=32, entropy="host"):
+    """quality.face_quality of every image as ONE whole-image rectangle (these images are face crops already) -> dict of
+    host arrays, one row per path: stats (n, 8) and QUALITY_COLUMNS.  Decoded batch by batch as embed_images decodes them."""
+    import torch
+    from ..frames import as_frames, frame_layout
+    from ..modules.utils.jpeg import imread_batch
+    from ..quality import face_quality
+    cols = {k: [] for k in ("stats",) + QUALITY_COLUMNS}
+    for i in range(0, len(paths), int(batch_size)):
+        decoded = imread_batch(paths[i:i + int(batch_size)], device, entropy=entropy)
+        frames = as_frames(list(decoded) if isinstance(decoded, (list, tuple)) else decoded, device)
+        rows = [[k, 0, 0, w, h, 0, 0, 0, 0] for k, (_, h, w) in enumerate(frame_layout(frames))]
+        items = torch.tensor(rows, dtype=torch.int32, device=device)
+        q = face_quality(frames, items, len(rows))
+        for k in cols:
+            cols[k].append(q[k].cpu().numpy())
+    return {k: np.concatenate(v) for k, v in cols.items()}
+
+
+def best_shots(q, labels, n_clusters):
+    """(n_clusters,) int32 rows: per cluster its image with the highest sharpness among the usable ones (an open QualityGate's
+    mask, and a Laplacian to speak of); -1 when a cluster has none."""
+    from ..quality import NO_LAPLACIAN, QualityGate, best_per_group
+    usable = QualityGate().mask(q).numpy() & ((q["flags"] & NO_LAPLACIAN) == 0)
+    return best_per_group(q["sharpness"], np.asarray(labels, np.int64), n_clusters, usable).numpy()
+
+
+def copy_best_shots(paths, best, target):
+    """Copy image best[c] to <target>/cluster_XXXX/best.jpg for every cluster c that has one.  Returns the files written."""
+    out = []
+    for c, row in enumerate(best):
+        if row >= 0:
+            out.append(shutil.copy(paths[int(row)], os.path.join(target, cluster_name(c), "best.jpg")))
+    return out
 
 
 def main(argv=None):
@@ -89,10 +132,20 @@ def main(argv=None):
     summ = cluster_summary(feats, res["labels"])
     labels, medoid = res["labels"].cpu().numpy(), summ["medoid"].cpu().numpy()
     groups = group_files(paths, labels, medoid, args.unlabelled_data_path, args.target_data_path)
+    quality = None
+    if args.best_shot:
+        q = image_quality(paths, model._device(), args.batch_size)
+        best = best_shots(q, labels, len(medoid))
+        copy_best_shots(paths, best, args.target_data_path)
+        quality = {f"quality_{k}": v for k, v in q.items()}
+        quality["best_shot"] = best.astype(np.int32)
     save_clusters(os.path.join(args.target_data_path, "clusters.npz"), paths, labels, res["core"].cpu().numpy(),
-                  res["degree"].cpu().numpy(), summ["centroids"].cpu().numpy(), medoid)
-    for folder, size, rep in groups:
-        print(f"{folder}: {size} of {len(paths)}" + (f", medoid {rep}" if rep is not None else ""))
+                  res["degree"].cpu().numpy(), summ["centroids"].cpu().numpy(), medoid, quality)
+    for k, (folder, size, rep) in enumerate(groups):
+        shot = ""
+        if quality is not None and k < len(medoid) and quality["best_shot"][k] >= 0:
+            shot = f", best shot {target_name(paths[int(quality['best_shot'][k])], args.unlabelled_data_path)}"
+        print(f"{folder}: {size} of {len(paths)}" + (f", medoid {rep}" if rep is not None else "") + shot)
     return groups
 
 

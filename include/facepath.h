@@ -1199,6 +1199,52 @@ int fp_draw_check(size_t frames_bytes, const fp_frame_desc* descs, int n_frames,
 int fp_draw_emulate(uint8_t* frames, size_t frames_bytes, const fp_frame_desc* descs, int n_frames, const fp_draw_cmd* cmds,
                     const int32_t* cmd_ranges, int n_cmds, const int32_t* tiles, int n_tiles, const uint8_t* font);
 
+/*
+ * Face crop quality (build-defined, parity-unpinned against OpenCV; DESIGN §7 "Face quality"; csrc/quality.hip): per face
+ * rectangle, integer luma statistics and the sums of a Laplacian, read from the u8 BGR frames of either kind of batch; per
+ * face, a pose record from its five landmarks.  All additive: ABI 14.
+ *
+ * Face i is items[i]'s source rectangle (src_image, sx, sy, sw, sh; the destination fields are ignored), clamped to its frame:
+ * sw x sh below are the clamped sizes.  s = max(1, ceil(max(sw, sh) / 112)), bw = sw / s, bh = sh / s (floor); everything is
+ * taken over the bw * s columns by bh * s rows anchored at the clamped corner, trailing pixels that fill no s x s block are
+ * left out.  Y = (1868 B + 9617 G + 4899 R + 8192) >> 14.  stats[i] = eight int64:
+ *   n_px, sum Y, sum Y^2, n_dark (Y <= 16), n_bright (Y >= 239), n_lap, sum L, sum L^2
+ * with Bk[r][c] the sum of Y over block (r, c) and, for 1 <= r < bh - 1, 1 <= c < bw - 1,
+ *   L = Bk[r-1][c] + Bk[r+1][c] + Bk[r][c-1] + Bk[r][c+1] - 4 Bk[r][c],   n_lap = (bw - 2) (bh - 2)
+ * (interior samples only: no mirrored border, unlike cv2.Laplacian).  flags[i] (written, not OR-ed):
+ *   FP_QUALITY_BAD_FRAME     src_image outside [0, n_frames), or the frame's descriptor outside [FP_FRAME_MIN_W, FP_FRAME_MAX_W]
+ *                            x [1, FP_FRAME_MAX_H] or not inside frames_bytes: nothing is loaded, stats 0
+ *   FP_QUALITY_EMPTY         the clamped rectangle holds no pixel: stats 0
+ *   FP_QUALITY_TOO_LARGE     s > FP_QUALITY_MAX_STEP: stats 0 (at s = 64, sum L^2 <= (4 * 255 * 64^2)^2 * 110^2 < 2^63)
+ *   FP_QUALITY_NO_LAPLACIAN  bw < 3 or bh < 3: the three Laplacian fields are 0 (bw or bh = 0: the whole row is)
+ * The first three exclude each other and the fourth.  One workgroup per face, integer arithmetic, no atomics: two runs are
+ * bit-identical.  Stream-ordered, allocates nothing.  Refusals before any launch (FP_ERR_INVALID_ARG): a NULL pointer, a
+ * negative count.  n == 0: FP_OK, nothing launched.  Trust boundary as fp_resize_ragged: descs and items are device memory the
+ * host does not read; the kernel never loads outside frames_bytes.
+ *
+ * Pose: lmarks [n][10] fp32 and fmt as fp_dets_to_crops_aligned writes and takes them (fmt 0: eyes, nose, mouth centre, slots
+ * 8, 9 unused; fmt 1, 2: eyes, nose, mouth corners).  With le, re the eyes, e = re - le, mouth the mouth centre (fmt 0) or the
+ * midpoint of its corners, mid the midpoint of the eyes and v = (-e.y, e.x) (e turned by +90 degrees: down the face), in fp32
+ * with + - * / and sqrtf only, every point taken relative to le first:
+ *   out[i] = (iod = |e|,  roll = e.y / iod,  yaw = 2 ((nose - le) . e) / iod^2 - 1,  pitch = ((nose - mid) . v) / ((mouth - mid) . v))
+ * FP_QUALITY_POSE_DEGENERATE is OR-ed into flags[i] and out[i] = 0 when iod < 1 or the pitch denominator is <= 0 (or either is
+ * not a number).  One lane per face.  Refusals: a NULL pointer, n < 0, fmt outside 0 .. 2 (FP_ERR_INVALID_ARG).
+ * The *_emulate forms run the same code serially on HOST memory (every pointer HOST) and give the same bits.
+ */
+#define FP_QUALITY_MAX_STEP 64
+#define FP_QUALITY_EMPTY 1
+#define FP_QUALITY_BAD_FRAME 2
+#define FP_QUALITY_NO_LAPLACIAN 4
+#define FP_QUALITY_TOO_LARGE 8
+#define FP_QUALITY_POSE_DEGENERATE 16
+int fp_face_quality(const uint8_t* frames, size_t frames_bytes, const fp_frame_desc* descs /*device*/, int n_frames,
+                    const fp_resize_item* items /*device*/, int n, int64_t* stats /* n x 8 */, int32_t* flags, void* stream);
+int fp_face_quality_emulate(const uint8_t* frames, size_t frames_bytes, const fp_frame_desc* descs, int n_frames,
+                            const fp_resize_item* items, int n, int64_t* stats, int32_t* flags);
+int fp_face_pose(const float* lmarks /* n x 10 */, int fmt, int n, float* out /* n x 4 */, int32_t* flags /* OR-ed into */,
+                 void* stream);
+int fp_face_pose_emulate(const float* lmarks, int fmt, int n, float* out, int32_t* flags);
+
 #ifdef __cplusplus
 }
 #endif

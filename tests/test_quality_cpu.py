@@ -1,0 +1,281 @@
+"""Face quality without a GPU: the library's host twins (the kernels' own code run serially) against the independent numpy
+restatement on every shared case, the pose record against fp64, what blurring does to `sharpness`, the gate's truth table and
+flag rules, best_per_group, and the C ABI of the new entry points."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import quality_cases as QC
+from conftest import ROOT
+from face_detection_and_recognition_amd import _lib as L
+from face_detection_and_recognition_amd import quality as Q
+
+
+# ------------------------------------------------------------------------------------------------ statistics
+
+@pytest.mark.parametrize("case", QC.CASES, ids=QC.IDS)
+def test_emulator_equals_numpy(case):
+    name, frames, _, items = case
+    want, got = QC.expected(case), Q.face_quality_emulate(frames, items)
+    assert got["stats"].dtype == np.int64 and got["stats"].shape == (len(items), 8) and got["flags"].dtype == np.int32
+    bad = np.nonzero((got["stats"] != want["stats"]).any(1) | (got["flags"] != want["flags"]))[0]
+    assert bad.size == 0, (name, bad[:5], items[bad[:5]], got["stats"][bad[:5]], want["stats"][bad[:5]])
+    for k in ("step",) + Q.DERIVED:
+        assert np.array_equal(got[k], want[k], equal_nan=True), (name, k)
+
+
+def test_cases_hit_what_they_are_for():
+    """The flags, steps and block grids the shared cases were chosen for (so that a changed case cannot silently stop covering
+    them), and the int64 bound at s = 64."""
+    by = {c[0]: (c, QC.expected(c)) for c in QC.CASES}
+    (_, _, _, items), q = by["dense2"]
+    f = q["flags"]
+    assert f[0] == f[1] == Q.NO_LAPLACIAN and q["stats"][0, 0] == 1 and q["stats"][1, 0] == 4                  # 1 x 1, 2 x 2
+    assert f[2] == 0 and q["stats"][2, 5] == 1                                                                 # 3 x 3: one sample
+    assert list(q["stats"][4:9, 0]) == [13 * 20, 14 * 20, 20 * 15, 20 * 10, 64 * 40] and list(q["side"][4:8]) == [13, 14, 15, 10]
+    assert list(f[9:13]) == [Q.EMPTY] * 4 and list(f[-3:]) == [Q.BAD_FRAME, Q.BAD_FRAME, Q.EMPTY]
+    assert not q["stats"][9:13].any() and not q["stats"][-3:].any()
+    # the 1-px checkerboard: |L| = 4 * 255 at every sample
+    k = 13 + 3
+    assert q["stats"][k, 7] == q["stats"][k, 5] * (4 * 255) ** 2 and q["stats"][k, 5] == 62 * 38
+    (_, _, _, items), q = by["sizes"]
+    assert list(q["step"][:5]) == [1, 2, 2, 1, 1] and list(q["stats"][:3, 0]) == [112 * 112, 112 * 112, 224 * 112]
+    assert list(q["stats"][:3, 5]) == [110 * 110, 54 * 54, 110 * 54]
+    assert q["step"][20] == 3 and q["stats"][20, 0] == 300 * 39 and q["step"][21] == 3
+    assert (q["flags"][[22, 24, 25]] == 0).all() and q["flags"][23] == Q.NO_LAPLACIAN
+    assert q["mean"][0] == 0 and q["mean"][5] == 255 and q["dark_frac"][0] == 1 and q["bright_frac"][5] == 1 and q["contrast"][5] == 0
+    (_, _, _, items), q = by["largest"]
+    assert list(q["step"]) == [64, 64, 0, 64] and list(q["flags"]) == [0, 0, Q.TOO_LARGE, Q.NO_LAPLACIAN]
+    assert q["stats"][0, 0] == 7168 * 192 and q["stats"][0, 5] == 110 * 1
+    assert q["stats"][0, 7] == 110 * (4 * 255 * 64 * 64) ** 2                       # every sample at the largest |L|
+    assert (4 * 255 * 64 ** 2) ** 2 * 110 ** 2 < 2 ** 63                            # a whole 112 x 112 grid of them fits
+    assert q["stats"][3, 0] == 111 * 64 * 2 * 64 and not q["stats"][2].any()
+    assert by["n0"][1]["stats"].shape == (0, 8) and by["n300"][1]["stats"].shape == (300, 8)
+    assert len(set(by["n300"][1]["step"].tolist())) >= 2
+
+
+def test_emulator_refusals(lib):
+    buf, d, it = np.zeros(64, np.uint8), np.zeros((1, 2), np.int64), np.zeros((1, 9), np.int32)
+    st, fl, lm, out = np.zeros((1, 8), np.int64), np.zeros(1, np.int32), np.zeros((1, 10), np.float32), np.zeros((1, 4), np.float32)
+    p = Q._p
+    assert lib.fp_face_quality_emulate(p(buf), 64, p(d), 1, p(it), 0, p(st), p(fl)) == L.FP_OK
+    assert lib.fp_face_quality_emulate(p(buf), 64, p(d), 1, p(it), -1, p(st), p(fl)) == L.FP_ERR_INVALID_ARG
+    assert lib.fp_face_quality_emulate(p(buf), 64, p(d), -1, p(it), 1, p(st), p(fl)) == L.FP_ERR_INVALID_ARG
+    for k in (0, 2, 4, 6, 7):
+        args = [p(buf), 64, p(d), 1, p(it), 1, p(st), p(fl)]
+        args[k] = None
+        assert lib.fp_face_quality_emulate(*args) == L.FP_ERR_INVALID_ARG, k
+        assert lib.fp_face_quality(*args, None) == L.FP_ERR_INVALID_ARG, k          # refused before any launch: no GPU needed
+    assert lib.fp_face_quality(p(buf), 64, p(d), 1, p(it), -1, p(st), p(fl), None) == L.FP_ERR_INVALID_ARG
+    assert lib.fp_face_pose_emulate(p(lm), 1, 0, p(out), p(fl)) == L.FP_OK
+    for args in ([p(lm), 3, 1, p(out), p(fl)], [p(lm), -1, 1, p(out), p(fl)], [p(lm), 1, -1, p(out), p(fl)], [None, 1, 1, p(out), p(fl)],
+                 [p(lm), 1, 1, None, p(fl)], [p(lm), 1, 1, p(out), None]):
+        assert lib.fp_face_pose_emulate(*args) == L.FP_ERR_INVALID_ARG
+        assert lib.fp_face_pose(*args, None) == L.FP_ERR_INVALID_ARG
+    # a frame that does not lie inside frames_bytes, and one narrower than the ragged kernels take: nothing is read
+    frames = [np.full((4, 4, 3), 9, np.uint8)]
+    descs = np.array([[0, 4 | (4 << 32)], [40, 4 | (4 << 32)], [0, 4 | (2 << 32)], [-1, 4 | (4 << 32)]], np.int64)
+    items = np.array([QC.item(f, 0, 0, 4, 4) for f in range(4)], np.int32)
+    st, fl = np.ones((4, 8), np.int64), np.ones(4, np.int32)
+    data = np.ascontiguousarray(frames[0]).reshape(-1)
+    assert lib.fp_face_quality_emulate(p(data), data.size, p(descs), 4, p(items), 4, p(st), p(fl)) == L.FP_OK
+    assert list(fl) == [0, Q.BAD_FRAME, Q.BAD_FRAME, Q.BAD_FRAME] and st[0, 0] == 16 and st[0, 1] == 16 * 9 and not st[1:].any()
+
+
+# ------------------------------------------------------------------------------------------------ pose
+
+POSE_TOL = 64 * 2.0 ** -24
+
+
+@pytest.mark.parametrize("fmt", QC.POSE_FMTS)
+def test_emulated_pose_against_fp64(fmt):
+    """fp32 against the fp64 restatement on the same fp32 landmarks: within 64 * 2^-24 * max(1, |want|) (a dozen roundings on
+    terms bounded by 4 iod^2 over iod^2).  The degenerate rows carry the flag and four zeros in both."""
+    names, lm, degenerate = QC.pose_landmarks(fmt)
+    n = len(lm)
+    le = lm[:, :2].astype(np.float64)
+    iod = np.hypot(*(lm[:, 2:4].astype(np.float64) - le).T)
+    for k in range(2, 5 if fmt else 4):
+        assert (np.hypot(*(lm[:, 2 * k:2 * k + 2].astype(np.float64) - le).T)[~degenerate] <= 4 * iod[~degenerate]).all()
+    frames = [np.zeros((4, 4, 3), np.uint8)]
+    items = np.array([QC.item(0, 0, 0, 4, 4)] * n, np.int32)
+    got = Q.face_quality_emulate(frames, items, lmarks=lm, fmt=fmt)
+    want = Q.face_quality_numpy(frames, items, lmarks=lm, fmt=fmt)
+    assert np.array_equal(got["flags"], want["flags"])
+    assert np.array_equal((got["flags"] & Q.POSE_DEGENERATE) != 0, degenerate), [names[i] for i in np.nonzero(degenerate)[0]]
+    for k in Q.POSE_FIELDS:
+        assert got[k].dtype == np.float32
+        err = np.abs(got[k].astype(np.float64) - want[k])
+        print(fmt, k, "max error / bound", float((err / (POSE_TOL * np.maximum(1, np.abs(want[k])))).max()))
+        bad = np.nonzero(~(err <= POSE_TOL * np.maximum(1, np.abs(want[k]))))[0]
+        assert bad.size == 0, (k, [names[i] for i in bad], got[k][bad], want[k][bad])
+        assert not got[k][degenerate].any() and not want[k][degenerate].any()
+    i = names.index("frontal")
+    assert want["iod"][i] == 60 and want["roll"][i] == 0 and want["yaw"][i] == 0 and abs(want["pitch"][i] - 35 / 65) < 1e-12
+    assert want["yaw"][names.index("yaw+30")] == 1 and want["yaw"][names.index("yaw-30")] == -1       # the nose under an eye
+    assert abs(want["roll"][names.index("roll+20")] - np.sin(np.radians(20))) < 1e-6
+    assert want["pitch"][names.index("pitch+10")] > want["pitch"][i] > want["pitch"][names.index("pitch-20")]
+    assert abs(want["yaw"][names.index("far")]) < 1e-12 and abs(want["iod"][names.index("far")] - 30) < 1e-12
+    if fmt:     # the mouth corners count only through their midpoint
+        lm2 = lm.copy()
+        lm2[:, 6] -= 8
+        lm2[:, 8] += 8
+        again = Q.face_quality_numpy(frames, items, lmarks=lm2, fmt=fmt)
+        assert np.allclose(again["pitch"], want["pitch"], rtol=1e-12, atol=0)
+
+
+# ------------------------------------------------------------------------------------------------ behaviour
+
+@pytest.mark.parametrize("side", [100, 113, 390])
+def test_blurring_lowers_sharpness(side):
+    rng = np.random.default_rng(side)
+    sharp = rng.integers(0, 256, (side + 10, side + 10, 3), dtype=np.uint8)
+    frames = [sharp, QC.box_blur(sharp, 1), QC.box_blur(sharp, 3)]
+    q = Q.face_quality_emulate(frames, np.array([QC.item(f, 5, 5, side, side) for f in range(3)], np.int32))
+    s = q["sharpness"]
+    print(side, "step", q["step"][0], "sharpness sharp / r = 1 / r = 3:", s)
+    assert s[0] > s[1] > s[2] > 0 and q["step"][0] == -(-side // 112)
+    assert abs(q["mean"][0] - q["mean"][2]) < 2            # the exposure columns do not move with the blur
+
+
+# ------------------------------------------------------------------------------------------------ gate
+
+def _q(n=1, **cols):
+    """A quality dict of n good faces with the columns of `cols` replaced."""
+    q = dict(stats=np.tile(np.array([100, 0, 0, 0, 0, 64, 0, 0], np.int64), (n, 1)), flags=np.zeros(n, np.int32),
+             side=np.full(n, 50.0), sharpness=np.full(n, 10.0), contrast=np.full(n, 30.0), dark_frac=np.full(n, 0.1),
+             bright_frac=np.full(n, 0.1), iod=np.full(n, 20.0, np.float32), roll=np.zeros(n, np.float32),
+             yaw=np.zeros(n, np.float32), pitch=np.full(n, 0.5, np.float32))
+    for k, v in cols.items():
+        q[k] = np.asarray(v, q[k].dtype)
+    return q
+
+
+def test_gate_truth_table():
+    gate_terms = [("min_side", "side", 40, [39.0, 40.0, 41.0], [False, True, True]),
+                  ("min_sharpness", "sharpness", 5.0, [4.9, 5.0, np.nan], [False, True, False]),
+                  ("min_contrast", "contrast", 10.0, [9.0, 10.0, np.nan], [False, True, False]),
+                  ("max_dark_frac", "dark_frac", 0.5, [0.6, 0.5, 0.0], [False, True, True]),
+                  ("max_bright_frac", "bright_frac", 0.5, [0.6, 0.5, 0.0], [False, True, True]),
+                  ("max_abs_yaw", "yaw", 0.4, [-0.5, 0.4, -0.4], [False, True, True]),
+                  ("max_abs_roll", "roll", 0.2, [0.3, -0.2, 0.0], [False, True, True]),
+                  ("pitch_range", "pitch", (0.3, 0.7), [0.2, 0.3, 0.8], [False, True, False])]
+    everything = {}
+    for term, col, thr, values, want in gate_terms:
+        m = Q.QualityGate(**{term: thr}).mask(_q(3, **{col: values}))
+        assert m.dtype == torch.bool and m.tolist() == want, term
+        assert Q.QualityGate().mask(_q(3, **{col: values})).tolist() == [True] * 3, term        # every threshold is off by default
+        everything[term] = thr
+    full = Q.QualityGate(**everything)
+    assert full.mask(_q(2)).tolist() == [True, True]
+    for term, col, thr, values, want in gate_terms:          # one failing column fails the conjunction
+        assert full.mask(_q(1, **{col: values[:1]})).tolist() == [False], term
+    assert not Q.QualityGate().uses_pose and Q.QualityGate(pitch_range=(0, 1)).uses_pose
+    assert "min_side=40" in repr(Q.QualityGate(min_side=40)) and "yaw" not in repr(Q.QualityGate(min_side=40))
+
+
+def test_gate_flag_rules():
+    flags = [0, Q.EMPTY, Q.BAD_FRAME, Q.TOO_LARGE, Q.NO_LAPLACIAN, Q.POSE_DEGENERATE, Q.NO_LAPLACIAN | Q.POSE_DEGENERATE]
+    q = _q(len(flags), flags=flags)
+    assert Q.QualityGate().mask(q).tolist() == [True, False, False, False, True, True, True]
+    assert Q.QualityGate(min_side=1).mask(q).tolist() == [True, False, False, False, True, True, True]
+    assert Q.QualityGate(min_sharpness=0.0).mask(q).tolist() == [True, False, False, False, False, True, False]
+    for pose in (dict(max_abs_yaw=9.0), dict(max_abs_roll=9.0), dict(pitch_range=(-9, 9))):
+        assert Q.QualityGate(**pose).mask(q).tolist() == [True, False, False, False, True, False, False], pose
+    # a rectangle narrower than one block counts no pixel: unusable, whatever its flags say
+    none = _q(1, flags=[Q.NO_LAPLACIAN])
+    none["stats"][0, 0] = 0
+    assert Q.QualityGate().mask(none).tolist() == [False]
+    # a pose threshold over a dict without the pose columns is refused, not passed
+    nopose = {k: v for k, v in _q(2).items() if k not in Q.POSE_FIELDS}
+    assert Q.QualityGate(min_side=1).mask(nopose).tolist() == [True, True]
+    with pytest.raises(ValueError):
+        Q.QualityGate(max_abs_yaw=0.5).mask(nopose)
+    # on real rows: the unusable rectangles of the shared case fail, the others pass an open gate
+    case = QC.CASES[0]
+    q = QC.expected(case)
+    assert Q.QualityGate().mask(q).tolist() == (((q["flags"] & Q.UNUSABLE) == 0) & (q["stats"][:, 0] > 0)).tolist()
+
+
+# ------------------------------------------------------------------------------------------------ best_per_group
+
+def _best_loop(score, groups, n_groups, mask=None):
+    out = [-1] * n_groups
+    for i, (s, g) in enumerate(zip(score, groups)):
+        if not 0 <= g < n_groups or (mask is not None and not mask[i]) or s != s:
+            continue
+        if out[g] < 0 or s > score[out[g]]:
+            out[g] = i
+    return out
+
+
+def test_best_per_group():
+    score = torch.tensor([1.0, 5.0, 5.0, 2.0, 9.0, 3.0, 7.0, float("nan"), 4.0])
+    groups = torch.tensor([0, 1, 1, 0, -1, 3, 3, 0, 5], dtype=torch.int32)
+    got = Q.best_per_group(score, groups, 5)
+    assert got.dtype == torch.int32 and got.tolist() == [3, 1, -1, 6, -1]        # tie -> row 1; group 2 empty; -1, NaN and 5 ignored
+    mask = torch.tensor([1, 0, 1, 0, 1, 1, 0, 1, 1], dtype=torch.bool)
+    assert Q.best_per_group(score, groups, 5, mask).tolist() == [0, 2, -1, 5, -1]
+    assert Q.best_per_group(score, groups, 5, torch.zeros(9, dtype=torch.bool)).tolist() == [-1] * 5
+    assert Q.best_per_group(torch.zeros(0), torch.zeros(0, dtype=torch.int64), 3).tolist() == [-1] * 3
+    assert Q.best_per_group(score, groups, 0).tolist() == []
+    assert Q.best_per_group(torch.full((4,), float("-inf")), torch.tensor([1, 1, 0, 0]), 2).tolist() == [2, 0]
+    rng = np.random.default_rng(5)
+    for _ in range(20):
+        n, k = int(rng.integers(1, 200)), int(rng.integers(1, 12))
+        s = rng.integers(0, 6, n).astype(np.float64)          # few values: many ties
+        g = rng.integers(-2, k + 1, n)
+        m = rng.random(n) < 0.7
+        assert Q.best_per_group(torch.from_numpy(s), torch.from_numpy(g), k, torch.from_numpy(m)).tolist() == _best_loop(s, g, k, m)
+        assert Q.best_per_group(s, g, k).tolist() == _best_loop(s, g, k)
+
+
+def test_cluster_faces_best_shot_helpers(tmp_path):
+    """cluster_faces.py's --best-shot pieces on host data: the pick per cluster, the files, the arrays of clusters.npz."""
+    from face_detection_and_recognition_amd.similar_face_filtering import cluster_faces as CF
+    assert CF.get_parsed_args(["--ud", "u", "--best-shot"]).best_shot and not CF.get_parsed_args(["--ud", "u"]).best_shot
+    rng = np.random.default_rng(2)
+    sharp = rng.integers(0, 256, (40, 40, 3), dtype=np.uint8)
+    frames = [QC.box_blur(sharp, 2), sharp, QC.box_blur(sharp, 1), sharp[:2, :30], sharp]
+    items = np.array([QC.item(k, 0, 0, f.shape[1], f.shape[0]) for k, f in enumerate(frames)], np.int32)
+    q = Q.face_quality_emulate(frames, items)
+    labels = [0, 0, 1, 2, -1]                                   # cluster 2 holds only a 30 x 2 strip: no Laplacian, no pick
+    best = CF.best_shots(q, labels, 3)
+    assert best.tolist() == [1, 2, -1]
+    paths = []
+    for k in range(5):
+        paths.append(str(tmp_path / f"img_{k}.jpg"))
+        open(paths[-1], "wb").write(bytes([k]) * 10)
+    for c in range(3):
+        os.makedirs(tmp_path / "out" / CF.cluster_name(c))
+    written = CF.copy_best_shots(paths, best, str(tmp_path / "out"))
+    assert len(written) == 2 and (tmp_path / "out" / "cluster_0000" / "best.jpg").read_bytes() == bytes([1]) * 10
+    assert (tmp_path / "out" / "cluster_0001" / "best.jpg").read_bytes() == bytes([2]) * 10
+    assert not (tmp_path / "out" / "cluster_0002" / "best.jpg").exists()
+    extra = {f"quality_{k}": q[k] for k in ("stats",) + CF.QUALITY_COLUMNS}
+    extra["best_shot"] = best
+    npz = CF.save_clusters(str(tmp_path / "clusters.npz"), paths, labels, [1] * 5, [2] * 5, np.zeros((3, 4)), [0, 2, 3], extra)
+    with np.load(npz, allow_pickle=False) as z:
+        assert z["best_shot"].tolist() == [1, 2, -1] and np.array_equal(z["quality_sharpness"], q["sharpness"], equal_nan=True)
+        assert z["quality_stats"].shape == (5, 8) and z["medoid"].tolist() == [0, 2, 3]
+
+
+# ------------------------------------------------------------------------------------------------ ABI
+
+def test_abi_of_the_new_entry_points(lib):
+    hdr = open(os.path.join(ROOT, "include", "facepath.h")).read()
+    assert lib.fp_abi_version() == L.ABI_VERSION == 14
+    for name in ("fp_face_quality", "fp_face_quality_emulate", "fp_face_pose", "fp_face_pose_emulate"):
+        m = re.search(r"\bint " + name + r"\(([^;]*)\);", hdr)
+        assert m, name
+        params = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
+        assert len(L.SIGNATURES[name][1]) == len(params.split(",")), name
+        assert hasattr(lib, name)
+    assert [len(L.SIGNATURES[n][1]) for n in ("fp_face_quality", "fp_face_quality_emulate", "fp_face_pose", "fp_face_pose_emulate")] == [9, 8, 6, 5]
+    consts = {k: int(v) for k, v in re.findall(r"#define FP_QUALITY_([A-Z_]+) (\d+)", hdr)}
+    assert consts == dict(MAX_STEP=L.QUALITY_MAX_STEP, EMPTY=Q.EMPTY, BAD_FRAME=Q.BAD_FRAME, NO_LAPLACIAN=Q.NO_LAPLACIAN,
+                          TOO_LARGE=Q.TOO_LARGE, POSE_DEGENERATE=Q.POSE_DEGENERATE)
+    assert len({Q.EMPTY, Q.BAD_FRAME, Q.NO_LAPLACIAN, Q.TOO_LARGE, Q.POSE_DEGENERATE}) == 5

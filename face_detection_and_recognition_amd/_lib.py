@@ -116,7 +116,8 @@ DRAW_RECT, DRAW_FILL, DRAW_RING, DRAW_GLYPH, DRAW_MOSAIC = 1, 2, 3, 4, 5   # fp_
 DRAW_TILE, DRAW_FONT_BYTES = 64, 760                                       # FP_DRAW_TILE, FP_DRAW_FONT_BYTES
 DRAW_MAX_ARG, DRAW_MAX_SCALE, DRAW_MAX_COORD = 4096, 64, 1 << 20           # FP_DRAW_MAX_*
 DRAW_MOSAIC_CELLS = (4, 8, 16, 32)
-QUALITY_MAX_STEP = 64                                                      # FP_QUALITY_MAX_STEP
+MERGE_CAP = 2048                                                           # FP_MERGE_CAP: candidates fp_merge_views takes per frame
+QUALITY_MAX_STEP = 64                                                     # FP_QUALITY_MAX_STEP
 QUALITY_EMPTY, QUALITY_BAD_FRAME, QUALITY_NO_LAPLACIAN, QUALITY_TOO_LARGE, QUALITY_POSE_DEGENERATE = 1, 2, 4, 8, 16   # FP_QUALITY_*
 
 JPEG_DECODE_ON_HOST = 1          # fp_jpeg_entropy_decode_device status: decode this image with fp_jpeg_entropy_decode
@@ -222,6 +223,9 @@ SIGNATURES = {
     "fp_face_quality_emulate": (_I, [_P, _SZ, _P, _I, _P, _I, _P, _P]),
     "fp_face_pose": (_I, [_P, _I, _I, _P, _P, _P]),
     "fp_face_pose_emulate": (_I, [_P, _I, _I, _P, _P]),
+    "fp_merge_views": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _F, _I, _P, _P, _P, _P]),
+    "fp_merge_views_emulate": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _F, _I, _P, _P, _P]),
+    "fp_gather_tiles": (_I, [_P, _SZ, _P, _I, _P, _I, _I, _I, _P, _P]),
 }
 
 _lib = None

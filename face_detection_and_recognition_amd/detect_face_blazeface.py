@@ -1,13 +1,16 @@
 """``python -m face_detection_and_recognition_amd.detect_face_blazeface -i img.jpg --md w.pth --mt back``
 Entry point with the reference's flags (face_detection_and_extraction/detect_face_blazeface.py:7-34).  Images
 only (the video / webcam GUI loops are out of scope); prints the post-processed detections as JSON.  ``-o out.jpg`` also
-saves the image with the detections drawn on, ``--anonymize CELL`` pixelates the faces in it first (annotate.py)."""
+saves the image with the detections drawn on, ``--anonymize CELL`` pixelates the faces in it first (annotate.py).  ``--tile W H
+--merge_thr T`` (with ``--overlap``, ``--edge_px``, ``--no_full_frame``) runs the detector on overlapping tiles of the image as well and
+merges the detections on the device (tiling.py)."""
 import argparse
 import json
 
 from .modules.blazeface.model import BlazeFaceModel
 from .modules.utils.inference import inference_img
 from .modules.utils.parser import get_argparse, torch_device
+from .tiling import add_tile_args, wrap_from_args
 
 
 def build_parser():
@@ -21,14 +24,16 @@ def build_parser():
                         help="Write the image with its detections drawn on (box, landmarks, caption) to this JPEG file.")
     parser.add_argument("--anonymize", dest="anonymize", type=int, choices=[4, 8, 16, 32], default=argparse.SUPPRESS, metavar="CELL",
                         help="With -o: pixelate every detected face first, mosaic cells of CELL x CELL pixels (4, 8, 16 or 32).")
-    return parser
+    return add_tile_args(parser)
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
     print("Current Arguments: ", args)
     net = BlazeFaceModel(args.model, args.det_thres, args.bbox_area_thres, args.model_type,
                          torch_device(args.device))
+    net = wrap_from_args(net, args, parser.error)
     post = inference_img(net, args.input_src, save=getattr(args, "output", None), anonymize=getattr(args, "anonymize", 0))
     print(json.dumps({"boxes": post.boxes.tolist(), "confs": post.bbox_confs.tolist(),
                       "areas": post.bbox_areas.tolist(), "landmarks": post.bbox_lmarks.tolist()}))

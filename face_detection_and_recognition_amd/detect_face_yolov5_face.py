@@ -1,6 +1,8 @@
 """``python -m face_detection_and_recognition_amd.detect_face_yolov5_face -i img.jpg --md yolov5n-face.pt``
 Entry point with the reference's flags (face_detection_and_extraction/detect_face_yolov5_face.py:13-66).  ``-o out.jpg`` also
-saves the image with the detections drawn on, ``--anonymize CELL`` pixelates the faces in it first (annotate.py)."""
+saves the image with the detections drawn on, ``--anonymize CELL`` pixelates the faces in it first (annotate.py).  ``--tile W H
+--merge_thr T`` (with ``--overlap``, ``--edge_px``, ``--no_full_frame``) runs the detector on overlapping tiles of the image as well and
+merges the detections on the device (tiling.py)."""
 import argparse
 import json
 import os
@@ -10,6 +12,7 @@ from .modules.utils.inference import inference_img
 from .modules.utils.parser import get_argparse, torch_device
 from .modules.yolov5_face import attempt_load, inference_pytorch_model_yolov5_face
 from .modules.yolov5_face.model import YOLOV5FaceModel
+from .tiling import add_tile_args, wrap_from_args
 
 
 def load_model(model_path: str, det_thres: float, bbox_area_thres: float, model_in_size: Tuple[int, int], device: str):
@@ -33,14 +36,16 @@ def build_parser():
                         help="Write the image with its detections drawn on (box, landmarks, caption) to this JPEG file.")
     parser.add_argument("--anonymize", dest="anonymize", type=int, choices=[4, 8, 16, 32], default=argparse.SUPPRESS, metavar="CELL",
                         help="With -o: pixelate every detected face first, mosaic cells of CELL x CELL pixels (4, 8, 16 or 32).")
-    return parser
+    return add_tile_args(parser)
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
     print("Current Arguments: ", args)
     args.input_size = tuple(map(int, args.input_size))
     net = load_model(args.model, args.det_thres, args.bbox_area_thres, args.input_size, args.device)
+    net = wrap_from_args(net, args, parser.error)
     post = inference_img(net, args.input_src, save=getattr(args, "output", None), anonymize=getattr(args, "anonymize", 0))
     print(json.dumps({"boxes": post.boxes.tolist(), "confs": post.bbox_confs.tolist(), "areas": post.bbox_areas.tolist()}))
     return post

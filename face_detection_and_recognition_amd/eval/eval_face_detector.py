@@ -6,7 +6,9 @@ face_detection_and_extraction/eval/eval_face_detector.py -- which hands the work
 ``--model`` are the reference's; ``--model_type`` takes blazeface, yolov5_face and mtcnn, ``--mt`` the variant (back / front,
 fast / slow, or the YOLOv5-face architecture name), ``--is W H`` the input size, ``-d`` the device, ``--batch`` the frames
 per detector call.  ``--dets detections.json`` scores an existing COCO-format detection file without running a detector.
-``--model synthetic`` runs seeded random weights (synth.py / workload.py).  Writes annotations.json and detections.json in
+``--model synthetic`` runs seeded random weights (synth.py / workload.py).  ``--tile W H --merge_thr T`` (with ``--overlap``,
+``--edge_px``, ``--no_full_frame``) scores the detector run on overlapping tiles of every image and on the whole image
+(tiling.TiledDetector; blazeface and yolov5_face, MTCNN refuses).  Writes annotations.json and detections.json in
 the reference's formats into ``--out`` (default: the current directory), prints the summary and returns the result.
 """
 import argparse
@@ -17,6 +19,7 @@ import numpy as np
 import torch
 
 from ..evaluation import DetectionEvaluator, clamp_boxes_xywh, coco_eval_bbox, dets_to_frame_boxes
+from ..tiling import add_tile_args, wrap_from_args
 
 
 def parse_wider(path, images_root=""):
@@ -170,6 +173,7 @@ def main(argv=None):
     parser.add_argument("--dets", default=None, help="Score this COCO-format detections.json instead of running a detector.")
     parser.add_argument("--out", default=".", help="Directory for annotations.json (written in --dets mode too) and detections.json "
                                                   "(default: %(default)s).")
+    add_tile_args(parser)
     args = parser.parse_args(argv)
     if args.batch < 1:
         parser.error("--batch must be positive")
@@ -191,7 +195,10 @@ def main(argv=None):
             raise NotImplementedError("the detectors have no CPU path: use -d hip, or --dets with -d cpu")
         if args.model is None:
             parser.error("--model is required unless --dets is given")
-        det = load_detector(args, device)
+        try:
+            det = wrap_from_args(load_detector(args, device), args, parser.error)
+        except ValueError as e:          # MTCNN under --tile, a bad tile / overlap
+            parser.error(str(e))
         evaluator = DetectionEvaluator(len(names), device).set_ground_truth(gt_boxes, gt_ids)
         cut = run_detector(det, names, device, args.batch, evaluator)
         if cut:

@@ -40,7 +40,7 @@ class FrameFacesObj:
 
 
 def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=None, save_face=False,
-                                     quality=95, align=False, quality_gate=None) -> List[FrameFacesObj]:
+                                     quality=95, align=False, quality_gate=None, tiled=None) -> List[FrameFacesObj]:
     """frames: (B, H, W, 3) u8 BGR (numpy or CUDA tensor), a RaggedFrames, or a list of (h, w, 3) frames.  One FacePipeline
     step (no similarity filter needed); returns per-frame records with boxes (each frame's own pixels, rounded), confs,
     area fractions and embeddings.  A list whose frames share one size is stacked and takes the uniform path; otherwise it
@@ -50,19 +50,26 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
     aligned faces the embedder saw (as u8), under the same names.  quality_gate: a quality.QualityGate; every face is measured
     (quality.face_quality on the step's items, with its landmarks when the step is aligned) and the faces that fail the gate
     are left out of the records -- before save_extracted_faces applies the per-frame face cap, so a frame's
-    MAX_N_FACES_PER_FRAME slots go to usable faces.  A gate with a pose term needs align (ValueError otherwise)."""
+    MAX_N_FACES_PER_FRAME slots go to usable faces.  A gate with a pose term needs align (ValueError otherwise).
+    tiled: dict(tile=(w, h), overlap=(ox, oy), merge_thr=t[, edge_px, full_frame, max_det]): for this call the pipeline's
+    detector runs on overlapping tiles of every frame as well (tiling.TiledDetector over pipe.det; merge_thr has no default)."""
     if isinstance(frames, (list, tuple)) and not frames:
         return []
     frames = as_frames(frames, pipe.dev)
     B = len(frames)
-    if align and not pipe.align:
-        pipe.align = True
-        try:
-            res = pipe.step(frames)
-        finally:
-            pipe.align = False
-    else:
+    was = (pipe.det, pipe.align)
+    if tiled is not None:
+        from ..tiling import TiledDetector
+        key = tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in tiled.items()))
+        cache = pipe.__dict__.setdefault("_tiled_dets", {})          # one wrapper (and its view tables) per option set
+        if (id(pipe.det), key) not in cache:
+            cache[(id(pipe.det), key)] = TiledDetector(pipe.det, **tiled)
+        pipe.det = cache[(id(pipe.det), key)]
+    pipe.align = pipe.align or bool(align)
+    try:
         res = pipe.step(frames)               # detect -> crops -> embed (+ the exact re-run on a detector overflow)
+    finally:
+        pipe.det, pipe.align = was
     n = res["n_faces"]
     emb = res["emb"].cpu().numpy()
     info = res["info"].cpu().numpy()
@@ -70,7 +77,8 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
     if quality_gate is not None:
         from ..quality import face_quality
         lm = res.get("lmarks")
-        q = face_quality(frames, res["items"], n, lmarks=lm, fmt=None if lm is None else pipe.det.dets_fmt)
+        fmt = 2 if tiled is not None else pipe.det.dets_fmt      # a tiled step's landmarks are fmt-2 rows
+        q = face_quality(frames, res["items"], n, lmarks=lm, fmt=None if lm is None else fmt)
         keep = quality_gate.mask(q).cpu().numpy()
     jpegs = None
     if save_face:
@@ -103,18 +111,18 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
 
 
 def extract_faces_from_images(pipe, paths, batch_size=256, entropy="host", save_face=False, quality=95,
-                              align=False, quality_gate=None) -> List[FrameFacesObj]:
+                              align=False, quality_gate=None, tiled=None) -> List[FrameFacesObj]:
     """The reference's image media items (:400-407: one photo per item, any size, recorded as FrameFacesObj(1, 1, ...)) for a
     whole list of files: decode batch_size files at a time (modules/utils/jpeg.py imread_batch; entropy as there), then one
     pipeline step per batch -- frames of different sizes as one RaggedFrames.  Returns one record per path, in order; pass
-    each to save_extracted_faces under its file's media_root.  align, quality_gate: as extract_face_feat_conf_area_list."""
+    each to save_extracted_faces under its file's media_root.  align, quality_gate, tiled: as extract_face_feat_conf_area_list."""
     from ..modules.utils.jpeg import imread_batch
     out = []
     for i in range(0, len(paths), int(batch_size)):
         chunk = paths[i:i + int(batch_size)]
         frames = imread_batch(chunk, pipe.dev, entropy=entropy)     # (B, H, W, 3) when the sizes agree, else a list
         recs = extract_face_feat_conf_area_list(pipe, frames, save_face=save_face, quality=quality, align=align,
-                                                quality_gate=quality_gate)
+                                                quality_gate=quality_gate, tiled=tiled)
         for r in recs:
             r.frame_num, r.time_sec = 1, 1
         out.extend(recs)

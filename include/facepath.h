@@ -1245,6 +1245,65 @@ int fp_face_pose(const float* lmarks /* n x 10 */, int fmt, int n, float* out /*
                  void* stream);
 int fp_face_pose_emulate(const float* lmarks, int fmt, int n, float* out, int32_t* flags);
 
+/*
+ * Tiled detection (build-defined, no reference counterpart; DESIGN §7 "Tiled detection"; csrc/tilemerge.hip).  A detector
+ * that sees a frame through one letterbox loses small faces; tiling.py runs it on overlapping tiles of every frame and on
+ * the whole frame.  Each such image is a VIEW of its frame.  All additive: ABI 14.
+ *
+ * fp_tile_view, 32 bytes: frame = index into descs; (x0, y0) = the view's origin in the frame; vw x vh = the part of the
+ * view's image that holds frame pixels (a tile larger than its frame: the frame's size); gain, pad_x, pad_y = the
+ * scale_coords values (modules/utils/image.py) of the image the detector was given (tile_w x tile_h for a tile, the frame
+ * for a whole-frame view) against the detector's input size.  The views of one frame are contiguous: frame f owns
+ * views[view_start[f] .. view_start[f + 1]), and dets [S][max_dets][row_floats] / counts [S] are the detector's rows of the
+ * views in the same order (fmt 0: BlazeFace rows, row_floats >= 17; fmt 1: YOLOv5-face rows with landmarks, >= 15).
+ *
+ * fp_merge_views: one workgroup per frame, all arithmetic fp32 in the written order, no contraction.
+ *   1. Every row r < min(max(counts[s], 0), max_dets) of every view s of the frame is a candidate, in (view, row) order; only
+ *      the first FP_MERGE_CAP are taken (overflow[f] |= 2 when there were more).  Model-input coordinates c as
+ *      fp_dets_to_crops takes them: fmt 0 column * in_w / in_h with the (y, x) column swap, fmt 1 as stored.
+ *   2. View pixels: v = (c - pad) / gain.
+ *   3. Cut rule.  A view edge is interior when it is not the frame's: x0 > 0, x0 + vw < W, y0 > 0, y0 + vh < H.  With
+ *      edge_px >= 0 a candidate is dropped when v_x1 <= edge_px at an interior left edge, v_x2 >= vw - edge_px at an interior
+ *      right edge, and the same in y.  Frame edges never cut; a whole-frame view has no interior edge; edge_px < 0: no cut.
+ *   4. The box is clamped to [0, vw] x [0, vh], then (float)x0, (float)y0 are added.  Landmarks take v = (c - pad) / gain +
+ *      origin, unclamped and unrounded: fmt 1 landmark i -> slot i; fmt 0 keypoints 0, 1, 2 -> slots 0, 1, 2, keypoint 3 (the
+ *      mouth centre) -> slots 3 AND 4, the ears are dropped.
+ *   5. Dropped: a candidate whose score or unclamped view box is not finite, and one with x2 <= x1 or y2 <= y1.
+ *   6. Order: score descending (-0 counts as +0), then view ascending, then row ascending.
+ *   7. Greedy hard suppression: walking in that order, a candidate c is kept unless an earlier kept box k has
+ *      inter > merge_thr * fminf(area_k, area_c), inter = max(min(x2) - max(x1), 0) * max(min(y2) - max(y1), 0):
+ *      intersection over the SMALLER area.  merge_thr = +inf suppresses nothing.
+ *   8. Kept rows go to out [B][max_out][16] in walk order = x1, y1, x2, y2, (x, y) x 5, score @ 14, 0: the fmt-2 row of
+ *      fp_dets_to_crops_px, in the frame's own pixels.  out_counts[f] = rows written (at most max_out; overflow[f] |= 4
+ *      when more were kept); rows behind the count are not written.  overflow [B] is OR-ed into: the caller presets it
+ *      (0, or 1 where the detector cut a view of the frame at its own cap).
+ * No global atomics, no workspace; two runs are bit-identical.  Refusals before any launch (FP_ERR_INVALID_ARG): a NULL
+ * pointer, fmt other than 0 / 1, a row too short for its format, max_dets, max_out, in_w or in_h < 1, a NaN merge_thr,
+ * B < 0 or S < 0.  B == 0: FP_OK, nothing launched.  views, view_start, counts and descs are device memory the host does
+ * not read: the kernel clamps view ranges to [0, S] and row counts to max_dets and writes nothing outside out[f].
+ * fp_merge_views_emulate: the same code serially on HOST memory (every pointer HOST), the same bits.
+ *
+ * fp_gather_tiles: out [S][tile_h][tile_w][3] u8 <- the rectangle (x0, y0, vw, vh) of every view's frame at the tile's top
+ * left, every other byte 125 (the letterbox pad value); either kind of batch (a dense batch is n_frames equal descriptors),
+ * one launch.  A view whose frame index, descriptor or origin is unusable becomes all 125.  Refusals: a NULL pointer,
+ * n_frames < 1, S < 0, a tile size outside 1 .. FP_FRAME_MAX_W x 1 .. FP_FRAME_MAX_H (FP_ERR_INVALID_ARG).  S == 0: FP_OK.
+ */
+typedef struct fp_tile_view {
+  int32_t frame;
+  int32_t x0, y0, vw, vh;
+  float gain, pad_x, pad_y;
+} fp_tile_view;              /* 32 bytes */
+#define FP_MERGE_CAP 2048
+int fp_merge_views(const float* dets, const int32_t* counts, int S, int max_dets, int row_floats, int fmt, int in_w, int in_h,
+                   const fp_tile_view* views, const int32_t* view_start /* B + 1 */, const fp_frame_desc* descs, int B,
+                   float merge_thr, float edge_px, int max_out, float* out, int32_t* out_counts, int32_t* overflow,
+                   void* stream);
+int fp_merge_views_emulate(const float* dets, const int32_t* counts, int S, int max_dets, int row_floats, int fmt, int in_w,
+                           int in_h, const fp_tile_view* views, const int32_t* view_start, const fp_frame_desc* descs, int B,
+                           float merge_thr, float edge_px, int max_out, float* out, int32_t* out_counts, int32_t* overflow);
+int fp_gather_tiles(const uint8_t* frames, size_t frames_bytes, const fp_frame_desc* descs /*device*/, int n_frames,
+                    const fp_tile_view* views /*device*/, int S, int tile_w, int tile_h, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

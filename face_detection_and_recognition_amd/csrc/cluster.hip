@@ -2,9 +2,9 @@
 //
 // The threshold graph  i ~ j  <=>  <X[i], X[j]> * inv[i] * inv[j] >= tau  is never stored.  It is walked twice, each time over
 // the UPPER TRIANGLE only (row tiles of 128 rows x 128-column chunks, a chunk is walked when it is not wholly at or below its
-// row tile's first row), with the arithmetic and the pipeline of cosine_topk_x6_kernel (sim.hip): planes of fp_split3_rows
-// staged by LDS-DMA, double-buffered, rows split in registers, fp_mfma_x6, score = acc * inv[i] * inv[j].  A pair (i < j) is
-// evaluated once, row i the register-split operand: the decision is unique.
+// row tile's first row), on the walk of cosinewalk.h (cw_walk: planes of fp_split3_rows staged by LDS-DMA, double-buffered,
+// rows split in registers), score = acc * inv[i] * inv[j].  A pair (i < j) is evaluated once, row i the register-split
+// operand: the decision is unique.
 //   pass 1 (degree): every edge adds one to the degree of both endpoints and enters both neighbour lists (min_samples - 2
 //           slots per point: complete for every non-core point, truncated and never read for a core point);
 //   pass 2 (union):  the same walk with the inverse norms of the non-core points zeroed -- a zero inverse norm is the library's
@@ -16,13 +16,10 @@
 // Then: flatten (root of every core point = the smallest row of its cluster), rank the roots (exclusive scan), label.
 // The result is a function of the edge set: degrees are sums, the root of a component is its minimum, a border point takes the
 // minimum over its complete list -- no arrival order, launch geometry or schedule enters.
-#include "split.h"
+#include "cosinewalk.h"
 #include "triwalk.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) void* lds_ptr;
-typedef const __attribute__((address_space(1))) void* gbl_ptr;
 
 constexpr int CL_MAX_MS = 64;
 
@@ -72,99 +69,29 @@ __global__ __launch_bounds__(256, 3) void cluster_walk_kernel(const float* __res
                                                                const unsigned short* __restrict__ X3, int Npad, int D, float tau,
                                                                int P, int* __restrict__ degree, int* __restrict__ nbr, int L,
                                                                int* __restrict__ parent) {
-  constexpr int MT = 2, NT16 = 8, NC = CL_NC, SLAB = 3 * NC * 32;
+  constexpr int MT = 2, NT16 = CW_NT16;
   typedef unsigned long long u64;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  unsigned short* Bl = (unsigned short*)smem_raw;        // [2][3][NC][32]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, q = lane >> 4;
-  const int nchunk = Npad / NC;
+  const int nchunk = Npad / CW_NC;
   // the longest rows first; the groups of one row tile next to each other on ONE XCD (its rows from that L2)
   const cl_item it = cl_decode((long)gridDim.x - 1 - (long)fp_xcd_block(), nchunk, P);
   const int cb = __builtin_amdgcn_readfirstlane(it.first), nck = __builtin_amdgcn_readfirstlane(it.count);
   const long row0 = (long)__builtin_amdgcn_readfirstlane(it.tile) * CL_ROWS + wave * (MT * 16);
-  const int KS = D / 32;
   const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-  const float qnan = __builtin_nanf("");
 
-  auto stage = [&](int chunk, int ks, int buf) {
-    unsigned char* dst = (unsigned char*)(Bl + buf * SLAB);
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-      const unsigned char* src = (const unsigned char*)(X3 + ((long)(ks * 3 + pl) * Npad + (long)chunk * NC) * 32) + lane * 16;
-#pragma unroll
-      for (int j = 0; j < NT16 / 4; ++j) {
-        const int c = j * 4 + wave;
-        __builtin_amdgcn_global_load_lds((gbl_ptr)(src + c * 1024), (lds_ptr)(dst + (pl * NC * 32 + c * 512) * 2), 16, 0, 0);
-      }
-    }
-  };
-  const float* Xw = X + fp_uniform(row0 * D);             // this wave's rows (rows past N - 1 read row N - 1, their inv is 0)
-  int arow[MT];
-#pragma unroll
-  for (int t = 0; t < MT; ++t) {
-    long r = row0 + 16 * t + l15;
-    r = r < N ? r : N - 1;
-    arow[t] = (int)(r - row0) * D + 8 * q;
-  }
-  f32x4 araw[MT][2];
-  auto load_a = [&](int ks) {
-#pragma unroll
-    for (int t = 0; t < MT; ++t) {
-      araw[t][0] = *(const f32x4*)(Xw + arow[t] + 32 * ks);
-      araw[t][1] = *(const f32x4*)(Xw + arow[t] + 32 * ks + 4);
-    }
-  };
-  f32x4 acc[MT][NT16];
-#pragma unroll
-  for (int t = 0; t < MT; ++t)
-#pragma unroll
-    for (int n = 0; n < NT16; ++n) acc[t][n] = z;
-
-  const int steps = nck * KS;
-  int ks = 0, chunk = cb;                                // of the step being computed
-  stage(cb, 0, 0);
-  load_a(0);
-  for (int s = 0; s < steps; ++s) {
-    fp_frag3 af[MT];
-#pragma unroll
-    for (int t = 0; t < MT; ++t) af[t] = fp_split8(araw[t][0], araw[t][1]);
-    __syncthreads();
-    if (s + 1 < steps) {
-      const bool last = ks + 1 == KS;
-      stage(last ? chunk + 1 : chunk, last ? 0 : ks + 1, (s + 1) & 1);
-      load_a(last ? 0 : ks + 1);
-    }
-    const unsigned short* Bc = Bl + (s & 1) * SLAB + (l15 * 32 + 8 * q);
-    fp_frag3 bf[2];
-    auto ldb = [&](int n, fp_frag3& b) {
-      b.h = *(const u32x4*)(Bc + n * 512);
-      b.m = *(const u32x4*)(Bc + NC * 32 + n * 512);
-      b.l = *(const u32x4*)(Bc + 2 * NC * 32 + n * 512);
-    };
-    ldb(0, bf[0]);
-#pragma unroll
-    for (int n = 0; n < NT16; ++n) {
-      if (n + 1 < NT16) ldb(n + 1, bf[(n + 1) & 1]);
-      const fp_frag3& b = bf[n & 1];
-#pragma unroll
-      for (int t = 0; t < MT; ++t) acc[t][n] = fp_mfma_x6(b.h, b.m, b.l, af[t].h, af[t].m, af[t].l, acc[t][n]);
-    }
-    if (++ks < KS) continue;
-    ks = 0;
-
-    // epilogue of a chunk: lane = row 16 t + l15, columns c0 + 16 n + 4 q + i.  Bit 4 n + i of eb[t]: that pair is an edge.
-    const int c0 = chunk * NC;
-    ++chunk;
+  // rows past N - 1 read row N - 1, their inv is 0.  Epilogue of a chunk: lane = row 16 t + l15, columns c0 + 16 n + 4 q + i.
+  // Bit 4 n + i of eb[t]: that pair is an edge.
+  cw_walk<MT>(X, N, row0, X3, Npad, D, cb, nck, (unsigned short*)smem_raw, [&](int c0, f32x4 (&acc)[MT][NT16]) {
     float gi[MT];
     int rowi[MT];
     unsigned eb[MT];
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
       rowi[t] = (int)row0 + 16 * t + l15;                // < Npad
-      const float g = inv[rowi[t]];
-      gi[t] = g == 0.f ? qnan : g;                       // dead row / past N: every score is NaN, NaN >= tau is false
+      gi[t] = cw_nan_if_zero(inv[rowi[t]]);              // dead row / past N: every score is NaN, NaN >= tau is false
       eb[t] = 0;
     }
 #pragma unroll
@@ -172,7 +99,7 @@ __global__ __launch_bounds__(256, 3) void cluster_walk_kernel(const float* __res
       const int colb = c0 + 16 * n + 4 * q;
       f32x4 rn = *(const f32x4*)(inv + colb);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) rn[i] = rn[i] == 0.f ? qnan : rn[i];
+      for (int i = 0; i < 4; ++i) rn[i] = cw_nan_if_zero(rn[i]);
 #pragma unroll
       for (int t = 0; t < MT; ++t) {
 #pragma unroll
@@ -183,7 +110,7 @@ __global__ __launch_bounds__(256, 3) void cluster_walk_kernel(const float* __res
         acc[t][n] = z;
       }
     }
-    if (__ballot((eb[0] | eb[1]) != 0) == 0) continue;   // the common case of a sparse graph: no edge in this wave's 32 x 128
+    if (__ballot((eb[0] | eb[1]) != 0) == 0) return;     // the common case of a sparse graph: no edge in this wave's 32 x 128
 
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
@@ -234,7 +161,7 @@ __global__ __launch_bounds__(256, 3) void cluster_walk_kernel(const float* __res
         }
       }
     }
-  }
+  });
 }
 
 // ---- the small kernels around the walks ----------------------------------------------------------------------------
@@ -329,11 +256,6 @@ __global__ __launch_bounds__(256) void cluster_label_kernel(const unsigned char*
   labels[i] = lab;
 }
 
-__device__ __forceinline__ unsigned cl_f2ord(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // One workgroup per cluster: centroid = normalised sum of the members' normalised rows, summed in the order given (thread d
 // owns feature d: a sequential fp32 sum, no atomics), and the medoid: the member with the largest cosine to the centroid,
 // the lower row on ties.  An empty cluster: a zero centroid, medoid -1.
@@ -368,7 +290,7 @@ __global__ __launch_bounds__(256) void cluster_centroid_kernel(const float* __re
     centroids[(long)c * D + d] = v;
   }
   __syncthreads();
-  u64 best = 0;                                          // key = ord(score) << 32 | ~row: larger = better, then the lower row
+  u64 best = 0;                                          // cw_key(score, row): larger = better, then the lower row
   for (int j = mb + wave; j < me; j += 4) {
     const int m = order[j];
     const float* p = X + (long)m * D;
@@ -378,7 +300,7 @@ __global__ __launch_bounds__(256) void cluster_centroid_kernel(const float* __re
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
     s *= xinv[m];
     if (!(s == s)) s = -__builtin_huge_valf();
-    const u64 key = ((u64)cl_f2ord(s) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)m);
+    const u64 key = cw_key(s, (unsigned)m);
     best = key > best ? key : best;
   }
   if (lane == 0) bestk[wave] = best;
@@ -386,7 +308,7 @@ __global__ __launch_bounds__(256) void cluster_centroid_kernel(const float* __re
   if (tid == 0) {
     u64 b = bestk[0];
     for (int w = 1; w < 4; ++w) b = bestk[w] > b ? bestk[w] : b;
-    medoid[c] = b ? (int)(0xFFFFFFFFu - (unsigned)(b & 0xFFFFFFFFull)) : -1;
+    medoid[c] = b ? cw_key_index(b) : -1;
   }
 }
 
@@ -398,7 +320,7 @@ struct cl_ws {
   size_t bytes;
 };
 cl_ws cl_layout(void* ws, int64_t N, int min_samples) {
-  const size_t Npad = (size_t)fp_round_up(N, CL_NC);
+  const size_t Npad = (size_t)fp_round_up(N, CW_NC);
   cl_ws w;
   char* p = (char*)ws;
   w.inv1 = (float*)p;
@@ -430,7 +352,7 @@ int fp_cosine_dbscan_x6(const float* X, const float* xinv, const void* X3, int64
   if (D % 32 || ((uintptr_t)X) % 16 || ((uintptr_t)X3) % 16 || ((uintptr_t)ws) % 16) return FP_ERR_ALIGNMENT;
   const cl_ws w = cl_layout(ws, N, min_samples);
   if (ws_bytes < w.bytes) return FP_ERR_INVALID_ARG;
-  const int n = (int)N, Npad = (int)fp_round_up(N, CL_NC), nchunk = Npad / CL_NC;
+  const int n = (int)N, Npad = (int)fp_round_up(N, CW_NC), nchunk = Npad / CW_NC;
   const long P = cl_chunks_per_group(nchunk, 3);   // the walk runs three workgroups per CU
   const long groups = cl_groups(nchunk, P);
   if (groups >= (1L << 31)) return FP_ERR_UNSUPPORTED;
@@ -441,18 +363,18 @@ int fp_cosine_dbscan_x6(const float* X, const float* xinv, const void* X3, int64
   hipLaunchKernelGGL(cluster_init_kernel, gP, b256, 0, s, xinv, n, Npad, w.inv1, degree, w.parent);
   FP_CHECK_LAUNCH();
   if (min_samples <= 2) {
-    hipLaunchKernelGGL((cluster_walk_kernel<true, true>), dim3((unsigned)groups), b256, CL_LDS, s, X, (const float*)w.inv1, n, x3,
+    hipLaunchKernelGGL((cluster_walk_kernel<true, true>), dim3((unsigned)groups), b256, CW_LDS, s, X, (const float*)w.inv1, n, x3,
                        Npad, D, tau, (int)P, degree, w.nbr, w.L, w.parent);
     FP_CHECK_LAUNCH();
     hipLaunchKernelGGL(cluster_core_kernel, gP, b256, 0, s, (const float*)w.inv1, (const int*)degree, n, Npad, min_samples, core, w.inv2);
     FP_CHECK_LAUNCH();
   } else {
-    hipLaunchKernelGGL((cluster_walk_kernel<true, false>), dim3((unsigned)groups), b256, CL_LDS, s, X, (const float*)w.inv1, n, x3,
+    hipLaunchKernelGGL((cluster_walk_kernel<true, false>), dim3((unsigned)groups), b256, CW_LDS, s, X, (const float*)w.inv1, n, x3,
                        Npad, D, tau, (int)P, degree, w.nbr, w.L, w.parent);
     FP_CHECK_LAUNCH();
     hipLaunchKernelGGL(cluster_core_kernel, gP, b256, 0, s, (const float*)w.inv1, (const int*)degree, n, Npad, min_samples, core, w.inv2);
     FP_CHECK_LAUNCH();
-    hipLaunchKernelGGL((cluster_walk_kernel<false, true>), dim3((unsigned)groups), b256, CL_LDS, s, X, (const float*)w.inv2, n, x3,
+    hipLaunchKernelGGL((cluster_walk_kernel<false, true>), dim3((unsigned)groups), b256, CW_LDS, s, X, (const float*)w.inv2, n, x3,
                        Npad, D, tau, (int)P, degree, w.nbr, w.L, w.parent);
     FP_CHECK_LAUNCH();
   }

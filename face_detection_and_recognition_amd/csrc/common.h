@@ -96,6 +96,17 @@ static inline int fp_window_bands(int rows, int N, int per_wg, int slots, int st
 }
 static inline long fp_round_up(long a, long b) { return (a + b - 1) / b * b; }
 
+// Compute units of the current device, asked once (256 if the runtime does not say): what launchers size their grids by.
+static inline int fp_num_cus() {
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus = n;
+  }
+  return cus;
+}
+
 // True if two NHWC views of the arena may share a float: each is (offset, per-image stride, pixels, pixel stride, channels)
 // over N images.  Plans lay the arena out image-major, so views with the same image stride overlap only if one image's
 // extents do; otherwise the whole-batch extents are compared.

@@ -7,23 +7,11 @@
 //    tile) so the M x Nr score matrix is never written to HBM.
 //  * L2-to-class-mean filter, the reference's actual semantics
 //    (similar_face_filtering/filter_faces_using_reference.py:71-100,183-197).
-#include "split.h"
+#include "cosinewalk.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_ptr;
-typedef const __attribute__((address_space(1))) void* gbl_ptr;
-
 constexpr int BM = 128, BN = 128, KC = 32, LDA = KC + 4;
-
-__device__ __forceinline__ unsigned int f2ord(float f) {
-  unsigned int u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(unsigned int o) {
-  unsigned int u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-  return __uint_as_float(u);
-}
 
 __global__ __launch_bounds__(256) void cosine_tile_kernel(const float* __restrict__ G, const float* __restrict__ ginv,
                                                           long M, const float* __restrict__ R,
@@ -117,10 +105,7 @@ __global__ __launch_bounds__(256) void cosine_tile_kernel(const float* __restric
         bidx = oi;
       }
     }
-    if (lr == 0 && m < M && bidx != 0x7FFFFFFF) {
-      const unsigned long long key = ((unsigned long long)f2ord(best) << 32) | (unsigned int)(0xFFFFFFFFu - (unsigned int)bidx);
-      atomicMax(&packed[m], key);
-    }
+    if (lr == 0 && m < M && bidx != 0x7FFFFFFF) atomicMax(&packed[m], cw_key(best, (unsigned)bidx));
   }
 }
 
@@ -129,9 +114,9 @@ __global__ __launch_bounds__(256) void cosine_tile_kernel(const float* __restric
 // The same filter with S = G R^T on the bf16 matrix cores (fp32-equivalent split arithmetic, split.h): the fp32 kernel above
 // reaches 117 TFLOP/s = 74 % of the fp32 MFMA peak; six bf16 products per fp32 product have a peak of 417.
 //   * R is split ONCE into three bf16 planes [D / 32][3][Npad][32] (split3_rows_kernel; the reference set of a filter run is
-//     fixed) -- the B operand, streamed slab by slab through LDS by LDS-DMA, double-buffered, one barrier per slab;
-//   * a workgroup = 4 waves x (MT x 16) gallery rows x 128 reference columns; a wave's A slab goes global -> registers -> split
-//     (as pwx6_kernel); column chunks of one row tile are adjacent in the grid, so the gallery rows are re-read from L2;
+//     fixed) -- the B operand of cw_walk (cosinewalk.h), streamed slab by slab through LDS by LDS-DMA;
+//   * a workgroup = 4 waves x (MT x 16) gallery rows x 128 reference columns, the one-chunk case of the walk; column chunks
+//     of one row tile are adjacent in the grid, so the gallery rows are re-read from L2;
 //   * swapped operands: a lane holds 4 consecutive COLUMNS of one gallery row per accumulator -> the row max over the lane's
 //     32 columns is plain VALU, then two shuffles across the four k-groups, one 64-bit atomicMax per row and workgroup.
 __global__ __launch_bounds__(256) void split3_rows_kernel(const float* __restrict__ R, int Nr, int D, int Npad,
@@ -158,135 +143,68 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 3) void cosine_x6_kernel(const f
                                                                           long M, const unsigned short* __restrict__ R3,
                                                                           const float* __restrict__ rinv, int Nr, int Npad, int D,
                                                                           unsigned long long* __restrict__ packed) {
-  constexpr int NT16 = 8, NC = 128, SLAB = 3 * NC * 32, XBM = 4 * MT * 16;
+  constexpr int NT16 = CW_NT16, XBM = 4 * MT * 16;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  unsigned short* Bl = (unsigned short*)smem_raw;        // [2][3][NC][32]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, q = lane >> 4;
-  const int nchunk = Npad / NC;
+  const int nchunk = Npad / CW_NC;
   const unsigned vb = fp_xcd_block();                    // the reference chunks of one gallery row tile on ONE XCD (gallery rows from its L2)
-  const int chunk = vb % nchunk;
   const long row0 = (long)(vb / nchunk) * XBM + wave * (MT * 16);
-  const int c0 = chunk * NC;
-  const int KS = D / 32;
-  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
 
-  auto stage = [&](int ks) {
-    unsigned char* dst = (unsigned char*)(Bl + (ks & 1) * SLAB);
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-      const unsigned char* src = (const unsigned char*)(R3 + ((long)(ks * 3 + pl) * Npad + c0) * 32) + lane * 16;
-#pragma unroll
-      for (int j = 0; j < NT16 / 4; ++j) {
-        const int c = j * 4 + wave;
-        __builtin_amdgcn_global_load_lds((gbl_ptr)(src + c * 1024), (lds_ptr)(dst + (pl * NC * 32 + c * 512) * 2), 16, 0, 0);
-      }
-    }
-  };
-  const float* arow[MT];
-#pragma unroll
-  for (int t = 0; t < MT; ++t) {
-    long r = row0 + 16 * t + l15;
-    r = r < M ? r : M - 1;
-    arow[t] = G + r * D + 8 * q;
-  }
-  f32x4 araw[MT][2];
-  auto load_a = [&](int ks) {
-#pragma unroll
-    for (int t = 0; t < MT; ++t) {
-      araw[t][0] = *(const f32x4*)(arow[t] + 32 * ks);
-      araw[t][1] = *(const f32x4*)(arow[t] + 32 * ks + 4);
-    }
-  };
-  f32x4 acc[MT][NT16];
-#pragma unroll
-  for (int t = 0; t < MT; ++t)
-#pragma unroll
-    for (int n = 0; n < NT16; ++n) acc[t][n] = z;
-
-  stage(0);
-  load_a(0);
-  for (int ks = 0; ks < KS; ++ks) {
-    fp_frag3 af[MT];
-#pragma unroll
-    for (int t = 0; t < MT; ++t) af[t] = fp_split8(araw[t][0], araw[t][1]);
-    __syncthreads();
-    if (ks + 1 < KS) {
-      stage(ks + 1);
-      load_a(ks + 1);
-    }
-    const unsigned short* Bc = Bl + (ks & 1) * SLAB + (l15 * 32 + 8 * q);
-    fp_frag3 bf[2];
-    auto ldb = [&](int n, fp_frag3& b) {
-      b.h = *(const u32x4*)(Bc + n * 512);
-      b.m = *(const u32x4*)(Bc + NC * 32 + n * 512);
-      b.l = *(const u32x4*)(Bc + 2 * NC * 32 + n * 512);
-    };
-    ldb(0, bf[0]);
+  // one chunk; its epilogue: lane = gallery row 16 t + l15, reference columns c0 + 16 n + 4 q + i
+  cw_walk<MT>(G, M, row0, R3, Npad, D, (int)(vb % nchunk), 1, (unsigned short*)smem_raw, [&](int c0, f32x4 (&acc)[MT][NT16]) {
+    f32x4 rn[NT16];
 #pragma unroll
     for (int n = 0; n < NT16; ++n) {
-      if (n + 1 < NT16) ldb(n + 1, bf[(n + 1) & 1]);
-      const fp_frag3& b = bf[n & 1];
+      const int col = c0 + 16 * n + 4 * q;
+      if (col + 3 < Nr) {
+        rn[n] = *(const f32x4*)(rinv + col);
+      } else {
 #pragma unroll
-      for (int t = 0; t < MT; ++t) acc[t][n] = fp_mfma_x6(b.h, b.m, b.l, af[t].h, af[t].m, af[t].l, acc[t][n]);
+        for (int i = 0; i < 4; ++i) rn[n][i] = col + i < Nr ? rinv[col + i] : 0.f;
+      }
     }
-  }
-
-  // epilogue: lane = gallery row 16 t + l15, reference columns c0 + 16 n + 4 q + i
-  f32x4 rn[NT16];
 #pragma unroll
-  for (int n = 0; n < NT16; ++n) {
-    const int col = c0 + 16 * n + 4 * q;
-    if (col + 3 < Nr) {
-      rn[n] = *(const f32x4*)(rinv + col);
-    } else {
+    for (int t = 0; t < MT; ++t) {
+      const long m = row0 + 16 * t + l15;
+      const float gi = m < M ? ginv[m] : 0.f;
+      float best = -__builtin_huge_valf();
+      int bidx = 0x7FFFFFFF;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) rn[n][i] = col + i < Nr ? rinv[col + i] : 0.f;
-    }
-  }
+      for (int n = 0; n < NT16; ++n)
 #pragma unroll
-  for (int t = 0; t < MT; ++t) {
-    const long m = row0 + 16 * t + l15;
-    const float gi = m < M ? ginv[m] : 0.f;
-    float best = -__builtin_huge_valf();
-    int bidx = 0x7FFFFFFF;
-#pragma unroll
-    for (int n = 0; n < NT16; ++n)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int col = c0 + 16 * n + 4 * q + i;
-        if (col < Nr) {
-          const float sv = acc[t][n][i] * gi * rn[n][i];
-          if (sv > best || (sv == best && col < bidx)) {
-            best = sv;
-            bidx = col;
+        for (int i = 0; i < 4; ++i) {
+          const int col = c0 + 16 * n + 4 * q + i;
+          if (col < Nr) {
+            const float sv = acc[t][n][i] * gi * rn[n][i];
+            if (sv > best || (sv == best && col < bidx)) {
+              best = sv;
+              bidx = col;
+            }
           }
         }
-      }
 #pragma unroll
-    for (int off = 16; off < 64; off <<= 1) {                  // the four k-group lanes of this row
-      const float ob = __shfl_xor(best, off);
-      const int oi = __shfl_xor(bidx, off);
-      if (ob > best || (ob == best && oi < bidx)) {
-        best = ob;
-        bidx = oi;
+      for (int off = 16; off < 64; off <<= 1) {                  // the four k-group lanes of this row
+        const float ob = __shfl_xor(best, off);
+        const int oi = __shfl_xor(bidx, off);
+        if (ob > best || (ob == best && oi < bidx)) {
+          best = ob;
+          bidx = oi;
+        }
       }
+      if (q == 0 && m < M && bidx != 0x7FFFFFFF) atomicMax(&packed[m], cw_key(best, (unsigned)bidx));
     }
-    if (q == 0 && m < M && bidx != 0x7FFFFFFF) {
-      const unsigned long long key = ((unsigned long long)f2ord(best) << 32) | (unsigned int)(0xFFFFFFFFu - (unsigned int)bidx);
-      atomicMax(&packed[m], key);
-    }
-  }
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Top-k search (identify against an enrolled gallery): S = Q G^T with the arithmetic of cosine_x6_kernel (gallery planes
-// from split3_rows_kernel, queries split in registers, fp_mfma_x6, score = acc * qinv[m] * ginv[n]), reduced to the k
+// Top-k search (identify against an enrolled gallery): S = Q G^T on the same walk as cosine_x6_kernel (gallery planes
+// from split3_rows_kernel, queries split in registers, score = acc * qinv[m] * ginv[n]), reduced to the k
 // best columns of every row.  One 64-bit atomicMax cannot carry k candidates, so the grid is (row tile) x (split): a
-// workgroup walks a CONTIGUOUS range of 128-column chunks as one flat, double-buffered pipeline (the next chunk's first
-// slab is staged under the last MFMAs of this one) and keeps a running top-k per row in LDS, as sorted 64-bit keys
-//     key = ord(score) << 32 | ~column        (larger = better: higher score, then LOWER column; 0 = empty slot).
+// workgroup walks a CONTIGUOUS range of 128-column chunks (cw_walk, cosinewalk.h: one flat, double-buffered pipeline) and
+// keeps a running top-k per row in LDS, as sorted 64-bit keys (cw_key: larger = better, higher score, then LOWER column;
+// 0 = empty slot).
 // The keys of all candidates are distinct and totally ordered, so the k largest are one well-defined set: inserting in any
 // order, in any partition of the columns, gives the same list -- the result does not depend on n_splits, on the order in
 // which lanes insert, or on workgroup scheduling.
@@ -305,102 +223,34 @@ __global__ __launch_bounds__(256, 3) void cosine_topk_x6_kernel(const float* __r
                                                                                const float* __restrict__ ginv, int N, int Npad, int D,
                                                                                int k, int n_splits,
                                                                                unsigned long long* __restrict__ partial) {
-  constexpr int NT16 = 8, NC = 128, SLAB = 3 * NC * 32, XBM = 4 * MT * 16;
+  constexpr int NT16 = CW_NT16, XBM = 4 * MT * 16;
   typedef unsigned long long u64;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  unsigned short* Bl = (unsigned short*)smem_raw;        // [2][3][NC][32]
-  volatile u64* Ls = (volatile u64*)(smem_raw + 2 * SLAB * 2);   // [XBM][LS] running top-k keys, descending
+  volatile u64* Ls = (volatile u64*)(smem_raw + CW_LDS);   // behind the staging buffer: [XBM][LS] running top-k keys, descending
   const int LS = k | 1;                                  // odd stride: the rows' k-th entries fall in different banks
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, q = lane >> 4;
-  const int nchunk = Npad / NC;
+  const int nchunk = Npad / CW_NC;
   const unsigned vb = fp_xcd_block();                    // the splits of one row tile on ONE XCD (query rows from its L2)
   const int split = vb % (unsigned)n_splits;
   const long row0 = (long)(vb / (unsigned)n_splits) * XBM + wave * (MT * 16);
-  // chunks [cb, ce) of this split: nchunk = n_splits * base + rem, the first rem splits take one more
+  // chunks [cb, cb + nck) of this split: nchunk = n_splits * base + rem, the first rem splits take one more
   const int base = nchunk / n_splits, rem = nchunk - base * n_splits;
   const int cb = split * base + (split < rem ? split : rem);
   const int nck = base + (split < rem ? 1 : 0);          // >= 1 (the launcher clamps n_splits to nchunk)
-  const int KS = D / 32;
   const f32x4 z = {0.f, 0.f, 0.f, 0.f};
   const float ninf = -__builtin_huge_valf(), qnan = __builtin_nanf("");
 
   for (int i = lane; i < MT * 16 * LS; i += 64) Ls[wave * (MT * 16) * LS + i] = 0;
   u64 lower = 0;                                         // the lanes of my row with a smaller q
   for (int qq = 0; qq < q; ++qq) lower |= 1ull << (l15 + 16 * qq);
+  float thr[MT];                                         // the k-th best score of my rows so far
+#pragma unroll
+  for (int t = 0; t < MT; ++t) thr[t] = ninf;
 
-  auto stage = [&](int chunk, int ks, int buf) {
-    unsigned char* dst = (unsigned char*)(Bl + buf * SLAB);
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-      const unsigned char* src = (const unsigned char*)(G3 + ((long)(ks * 3 + pl) * Npad + (long)chunk * NC) * 32) + lane * 16;
-#pragma unroll
-      for (int j = 0; j < NT16 / 4; ++j) {
-        const int c = j * 4 + wave;
-        __builtin_amdgcn_global_load_lds((gbl_ptr)(src + c * 1024), (lds_ptr)(dst + (pl * NC * 32 + c * 512) * 2), 16, 0, 0);
-      }
-    }
-  };
-  const float* Qw = Q + fp_uniform(row0 * D);             // this wave's rows; row0 < M
-  int arow[MT];                                          // 32-bit offsets: at most 64 rows x D floats
-  float thr[MT];
-#pragma unroll
-  for (int t = 0; t < MT; ++t) {
-    long r = row0 + 16 * t + l15;
-    r = r < M ? r : M - 1;
-    arow[t] = (int)(r - row0) * D + 8 * q;
-    thr[t] = ninf;
-  }
-  f32x4 araw[MT][2];
-  auto load_a = [&](int ks) {
-#pragma unroll
-    for (int t = 0; t < MT; ++t) {
-      araw[t][0] = *(const f32x4*)(Qw + arow[t] + 32 * ks);
-      araw[t][1] = *(const f32x4*)(Qw + arow[t] + 32 * ks + 4);
-    }
-  };
-  f32x4 acc[MT][NT16];
-#pragma unroll
-  for (int t = 0; t < MT; ++t)
-#pragma unroll
-    for (int n = 0; n < NT16; ++n) acc[t][n] = z;
-
-  const int steps = nck * KS;
-  int ks = 0, chunk = cb;                                // of the step being computed
-  stage(cb, 0, 0);
-  load_a(0);
-  for (int s = 0; s < steps; ++s) {
-    fp_frag3 af[MT];
-#pragma unroll
-    for (int t = 0; t < MT; ++t) af[t] = fp_split8(araw[t][0], araw[t][1]);
-    __syncthreads();
-    if (s + 1 < steps) {
-      const bool last = ks + 1 == KS;
-      stage(last ? chunk + 1 : chunk, last ? 0 : ks + 1, (s + 1) & 1);
-      load_a(last ? 0 : ks + 1);
-    }
-    const unsigned short* Bc = Bl + (s & 1) * SLAB + (l15 * 32 + 8 * q);
-    fp_frag3 bf[2];
-    auto ldb = [&](int n, fp_frag3& b) {
-      b.h = *(const u32x4*)(Bc + n * 512);
-      b.m = *(const u32x4*)(Bc + NC * 32 + n * 512);
-      b.l = *(const u32x4*)(Bc + 2 * NC * 32 + n * 512);
-    };
-    ldb(0, bf[0]);
-#pragma unroll
-    for (int n = 0; n < NT16; ++n) {
-      if (n + 1 < NT16) ldb(n + 1, bf[(n + 1) & 1]);
-      const fp_frag3& b = bf[n & 1];
-#pragma unroll
-      for (int t = 0; t < MT; ++t) acc[t][n] = fp_mfma_x6(b.h, b.m, b.l, af[t].h, af[t].m, af[t].l, acc[t][n]);
-    }
-    if (++ks < KS) continue;
-    ks = 0;
-
-    // epilogue of a chunk: lane = query row 16 t + l15, gallery columns c0 + 16 n + 4 q + i
-    const int c0 = chunk * NC;
-    ++chunk;
+  // epilogue of a chunk: lane = query row 16 t + l15, gallery columns c0 + 16 n + 4 q + i
+  cw_walk<MT>(Q, M, row0, G3, Npad, D, cb, nck, (unsigned short*)smem_raw, [&](int c0, f32x4 (&acc)[MT][NT16]) {
     float gi[MT];
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
@@ -418,7 +268,7 @@ __global__ __launch_bounds__(256, 3) void cosine_topk_x6_kernel(const float* __r
         for (int i = 0; i < 4; ++i) rn[i] = colb + i < N ? ginv[colb + i] : 0.f;
       }
 #pragma unroll
-      for (int i = 0; i < 4; ++i) rn[i] = rn[i] == 0.f ? qnan : rn[i];      // masked / padding: never a candidate
+      for (int i = 0; i < 4; ++i) rn[i] = cw_nan_if_zero(rn[i]);            // masked / padding: never a candidate
 #pragma unroll
       for (int t = 0; t < MT; ++t) {
         volatile u64* Lr = Ls + (wave * (MT * 16) + 16 * t + l15) * LS;
@@ -433,7 +283,7 @@ __global__ __launch_bounds__(256, 3) void cosine_topk_x6_kernel(const float* __r
         for (int i = 0; i < 4; ++i) {
           const float v = i == 0 ? sv[0] : i == 1 ? sv[1] : i == 2 ? sv[2] : sv[3];
           bool pend = v >= thr[t];
-          const u64 key = ((u64)f2ord(v) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)(colb + i));
+          const u64 key = cw_key(v, (unsigned)(colb + i));
           for (;;) {
             const u64 mask = __ballot(pend);
             if (!mask) break;
@@ -454,15 +304,15 @@ __global__ __launch_bounds__(256, 3) void cosine_topk_x6_kernel(const float* __r
           }
         }
         const u64 kth = Lr[k - 1];
-        thr[t] = kth ? ord2f((unsigned)(kth >> 32)) : ninf;
+        thr[t] = kth ? cw_key_score(kth) : ninf;
       }
     }
 #pragma unroll
     for (int t = 0; t < MT; ++t) {                         // other lanes of the row may have raised it
       const u64 kth = Ls[(wave * (MT * 16) + 16 * t + l15) * LS + k - 1];
-      thr[t] = kth ? ord2f((unsigned)(kth >> 32)) : ninf;
+      thr[t] = kth ? cw_key_score(kth) : ninf;
     }
-  }
+  });
 
   // the lists of this wave's rows -> partial[m][split][0 .. k)
   __builtin_amdgcn_wave_barrier();
@@ -490,8 +340,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const unsigned long lon
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
-      const unsigned lo = __shfl_xor((unsigned)best, off), hi = __shfl_xor((unsigned)(best >> 32), off);
-      const u64 o = ((u64)hi << 32) | lo;
+      const u64 o = __shfl_xor(best, off);
       best = o > best ? o : best;
     }
     if (lane == j) mine = best;
@@ -499,8 +348,8 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const unsigned long lon
     if (best == 0) break;
   }
   if (lane < k) {
-    scores[m * k + lane] = mine ? ord2f((unsigned)(mine >> 32)) : -__builtin_huge_valf();
-    idx[m * k + lane] = mine ? (int)(0xFFFFFFFFu - (unsigned)(mine & 0xFFFFFFFFull)) : -1;
+    scores[m * k + lane] = mine ? cw_key_score(mine) : -__builtin_huge_valf();
+    idx[m * k + lane] = mine ? cw_key_index(mine) : -1;
   }
 }
 
@@ -543,10 +392,9 @@ __global__ __launch_bounds__(256) void cosine_finalize_kernel(const unsigned lon
   const long m = (long)blockIdx.x * 256 + threadIdx.x;
   if (m >= M) return;
   const unsigned long long key = packed[m];
-  const float s = ord2f((unsigned int)(key >> 32));
-  const int j = (int)(0xFFFFFFFFu - (unsigned int)(key & 0xFFFFFFFFull));
+  const float s = cw_key_score(key);
   best[m] = s;
-  arg[m] = j;
+  arg[m] = cw_key_index(key);
   keep[m] = s >= tau ? 1 : 0;
 }
 
@@ -649,12 +497,12 @@ int fp_cosine_filter(const float* G, const float* ginv, int64_t M, const float* 
 }
 
 
-size_t fp_split3_bytes(int Nr, int D) { return (size_t)(D / 32) * 3 * (size_t)fp_round_up(Nr, 128) * 32 * 2; }
+size_t fp_split3_bytes(int Nr, int D) { return (size_t)(D / 32) * 3 * (size_t)fp_round_up(Nr, CW_NC) * 32 * 2; }
 
 int fp_split3_rows(const float* R, int Nr, int D, void* out, void* stream) {
   if (!R || !out || Nr <= 0 || D <= 0) return FP_ERR_INVALID_ARG;
   if (D % 32 || ((uintptr_t)R) % 16 || ((uintptr_t)out) % 16) return FP_ERR_ALIGNMENT;
-  const int Npad = (int)fp_round_up(Nr, 128);
+  const int Npad = (int)fp_round_up(Nr, CW_NC);
   const long items = (long)Npad * (D / 8);
   hipLaunchKernelGGL(split3_rows_kernel, dim3((unsigned)fp_ceil_div(items, 256)), dim3(256), 0, (hipStream_t)stream, R, Nr, D, Npad,
                      (unsigned short*)out);
@@ -673,18 +521,17 @@ int fp_cosine_filter_x6(const float* G, const float* ginv, int64_t M, const void
     fp_set_hip_error(hipGetLastError());
     return FP_ERR_LAUNCH;
   }
-  const int Npad = (int)fp_round_up(Nr, 128);
-  const long nchunk = Npad / 128;
-  constexpr int lds = 2 * 3 * 128 * 32 * 2;
+  const int Npad = (int)fp_round_up(Nr, CW_NC);
+  const long nchunk = Npad / CW_NC;
   // 256-row tiles (two workgroups per CU) when they fill several rounds of workgroups, else 128-row tiles (three per CU)
   const long big = (M + 255) / 256 * nchunk;
   if (big >= 2048) {
     if (big >= (1L << 31)) return FP_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((cosine_x6_kernel<4>), dim3((unsigned)big), dim3(256), lds, s, G, ginv, (long)M, (const unsigned short*)R3, rinv,
+    hipLaunchKernelGGL((cosine_x6_kernel<4>), dim3((unsigned)big), dim3(256), CW_LDS, s, G, ginv, (long)M, (const unsigned short*)R3, rinv,
                        Nr, Npad, D, (unsigned long long*)packed);
   } else {
     const long tiles = (M + 127) / 128 * nchunk;
-    hipLaunchKernelGGL((cosine_x6_kernel<2>), dim3((unsigned)tiles), dim3(256), lds, s, G, ginv, (long)M, (const unsigned short*)R3, rinv,
+    hipLaunchKernelGGL((cosine_x6_kernel<2>), dim3((unsigned)tiles), dim3(256), CW_LDS, s, G, ginv, (long)M, (const unsigned short*)R3, rinv,
                        Nr, Npad, D, (unsigned long long*)packed);
   }
   FP_CHECK_LAUNCH();
@@ -697,16 +544,6 @@ int fp_cosine_filter_x6(const float* G, const float* ginv, int64_t M, const void
 }  // extern "C"
 
 namespace {
-constexpr int TOPK_NC = 128, TOPK_LDS_B = 2 * 3 * 128 * 32 * 2;
-int topk_num_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus = n;
-  }
-  return cus;
-}
 // 128-row tiles (MT = 2).  The 256-row form of cosine_x6_kernel does not fit here: the flat chunk loop and the rows' thresholds
 // on top of its 250 registers spill (checked with tools/kernel_resources.py), and a spill is worse than the smaller tile.
 constexpr int TOPK_ROWS = 128;
@@ -729,12 +566,12 @@ extern "C" {
 
 size_t fp_cosine_topk_workspace(int64_t M, int N, int k, int n_splits) {
   if (M <= 0 || N <= 0 || k < 1 || k > FP_TOPK_MAX || n_splits < 0) return 0;
-  const size_t nchunk = (size_t)(fp_round_up(N, TOPK_NC) / TOPK_NC);
+  const size_t nchunk = (size_t)(fp_round_up(N, CW_NC) / CW_NC);
   if (n_splits) return (size_t)M * (nchunk < (size_t)n_splits ? nchunk : (size_t)n_splits) * (size_t)k * sizeof(uint64_t);
   // automatic: a bound on M * n_splits that grows with M and k whatever the choice rounds to -- tiles * n_splits is at most
   // (workgroups wanted at the smallest k) + tiles, and never above tiles * nchunk
   const size_t tiles = (size_t)((M + TOPK_ROWS - 1) / TOPK_ROWS);
-  const size_t want = (size_t)TOPK_ROUNDS * 3 * topk_num_cus() + tiles;
+  const size_t want = (size_t)TOPK_ROUNDS * 3 * fp_num_cus() + tiles;
   const size_t lists = tiles * nchunk < want ? tiles * nchunk : want;
   return lists * TOPK_ROWS * (size_t)k * sizeof(uint64_t);
 }
@@ -748,18 +585,18 @@ int fp_cosine_topk_x6(const float* Q, const float* qinv, int64_t M, const void* 
   if (M == 0) return FP_OK;
   if (ws_bytes < fp_cosine_topk_workspace(M, N, k, n_splits)) return FP_ERR_INVALID_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int Npad = (int)fp_round_up(N, TOPK_NC);
-  const int nchunk = Npad / TOPK_NC;
-  const int cus = topk_num_cus();
+  const int Npad = (int)fp_round_up(N, CW_NC);
+  const int nchunk = Npad / CW_NC;
+  const int cus = fp_num_cus();
   int ns = n_splits ? n_splits : topk_auto_splits(M, k, cus);
   ns = ns > nchunk ? nchunk : ns;
   const int rows = TOPK_ROWS;
   const long blocks = (M + rows - 1) / rows * ns;
   if (blocks >= (1L << 31)) return FP_ERR_UNSUPPORTED;
-  const int lds = TOPK_LDS_B + rows * (k | 1) * 8;        // B slabs + the rows' key lists: 53 KiB at k = 5 (three per CU), 65 KiB at 16 (two)
+  const int lds = CW_LDS + rows * (k | 1) * 8;        // B slabs + the rows' key lists: 53 KiB at k = 5 (three per CU), 65 KiB at 16 (two)
   static bool attr_set = false;                          // dynamic LDS above 64 KiB (k > 14) needs the attribute
   if (!attr_set) {
-    const int mx = TOPK_LDS_B + TOPK_ROWS * (FP_TOPK_MAX | 1) * 8;
+    const int mx = CW_LDS + TOPK_ROWS * (FP_TOPK_MAX | 1) * 8;
     if (hipFuncSetAttribute((const void*)cosine_topk_x6_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess) {
       fp_set_hip_error(hipGetLastError());
       return FP_ERR_LAUNCH;

@@ -1,9 +1,9 @@
 // triwalk.h — the triangular work list of the all-pairs walks over the upper triangle of X X^T (cluster.hip, pairhist.hip):
 // row tiles of 128 rows x 128-column chunks, a chunk is walked when it is not wholly at or below its row tile's first row.
 #pragma once
-#include "common.h"
+#include "cosinewalk.h"
 
-constexpr int CL_NC = 128, CL_ROWS = 128, CL_LDS = 2 * 3 * CL_NC * 32 * 2;   // chunk columns, tile rows, the staging buffer
+constexpr int CL_ROWS = CW_NC;   // rows of a row tile = columns of a chunk: tile r starts on the diagonal at chunk r
 
 // Row tile r walks the m = nchunk - r chunks r .. nchunk - 1, cut into ceil(m / P) workgroups of nearly equal, contiguous
 // chunk ranges (at most P each).  Items are numbered by increasing m: tile m = P b + e + 1 (0 <= e < P) has b + 1 groups and
@@ -30,19 +30,9 @@ __host__ __device__ inline cl_item cl_decode(long v, int nchunk, int P) {
   return it;
 }
 
-static inline int cl_num_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus = n;
-  }
-  return cus;
-}
-
 // Chunks per workgroup: about four rounds of the workgroups the device holds (wg_per_cu per CU), at most 16 chunks each.
 static inline long cl_chunks_per_group(int nchunk, int wg_per_cu) {
   const long total = (long)nchunk * (nchunk + 1) / 2;
-  const long P = total / (4L * wg_per_cu * cl_num_cus());
+  const long P = total / (4L * wg_per_cu * fp_num_cus());
   return P < 1 ? 1 : P > 16 ? 16 : P;
 }

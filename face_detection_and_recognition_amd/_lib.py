@@ -120,6 +120,16 @@ MERGE_CAP = 2048                                                           # FP_
 QUALITY_MAX_STEP = 64                                                     # FP_QUALITY_MAX_STEP
 QUALITY_EMPTY, QUALITY_BAD_FRAME, QUALITY_NO_LAPLACIAN, QUALITY_TOO_LARGE, QUALITY_POSE_DEGENERATE = 1, 2, 4, 8, 16   # FP_QUALITY_*
 
+TRACK_SLOTS, TRACK_MAX_DETS, TRACK_MAX_DIM, TRACK_MAX_ROWS = 64, 64, 1024, 1 << 30                     # FP_TRACK_*
+TRACK_SLOT_INTS, TRACK_SLOT_FLOATS = 5, 10                                # columns of fp_track_state.slot_i / slot_f
+TRACK_NEW, TRACK_BEST, TRACK_DEAD_ROW, TRACK_FULL, TRACK_NO_STREAM, TRACK_OVER = 1, 2, 4, 8, 16, 32   # track_flags bits
+
+
+class FpTrackState(C.Structure):
+    """Mirror of struct fp_track_state: the five state arrays of fp_tracklets_step (include/facepath.h "Tracklets")."""
+    _fields_ = [("hdr", C.c_void_p), ("slot_i", C.c_void_p), ("slot_f", C.c_void_p), ("emb", C.c_void_p), ("best_emb", C.c_void_p)]
+
+
 JPEG_DECODE_ON_HOST = 1          # fp_jpeg_entropy_decode_device status: decode this image with fp_jpeg_entropy_decode
 JPEG_444, JPEG_422, JPEG_420 = 0, 1, 2   # fp_jpeg_encode_* subsampling (Pillow's numbering)
 JPEG_ENC_BYTES_PER_BLOCK = 416   # worst-case scan bytes of one 8 x 8 block, stuffing included
@@ -226,6 +236,9 @@ SIGNATURES = {
     "fp_merge_views": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _F, _I, _P, _P, _P, _P]),
     "fp_merge_views_emulate": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _F, _I, _P, _P, _P]),
     "fp_gather_tiles": (_I, [_P, _SZ, _P, _I, _P, _I, _I, _I, _P, _P]),
+    "fp_tracklets_step": (_I, [C.POINTER(FpTrackState), _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P]),
+    "fp_tracklets_step_emulate": (_I, [C.POINTER(FpTrackState), _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _F, _F, _F, _P, _P, _P,
+                                       _P]),
 }
 
 _lib = None

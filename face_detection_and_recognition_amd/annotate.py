@@ -316,7 +316,8 @@ def face_draw_list(info, n, sizes, lmarks=None, labels=None, areas=True, colors=
 
 def step_labels(result, names=None):
     """One caption suffix per face of a FacePipeline.step result, or None when it carries nothing to say: the gallery name of
-    `identity` (names[identity], a dict or a sequence; nothing for -1) and the arg-max gender / age classes."""
+    `identity` (names[identity], a dict or a sequence; nothing for -1), the arg-max gender / age classes and, for a step with a
+    tracker, " #<track_id>" (nothing for id 0)."""
     n = result["n_faces"]
     parts = [""] * n
     said = False
@@ -332,6 +333,11 @@ def step_labels(result, names=None):
         for i in range(n):
             if not (np.isnan(age[i]).any() or np.isnan(gender[i]).any()):
                 parts[i] += f" {GENDER_LIST[int(gender[i].argmax())]}{AGE_LIST[int(age[i].argmax())]}"
+    if "track_id" in result:
+        said = True
+        for i, k in enumerate(result["track_id"][:n].tolist()):
+            if k > 0:
+                parts[i] += f" #{k}"
     return parts if said else None
 
 

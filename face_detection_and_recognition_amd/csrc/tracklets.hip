@@ -1,0 +1,525 @@
+// tracklets.hip — batched face tracking across the frames of many streams (gfx950).  Build-defined, no reference counterpart
+// (DESIGN §7 "Tracklets"; include/facepath.h states the procedure; tracker.hip stays the port of the reference's per-frame
+// first-match rule).  Build with -ffp-contract=off: the IoU gate and the cosine are the same bits on device and host emulator.
+//
+// 1. fp_tracklets_step: ONE launch, one workgroup per stream; a workgroup whose stream owns no frame of the step leaves after
+//    the first pass.  That pass reads frame[] once: the min / max frame index of every chunk of rows goes to LDS (so a frame's
+//    rows are later looked for only in the chunks that can hold them: one or two when the rows come in frame order, all of
+//    them at worst), and the rows nobody tracks get their NO_STREAM outputs from the workgroup that owns their chunk.  Then
+//    the workgroup marches over its frames in ascending batch index with the stream's slot table in LDS:
+//      expiry -> the frame's rows by ballot compaction in row order -> live tracks x live detections, one pair per 16 lanes
+//      (float4 loads, xor-shuffle sum) -> 64-bit keys in LDS (~ord(c) << 32 | slot << 8 | position: ascending = c descending,
+//      lower slot, lower row) -> bitonic sort -> wave 0 walks the keys 64 at a time with a ballot per taken pair (two 64-bit
+//      masks: tracks and detections already taken) -> the unmatched detections open tracks in the lowest free slots by rank
+//      -> slot fields in LDS, embeddings copied in global memory by the whole workgroup.
+//    No global atomics, no scratch, no host synchronisation: two runs are bit-identical.
+// 2. fp_tracklets_step_emulate: the same __host__ __device__ decision code (liveness, dot product in the device's order, IoU,
+//    admissibility, key) run serially on host memory, std::sort for the keys (the order is total).
+#include <limits.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "common.h"
+
+namespace {
+
+constexpr int SLOTS = FP_TRACK_SLOTS, MAXD = FP_TRACK_MAX_DETS;
+constexpr int TPB = 512, NW = TPB / FP_WAVE;
+constexpr int GL = 16, NG = TPB / GL;   // lanes per pair, pairs in flight
+constexpr int MAXCH = 1024;             // row chunks whose frame range is kept in LDS
+constexpr int NI = FP_TRACK_SLOT_INTS, NF = FP_TRACK_SLOT_FLOATS;
+constexpr unsigned long long KEY_NONE = ~0ull;
+static_assert(SLOTS == 64 && MAXD == 64, "one 64-bit mask of tracks and one of detections; slot and position are key bytes");
+
+// slot_i columns / slot_f columns
+enum { I_ID = 0, I_FIRST = 1, I_LAST = 2, I_HITS = 3, I_BEST_CLOCK = 4 };
+enum { F_BOX = 0, F_INV = 4, F_BEST_SCORE = 5, F_BEST_BOX = 6 };
+
+struct TrackArgs {
+  int* hdr;      // [S][2] clock, next_id
+  int* si;       // [S][SLOTS][NI]
+  float* sf;     // [S][SLOTS][NF]
+  float* semb;   // [S][SLOTS][D]
+  float* sbest;  // [S][SLOTS][D]
+  int S, D;
+  const int* frame;
+  const float* box;
+  const float* emb;
+  const float* xinv;
+  const float* score;   // may be null
+  int n;
+  const int* sof;
+  int B;
+  int max_age;
+  float tau_near, tau_far, iou_min;
+  int* o_id;
+  int* o_hits;
+  int* o_clock;
+  int* o_flags;
+};
+
+// ---------------------------------------------------------------------------------------- the decision code, host and device
+__host__ __device__ __forceinline__ bool tk_live(float inv) { return inv > 0.f && inv - inv == 0.f; }
+
+__host__ __device__ __forceinline__ bool tk_untracked(const TrackArgs& p, int f) {
+  if (f < 0 || f >= p.B) return true;
+  const int s = p.sof[f];
+  return s < 0 || s >= p.S;
+}
+
+// lane gl of 16: the products of float4 gl, gl + 16, ... added in index order
+__host__ __device__ __forceinline__ float tk_partial(const float* t, const float* d, int D, int gl) {
+  float acc = 0.f;
+  for (int k = gl * 4; k < D; k += GL * 4) {
+    acc += t[k] * d[k];
+    acc += t[k + 1] * d[k + 1];
+    acc += t[k + 2] * d[k + 2];
+    acc += t[k + 3] * d[k + 3];
+  }
+  return acc;
+}
+
+__host__ __device__ __forceinline__ float tk_cos(float dot, float inv_t, float inv_d) { return (dot * inv_t) * inv_d; }
+
+// t: the track's last box, d: the detection's; min(a, b) = a < b ? a : b and max(a, b) = a > b ? a : b with a the track's value
+__host__ __device__ __forceinline__ float tk_iou(const float* t, const float* d) {
+  const float ix1 = t[0] > d[0] ? t[0] : d[0], iy1 = t[1] > d[1] ? t[1] : d[1];
+  const float ix2 = t[2] < d[2] ? t[2] : d[2], iy2 = t[3] < d[3] ? t[3] : d[3];
+  const float iw = ix2 - ix1, ih = iy2 - iy1;
+  if (!(iw > 0.f && ih > 0.f)) return 0.f;
+  const float inter = iw * ih;
+  const float area_t = (t[2] - t[0]) * (t[3] - t[1]), area_d = (d[2] - d[0]) * (d[3] - d[1]);
+  return inter / ((area_t + area_d) - inter);
+}
+
+__host__ __device__ __forceinline__ bool tk_admissible(const TrackArgs& p, float c, float iou) {
+  return (c > p.tau_near && iou > p.iou_min) || c > p.tau_far;
+}
+
+// ascending keys = c descending (-0 counts as +0), then slot ascending, then position in the frame ascending
+__host__ __device__ __forceinline__ unsigned long long tk_key(float c, int slot, int pos) {
+  if (c == 0.f) c = 0.f;
+  unsigned u;
+  __builtin_memcpy(&u, &c, 4);
+  const unsigned ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)(~ord) << 32) | (unsigned)(slot << 8 | pos);
+}
+__host__ __device__ __forceinline__ int tk_key_slot(unsigned long long k) { return (int)((unsigned)k >> 8) & 0xFF; }
+__host__ __device__ __forceinline__ int tk_key_pos(unsigned long long k) { return (int)((unsigned)k & 0xFF); }
+
+__host__ __device__ __forceinline__ void tk_out(const TrackArgs& p, long row, int id, int hits, int clock, int flags) {
+  p.o_id[row] = id;
+  p.o_hits[row] = hits;
+  p.o_clock[row] = clock;
+  p.o_flags[row] = flags;
+}
+
+// rows of one chunk; TPB * MAXCH chunks of TPB rows cover 2^19 rows, more rows make the chunks longer
+__host__ __device__ __forceinline__ int tk_chunk_rows(int n) { return TPB * (int)(((long)n + (long)TPB * MAXCH - 1) / ((long)TPB * MAXCH)); }
+
+// A matched (is_new false) or opened detection rewrites its slot: ints and floats of the slot table (LDS on the device).
+// Returns the row's flags.
+__host__ __device__ __forceinline__ int tk_update_slot(const TrackArgs& p, int* si, float* sf, long row, float inv, bool is_new,
+                                                       int clock, int new_id) {
+  const float* b = p.box + row * 4;
+  const float sc = p.score ? p.score[row] : 0.f;
+  if (is_new) {
+    si[I_ID] = new_id;
+    si[I_FIRST] = clock;
+    si[I_HITS] = 1;
+  } else {
+    si[I_HITS] += 1;
+  }
+  si[I_LAST] = clock;
+  for (int k = 0; k < 4; ++k) sf[F_BOX + k] = b[k];
+  sf[F_INV] = inv;
+  int flags = is_new ? FP_TRACK_NEW : 0;
+  if (is_new || sc > sf[F_BEST_SCORE]) {
+    sf[F_BEST_SCORE] = sc;
+    si[I_BEST_CLOCK] = clock;
+    for (int k = 0; k < 4; ++k) sf[F_BEST_BOX + k] = b[k];
+    flags |= FP_TRACK_BEST;
+  }
+  return flags;
+}
+
+// ------------------------------------------------------------------------------------------------------------ the kernel
+__global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
+  __shared__ unsigned long long key[SLOTS * MAXD];   // 32 KB
+  __shared__ int cmin[MAXCH], cmax[MAXCH];
+  __shared__ int s_i[SLOTS][NI];
+  __shared__ float s_f[SLOTS][NF];
+  __shared__ int det_row[MAXD], det_slot[MAXD], det_flag[MAXD];
+  __shared__ float det_inv[MAXD];                    // 0 = a dead row
+  __shared__ int lt[SLOTS], ld[MAXD];                // the live slots / the positions of the live detections, ascending
+  __shared__ int wcount[NW];
+  __shared__ unsigned long long fmask[NW];
+  __shared__ int s_nT, s_nD;
+
+  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int D = p.D, D4 = D >> 2, n = p.n;
+  const int CH = tk_chunk_rows(n), nch = n > 0 ? (n + CH - 1) / CH : 0;
+  const unsigned long long lane_lt = (1ull << lane) - 1ull;
+
+  for (int c = tid; c < nch; c += TPB) {
+    cmin[c] = INT_MAX;
+    cmax[c] = INT_MIN;
+  }
+  for (int i = tid; i < SLOTS * NI; i += TPB) (&s_i[0][0])[i] = p.si[(long)s * SLOTS * NI + i];
+  for (int i = tid; i < SLOTS * NF; i += TPB) (&s_f[0][0])[i] = p.sf[(long)s * SLOTS * NF + i];
+  __syncthreads();
+
+  // first pass over the rows: frame range of every chunk; the untracked rows of the groups this workgroup owns
+  for (int g0 = 0; g0 < n; g0 += TPB) {
+    const int i = g0 + tid;
+    if (i < n) {
+      const int f = p.frame[i], c = i / CH;
+      atomicMin(&cmin[c], f);
+      atomicMax(&cmax[c], f);
+      if ((unsigned)(g0 / TPB) % gridDim.x == (unsigned)s && tk_untracked(p, f)) tk_out(p, i, 0, 0, 0, FP_TRACK_NO_STREAM);
+    }
+  }
+  __syncthreads();
+
+  int clock = p.hdr[2 * s], next_id = p.hdr[2 * s + 1];   // next_id is kept by wave 0
+  float* semb = p.semb + (long)s * SLOTS * D;
+  float* sbest = p.sbest + (long)s * SLOTS * D;
+
+  for (int f0 = 0; f0 < p.B; f0 += TPB) {
+    const bool mine = f0 + tid < p.B && p.sof[f0 + tid] == s;
+    const unsigned long long mb = __ballot(mine);
+    if (lane == 0) fmask[wave] = mb;
+    __syncthreads();
+    for (int w = 0; w < NW; ++w) {
+      unsigned long long mm = fmask[w];
+      while (mm) {
+        const int f = f0 + w * 64 + (__ffsll((long long)mm) - 1);
+        mm &= mm - 1ull;
+
+        // ---- 1. the clock, expiry
+        clock += 1;
+        if (tid < SLOTS && s_i[tid][I_ID] != 0 && clock - s_i[tid][I_LAST] > p.max_age) s_i[tid][I_ID] = 0;
+
+        // ---- 2. the frame's rows in row order: the first MAXD take part
+        int base = 0;
+        for (int c = 0; c < nch; ++c) {
+          if (f < cmin[c] || f > cmax[c]) continue;
+          const int g_end = min(c * CH + CH, n);   // n <= FP_TRACK_MAX_ROWS: no index here passes 2^31
+          for (int g0 = c * CH; g0 < g_end; g0 += TPB) {
+            const int i = g0 + tid;
+            const bool pred = i < g_end && p.frame[i] == f;
+            const unsigned long long bm = __ballot(pred);
+            if (lane == 0) wcount[wave] = __popcll(bm);
+            __syncthreads();
+            int before = 0, total = 0;
+            for (int v = 0; v < NW; ++v) {
+              const int cv = wcount[v];
+              before += v < wave ? cv : 0;
+              total += cv;
+            }
+            if (pred) {
+              const int pos = base + before + __popcll(bm & lane_lt);
+              if (pos < MAXD) {
+                const float inv = p.xinv[i];
+                det_row[pos] = i;
+                det_inv[pos] = tk_live(inv) ? inv : 0.f;
+              } else {
+                tk_out(p, i, 0, 0, clock, FP_TRACK_OVER);
+              }
+            }
+            base += total;
+            __syncthreads();
+          }
+        }
+        const int nd = min(base, MAXD);
+        __syncthreads();
+        if (nd == 0) continue;
+
+        // ---- live slots and live detections, ascending
+        if (wave == 0) {
+          const bool tl = s_i[lane][I_ID] != 0;
+          const unsigned long long tm = __ballot(tl);
+          if (tl) lt[__popcll(tm & lane_lt)] = lane;
+          if (lane == 0) s_nT = __popcll(tm);
+        } else if (wave == 1) {
+          const bool dl = lane < nd && det_inv[lane] > 0.f;
+          const unsigned long long dm = __ballot(dl);
+          if (dl) ld[__popcll(dm & lane_lt)] = lane;
+          if (lane == 0) s_nD = __popcll(dm);
+          det_slot[lane] = -1;
+          det_flag[lane] = 0;
+        }
+        __syncthreads();
+        const int nT = s_nT, nD = s_nD, np = nT * nD;
+
+        // ---- 3. the pairs: cosine, IoU, key
+        int n_valid = 0;
+        if (np > 0) {
+          int n_sort = 2;
+          while (n_sort < np) n_sort <<= 1;
+          const int grp = tid / GL, gl = tid % GL;
+          for (int q0 = 0; q0 < np; q0 += NG) {
+            const int q = min(q0 + grp, np - 1);
+            const int slot = lt[q / nD], pos = ld[q % nD];
+            const long row = det_row[pos];
+            float v = tk_partial(semb + (long)slot * D, p.emb + row * D, D, gl);
+            v += __shfl_xor(v, 8);
+            v += __shfl_xor(v, 4);
+            v += __shfl_xor(v, 2);
+            v += __shfl_xor(v, 1);
+            if (gl == 0 && q0 + grp < np) {
+              const float c = tk_cos(v, s_f[slot][F_INV], det_inv[pos]);
+              const float iou = tk_iou(&s_f[slot][F_BOX], p.box + row * 4);
+              key[q] = tk_admissible(p, c, iou) ? tk_key(c, slot, pos) : KEY_NONE;
+            }
+          }
+          for (int i = np + tid; i < n_sort; i += TPB) key[i] = KEY_NONE;
+          __syncthreads();
+
+          for (int k = 2; k <= n_sort; k <<= 1)
+            for (int j = k >> 1; j > 0; j >>= 1) {
+              for (int t = tid; t < (n_sort >> 1); t += TPB) {
+                const int i = 2 * t - (t & (j - 1)), r = i + j;
+                const unsigned long long a = key[i], b = key[r];
+                if ((a > b) == ((i & k) == 0)) {
+                  key[i] = b;
+                  key[r] = a;
+                }
+              }
+              __syncthreads();
+            }
+          for (int step = n_sort; step > 0; step >>= 1)   // the keys in front of the first KEY_NONE
+            if (n_valid + step <= n_sort && key[n_valid + step - 1] != KEY_NONE) n_valid += step;
+        }
+
+        // ---- 3 (walk), 4, 5: wave 0; lane j stands for the detection at position j
+        if (wave == 0) {
+          int my_slot = -1;
+          unsigned long long t_taken = 0ull, d_taken = 0ull;
+          const int most = min(nT, nD);
+          int taken = 0;
+          for (int i0 = 0; i0 < n_valid && taken < most; i0 += FP_WAVE) {
+            const int i = i0 + lane;
+            const bool have = i < n_valid;
+            const unsigned long long kk = have ? key[i] : 0ull;
+            const int k_slot = tk_key_slot(kk), k_pos = tk_key_pos(kk);
+            bool alive = have && !((t_taken >> k_slot) & 1ull) && !((d_taken >> k_pos) & 1ull);
+            unsigned long long live = __ballot(alive);
+            while (live) {
+              const int l = __ffsll((long long)live) - 1;   // the first pair of the batch still free is taken
+              const int w_slot = __shfl(k_slot, l), w_pos = __shfl(k_pos, l);
+              t_taken |= 1ull << w_slot;
+              d_taken |= 1ull << w_pos;
+              ++taken;
+              if (lane == w_pos) my_slot = w_slot;
+              if (alive && (k_slot == w_slot || k_pos == w_pos)) alive = false;
+              live = __ballot(alive);
+            }
+          }
+          // the unmatched live detections open tracks in the lowest free slots, in row order
+          const bool dl = lane < nd && det_inv[lane] > 0.f;
+          const bool matched = my_slot >= 0;
+          const unsigned long long freem = __ballot(s_i[lane][I_ID] == 0);
+          const bool need = dl && !matched;
+          const unsigned long long needm = __ballot(need);
+          const int n_free = __popcll(freem);
+          int flags = 0, new_id = 0;
+          if (need) {
+            const int rank = __popcll(needm & lane_lt);
+            if (rank < n_free) {
+              unsigned long long fm = freem;
+              for (int r = 0; r < rank; ++r) fm &= fm - 1ull;
+              my_slot = __ffsll((long long)fm) - 1;
+              new_id = next_id + rank;
+            } else {
+              flags = FP_TRACK_FULL;
+            }
+          }
+          next_id += min(__popcll(needm), n_free);
+          if (lane < nd) {
+            const long row = det_row[lane];
+            if (!dl) {
+              tk_out(p, row, 0, 0, clock, FP_TRACK_DEAD_ROW);
+            } else if (my_slot < 0) {
+              tk_out(p, row, 0, 0, clock, flags);
+            } else {
+              flags = tk_update_slot(p, s_i[my_slot], s_f[my_slot], row, det_inv[lane], !matched, clock, new_id);
+              tk_out(p, row, s_i[my_slot][I_ID], s_i[my_slot][I_HITS], clock, flags);
+              det_slot[lane] = my_slot;
+              det_flag[lane] = flags;
+            }
+          }
+        }
+        __syncthreads();
+
+        // ---- the embeddings of the rewritten slots
+        for (int idx = tid; idx < nD * D4; idx += TPB) {
+          const int pos = ld[idx / D4], k = idx % D4, slot = det_slot[pos];
+          if (slot < 0) continue;
+          const f32x4 v = ((const f32x4*)(p.emb + (long)det_row[pos] * D))[k];
+          ((f32x4*)(semb + (long)slot * D))[k] = v;
+          if (det_flag[pos] & FP_TRACK_BEST) ((f32x4*)(sbest + (long)slot * D))[k] = v;
+        }
+        __threadfence_block();
+        __syncthreads();   // the rewritten embeddings are what the next frame's pairs read
+      }
+    }
+    __syncthreads();   // fmask is rewritten by the next batch of frames
+  }
+
+  for (int i = tid; i < SLOTS * NI; i += TPB) p.si[(long)s * SLOTS * NI + i] = (&s_i[0][0])[i];
+  for (int i = tid; i < SLOTS * NF; i += TPB) p.sf[(long)s * SLOTS * NF + i] = (&s_f[0][0])[i];
+  if (tid == 0) {
+    p.hdr[2 * s] = clock;
+    p.hdr[2 * s + 1] = next_id;
+  }
+}
+
+int check_track(const TrackArgs& a, const fp_track_state* st) {
+  if (!st || !a.hdr || !a.si || !a.sf || !a.semb || !a.sbest) return FP_ERR_INVALID_ARG;
+  if (a.S < 1 || a.D < 4 || a.D % 4 != 0 || a.D > FP_TRACK_MAX_DIM || a.n < 0 || a.n > FP_TRACK_MAX_ROWS || a.B < 0 || a.max_age < 0) return FP_ERR_INVALID_ARG;
+  if (a.B > 0 && !a.sof) return FP_ERR_INVALID_ARG;
+  if (a.n > 0 && (!a.frame || !a.box || !a.emb || !a.xinv || !a.o_id || !a.o_hits || !a.o_clock || !a.o_flags))
+    return FP_ERR_INVALID_ARG;
+  if (((uintptr_t)a.semb | (uintptr_t)a.sbest | (uintptr_t)a.emb) % 16 != 0) return FP_ERR_INVALID_ARG;   // float4 rows
+  if (!(a.tau_far >= a.tau_near) || a.iou_min != a.iou_min) return FP_ERR_INVALID_ARG;
+  return FP_OK;
+}
+
+TrackArgs track_args(const fp_track_state* st, int n_streams, int D, const int32_t* frame, const float* box, const float* emb,
+                     const float* xinv, const float* score, int n, const int32_t* stream_of_frame, int B, int max_age,
+                     float tau_near, float tau_far, float iou_min, int32_t* track_id, int32_t* track_hits, int32_t* track_clock,
+                     int32_t* track_flags) {
+  TrackArgs a;
+  a.hdr = st ? st->hdr : nullptr;
+  a.si = st ? st->slot_i : nullptr;
+  a.sf = st ? st->slot_f : nullptr;
+  a.semb = st ? st->emb : nullptr;
+  a.sbest = st ? st->best_emb : nullptr;
+  a.S = n_streams; a.D = D;
+  a.frame = frame; a.box = box; a.emb = emb; a.xinv = xinv; a.score = score; a.n = n;
+  a.sof = stream_of_frame; a.B = B;
+  a.max_age = max_age; a.tau_near = tau_near; a.tau_far = tau_far; a.iou_min = iou_min;
+  a.o_id = track_id; a.o_hits = track_hits; a.o_clock = track_clock; a.o_flags = track_flags;
+  return a;
+}
+
+// ---------------------------------------------------------------------------------------------------------- the host twin
+void emulate_frame(const TrackArgs& p, int s, int f, int& clock, int& next_id, std::vector<unsigned long long>& key) {
+  int* si = p.si + (long)s * SLOTS * NI;
+  float* sf = p.sf + (long)s * SLOTS * NF;
+  float* semb = p.semb + (long)s * SLOTS * p.D;
+  float* sbest = p.sbest + (long)s * SLOTS * p.D;
+  clock += 1;
+  for (int t = 0; t < SLOTS; ++t)
+    if (si[t * NI + I_ID] != 0 && clock - si[t * NI + I_LAST] > p.max_age) si[t * NI + I_ID] = 0;
+  long det_row[MAXD];
+  float det_inv[MAXD];
+  int nd = 0;
+  for (long i = 0; i < p.n; ++i) {
+    if (p.frame[i] != f) continue;
+    if (nd < MAXD) {
+      det_row[nd] = i;
+      det_inv[nd] = tk_live(p.xinv[i]) ? p.xinv[i] : 0.f;
+      ++nd;
+    } else {
+      tk_out(p, i, 0, 0, clock, FP_TRACK_OVER);
+    }
+  }
+  key.clear();
+  for (int t = 0; t < SLOTS; ++t) {
+    if (si[t * NI + I_ID] == 0) continue;
+    for (int j = 0; j < nd; ++j) {
+      if (!(det_inv[j] > 0.f)) continue;
+      float part[GL];
+      for (int gl = 0; gl < GL; ++gl) part[gl] = tk_partial(semb + (long)t * p.D, p.emb + det_row[j] * p.D, p.D, gl);
+      for (int off = GL / 2; off > 0; off >>= 1)   // the xor-shuffle sum as lane 0 sees it
+        for (int l = 0; l < off; ++l) part[l] = part[l] + part[l + off];
+      const float c = tk_cos(part[0], sf[t * NF + F_INV], det_inv[j]);
+      const float iou = tk_iou(sf + t * NF + F_BOX, p.box + det_row[j] * 4);
+      if (tk_admissible(p, c, iou)) key.push_back(tk_key(c, t, j));
+    }
+  }
+  std::sort(key.begin(), key.end());
+  int my_slot[MAXD];
+  for (int j = 0; j < MAXD; ++j) my_slot[j] = -1;
+  unsigned long long t_taken = 0ull, d_taken = 0ull;
+  for (size_t i = 0; i < key.size(); ++i) {
+    const int k_slot = tk_key_slot(key[i]), k_pos = tk_key_pos(key[i]);
+    if (((t_taken >> k_slot) & 1ull) || ((d_taken >> k_pos) & 1ull)) continue;
+    t_taken |= 1ull << k_slot;
+    d_taken |= 1ull << k_pos;
+    my_slot[k_pos] = k_slot;
+  }
+  int slot_of[MAXD], flag_of[MAXD];
+  for (int j = 0; j < nd; ++j) {
+    const long row = det_row[j];
+    slot_of[j] = -1;
+    flag_of[j] = 0;
+    if (!(det_inv[j] > 0.f)) {
+      tk_out(p, row, 0, 0, clock, FP_TRACK_DEAD_ROW);
+      continue;
+    }
+    int slot = my_slot[j];
+    const bool matched = slot >= 0;
+    int new_id = 0;
+    if (!matched) {
+      for (int t = 0; t < SLOTS && slot < 0; ++t)
+        if (si[t * NI + I_ID] == 0) slot = t;
+      if (slot < 0) {
+        tk_out(p, row, 0, 0, clock, FP_TRACK_FULL);
+        continue;
+      }
+      new_id = next_id++;
+    }
+    const int flags = tk_update_slot(p, si + slot * NI, sf + slot * NF, row, det_inv[j], !matched, clock, new_id);
+    tk_out(p, row, si[slot * NI + I_ID], si[slot * NI + I_HITS], clock, flags);
+    slot_of[j] = slot;
+    flag_of[j] = flags;
+  }
+  for (int j = 0; j < nd; ++j) {   // after every pair of the frame was scored against the old embeddings
+    if (slot_of[j] < 0) continue;
+    const float* e = p.emb + det_row[j] * p.D;
+    std::copy(e, e + p.D, semb + (long)slot_of[j] * p.D);
+    if (flag_of[j] & FP_TRACK_BEST) std::copy(e, e + p.D, sbest + (long)slot_of[j] * p.D);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int fp_tracklets_step(const fp_track_state* state, int n_streams, int D, const int32_t* frame, const float* box,
+                      const float* emb, const float* xinv, const float* score, int n, const int32_t* stream_of_frame, int B,
+                      int max_age, float tau_near, float tau_far, float iou_min, int32_t* track_id, int32_t* track_hits,
+                      int32_t* track_clock, int32_t* track_flags, void* stream) {
+  const TrackArgs a = track_args(state, n_streams, D, frame, box, emb, xinv, score, n, stream_of_frame, B, max_age, tau_near,
+                                 tau_far, iou_min, track_id, track_hits, track_clock, track_flags);
+  const int rc = check_track(a, state);
+  if (rc != FP_OK || (B == 0 && n == 0)) return rc;
+  hipLaunchKernelGGL(tracklets_kernel, dim3((unsigned)n_streams), dim3(TPB), 0, (hipStream_t)stream, a);
+  FP_CHECK_LAUNCH();
+  return FP_OK;
+}
+
+int fp_tracklets_step_emulate(const fp_track_state* state, int n_streams, int D, const int32_t* frame, const float* box,
+                              const float* emb, const float* xinv, const float* score, int n, const int32_t* stream_of_frame,
+                              int B, int max_age, float tau_near, float tau_far, float iou_min, int32_t* track_id,
+                              int32_t* track_hits, int32_t* track_clock, int32_t* track_flags) {
+  const TrackArgs p = track_args(state, n_streams, D, frame, box, emb, xinv, score, n, stream_of_frame, B, max_age, tau_near,
+                                 tau_far, iou_min, track_id, track_hits, track_clock, track_flags);
+  const int rc = check_track(p, state);
+  if (rc != FP_OK) return rc;
+  for (long i = 0; i < n; ++i)
+    if (tk_untracked(p, frame[i])) tk_out(p, i, 0, 0, 0, FP_TRACK_NO_STREAM);
+  std::vector<unsigned long long> key;
+  for (int f = 0; f < B; ++f) {   // streams are independent: batch order is every stream's own order
+    const int s = stream_of_frame[f];
+    if (s < 0 || s >= n_streams) continue;
+    emulate_frame(p, s, f, p.hdr[2 * s], p.hdr[2 * s + 1], key);
+  }
+  return FP_OK;
+}
+
+}  // extern "C"

@@ -37,10 +37,12 @@ class FrameFacesObj:
     boxes: np.ndarray
     feats: List[np.ndarray] = field(default_factory=list)
     face_jpegs: List[bytes] = field(default_factory=list)   # save_face=True: each face's JPEG file (None: an empty crop)
+    track_ids: List[int] = field(default_factory=list)      # tracker=...: each face's track id (0: none); else empty
 
 
 def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=None, save_face=False,
-                                     quality=95, align=False, quality_gate=None, tiled=None) -> List[FrameFacesObj]:
+                                     quality=95, align=False, quality_gate=None, tiled=None, tracker=None,
+                                     streams=None) -> List[FrameFacesObj]:
     """frames: (B, H, W, 3) u8 BGR (numpy or CUDA tensor), a RaggedFrames, or a list of (h, w, 3) frames.  One FacePipeline
     step (no similarity filter needed); returns per-frame records with boxes (each frame's own pixels, rounded), confs,
     area fractions and embeddings.  A list whose frames share one size is stacked and takes the uniform path; otherwise it
@@ -52,12 +54,14 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
     are left out of the records -- before save_extracted_faces applies the per-frame face cap, so a frame's
     MAX_N_FACES_PER_FRAME slots go to usable faces.  A gate with a pose term needs align (ValueError otherwise).
     tiled: dict(tile=(w, h), overlap=(ox, oy), merge_thr=t[, edge_px, full_frame, max_det]): for this call the pipeline's
-    detector runs on overlapping tiles of every frame as well (tiling.TiledDetector over pipe.det; merge_thr has no default)."""
+    detector runs on overlapping tiles of every frame as well (tiling.TiledDetector over pipe.det; merge_thr has no default).
+    tracker: a tracking.StreamTracker: for this call the step also tracks its faces (streams: the stream of every frame, None =
+    consecutive frames of stream 0) and every record carries track_ids, one per face; calls must come in video order."""
     if isinstance(frames, (list, tuple)) and not frames:
         return []
     frames = as_frames(frames, pipe.dev)
     B = len(frames)
-    was = (pipe.det, pipe.align)
+    was = (pipe.det, pipe.align, pipe.tracker)
     if tiled is not None:
         from ..tiling import TiledDetector
         key = tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in tiled.items()))
@@ -66,13 +70,16 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
             cache[(id(pipe.det), key)] = TiledDetector(pipe.det, **tiled)
         pipe.det = cache[(id(pipe.det), key)]
     pipe.align = pipe.align or bool(align)
+    if tracker is not None:
+        pipe.tracker = tracker
     try:
-        res = pipe.step(frames)               # detect -> crops -> embed (+ the exact re-run on a detector overflow)
+        res = pipe.step(frames, streams=streams)   # detect -> crops -> embed (+ the exact re-run on a detector overflow)
     finally:
-        pipe.det, pipe.align = was
+        pipe.det, pipe.align, pipe.tracker = was
     n = res["n_faces"]
     emb = res["emb"].cpu().numpy()
     info = res["info"].cpu().numpy()
+    track_ids = res["track_id"].cpu().numpy() if "track_id" in res else None
     keep = None
     if quality_gate is not None:
         from ..quality import face_quality
@@ -104,6 +111,8 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
         out[f].feats.append(emb[k])
         if jpegs is not None:
             out[f].face_jpegs.append(jpegs[k])
+        if track_ids is not None:
+            out[f].track_ids.append(int(track_ids[k]))
     for f in range(B):
         if boxes[f]:
             out[f].boxes = np.asarray(boxes[f], dtype=np.float32)

@@ -1,0 +1,119 @@
+"""track_faces_in_frames: the faces of one video, given as a folder of its frames, grouped into tracks.
+
+Every .jpg of --frames (sorted by name = video order) goes through FacePipeline (BlazeFace-back + Mobile-FaceNet) batch by
+batch with a tracking.StreamTracker behind the embedder: one fp_tracklets_step launch per batch assigns every face a track id
+(DESIGN section 7 "Tracklets").  A TrackBook collects, per track, its first and last frame, its hits and its best row (the
+highest detector confidence, or with --quality the sharpest crop); at the end <td>/tracks.json lists the tracks and
+<td>/track_XXXX/best.jpg is each track's best face crop, encoded on the device (modules/utils/jpeg.py encode_crops).
+
+`--model synthetic` (the default: no trained weights ship with the project) runs the seeded random weights of workload.py.
+The thresholds default to the reference's numbers restated as cosines, unmeasured on real video; --max_age has no default.
+Build-defined: the reference labels faces frame by frame (face_tracker.py is that port).
+"""
+import argparse
+import glob
+import json
+import os
+
+import numpy as np
+
+from ..tracking import BEST, IOU_MIN, TAU_FAR, TAU_NEAR, StreamTracker, TrackBook
+
+
+def get_parsed_args(argv=None):
+    parser = argparse.ArgumentParser()
+    parser.add_argument('--frames', dest="frames_path", type=str, required=True, help="a folder of one video's frames as .jpg")
+    parser.add_argument('--td', '--target_data_path', dest="target_data_path", type=str, default="data/tracks")
+    parser.add_argument('--model', default="synthetic", help="'synthetic' (seeded random weights); trained weights: use the API")
+    parser.add_argument('--max_age', type=int, required=True,
+                        help='a track unseen for more than this many frames ends (no default: nothing has been measured)')
+    parser.add_argument('--tau_near', type=float, default=TAU_NEAR)
+    parser.add_argument('--tau_far', type=float, default=TAU_FAR)
+    parser.add_argument('--iou_min', type=float, default=IOU_MIN)
+    parser.add_argument('--quality', action="store_true", help="best shot by crop sharpness instead of detector confidence")
+    parser.add_argument('-b', '--batch_size', type=int, default=256)
+    parser.add_argument('--jpeg_quality', type=int, default=95)
+    parser.add_argument('-d', '--device', default="cuda:0")
+    return parser.parse_args(argv)
+
+
+def frame_files(folder):
+    return sorted(glob.glob(os.path.join(folder, "*.jpg")))
+
+
+def build_pipeline(args, dev, first_frames):
+    """(pipeline, tracker) on the synthetic weights, the detector's scores calibrated on the first frames."""
+    from .. import workload as W
+    from ..pipeline import FacePipeline
+    if args.model != "synthetic":
+        raise ValueError("only --model synthetic is wired here; build a FacePipeline(..., tracker=StreamTracker(...)) for real weights")
+    det = W.build_detector(dev, first_frames, cand_per_frame=48)
+    emb = W.build_embedder(dev)
+    tracker = StreamTracker(1, emb.embedding_size, args.max_age, args.tau_near, args.tau_far, args.iou_min, device=dev)
+    return FacePipeline(det, emb, None, quality=True if args.quality else None, tracker=tracker), tracker
+
+
+def track_frames(pipe, paths, batch_size, jpeg_quality=95):
+    """-> (TrackBook, {(stream, id): JPEG bytes of the best row's crop}).  Frames of one size (a video's)."""
+    import torch
+    from ..modules.utils.jpeg import encode_crops, imread_batch
+    book, shots = TrackBook(), {}
+    for lo in range(0, len(paths), int(batch_size)):
+        frames = imread_batch(paths[lo:lo + int(batch_size)], pipe.dev)
+        if not isinstance(frames, torch.Tensor):
+            raise ValueError("the frames of a video share one size")
+        res = pipe.step(frames)
+        n, info = res["n_faces"], res["info"]
+        score = res["quality"]["sharpness"] if "quality" in res else info[:, 5]
+        sof = np.zeros((frames.shape[0],), np.int32)
+        out = {k: res[k] for k in pipe.TRACK_KEYS}
+        book.update(out, info[:n, 0].to(torch.int32), info[:n, 1:5], sof, emb=res["emb"], score=score[:n], frame_base=lo)
+        flags, ids = res["track_flags"].cpu().numpy(), res["track_id"].cpu().numpy()
+        best_rows = [i for i in range(n) if flags[i] & BEST and ids[i] > 0]
+        if best_rows:                              # the crops of this batch's BEST rows, one device call; a later BEST replaces
+            idx = torch.as_tensor(best_rows, device=pipe.dev)
+            files = encode_crops(frames, res["items"][idx].contiguous(), len(best_rows), quality=jpeg_quality)
+            for i, data in zip(best_rows, files):
+                shots[(0, int(ids[i]))] = data
+    return book, shots
+
+
+def save_tracks(target, book, shots, paths):
+    """<target>/tracks.json and <target>/track_XXXX/best.jpg.  -> the list written to tracks.json."""
+    os.makedirs(target, exist_ok=True)
+    tracks = []
+    for r in book.rows():
+        name = f"track_{r['id']:04d}"
+        rec = dict(id=r["id"], first_frame=os.path.basename(paths[r["first_clock"] - 1]),
+                   last_frame=os.path.basename(paths[r["last_clock"] - 1]), hits=r["hits"], best_score=r["best_score"],
+                   best_file=os.path.basename(paths[r["best_frame"]]), best_box=r["best_box"], best_jpg=None)
+        data = shots.get((r["stream"], r["id"]))
+        if data is not None:
+            os.makedirs(os.path.join(target, name), exist_ok=True)
+            with open(os.path.join(target, name, "best.jpg"), "wb") as f:
+                f.write(data)
+            rec["best_jpg"] = f"{name}/best.jpg"
+        tracks.append(rec)
+    with open(os.path.join(target, "tracks.json"), "w") as f:
+        json.dump(dict(frames=len(paths), tracks=tracks), f, indent=1)
+    return tracks
+
+
+def main(argv=None):
+    import torch
+    from ..modules.utils.jpeg import imread_batch
+    args = get_parsed_args(argv)
+    print(args)
+    paths = frame_files(args.frames_path)
+    if not paths:
+        raise Exception(f"no .jpg under {args.frames_path}")
+    dev = torch.device(args.device)
+    pipe, _ = build_pipeline(args, dev, imread_batch(paths[:8], dev))
+    book, shots = track_frames(pipe, paths, args.batch_size, args.jpeg_quality)
+    tracks = save_tracks(args.target_data_path, book, shots, paths)
+    print(f"{len(tracks)} tracks in {len(paths)} frames -> {os.path.join(args.target_data_path, 'tracks.json')}")
+    return tracks
+
+
+if __name__ == "__main__":
+    main()

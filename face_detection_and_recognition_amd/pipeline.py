@@ -35,7 +35,12 @@ class FacePipeline:
     face in the order of emb, voted by `vote` ("top1" | "majority"); side stream as the attributes.
     quality: True or a QualityGate (quality.py): step results then also carry quality, the face_quality dict of the step's items
     (with align, the pose columns from its landmarks), rows in the order of emb, and, with a gate, quality_keep (n,) bool: its
-    mask, which compacts nothing (as the cosine filter's keep); side stream as the attributes."""
+    mask, which compacts nothing (as the cosine filter's keep); side stream as the attributes.
+    tracker: a StreamTracker (tracking.py) whose feat_dim is the embedder's: step results then also carry track_id, track_hits,
+    track_clock and track_flags (n,) int32, rows in the order of emb, from one fp_tracklets_step launch behind the embedder (side
+    stream as the attributes).  step / step_overlapped take streams = the stream of every frame ((B,) ints, -1: not tracked;
+    None: the batch is consecutive frames of stream 0).  The score of the best shot is the conf column of info, or
+    quality["sharpness"] with quality on.  Steps must reach the tracker in order: it carries state from step to step."""
 
     # embed(): a batch a little above a multiple of ROUND_CROPS crops is run as that multiple + the remainder on a side stream
     ROUND_CROPS = 512     # crops whose tiles fill whole rounds of workgroups in every Depth_Wise kernel (2 / 4 / 7 tiles per crop, 512 slots)
@@ -44,8 +49,11 @@ class FacePipeline:
 
     def __init__(self, detector, embedder, reference=None, tau=0.3, max_faces_per_frame=8, bucket=8, two_streams=False,
                  split_tail=True, align=False, attributes=None, gallery=None, top_k=5, identify_tau=None, vote="top1",
-                 quality=None):
+                 quality=None, tracker=None):
         self.det = detector
+        if tracker is not None and tracker.D != embedder.embedding_size:
+            raise ValueError(f"tracker feat_dim {tracker.D} is not the embedder's {embedder.embedding_size}")
+        self.tracker = tracker
         if not (quality is None or quality is True or isinstance(quality, Q.QualityGate)):
             raise ValueError(f"quality must be None, True or a QualityGate, got {quality!r}")
         self.quality = quality
@@ -173,7 +181,7 @@ class FacePipeline:
         return self.emb.plan_for(cap, n_run=n_pad)
 
     # -- software-pipelined form ----------------------------------------------------------------------
-    def step_overlapped(self, frames):
+    def step_overlapped(self, frames, streams=None):
         """step() with the host round trip taken off the GPU's critical path: this call ENQUEUES the detector stages of
         `frames` and then finishes the PREVIOUS call's batch (embed + filter), whose face count -- produced a whole
         detector pass ago -- is already on the host when it is read (pinned buffer + event).  The GPU queue never drains
@@ -190,7 +198,7 @@ class FacePipeline:
         self._counts_to_host(nf, over, host)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.dev))
-        prev, self._pending = getattr(self, "_pending", None), (frames, (items, info, nf, al), host, ev)
+        prev, self._pending = getattr(self, "_pending", None), (frames, (items, info, nf, al), host, ev, streams)
         return None if prev is None else self._finish(prev)
 
     def flush(self):
@@ -208,7 +216,7 @@ class FacePipeline:
         host[1] = 0
         host[:both.numel()].copy_(both, non_blocking=True)
 
-    def _result(self, frames, crops, n, n_over, side=None):
+    def _result(self, frames, crops, n, n_over, side=None, streams=None):
         """The step's result dict from the crop stage's outputs and the two host counts: the exact re-run after a detector
         overflow, the cap check, embed, filter, attributes, identity, alignment records.  side = (stream, event the crops are
         complete at): embed and everything after it run there and the dict carries the event `done` (_finish)."""
@@ -229,6 +237,8 @@ class FacePipeline:
             self._add_identity(out)
             if self.quality is not None:
                 self._add_quality(out, frames, items, al, n)
+            if self.tracker is not None:
+                self._add_tracks(out, batch_len(frames), streams)
             return out, res
         if side is None:
             out, res = tail()
@@ -255,6 +265,7 @@ class FacePipeline:
             attrs = tuple(out[k] for k in ("age_probs", "gender_probs") + self.IDENTITY_KEYS if k in out)
             if self.quality is not None:
                 attrs += tuple(out["quality"].values()) + ((out["quality_keep"],) if "quality_keep" in out else ())
+            attrs += tuple(out[k] for k in self.TRACK_KEYS if k in out)
             for t in (out["emb"],) + attrs + (tuple(res) if res is not None else ()):
                 t.record_stream(main)
             self._emb_done = torch.cuda.Event()
@@ -263,9 +274,10 @@ class FacePipeline:
         return out, res
 
     def _finish(self, pending):
-        frames, crops, host, ev = pending
+        frames, crops, host, ev, streams = pending
         ev.synchronize()
-        return self._result(frames, crops, int(host[0]), int(host[1]), None if self.emb_stream is None else (self.emb_stream, ev))
+        return self._result(frames, crops, int(host[0]), int(host[1]), None if self.emb_stream is None else (self.emb_stream, ev),
+                            streams)
 
     ATTR_CAP_STEP = 64    # the attribute plan's capacity grows in steps of this many crops (about 3.8 MB of arena each)
 
@@ -307,6 +319,26 @@ class FacePipeline:
         if self.quality is not True:
             out["quality_keep"] = self.quality.mask(out["quality"])
 
+    TRACK_KEYS = ("track_id", "track_hits", "track_clock", "track_flags")
+
+    def _stream_of_frame(self, B, streams):
+        """(B,) int32 on the device: zeros for None (small cache by B), else the caller's streams."""
+        if streams is None:
+            cache = self.__dict__.setdefault("_stream0", {})
+            if B not in cache:
+                cache[B] = torch.zeros((B,), dtype=torch.int32, device=self.dev)
+            return cache[B]
+        sof = torch.as_tensor(streams, dtype=torch.int32).reshape(-1)
+        if sof.shape[0] != B:
+            raise ValueError(f"streams has {sof.shape[0]} entries for a batch of {B} frames")
+        return sof.to(self.dev, non_blocking=True)
+
+    def _add_tracks(self, out, B, streams):
+        """One tracker launch over the step's rows (info's frame and box columns, emb, the score)."""
+        n, info = out["n_faces"], out["info"]
+        score = out["quality"]["sharpness"] if self.quality is not None else info[:, 5]
+        out.update(self.tracker.step(info[:, 0], info[:, 1:5], out["emb"], self._stream_of_frame(B, streams), score=score, n=n))
+
     @staticmethod
     def _add_align(out, al, n):
         if al is not None:
@@ -326,7 +358,7 @@ class FacePipeline:
         return annotate_step(frames, result, **kw)
 
     # -- whole step ------------------------------------------------------------------------------
-    def step(self, frames, beside=False):
+    def step(self, frames, beside=False, streams=None):
         """One pass over a batch of frames ((B, H, W, 3) u8 BGR on device, or a RaggedFrames of different sizes).
         Returns dict(n_faces, info, emb, best, arg, keep).
         ``emb`` is a copy (the embedder's output lives in its plan arena and the next step overwrites it).
@@ -334,4 +366,4 @@ class FacePipeline:
         dets, counts, over = self.detect(frames, beside=beside)
         crops = self._crops(frames, dets, counts)
         n, n_over = self._counts_to_host(crops[2], over)     # (the face count sizes the embedder batch)
-        return self._result(frames, crops, n, n_over)
+        return self._result(frames, crops, n, n_over, streams=streams)

@@ -1304,6 +1304,84 @@ int fp_merge_views_emulate(const float* dets, const int32_t* counts, int S, int 
 int fp_gather_tiles(const uint8_t* frames, size_t frames_bytes, const fp_frame_desc* descs /*device*/, int n_frames,
                     const fp_tile_view* views /*device*/, int S, int tile_w, int tile_h, uint8_t* out, void* stream);
 
+/*
+ * Tracklets (build-defined, no reference counterpart; DESIGN §7 "Tracklets"; csrc/tracklets.hip): faces tracked across the
+ * frames of many streams, one launch per step, nothing read back.  fp_tracker_step stays the port of the reference's
+ * per-frame first-match rule; this is the batched tracker of the pipeline's 256-frame steps (256 frames of one video, one
+ * frame of each of 256 cameras, or any mix).  All additive: ABI 14.
+ *
+ * State, owned by the caller (fp_track_state: five arrays, zero-filled except next_id = 1 for a fresh tracker), per stream s:
+ *   hdr      [S][2] int32                       clock (frames processed so far), next_id (starts at 1)
+ *   slot_i   [S][FP_TRACK_SLOTS][5] int32       id (0 = free), first_clock, last_clock, hits, best_clock
+ *   slot_f   [S][FP_TRACK_SLOTS][10] fp32       last box x1 y1 x2 y2, inverse norm of the last embedding, best_score,
+ *                                               best box x1 y1 x2 y2
+ *   emb      [S][FP_TRACK_SLOTS][D] fp32        last embedding;    best_emb likewise: the best row's embedding
+ * Inputs of a step: n face rows -- frame[i] (index into the batch), box[i] (4 fp32), emb [n][D] fp32, xinv[i] =
+ * fp_row_inv_norm(emb), score[i] (NULL: every score is 0) -- and stream_of_frame [B] (-1: the frame is not tracked).  A row is
+ * LIVE when xinv is finite and > 0 (the rule of fp_cosine_dbscan_x6 and fp_pair_histogram_x6).  Frames of one stream are
+ * processed in ascending batch index, the rows of a frame in row order (they need not be contiguous); streams are independent.
+ * A row's POSITION is its rank among the rows of its frame, dead rows included; rows at positions >= FP_TRACK_MAX_DETS take
+ * no part (flag OVER).  For each frame of stream s, all arithmetic fp32 in the written order, no contraction:
+ *   1. clock += 1; every slot with clock - last_clock > max_age is freed.
+ *   2. For every live track t and every live detection d: c = (dot(emb_t, emb_d) * inv_t) * inv_d (the order of the dot
+ *      product's additions is the kernel's own: the device and the emulator share it, another implementation agrees wherever
+ *      no c lies within D * 2^-24 of a threshold or of another c).  With min(a, b) = a < b ? a : b, max(a, b) = a > b ? a : b
+ *      and a the track's value: iw = min(x2) - max(x1), ih likewise; if not (iw > 0 and ih > 0) iou = 0, else inter = iw * ih,
+ *      iou = inter / ((area_t + area_d) - inter), area = (x2 - x1) * (y2 - y1).  The pair is admissible when
+ *      (c > tau_near && iou > iou_min) || c > tau_far; comparisons with NaN are false.
+ *   3. Admissible pairs in the order c descending (-0 counts as +0), then lower slot, then lower position; walking them, a pair
+ *      is taken when its track and its detection are both still free.  A match rewrites the slot's last box, last embedding
+ *      and inverse norm, sets last_clock = clock and increments hits.
+ *   4. Every live detection left unmatched, in row order, opens a track in the lowest free slot: id = next_id++, hits = 1,
+ *      first_clock = last_clock = clock.  No free slot: the row gets id 0 and FP_TRACK_FULL.  (A track opened in a frame is
+ *      not matched in that frame.)
+ *   5. A matched row whose score is strictly greater than the slot's best_score, and every opening row, becomes the track's
+ *      best: best_score, best_clock, best box and best_emb are rewritten and the row gets FP_TRACK_BEST.
+ * Per-row outputs: track_id (0: none), track_hits (the slot's hits after the row; 0 without an id), track_clock (the
+ * stream's clock at the row's frame; 0 for NO_STREAM) and track_flags: NEW, BEST, DEAD_ROW (a row that is not live), FULL,
+ * NO_STREAM (frame[i] outside [0, B), or its stream -1 or outside [0, n_streams)), OVER.  DEAD_ROW, FULL, NO_STREAM and OVER
+ * rows change no state; an OVER row is flagged OVER alone.
+ * The defaults of tracking.py restate the reference's thresholds (fp_tracker_step) for unit vectors through
+ * cos = 1 - dist^2 / 2: dist < 1.0 with IoU > 0.1 -> tau_near = 0.5, iou_min = 0.1; dist < 0.72 alone -> tau_far = 0.7408.
+ * They are the reference's numbers, unmeasured on real video.  max_age has no reference counterpart and no default.
+ *
+ * fp_tracklets_step: one launch, one workgroup per stream (one whose stream has no frame in the step leaves at once); no
+ * global atomics, no workspace, no host synchronisation; two runs are bit-identical.  Every pointer but `state` itself (a
+ * HOST struct of device pointers) is device memory the host does not read.  Refusals before any launch (FP_ERR_INVALID_ARG): a
+ * NULL state or state array, n_streams < 1, D not a multiple of 4, D < 4 or D > FP_TRACK_MAX_DIM, n < 0 or n >
+ * FP_TRACK_MAX_ROWS, B < 0, max_age < 0, a NULL stream_of_frame with B > 0, a NULL row input or output with n > 0, emb or a
+ * state embedding array not 16-byte aligned, tau_far < tau_near or a NaN threshold.  B == 0 and n == 0: FP_OK, nothing launched;
+ * frames without rows still advance their stream's clock.
+ * fp_tracklets_step_emulate: the same decision code serially on HOST memory (every pointer HOST), the same bits.
+ */
+#define FP_TRACK_SLOTS 64
+#define FP_TRACK_MAX_DETS 64
+#define FP_TRACK_MAX_DIM 1024
+#define FP_TRACK_MAX_ROWS (1 << 30)
+#define FP_TRACK_SLOT_INTS 5
+#define FP_TRACK_SLOT_FLOATS 10
+#define FP_TRACK_NEW 1
+#define FP_TRACK_BEST 2
+#define FP_TRACK_DEAD_ROW 4
+#define FP_TRACK_FULL 8
+#define FP_TRACK_NO_STREAM 16
+#define FP_TRACK_OVER 32
+typedef struct fp_track_state {
+  int32_t* hdr;
+  int32_t* slot_i;
+  float* slot_f;
+  float* emb;
+  float* best_emb;
+} fp_track_state;
+int fp_tracklets_step(const fp_track_state* state /*host struct*/, int n_streams, int D, const int32_t* frame, const float* box,
+                      const float* emb, const float* xinv, const float* score /* or NULL */, int n,
+                      const int32_t* stream_of_frame /* B */, int B, int max_age, float tau_near, float tau_far, float iou_min,
+                      int32_t* track_id, int32_t* track_hits, int32_t* track_clock, int32_t* track_flags, void* stream);
+int fp_tracklets_step_emulate(const fp_track_state* state, int n_streams, int D, const int32_t* frame, const float* box,
+                              const float* emb, const float* xinv, const float* score, int n, const int32_t* stream_of_frame,
+                              int B, int max_age, float tau_near, float tau_far, float iou_min, int32_t* track_id,
+                              int32_t* track_hits, int32_t* track_clock, int32_t* track_flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,197 @@
+"""Tracklets on the host (no GPU): the numpy restatement against fp_tracklets_step_emulate on every case of track_cases.py (the
+four per-row outputs and the whole final state, equal, after the case passed its gap condition), the outcome each crafted case
+was built for, the invariances (split, interleave, row order), the reference's first-match rule answering differently on the
+greedy case, TrackBook on a hand-written sequence, the refusals, and header / binding agreement."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+import track_cases as TC
+from face_detection_and_recognition_amd import _lib as L
+from face_detection_and_recognition_amd import tracking as T
+
+CASES = TC.crafted_cases()
+BUSY = [TC.busy(D, seed) for D in TC.DIMS for seed in (5, 6)]
+
+
+@pytest.fixture(scope="module")
+def numpy_runs():
+    """name -> (outs, state) of the numpy run of every case, made once (assert_gap is that run)."""
+    return {c["name"]: TC.assert_gap(c) for c in CASES + BUSY}
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
+def test_crafted_case_numpy_equals_emulator_and_states_its_outcome(case, numpy_runs):
+    want = numpy_runs[case["name"]]
+    case["expect"](*want)
+    got = TC.run_case(case, T.track_step_emulate)
+    case["expect"](*got)
+    TC.assert_same(got, want, case["name"])
+
+
+@pytest.mark.parametrize("case", BUSY, ids=[c["name"] for c in BUSY])
+def test_busy_batch_numpy_equals_emulator(case, numpy_runs):
+    want = numpy_runs[case["name"]]
+    ids = want[0][0]["track_id"]
+    assert (ids > 0).sum() > 20 and len(np.unique(want[0][0]["track_clock"])) > 4
+    assert (want[0][0]["track_flags"] & T.NO_STREAM).any()
+    assert (want[1]["hdr"][:, 1] - 1).sum() > 3 * case["S"]          # more ids than identities: tracks expired and came back
+    TC.assert_same(TC.run_case(case, T.track_step_emulate), want, case["name"])
+
+
+@pytest.mark.parametrize("step_fn", [T.track_step_numpy, T.track_step_emulate], ids=["numpy", "emulate"])
+@pytest.mark.parametrize("case", BUSY[::2], ids=[c["name"] for c in BUSY[::2]])
+def test_split_anywhere_changes_nothing(case, step_fn, numpy_runs):
+    """One step equals the same frames as two steps cut at ANY frame, inside the burst of empty frames too."""
+    (whole,), state = numpy_runs[case["name"]]
+    B = len(case["steps"][0]["stream_of_frame"])
+    for k in range(0, B + 1):
+        two, rows = TC.split_case(case, k)
+        outs, st = TC.run_case(two, step_fn)
+        for part, r in zip(outs, rows):
+            for key in T.OUT_KEYS:
+                assert np.array_equal(part[key], whole[key][r]), (k, key)
+        TC.assert_same_state(st, state, f"split at {k}")
+
+
+@pytest.mark.parametrize("step_fn", [T.track_step_numpy, T.track_step_emulate], ids=["numpy", "emulate"])
+@pytest.mark.parametrize("case", BUSY[::2], ids=[c["name"] for c in BUSY[::2]])
+def test_interleaved_streams_equal_each_stream_alone(case, step_fn, numpy_runs):
+    (whole,), state = numpy_runs[case["name"]]
+    for s in range(case["S"]):
+        alone, rows = TC.stream_alone(case, s)
+        (out,), st = TC.run_case(alone, step_fn)
+        assert len(rows) > 0
+        for key in T.OUT_KEYS:
+            assert np.array_equal(out[key], whole[key][rows]), (s, key)
+        for key in T.STATE_KEYS:
+            assert st[key][0].tobytes() == state[key][s].tobytes(), (s, key)
+
+
+@pytest.mark.parametrize("step_fn", [T.track_step_numpy, T.track_step_emulate], ids=["numpy", "emulate"])
+@pytest.mark.parametrize("case", BUSY[::2], ids=[c["name"] for c in BUSY[::2]])
+def test_rows_of_a_frame_need_not_be_contiguous(case, step_fn, numpy_runs):
+    (whole,), state = numpy_runs[case["name"]]
+    mixed, perm = TC.scattered(case)
+    fr = mixed["steps"][0]["frame"]
+    assert (np.diff(fr) < 0).sum() > len(fr) // 4                   # really out of frame order
+    (out,), st = TC.run_case(mixed, step_fn)
+    for key in T.OUT_KEYS:
+        assert np.array_equal(out[key], whole[key][perm]), key
+    TC.assert_same_state(st, state, "scattered rows")
+
+
+def test_reference_first_match_rule_answers_a_where_greedy_answers_b():
+    """Why the new rule exists: the reference's Net.check_if_face_exists (oracle FaceTrackerRef, walk in insertion order, first
+    admissible face wins) gives the greedy case's detection to track A, the marginal match that shadows the strong one."""
+    from oracle.tracker_ref import FaceTrackerRef
+    for D in TC.DIMS:
+        a, b, d, (ba, bb, bd) = TC.greedy_rows(D)
+        a, b, d = (np.asarray(v, np.float32) for v in (a, b, d))
+        dist = lambda u, v: float(np.linalg.norm(u.astype(np.float64) - v))        # noqa: E731
+        assert 0.72 + 1e-3 < dist(a, d) < 1.0 - 1e-3 and dist(b, d) < 0.72 - 1e-3    # A: with IoU only; B: alone
+        ref = FaceTrackerRef("MOBILE_FACENET")
+        ids, exists = ref.track([a, b], [ba, bb])
+        assert ids.tolist() == [1, 2] and not exists.any()
+        ids, exists = ref.track([d], [bd])
+        assert ids.tolist() == [1] and exists.all()                                  # first match: A
+        (out,), _ = TC.run_case(TC.greedy_beats_first_match(D), T.track_step_numpy)
+        assert out["track_id"].tolist() == [1, 2, 2]                                 # greedy: B
+
+
+def test_trackbook_on_a_hand_written_sequence():
+    book = T.TrackBook()
+    NB = T.NEW | T.BEST
+    out0 = dict(track_id=np.array([1, 2, 0, 1]), track_hits=np.array([1, 1, 0, 2]), track_clock=np.array([1, 1, 1, 2]),
+                track_flags=np.array([NB, NB, T.DEAD_ROW, 0]))
+    frame0, sof0 = np.array([0, 0, 0, 1]), np.array([3, 3])
+    boxes0 = np.arange(16, dtype=np.float32).reshape(4, 4)
+    emb0 = np.arange(8, dtype=np.float32).reshape(4, 2)
+    assert book.update(out0, frame0, boxes0, sof0, emb=emb0, score=np.array([0.5, 0.1, 0.9, 0.4], np.float32)) == [(3, 1), (3, 2), (3, 1)]
+    out1 = dict(track_id=np.array([1, 1]), track_hits=np.array([3, 1]), track_clock=np.array([3, 1]), track_flags=np.array([T.BEST, NB]))
+    touched = book.update(out1, np.array([0, 1]), boxes0[:2] + 100, np.array([3, 0]), emb=emb0[2:], score=np.array([0.75, 0.2], np.float32),
+                          frame_base=2)
+    assert touched == [(3, 1), (0, 1)] and len(book) == 3
+    r = book[(3, 1)]
+    assert (r["first_clock"], r["last_clock"], r["hits"], r["best_clock"], r["best_frame"]) == (1, 3, 3, 3, 2)
+    assert r["best_score"] == 0.75 and r["best_box"] == [100.0, 101.0, 102.0, 103.0] and r["best_emb"].tolist() == [4.0, 5.0]
+    r = book[(3, 2)]
+    assert (r["first_clock"], r["last_clock"], r["hits"], r["best_frame"]) == (1, 1, 1, 0) and abs(r["best_score"] - 0.1) < 1e-7
+    assert book[(0, 1)]["best_frame"] == 3 and [x["stream"] for x in book.rows()] == [0, 3, 3]
+
+
+# ------------------------------------------------------------------------------------------------ refusals, ABI, header
+
+def _emulate_args(D=32, n=2, B=2, S=1):
+    st = T.new_state(S, D)
+    rows = dict(frame=np.zeros((n,), np.int32), box=np.zeros((n, 4), np.float32), emb=np.ones((n, D), np.float32),
+                xinv=np.ones((n,), np.float32), sof=np.zeros((B,), np.int32))
+    outs = [np.zeros((n,), np.int32) for _ in range(4)]
+    return st, rows, outs
+
+
+def test_refusals(lib):
+    p = lambda a: ctypes.c_void_p(a.ctypes.data)                     # noqa: E731
+    st, r, outs = _emulate_args()
+    struct = L.FpTrackState(*[p(st[k]) for k in T.STATE_KEYS])
+
+    def call(fn=lib.fp_tracklets_step_emulate, state=struct, S=1, D=32, n=2, B=2, max_age=1, tn=0.5, tf=0.7, im=0.1, tail=(), **ptr):
+        a = {k: p(v) for k, v in r.items()}
+        a.update(ptr)
+        o = [p(x) for x in outs]
+        if "out" in ptr:
+            o[ptr["out"]] = None
+        return fn(None if state is None else ctypes.byref(state), S, D, a["frame"], a["box"], a["emb"], a["xinv"], None, n, a["sof"], B,
+                  max_age, tn, tf, im, *o, *tail)
+    assert call() == L.FP_OK
+    for kw in (dict(D=30), dict(D=1028), dict(D=0), dict(S=0), dict(n=-1), dict(B=-1), dict(max_age=-1), dict(tn=0.8, tf=0.7),
+               dict(tn=float("nan")), dict(tf=float("nan")), dict(im=float("nan")), dict(state=None), dict(frame=None),
+               dict(box=None), dict(emb=None), dict(xinv=None), dict(sof=None), dict(out=0), dict(out=3)):
+        assert call(**kw) == L.FP_ERR_INVALID_ARG, kw
+        assert call(fn=lib.fp_tracklets_step, tail=(None,), **kw) == L.FP_ERR_INVALID_ARG, kw     # refused before any HIP call
+    for k in T.STATE_KEYS:                                           # a NULL state array
+        bad = L.FpTrackState(*[None if j == k else p(st[j]) for j in T.STATE_KEYS])
+        assert call(state=bad) == L.FP_ERR_INVALID_ARG, k
+    odd = np.ones((2 * 32 + 1,), np.float32)[1:]                     # rows that are not 16-byte aligned
+    assert call(emb=ctypes.c_void_p(odd.ctypes.data)) == L.FP_ERR_INVALID_ARG
+    assert call(n=0, frame=None, box=None, emb=None, xinv=None) == L.FP_OK          # empty frames alone
+    assert lib.fp_abi_version() == 14                                # additions only
+
+
+def test_python_refusals():
+    for kw in (dict(n_streams=0), dict(feat_dim=30), dict(feat_dim=1028), dict(max_age=-1), dict(tau_near=0.8, tau_far=0.7),
+               dict(tau_far=float("nan"))):
+        a = dict(n_streams=1, feat_dim=32, max_age=1, tau_near=0.5, tau_far=0.7, iou_min=0.1)
+        a.update(kw)
+        with pytest.raises(ValueError):
+            T.check_params(**a)
+        with pytest.raises(ValueError):
+            T.StreamTracker(device="cpu", **a)                       # refused before anything touches a device
+    st = T.new_state(1, 32)
+    with pytest.raises(ValueError):
+        T.track_step_numpy(st, [0], np.zeros((1, 4)), np.ones((1, 32)), [1.0], [0], 1, tau_near=0.8, tau_far=0.7)
+    with pytest.raises(TypeError):
+        T.StreamTracker(1, 32)                                       # max_age has no default
+
+
+def test_header_and_bindings_agree():
+    from conftest import ROOT
+    hdr = open(os.path.join(ROOT, "include", "facepath.h")).read()
+    for name, val in (("SLOTS", L.TRACK_SLOTS), ("MAX_DETS", L.TRACK_MAX_DETS), ("MAX_DIM", L.TRACK_MAX_DIM),
+                      ("SLOT_INTS", L.TRACK_SLOT_INTS), ("SLOT_FLOATS", L.TRACK_SLOT_FLOATS), ("NEW", L.TRACK_NEW),
+                      ("BEST", L.TRACK_BEST), ("DEAD_ROW", L.TRACK_DEAD_ROW), ("FULL", L.TRACK_FULL),
+                      ("NO_STREAM", L.TRACK_NO_STREAM), ("OVER", L.TRACK_OVER)):
+        assert f"#define FP_TRACK_{name} {val}\n" in hdr, name
+    assert f"#define FP_TRACK_MAX_ROWS (1 << {L.TRACK_MAX_ROWS.bit_length() - 1})\n" in hdr
+    assert L.TRACK_SLOTS == 64 and L.TRACK_MAX_DETS == 64
+    for fn in ("fp_tracklets_step", "fp_tracklets_step_emulate"):
+        decl = re.search(r"\nint " + fn + r"\(([^;]*)\);", hdr).group(1)
+        n_args = len([a for a in re.sub(r"/\*.*?\*/", "", decl, flags=re.S).split(",") if a.strip()])
+        assert n_args == len(L.SIGNATURES[fn][1]), fn
+    fields = re.search(r"typedef struct fp_track_state \{(.*?)\} fp_track_state;", hdr, re.S).group(1)
+    assert re.findall(r"\*\s*(\w+);", fields) == [f[0] for f in L.FpTrackState._fields_] == list(T.STATE_KEYS)
+    integ = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    assert "fp_tracklets_step" in integ and "fp_tracklets_step_emulate" in integ

@@ -1,0 +1,152 @@
+"""The batched tracker (tracking.StreamTracker, fp_tracklets_step) next to the per-frame port of the reference's rule
+(face_extraction/face_tracker.py FaceTracker.track, fp_tracker_step), on the same rows in the same run, D = 512:
+
+  a   256 streams x 1 frame, 2 faces each          (256 workgroups, one frame each)
+  b   1 stream x 256 frames, 2 faces each          (one workgroup marches 256 frames)
+  c   1 stream x 256 frames, 8 faces each, 32 identities taking turns: about 32 live tracks
+
+Per layout, milliseconds per step of 256 frames: tracklets_ms (one launch, fp_row_inv_norm included) and per_frame_ms (the
+same rows through FaceTracker.track, one call per frame -- layout a: one FaceTracker per stream), and their ratio.  The two
+apply different rules (greedy one-to-one with expiry against first match); the comparison is of cost, not of answers.
+Then the pipeline: FacePipeline.step on 256 synthetic frames with and without tracker=, and step_overlapped with two_streams
+(the tracker on the side stream) with and without.  Timed with device events after warm-up, `--iters` calls per round,
+`--rounds` rounds; median with min .. max.  Prints one JSON line.  No pass / fail threshold.
+
+  python tools/track_bench.py [--iters 10] [--rounds 5] [--small] [--no-pipeline]
+
+--small: 8 frames per layout, 1 iteration, 2 rounds."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from face_detection_and_recognition_amd import workload as W  # noqa: E402
+from face_detection_and_recognition_amd.face_extraction.face_tracker import FaceTracker  # noqa: E402
+from face_detection_and_recognition_amd.pipeline import FacePipeline  # noqa: E402
+from face_detection_and_recognition_amd.tracking import StreamTracker  # noqa: E402
+
+D = 512
+
+
+def timed(fn, reps, dev):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record(torch.cuda.current_stream(dev))
+    for _ in range(reps):
+        fn()
+    e.record(torch.cuda.current_stream(dev))
+    e.synchronize()
+    return s.elapsed_time(e) / reps
+
+
+def summary(ts):
+    return dict(median=round(statistics.median(ts), 4), min=round(min(ts), 4), max=round(max(ts), 4))
+
+
+def layout_rows(n_streams, n_frames, faces, n_ident, seed, dev):
+    """Rows of one step: frame f of stream s shows `faces` of the stream's n_ident identities, taking turns; every sighting is
+    the identity's unit vector plus noise at a cosine of about 0.95, its box the identity's cell."""
+    rng = np.random.default_rng(seed)
+    B = n_streams * n_frames
+    ident = rng.standard_normal((n_streams, n_ident, D))
+    ident /= np.linalg.norm(ident, axis=2, keepdims=True)
+    frame, boxes, emb = [], [], []
+    for f in range(B):
+        s, t = f % n_streams, f // n_streams
+        for j in range(faces):
+            k = (t * faces + j) % n_ident
+            noise = rng.standard_normal(D)
+            frame.append(f)
+            emb.append(ident[s, k] + 0.33 * noise / np.linalg.norm(noise))
+            x, y = 100 * (k % 8), 100 * (k // 8)
+            boxes.append([x, y, x + 60, y + 60])
+    emb = np.asarray(emb, np.float32)
+    emb /= np.linalg.norm(emb, axis=1, keepdims=True)
+    to = lambda a, dt: torch.from_numpy(np.asarray(a, dt)).to(dev)      # noqa: E731
+    return dict(frame=to(frame, np.int32), boxes=to(boxes, np.float32), emb=to(emb, np.float32),
+                sof=to(np.arange(B) % n_streams, np.int32), B=B, faces=faces, n_streams=n_streams)
+
+
+def measure_layout(name, rows, max_age, args, dev):
+    tr = StreamTracker(rows["n_streams"], D, max_age, device=dev)
+    step = lambda: tr.step(rows["frame"], rows["boxes"], rows["emb"], rows["sof"])     # noqa: E731
+    olds = [FaceTracker("MOBILE_FACENET", D, dev, max_faces=64) for _ in range(rows["n_streams"])]
+    ib = rows["boxes"].to(torch.int32)
+    per = [(olds[f % rows["n_streams"]], rows["emb"][f * rows["faces"]:(f + 1) * rows["faces"]],
+            ib[f * rows["faces"]:(f + 1) * rows["faces"]]) for f in range(rows["B"])]
+
+    def loop():
+        for t, e, b in per:
+            t.track(e, b)
+    out = step()
+    step()
+    loop()
+    torch.cuda.synchronize()
+    live = int((tr.state["slot_i"][:, :, 0] != 0).sum().item())
+    rec = dict(name=name, streams=rows["n_streams"], frames=rows["B"], rows=int(rows["frame"].shape[0]), live_tracks=live,
+               new_rows_first_step=int((out["track_flags"] & 1).ne(0).sum().item()))
+    rec["tracklets_ms"] = summary([timed(step, args.iters, dev) for _ in range(args.rounds)])
+    rec["per_frame_ms"] = summary([timed(loop, max(1, args.iters // 5), dev) for _ in range(args.rounds)])
+    rec["per_frame_over_tracklets"] = round(rec["per_frame_ms"]["median"] / rec["tracklets_ms"]["median"], 2)
+    return rec
+
+
+def measure_pipeline(n_frames, args, dev):
+    frames = W.make_frames(n_frames, dev)
+    det = W.build_detector(dev, W.make_frames(min(64, n_frames), dev, seed=999))
+    emb = W.build_embedder(dev)
+    ref = W.make_reference(256, dev)
+    rec = dict(frames=n_frames)
+    for two in (False, True):
+        for with_tracker in (False, True):
+            tr = StreamTracker(1, D, 8, device=dev) if with_tracker else None
+            pipe = FacePipeline(det, emb, ref, tau=0.0, two_streams=two, tracker=tr)
+            if two:
+                def fn():
+                    pipe.step_overlapped(frames)
+            else:
+                def fn():
+                    pipe.step(frames)
+            for _ in range(3):
+                fn()
+            if two:
+                pipe.flush()
+            torch.cuda.synchronize()
+            ts = [timed(fn, args.iters, dev) for _ in range(args.rounds)]
+            if two:
+                rec["n_faces"] = pipe.flush()["n_faces"]
+            torch.cuda.synchronize()
+            rec[("overlapped_" if two else "step_") + ("tracker_ms" if with_tracker else "plain_ms")] = summary(ts)
+    for k in ("step", "overlapped"):
+        rec[k + "_tracker_cost_ms"] = round(rec[k + "_tracker_ms"]["median"] - rec[k + "_plain_ms"]["median"], 4)
+    return rec
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--small", action="store_true")
+    ap.add_argument("--no-pipeline", dest="pipeline", action="store_false")
+    args = ap.parse_args(argv)
+    dev = torch.device("cuda:0")
+    if args.small:
+        args.iters, args.rounds = 1, 2
+    F = 8 if args.small else 256
+    out = dict(bench="track", small=bool(args.small), iters=args.iters, rounds=args.rounds, D=D, layouts=[])
+    out["layouts"].append(measure_layout("a", layout_rows(F, 1, 2, 2, 1, dev), 8, args, dev))
+    out["layouts"].append(measure_layout("b", layout_rows(1, F, 2, 2, 2, dev), 8, args, dev))
+    out["layouts"].append(measure_layout("c", layout_rows(1, F, 8, 32, 3, dev), 8, args, dev))
+    if args.pipeline:
+        out["pipeline"] = measure_pipeline(F, args, dev)
+    print(json.dumps(out))
+    return out
+
+
+if __name__ == "__main__":
+    main()

@@ -71,7 +71,8 @@ class FpFrameDesc(C.Structure):
 FRAME_MIN_W, FRAME_MAX_W, FRAME_MAX_H = 3, 32767, 65535   # fp_frame_desc sizes the ragged kernels take
 RAGGED_U8, RAGGED_F32_LUT = 0, 1                           # fp_resize_ragged output modes
 TOPK_MAX = 16                                              # FP_TOPK_MAX: largest k of fp_cosine_topk_x6
-DBSCAN_MAX_MIN_SAMPLES = 64                                # largest min_samples of fp_cosine_dbscan_x6
+COARSE_MAX, QUANT_MAX_D = 64, 1024                         # FP_COARSE_MAX: largest pool of fp_cosine_topk_i8; FP_QUANT_MAX_D
+DBSCAN_MAX_MIN_SAMPLES = 64                               # largest min_samples of fp_cosine_dbscan_x6
 PAIRHIST_MAX_BINS = 1024                                   # FP_PAIRHIST_MAX_BINS: most bins of fp_pair_histogram_x6
 ALIGN_SIZE, ALIGN_DEGENERATE = 112, 1                      # fp_align_warp canvas side, fp_dets_to_crops_aligned flag
 DETEVAL_MAX_THRS, DETEVAL_MAX_RECS = 31, 1024              # FP_DETEVAL_MAX_*: IoU / recall thresholds fp_det_match / fp_pr_accumulate take
@@ -187,6 +188,11 @@ SIGNATURES = {
     "fp_cosine_filter_x6": (_I, [_P, _P, _I64, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P]),
     "fp_cosine_topk_workspace": (_SZ, [_I64, _I, _I, _I]),
     "fp_cosine_topk_x6": (_I, [_P, _P, _I64, _P, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "fp_quant_i8_bytes": (_SZ, [_I, _I]),
+    "fp_quantize_rows_i8": (_I, [_P, _I, _I, _P, _P, _P]),
+    "fp_cosine_topk_i8_workspace": (_SZ, [_I64, _I, _I, _I]),
+    "fp_cosine_topk_i8": (_I, [_P, _P, _I64, _P, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "fp_rerank_topk": (_I, [_P, _P, _I64, _I, _P, _I, _P, _P, _P, _I, _I, _P, _P, _P]),
     "fp_topk_vote": (_I, [_P, _P, _I64, _I, _P, _I, _F, _I, _P, _P, _P, _P]),
     "fp_cosine_dbscan_workspace": (_SZ, [_I64, _I]),
     "fp_cosine_dbscan_x6": (_I, [_P, _P, _P, _I64, _I, _F, _I, _P, _P, _P, _P, _P, _SZ, _P]),

@@ -26,6 +26,10 @@ __device__ __forceinline__ float cw_key_score(unsigned long long key) {
 }
 __device__ __forceinline__ int cw_key_index(unsigned long long key) { return (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull)); }
 
+// The final merge of the searches that keep cw_key lists (sim.hip: topk_merge_kernel, one wave per row: the k <= 64 largest of a
+// row's cnt keys, unpacked), shared with the int8 coarse search (simi8.hip).
+int fp_launch_topk_merge(const uint64_t* partial, int64_t M, int cnt, int k, float* scores, int32_t* idx, hipStream_t s);
+
 // A zero inverse norm is the library's mask (a dead row, the padding): as a NaN factor every score it enters compares false.
 __device__ __forceinline__ float cw_nan_if_zero(float inv) { return inv == 0.f ? __builtin_nanf("") : inv; }
 

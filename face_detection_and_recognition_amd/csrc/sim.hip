@@ -613,6 +613,18 @@ int fp_cosine_topk_x6(const float* Q, const float* qinv, int64_t M, const void* 
   return FP_OK;
 }
 
+}  // extern "C"
+
+// topk_merge_kernel for the other searches that keep cw_key lists (simi8.hip): cnt keys per row, the k <= 64 largest unpacked.
+int fp_launch_topk_merge(const uint64_t* partial, int64_t M, int cnt, int k, float* scores, int32_t* idx, hipStream_t s) {
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)fp_ceil_div(M, 4)), dim3(256), 0, s, (const unsigned long long*)partial, (long)M,
+                     cnt, k, scores, idx);
+  FP_CHECK_LAUNCH();
+  return FP_OK;
+}
+
+extern "C" {
+
 int fp_topk_vote(const float* scores, const int32_t* idx, int64_t M, int k, const int32_t* labels, int N, float tau, int mode,
                  int32_t* out_label, float* out_score, int32_t* out_votes, void* stream) {
   if (!scores || !idx || !labels || !out_label || !out_score || !out_votes) return FP_ERR_INVALID_ARG;

@@ -3,7 +3,7 @@
 The filter script checks a folder of faces against the ONE class whose name the folder carries; this one asks the recognition
 question.  Every class folder under --rd is enrolled into a FaceGallery (gallery.py; up to -r images per class), every .jpg
 under --ud (flat or nested) is embedded with the same network and preprocess, identified against the gallery (top-k cosine
-search + vote, csrc/sim.hip) and copied to <td>/<class name>/ or <td>/unknown/.  Same networks, weights and argument
+search + vote, csrc/sim.hip; with --coarse int8 the two-stage search of a CompressedGallery, csrc/simi8.hip) and copied to <td>/<class name>/ or <td>/unknown/.  Same networks, weights and argument
 conventions as the filter (embed_images, load_model).  Build-defined: the reference has no counterpart.
 """
 import argparse
@@ -37,8 +37,16 @@ def get_parsed_args(argv=None):
     parser.add_argument('--vote', choices=["top1", "majority"], default="top1")
     parser.add_argument('--preprocess', choices=["mobile_facenet", "tf_standardize"], default=None,
                         help='(default: mobile_facenet with --net mobile_facenet, tf_standardize with facenet)')
+    parser.add_argument('--coarse', choices=["int8"], default=None,
+                        help='search a CompressedGallery: an int8 coarse pass over every row, then an exact rerank of --pool '
+                             'candidates (default: off, the exact FaceGallery search)')
+    parser.add_argument('--pool', type=int, default=None, help='candidates the coarse pass keeps per face (default: min(64, 4k))')
+    parser.add_argument('--rows', choices=["device", "host", "none"], default="device",
+                        help='with --coarse: where the fp32 rows of the rerank live; none = coarse scores only (approximate)')
     parser.add_argument('-d', '--device', default="cuda")
     args = parser.parse_args(argv)
+    if args.coarse is None and (args.pool is not None or args.rows != "device"):
+        parser.error("--pool and --rows need --coarse int8")
     if args.preprocess is None:
         args.preprocess = "tf_standardize" if args.net == "facenet" else "mobile_facenet"
     if args.savedmodel_path is None:
@@ -67,7 +75,10 @@ def enrol_reference(model, reference_root, args):
             labels += [label] * len(paths)
     if not feats:
         raise Exception(f"no reference .jpg under {reference_root}")
-    return FaceGallery(torch.cat(feats), torch.tensor(labels, dtype=torch.int32), names, device=feats[0].device)
+    gallery = FaceGallery(torch.cat(feats), torch.tensor(labels, dtype=torch.int32), names, device=feats[0].device)
+    if getattr(args, "coarse", None) == "int8":
+        gallery = gallery.compress(rows=None if args.rows == "none" else args.rows)
+    return gallery
 
 
 def identify_images(model, gallery, paths, args):
@@ -75,7 +86,8 @@ def identify_images(model, gallery, paths, args):
     if not paths:
         return []
     feats = embed_images(model, paths, args.batch_size, preprocess=args.preprocess)
-    res = gallery.identify(feats, k=min(args.top_k, 16), tau=args.tau, vote=args.vote)
+    kw = dict(pool=args.pool) if getattr(args, "coarse", None) == "int8" else {}
+    res = gallery.identify(feats, k=min(args.top_k, 16), tau=args.tau, vote=args.vote, **kw)
     return [gallery.name_of(l) for l in res["label"].cpu().tolist()]
 
 

@@ -6,6 +6,7 @@
       face_detection_and_extraction/face_extraction/extract_and_label_faces_from_dataset.py:106)
   cosine_topk / topk_vote    — the k best gallery rows of every query and the identity they vote for (build-defined)
 """
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -98,6 +99,131 @@ def cosine_topk(Q, G, k, qinv=None, ginv=None, g3=None, n_splits=0):
     ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.int64, device=dev)
     L.check(lib.fp_cosine_topk_x6(L.ptr(Q), L.ptr(qinv), M, L.ptr(g3), L.ptr(ginv), N, D, k, int(n_splits), L.ptr(scores),
                                   L.ptr(idx), L.ptr(ws), ws.numel() * 8, L.current_stream(dev)), "fp_cosine_topk_x6")
+    return scores, idx
+
+
+# ---- the compressed gallery: int8 coarse search + exact rerank (csrc/simi8.hip, DESIGN S7 "Compressed gallery") -------------
+def pad_features64(x):
+    """x (M, D) with D zero-padded to the next multiple of 64 (one k-slab of the i8 MFMA).  x itself when D already is one."""
+    D = x.shape[1]
+    return x if D % 64 == 0 else torch.nn.functional.pad(x, (0, 64 - D % 64)).contiguous()
+
+
+def quantize_rows_i8(X):
+    """X (N, D) fp32 on the device -> q8 (D64 / 64, round_up(N, 128), 64) int8, the staged layout of the coarse search with zero
+    rows in the padding, and scale (N,) fp32.  Per row q = rint(x * (127 / amax)), scale = amax / 127; a row that is all zero
+    or holds a non-finite value is dead (q = 0, scale = 0).  Equal to quantize_rows_i8_numpy byte for byte, bit for bit."""
+    X = pad_features64(_f32c(X))
+    N, D = X.shape
+    if D > L.QUANT_MAX_D:
+        raise ValueError(f"{D} features: the int8 search takes at most {L.QUANT_MAX_D} (the int32 dot must convert to fp32 exactly)")
+    lib = L.load()
+    q8 = torch.empty((D // 64, lib.fp_quant_i8_bytes(N, D) // D, 64), dtype=torch.int8, device=X.device)
+    scale = torch.empty((N,), dtype=torch.float32, device=X.device)
+    L.check(lib.fp_quantize_rows_i8(L.ptr(X), N, D, L.ptr(q8), L.ptr(scale), L.current_stream(X.device)), "fp_quantize_rows_i8")
+    return q8, scale
+
+
+def stage_rows_i8(q):
+    """q (N, D) int8 codes, D a multiple of 64 -> the staged layout of quantize_rows_i8 (plain tensor moves; for tests and tools
+    that bring their own codes)."""
+    N, D = q.shape
+    assert q.dtype == torch.int8 and D % 64 == 0
+    out = torch.zeros((D // 64, (N + 127) // 128 * 128, 64), dtype=torch.int8, device=q.device)
+    out[:, :N] = q.reshape(N, D // 64, 64).permute(1, 0, 2)
+    return out
+
+
+def unstage_rows_i8(q8, N):
+    """The inverse of stage_rows_i8: (N, D) int8."""
+    return q8[:, :N].permute(1, 0, 2).reshape(N, -1).contiguous()
+
+
+def quantize_rows_i8_numpy(X):
+    """The restatement of quantize_rows_i8 in numpy fp32: X (N, D) -> q (N, D64) int8 row-major, scale (N,) fp32."""
+    X = np.asarray(X, np.float32)
+    if X.shape[1] % 64:
+        X = np.pad(X, ((0, 0), (0, 64 - X.shape[1] % 64)))
+    with np.errstate(all="ignore"):
+        amax = np.abs(X).max(axis=1)
+        dead = ~np.isfinite(X).all(axis=1) | (amax == 0)
+        safe = np.where(dead, np.float32(1), amax).astype(np.float32)
+        r = (np.float32(127) / safe).astype(np.float32)
+        y = np.rint((X * r[:, None]).astype(np.float32))
+        y = np.clip(np.where(np.isnan(y), np.float32(0), y), -127, 127)
+        q = y.astype(np.int8)
+        q[dead] = 0
+        scale = np.where(dead, np.float32(0), (safe / np.float32(127)).astype(np.float32)).astype(np.float32)
+    return q, scale
+
+
+def cosine_topk_i8(qq, u, g8, w, N, pool, n_splits=0):
+    """The coarse search.  qq / g8: staged int8 codes of the M = len(u) queries and the N gallery rows (quantize_rows_i8),
+    u (M,) fp32 positive per-query factors, w (N,) fp32 per-row weights, ANY values: c = fp32(float(int32 dot) * w[n]) orders
+    the rows (higher first, then the LOWER index), the score returned is fp32(c * u[m]).  w == 0 masks a gallery row; a query
+    whose u is not positive and finite is dead.  -> scores (M, pool) fp32 non-increasing, idx (M, pool) int32, -inf / -1 for
+    dead queries and beyond the live rows.  Exactly cosine_topk_i8_numpy, for every n_splits."""
+    assert qq.dtype == torch.int8 and g8.dtype == torch.int8 and qq.is_contiguous() and g8.is_contiguous()
+    assert qq.shape[0] == g8.shape[0], "queries and gallery differ in (padded) features"
+    u, w = _f32c(u), _f32c(w)
+    M, pool, N = u.shape[0], int(pool), int(N)
+    assert w.shape[0] == N and qq.shape[1] == (M + 127) // 128 * 128 and g8.shape[1] == (N + 127) // 128 * 128 and qq.shape[2] == 64
+    D = qq.shape[0] * 64
+    dev = g8.device
+    lib = L.load()
+    scores = torch.empty((M, pool), dtype=torch.float32, device=dev)
+    idx = torch.empty((M, pool), dtype=torch.int32, device=dev)
+    ws_bytes = lib.fp_cosine_topk_i8_workspace(M, N, pool, int(n_splits))
+    ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.int64, device=dev)
+    L.check(lib.fp_cosine_topk_i8(L.ptr(qq), L.ptr(u), M, L.ptr(g8), L.ptr(w), N, D, pool, int(n_splits), L.ptr(scores),
+                                  L.ptr(idx), L.ptr(ws), ws.numel() * 8, L.current_stream(dev)), "fp_cosine_topk_i8")
+    return scores, idx
+
+
+def cosine_topk_i8_numpy(qq, u, qg, w, pool):
+    """The restatement of cosine_topk_i8: qq (M, D) / qg (N, D) int8 ROW-MAJOR codes, u (M,), w (N,) fp32."""
+    qq, qg = np.asarray(qq), np.asarray(qg)
+    u, w = np.asarray(u, np.float32), np.asarray(w, np.float32)
+    M, N = qq.shape[0], qg.shape[0]
+    dots = qq.astype(np.float64) @ qg.astype(np.float64).T             # integers below 2^53: exact
+    with np.errstate(all="ignore"):
+        c = (dots.astype(np.float32) * w[None, :]).astype(np.float32)
+        live_q = (u > 0) & np.isfinite(u)
+        out = ~live_q[:, None] | (w == 0)[None, :] | np.isnan(c)
+        c = np.where(out, -np.inf, c).astype(np.float32)
+        order = np.argsort(-c, axis=1, kind="stable")[:, :pool]         # stable: the lower index first on equal scores
+        cs = np.take_along_axis(c, order, 1)
+        gone = np.take_along_axis(out, order, 1)
+        scores = np.where(gone, -np.inf, (cs * u[:, None]).astype(np.float32)).astype(np.float32)
+        idx = np.where(gone, -1, order).astype(np.int32)
+    if N < pool:
+        scores = np.pad(scores, ((0, 0), (0, pool - N)), constant_values=-np.inf)
+        idx = np.pad(idx, ((0, 0), (0, pool - N)), constant_values=-1)
+    return scores, idx
+
+
+def rerank_topk(Q, cand, k, G=None, ginv=None, qinv=None, rows=None):
+    """The exact scores of a candidate list.  Q (M, D) fp32, cand (M, pool) int32 gallery rows (-1 and rows whose ginv is 0 are
+    skipped), ginv (N,) -> scores (M, k) descending, idx (M, k) int32 gallery rows, -inf / -1 behind the valid ones.  The fp32
+    rows come from G (N, D64) on the device, or from rows (M, pool, D64): the candidates' rows gathered in the order of cand
+    (a gallery whose rows live on the host).  score = <Q, row> * qinv * ginv in fp32 with a fixed summation order: both
+    modes and every run give the same bits.  D64: the features zero-padded to a multiple of 64 (pad_features64)."""
+    Q = pad_features64(_f32c(Q))
+    M, D = Q.shape
+    cand = cand.contiguous()
+    assert cand.dtype == torch.int32 and cand.shape[0] == M and (G is None) != (rows is None) and ginv is not None
+    pool, k = cand.shape[1], int(k)
+    src = _f32c(G if rows is None else rows)
+    assert src.shape[-1] == D and (rows is None or tuple(src.shape) == (M, pool, D))
+    ginv = _f32c(ginv)
+    assert rows is not None or src.shape[0] == ginv.shape[0]
+    qinv = row_inv_norm(Q) if qinv is None else _f32c(qinv)
+    dev = Q.device
+    scores = torch.empty((M, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((M, k), dtype=torch.int32, device=dev)
+    L.check(L.load().fp_rerank_topk(L.ptr(Q), L.ptr(qinv), M, D, L.ptr(cand), pool, L.ptr(src) if rows is None else None,
+                                    None if rows is None else L.ptr(src), L.ptr(ginv), ginv.shape[0], k, L.ptr(scores),
+                                    L.ptr(idx), L.current_stream(dev)), "fp_rerank_topk")
     return scores, idx
 
 

@@ -648,6 +648,46 @@ int fp_cosine_topk_x6(const float* Q, const float* qinv, int64_t M, const void* 
                       int n_splits, float* scores, int32_t* idx, void* workspace, size_t ws_bytes, void* stream);
 
 /*
+ * Compressed gallery (build-defined, DESIGN S7 "Compressed gallery"): an int8 coarse search over everything and an exact
+ * rerank of a short candidate list.  Additions to ABI 14.
+ *
+ * fp_quantize_rows_i8: X [N][D] fp32, D a multiple of 64 and <= FP_QUANT_MAX_D.  Per row: amax = max |x|; a row with amax == 0
+ * or a non-finite value is dead (q = 0, scale = 0); else r = 127 / amax, q = int8(rint(x * r)) (one fp32 multiply, round half
+ * to even, clamped to +-127), scale = amax / 127.  q8 holds fp_quant_i8_bytes(N, D) bytes in the layout
+ * [D / 64][round_up(N, 128)][64] int8 with zero rows in the padding, scale [N] fp32.  16-byte aligned X and q8.
+ *
+ * fp_cosine_topk_i8: per query row the `pool` best gallery rows by coarse score.  Q8 = the codes of the M query rows, G8
+ * those of the N gallery rows (both from fp_quantize_rows_i8).  c[m][n] = float(dot_i32(Q8[m], G8[n])) * w[n] in one rounding
+ * (|dot| <= 1024 * 127^2 < 2^24); rows are ordered by c, higher first, then the LOWER index; the score written is c * u[m].
+ * w[n] == 0 masks gallery row n (dead, removed); a query row whose u is not a positive finite number is dead: all its slots
+ * are -inf / -1, as are the slots beyond the live rows.  scores [M][pool] fp32, idx [M][pool] int32.  n_splits and the
+ * workspace as fp_cosine_topk_x6 (fp_cosine_topk_i8_workspace bytes, 8-byte aligned); the result is the same for every
+ * n_splits.  1 <= pool <= FP_COARSE_MAX.  w must be 16-byte aligned.  Galleries of 65 536 rows and more are searched in several
+ * passes over growing prefixes of the rows, each handing the next a lower bound per query through `scores` (which therefore
+ * holds intermediate values until the call's last kernel has run); the result is that of one pass.
+ *
+ * fp_rerank_topk: the exact scores of the candidates.  cand [M][pool] int32 gallery rows; -1 (or any index outside 0 .. N-1)
+ * and rows with ginv == 0 are skipped, the others are distinct.  score = dot_fp32(Q[m], row) * qinv[m] * ginv[cand], the dot
+ * summed in a fixed order (two runs agree bit for bit); the k best by (score descending, index ascending) to scores [M][k],
+ * idx [M][k] (gallery rows), -inf / -1 behind them.  The fp32 rows come from G [N][D] (rows == NULL) or, for a gallery whose
+ * rows stay on the host, from the compact block rows [M][pool][D] gathered in the order of cand (G == NULL); exactly one of
+ * the two is given and both modes compute the same bits.  1 <= k <= min(pool, FP_TOPK_MAX), pool <= FP_COARSE_MAX.
+ *
+ * Refusals, before any launch: a NULL pointer, D > FP_QUANT_MAX_D, pool or k out of range, k > pool, N <= 0, n_splits < 0, a
+ * workspace that is too small: FP_ERR_INVALID_ARG; D % 64 or a misaligned pointer: FP_ERR_ALIGNMENT.  M == 0: FP_OK,
+ * nothing launched.
+ */
+#define FP_COARSE_MAX 64
+#define FP_QUANT_MAX_D 1024
+size_t fp_quant_i8_bytes(int N, int D);
+int fp_quantize_rows_i8(const float* X, int N, int D, void* q8, float* scale, void* stream);
+size_t fp_cosine_topk_i8_workspace(int64_t M, int N, int pool, int n_splits);
+int fp_cosine_topk_i8(const void* Q8, const float* u, int64_t M, const void* G8, const float* w, int N, int D, int pool,
+                      int n_splits, float* scores, int32_t* idx, void* workspace, size_t ws_bytes, void* stream);
+int fp_rerank_topk(const float* Q, const float* qinv, int64_t M, int D, const int32_t* cand, int pool, const float* G,
+                   const float* rows, const float* ginv, int N, int k, float* scores, int32_t* idx, void* stream);
+
+/*
  * Identity of every row of a top-k result (one thread per row).  labels [N] int32: the label of every gallery row.  A
  * candidate counts when its index is >= 0 and its score >= tau.  mode 0 (top-1): the label of the best candidate if it
  * counts, else -1.  mode 1 (majority): the label with the most counting candidates; ties go to the larger summed score, then

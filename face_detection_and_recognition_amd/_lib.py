@@ -124,6 +124,7 @@ QUALITY_EMPTY, QUALITY_BAD_FRAME, QUALITY_NO_LAPLACIAN, QUALITY_TOO_LARGE, QUALI
 TRACK_SLOTS, TRACK_MAX_DETS, TRACK_MAX_DIM, TRACK_MAX_ROWS = 64, 64, 1024, 1 << 30                     # FP_TRACK_*
 TRACK_SLOT_INTS, TRACK_SLOT_FLOATS = 5, 10                                # columns of fp_track_state.slot_i / slot_f
 TRACK_NEW, TRACK_BEST, TRACK_DEAD_ROW, TRACK_FULL, TRACK_NO_STREAM, TRACK_OVER = 1, 2, 4, 8, 16, 32   # track_flags bits
+MOT_MAX_ROWS, MOT_STATE_ROWS = 64, 6   # FP_MOT_MAX_ROWS: rows of one frame fp_mot_match takes; int32 rows of its per-id state
 
 
 class FpTrackState(C.Structure):
@@ -141,6 +142,7 @@ _I = C.c_int
 _F = C.c_float
 _SZ = C.c_size_t
 _I64 = C.c_int64
+_D = C.c_double
 
 # name -> (restype, argtypes); every symbol declared in include/facepath.h
 SIGNATURES = {
@@ -245,6 +247,10 @@ SIGNATURES = {
     "fp_tracklets_step": (_I, [C.POINTER(FpTrackState), _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P]),
     "fp_tracklets_step_emulate": (_I, [C.POINTER(FpTrackState), _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _F, _F, _F, _P, _P, _P,
                                        _P]),
+    "fp_mot_match_workspace": (_SZ, [_I64, _I64]),
+    "fp_mot_match": (_I, [_P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I64, _D, _P, _P, _P, _P, _P, _SZ, _P]),
+    "fp_mot_match_emulate": (_I, [_P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I64, _D, _P, _P, _P, _P, _P,
+                                  _SZ]),
 }
 
 _lib = None

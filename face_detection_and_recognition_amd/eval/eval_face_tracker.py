@@ -1,0 +1,183 @@
+"""``python -m face_detection_and_recognition_amd.eval.eval_face_tracker data/ --tracks hyp/`` or
+``... data/ --model synthetic --max_age 30 [--sweep max_age=5,15,30]``
+
+Scores a face tracker on labelled video with CLEAR-MOT (MOTA, MOTP, IDSW, Frag, MT / PT / ML) and the identity measures
+(IDF1, IDP, IDR): tracking_eval.py, the kernel of csrc/moteval.hip on a HIP device, numpy with ``-d cpu``; DESIGN.md
+section 7 "Tracker evaluation".  Build-defined: the reference calls no tracking scorer; parity with TrackEval /
+py-motmetrics is unpinned.
+
+``data`` is a folder of sequences, each a folder with ``gt.txt`` (MOTChallenge rows ``frame,id,x,y,w,h,...``, frames 1-based)
+and ``frames/*.jpg`` (sorted by name = video order).  The hypotheses are either
+
+  * ``--tracks DIR``: ``DIR/<sequence>.txt`` in the same format (a sequence without a file has no hypotheses), or
+  * a model plus ``--max_age`` (and ``--tau_near / --tau_far / --iou_min``): FacePipeline(tracker=StreamTracker) runs over the
+    frames, one stream per sequence, and every step's rows go to a TrackingEvaluator on the device.
+
+``--sweep key=v1,v2,...`` (key: max_age, tau_near, tau_far or iou_min) repeats the run per value and prints one combined row
+each.  Prints the table (one line per sequence and the combined line) and returns the result (a list of (value, result)
+under --sweep).  The thresholds' defaults are the reference's numbers restated as cosines; max_age has no default.
+"""
+import argparse
+import glob
+import os
+
+import numpy as np
+
+from ..tracking import IOU_MIN, TAU_FAR, TAU_NEAR
+from ..tracking_eval import TrackingEvaluator, mot_eval, read_mot_txt
+
+SWEEP_KEYS = dict(max_age=int, tau_near=float, tau_far=float, iou_min=float)
+
+
+def load_sequences(root):
+    """-> list of dict(name, gt (read_mot_txt), frames (sorted .jpg paths), n_frames) for every folder of root with a gt.txt.
+    n_frames is the number of .jpg files, or without a frames folder the last labelled frame + 1."""
+    seqs = []
+    for name in sorted(os.listdir(root)):
+        gt_path = os.path.join(root, name, "gt.txt")
+        if not os.path.isfile(gt_path):
+            continue
+        gt = read_mot_txt(gt_path)
+        frames = sorted(glob.glob(os.path.join(root, name, "frames", "*.jpg")))
+        n_frames = len(frames) if frames else (int(gt["frame"].max()) + 1 if len(gt["frame"]) else 0)
+        if len(gt["frame"]) and (gt["frame"].min() < 0 or gt["frame"].max() >= n_frames):
+            raise ValueError(f"{gt_path}: frame numbers outside 1 .. {n_frames}")
+        seqs.append(dict(name=name, gt=gt, frames=frames, n_frames=n_frames))
+    if not seqs:
+        raise ValueError(f"no sequence (a folder with gt.txt) under {root}")
+    return seqs
+
+
+def stack_rows(per_seq):
+    """A list of read_mot_txt dicts (None: no rows), one per sequence -> (seq, frame, id, boxes) arrays."""
+    seq, frame, ids, boxes = [], [], [], []
+    for s, rows in enumerate(per_seq):
+        if rows is None:
+            continue
+        seq.append(np.full(len(rows["frame"]), s, np.int64))
+        frame.append(rows["frame"])
+        ids.append(rows["id"])
+        boxes.append(rows["boxes"])
+    if not seq:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros((0, 4))
+    return np.concatenate(seq), np.concatenate(frame), np.concatenate(ids), np.concatenate(boxes)
+
+
+def ground_truth(seqs):
+    return stack_rows([s["gt"] for s in seqs]) + (np.array([s["n_frames"] for s in seqs], np.int64),)
+
+
+def score_tracks(seqs, tracks_dir, thr, device):
+    hyp = []
+    for s in seqs:
+        path = os.path.join(tracks_dir, s["name"] + ".txt")
+        hyp.append(read_mot_txt(path) if os.path.isfile(path) else None)
+        if hyp[-1] is not None and len(hyp[-1]["frame"]) and hyp[-1]["frame"].max() >= s["n_frames"]:
+            s["n_frames"] = int(hyp[-1]["frame"].max()) + 1 if not s["frames"] else s["n_frames"]
+    gt = ground_truth(seqs)
+    return mot_eval(*gt[:4], *stack_rows(hyp), gt[4], thr=thr, device=device)
+
+
+def build_parts(seqs, args, dev):
+    """(detector, embedder) on the synthetic weights, the detector's scores calibrated on the first frames; built once per
+    sweep."""
+    from .. import workload as W
+    from ..modules.utils.jpeg import imread_batch
+    if args.model != "synthetic":
+        raise ValueError("only --model synthetic is wired here; build a FacePipeline(..., tracker=StreamTracker(...)) for real "
+                         "weights and feed a TrackingEvaluator from its steps")
+    first = next((s["frames"] for s in seqs if s["frames"]), None)
+    if first is None:
+        raise ValueError("no frames/*.jpg in any sequence: nothing to run the tracker on (use --tracks)")
+    return W.build_detector(dev, imread_batch(first[:8], dev), cand_per_frame=48), W.build_embedder(dev)
+
+
+def run_tracker(seqs, args, dev, parts):
+    """The pipeline over every sequence's frames, batch by batch, one stream per sequence -> MotResult."""
+    import torch
+    from ..modules.utils.jpeg import imread_batch
+    from ..pipeline import FacePipeline
+    from ..tracking import StreamTracker
+    det, emb = parts
+    tracker = StreamTracker(len(seqs), emb.embedding_size, args.max_age, args.tau_near, args.tau_far, args.iou_min, device=dev)
+    pipe = FacePipeline(det, emb, None, tracker=tracker)
+    ev = TrackingEvaluator(len(seqs), dev, thr=args.thr).set_ground_truth(*ground_truth(seqs))
+    for s, seq in enumerate(seqs):
+        for lo in range(0, len(seq["frames"]), args.batch_size):
+            frames = imread_batch(seq["frames"][lo:lo + args.batch_size], dev)
+            if not isinstance(frames, torch.Tensor):
+                raise ValueError(f"{seq['name']}: the frames of a video share one size")
+            B = int(frames.shape[0])
+            res = pipe.step(frames, streams=[s] * B)
+            n, info = res["n_faces"], res["info"]
+            ev.add(torch.full((B,), s, dtype=torch.int64), lo, info[:n, 0].to(torch.int32), info[:n, 1:5], res["track_id"][:n])
+    result = ev.evaluate()
+    if ev.dropped:
+        print(f"[WARNING] {ev.dropped} face rows carried no track id (FULL, OVER or dead rows) and were not scored")
+    return result
+
+
+def parse_sweep(text):
+    key, _, values = text.partition("=")
+    if key not in SWEEP_KEYS or not values:
+        raise ValueError(f"--sweep takes key=v1,v2,... with key one of {sorted(SWEEP_KEYS)}")
+    return key, [SWEEP_KEYS[key](v) for v in values.split(",")]
+
+
+def main(argv=None):
+    import torch
+    parser = argparse.ArgumentParser(description="Evaluate face trackers with CLEAR-MOT and IDF1 (MI355X HIP path)")
+    parser.add_argument("data", help="Folder of sequences: <sequence>/gt.txt and <sequence>/frames/*.jpg.")
+    parser.add_argument("--tracks", default=None, help="Folder of hypothesis files <sequence>.txt; no tracker is run.")
+    parser.add_argument("--model", default=None, help="'synthetic' (seeded random weights); trained weights: use the API.")
+    parser.add_argument("--max_age", type=int, default=None, help="Required with --model unless swept: nothing has been measured.")
+    parser.add_argument("--tau_near", type=float, default=TAU_NEAR)
+    parser.add_argument("--tau_far", type=float, default=TAU_FAR)
+    parser.add_argument("--iou_min", type=float, default=IOU_MIN)
+    parser.add_argument("--sweep", default=None, help="key=v1,v2,...: repeat the run per value of max_age / tau_near / tau_far / iou_min.")
+    parser.add_argument("--thr", type=float, default=0.5, help="IoU threshold of a match (default: %(default)s).")
+    parser.add_argument("-b", "--batch_size", type=int, default=256)
+    parser.add_argument("-d", "--device", default="hip", help="hip[:N] / cuda[:N]; cpu (numpy path) with --tracks (default: %(default)s).")
+    args = parser.parse_args(argv)
+    if (args.tracks is None) == (args.model is None):
+        parser.error("give either --tracks DIR or --model")
+    if args.batch_size < 1:
+        parser.error("--batch_size must be positive")
+    device = None if args.device == "cpu" else torch.device(args.device.replace("hip", "cuda"))
+    seqs = load_sequences(args.data)
+    names = [s["name"] for s in seqs]
+    if args.tracks is not None:
+        if args.sweep:
+            parser.error("--sweep needs a tracker to run: use --model")
+        if device is not None and not torch.cuda.is_available():
+            print("[WARNING] no HIP device: scoring the track files with the numpy path")
+            device = None
+        result = score_tracks(seqs, args.tracks, args.thr, device)
+        print(result.summary(names))
+        return result
+    if device is None:
+        raise NotImplementedError("the pipeline has no CPU path: use -d hip, or --tracks with -d cpu")
+    try:
+        key, values = parse_sweep(args.sweep) if args.sweep else (None, [None])
+    except ValueError as e:
+        parser.error(str(e))
+    if args.max_age is None and key != "max_age":
+        parser.error("--max_age is required (it has no default: nothing has been measured)")
+    results, parts = [], build_parts(seqs, args, device)
+    for v in values:
+        if key is not None:
+            setattr(args, key, v)
+        result = run_tracker(seqs, args, device, parts)
+        results.append((v, result))
+        if key is None:
+            print(result.summary(names))
+        else:
+            head, _, last = result.summary(names).partition("\n")
+            if len(results) == 1:
+                print(f"{key:<10}" + head)
+            print(f"{v!s:<10}" + last.splitlines()[-1])
+    return results[0][1] if key is None else results
+
+
+if __name__ == "__main__":
+    main()

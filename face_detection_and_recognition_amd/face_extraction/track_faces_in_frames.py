@@ -9,6 +9,9 @@ highest detector confidence, or with --quality the sharpest crop); at the end <t
 `--model synthetic` (the default: no trained weights ship with the project) runs the seeded random weights of workload.py.
 The thresholds default to the reference's numbers restated as cosines, unmeasured on real video; --max_age has no default.
 Build-defined: the reference labels faces frame by frame (face_tracker.py is that port).
+
+--mot_out FILE also writes every tracked face as a MOTChallenge row `frame,id,x,y,w,h,conf,-1,-1,-1` (frames 1-based in video
+order): a hypothesis file for eval/eval_face_tracker.py --tracks.  Nothing changes without it.
 """
 import argparse
 import glob
@@ -34,6 +37,7 @@ def get_parsed_args(argv=None):
     parser.add_argument('-b', '--batch_size', type=int, default=256)
     parser.add_argument('--jpeg_quality', type=int, default=95)
     parser.add_argument('-d', '--device', default="cuda:0")
+    parser.add_argument('--mot_out', type=str, default=None, help="also write the tracked rows as MOTChallenge text to this file")
     return parser.parse_args(argv)
 
 
@@ -53,8 +57,9 @@ def build_pipeline(args, dev, first_frames):
     return FacePipeline(det, emb, None, quality=True if args.quality else None, tracker=tracker), tracker
 
 
-def track_frames(pipe, paths, batch_size, jpeg_quality=95):
-    """-> (TrackBook, {(stream, id): JPEG bytes of the best row's crop}).  Frames of one size (a video's)."""
+def track_frames(pipe, paths, batch_size, jpeg_quality=95, mot_rows=None):
+    """-> (TrackBook, {(stream, id): JPEG bytes of the best row's crop}).  Frames of one size (a video's).  mot_rows: a list
+    that receives, per batch, (frame numbers, ids, xywh boxes, confidences) of the rows with a track id (numpy)."""
     import torch
     from ..modules.utils.jpeg import encode_crops, imread_batch
     book, shots = TrackBook(), {}
@@ -69,6 +74,11 @@ def track_frames(pipe, paths, batch_size, jpeg_quality=95):
         out = {k: res[k] for k in pipe.TRACK_KEYS}
         book.update(out, info[:n, 0].to(torch.int32), info[:n, 1:5], sof, emb=res["emb"], score=score[:n], frame_base=lo)
         flags, ids = res["track_flags"].cpu().numpy(), res["track_id"].cpu().numpy()
+        if mot_rows is not None:
+            rows = info[:n].cpu().numpy().astype(np.float64)
+            keep = ids[:n] > 0
+            xywh = np.concatenate([rows[:, 1:3], rows[:, 3:5] - rows[:, 1:3]], 1)
+            mot_rows.append((lo + rows[keep, 0].astype(np.int64), ids[:n][keep].astype(np.int64), xywh[keep], rows[keep, 5]))
         best_rows = [i for i in range(n) if flags[i] & BEST and ids[i] > 0]
         if best_rows:                              # the crops of this batch's BEST rows, one device call; a later BEST replaces
             idx = torch.as_tensor(best_rows, device=pipe.dev)
@@ -99,6 +109,13 @@ def save_tracks(target, book, shots, paths):
     return tracks
 
 
+def write_mot_rows(path, mot_rows):
+    """The batches collected by track_frames(mot_rows=) as one MOTChallenge text file."""
+    from ..tracking_eval import write_mot_txt
+    cols = [np.concatenate([r[k] for r in mot_rows]) if mot_rows else np.zeros((0, 4) if k == 2 else 0) for k in range(4)]
+    write_mot_txt(path, cols[0].astype(np.int64), cols[1].astype(np.int64), cols[2], cols[3])
+
+
 def main(argv=None):
     import torch
     from ..modules.utils.jpeg import imread_batch
@@ -109,8 +126,11 @@ def main(argv=None):
         raise Exception(f"no .jpg under {args.frames_path}")
     dev = torch.device(args.device)
     pipe, _ = build_pipeline(args, dev, imread_batch(paths[:8], dev))
-    book, shots = track_frames(pipe, paths, args.batch_size, args.jpeg_quality)
+    mot_rows = [] if args.mot_out else None
+    book, shots = track_frames(pipe, paths, args.batch_size, args.jpeg_quality, mot_rows=mot_rows)
     tracks = save_tracks(args.target_data_path, book, shots, paths)
+    if args.mot_out:
+        write_mot_rows(args.mot_out, mot_rows)
     print(f"{len(tracks)} tracks in {len(paths)} frames -> {os.path.join(args.target_data_path, 'tracks.json')}")
     return tracks
 

@@ -1422,6 +1422,77 @@ int fp_tracklets_step_emulate(const fp_track_state* state, int n_streams, int D,
                               int B, int max_age, float tau_near, float tau_far, float iou_min, int32_t* track_id,
                               int32_t* track_hits, int32_t* track_clock, int32_t* track_flags);
 
+/*
+ * Tracker evaluation: CLEAR-MOT and IDF1 (build-defined, the reference calls no tracking scorer; DESIGN §7 "Tracker
+ * evaluation"; csrc/moteval.hip; tracking_eval.py holds the numpy restatement and the host half).  All additive: ABI 14.
+ *
+ * Inputs.  Ground-truth rows (seq, frame, id, box xywh) and hypothesis rows (seq, frame, id, box xywh); n_seqs, n_frames[seq]
+ * and one IoU threshold thr (default 0.5).  One class, no ignore regions, no distractors.  Ids are arbitrary integers: Python
+ * remaps them to dense 0 .. G_s - 1 / 0 .. H_s - 1 per sequence.  An id twice in one frame of one sequence, or more than
+ * FP_MOT_MAX_ROWS = 64 ground-truth rows or hypothesis rows in one frame of one sequence, is refused in Python (ValueError);
+ * 64 is the wave width and the tracker's FP_TRACK_MAX_DETS.
+ * Order.  Sequences are independent.  The frames of a sequence run 0 .. n_frames - 1 in ascending order, every frame
+ * processed, the empty ones too.  Inside a frame the rows keep the caller's relative order (stable sort by (seq, frame)); a
+ * row's POSITION is its rank in that order.
+ * State.  Per ground-truth id g: last[g] (hypothesis id of its most recent match ever, or none), cur[g] (the hypothesis id it
+ * was matched to in the previous frame of the sequence, or none), counters seen[g], hit[g], runs[g].  Per sequence: TP, FN,
+ * FP, IDSW (int64), sum_iou (fp64), pot[G_s][H_s] (int32).
+ * Per frame, with n ground-truth rows and m hypothesis rows:
+ *   1. sim[i][j] = IoU in fp64: iw = min(ax + aw, bx + bw) - max(ax, bx), ih likewise; 0 if iw <= 0 or ih <= 0, else
+ *      i = iw * ih, i / (aw * ah + bw * bh - i) -- the operations and order of evaluation._iou_matrix.  adm = sim >= thr.
+ *   2. pot[g_i][h_j] += 1 for every admissible pair (all pairs, not one-to-one).
+ *   3. score[i][j] = adm ? sim + (cur[g_i] == h_j ? 1000.0 : 0.0) : 0.0.
+ *   4. Assignment: score padded with zeros to N x N, N = max(n, m); C = -score; the shortest-augmenting-path Hungarian
+ *      method with potentials u, v in fp64, rows inserted in ascending order.  For row i: p[0] = i, j0 = 0, minv[] = inf,
+ *      used[] = false; repeat { used[j0] = true; i0 = p[j0]; delta = inf; for the columns j = 1 .. N not used, ascending:
+ *      cur = (C[i0][j] - u[i0]) - v[j]; if cur < minv[j]: minv[j] = cur, way[j] = j0; if minv[j] < delta: delta = minv[j],
+ *      j1 = j (strict comparisons: the lowest column wins a tie); then for j = 0 .. N: used ? (u[p[j]] += delta, v[j] -= delta)
+ *      : (minv[j] -= delta); j0 = j1 } until p[j0] == 0; then augment: repeat { j1 = way[j0]; p[j0] = p[j1]; j0 = j1 } until
+ *      j0 == 0.  Matched pairs are the assigned (i, j) with i < n, j < m and score[i][j] > 0.
+ *   5. For each matched pair in ascending ground-truth position: IDSW += (last[g] exists and last[g] != h); hit[g] += 1;
+ *      runs[g] += (cur[g] was none before this frame); sum_iou += sim[i][j] (one fp64 addition per match, in this order).
+ *   6. seen[g] += 1 for every ground-truth row; last[g] = h for matched rows; cur[] = none for every id of the sequence, then
+ *      cur[g] = h for matched rows.
+ *   7. TP += k, FN += n - k, FP += m - k, k = number of matches.
+ * Per-row outputs: gt_match [n_gt] int32 = the index of the matched hypothesis row (in the order given to the call), -1
+ * without one; gt_switch [n_gt] uint8.
+ * Derived on the host in fp64 from the integers (tracking_eval.py): MOTA = (TP - FP - IDSW) / (TP + FN), MOTP = sum_iou / TP,
+ * Frag = sum over g of max(runs[g] - 1, 0), MT / PT / ML from hit / seen (> 0.8; >= 0.2 and not MT; the rest) over ids with
+ * seen > 0, precision, recall; IDTP = the maximum over one-to-one assignments of ground-truth ids to hypothesis ids of the
+ * sequence of the sum of pot[g][h] (equal to the published IDFN + IDFP minimum: matching g with h saves 2 pot[g][h]);
+ * IDFN = rows of ground truth - IDTP, IDFP = hypothesis rows - IDTP, IDF1 = IDTP / (IDTP + (IDFN + IDFP) / 2).  The combined
+ * result sums the integers and sum_iou in sequence order, then derives.  -1 where a denominator is 0.
+ * Known departures: parity with TrackEval / py-motmetrics is unpinned; every frame is processed (step 6 always runs, so a
+ * target missed in a frame without any hypothesis starts a new run); admissibility is sim >= thr without an epsilon; no HOTA.
+ *
+ * fp_mot_match: one launch, one workgroup per sequence marching its frames; no global atomics, no scratch, no host
+ * synchronisation; two runs are bit-identical.  A single long sequence is a chain of dependent frames: latency-bound.
+ * Rows sorted by (sequence, frame), stable: gt_boxes [n_gt][4] fp64, gt_id [n_gt] int32 dense per sequence, gt_off
+ * [n_frames + 1] int32 CSR over the global frame index frame_base[seq] + frame; hy_* likewise.  frame_base [n_seqs + 1] int32,
+ * gt_id_base [n_seqs + 1] int32 (prefix sums of G_s), hy_id_count [n_seqs] int32 (H_s), pot_base [n_seqs + 1] int64 (prefix
+ * sums of G_s * H_s); n_frames, n_gt_ids, n_pot: their last entries, as host integers.  Outputs: counts [n_seqs][4] int64 =
+ * TP, FN, FP, IDSW; sum_iou [n_seqs] fp64; gt_match, gt_switch.  workspace (fp_mot_match_workspace(n_gt_ids, n_pot) bytes,
+ * zeroed here) is an output too: six int32 rows of n_gt_ids entries -- last + 1, cur, the stamp of cur, seen, hit, runs --
+ * and behind them pot, n_pot int32.  Every pointer is device memory the host does not read.  Indices read from device
+ * memory are clamped into the arrays.  Refusals (FP_ERR_INVALID_ARG): a NULL pointer that is needed, a negative count, 2^31
+ * or more rows, ids or frames, a NaN thr, a workspace that is too small; FP_ERR_ALIGNMENT: an fp64 / int64 array not 8-byte
+ * aligned, an int32 array not 4-byte aligned.
+ * fp_mot_match_emulate: the same decision code serially on HOST memory (every pointer HOST), the same bits.
+ */
+#define FP_MOT_MAX_ROWS 64
+size_t fp_mot_match_workspace(int64_t n_gt_ids, int64_t n_pot);
+int fp_mot_match(const double* gt_boxes, const int32_t* gt_id, const int32_t* gt_off, int64_t n_gt, const double* hy_boxes,
+                 const int32_t* hy_id, const int32_t* hy_off, int64_t n_hy, const int32_t* frame_base,
+                 const int32_t* gt_id_base, const int32_t* hy_id_count, const int64_t* pot_base, int n_seqs, int64_t n_frames,
+                 int64_t n_gt_ids, int64_t n_pot, double thr, int64_t* counts, double* sum_iou, int32_t* gt_match,
+                 uint8_t* gt_switch, void* workspace, size_t ws_bytes, void* stream);
+int fp_mot_match_emulate(const double* gt_boxes, const int32_t* gt_id, const int32_t* gt_off, int64_t n_gt,
+                         const double* hy_boxes, const int32_t* hy_id, const int32_t* hy_off, int64_t n_hy,
+                         const int32_t* frame_base, const int32_t* gt_id_base, const int32_t* hy_id_count,
+                         const int64_t* pot_base, int n_seqs, int64_t n_frames, int64_t n_gt_ids, int64_t n_pot, double thr,
+                         int64_t* counts, double* sum_iou, int32_t* gt_match, uint8_t* gt_switch, void* workspace,
+                         size_t ws_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,299 @@
+"""Tracker evaluation without a GPU (tracking_eval.py, csrc/moteval.hip's host emulator from the built library): the hand cases
+of DESIGN section 7 on the numpy path, the restated assignment against brute force and (when installed) scipy, the emulator
+against numpy bit for bit, the refusals, the invariances (steps, interleaved sequences, row order), the MOTChallenge text
+round trip and the ABI."""
+import ctypes
+import itertools
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import moteval_cases as MC
+from face_detection_and_recognition_amd import _lib as L
+from face_detection_and_recognition_amd import tracking_eval as TE
+from face_detection_and_recognition_amd.evaluation import _iou_matrix
+
+HAND = MC.hand_cases()
+EMU = MC.emulator_inputs()
+
+
+@pytest.fixture(scope="module")
+def numpy_results():
+    return {name: TE.mot_eval(**data) for name, data in EMU.items()}
+
+
+@pytest.mark.parametrize("name", sorted(HAND))
+def test_hand_case_numpy(name):
+    data, want = HAND[name]
+    res = TE.mot_eval(**data)
+    assert {k: res.combined[k] for k in want} == want
+    assert res.sequences[0]["TP"] == res.combined["TP"] and len(res.sequences) == 1
+    if name == "A":
+        assert res.IDF1 == 0.5 and res.MOTA == 5 / 6 and res.MOTP == 1.0
+        assert list(res.gt_switch) == [0, 0, 0, 1, 0, 0]
+    if name == "B":                         # frame 1 keeps hypothesis 5 (row 2 of the caller's rows), not the closer 6
+        assert list(res.gt_match) == [0, 2] and res.MOTP == pytest.approx(70 / 130)
+    if name == "C":                         # a greedy-by-IoU matcher takes (0, 0) first and ends with TP 1
+        assert list(res.gt_match) == [1, 0]
+        sim = _iou_matrix(data["gt_boxes"], data["hy_boxes"])
+        assert np.allclose(sim, [[.8182, .5385], [.6, .2121]], atol=1e-4)
+    if name == "D":
+        assert list(res.gt_match) == [0, 1, -1, 2, 3] and res.recall == 0.8
+    if name == "F":
+        assert list(res.gt_switch) == [0, 0, 0, 0, 1, 1, 0, 0] and res.IDF1 == 0.5
+
+
+def test_empty_denominators_are_minus_one():
+    res = TE.mot_eval(**MC.make([], [], [3]))
+    assert res.MOTA == res.MOTP == res.IDF1 == res.precision == res.recall == -1.0 and res.TP == 0
+    res = TE.mot_eval(**MC.make([], [], []))
+    assert res.sequences == [] and res.MOTA == -1.0
+    assert "COMBINED" in res.summary()
+
+
+def test_assignment_against_brute_force():
+    """300 seeded matrices, n, m <= 5, entries 0 or in [0.5, 1), some with + 1000: the total of the restated assignment equals
+    the maximum over all one-to-one assignments to 1e-9."""
+    rng = np.random.default_rng(0)
+    for _ in range(300):
+        n, m = int(rng.integers(1, 6)), int(rng.integers(1, 6))
+        score = np.where(rng.random((n, m)) < 0.4, 0.0, rng.uniform(0.5, 1.0, (n, m)))
+        score = score + np.where((score > 0) & (rng.random((n, m)) < 0.25), 1000.0, 0.0)
+        col = TE.assign_max(score)
+        assert len(set(col[col >= 0])) == int((col >= 0).sum())
+        got = sum(score[i, j] for i, j in enumerate(col) if j >= 0)
+        N = max(n, m)
+        pad = np.zeros((N, N))
+        pad[:n, :m] = score
+        best = max(sum(pad[i, perm[i]] for i in range(N)) for perm in itertools.permutations(range(N)))
+        assert abs(got - best) <= 1e-9, (score, col)
+
+
+def _scipy_walk(data, thr=0.5):
+    """The procedure of DESIGN section 7 with scipy's assignment; checks the restated assignment's total frame by frame."""
+    lsa = pytest.importorskip("scipy.optimize").linear_sum_assignment
+    gf, gi, gb = data["gt_frame"], data["gt_id"], data["gt_boxes"]
+    hf, hi, hb = data["hy_frame"], data["hy_id"], data["hy_boxes"]
+    last, cur, runs, seen, hit = {}, {}, {}, {}, {}
+    gids, hids = sorted(set(gi.tolist())), sorted(set(hi.tolist()))
+    pot = np.zeros((len(gids), len(hids)), np.int64)
+    TP = FN = FP = IDSW = 0
+    for f in range(int(data["n_frames"][0])):
+        g, h = np.nonzero(gf == f)[0], np.nonzero(hf == f)[0]
+        new_cur, k = {}, 0
+        if len(g) and len(h):
+            sim = _iou_matrix(gb[g], hb[h])
+            adm = sim >= thr
+            for i, j in zip(*np.nonzero(adm)):
+                pot[gids.index(gi[g[i]]), hids.index(hi[h[j]])] += 1
+            bonus = np.array([[1000.0 if cur.get(gi[a]) == hi[b] else 0.0 for b in h] for a in g])
+            score = np.where(adm, sim + bonus, 0.0)
+            r, c = lsa(score, maximize=True)
+            col = TE.assign_max(score)
+            mine = sum(score[i, j] for i, j in enumerate(col) if j >= 0)
+            assert abs(mine - score[r, c].sum()) <= 1e-9, f
+            for i, j in zip(r, c):
+                if score[i, j] > 0:
+                    a, b = gi[g[i]], hi[h[j]]
+                    IDSW += a in last and last[a] != b
+                    hit[a] = hit.get(a, 0) + 1
+                    runs[a] = runs.get(a, 0) + (a not in cur)
+                    last[a] = new_cur[a] = b
+                    k += 1
+        for a in gi[g]:
+            seen[a] = seen.get(a, 0) + 1
+        cur = new_cur
+        TP, FN, FP = TP + k, FN + len(g) - k, FP + len(h) - k
+    r, c = lsa(-pot)
+    return dict(TP=TP, FN=FN, FP=FP, IDSW=IDSW, Frag=sum(max(v - 1, 0) for v in runs.values()), IDTP=int(pot[r, c].sum()))
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_seeded_sets_against_scipy(seed, numpy_results):
+    data = EMU[f"seed{seed}"]
+    assert int(data["n_frames"][0]) == 40 and len(set(data["gt_id"].tolist())) == 6
+    assert np.bincount(data["hy_frame"]).max() <= 7
+    want = _scipy_walk(data)
+    res = numpy_results[f"seed{seed}"]
+    assert {k: res.combined[k] for k in want} == want
+    if seed == 0:                           # the data is not trivial
+        assert res.IDSW > 0 and res.Frag > 0 and res.FN > 0 and res.FP > 0
+
+
+@pytest.mark.parametrize("name", sorted(EMU))
+def test_emulator_equals_numpy(name, numpy_results, lib):
+    """Integers, gt_match / gt_switch, pot and the bits of sum_iou; seeded sets, 3 x 7, 7 x 3, the full 64 x 64 frame, empty
+    frames, sequences without rows."""
+    MC.assert_same_result(TE.mot_eval_emulate(**EMU[name]), numpy_results[name], name)
+
+
+def test_emulator_many_sequences_in_one_call(lib):
+    data = MC.many_sequences()
+    res = TE.mot_eval(**data)
+    assert len(res.sequences) == 32 and res.sequences[3]["TP"] + res.sequences[3]["FN"] == 0
+    MC.assert_same_result(TE.mot_eval_emulate(**data), res, "many")
+    lines = res.summary().splitlines()
+    assert len(lines) == 34 and lines[-1].startswith("COMBINED")
+
+
+def test_errors():
+    ok = HAND["B"][0]
+    TE.mot_eval(**ok)
+
+    def bad(**kw):
+        with pytest.raises(ValueError):
+            TE.mot_eval(**{**ok, **kw})
+    over = MC.make([(0, 0, i, [10.0 * i, 0, 5, 5]) for i in range(65)], [], [1])
+    with pytest.raises(ValueError, match="more than 64"):
+        TE.mot_eval(**over)
+    TE.mot_eval(**MC.make([(0, 0, i, [10.0 * i, 0, 5, 5]) for i in range(64)], [], [1]))
+    with pytest.raises(ValueError, match="more than 64"):
+        TE.mot_eval(**MC.make([], [(0, 0, i, [10.0 * i, 0, 5, 5]) for i in range(65)], [1]))
+    with pytest.raises(ValueError, match="twice"):
+        TE.mot_eval(**MC.make([(0, 0, 1, MC.B), (0, 0, 1, MC.shifted(200))], [], [1]))
+    with pytest.raises(ValueError, match="twice"):
+        TE.mot_eval(**MC.make([], [(0, 1, 4, MC.B), (0, 0, 4, MC.B), (0, 1, 4, MC.shifted(200))], [2]))
+    TE.mot_eval(**MC.make([(0, 0, 1, MC.B), (1, 0, 1, MC.B)], [], [1, 1]))         # the same id in two sequences is fine
+    bad(gt_boxes=np.zeros((2, 3)))
+    bad(gt_boxes=np.zeros((3, 4)))
+    bad(gt_id=np.zeros(3, np.int64))
+    bad(hy_frame=np.zeros(2, np.int64))
+    bad(gt_id=np.array([1.0, 1.0]))
+    bad(gt_boxes=np.array([MC.B, [0, 0, np.inf, 1]]))
+    bad(hy_boxes=np.array([MC.B, MC.B, [np.nan, 0, 1, 1]]))
+    bad(hy_boxes=np.array([MC.B, MC.B, [0, 0, -1, 1]]))
+    bad(gt_frame=np.array([0, 2]))
+    bad(gt_frame=np.array([-1, 0]))
+    bad(gt_seq=np.array([0, 1]))
+    bad(n_frames=np.array([-1]))
+    bad(thr=float("nan"))
+
+
+def _tracker_steps(data, cuts):
+    """The hypothesis rows of a one-sequence set as pipeline steps: (seq_of_frame, frame_base, frame, boxes_xyxy, track_id) per
+    step, the frames cut at `cuts`; adds rows the evaluator must drop."""
+    n_frames = int(data["n_frames"][0])
+    edges = [0] + list(cuts) + [n_frames]
+    for lo, hi in zip(edges[:-1], edges[1:]):
+        sel = np.nonzero((data["hy_frame"] >= lo) & (data["hy_frame"] < hi))[0]
+        b = data["hy_boxes"][sel]
+        xyxy = np.concatenate([b[:, :2], b[:, :2] + b[:, 2:]], 1)
+        frame = data["hy_frame"][sel] - lo
+        tid = data["hy_id"][sel]
+        # one row without an id and one in an unscored frame (batch index hi - lo)
+        frame = np.concatenate([frame, [0, hi - lo]])
+        xyxy = np.concatenate([xyxy, [[0, 0, 10, 10], [0, 0, 10, 10]]])
+        tid = np.concatenate([tid, [0, 77]])
+        sof = np.concatenate([np.zeros(hi - lo, np.int64), [-1]])
+        yield sof, lo, frame, xyxy, tid
+
+
+def test_evaluator_in_three_steps_equals_one_run(numpy_results):
+    data = EMU["seed2"]
+    ev = TE.TrackingEvaluator(1, "cpu").set_ground_truth(data["gt_seq"], data["gt_frame"], data["gt_id"], data["gt_boxes"],
+                                                        data["n_frames"])
+    for sof, base, frame, xyxy, tid in _tracker_steps(data, (11, 12)):
+        ev.add(torch.from_numpy(sof), base, torch.from_numpy(frame), torch.from_numpy(xyxy), torch.from_numpy(tid))
+    assert ev.dropped == 6
+    res = ev.evaluate()
+    want = numpy_results["seed2"]
+    for key in MC.INT_KEYS:
+        assert res.combined[key] == want.combined[key], key
+    assert abs(res.combined["sum_iou"] - want.combined["sum_iou"]) < 1e-9       # xywh -> xyxy -> xywh rounds the sizes
+    with pytest.raises(ValueError):
+        TE.TrackingEvaluator(1, "cpu").evaluate()
+    with pytest.raises(ValueError):
+        ev.add(torch.zeros(2, dtype=torch.int64), 0, torch.zeros(3, dtype=torch.int64), torch.zeros((2, 4)), torch.zeros(3, dtype=torch.int64))
+
+
+def test_split_anywhere_is_exact_on_integer_boxes():
+    """Boxes on integer pixels survive xyxy: every cut of the frames into steps gives the one-run result, bit for bit."""
+    data = MC.seeded_set(31, n_frames=12, n_targets=3)
+    for key in ("gt_boxes", "hy_boxes"):
+        data[key] = np.round(data[key])
+    want = TE.mot_eval(**data)
+    for cut in range(1, 12):
+        ev = TE.TrackingEvaluator(1, "cpu").set_ground_truth(*(data[k] for k in MC.KEYS[:4]), data["n_frames"])
+        for sof, base, frame, xyxy, tid in _tracker_steps(data, (cut,)):
+            ev.add(torch.from_numpy(sof), torch.arange(base, base + len(sof)), torch.from_numpy(frame), torch.from_numpy(xyxy),
+                   torch.from_numpy(tid))
+        got = ev.evaluate()
+        for key in MC.INT_KEYS:
+            assert got.combined[key] == want.combined[key], (cut, key)
+        assert got.combined["sum_iou"] == want.combined["sum_iou"]
+
+
+def test_interleaved_sequences_equal_each_alone(numpy_results):
+    a, b = EMU["seed1"], EMU["seed4"]
+    both = TE.mot_eval(**MC.combine([a, b], merge_seed=3))
+    for s, name in enumerate(("seed1", "seed4")):
+        alone = numpy_results[name].sequences[0]
+        for key in MC.INT_KEYS:
+            assert both.sequences[s][key] == alone[key], (name, key)
+        assert both.sequences[s]["sum_iou"] == alone["sum_iou"]
+        assert np.array_equal(both.pot[s], numpy_results[name].pot[0])
+    assert both.TP == sum(numpy_results[n].TP for n in ("seed1", "seed4"))
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_row_order_inside_frames_does_not_change_the_integers(seed, numpy_results):
+    """The optimum of every frame of the seeded sets is unique, so the positions do not matter."""
+    got = TE.mot_eval(**MC.permute_within_frames(EMU[f"seed{seed}"], 100 + seed))
+    for key in MC.INT_KEYS:
+        assert got.combined[key] == numpy_results[f"seed{seed}"].combined[key], key
+
+
+def test_idtp_components_and_worst_case():
+    rng = np.random.default_rng(4)
+    lsa = pytest.importorskip("scipy.optimize").linear_sum_assignment
+    for _ in range(20):
+        pot = np.where(rng.random((9, 12)) < 0.25, rng.integers(1, 50, (9, 12)), 0)
+        r, c = lsa(-pot)
+        assert TE._idtp(pot) == int(pot[r, c].sum())
+    assert TE._idtp(np.zeros((0, 5), np.int32)) == 0 and TE._idtp(np.zeros((3, 0), np.int32)) == 0
+    assert len(TE._components(np.eye(4, dtype=np.int32))) == 4
+
+
+def test_mot_txt_round_trip(tmp_path):
+    data = EMU["seed3"]
+    path = tmp_path / "gt.txt"
+    TE.write_mot_txt(path, data["gt_frame"], data["gt_id"], data["gt_boxes"], conf=np.linspace(0, 1, len(data["gt_id"])))
+    first = open(path).readline().split(",")
+    assert len(first) == 10 and first[0] == "1" and first[-3:] == ["-1", "-1", "-1\n"]
+    back = TE.read_mot_txt(path)
+    assert np.array_equal(back["frame"], data["gt_frame"]) and np.array_equal(back["id"], data["gt_id"])
+    assert back["boxes"].tobytes() == data["gt_boxes"].tobytes()
+    assert np.array_equal(back["conf"], np.linspace(0, 1, len(data["gt_id"])))
+    path.write_text("1, 2, 3, 4, 5, 6\n\n2,2,3.5,4,5,6,0.5,-1,-1,-1\n")
+    back = TE.read_mot_txt(path)
+    assert list(back["frame"]) == [0, 1] and list(back["conf"]) == [1.0, 0.5] and back["boxes"][1, 0] == 3.5
+    path.write_text("1,2,3\n")
+    with pytest.raises(ValueError):
+        TE.read_mot_txt(path)
+
+
+def test_abi_constants_and_c_refusals(lib):
+    from conftest import ROOT
+    hdr = open(os.path.join(ROOT, "include", "facepath.h")).read()
+    assert lib.fp_abi_version() == 14 == L.ABI_VERSION
+    assert int(re.search(r"#define FP_MOT_MAX_ROWS (\d+)", hdr).group(1)) == L.MOT_MAX_ROWS == L.TRACK_MAX_DETS
+    for fn in ("fp_mot_match", "fp_mot_match_emulate", "fp_mot_match_workspace"):
+        decl = re.search(r"^(?:int|size_t) %s\((.*?)\);" % fn, hdr, re.S | re.M).group(1)
+        assert len(decl.split(",")) == len(L.SIGNATURES[fn][1]), fn
+    assert lib.fp_mot_match_workspace(5, 12) == (6 * 5 + 12) * 4 and lib.fp_mot_match_workspace(0, 0) == 4
+    assert lib.fp_mot_match_workspace(-1, 0) == 0
+    P = ctypes.c_void_p(4096)      # never dereferenced: every call below is refused first
+
+    def call(fn=lib.fp_mot_match_emulate, gt_off=P, ws=P, ws_bytes=1 << 20, n_gt=5, S=2, thr=0.5, counts=P, gt_box=P, n_ids=5):
+        return fn(gt_box, P, gt_off, n_gt, P, P, P, 5, P, P, P, P, S, 10, n_ids, 25, thr, counts, P, P, P, ws, ws_bytes)
+    assert call(gt_off=None) == L.FP_ERR_INVALID_ARG and call(ws=None) == L.FP_ERR_INVALID_ARG
+    assert call(ws_bytes=(6 * 5 + 25) * 4 - 1) == L.FP_ERR_INVALID_ARG and call(n_gt=-1) == L.FP_ERR_INVALID_ARG
+    assert call(n_gt=1 << 31) == L.FP_ERR_INVALID_ARG and call(S=-1) == L.FP_ERR_INVALID_ARG
+    assert call(thr=float("nan")) == L.FP_ERR_INVALID_ARG and call(counts=None) == L.FP_ERR_INVALID_ARG
+    assert call(gt_box=None) == L.FP_ERR_INVALID_ARG and call(n_ids=-1) == L.FP_ERR_INVALID_ARG
+    assert call(gt_box=ctypes.c_void_p(4100)) == -5               # FP_ERR_ALIGNMENT
+    dev_call = lambda **kw: call(fn=lambda *a: lib.fp_mot_match(*a, None), **kw)   # noqa: E731
+    assert dev_call(gt_off=None) == L.FP_ERR_INVALID_ARG and dev_call(ws_bytes=8) == L.FP_ERR_INVALID_ARG

@@ -123,6 +123,7 @@ QUALITY_EMPTY, QUALITY_BAD_FRAME, QUALITY_NO_LAPLACIAN, QUALITY_TOO_LARGE, QUALI
 
 TRACK_SLOTS, TRACK_MAX_DETS, TRACK_MAX_DIM, TRACK_MAX_ROWS = 64, 64, 1024, 1 << 30                     # FP_TRACK_*
 TRACK_SLOT_INTS, TRACK_SLOT_FLOATS = 5, 10                                # columns of fp_track_state.slot_i / slot_f
+TRACK_MOTION_FLOATS = 20                  # FP_TRACK_MOTION_FLOATS: x, v, p00, p01, p11 of cx, cy, w, h per slot of `motion`
 TRACK_NEW, TRACK_BEST, TRACK_DEAD_ROW, TRACK_FULL, TRACK_NO_STREAM, TRACK_OVER = 1, 2, 4, 8, 16, 32   # track_flags bits
 MOT_MAX_ROWS, MOT_STATE_ROWS = 64, 6   # FP_MOT_MAX_ROWS: rows of one frame fp_mot_match takes; int32 rows of its per-id state
 
@@ -247,6 +248,10 @@ SIGNATURES = {
     "fp_tracklets_step": (_I, [C.POINTER(FpTrackState), _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P]),
     "fp_tracklets_step_emulate": (_I, [C.POINTER(FpTrackState), _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _F, _F, _F, _P, _P, _P,
                                        _P]),
+    "fp_tracklets_step_motion": (_I, [C.POINTER(FpTrackState), _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P,
+                                      _P, _F, _F, _P, _P]),
+    "fp_tracklets_step_motion_emulate": (_I, [C.POINTER(FpTrackState), _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _F, _F, _F, _P, _P,
+                                              _P, _P, _P, _F, _F, _P]),
     "fp_mot_match_workspace": (_SZ, [_I64, _I64]),
     "fp_mot_match": (_I, [_P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I64, _D, _P, _P, _P, _P, _P, _SZ, _P]),
     "fp_mot_match_emulate": (_I, [_P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I64, _D, _P, _P, _P, _P, _P,

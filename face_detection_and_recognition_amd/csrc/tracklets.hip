@@ -15,6 +15,11 @@
 //    No global atomics, no scratch, no host synchronisation: two runs are bit-identical.
 // 2. fp_tracklets_step_emulate: the same __host__ __device__ decision code (liveness, dot product in the device's order, IoU,
 //    admissibility, key) run serially on host memory, std::sort for the keys (the order is total).
+// 3. fp_tracklets_step_motion / _emulate: the same kernel as tracklets_kernel<true> ("Tracklets: motion prediction" in
+//    include/facepath.h).  The slot's four constant-velocity filters (20 floats) and the predicted boxes sit in LDS beside the
+//    slot table; step 1b predicts one (slot, coordinate) per thread on the first 256 threads, the pair phase takes its IoU with
+//    the predicted box, wave 0 updates / opens the filters where it rewrites the slots.  tracklets_kernel<false> is the kernel
+//    of 1: no motion array is read, nothing of it is compiled in.
 #include <limits.h>
 
 #include <algorithm>
@@ -28,13 +33,16 @@ constexpr int SLOTS = FP_TRACK_SLOTS, MAXD = FP_TRACK_MAX_DETS;
 constexpr int TPB = 512, NW = TPB / FP_WAVE;
 constexpr int GL = 16, NG = TPB / GL;   // lanes per pair, pairs in flight
 constexpr int MAXCH = 1024;             // row chunks whose frame range is kept in LDS
-constexpr int NI = FP_TRACK_SLOT_INTS, NF = FP_TRACK_SLOT_FLOATS;
+constexpr int NI = FP_TRACK_SLOT_INTS, NF = FP_TRACK_SLOT_FLOATS, MF = FP_TRACK_MOTION_FLOATS;
 constexpr unsigned long long KEY_NONE = ~0ull;
 static_assert(SLOTS == 64 && MAXD == 64, "one 64-bit mask of tracks and one of detections; slot and position are key bytes");
 
 // slot_i columns / slot_f columns
 enum { I_ID = 0, I_FIRST = 1, I_LAST = 2, I_HITS = 3, I_BEST_CLOCK = 4 };
 enum { F_BOX = 0, F_INV = 4, F_BEST_SCORE = 5, F_BEST_BOX = 6 };
+// motion columns of one coordinate c of (cx, cy, w, h): motion[slot][c * MC + ...]
+enum { M_X = 0, M_V = 1, M_P00 = 2, M_P01 = 3, M_P11 = 4, MC = 5 };
+static_assert(MF == 4 * MC, "four two-state filters per slot");
 
 struct TrackArgs {
   int* hdr;      // [S][2] clock, next_id
@@ -57,6 +65,9 @@ struct TrackArgs {
   int* o_hits;
   int* o_clock;
   int* o_flags;
+  float* motion;        // [S][SLOTS][MF]; null without motion prediction
+  float std_pos, std_vel;
+  float* o_pred;        // [n][4]
 };
 
 // ---------------------------------------------------------------------------------------- the decision code, host and device
@@ -144,12 +155,79 @@ __host__ __device__ __forceinline__ int tk_update_slot(const TrackArgs& p, int* 
   return flags;
 }
 
+// -------------------------------------------------------------------------- motion prediction, host and device (fp32, no contraction)
+__host__ __device__ __forceinline__ float tk_hs(float t) { return t > 1.f ? t : 1.f; }
+__host__ __device__ __forceinline__ bool tk_finite(float t) { return t - t == 0.f; }
+
+// coordinate c of the measurement (cx, cy, w, h) of a box x1 y1 x2 y2
+__host__ __device__ __forceinline__ float tk_measure(const float* b, int c) { return c < 2 ? 0.5f * (b[c] + b[c + 2]) : b[c] - b[c - 2]; }
+
+__host__ __device__ __forceinline__ void tk_motion_init(const TrackArgs& p, float* m, const float* b) {
+  const float H = tk_hs(tk_measure(b, 3));
+  const float sp = (2.f * p.std_pos) * H, sv = (10.f * p.std_vel) * H;
+  for (int c = 0; c < 4; ++c) {
+    float* mc = m + c * MC;
+    mc[M_X] = tk_measure(b, c);
+    mc[M_V] = 0.f;
+    mc[M_P00] = sp * sp;
+    mc[M_P01] = 0.f;
+    mc[M_P11] = sv * sv;
+  }
+}
+
+// one coordinate one frame on; H the scale read before any coordinate of the slot moved.  Returns the new x.
+__host__ __device__ __forceinline__ float tk_motion_predict(const TrackArgs& p, float* mc, float H) {
+  const float q0 = (p.std_pos * H) * (p.std_pos * H), q1 = (p.std_vel * H) * (p.std_vel * H);
+  const float x = mc[M_X] + mc[M_V];
+  const float a = mc[M_P01] + mc[M_P11];
+  mc[M_X] = x;
+  mc[M_P00] = ((mc[M_P00] + mc[M_P01]) + a) + q0;
+  mc[M_P01] = a;
+  mc[M_P11] = mc[M_P11] + q1;
+  return x;
+}
+
+// half of the predicted box: the centre coordinate and the clamped extent -> (low, high)
+__host__ __device__ __forceinline__ void tk_motion_span(float centre, float extent, float* lo, float* hi) {
+  const float e = extent > 0.f ? extent : 0.f;
+  *lo = centre - 0.5f * e;
+  *hi = centre + 0.5f * e;
+}
+
+// a match: the four filters take the detection's box; a state that left the finite numbers starts again from the box
+__host__ __device__ __forceinline__ void tk_motion_update(const TrackArgs& p, float* m, const float* b) {
+  const float H = tk_hs(m[3 * MC + M_X]);
+  const float r = (p.std_pos * H) * (p.std_pos * H);
+  bool ok = true;
+  for (int c = 0; c < 4; ++c) {
+    float* mc = m + c * MC;
+    const float p00 = mc[M_P00], p01 = mc[M_P01];
+    const float s = p00 + r, k0 = p00 / s, k1 = p01 / s, y = tk_measure(b, c) - mc[M_X];
+    const float x = mc[M_X] + k0 * y, v = mc[M_V] + k1 * y;
+    mc[M_X] = x;
+    mc[M_V] = v;
+    mc[M_P11] = mc[M_P11] - k1 * p01;
+    mc[M_P01] = p01 - k1 * p00;
+    mc[M_P00] = p00 - k0 * p00;
+    ok = ok && tk_finite(x) && tk_finite(v);
+  }
+  if (!ok) tk_motion_init(p, m, b);
+}
+
+// track_pred of a row: the box its matched track was predicted at (pb), four zeros for every other row (pb null)
+__host__ __device__ __forceinline__ void tk_pred(const TrackArgs& p, long row, const float* pb) {
+  for (int k = 0; k < 4; ++k) p.o_pred[row * 4 + k] = pb ? pb[k] : 0.f;
+}
+
 // ------------------------------------------------------------------------------------------------------------ the kernel
+template <bool MOTION>
 __global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
   __shared__ unsigned long long key[SLOTS * MAXD];   // 32 KB
   __shared__ int cmin[MAXCH], cmax[MAXCH];
   __shared__ int s_i[SLOTS][NI];
   __shared__ float s_f[SLOTS][NF];
+  __shared__ float s_m[MOTION ? SLOTS : 1][MF];      // <true> only: the filters and the predicted boxes
+  __shared__ float s_pb[MOTION ? SLOTS : 1][4];
   __shared__ int det_row[MAXD], det_slot[MAXD], det_flag[MAXD];
   __shared__ float det_inv[MAXD];                    // 0 = a dead row
   __shared__ int lt[SLOTS], ld[MAXD];                // the live slots / the positions of the live detections, ascending
@@ -177,7 +255,10 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
       const int f = p.frame[i], c = i / CH;
       atomicMin(&cmin[c], f);
       atomicMax(&cmax[c], f);
-      if ((unsigned)(g0 / TPB) % gridDim.x == (unsigned)s && tk_untracked(p, f)) tk_out(p, i, 0, 0, 0, FP_TRACK_NO_STREAM);
+      if ((unsigned)(g0 / TPB) % gridDim.x == (unsigned)s && tk_untracked(p, f)) {
+        tk_out(p, i, 0, 0, 0, FP_TRACK_NO_STREAM);
+        if constexpr (MOTION) tk_pred(p, i, nullptr);
+      }
     }
   }
   __syncthreads();
@@ -185,6 +266,7 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
   int clock = p.hdr[2 * s], next_id = p.hdr[2 * s + 1];   // next_id is kept by wave 0
   float* semb = p.semb + (long)s * SLOTS * D;
   float* sbest = p.sbest + (long)s * SLOTS * D;
+  bool owned = false;   // MOTION: the stream has a frame in this step, its filters are in s_m
 
   for (int f0 = 0; f0 < p.B; f0 += TPB) {
     const bool mine = f0 + tid < p.B && p.sof[f0 + tid] == s;
@@ -193,13 +275,38 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
     __syncthreads();
     for (int w = 0; w < NW; ++w) {
       unsigned long long mm = fmask[w];
+      if constexpr (MOTION) {
+        if (mm != 0ull && !owned) {   // the stream's first frame of the step: only now is motion read (and written at the end)
+          for (int i = tid; i < SLOTS * MF; i += TPB) (&s_m[0][0])[i] = p.motion[(long)s * SLOTS * MF + i];
+          owned = true;
+          __syncthreads();
+        }
+      }
       while (mm) {
         const int f = f0 + w * 64 + (__ffsll((long long)mm) - 1);
         mm &= mm - 1ull;
 
         // ---- 1. the clock, expiry
         clock += 1;
+        // ---- 1b. thread 4 * slot + c moves coordinate c of a slot that survives the expiry; the scale is read first
+        const int m_slot = tid >> 2, m_c = tid & 3;
+        float m_H = 1.f;
+        bool m_live = false;
+        if constexpr (MOTION) {
+          if (tid < 4 * SLOTS) {
+            m_H = tk_hs(s_m[m_slot][3 * MC + M_X]);
+            m_live = s_i[m_slot][I_ID] != 0 && !(clock - s_i[m_slot][I_LAST] > p.max_age);
+          }
+          __syncthreads();
+        }
         if (tid < SLOTS && s_i[tid][I_ID] != 0 && clock - s_i[tid][I_LAST] > p.max_age) s_i[tid][I_ID] = 0;
+        if constexpr (MOTION) {
+          if (tid < 4 * SLOTS) {   // whole waves: the centre lanes (c < 2) fetch their extent from lane + 2
+            const float x = m_live ? tk_motion_predict(p, &s_m[m_slot][m_c * MC], m_H) : 0.f;
+            const float other = __shfl_xor(x, 2);
+            if (m_live && m_c < 2) tk_motion_span(x, other, &s_pb[m_slot][m_c], &s_pb[m_slot][m_c + 2]);
+          }
+        }
 
         // ---- 2. the frame's rows in row order: the first MAXD take part
         int base = 0;
@@ -226,6 +333,7 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
                 det_inv[pos] = tk_live(inv) ? inv : 0.f;
               } else {
                 tk_out(p, i, 0, 0, clock, FP_TRACK_OVER);
+                if constexpr (MOTION) tk_pred(p, i, nullptr);
               }
             }
             base += total;
@@ -270,7 +378,7 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
             v += __shfl_xor(v, 1);
             if (gl == 0 && q0 + grp < np) {
               const float c = tk_cos(v, s_f[slot][F_INV], det_inv[pos]);
-              const float iou = tk_iou(&s_f[slot][F_BOX], p.box + row * 4);
+              const float iou = tk_iou(MOTION ? s_pb[slot] : &s_f[slot][F_BOX], p.box + row * 4);
               key[q] = tk_admissible(p, c, iou) ? tk_key(c, slot, pos) : KEY_NONE;
             }
           }
@@ -339,6 +447,11 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
           next_id += min(__popcll(needm), n_free);
           if (lane < nd) {
             const long row = det_row[lane];
+            if constexpr (MOTION) {
+              tk_pred(p, row, matched ? s_pb[my_slot] : nullptr);
+              if (matched) tk_motion_update(p, s_m[my_slot], p.box + row * 4);
+              else if (dl && my_slot >= 0) tk_motion_init(p, s_m[my_slot], p.box + row * 4);
+            }
             if (!dl) {
               tk_out(p, row, 0, 0, clock, FP_TRACK_DEAD_ROW);
             } else if (my_slot < 0) {
@@ -370,6 +483,9 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
 
   for (int i = tid; i < SLOTS * NI; i += TPB) p.si[(long)s * SLOTS * NI + i] = (&s_i[0][0])[i];
   for (int i = tid; i < SLOTS * NF; i += TPB) p.sf[(long)s * SLOTS * NF + i] = (&s_f[0][0])[i];
+  if constexpr (MOTION)
+    if (owned)
+      for (int i = tid; i < SLOTS * MF; i += TPB) p.motion[(long)s * SLOTS * MF + i] = (&s_m[0][0])[i];
   if (tid == 0) {
     p.hdr[2 * s] = clock;
     p.hdr[2 * s + 1] = next_id;
@@ -384,6 +500,15 @@ int check_track(const TrackArgs& a, const fp_track_state* st) {
     return FP_ERR_INVALID_ARG;
   if (((uintptr_t)a.semb | (uintptr_t)a.sbest | (uintptr_t)a.emb) % 16 != 0) return FP_ERR_INVALID_ARG;   // float4 rows
   if (!(a.tau_far >= a.tau_near) || a.iou_min != a.iou_min) return FP_ERR_INVALID_ARG;
+  return FP_OK;
+}
+
+// the motion entry points: check_track's refusals and their own
+int check_motion(const TrackArgs& a, const fp_track_state* st) {
+  const int rc = check_track(a, st);
+  if (rc != FP_OK) return rc;
+  if (!a.motion || (a.n > 0 && !a.o_pred)) return FP_ERR_INVALID_ARG;
+  if (!(a.std_pos > 0.f && tk_finite(a.std_pos) && a.std_vel > 0.f && tk_finite(a.std_vel))) return FP_ERR_INVALID_ARG;
   return FP_OK;
 }
 
@@ -402,6 +527,12 @@ TrackArgs track_args(const fp_track_state* st, int n_streams, int D, const int32
   a.sof = stream_of_frame; a.B = B;
   a.max_age = max_age; a.tau_near = tau_near; a.tau_far = tau_far; a.iou_min = iou_min;
   a.o_id = track_id; a.o_hits = track_hits; a.o_clock = track_clock; a.o_flags = track_flags;
+  a.motion = nullptr; a.std_pos = a.std_vel = 0.f; a.o_pred = nullptr;
+  return a;
+}
+
+TrackArgs with_motion(TrackArgs a, float* motion, float std_pos, float std_vel, float* track_pred) {
+  a.motion = motion; a.std_pos = std_pos; a.std_vel = std_vel; a.o_pred = track_pred;
   return a;
 }
 
@@ -414,6 +545,16 @@ void emulate_frame(const TrackArgs& p, int s, int f, int& clock, int& next_id, s
   clock += 1;
   for (int t = 0; t < SLOTS; ++t)
     if (si[t * NI + I_ID] != 0 && clock - si[t * NI + I_LAST] > p.max_age) si[t * NI + I_ID] = 0;
+  float* sm = p.motion ? p.motion + (long)s * SLOTS * MF : nullptr;
+  float pbox[SLOTS][4];   // step 1b: the predicted boxes of the live slots
+  for (int t = 0; sm && t < SLOTS; ++t) {
+    if (si[t * NI + I_ID] == 0) continue;
+    float* m = sm + t * MF;
+    const float H = tk_hs(m[3 * MC + M_X]);
+    float x[4];
+    for (int c = 0; c < 4; ++c) x[c] = tk_motion_predict(p, m + c * MC, H);
+    for (int c = 0; c < 2; ++c) tk_motion_span(x[c], x[c + 2], &pbox[t][c], &pbox[t][c + 2]);
+  }
   long det_row[MAXD];
   float det_inv[MAXD];
   int nd = 0;
@@ -425,6 +566,7 @@ void emulate_frame(const TrackArgs& p, int s, int f, int& clock, int& next_id, s
       ++nd;
     } else {
       tk_out(p, i, 0, 0, clock, FP_TRACK_OVER);
+      if (sm) tk_pred(p, i, nullptr);
     }
   }
   key.clear();
@@ -437,7 +579,7 @@ void emulate_frame(const TrackArgs& p, int s, int f, int& clock, int& next_id, s
       for (int off = GL / 2; off > 0; off >>= 1)   // the xor-shuffle sum as lane 0 sees it
         for (int l = 0; l < off; ++l) part[l] = part[l] + part[l + off];
       const float c = tk_cos(part[0], sf[t * NF + F_INV], det_inv[j]);
-      const float iou = tk_iou(sf + t * NF + F_BOX, p.box + det_row[j] * 4);
+      const float iou = tk_iou(sm ? pbox[t] : sf + t * NF + F_BOX, p.box + det_row[j] * 4);
       if (tk_admissible(p, c, iou)) key.push_back(tk_key(c, t, j));
     }
   }
@@ -457,6 +599,7 @@ void emulate_frame(const TrackArgs& p, int s, int f, int& clock, int& next_id, s
     const long row = det_row[j];
     slot_of[j] = -1;
     flag_of[j] = 0;
+    if (sm) tk_pred(p, row, my_slot[j] >= 0 ? pbox[my_slot[j]] : nullptr);
     if (!(det_inv[j] > 0.f)) {
       tk_out(p, row, 0, 0, clock, FP_TRACK_DEAD_ROW);
       continue;
@@ -473,6 +616,8 @@ void emulate_frame(const TrackArgs& p, int s, int f, int& clock, int& next_id, s
       }
       new_id = next_id++;
     }
+    if (sm && matched) tk_motion_update(p, sm + slot * MF, p.box + row * 4);
+    if (sm && !matched) tk_motion_init(p, sm + slot * MF, p.box + row * 4);
     const int flags = tk_update_slot(p, si + slot * NI, sf + slot * NF, row, det_inv[j], !matched, clock, new_id);
     tk_out(p, row, si[slot * NI + I_ID], si[slot * NI + I_HITS], clock, flags);
     slot_of[j] = slot;
@@ -483,6 +628,20 @@ void emulate_frame(const TrackArgs& p, int s, int f, int& clock, int& next_id, s
     const float* e = p.emb + det_row[j] * p.D;
     std::copy(e, e + p.D, semb + (long)slot_of[j] * p.D);
     if (flag_of[j] & FP_TRACK_BEST) std::copy(e, e + p.D, sbest + (long)slot_of[j] * p.D);
+  }
+}
+
+void emulate_step(const TrackArgs& p) {
+  for (long i = 0; i < p.n; ++i)
+    if (tk_untracked(p, p.frame[i])) {
+      tk_out(p, i, 0, 0, 0, FP_TRACK_NO_STREAM);
+      if (p.motion) tk_pred(p, i, nullptr);
+    }
+  std::vector<unsigned long long> key;
+  for (int f = 0; f < p.B; ++f) {   // streams are independent: batch order is every stream's own order
+    const int s = p.sof[f];
+    if (s < 0 || s >= p.S) continue;
+    emulate_frame(p, s, f, p.hdr[2 * s], p.hdr[2 * s + 1], key);
   }
 }
 
@@ -498,7 +657,7 @@ int fp_tracklets_step(const fp_track_state* state, int n_streams, int D, const i
                                  tau_far, iou_min, track_id, track_hits, track_clock, track_flags);
   const int rc = check_track(a, state);
   if (rc != FP_OK || (B == 0 && n == 0)) return rc;
-  hipLaunchKernelGGL(tracklets_kernel, dim3((unsigned)n_streams), dim3(TPB), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(tracklets_kernel<false>, dim3((unsigned)n_streams), dim3(TPB), 0, (hipStream_t)stream, a);
   FP_CHECK_LAUNCH();
   return FP_OK;
 }
@@ -511,14 +670,36 @@ int fp_tracklets_step_emulate(const fp_track_state* state, int n_streams, int D,
                                  tau_far, iou_min, track_id, track_hits, track_clock, track_flags);
   const int rc = check_track(p, state);
   if (rc != FP_OK) return rc;
-  for (long i = 0; i < n; ++i)
-    if (tk_untracked(p, frame[i])) tk_out(p, i, 0, 0, 0, FP_TRACK_NO_STREAM);
-  std::vector<unsigned long long> key;
-  for (int f = 0; f < B; ++f) {   // streams are independent: batch order is every stream's own order
-    const int s = stream_of_frame[f];
-    if (s < 0 || s >= n_streams) continue;
-    emulate_frame(p, s, f, p.hdr[2 * s], p.hdr[2 * s + 1], key);
-  }
+  emulate_step(p);
+  return FP_OK;
+}
+
+int fp_tracklets_step_motion(const fp_track_state* state, int n_streams, int D, const int32_t* frame, const float* box,
+                             const float* emb, const float* xinv, const float* score, int n, const int32_t* stream_of_frame,
+                             int B, int max_age, float tau_near, float tau_far, float iou_min, int32_t* track_id,
+                             int32_t* track_hits, int32_t* track_clock, int32_t* track_flags, float* motion, float std_pos,
+                             float std_vel, float* track_pred, void* stream) {
+  const TrackArgs a = with_motion(track_args(state, n_streams, D, frame, box, emb, xinv, score, n, stream_of_frame, B, max_age,
+                                             tau_near, tau_far, iou_min, track_id, track_hits, track_clock, track_flags),
+                                  motion, std_pos, std_vel, track_pred);
+  const int rc = check_motion(a, state);
+  if (rc != FP_OK || (B == 0 && n == 0)) return rc;
+  hipLaunchKernelGGL(tracklets_kernel<true>, dim3((unsigned)n_streams), dim3(TPB), 0, (hipStream_t)stream, a);
+  FP_CHECK_LAUNCH();
+  return FP_OK;
+}
+
+int fp_tracklets_step_motion_emulate(const fp_track_state* state, int n_streams, int D, const int32_t* frame, const float* box,
+                                     const float* emb, const float* xinv, const float* score, int n,
+                                     const int32_t* stream_of_frame, int B, int max_age, float tau_near, float tau_far,
+                                     float iou_min, int32_t* track_id, int32_t* track_hits, int32_t* track_clock,
+                                     int32_t* track_flags, float* motion, float std_pos, float std_vel, float* track_pred) {
+  const TrackArgs p = with_motion(track_args(state, n_streams, D, frame, box, emb, xinv, score, n, stream_of_frame, B, max_age,
+                                             tau_near, tau_far, iou_min, track_id, track_hits, track_clock, track_flags),
+                                  motion, std_pos, std_vel, track_pred);
+  const int rc = check_motion(p, state);
+  if (rc != FP_OK) return rc;
+  emulate_step(p);
   return FP_OK;
 }
 

@@ -1,5 +1,5 @@
 """``python -m face_detection_and_recognition_amd.eval.eval_face_tracker data/ --tracks hyp/`` or
-``... data/ --model synthetic --max_age 30 [--sweep max_age=5,15,30]``
+``... data/ --model synthetic --max_age 30 [--motion STD_POS STD_VEL] [--sweep max_age=5,15,30]``
 
 Scores a face tracker on labelled video with CLEAR-MOT (MOTA, MOTP, IDSW, Frag, MT / PT / ML) and the identity measures
 (IDF1, IDP, IDR): tracking_eval.py, the kernel of csrc/moteval.hip on a HIP device, numpy with ``-d cpu``; DESIGN.md
@@ -13,9 +13,12 @@ and ``frames/*.jpg`` (sorted by name = video order).  The hypotheses are either
   * a model plus ``--max_age`` (and ``--tau_near / --tau_far / --iou_min``): FacePipeline(tracker=StreamTracker) runs over the
     frames, one stream per sequence, and every step's rows go to a TrackingEvaluator on the device.
 
-``--sweep key=v1,v2,...`` (key: max_age, tau_near, tau_far or iou_min) repeats the run per value and prints one combined row
-each.  Prints the table (one line per sequence and the combined line) and returns the result (a list of (value, result)
-under --sweep).  The thresholds' defaults are the reference's numbers restated as cosines; max_age has no default.
+``--motion STD_POS STD_VEL`` turns the tracker's constant-velocity prediction on (tracking.ConstantVelocity; DESIGN section 7
+"Tracklets: motion prediction"): no defaults, nothing has been measured; DeepSORT publishes 0.05 and 0.00625.
+``--sweep key=v1,v2,...`` (key: max_age, tau_near, tau_far, iou_min, or with --motion std_pos / std_vel) repeats the run per
+value and prints one combined row each.  Prints the table (one line per sequence and the combined line) and returns the result
+(a list of (value, result) under --sweep).  The thresholds' defaults are the reference's numbers restated as cosines; max_age
+has no default.
 """
 import argparse
 import glob
@@ -26,7 +29,7 @@ import numpy as np
 from ..tracking import IOU_MIN, TAU_FAR, TAU_NEAR
 from ..tracking_eval import TrackingEvaluator, mot_eval, read_mot_txt
 
-SWEEP_KEYS = dict(max_age=int, tau_near=float, tau_far=float, iou_min=float)
+SWEEP_KEYS = dict(max_age=int, tau_near=float, tau_far=float, iou_min=float, std_pos=float, std_vel=float)
 
 
 def load_sequences(root):
@@ -97,9 +100,11 @@ def run_tracker(seqs, args, dev, parts):
     import torch
     from ..modules.utils.jpeg import imread_batch
     from ..pipeline import FacePipeline
-    from ..tracking import StreamTracker
+    from ..tracking import ConstantVelocity, StreamTracker
     det, emb = parts
-    tracker = StreamTracker(len(seqs), emb.embedding_size, args.max_age, args.tau_near, args.tau_far, args.iou_min, device=dev)
+    motion = None if args.motion is None else ConstantVelocity(*args.motion)
+    tracker = StreamTracker(len(seqs), emb.embedding_size, args.max_age, args.tau_near, args.tau_far, args.iou_min, device=dev,
+                            motion=motion)
     pipe = FacePipeline(det, emb, None, tracker=tracker)
     ev = TrackingEvaluator(len(seqs), dev, thr=args.thr).set_ground_truth(*ground_truth(seqs))
     for s, seq in enumerate(seqs):
@@ -134,7 +139,10 @@ def main(argv=None):
     parser.add_argument("--tau_near", type=float, default=TAU_NEAR)
     parser.add_argument("--tau_far", type=float, default=TAU_FAR)
     parser.add_argument("--iou_min", type=float, default=IOU_MIN)
-    parser.add_argument("--sweep", default=None, help="key=v1,v2,...: repeat the run per value of max_age / tau_near / tau_far / iou_min.")
+    parser.add_argument("--motion", type=float, nargs=2, default=None, metavar=("STD_POS", "STD_VEL"),
+                        help="Constant-velocity prediction for the IoU gate: noise as fractions of the box height (no defaults).")
+    parser.add_argument("--sweep", default=None, help="key=v1,v2,...: repeat the run per value of max_age / tau_near / tau_far / iou_min "
+                                                      "/ std_pos / std_vel (the last two with --motion).")
     parser.add_argument("--thr", type=float, default=0.5, help="IoU threshold of a match (default: %(default)s).")
     parser.add_argument("-b", "--batch_size", type=int, default=256)
     parser.add_argument("-d", "--device", default="hip", help="hip[:N] / cuda[:N]; cpu (numpy path) with --tracks (default: %(default)s).")
@@ -163,9 +171,13 @@ def main(argv=None):
         parser.error(str(e))
     if args.max_age is None and key != "max_age":
         parser.error("--max_age is required (it has no default: nothing has been measured)")
+    if key in ("std_pos", "std_vel") and args.motion is None:
+        parser.error(f"--sweep {key}= needs --motion STD_POS STD_VEL for the value that is not swept")
     results, parts = [], build_parts(seqs, args, device)
     for v in values:
-        if key is not None:
+        if key in ("std_pos", "std_vel"):
+            args.motion[("std_pos", "std_vel").index(key)] = v
+        elif key is not None:
             setattr(args, key, v)
         result = run_tracker(seqs, args, device, parts)
         results.append((v, result))

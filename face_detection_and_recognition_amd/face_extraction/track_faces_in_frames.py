@@ -8,6 +8,8 @@ highest detector confidence, or with --quality the sharpest crop); at the end <t
 
 `--model synthetic` (the default: no trained weights ship with the project) runs the seeded random weights of workload.py.
 The thresholds default to the reference's numbers restated as cosines, unmeasured on real video; --max_age has no default.
+--motion STD_POS STD_VEL turns the tracker's constant-velocity prediction on (tracking.ConstantVelocity: the IoU gate takes the
+box a track is predicted at; no defaults, nothing has been measured).
 Build-defined: the reference labels faces frame by frame (face_tracker.py is that port).
 
 --mot_out FILE also writes every tracked face as a MOTChallenge row `frame,id,x,y,w,h,conf,-1,-1,-1` (frames 1-based in video
@@ -20,7 +22,7 @@ import os
 
 import numpy as np
 
-from ..tracking import BEST, IOU_MIN, TAU_FAR, TAU_NEAR, StreamTracker, TrackBook
+from ..tracking import BEST, IOU_MIN, TAU_FAR, TAU_NEAR, ConstantVelocity, StreamTracker, TrackBook
 
 
 def get_parsed_args(argv=None):
@@ -33,6 +35,8 @@ def get_parsed_args(argv=None):
     parser.add_argument('--tau_near', type=float, default=TAU_NEAR)
     parser.add_argument('--tau_far', type=float, default=TAU_FAR)
     parser.add_argument('--iou_min', type=float, default=IOU_MIN)
+    parser.add_argument('--motion', type=float, nargs=2, default=None, metavar=("STD_POS", "STD_VEL"),
+                        help="constant-velocity prediction for the IoU gate: noise as fractions of the box height (no defaults)")
     parser.add_argument('--quality', action="store_true", help="best shot by crop sharpness instead of detector confidence")
     parser.add_argument('-b', '--batch_size', type=int, default=256)
     parser.add_argument('--jpeg_quality', type=int, default=95)
@@ -53,7 +57,8 @@ def build_pipeline(args, dev, first_frames):
         raise ValueError("only --model synthetic is wired here; build a FacePipeline(..., tracker=StreamTracker(...)) for real weights")
     det = W.build_detector(dev, first_frames, cand_per_frame=48)
     emb = W.build_embedder(dev)
-    tracker = StreamTracker(1, emb.embedding_size, args.max_age, args.tau_near, args.tau_far, args.iou_min, device=dev)
+    motion = None if args.motion is None else ConstantVelocity(*args.motion)
+    tracker = StreamTracker(1, emb.embedding_size, args.max_age, args.tau_near, args.tau_far, args.iou_min, device=dev, motion=motion)
     return FacePipeline(det, emb, None, quality=True if args.quality else None, tracker=tracker), tracker
 
 

@@ -38,7 +38,7 @@ class FacePipeline:
     mask, which compacts nothing (as the cosine filter's keep); side stream as the attributes.
     tracker: a StreamTracker (tracking.py) whose feat_dim is the embedder's: step results then also carry track_id, track_hits,
     track_clock and track_flags (n,) int32, rows in the order of emb, from one fp_tracklets_step launch behind the embedder (side
-    stream as the attributes).  step / step_overlapped take streams = the stream of every frame ((B,) ints, -1: not tracked;
+    stream as the attributes); a tracker built with motion= adds track_pred (n, 4) fp32, the predicted box of every matched row.  step / step_overlapped take streams = the stream of every frame ((B,) ints, -1: not tracked;
     None: the batch is consecutive frames of stream 0).  The score of the best shot is the conf column of info, or
     quality["sharpness"] with quality on.  Steps must reach the tracker in order: it carries state from step to step."""
 
@@ -265,7 +265,7 @@ class FacePipeline:
             attrs = tuple(out[k] for k in ("age_probs", "gender_probs") + self.IDENTITY_KEYS if k in out)
             if self.quality is not None:
                 attrs += tuple(out["quality"].values()) + ((out["quality_keep"],) if "quality_keep" in out else ())
-            attrs += tuple(out[k] for k in self.TRACK_KEYS if k in out)
+            attrs += tuple(out[k] for k in self.TRACK_RESULT_KEYS if k in out)
             for t in (out["emb"],) + attrs + (tuple(res) if res is not None else ()):
                 t.record_stream(main)
             self._emb_done = torch.cuda.Event()
@@ -320,6 +320,7 @@ class FacePipeline:
             out["quality_keep"] = self.quality.mask(out["quality"])
 
     TRACK_KEYS = ("track_id", "track_hits", "track_clock", "track_flags")
+    TRACK_RESULT_KEYS = TRACK_KEYS + ("track_pred",)      # track_pred: only from a tracker with motion=
 
     def _stream_of_frame(self, B, streams):
         """(B,) int32 on the device: zeros for None (small cache by B), else the caller's streams."""

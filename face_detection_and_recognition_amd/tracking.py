@@ -11,8 +11,14 @@ DESIGN.md section 7 "Tracklets"; track_step_numpy restates it (IoU float32 in th
 oracle of the tests, track_step_emulate runs the kernel's own decision code on the host.  The three agree exactly wherever no
 decisive cosine lies within D * 2^-24 of a threshold or of another one.  tau_near = 0.5, tau_far = 0.7408 and iou_min = 0.1
 restate the reference's thresholds for unit vectors (L2 distance < 1.0 with IoU > 0.1, or < 0.72 alone; cos = 1 - d^2 / 2):
-they are the reference's numbers, unmeasured on real video.  max_age has no reference counterpart and no default.  Motion
-prediction (Kalman, constant velocity) is not part of this.
+they are the reference's numbers, unmeasured on real video.  max_age has no reference counterpart and no default.
+
+Motion prediction is opt-in: motion=ConstantVelocity(std_pos, std_vel) gives every slot four two-state constant-velocity Kalman
+filters (centre, width, height), the IoU gate then takes the box the track is PREDICTED at in the frame instead of its last box,
+and every matched row also reports that box (track_pred).  fp_tracklets_step_motion, include/facepath.h "Tracklets: motion
+prediction"; the filter is float32 in the written order on all three paths, so it adds nothing to the agreement condition.
+Without motion= nothing changes.  Rows for coasting tracks, Mahalanobis gating and camera-motion compensation are not part of
+this, and no value of std_pos / std_vel has been measured.
 """
 import ctypes as C
 
@@ -29,6 +35,31 @@ I_ID, I_FIRST, I_LAST, I_HITS, I_BEST_CLOCK = range(5)      # slot_i columns
 F_BOX, F_INV, F_BEST_SCORE, F_BEST_BOX = 0, 4, 5, 6         # slot_f columns
 STATE_KEYS = ("hdr", "slot_i", "slot_f", "emb", "best_emb")
 OUT_KEYS = ("track_id", "track_hits", "track_clock", "track_flags")
+MOTION_FLOATS = L.TRACK_MOTION_FLOATS
+M_X, M_V, M_P00, M_P01, M_P11, M_COLS = 0, 1, 2, 3, 4, 5    # columns of one coordinate (cx, cy, w, h) of a slot of `motion`
+
+
+class ConstantVelocity:
+    """The parameters of the tracker's motion prediction: noise as a fraction of the box height, both finite and > 0
+    (ValueError otherwise).  No defaults, as max_age has none: nothing has been measured here.  DEEPSORT_STD_POS and
+    DEEPSORT_STD_VEL are the constants DeepSORT's Kalman filter publishes (1/20 and 1/160), named for convenience and
+    unmeasured on this tracker."""
+    DEEPSORT_STD_POS = 1 / 20
+    DEEPSORT_STD_VEL = 1 / 160
+
+    def __init__(self, std_pos, std_vel):
+        self.std_pos, self.std_vel = float(std_pos), float(std_vel)
+        for name, v in (("std_pos", self.std_pos), ("std_vel", self.std_vel)):
+            if not (v > 0 and np.isfinite(np.float32(v))):
+                raise ValueError(f"{name} must be finite and > 0, got {v}")
+
+    def __repr__(self):
+        return f"ConstantVelocity(std_pos={self.std_pos}, std_vel={self.std_vel})"
+
+
+def new_motion_state(n_streams):
+    """A fresh `motion` array: zeros (n_streams, SLOTS, MOTION_FLOATS) float32."""
+    return np.zeros((int(n_streams), SLOTS, MOTION_FLOATS), np.float32)
 
 
 def check_params(n_streams, feat_dim, max_age, tau_near, tau_far, iou_min):
@@ -78,6 +109,68 @@ def row_inv_norm_numpy(emb):
 
 # ------------------------------------------------------------------------------------------------ the numpy restatement
 
+_F = np.float32
+
+
+def _hs(t):
+    return t if t > _F(1) else _F(1)
+
+
+def _measure(b):
+    """include/facepath.h "Tracklets: motion prediction": z of a float32 box."""
+    return (_F(0.5) * (b[0] + b[2]), _F(0.5) * (b[1] + b[3]), b[2] - b[0], b[3] - b[1])
+
+
+def _motion_init(m, box, sp, sv):
+    z = _measure(box)
+    H = _hs(z[3])
+    a, b = (_F(2) * sp) * H, (_F(10) * sv) * H
+    for c in range(4):
+        m[c * M_COLS:(c + 1) * M_COLS] = (z[c], _F(0), a * a, _F(0), b * b)
+
+
+def _motion_predict(m, sp, sv):
+    """One live slot one frame on (m: its (MOTION_FLOATS,) float32 row, IN PLACE) -> the predicted box (4,) float32."""
+    H = _hs(m[3 * M_COLS + M_X])
+    q0, q1 = (sp * H) * (sp * H), (sv * H) * (sv * H)
+    for c in range(4):
+        x, v, p00, p01, p11 = m[c * M_COLS:(c + 1) * M_COLS]
+        a = p01 + p11
+        m[c * M_COLS:(c + 1) * M_COLS] = (x + v, v, ((p00 + p01) + a) + q0, a, p11 + q1)
+    cx, cy, w, h = (m[c * M_COLS + M_X] for c in range(4))
+    pw, ph = (w if w > 0 else _F(0)), (h if h > 0 else _F(0))
+    return np.array([cx - _F(0.5) * pw, cy - _F(0.5) * ph, cx + _F(0.5) * pw, cy + _F(0.5) * ph], np.float32)
+
+
+def _motion_update(m, box, sp, sv):
+    z = _measure(box)
+    H = _hs(m[3 * M_COLS + M_X])
+    r = (sp * H) * (sp * H)
+    ok = True
+    for c in range(4):
+        x, v, p00, p01, p11 = m[c * M_COLS:(c + 1) * M_COLS]
+        s = p00 + r
+        k0, k1, y = p00 / s, p01 / s, z[c] - x
+        x, v = x + k0 * y, v + k1 * y
+        m[c * M_COLS:(c + 1) * M_COLS] = (x, v, p00 - k0 * p00, p01 - k1 * p00, p11 - k1 * p01)
+        ok = ok and x - x == 0 and v - v == 0
+    if not ok:
+        _motion_init(m, box, sp, sv)
+
+
+def _motion_args(motion, motion_state, S):
+    """(None, None, None) without motion; else (std_pos, std_vel as float32, the checked state array)."""
+    if motion is None:
+        if motion_state is not None:
+            raise ValueError("motion_state without motion=")
+        return None, None, None
+    ms = motion_state
+    if not (isinstance(ms, np.ndarray) and ms.dtype == np.float32 and ms.shape == (S, SLOTS, MOTION_FLOATS)
+            and ms.flags.c_contiguous and ms.flags.writeable):
+        raise ValueError(f"motion_state must be a writable C-contiguous float32 array ({S}, {SLOTS}, {MOTION_FLOATS}) "
+                         "(new_motion_state)")
+    return np.float32(motion.std_pos), np.float32(motion.std_vel), ms
+
 def _iou_f32(t, d):
     """include/facepath.h "Tracklets" step 2: float32, written order; t the track's box, d (k, 4) the detections'."""
     f = np.float32
@@ -92,18 +185,24 @@ def _iou_f32(t, d):
 
 
 def track_step_numpy(state, frame, boxes, emb, xinv, stream_of_frame, max_age, tau_near=TAU_NEAR, tau_far=TAU_FAR,
-                     iou_min=IOU_MIN, score=None, cosines=None):
+                     iou_min=IOU_MIN, score=None, cosines=None, motion=None, motion_state=None):
     """fp_tracklets_step in numpy on a host state (new_state; updated IN PLACE).  IoU in float32 in the written order, the
     cosine in float64: (dot * inv_t) * inv_d with float64 products of the float32 values.  -> dict of the four per-row int32
     arrays.  cosines: a list that receives, per frame with live tracks and live detections, (frame, slots, rows, c (T, K)
-    float64, iou (T, K) float32, the tracks' stored rows (T, D)) -- what the tests' gap condition looks at."""
+    float64, iou (T, K) float32, the tracks' stored rows (T, D)) -- what the tests' gap condition looks at.
+    motion: a ConstantVelocity, with motion_state = the streams' `motion` array (new_motion_state; updated IN PLACE): the filter
+    of "Tracklets: motion prediction" in np.float32 scalars, the IoU taken with the predicted boxes, and the result also
+    carries track_pred (n, 4) float32."""
     frame, boxes, emb, xinv, score, sof = _row_inputs(frame, boxes, emb, xinv, score, stream_of_frame)
     n, B = frame.shape[0], sof.shape[0]
     S, D = state["hdr"].shape[0], state["emb"].shape[2]
     check_params(S, D, max_age, tau_near, tau_far, iou_min)
     f32 = np.float32
     tn, tf, im = float(f32(tau_near)), float(f32(tau_far)), f32(iou_min)
+    sp, sv, mstate = _motion_args(motion, motion_state, S)
     out = {k: np.zeros((n,), np.int32) for k in OUT_KEYS}
+    if motion is not None:
+        out["track_pred"] = np.zeros((n, 4), np.float32)
     live_row = np.isfinite(xinv) & (xinv > 0)
     ok_frame = (frame >= 0) & (frame < B)
     srow = np.full((n,), -1, np.int64)
@@ -120,6 +219,8 @@ def track_step_numpy(state, frame, boxes, emb, xinv, stream_of_frame, max_age, t
             hdr[0] += 1
             clock = int(hdr[0])
             si[(si[:, I_ID] != 0) & (clock - si[:, I_LAST] > max_age), I_ID] = 0
+            if motion is not None:                          # step 1b: every live slot, rows or not
+                pbox = {int(t): _motion_predict(mstate[s, t], sp, sv) for t in np.nonzero(si[:, I_ID] != 0)[0]}
             rows = np.nonzero(frame == f)[0]
             for i in rows[MAX_DETS:]:
                 out["track_clock"][i], out["track_flags"][i] = clock, OVER
@@ -133,7 +234,7 @@ def track_step_numpy(state, frame, boxes, emb, xinv, stream_of_frame, max_age, t
                 te, de = state["emb"][s][slots].astype(np.float64), emb[dets].astype(np.float64)
                 dot = (te[:, None, :] * de[None, :, :]).sum(axis=2)       # row by row: equal rows give equal sums
                 c = (dot * sf[slots, F_INV].astype(np.float64)[:, None]) * xinv[dets].astype(np.float64)[None, :]
-                iou = np.stack([_iou_f32(sf[t, F_BOX:F_BOX + 4], boxes[dets]) for t in slots])
+                iou = np.stack([_iou_f32(sf[t, F_BOX:F_BOX + 4] if motion is None else pbox[int(t)], boxes[dets]) for t in slots])
                 if cosines is not None:
                     cosines.append((f, slots.copy(), dets.copy(), c.copy(), iou.copy(), state["emb"][s][slots].copy()))
                 adm = ((c > tn) & (iou > im)) | (c > tf)
@@ -158,6 +259,11 @@ def track_step_numpy(state, frame, boxes, emb, xinv, stream_of_frame, max_age, t
                     slot, is_new = int(free[0]), True
                     si[slot, I_ID], si[slot, I_FIRST], si[slot, I_HITS] = hdr[1], clock, 0
                     hdr[1] += 1
+                if motion is not None and is_new:
+                    _motion_init(mstate[s, slot], boxes[i], sp, sv)
+                elif motion is not None:
+                    out["track_pred"][i] = pbox[slot]
+                    _motion_update(mstate[s, slot], boxes[i], sp, sv)
                 sc = f32(0) if score is None else score[i]
                 si[slot, I_HITS] += 1
                 si[slot, I_LAST] = clock
@@ -188,9 +294,9 @@ def _state_struct(arrays, pointer):
 
 
 def track_step_emulate(state, frame, boxes, emb, xinv, stream_of_frame, max_age, tau_near=TAU_NEAR, tau_far=TAU_FAR,
-                       iou_min=IOU_MIN, score=None):
-    """fp_tracklets_step_emulate on a host state (new_state; updated IN PLACE): track_step_numpy's arguments and results.
-    Raises FacepathError on a refusal.  Needs no GPU."""
+                       iou_min=IOU_MIN, score=None, motion=None, motion_state=None):
+    """fp_tracklets_step_emulate on a host state (new_state; updated IN PLACE): track_step_numpy's arguments and results; with
+    motion= and motion_state=, fp_tracklets_step_motion_emulate.  Raises FacepathError on a refusal.  Needs no GPU."""
     lib = L.load()
     frame, boxes, emb, xinv, score, sof = _row_inputs(frame, boxes, emb, xinv, score, stream_of_frame)
     n, B = frame.shape[0], sof.shape[0]
@@ -206,9 +312,18 @@ def track_step_emulate(state, frame, boxes, emb, xinv, stream_of_frame, max_age,
         aligned = buf[off:off + emb.size].reshape(emb.shape)
         aligned[...] = emb
         emb = aligned
+    sp, sv, mstate = _motion_args(motion, motion_state, S)
     out = {k: np.zeros((n,), np.int32) for k in OUT_KEYS}
     p = lambda a: None if a is None else C.c_void_p(a.ctypes.data)          # noqa: E731
     st = _state_struct(state, p)
+    if motion is not None:
+        pred = np.zeros((n, 4), np.float32)
+        L.check(lib.fp_tracklets_step_motion_emulate(C.byref(st), S, D, p(frame), p(boxes), p(emb), p(xinv), p(score), n, p(sof),
+                                                     B, int(max_age), float(tau_near), float(tau_far), float(iou_min),
+                                                     *[p(out[k]) for k in OUT_KEYS], p(mstate), float(sp), float(sv), p(pred)),
+                "fp_tracklets_step_motion_emulate")
+        out["track_pred"] = pred
+        return out
     L.check(lib.fp_tracklets_step_emulate(C.byref(st), S, D, p(frame), p(boxes), p(emb), p(xinv), p(score), n, p(sof), B,
                                           int(max_age), float(tau_near), float(tau_far), float(iou_min),
                                           *[p(out[k]) for k in OUT_KEYS]), "fp_tracklets_step_emulate")
@@ -218,22 +333,35 @@ def track_step_emulate(state, frame, boxes, emb, xinv, stream_of_frame, max_age,
 class StreamTracker:
     """n_streams independent streams, each with up to L.TRACK_SLOTS live tracks of feat_dim-float embeddings, on `device`.
     max_age: a track unseen for more than max_age frames of its stream is freed (required: nothing to restate).  The
-    thresholds default to the reference's numbers as cosines (module docstring); tau_far < tau_near is a ValueError."""
+    thresholds default to the reference's numbers as cosines (module docstring); tau_far < tau_near is a ValueError.
+    motion: None, or a ConstantVelocity: the IoU gate takes the predicted box (fp_tracklets_step_motion), the state gains
+    "motion" (n_streams, SLOTS, MOTION_FLOATS) and step() also returns track_pred."""
 
-    def __init__(self, n_streams, feat_dim, max_age, tau_near=TAU_NEAR, tau_far=TAU_FAR, iou_min=IOU_MIN, device="cuda:0"):
+    def __init__(self, n_streams, feat_dim, max_age, tau_near=TAU_NEAR, tau_far=TAU_FAR, iou_min=IOU_MIN, device="cuda:0",
+                 motion=None):
         check_params(n_streams, feat_dim, max_age, tau_near, tau_far, iou_min)
+        if motion is not None and not isinstance(motion, ConstantVelocity):
+            raise TypeError(f"motion must be None or a ConstantVelocity, got {type(motion).__name__}")
+        self.motion = motion
         self.S, self.D, self.max_age = int(n_streams), int(feat_dim), int(max_age)
         self.tau_near, self.tau_far, self.iou_min = float(tau_near), float(tau_far), float(iou_min)
         self.dev = torch.device(device)
         self.state = {k: torch.from_numpy(v).to(self.dev) for k, v in new_state(self.S, self.D).items()}
         self._struct = _state_struct(self.state, L.ptr)
+        if motion is not None:
+            self.state["motion"] = torch.from_numpy(new_motion_state(self.S)).to(self.dev)
+
+    @property
+    def state_keys(self):
+        return STATE_KEYS + (("motion",) if self.motion is not None else ())
 
     def step(self, frame, boxes, emb, stream_of_frame, score=None, n=None, xinv=None):
         """One launch on the current stream.  frame (n,) int32 batch index of every face row, boxes (n, 4) fp32 (the
         info[:, 1:5] columns), emb (n, D) fp32, stream_of_frame (B,) int32 (-1: the frame is not tracked), score (n,) fp32
         or None; n: use the first n rows only (default: all); xinv: (n,) fp32 inverse norms of the rows of emb when the caller
         has them (default: fp_row_inv_norm here).  Device tensors; a frames / boxes tensor with a row stride (a
-        column slice of info) is made contiguous.  -> dict(track_id, track_hits, track_clock, track_flags), (n,) int32 each."""
+        column slice of info) is made contiguous.  -> dict(track_id, track_hits, track_clock, track_flags), (n,) int32 each;
+        with motion= also track_pred (n, 4) fp32: the box a matched row's track was predicted at, zeros for every other row."""
         n = int(emb.shape[0] if n is None else n)
         f32c = lambda t: t[:n].to(self.dev, torch.float32).contiguous()      # noqa: E731
         frame = frame[:n].to(self.dev, torch.int32).contiguous()
@@ -253,24 +381,37 @@ class StreamTracker:
         elif n:
             xinv = torch.empty((n,), dtype=torch.float32, device=self.dev)
             L.check(lib.fp_row_inv_norm(L.ptr(emb), n, self.D, L.ptr(xinv), L.current_stream(self.dev)), "fp_row_inv_norm")
-        L.check(lib.fp_tracklets_step(C.byref(self._struct), self.S, self.D, L.ptr(frame), L.ptr(boxes), L.ptr(emb), L.ptr(xinv),
-                                      L.ptr(score), n, L.ptr(sof), sof.shape[0], self.max_age, self.tau_near, self.tau_far,
-                                      self.iou_min, *[L.ptr(out[k]) for k in OUT_KEYS], L.current_stream(self.dev)),
-                "fp_tracklets_step")
+        rows = (C.byref(self._struct), self.S, self.D, L.ptr(frame), L.ptr(boxes), L.ptr(emb), L.ptr(xinv), L.ptr(score), n,
+                L.ptr(sof), sof.shape[0], self.max_age, self.tau_near, self.tau_far, self.iou_min, *[L.ptr(out[k]) for k in OUT_KEYS])
+        if self.motion is None:
+            L.check(lib.fp_tracklets_step(*rows, L.current_stream(self.dev)), "fp_tracklets_step")
+            return out
+        out["track_pred"] = torch.empty((n, 4), dtype=torch.float32, device=self.dev)
+        L.check(lib.fp_tracklets_step_motion(*rows, L.ptr(self.state["motion"]), self.motion.std_pos, self.motion.std_vel,
+                                             L.ptr(out["track_pred"]), L.current_stream(self.dev)), "fp_tracklets_step_motion")
         return out
 
     def tracks(self, stream):
         """The live slots of one stream (a host read): dict of numpy arrays slot, id, first_clock, last_clock, hits, box,
-        best_score, best_clock, best_box, best_emb, in slot order, and clock / next_id."""
+        best_score, best_clock, best_box, best_emb, in slot order, and clock / next_id; with motion= also pred_box (the box the
+        filter holds now: the prediction of the stream's last frame, or the update of a track matched in it) and velocity (the
+        filter's v of cx, cy, w, h, per frame)."""
         s = int(stream)
         if not 0 <= s < self.S:
             raise ValueError(f"stream {stream} outside 0 .. {self.S - 1}")
         hdr, si, sf = (self.state[k][s].cpu().numpy() for k in ("hdr", "slot_i", "slot_f"))
         live = np.nonzero(si[:, I_ID] != 0)[0]
-        return dict(slot=live, id=si[live, I_ID], first_clock=si[live, I_FIRST], last_clock=si[live, I_LAST],
-                    hits=si[live, I_HITS], box=sf[live, F_BOX:F_BOX + 4], best_score=sf[live, F_BEST_SCORE],
-                    best_clock=si[live, I_BEST_CLOCK], best_box=sf[live, F_BEST_BOX:F_BEST_BOX + 4],
-                    best_emb=self.state["best_emb"][s].cpu().numpy()[live], clock=int(hdr[0]), next_id=int(hdr[1]))
+        t = dict(slot=live, id=si[live, I_ID], first_clock=si[live, I_FIRST], last_clock=si[live, I_LAST],
+                 hits=si[live, I_HITS], box=sf[live, F_BOX:F_BOX + 4], best_score=sf[live, F_BEST_SCORE],
+                 best_clock=si[live, I_BEST_CLOCK], best_box=sf[live, F_BEST_BOX:F_BEST_BOX + 4],
+                 best_emb=self.state["best_emb"][s].cpu().numpy()[live], clock=int(hdr[0]), next_id=int(hdr[1]))
+        if self.motion is not None:
+            m = self.state["motion"][s].cpu().numpy()[live].reshape(len(live), 4, M_COLS)
+            cx, cy, w, h = (m[:, c, M_X] for c in range(4))
+            w, h = np.maximum(w, 0), np.maximum(h, 0)
+            t["pred_box"] = np.stack([cx - 0.5 * w, cy - 0.5 * h, cx + 0.5 * w, cy + 0.5 * h], axis=1).astype(np.float32)
+            t["velocity"] = m[:, :, M_V].copy()
+        return t
 
     def reset(self, streams=None):
         """Forget the tracks, clocks and ids of `streams` (an iterable of stream indices; None: all)."""
@@ -278,26 +419,32 @@ class StreamTracker:
         idx = slice(None) if streams is None else torch.as_tensor(list(streams), dtype=torch.long, device=self.dev)
         for k in STATE_KEYS:
             self.state[k][idx] = torch.from_numpy(fresh[k][0]).to(self.dev)
+        if self.motion is not None:
+            self.state["motion"][idx] = 0
 
     def state_dict(self):
         """A copy of the device state and the parameters (host tensors)."""
         d = {k: v.detach().cpu().clone() for k, v in self.state.items()}
         d["params"] = dict(n_streams=self.S, feat_dim=self.D, max_age=self.max_age, tau_near=self.tau_near,
                            tau_far=self.tau_far, iou_min=self.iou_min)
+        if self.motion is not None:
+            d["params"].update(std_pos=self.motion.std_pos, std_vel=self.motion.std_vel)
         return d
 
     def load_state_dict(self, d):
         """The arrays of a state_dict of a tracker with the same n_streams and feat_dim (ValueError otherwise), copied into
-        this tracker's own buffers; the parameters stay this tracker's."""
-        for k in STATE_KEYS:
+        this tracker's own buffers; the parameters stay this tracker's.  A tracker with motion= needs the "motion" array too
+        (KeyError without it); one without ignores it."""
+        for k in self.state_keys:
             if tuple(d[k].shape) != tuple(self.state[k].shape):
                 raise ValueError(f"state_dict[{k!r}] has shape {tuple(d[k].shape)}, this tracker {tuple(self.state[k].shape)}")
-        for k in STATE_KEYS:
+        for k in self.state_keys:
             self.state[k].copy_(torch.as_tensor(d[k]).to(self.state[k].dtype))
 
     def host_state(self):
-        """The state as a dict of numpy arrays (new_state's layout): what track_step_numpy / track_step_emulate continue from."""
-        return {k: self.state[k].detach().cpu().numpy().copy() for k in STATE_KEYS}
+        """The state as a dict of numpy arrays (new_state's layout, plus "motion" with motion=): what track_step_numpy /
+        track_step_emulate continue from."""
+        return {k: self.state[k].detach().cpu().numpy().copy() for k in self.state_keys}
 
 
 class TrackBook:

@@ -1423,6 +1423,55 @@ int fp_tracklets_step_emulate(const fp_track_state* state, int n_streams, int D,
                               int32_t* track_hits, int32_t* track_clock, int32_t* track_flags);
 
 /*
+ * Tracklets: motion prediction (build-defined; DESIGN §7 "Tracklets: motion prediction"; csrc/tracklets.hip,
+ * tracklets_kernel<true>).  Opt-in: fp_tracklets_step and its state are untouched.  All additive: ABI 14.
+ *
+ * Each slot carries four independent two-state filters, one per coordinate c of the centre form (cx, cy, w, h): the
+ * decomposition that DeepSORT's 8-state constant-velocity filter has anyway, its covariance never couples two coordinates.  Per
+ * slot and coordinate five fp32 values x, v, p00, p01, p11 (position, velocity per frame, covariance), in that order,
+ * coordinate after coordinate: a caller-owned state array
+ *   motion   [S][FP_TRACK_SLOTS][FP_TRACK_MOTION_FLOATS = 20] fp32, zero-filled for a fresh tracker.
+ * Two parameters, std_pos and std_vel, both finite and > 0: noise as a fraction of the box height.  All arithmetic fp32, one
+ * rounding per written operation, in the written order.
+ *   Measurement of a box.  z = (0.5f*(x1+x2), 0.5f*(y1+y2), x2-x1, y2-y1).
+ *   Scale.  hs(t) = t > 1.f ? t : 1.f (a NaN gives 1).
+ *   Init (a row opens a track; re-init below).  With H = hs(z_h): x = z, v = 0, p01 = 0, p00 = (2*std_pos*H)*(2*std_pos*H),
+ *     p11 = (10*std_vel*H)*(10*std_vel*H).
+ *   Predict: step 1b, in every frame of the stream, after expiry, for every live slot, whether or not the frame has rows.
+ *     H = hs(x_h), read before any coordinate of the slot is advanced; q0 = (std_pos*H)*(std_pos*H), q1 = (std_vel*H)*(std_vel*H).
+ *     Per coordinate, in this order: x = x + v; a = p01 + p11; p00 = ((p00 + p01) + a) + q0; p01 = a; p11 = p11 + q1.
+ *     The predicted box: pw = w > 0 ? w : 0, ph likewise; x1 = cx - 0.5f*pw, x2 = cx + 0.5f*pw, y1 = cy - 0.5f*ph, y2 = cy + 0.5f*ph.
+ *   Gate: step 2 takes its IoU with the predicted box where it took the last box.  Nothing else of steps 2-5 changes: the
+ *     admissibility rule, the key, the greedy walk, openings and best shot stay; slot_f's last box still receives the detection's.
+ *   Update, on a match, beside the slot rewrite.  H = hs(x_h) after this frame's prediction, r = (std_pos*H)*(std_pos*H).  Per
+ *     coordinate, the old p00 and p01 on the right-hand sides: s = p00 + r, k0 = p00/s, k1 = p01/s, y = z - x; x = x + k0*y,
+ *     v = v + k1*y; p11 = p11 - k1*p01, p01 = p01 - k1*p00, p00 = p00 - k0*p00.  If afterwards any of the slot's eight x, v values
+ *     fails t - t == 0, the slot is re-initialised from z as at opening.
+ *   Coasting.  Unmatched tracks keep their predicted state.
+ * New per-row output: track_pred [n][4] fp32, the predicted box the matched track had in that frame; every row that is not a
+ * match (an opening row, DEAD_ROW, FULL, NO_STREAM, OVER) gets four zeros.
+ * Out of scope: emitting rows for coasting tracks, Mahalanobis gating, camera-motion compensation, and any measured value of
+ * std_pos / std_vel (tracking.ConstantVelocity names DeepSORT's published 1/20 and 1/160, unmeasured here).
+ *
+ * fp_tracklets_step_motion: fp_tracklets_step's launch shape and promises (one launch, one workgroup per stream; the filters and
+ * the predicted boxes in LDS; no global atomics, no scratch, no host synchronisation); a workgroup whose stream owns no frame
+ * leaves without touching motion.  Refusals before any launch: everything fp_tracklets_step refuses, a NULL motion, a NULL
+ * track_pred with n > 0, a std_pos or std_vel that is not finite and > 0.
+ * fp_tracklets_step_motion_emulate: the same filter code serially on HOST memory (every pointer HOST), the same bits.
+ */
+#define FP_TRACK_MOTION_FLOATS 20
+int fp_tracklets_step_motion(const fp_track_state* state /*host struct*/, int n_streams, int D, const int32_t* frame,
+                             const float* box, const float* emb, const float* xinv, const float* score /* or NULL */, int n,
+                             const int32_t* stream_of_frame /* B */, int B, int max_age, float tau_near, float tau_far,
+                             float iou_min, int32_t* track_id, int32_t* track_hits, int32_t* track_clock, int32_t* track_flags,
+                             float* motion, float std_pos, float std_vel, float* track_pred /* n x 4 */, void* stream);
+int fp_tracklets_step_motion_emulate(const fp_track_state* state, int n_streams, int D, const int32_t* frame, const float* box,
+                                     const float* emb, const float* xinv, const float* score, int n,
+                                     const int32_t* stream_of_frame, int B, int max_age, float tau_near, float tau_far,
+                                     float iou_min, int32_t* track_id, int32_t* track_hits, int32_t* track_clock,
+                                     int32_t* track_flags, float* motion, float std_pos, float std_vel, float* track_pred);
+
+/*
  * Tracker evaluation: CLEAR-MOT and IDF1 (build-defined, the reference calls no tracking scorer; DESIGN §7 "Tracker
  * evaluation"; csrc/moteval.hip; tracking_eval.py holds the numpy restatement and the host half).  All additive: ABI 14.
  *

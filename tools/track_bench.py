@@ -8,8 +8,11 @@
 Per layout, milliseconds per step of 256 frames: tracklets_ms (one launch, fp_row_inv_norm included) and per_frame_ms (the
 same rows through FaceTracker.track, one call per frame -- layout a: one FaceTracker per stream), and their ratio.  The two
 apply different rules (greedy one-to-one with expiry against first match); the comparison is of cost, not of answers.
-Then the pipeline: FacePipeline.step on 256 synthetic frames with and without tracker=, and step_overlapped with two_streams
-(the tracker on the side stream) with and without.  Timed with device events after warm-up, `--iters` calls per round,
+The motion leg: per layout a second StreamTracker with motion=ConstantVelocity (fp_tracklets_step_motion) on the same rows,
+timed in the same process in rounds that alternate with the plain tracker's: motion_off_ms, motion_on_ms and
+motion_cost_us_per_frame = their medians' difference over the frames one workgroup marches (1, 256, 256).
+Then the pipeline: FacePipeline.step on 256 synthetic frames without tracker=, with it, and with a tracker with motion=, and
+step_overlapped with two_streams (the tracker on the side stream) likewise.  Timed with device events after warm-up, `--iters` calls per round,
 `--rounds` rounds; median with min .. max.  Prints one JSON line.  No pass / fail threshold.
 
   python tools/track_bench.py [--iters 10] [--rounds 5] [--small] [--no-pipeline]
@@ -29,9 +32,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from face_detection_and_recognition_amd import workload as W  # noqa: E402
 from face_detection_and_recognition_amd.face_extraction.face_tracker import FaceTracker  # noqa: E402
 from face_detection_and_recognition_amd.pipeline import FacePipeline  # noqa: E402
-from face_detection_and_recognition_amd.tracking import StreamTracker  # noqa: E402
+from face_detection_and_recognition_amd.tracking import ConstantVelocity, StreamTracker  # noqa: E402
 
 D = 512
+MOTION = ConstantVelocity(ConstantVelocity.DEEPSORT_STD_POS, ConstantVelocity.DEEPSORT_STD_VEL)   # the cost does not depend on them
 
 
 def timed(fn, reps, dev):
@@ -93,6 +97,18 @@ def measure_layout(name, rows, max_age, args, dev):
     rec["tracklets_ms"] = summary([timed(step, args.iters, dev) for _ in range(args.rounds)])
     rec["per_frame_ms"] = summary([timed(loop, max(1, args.iters // 5), dev) for _ in range(args.rounds)])
     rec["per_frame_over_tracklets"] = round(rec["per_frame_ms"]["median"] / rec["tracklets_ms"]["median"], 2)
+    trm = StreamTracker(rows["n_streams"], D, max_age, device=dev, motion=MOTION)
+    mstep = lambda: trm.step(rows["frame"], rows["boxes"], rows["emb"], rows["sof"])   # noqa: E731
+    mstep()
+    mstep()
+    torch.cuda.synchronize()
+    off, on = [], []
+    for _ in range(args.rounds):            # alternated: both see the same machine
+        off.append(timed(step, args.iters, dev))
+        on.append(timed(mstep, args.iters, dev))
+    rec["motion_off_ms"], rec["motion_on_ms"] = summary(off), summary(on)
+    rec["motion_cost_us_per_frame"] = round((rec["motion_on_ms"]["median"] - rec["motion_off_ms"]["median"]) * 1000.0
+                                            / (rows["B"] // rows["n_streams"]), 3)
     return rec
 
 
@@ -103,8 +119,8 @@ def measure_pipeline(n_frames, args, dev):
     ref = W.make_reference(256, dev)
     rec = dict(frames=n_frames)
     for two in (False, True):
-        for with_tracker in (False, True):
-            tr = StreamTracker(1, D, 8, device=dev) if with_tracker else None
+        for kind in ("plain", "tracker", "motion"):
+            tr = None if kind == "plain" else StreamTracker(1, D, 8, device=dev, motion=MOTION if kind == "motion" else None)
             pipe = FacePipeline(det, emb, ref, tau=0.0, two_streams=two, tracker=tr)
             if two:
                 def fn():
@@ -121,9 +137,10 @@ def measure_pipeline(n_frames, args, dev):
             if two:
                 rec["n_faces"] = pipe.flush()["n_faces"]
             torch.cuda.synchronize()
-            rec[("overlapped_" if two else "step_") + ("tracker_ms" if with_tracker else "plain_ms")] = summary(ts)
+            rec[("overlapped_" if two else "step_") + kind + "_ms"] = summary(ts)
     for k in ("step", "overlapped"):
         rec[k + "_tracker_cost_ms"] = round(rec[k + "_tracker_ms"]["median"] - rec[k + "_plain_ms"]["median"], 4)
+        rec[k + "_motion_cost_ms"] = round(rec[k + "_motion_ms"]["median"] - rec[k + "_tracker_ms"]["median"], 4)
     return rec
 
 

@@ -109,7 +109,6 @@ static int spans_dwblock(const fp_op& op, size_t wf, size_t) {
   const bool x6 = (op.flags & FP_OPF_SPLIT3) != 0;
   if (!span_ok(op.w_off, x6 ? fp_dwblock_x6_we_floats(op) : (int64_t)op.Cin * op.Cmid, wf)) return FP_ERR_BOUNDS;
   if (!span_ok(op.scale_off, 15 * (int64_t)op.Cmid, wf)) return FP_ERR_BOUNDS;
-  if ((op.flags & FP_OPF_IN_DW) && !span_ok(op.bias_off, 12 * (int64_t)op.Cin, wf)) return FP_ERR_BOUNDS;
   const int64_t wp = x6 ? fp_dwblock_x6_wp_floats(op) : (int64_t)op.Cmid * op.Cout + 2 * (int64_t)op.Cout;
   return span_ok(op.slope_off, wp, wf) ? FP_OK : FP_ERR_BOUNDS;
 }
@@ -185,7 +184,7 @@ static constexpr kind_row k_kinds[] = {
     {fp_launch_ystem, T_CONVLIKE, FP_OPF_IN_C3, spans_ystem},
     {fp_launch_ystem_u8, T_CONVLIKE | T_EXT_IN, 0, spans_ystem},
     {fp_launch_stem_u8, T_CONVLIKE | T_EXT_IN | T_ROWWIN | T_EPILOGUE | T_W_FIRST, FP_OPF_OUT_ROWPAD | FP_OPF_SPLIT3, spans_stem_u8},
-    {fp_launch_dwblock, T_CONVLIKE | T_CMID | T_RES, FP_OPF_SPLIT3 | FP_OPF_IN_DW, spans_dwblock, is_split3, fp_launch_dwblock_x6},
+    {fp_launch_dwblock, T_CONVLIKE | T_CMID | T_RES, FP_OPF_SPLIT3, spans_dwblock, is_split3, fp_launch_dwblock_x6},
     {fp_launch_blazepair, T_CONVLIKE | T_ROWWIN, ROWPADS, spans_blazepair, is_stride2, fp_launch_blazepair_s2},
     {fp_launch_blazechain, T_CONVLIKE | T_CMID, FP_OPF_SPLIT3, spans_blazechain},
     {fp_launch_shufdown, T_CONVLIKE | T_CMID | T_ACT2, FP_OPF_SPLIT3, spans_shufdown},
@@ -232,9 +231,9 @@ static int validate_op(const fp_op& op, size_t weight_floats, size_t arena_float
   }
   if (Cout <= 0 || op.out_cmul < 1 || op.in_ld < op.Cin) return FP_ERR_INVALID_ARG;
   // flags (facepath.h FP_OPF_*): a bit the kind may not carry is an argument error, a row-padded view it does not take is
-  // unsupported; IN_DW on a kind that may not carry it is refused behind the spans of OUT_DW and IN_UP2
+  // unsupported
   const int32_t refused = op.flags & ~k.flags;
-  if (refused & ~(ROWPADS | FP_OPF_IN_DW)) return FP_ERR_INVALID_ARG;
+  if (refused & ~ROWPADS) return FP_ERR_INVALID_ARG;
   if (op.flags & FP_OPF_OUT_DW) {
     // Mobile-FaceNet's conv1 + conv2_dw: the conv's slopes are followed by the depthwise block's [12][Cout]
     if (!span_ok(op.slope_off, 13 * (int64_t)op.Cout, weight_floats)) return FP_ERR_BOUNDS;
@@ -245,7 +244,6 @@ static int validate_op(const fp_op& op, size_t weight_floats, size_t arena_float
     if (!(op.flags & FP_OPF_SPLIT3)) return FP_ERR_INVALID_ARG;
     if (!span_ok(op.res_off, res_extent(op, (int64_t)op.res_H * op.res_W, op.res_C), arena_floats)) return FP_ERR_BOUNDS;
   }
-  if ((op.flags & FP_OPF_IN_DW) && ((refused & FP_OPF_IN_DW) || !(op.flags & FP_OPF_SPLIT3))) return FP_ERR_INVALID_ARG;
   if ((op.flags & FP_OPF_IN_C3) && op.Cin != 4) return FP_ERR_INVALID_ARG;
   const bool in_rp = (op.flags & FP_OPF_IN_ROWPAD) != 0, out_rp = (op.flags & FP_OPF_OUT_ROWPAD) != 0;
   if (refused) return FP_ERR_UNSUPPORTED;

@@ -1,11 +1,10 @@
 // stemdw.hip — Mobile-FaceNet's first two layers in one kernel (gfx950):
 //     conv1    = Conv_block(3, 64, 3x3, stride 2, pad 1): conv -> BN -> PReLU      (mobile_facenet.py:107, :141)
 //     conv2_dw = Conv_block(64, 64, 3x3, stride 1, pad 1, groups 64): depthwise conv -> BN -> PReLU  (:108, :142)
-// FP_OP_CONV + FP_OPF_OUT_DW (include/facepath.h).  conv1's 56 x 56 x 64 output (803 KB per crop) used to be written by the
-// stem kernel (stem.hip, at the rate this part writes memory: 123 us per 512 crops) and read back by the depthwise conv in
-// the prologue of conv_23's kernel (dwblockx6.hip FP_OPF_IN_DW: an LDS image of conv1's rows, nine b128 reads per element,
-// +143 us on that kernel).  Here conv1's rows never leave the CU: the depthwise conv runs on them in LDS and its output --
-// the same bytes the stem alone wrote -- is what goes to memory; conv_23 then runs in its plain form.
+// FP_OP_CONV + FP_OPF_OUT_DW (include/facepath.h).  conv1's 56 x 56 x 64 output (803 KB per crop, 123 us per 512 crops at
+// the rate this part writes memory when the stem kernel, stem.hip, writes it) never leaves the CU: the depthwise conv runs
+// on conv1's rows in LDS and its output -- as many bytes as the stem alone would write -- is what goes to memory, where
+// conv_23's kernel (dwblockx6.hip) reads it.
 //   tile     = RB = 4 output rows x 56 columns x 64 channels of one crop, one 256-thread workgroup, two per CU (<= 78 KiB)
 //   stage    = the 13 input rows (4-float pixels, zero borders) of the tile's 6 conv1 rows (halo rows recomputed: 6 for 4);
 //              persistent workgroups: the NEXT tile's rows are loaded into registers while the current tile computes (a tile's

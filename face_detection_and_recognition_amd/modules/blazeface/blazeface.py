@@ -6,8 +6,6 @@
   _weighted_non_max_suppression (:404-458)        -> fp_blaze_weighted_nms  (csrc/post.hip)
   _preprocess x/127.5-1 (:248-250)                -> LUT inside fp_resize_normalize (csrc/image.hip)
 """
-import os
-
 import numpy as np
 import torch
 import torch.nn as nn
@@ -51,9 +49,9 @@ class BlazeBlock(_NoCompute):
 
     FUSE = True   # class-wide switch: False emits the unfused DWCONV + CONV pair (A/B parity tests)
     ROWPAD = True  # class-wide switch: False keeps every activation dense (A/B parity tests)
-    PAIR = os.environ.get("FP_BLAZE_PAIR", "1") == "1"    # class-wide switch: two consecutive stride-1 24 -> 24 blocks as ONE op (FP_OP_BLAZEPAIR, csrc/blazepair.hip)
+    PAIR = True    # class-wide switch: two consecutive stride-1 24 -> 24 blocks as ONE op (FP_OP_BLAZEPAIR, csrc/blazepair.hip)
 
-    CHAIN = os.environ.get("FP_BLAZE_CHAIN", "1") == "1"   # class-wide switch: a run of stride-1 96 -> 96 blocks on the 16 x 16 map as ONE op (FP_OP_BLAZECHAIN, csrc/blazechain.hip)
+    CHAIN = True   # class-wide switch: a run of stride-1 96 -> 96 blocks on the 16 x 16 map as ONE op (FP_OP_BLAZECHAIN, csrc/blazechain.hip)
 
     def chains(self):
         """True if this block can be a member of an FP_OP_BLAZECHAIN run."""
@@ -64,8 +62,8 @@ class BlazeBlock(_NoCompute):
         blocks (PAIR) whose op the launcher takes."""
         return BlazeBlock.PAIR and self._pair_taken(other, 1, pb, x)
 
-    PAIR_S2 = os.environ.get("FP_BLAZE_PAIR_S2", "1") == "1"   # class-wide switch: the single stride-1 24 -> 24 block that ends a stage and
-                                                                # the stride-2 block behind it as ONE op (csrc/blazepair.hip)
+    PAIR_S2 = True   # class-wide switch: the single stride-1 24 -> 24 block that ends a stage and the stride-2 block behind it
+                     # as ONE op (csrc/blazepair.hip)
 
     def pairs_with_s2(self, other, pb, x):
         """True if self (stride 1, 24 -> 24) followed by the stride-2 block `other`, fed the row-padded view x, runs as one
@@ -196,7 +194,7 @@ class BlazeFace(PlanCacheMixin, nn.Module):
     # class-wide switch: the back model's 5 x 5 stem on u8 frames on the bf16 matrix cores (FP_OP_STEM_U8 + FP_OPF_SPLIT3,
     # stem5_u8_x6_kernel; needs PlanBuilder.X6 as every split kernel does).  False: the fp32-MFMA band kernel, whose results are
     # bit-identical to the stand-alone letterbox + conv (the tests of that identity switch it off)
-    STEM_X6 = os.environ.get("FP_BLAZE_STEM_X6", "1") == "1"
+    STEM_X6 = True
 
     def __init__(self, back_model=False):
         super().__init__()
@@ -273,7 +271,7 @@ class BlazeFace(PlanCacheMixin, nn.Module):
     # class-wide switch: on a letterboxed frame (u8 plans, back model, batch >= 16) the stem and the pair kernels of the 128 x 128
     # and 64 x 64 stages compute only the rows that depend on the frame's content (row windows, include/facepath.h); the
     # rest, which only the pad colour reaches, is left from the plan's unrestricted runs (CompiledPlan).  False: every row
-    ROW_WINDOW = os.environ.get("FP_BLAZE_ROW_WINDOW", "1") == "1"
+    ROW_WINDOW = True
 
     def _emit(self, N, frame_hw=None):
         """Emit the op list for batch N (host only, no GPU needed).  frame_hw = (frame_h, frame_w): the stem reads u8
@@ -290,7 +288,7 @@ class BlazeFace(PlanCacheMixin, nn.Module):
         blocks = seq[2:]
 
         def chain_len(i, h, w):    # blocks[i:i + n] on an h x w map run as one FP_OP_BLAZECHAIN (0: they do not)
-            if not (BlazeBlock.FUSE and BlazeBlock.CHAIN and (not self.co_scheduled or os.environ.get("FP_CHAIN_CO") == "1") and
+            if not (BlazeBlock.FUSE and BlazeBlock.CHAIN and not self.co_scheduled and
                     PlanBuilder.X6 and (h, w) == (16, 16)):
                 return 0
             n = 0
@@ -406,8 +404,7 @@ class BlazeFace(PlanCacheMixin, nn.Module):
     def plan_for(self, N, frame_hw=None):
         if self._device().type != "cuda":
             raise L.FacepathError("BlazeFace runs only on a HIP device (model.to('cuda')); there is no CPU path")
-        key = (N, frame_hw, self.co_scheduled, os.environ.get("FP_CHAIN_CO") == "1",
-               switch_key(PlanBuilder, BlazeBlock, BlazeFace))
+        key = (N, frame_hw, self.co_scheduled, switch_key(PlanBuilder, BlazeBlock, BlazeFace))
         return self._plans.get(key, lambda cache: self._build(N, cache, frame_hw))
 
     # ------------------------------------------------------------------ inference

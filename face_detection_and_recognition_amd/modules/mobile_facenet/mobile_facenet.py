@@ -115,29 +115,24 @@ class Depth_Wise(_NoCompute, metaclass=_X6Switch):
             shapes.append(7)
         return tuple(shapes)
 
-    def emit(self, pb, x, expanded=None, in_dw=None):
-        """expanded: the output of self.conv when the caller has already produced it (fused into the previous
-        depthwise Conv_block, see MobileFaceNet._emit); x is then only the residual source.  in_dw: a depthwise
-        Conv_block that precedes this block and is computed inside its kernel (FP_OPF_IN_DW: conv2_dw + conv_23); None
-        (nothing emitted) if no kernel takes the block in that form."""
+    def emit(self, pb, x):
+        """The block on view x: ONE op where a whole-block kernel takes it, else the 1x1 expand followed by the fused
+        dw -> 1x1 op, else (FUSE off) the three convs."""
         dw, pj, ex = self.conv_dw, self.project, self.conv
         shapes = Depth_Wise.BLOCK_SHAPES
         if shapes is None:
             shapes = pb.dwblock_shapes
         if shapes is None:
             shapes = Depth_Wise.block_policy(pb.N)
-        if Depth_Wise.FUSE and expanded is None and dw.k == 3 and dw.p == 1:
+        if Depth_Wise.FUSE and dw.k == 3 and dw.p == 1:
             # the whole block as one op: the split kernel wherever it takes the block, the fp32 one on the map sizes of `shapes`
             y = pb.new_buf(x.H // dw.s, x.W // dw.s, pj.out_c, peek=True)
             if pb.dwblock(x, npy(ex.conv.weight), _affine(ex.bn), npy(ex.prelu.weight),
                           npy(dw.conv.weight), _affine(dw.bn), npy(dw.prelu.weight),
                           npy(pj.conv.weight), _affine(pj.bn), y.view(), self.residual, stride=dw.s,
-                          in_dw=None if in_dw is None else (npy(in_dw.conv.weight), _affine(in_dw.bn), npy(in_dw.prelu.weight)),
                           fp32=x.H in shapes) is not None:
                 return pb.take(y)
-        if in_dw is not None:
-            return None
-        a = expanded if expanded is not None else self.conv.emit(pb, x)
+        a = self.conv.emit(pb, x)
         if (Depth_Wise.FUSE and dw.k == 3 and dw.p == 1 and dw.groups % 64 == 0 and pj.out_c % 4 == 0 and
                 pj.out_c <= 128):
             OH = (a.H + 2 - 3) // dw.s + 1
@@ -180,11 +175,6 @@ class MobileFaceNet(PlanCacheMixin, nn.Module):
     """mobile_facenet.py:104-154.  ``forward(x)``: (b, 3, 112, 112) float in [-1, 1] (BGR, as
     mobile_facenet/utils.py:13-17 feeds it) -> (b, embedding_size) unit-norm embeddings."""
 
-    # conv2_dw + conv_23: True = depthwise launch + whole-block split-MFMA kernel; False = the round-2 pair of dw->pw kernels
-    X6_CONV23 = True
-    X6_CONV2_IN = True    # ... with conv2_dw inside that kernel's prologue (False: a separate depthwise launch)
-    STEM_DW = True        # conv1 + conv2_dw as ONE kernel (FP_OPF_OUT_DW, csrc/stemdw.hip); conv_23 then takes conv2_dw's output
-
     def __init__(self, embedding_size):
         super().__init__()
         self.embedding_size = embedding_size
@@ -212,46 +202,21 @@ class MobileFaceNet(PlanCacheMixin, nn.Module):
         pb = PlanBuilder(N, dwblock_shapes=block_shapes)
         inp = pb.new_buf(H, W, 3)
         c1, c2, c23 = self.conv1, self.conv2_dw, self.conv_23
-        stem_dw = False
-        if (Depth_Wise.FUSE and MobileFaceNet.STEM_DW and c1.groups == 1 and (c1.k, c1.s, c1.p) == (3, 2, 1) and
+        x = None
+        if (Depth_Wise.FUSE and c1.groups == 1 and (c1.k, c1.s, c1.p) == (3, 2, 1) and
                 (c2.k, c2.s, c2.p) == (3, 1, 1) and c2.groups == c2.in_c == c2.out_c == c1.out_c):
-            # conv1 + conv2_dw in ONE kernel (FP_OPF_OUT_DW, csrc/stemdw.hip): conv1's 56 x 56 x 64 rows stay in LDS, the
-            # depthwise conv runs on them there; conv_23 below then runs in its plain form (no FP_OPF_IN_DW prologue)
+            # conv1 + conv2_dw in ONE kernel where the launcher takes them (FP_OPF_OUT_DW, csrc/stemdw.hip): conv1's
+            # 56 x 56 x 64 rows stay in LDS, the depthwise conv runs on them there
             y = pb.new_buf(H // 2, W // 2, c1.out_c, peek=True)
             s1, b1 = _affine(c1.bn)
-            stem_dw = pb.conv(inp.view(), npy(c1.conv.weight), y.view(), stride=2, pad=(1, 1), scale=s1, bias=b1,
-                              slope=npy(c1.prelu.weight), act=L.ACT_PRELU,
-                              out_dw=(npy(c2.conv.weight), _affine(c2.bn), npy(c2.prelu.weight))) is not None
-            if stem_dw:
+            if pb.conv(inp.view(), npy(c1.conv.weight), y.view(), stride=2, pad=(1, 1), scale=s1, bias=b1,
+                       slope=npy(c1.prelu.weight), act=L.ACT_PRELU,
+                       out_dw=(npy(c2.conv.weight), _affine(c2.bn), npy(c2.prelu.weight))) is not None:
                 x = pb.take(y)
-        if not stem_dw:
+        if x is None:
             x = c1.emit(pb, inp.view())
-        # conv2_dw + ALL of conv_23 (expand -> dw stride 2 -> project) as one split-MFMA kernel where it takes them: conv2_dw
-        # is formed in the kernel's prologue from an LDS image of conv1's rows (FP_OPF_IN_DW); neither its output (424 MB
-        # at 528 crops) nor the 128-channel 56x56 tensor (848 MB) ever exists
-        conv2_in = (not stem_dw and Depth_Wise.FUSE and Depth_Wise.X6 and MobileFaceNet.X6_CONV23 and
-                    MobileFaceNet.X6_CONV2_IN and c2.k == 3 and c2.s == 1 and c2.p == 1 and c2.groups == c2.in_c == c2.out_c)
-        y = c23.emit(pb, x.view(), in_dw=c2) if conv2_in else None
-        if y is not None:
-            pb.free(x); x = y
-        elif stem_dw or (Depth_Wise.FUSE and Depth_Wise.X6 and MobileFaceNet.X6_CONV23 and not MobileFaceNet.X6_CONV2_IN):
-            if not stem_dw:      # conv2_dw as a launch of its own, then conv_23 (as one op where the launcher takes it)
-                y = c2.emit(pb, x.view()); pb.free(x); x = y
-            y = c23.emit(pb, x.view()); pb.free(x); x = y
-        elif Depth_Wise.FUSE and c2.k == 3 and c2.s == 1 and c2.p == 1 and c2.groups % 64 == 0 and not c23.residual:
-            # conv2_dw (dw3x3 + BN + PReLU) -> conv_23.conv (1x1 + BN + PReLU) as ONE dw->pw kernel: the 64-channel
-            # 56x56 tensor between them (873 MB at N = 1088) never goes to HBM
-            ex = c23.conv
-            a = pb.new_buf(x.H, x.W, ex.out_c)
-            ds, db = _affine(c2.bn)
-            es, eb = _affine(ex.bn)
-            pb.dwpw(x.view(), npy(c2.conv.weight), ds, db, npy(c2.prelu.weight), npy(ex.conv.weight), es, eb,
-                    a.view(), 1, out_slope=npy(ex.prelu.weight))
-            pb.free(x)
-            x = c23.emit(pb, None, expanded=a)
-        else:
             y = c2.emit(pb, x.view()); pb.free(x); x = y
-            y = c23.emit(pb, x.view()); pb.free(x); x = y
+        y = c23.emit(pb, x.view()); pb.free(x); x = y
         x = self.conv_3.emit(pb, x)
         y = self.conv_34.emit(pb, x.view()); pb.free(x); x = y
         x = self.conv_4.emit(pb, x)

@@ -11,8 +11,6 @@ to multiples of 4 (16-byte accesses) with zero weights in the padding.
 import ctypes as C
 from dataclasses import dataclass
 
-import os
-
 import numpy as np
 
 from . import _lib as L
@@ -395,19 +393,18 @@ class PlanBuilder:
     # Master switch of the bf16x6 split-MFMA kernels (csrc/split.h): False = every GEMM on the fp32 MFMA (the fmaf-chain
     # kernels of rounds 1-3).  Mobile-FaceNet's Depth_Wise.X6 is this attribute.
     X6 = True
-    # Pointwise convs with K >= PW_X6_MIN_K input channels on the split kernel; 0 = never.
+    # Pointwise convs with K >= PW_X6_MIN_K input channels on the split kernel.
     # (YOLOv5n-face forward at batch 256: 18.2 ms with 128, 17.0 ms with 64, 17.5 ms with 32.)
-    PW_X6_MIN_K = int(os.environ.get("FP_PW_X6_MIN_K", "64"))         # (the environment variables are lab knobs)
-    # Dense 3x3 convs (pad 1, stride 1 / 2) with at least this many input channels on the split kernel as well; 0 = never.
-    CONV3_X6_MIN_K = int(os.environ.get("FP_CONV3_X6_MIN_K", "32"))
-    # ... and those on 8 / 16 / 24 input channels, with K flattened over (tap, channel) (YOLOv5n-face's stem_2b, 16 -> 32
+    PW_X6_MIN_K = 64
+    # Dense 3x3 convs (pad 1, stride 1 / 2) with at least this many input channels on the split kernel as well,
+    # and those on 8 / 16 / 24 input channels, with K flattened over (tap, channel) (YOLOv5n-face's stem_2b, 16 -> 32
     # stride 2 at 320x320: 945 us on conv_igemm_kernel)
-    CONV3_X6_FLAT = os.environ.get("FP_CONV3_X6_FLAT", "1") == "1"
+    CONV3_X6_MIN_K = 32
     X6_SMALL_K_MIN_PIXELS = 400   # below 128 input channels only on maps of at least 20 x 20 (measured on YOLOv5-face; the
                                   # small-map 1x1 convs of BlazeFace stay on the fp32-MFMA kernels)
     X6_MIN_COUT = 48              # from 32 input channels on, at least 48 outputs (32: a third of the three-tile chunk would
                                   # be padding)
-    UP2_FOLD = os.environ.get("FP_UP2_FOLD", "1") == "1"   # nn.Upsample + Concat in front of a pointwise conv as operand addressing
+    UP2_FOLD = True               # nn.Upsample + Concat in front of a pointwise conv as operand addressing
 
     def x6_policy(self, x, out, kh, kw, stride, pad):
         """True if the size policy above sends this conv to the split kernels (where the launcher takes it).  The policy
@@ -419,10 +416,9 @@ class PlanBuilder:
         k3 = (kh, kw, *pad) == (3, 3, 1, 1)
         if self.x6_all or not (k1 or k3):
             return True
-        if k1 and (not self.PW_X6_MIN_K or x.C < self.PW_X6_MIN_K):
+        if k1 and x.C < self.PW_X6_MIN_K:
             return False
-        if k3 and (not self.CONV3_X6_MIN_K or
-                   (x.C < self.CONV3_X6_MIN_K and not (self.CONV3_X6_FLAT and x.C in (8, 16, 24)))):
+        if k3 and x.C < self.CONV3_X6_MIN_K and x.C not in (8, 16, 24):
             return False
         if x.C < 128 and out.H * out.W < self.X6_SMALL_K_MIN_PIXELS:
             return False
@@ -642,8 +638,7 @@ class PlanBuilder:
         self.alg_bytes.append(len(blocks) * 4 * self.N * 256 * 96 * 4)     # four tensor passes per block
         return out
 
-    DWPW_X6 = os.environ.get("FP_DWPW_X6", "1") == "1"    # the dw -> 1x1 op with its 1x1 on the split MFMA (csrc/dwpwx6.hip)
-    # ... for 128 outputs only: measured on YOLOv5n-face (256 images): 128 -> 128 at 40x40 278 -> 246 us, 80x80 stride 2
+    # The dw -> 1x1 op with its 1x1 on the split MFMA (csrc/dwpwx6.hip) for 128 outputs only: measured on YOLOv5n-face (256 images): 128 -> 128 at 40x40 278 -> 246 us, 80x80 stride 2
     # 367 / 298 -> 345 / 248; 64 -> 64 at 80x80 420 -> 440 (the depthwise phase, not the 1x1, bounds the narrow form)
     DWPW_X6_COUT = 128
 
@@ -652,7 +647,7 @@ class PlanBuilder:
         """Fused Depth_Wise tail (mobile_facenet.py:72-85): dw3x3 stride s (+BN affine, +PReLU) -> 1x1 (+BN affine)
         [+ res], or -- with out_slope -- a depthwise Conv_block followed by a 1x1 Conv_block (BN + PReLU on both:
         conv2_dw -> conv_23.conv, mobile_facenet.py:117-118,70).  x has G (multiple of 64) channels.  The 1x1 runs on the
-        split MFMA (FP_OPF_SPLIT3, its weights as k-slab planes: csrc/dwpwx6.hip) when DWPW_X6 and DWPW_X6_COUT allow it and
+        split MFMA (FP_OPF_SPLIT3, its weights as k-slab planes: csrc/dwpwx6.hip) when X6 and DWPW_X6_COUT allow it and
         the launcher takes the op."""
         G = dw_w.shape[0]
         cout, cin = pw_w.shape[0], pw_w.shape[1]
@@ -678,8 +673,7 @@ class PlanBuilder:
                 self._set_res(op, res, min(res.C, out.C))
             return op
 
-        split = (self.X6 and self.DWPW_X6 and out.C == self.DWPW_X6_COUT and
-                 self.probe(make(L.OPF_SPLIT3)) is not None)
+        split = self.X6 and out.C == self.DWPW_X6_COUT and self.probe(make(L.OPF_SPLIT3)) is not None
         op = make(L.OPF_SPLIT3 if split else 0)
         op.w_off = self.add_weight(dw_rows(dw_w, (dw_scale, dw_bias), dw_slope, G))
         if split:
@@ -697,15 +691,12 @@ class PlanBuilder:
         self.alg_bytes.append(4 * self.N * (x.H * x.W * G + opix * G + opix * G + opix * cout))
         return out
 
-    def dwblock(self, x, e_w, e_aff, e_slope, dw_w, dw_aff, dw_slope, pw_w, pw_aff, out, residual, stride=1, in_dw=None,
-                fp32=True):
+    def dwblock(self, x, e_w, e_aff, e_slope, dw_w, dw_aff, dw_slope, pw_w, pw_aff, out, residual, stride=1, fp32=True):
         """A whole Depth_Wise block (mobile_facenet.py:67-88) as ONE op (FP_OP_DWBLOCK): 1x1 expand + BN + PReLU -> dw3x3
         (stride) + BN + PReLU -> 1x1 project + BN [+ x]; the expanded tensor stays in LDS.  *_aff = (scale, bias) of the
         eval-mode BatchNorm.  The split form (FP_OPF_SPLIT3, csrc/dwblockx6.hip) when X6 is on and the launcher takes it,
         else the fp32 form (csrc/dwblock.hip) if the caller's policy allows it (`fp32`) and the launcher takes it, else None
-        (nothing emitted).
-        in_dw = (weights [Cin,1,3,3], (scale, bias), PReLU slope) of a depthwise 3x3 stride-1 Conv_block in front of the block,
-        computed in the kernel's prologue (FP_OPF_IN_DW: conv2_dw + conv_23 of Mobile-FaceNet); its dw_rows go to bias_off."""
+        (nothing emitted)."""
         cmid, cin = e_w.shape[0], e_w.shape[1]
         cout = pw_w.shape[0]
         assert dw_w.shape == (cmid, 1, 3, 3) and pw_w.shape[1] == cmid
@@ -717,18 +708,17 @@ class PlanBuilder:
             op.Cout, op.Cmid = cout, cmid
             self._set_window(op, 3, stride, 1)
             op.act = L.ACT_PRELU
-            self._offsets(op, True, True, in_dw is not None, True)
+            self._offsets(op, True, True, False, True)
             if residual:
                 op.res_mode = L.RES_ADD_AFTER_ACT
                 self._set_res(op, x, cin)
             return op
 
-        in_flag = L.OPF_IN_DW if in_dw is not None else 0
         forms = ([L.OPF_SPLIT3] if self.X6 else []) + ([0] if fp32 else [])
-        split = next((f for f in forms if self.probe(make(f | in_flag)) is not None), None)
+        split = next((f for f in forms if self.probe(make(f)) is not None), None)
         if split is None:
             return None
-        op = make(split | in_flag)
+        op = make(split)
         if split:      # include/facepath.h, DWBLOCK: the expand matrix in row blocks, the projection in k-slabs
             op.w_off = self.add_weight(pack_rowblock_x6(_mat(e_w)))
             wp = pack_kslab_x6(_mat(pw_w))
@@ -739,14 +729,9 @@ class PlanBuilder:
                                                        dw_rows(dw_w, dw_aff, dw_slope, cmid)]))
         op.slope_off = self.add_weight(np.concatenate([wp, affine_rows(pw_aff, cout)]))
         pix, opix = x.H * x.W, out.H * out.W
-        extra = 0
-        if in_dw is not None:
-            assert in_dw[0].shape == (cin, 1, 3, 3)
-            op.bias_off = self.add_weight(dw_rows(*in_dw, cin))
-            extra = pix * 2 * cin
         self.ops.append(op)
-        # the three convs of the block (+ the depthwise conv in front), each input once + output once
-        self.alg_bytes.append(4 * self.N * (extra + pix * (cin + cmid) + (pix + opix) * cmid + opix * (cmid + cout)))
+        # the three convs of the block, each input once + output once
+        self.alg_bytes.append(4 * self.N * (pix * (cin + cmid) + (pix + opix) * cmid + opix * (cmid + cout)))
         return out
 
     def _shuf_op(self, kind, x, out, cb, stride):

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define FP_ABI_VERSION 14
+#define FP_ABI_VERSION 15
 
 typedef enum fp_status {
   FP_OK = 0,
@@ -205,14 +205,7 @@ typedef struct fp_op {
  *                to 16 k, the sixth ky and channels 24 .. 31 zero).  The semantics of the ops do not change.
  */
 #define FP_OPF_SPLIT3 8
-/*
- * FP_OPF_IN_DW (ABI 5) : an FP_OP_DWBLOCK whose input first passes through a depthwise 3x3 stride-1 Conv_block (conv + BN +
- *                PReLU, mobile_facenet.py:39-51) -- Mobile-FaceNet's conv2_dw in front of conv_23 (:107-108,141-143).  bias_off
- *                -> [12][Cin]: its nine taps (ky*3 + kx), BN scale, BN bias, PReLU slope.  Only with FP_OPF_SPLIT3 on the
- *                (Cin 64, Cmid 128, Cout 64, 56 x 56, stride 2) block: the depthwise output is formed in the kernel's
- *                prologue from an LDS image of the input rows and never goes to memory.
- */
-#define FP_OPF_IN_DW 16
+/* (bit 16 is unassigned since ABI 15: an op carrying it is FP_ERR_INVALID_ARG, as any unknown bit) */
 /*
  * FP_OPF_IN_UP2 (ABI 7) : a pointwise (1x1) FP_OP_CONV on the split-MFMA kernels (FP_OPF_SPLIT3) whose input is
  *                cat(upsample2x_nearest(u), v) -- nn.Upsample + Concat in front of a C3 in YOLOv5-face's head

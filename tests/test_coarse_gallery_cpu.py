@@ -22,8 +22,8 @@ def test_coarse_constants_agree(lib):
     hdr = open(os.path.join(ROOT, "include", "facepath.h")).read()
     assert int(re.search(r"#define FP_COARSE_MAX (\d+)", hdr).group(1)) == L.COARSE_MAX == 64
     assert int(re.search(r"#define FP_QUANT_MAX_D (\d+)", hdr).group(1)) == L.QUANT_MAX_D == 1024
-    assert int(re.search(r"#define FP_ABI_VERSION (\d+)", hdr).group(1)) == 14      # additions only
-    assert lib.fp_abi_version() == 14 == L.ABI_VERSION
+    assert int(re.search(r"#define FP_ABI_VERSION (\d+)", hdr).group(1)) == 15      # additions only
+    assert lib.fp_abi_version() == 15 == L.ABI_VERSION
     for name in ("fp_quant_i8_bytes", "fp_quantize_rows_i8", "fp_cosine_topk_i8_workspace", "fp_cosine_topk_i8", "fp_rerank_topk"):
         assert name in L.SIGNATURES and re.search(r"\b%s\(" % name, hdr), name
     assert 1024 * 127 * 127 < 2 ** 24                    # what FP_QUANT_MAX_D is for: the int32 dot converts to fp32 exactly

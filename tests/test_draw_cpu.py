@@ -350,7 +350,7 @@ int main(void) {
         assert int(got[f"fp_draw_cmd.{fname}"][0]) == getattr(L.FpDrawCmd, fname).offset == A.CMD_DTYPE.fields[fname][1], fname
     assert [int(v) for v in got["kinds"]] == [L.DRAW_RECT, L.DRAW_FILL, L.DRAW_RING, L.DRAW_GLYPH, L.DRAW_MOSAIC]
     assert [int(v) for v in got["consts"]] == [L.DRAW_TILE, L.DRAW_FONT_BYTES, L.DRAW_MAX_ARG, L.DRAW_MAX_SCALE, L.DRAW_MAX_COORD]
-    assert [int(v) for v in got["abi"]] == [L.ABI_VERSION, L.ABI_VERSION] == [14, 14]
+    assert [int(v) for v in got["abi"]] == [L.ABI_VERSION, L.ABI_VERSION] == [15, 15]
 
 
 # ---------------------------------------------------------------------------------------------------- the programs' flags

@@ -314,7 +314,7 @@ int main(void) {
                         ("fp_dets_to_crops_aligned_emulate", 25), ("fp_align_warp", 14), ("fp_align_warp_ragged", 14),
                         ("fp_align_emulate", 12)]:
         assert len(L.SIGNATURES[name][1]) == nargs, name
-    assert L.ABI_VERSION == 14
+    assert L.ABI_VERSION == 15
 
 
 # ---------------------------------------------------------------------------------------------- GPU

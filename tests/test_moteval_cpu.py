@@ -278,7 +278,7 @@ def test_mot_txt_round_trip(tmp_path):
 def test_abi_constants_and_c_refusals(lib):
     from conftest import ROOT
     hdr = open(os.path.join(ROOT, "include", "facepath.h")).read()
-    assert lib.fp_abi_version() == 14 == L.ABI_VERSION
+    assert lib.fp_abi_version() == 15 == L.ABI_VERSION
     assert int(re.search(r"#define FP_MOT_MAX_ROWS (\d+)", hdr).group(1)) == L.MOT_MAX_ROWS == L.TRACK_MAX_DETS
     for fn in ("fp_mot_match", "fp_mot_match_emulate", "fp_mot_match_workspace"):
         decl = re.search(r"^(?:int|size_t) %s\((.*?)\);" % fn, hdr, re.S | re.M).group(1)

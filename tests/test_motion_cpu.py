@@ -180,7 +180,7 @@ def test_refusals(lib):
     assert call(emb=ctypes.c_void_p(odd.ctypes.data)) == L.FP_ERR_INVALID_ARG
     assert call(n=0, frame=None, box=None, emb=None, xinv=None, pred=None) == L.FP_OK     # empty frames alone need no track_pred
     assert call(n=0, motion=None) == L.FP_ERR_INVALID_ARG
-    assert lib.fp_abi_version() == 14                                # additions only
+    assert lib.fp_abi_version() == 15                                # additions only
 
 
 def test_python_refusals():

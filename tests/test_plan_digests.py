@@ -13,6 +13,7 @@ import ctypes
 import hashlib
 import json
 import os
+import subprocess
 import sys
 
 import pytest
@@ -94,6 +95,51 @@ def test_existing_plans_unchanged(lib):
     assert sorted(got) == sorted(want)
     moved = [k for k in want if got[k] != want[k]]
     assert not moved, f"plans changed: {moved}"
+
+
+RETIRED_ENV = {"FP_BLAZE_PAIR": "0", "FP_BLAZE_CHAIN": "0", "FP_BLAZE_PAIR_S2": "0", "FP_BLAZE_STEM_X6": "0",
+               "FP_BLAZE_ROW_WINDOW": "0", "FP_UP2_FOLD": "0", "FP_DWPW_X6": "0", "FP_PW_X6_MIN_K": "0",
+               "FP_CONV3_X6_MIN_K": "0", "FP_CONV3_X6_FLAT": "0", "FP_CHAIN_CO": "1"}
+CHILD = """
+import json, sys
+sys.path.insert(0, sys.argv[1])
+import test_plan_digests as T
+nets = T._networks()
+print(json.dumps({name + "/N=16/X6=1": T.plan_digest(nets[name](16)) for name in sys.argv[2:]}))
+"""
+
+
+def test_plans_do_not_follow_the_environment():
+    """The package reads no FP_* environment variable: a process started with every retired lab knob set against its
+    default emits the golden's plans (split kernels on, N = 16) for BlazeFace on u8 frames, YOLOv5n and Mobile-FaceNet."""
+    names = ["blazeface_back_u8", "yolov5n", "mobile_facenet"]
+    out = subprocess.run([sys.executable, "-c", CHILD, os.path.dirname(os.path.abspath(__file__))] + names,
+                         env=dict(os.environ, **RETIRED_ENV), capture_output=True, text=True, check=True).stdout
+    got = json.loads(out.strip().splitlines()[-1])
+    with open(FIXTURE) as f:
+        want = json.load(f)
+    assert got == {k: want[k] for k in got} and len(got) == 3
+
+
+def test_switch_surface_is_a_literal():
+    """Every class-wide switch in a plan-cache key (plan.switch_key), by name: a new one is a decision made here."""
+    from face_detection_and_recognition_amd.modules.blazeface.blazeface import BlazeBlock, BlazeFace
+    from face_detection_and_recognition_amd.modules.mobile_facenet.mobile_facenet import Depth_Wise, MobileFaceNet
+    from face_detection_and_recognition_amd.modules.yolov5_face import yolo as Y
+    from face_detection_and_recognition_amd.plan import PlanBuilder, switch_key
+
+    def names(*classes):
+        return [f"{c}.{n}" for c, n, _ in switch_key(*classes)]
+
+    builder = ["PlanBuilder.CONV3_X6_MIN_K", "PlanBuilder.DWPW_X6_COUT", "PlanBuilder.PW_X6_MIN_K", "PlanBuilder.UP2_FOLD",
+               "PlanBuilder.X6", "PlanBuilder.X6_MIN_COUT", "PlanBuilder.X6_SMALL_K_MIN_PIXELS"]
+    assert names(PlanBuilder, Depth_Wise, MobileFaceNet) == builder + ["Depth_Wise.BLOCK_SHAPES", "Depth_Wise.FUSE"]
+    assert names(PlanBuilder, BlazeBlock, BlazeFace) == builder + [
+        "BlazeBlock.CHAIN", "BlazeBlock.FUSE", "BlazeBlock.PAIR", "BlazeBlock.PAIR_S2", "BlazeBlock.ROWPAD",
+        "BlazeFace.FUSE_LETTERBOX", "BlazeFace.ROW_WINDOW", "BlazeFace.STEM_X6"]
+    assert names(PlanBuilder, Y.Conv, Y.StemBlock, Y.C3, Y.ShuffleV2Block, Y.SPP, Y.Concat, Y.Model) == builder + [
+        "StemBlock.FUSE", "StemBlock.FUSE_TAIL", "C3.MERGE", "ShuffleV2Block.FUSE", "ShuffleV2Block.FUSE_DOWN",
+        "ShuffleV2Block.FUSE_UNIT", "Model.CONCAT_IN_PLACE", "Model.FOLD_UPSAMPLE", "Model.FUSE_LETTERBOX"]
 
 
 if __name__ == "__main__":

@@ -267,7 +267,7 @@ def test_cluster_faces_best_shot_helpers(tmp_path):
 
 def test_abi_of_the_new_entry_points(lib):
     hdr = open(os.path.join(ROOT, "include", "facepath.h")).read()
-    assert lib.fp_abi_version() == L.ABI_VERSION == 14
+    assert lib.fp_abi_version() == L.ABI_VERSION == 15
     for name in ("fp_face_quality", "fp_face_quality_emulate", "fp_face_pose", "fp_face_pose_emulate"):
         m = re.search(r"\bint " + name + r"\(([^;]*)\);", hdr)
         assert m, name

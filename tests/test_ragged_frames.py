@@ -61,7 +61,7 @@ int main(void) {
     for fname, _ in L.FpFrameDesc._fields_:
         assert int(got[f"fp_frame_desc.{fname}"][0]) == getattr(L.FpFrameDesc, fname).offset
     assert [int(v) for v in got["consts"]] == [L.FRAME_MIN_W, L.FRAME_MAX_W, L.FRAME_MAX_H, L.RAGGED_U8, L.RAGGED_F32_LUT]
-    assert [int(v) for v in got["abi"]] == [L.ABI_VERSION, L.ABI_VERSION] == [14, 14]
+    assert [int(v) for v in got["abi"]] == [L.ABI_VERSION, L.ABI_VERSION] == [15, 15]
     assert len(L.SIGNATURES["fp_resize_ragged"][1]) == 15 and len(L.SIGNATURES["fp_dets_to_crops_ragged"][1]) == 23
 
 

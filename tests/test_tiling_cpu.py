@@ -199,7 +199,7 @@ def test_refusals(lib):
     assert lib.fp_gather_tiles(None, 0, None, 1, None, 0, 64, 64, None, None) == L.FP_ERR_INVALID_ARG
     assert ctypes.sizeof(ctypes.c_int32) * 8 == T.VIEW_DTYPE.itemsize == 32
     assert len(L.SIGNATURES["fp_merge_views"][1]) == 19 and len(L.SIGNATURES["fp_merge_views_emulate"][1]) == 18
-    assert L.ABI_VERSION == 14 and L.MERGE_CAP == 2048
+    assert L.ABI_VERSION == 15 and L.MERGE_CAP == 2048
 
 
 def test_tiled_detector_refusals_and_tables():

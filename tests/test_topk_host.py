@@ -13,7 +13,7 @@ def test_topk_constants_agree():
     from conftest import ROOT
     hdr = open(os.path.join(ROOT, "include", "facepath.h")).read()
     assert int(re.search(r"#define FP_TOPK_MAX (\d+)", hdr).group(1)) == L.TOPK_MAX == 16
-    assert int(re.search(r"#define FP_ABI_VERSION (\d+)", hdr).group(1)) == 14
+    assert int(re.search(r"#define FP_ABI_VERSION (\d+)", hdr).group(1)) == 15
 
 
 def test_cosine_topk_refusals(lib):

@@ -158,7 +158,7 @@ def test_refusals(lib):
     odd = np.ones((2 * 32 + 1,), np.float32)[1:]                     # rows that are not 16-byte aligned
     assert call(emb=ctypes.c_void_p(odd.ctypes.data)) == L.FP_ERR_INVALID_ARG
     assert call(n=0, frame=None, box=None, emb=None, xinv=None) == L.FP_OK          # empty frames alone
-    assert lib.fp_abi_version() == 14                                # additions only
+    assert lib.fp_abi_version() == 15                                # additions only
 
 
 def test_python_refusals():

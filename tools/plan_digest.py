@@ -4,7 +4,7 @@ so two versions of the plan builder that print the same digests hand the kernels
 One line per case: SHA-256 over the raw bytes of every fp_op, the weight blob, the arena size, alg_bytes and the row windows;
 then the op count, the weight count and validate_on_host's status.  Every case runs at the default switches, with
 PlanBuilder.X6 off, and with every other boolean class-wide switch of its plan-cache key (switch_key) flipped alone; a few
-combinations that single flips do not reach follow.  The tool ends with the (op kind, SPLIT3, OUT_DW / IN_DW / IN_UP2 ...)
+combinations that single flips do not reach follow.  The tool ends with the (op kind, SPLIT3, OUT_DW / IN_UP2 ...)
 combinations it saw.
 
 usage: python tools/plan_digest.py [--out FILE] [--compare FILE] [--only SUBSTRING]
@@ -48,8 +48,8 @@ def digest(pb):
     h = hashlib.sha256()
     for op in ops:
         h.update(bytes(op))
-        tags = [name for name, bit in (("OUT_DW", L.OPF_OUT_DW), ("IN_DW", L.OPF_IN_DW), ("IN_UP2", L.OPF_IN_UP2)) if op.flags & bit]
-        # forms the three flags do not tell apart: the flat-K split conv, the stride-2 pair, the ops reading u8 frames with /
+        tags = [name for name, bit in (("OUT_DW", L.OPF_OUT_DW), ("IN_UP2", L.OPF_IN_UP2)) if op.flags & bit]
+        # forms the two flags do not tell apart: the flat-K split conv, the stride-2 pair, the ops reading u8 frames with /
         # without a scale, the dw -> 1x1 op's second PReLU and its shuffle epilogue
         if op.kind == L.OP_CONV and op.flags & L.OPF_SPLIT3 and not op.flags & L.OPF_OUT_DW and op.Cin < 32:
             tags.append("flatK")
@@ -99,20 +99,14 @@ def cases():
                 out.append((f"blazeface-{'back' if back else 'front'} N={n} frame_hw={fhw}", blaze, (),
                             lambda net=net, n=n, fhw=fhw: net._emit(n, frame_hw=fhw)[0]))
     mfn_cls = (PlanBuilder, Depth_Wise, MobileFaceNet)
-    x6off, stemoff = (PlanBuilder, "X6", False), (MobileFaceNet, "STEM_DW", False)
-    mfn_extra = [("X6=0 BLOCK_SHAPES=(7,14)", [x6off, (Depth_Wise, "BLOCK_SHAPES", (7, 14))]),
-                 ("X6=0 STEM_DW=0", [x6off, stemoff]),
-                 ("STEM_DW=0 X6_CONV23=0", [stemoff, (MobileFaceNet, "X6_CONV23", False)]),
-                 ("STEM_DW=0 X6_CONV2_IN=0", [stemoff, (MobileFaceNet, "X6_CONV2_IN", False)]),
-                 ("STEM_DW=0 DWPW_X6=0 X6_CONV23=0", [stemoff, (PlanBuilder, "DWPW_X6", False), (MobileFaceNet, "X6_CONV23", False)])]
+    x6off = (PlanBuilder, "X6", False)
+    mfn_extra = [("X6=0 BLOCK_SHAPES=(7,14)", [x6off, (Depth_Wise, "BLOCK_SHAPES", (7, 14))])]
     mfn = synth(MobileFaceNet(512), 12)
     for n in (4, 528):
         out.append((f"mobilefacenet N={n}", mfn_cls, mfn_extra, lambda n=n: mfn._emit(n)[0]))
     yolo = (PlanBuilder, Y.Conv, Y.StemBlock, Y.C3, Y.ShuffleV2Block, Y.SPP, Y.Concat, Y.Model)
     yolo_extra = [("X6=0 FUSE=0", [x6off, (Y.ShuffleV2Block, "FUSE", False), (Y.StemBlock, "FUSE", False)]),
-                  ("FUSE_DOWN=0 FUSE_UNIT=0", [(Y.ShuffleV2Block, "FUSE_DOWN", False), (Y.ShuffleV2Block, "FUSE_UNIT", False)]),
-                  ("FUSE_DOWN=0 FUSE_UNIT=0 DWPW_X6=0", [(Y.ShuffleV2Block, "FUSE_DOWN", False), (Y.ShuffleV2Block, "FUSE_UNIT", False),
-                                                        (PlanBuilder, "DWPW_X6", False)])]
+                  ("FUSE_DOWN=0 FUSE_UNIT=0", [(Y.ShuffleV2Block, "FUSE_DOWN", False), (Y.ShuffleV2Block, "FUSE_UNIT", False)])]
     for name in ("yolov5n", "yolov5n-0.5", "yolov5s"):
         for fused in (False, True):
             net = synth(Y.Model(name), 13)

@@ -612,6 +612,13 @@ static bool convx6_eligible(const fp_op& op) {
   }
   // 32-bit row decode by multiply-high (divisors >= 2; a 1 x 1 map or a single column skips that division)
   if ((long)op.N * OHW >= (1L << 31)) return false;
+  // the kernel keeps a pixel's first-tap coordinates as two 16-bit halves of one int (iyx) and computes pixel offsets within an
+  // image in 32 bits: the last tap of the last window at row / column 32767 at most, H * W * in_ld below 2^31 (and the same for
+  // the half-size map of a folded upsample).  A larger map runs on the fp32 kernel.
+  if ((long)(op.OH - 1) * op.stride - op.pad_t + op.KH - 1 > 32767 || (long)(op.OW - 1) * op.stride - op.pad_l + op.KW - 1 > 32767)
+    return false;
+  if ((long)op.H * op.W * op.in_ld >= (1L << 31)) return false;
+  if ((op.flags & FP_OPF_IN_UP2) && (long)op.res_H * op.res_W * op.res_ld >= (1L << 31)) return false;
   return true;
 }
 

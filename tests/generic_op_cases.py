@@ -66,6 +66,10 @@ class Case:
     out_rowpad: bool = False
     partial: int = 0         # > 0: also run(partial) on the plan of capacity N
     special: str = ""        # "inf": +-inf among the inputs; "zero_row": one all-zero input row; "neg": bias pushes every channel negative
+                             # "inf_pair": one +inf and one -inf among the inputs
+    up_C: int = 0            # conv, FP_OPF_IN_UP2 (tests/split_conv_cases.py): channels [0, up_C) of the input view are the
+    up_buf_C: int = 0        # nearest-neighbour 2x of an (H/2, W/2, up_C) view at up_coff of a buffer up_buf_C wide (0: up_C)
+    up_coff: int = 0
 
 
 def _out_hw(c):
@@ -134,6 +138,8 @@ def inputs(c):
         pos = rng.choice(flat.size, size=max(2, flat.size // 9), replace=False)
         flat[pos[::2]] = -np.inf
         flat[pos[1::2]] = np.inf
+    if c.special == "inf_pair":        # one +inf and one -inf: the outputs whose windows miss both stay finite
+        x[0, 0, 0, 0], x[-1, -1, -1, -1] = np.inf, -np.inf
     if c.special == "zero_row":
         x[c.N // 2, c.H // 2, c.W // 2, :] = 0.0
     d = {"x": x}
@@ -141,12 +147,14 @@ def inputs(c):
         oh, ow = _out_hw(c)
         rh, rw = (2 * oh, 2 * ow) if c.res == "pool2" else (oh, ow)
         d["res"] = rng.normal(0, 1, (c.N, rh, rw, c.res_C or _out_view_C(c))).astype(np.float32)
+    if c.up_C:
+        d["up"] = rng.normal(0, 1, (c.N, c.H // 2, c.W // 2, c.up_C)).astype(np.float32)
     return d
 
 
 def build(c, N=None):
     """Emit the one-op plan of a case -> (builder, {"x": Buf, "out": Buf, "res": Buf or None}).  The fp32 kernels only
-    (PlanBuilder.X6 off on this builder: the split-MFMA kernels have their own tests)."""
+    (PlanBuilder.X6 off on this builder: the split-MFMA conv kernels have a table of their own, tests/split_conv_cases.py)."""
     pb = PlanBuilder(N or c.N)
     pb.X6 = False
     oh, ow = _out_hw(c)
@@ -219,19 +227,24 @@ def _vec(p, key, n, dt, fill):
     return out
 
 
-def reference(c, data, dt, pre=False):
+def reference(c, data, dt, pre=False, p=None, conv=None):
     """The op of case c on data (inputs()) -> (N, OH, OW, written channels) numpy array of dtype dt.  pre: the conv / dwconv
-    value in front of the activation instead."""
+    value in front of the activation instead.  p: parameters other than weights(c) (a mutant); conv: what computes the dense
+    conv of the padded NCHW input in place of F.conv2d(xp, w, stride=...) (another summation order)."""
     x = torch.from_numpy(data["x"]).to(dt).permute(0, 3, 1, 2)
     oh, ow = _out_hw(c)
-    p = weights(c)
+    p = weights(c) if p is None else p
+    if c.up_C:      # the folded nn.Upsample(2, "nearest") + Concat: the small map's 2x in front of the direct channels
+        u = torch.from_numpy(data["up"]).to(dt).permute(0, 3, 1, 2)
+        iy, ix = torch.arange(c.H) // 2, torch.arange(c.W) // 2
+        x = torch.cat([u[:, :, iy][:, :, :, ix], x[:, c.up_C:]], dim=1)
     if c.kind in ("conv", "dwconv"):
         oc = _out_view_C(c)
         xp = _pad_window(x, 0.0, c.k, c.stride, c.pad, oh, ow)
         if c.kind == "conv":
             w = torch.zeros((oc, c.C, *c.k), dtype=dt)
             w[:c.cout, :c.cin or c.C] = torch.from_numpy(p["w"]).to(dt)
-            v = F.conv2d(xp, w, stride=c.stride)
+            v = F.conv2d(xp, w, stride=c.stride) if conv is None else conv(xp, w, c.stride)
         else:
             v = F.conv2d(xp, torch.from_numpy(p["w"]).to(dt), stride=c.stride, groups=c.C)
         v = v[:, :, :oh, :ow]

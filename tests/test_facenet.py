@@ -234,6 +234,15 @@ def test_conv_splits_exactly_where_the_launcher_takes_it(lib, monkeypatch):
                     assert not c_ok
                 seen[c_ok] += 1
     assert seen[True] > 1000 and seen[False] > 1000
+    # maps beyond the split kernel's 16-bit window coordinates or 32-bit pixel offsets are refused by both, the largest maps
+    # within them are taken by both
+    for cin, kh, kw, pt, pl, stride, H, W, want in ((32, 1, 3, 0, 1, 1, 1, 33000, False), (32, 3, 1, 1, 0, 1, 33000, 1, False),
+                                                    (16, 3, 3, 1, 1, 2, 2, 40000, False), (512, 1, 3, 0, 1, 1, 2048, 2048, False),
+                                                    (32, 1, 3, 0, 1, 1, 1, 32767, True), (16, 3, 3, 1, 1, 2, 2, 32768, True),
+                                                    (508, 1, 3, 0, 1, 1, 2048, 2048, True)):
+        pb, x, out, op = _window_op(cin, 32, kh, kw, pt, pl, stride, H, W)
+        assert (lib.fp_plan_validate(ctypes.byref(op), 1, big, big) == 0) == want, (cin, kh, kw, H, W)
+        assert emits_split(pb, x, out, cin, 32, kh, kw, stride, (pt, pl)) == want, (cin, kh, kw, H, W)
     # input channels not a multiple of 4, and an input narrower than 32 under anything but a 3x3, are refused by both
     for cin, kh, kw in ((34, 3, 3), (30, 1, 7), (16, 1, 3), (4, 1, 1)):
         pb, x, out, op = _window_op(cin, 64, kh, kw, 0, 0, 1, 9, 9)

@@ -21,7 +21,12 @@
 //           window in registers), result split into bf16 planes -> D-tile [3][pixels][32]
 //       P   W_p^T (registers, prefetched during D) x D^T -> output tile in registers (wave w owns C / 4 output channels)
 //     two workgroup barriers per round (three more at 28x28, where D / P run in two row chunks to keep LDS <= 80 KiB).
-//   epilogue  = BN affine + x, 16-byte loads / stores straight from the accumulators.
+//     Inside E the BN / PReLU parameters of both channel tiles are requested in front of the first MFMA group, so the
+//     tail behind the last MFMA is arithmetic and stores only; D reads its taps and parameters once per round.
+//   last round = its own copy of the round body (one lambda, compile-time flag): the x fragments are dead once its E is
+//               done, and the shortcut values and the project BN affine of the epilogue are requested there, into those
+//               registers, and arrive under the last D and P phases (finding 81).
+//   epilogue  = BN affine + x, 16-byte stores straight from the accumulators; no load is left in it.
 //
 // Traffic per tile: x once (+ halo rows), y once, weights from L2 (the split weights are 1.5x the fp32 ones).
 // MFMA work per 14x14 block: 2 bands x 8 rounds x (7 x 2 x 4 + 7 x 8) tile-slabs x 6 = 10.7 k MFMAs of 16 cycles per
@@ -45,10 +50,6 @@ namespace {
 // for half of every MFMA; a D-phase wave with a higher priority gets the port whenever it is ready.
 #ifndef FP_X6_DPRIO
 #define FP_X6_DPRIO 0
-#endif
-// Lab knob: the depthwise taps of dwblock_x6_kernel as plain instead of packed FMAs.
-#ifndef FP_X6_DSCALAR
-#define FP_X6_DSCALAR 0
 #endif
 #define X6_DPRIO_ON()  do { if (FP_X6_DPRIO) __builtin_amdgcn_s_setprio(FP_X6_DPRIO); } while (0)
 #define X6_DPRIO_OFF() do { if (FP_X6_DPRIO) __builtin_amdgcn_s_setprio(0); } while (0)
@@ -83,6 +84,23 @@ struct DwbX6Args {
 #else
 #define X6_STAMP(k) do { } while (0)
 #endif
+
+// Depthwise parameters of a round for one lane: nine taps, BN scale and bias, PReLU slope - 1 (T = f32x2: a channel pair
+// from channel ch, T = float: the one channel ch).  Pc is the round's half of the parameter double buffer.
+template <typename T>
+struct X6DwPar {
+  T tap[9], dsc, dbi, dsl;
+};
+template <typename T, int KCH>
+__device__ __forceinline__ X6DwPar<T> x6_dw_par(const float* Pc, int ch) {
+  X6DwPar<T> d;
+#pragma unroll
+  for (int t = 0; t < 9; ++t) d.tap[t] = *(const T*)&Pc[(3 + t) * KCH + ch];
+  d.dsc = *(const T*)&Pc[12 * KCH + ch];
+  d.dbi = *(const T*)&Pc[13 * KCH + ch];
+  d.dsl = *(const T*)&Pc[14 * KCH + ch] - T(1.f);
+  return d;
+}
 
 template <int C, int HW>
 struct X6Cfg {
@@ -201,9 +219,18 @@ __global__ __launch_bounds__(256, 2) void dwblock_x6_kernel(DwbX6Args p) {
   // E(s): expand round s -> E-image.  Straight-line: a wave whose last owned tile does not exist (m >= MTE) computes it
   // on clamped pixels and drops it into the junk slot -- a wave-uniform branch around every MFMA group keeps hipcc from
   // moving the next group's LDS reads above this group's MFMAs.  The weight fragments of group g + 1 are requested
-  // before the MFMAs of group g.
+  // before the MFMAs of group g, and the BN / PReLU parameters of both channel tiles before the first group: requested
+  // behind the last MFMA, where the epilogue needs them, their LDS round trip was part of the tail in which the wave
+  // has nothing else to issue (finding 81).
   auto expand = [&](int s) {
     const float* Pc = Pl + (s & 1) * K::PL;
+    f32x4 es[2], eb[2], em[2];
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+      es[nt] = *(const f32x4*)&Pc[16 * nt + 4 * q];
+      eb[nt] = *(const f32x4*)&Pc[K::KCH + 16 * nt + 4 * q];
+      em[nt] = *(const f32x4*)&Pc[2 * K::KCH + 16 * nt + 4 * q] - f32x4{1.f, 1.f, 1.f, 1.f};
+    }
     f32x4 acc[K::NOWN][2];
 #pragma unroll
     for (int t = 0; t < K::NOWN; ++t) acc[t][0] = acc[t][1] = z;
@@ -225,16 +252,13 @@ __global__ __launch_bounds__(256, 2) void dwblock_x6_kernel(DwbX6Args p) {
     // v = acc*s + b; PReLU(v) = v + (slope - 1)*min(v, 0); channels 16 nt + 4 q + i of pixel l15
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-      const f32x4 es = *(const f32x4*)&Pc[16 * nt + 4 * q];
-      const f32x4 eb = *(const f32x4*)&Pc[K::KCH + 16 * nt + 4 * q];
-      const f32x4 em = *(const f32x4*)&Pc[2 * K::KCH + 16 * nt + 4 * q] - f32x4{1.f, 1.f, 1.f, 1.f};
 #pragma unroll
       for (int t = 0; t < K::NOWN; ++t) {
-        f32x4 v = acc[t][nt] * es + eb;
+        f32x4 v = acc[t][nt] * es[nt] + eb[nt];
         f32x4 neg;
 #pragma unroll
         for (int i = 0; i < 4; ++i) neg[i] = __builtin_fminf(v[i], 0.f);
-        v = neg * em + v;
+        v = neg * em[nt] + v;
         *(f32x4*)&El[eoff[t] + 16 * nt] = v;
       }
     }
@@ -246,17 +270,13 @@ __global__ __launch_bounds__(256, 2) void dwblock_x6_kernel(DwbX6Args p) {
   // stores, into the registers of the rows that just left the window.  hipcc keeps an LDS read behind every earlier LDS
   // write (E-image and D-tile may alias for all it knows): with the reads at the top of each row the seven rows were seven
   // serial round trips read -> 9 dependent FMAs -> split -> write (3000 cycles alone, 5300 beside the partner's MFMAs; FINDINGS 47)
-  auto depthwise = [&](int s, auto cc) {
+  // The round's nine taps, scale, bias and slope come in as dp (x6_dw_par): read once per round, not once per chunk.
+  auto depthwise = [&](const X6DwPar<f32x2>& dp, auto cc) {
     constexpr int c = decltype(cc)::value;
     constexpr int NR = K::crows(c);
-    const float* Pc = Pl + (s & 1) * K::PL;
     const int c2 = tid & 15, strip = tid >> 4;
-    f32x2 tap[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) tap[t] = *(const f32x2*)&Pc[(3 + t) * K::KCH + 2 * c2];
-    const f32x2 dsc = *(const f32x2*)&Pc[12 * K::KCH + 2 * c2];
-    const f32x2 dbi = *(const f32x2*)&Pc[13 * K::KCH + 2 * c2];
-    const f32x2 dsl = *(const f32x2*)&Pc[14 * K::KCH + 2 * c2] - f32x2{1.f, 1.f};
+    const f32x2* tap = dp.tap;
+    const f32x2 dsc = dp.dsc, dbi = dp.dbi, dsl = dp.dsl;
 #pragma unroll
     for (int ps = 0; ps < K::NPASS; ++ps) {
       const int col = strip + 16 * ps;
@@ -269,20 +289,6 @@ __global__ __launch_bounds__(256, 2) void dwblock_x6_kernel(DwbX6Args p) {
           for (int dx = 0; dx < 3; ++dx) w[dx] = *(const f32x2*)(base + (vr * K::ROWP + dx) * K::LDE);
         };
         auto taps = [&](const f32x2* w0, const f32x2* w1, const f32x2* w2) {
-#if FP_X6_DSCALAR
-          // lab: plain v_fma_f32 -- beside an MFMA stream a packed FMA retires every 22.5 cycles, a plain one every 8.7 (finding 24)
-          float a0, a1;
-          asm volatile("v_mul_f32 %0, %1, %2" : "=v"(a0) : "v"(w0[0][0]), "v"(tap[0][0]));
-          asm volatile("v_mul_f32 %0, %1, %2" : "=v"(a1) : "v"(w0[0][1]), "v"(tap[0][1]));
-#define X6_SFMA(W, T)                                                                  \
-  asm volatile("v_fmac_f32 %0, %1, %2" : "+v"(a0) : "v"((W)[0]), "v"((T)[0]));         \
-  asm volatile("v_fmac_f32 %0, %1, %2" : "+v"(a1) : "v"((W)[1]), "v"((T)[1]));
-          X6_SFMA(w0[1], tap[1]) X6_SFMA(w0[2], tap[2])
-          X6_SFMA(w1[0], tap[3]) X6_SFMA(w1[1], tap[4]) X6_SFMA(w1[2], tap[5])
-          X6_SFMA(w2[0], tap[6]) X6_SFMA(w2[1], tap[7]) X6_SFMA(w2[2], tap[8])
-#undef X6_SFMA
-          return f32x2{a0, a1};
-#else
           f32x2 sacc = w0[0] * tap[0];
           sacc += w0[1] * tap[1];
           sacc += w0[2] * tap[2];
@@ -291,7 +297,6 @@ __global__ __launch_bounds__(256, 2) void dwblock_x6_kernel(DwbX6Args p) {
 #pragma unroll
           for (int dx = 0; dx < 3; ++dx) sacc += w2[dx] * tap[6 + dx];
           return sacc;
-#endif
         };
         auto finish = [&](f32x2 sacc, int r) {
           f32x2 v = sacc * dsc + dbi;
@@ -369,16 +374,51 @@ __global__ __launch_bounds__(256, 2) void dwblock_x6_kernel(DwbX6Args p) {
 
   __syncthreads();   // E-image zeroed, round 0 staged (the barrier drains the LDS-DMA)
 
-  for (int s = 0; s < R; ++s) {
+  // shortcut values and the project BN affine of the epilogue, lane = pixel l15 of the tile, channels 16 ct + 4 q .. + 3.
+  // They are requested in the LAST round, behind its expand phase: the x fragments (96 registers) are dead from there on,
+  // and the values arrive under the last depthwise and project phases instead of one round trip to L2 / HBM behind them.
+  f32x4 rv[K::NCHUNK][K::NCT][K::mtc(0)], ps[K::NCT], pb[K::NCT];
+  auto request_tail = [&]() {
+#pragma unroll
+    for (int j = 0; j < K::NCT; ++j) {
+      const int ch = 16 * (wave * K::NCT + j) + 4 * q;
+      ps[j] = *(const f32x4*)(p.paff + ch);
+      pb[j] = *(const f32x4*)(p.paff + C + ch);
+    }
+    if (p.has_res) {   // one wave-uniform branch around all of them: a block without a shortcut requests nothing
+#pragma unroll
+      for (int j = 0; j < K::NCT; ++j)
+#pragma unroll
+        for (int c = 0; c < K::NCHUNK; ++c)
+#pragma unroll
+          for (int t = 0; t < K::mtc(c); ++t) {
+            const int o = min(16 * t + l15, K::crows(c) * HW - 1);
+            rv[c][j][t] = *(const f32x4*)(xin + (((r0 + K::crow0(c)) * HW + o) * C + 16 * (wave * K::NCT + j) + 4 * q));
+          }
+    } else {
+#pragma unroll
+      for (int j = 0; j < K::NCT; ++j)
+#pragma unroll
+        for (int c = 0; c < K::NCHUNK; ++c)
+#pragma unroll
+          for (int t = 0; t < K::mtc(c); ++t) rv[c][j][t] = z;
+    }
+  };
+
+  // one round; last: round R - 1 (nothing to stage behind it, the epilogue's loads go out instead)
+  auto round = [&](int s, auto last_c) {
+    constexpr bool last = decltype(last_c)::value;
     X6_STAMP(0);
     expand(s);
+    if (last) request_tail();
     X6_STAMP(1);
     __syncthreads();                       // E-image complete; every wave is done with this round's expand weights
     X6_STAMP(2);
+    const X6DwPar<f32x2> dp = x6_dw_par<f32x2, K::KCH>(Pl + (s & 1) * K::PL, 2 * (tid & 15));
     load_pbw(s);                           // first: vmcnt is in order, P waits for these and not for the DMA behind them
-    if (s + 1 < R) stage(s + 1);
+    if (!last) stage(s + 1);
     X6_DPRIO_ON();
-    depthwise(s, std::integral_constant<int, 0>());
+    depthwise(dp, std::integral_constant<int, 0>());
     X6_DPRIO_OFF();
     X6_STAMP(3);
     lds_barrier();                         // D-tile complete
@@ -388,46 +428,31 @@ __global__ __launch_bounds__(256, 2) void dwblock_x6_kernel(DwbX6Args p) {
     if (K::NCHUNK > 1) {
       lds_barrier();                       // chunk 0's D-tile consumed
       X6_DPRIO_ON();
-      depthwise(s, std::integral_constant<int, K::NCHUNK - 1>());
+      depthwise(dp, std::integral_constant<int, K::NCHUNK - 1>());
       X6_DPRIO_OFF();
       lds_barrier();
       project(std::integral_constant<int, K::NCHUNK - 1>());
     }
-    if (s + 1 < R) __syncthreads();        // next round's weights and parameters landed (the DMA had D + P to do so)
-  }
+    if (!last) __syncthreads();            // next round's weights and parameters landed (the DMA had D + P to do so)
+  };
+  for (int s = 0; s < R - 1; ++s) round(s, std::false_type());
+  round(R - 1, std::true_type());
   {
     [[maybe_unused]] const int s = R;
     X6_STAMP(0);
   }
 
-  // ---- epilogue: y = acc*s + b (+ x), lane = pixel l15 of the tile, channels 16 ct + 4 q .. + 3 ----
-  // every shortcut value is requested before the first one is used: one round trip to L2 / HBM for the tile instead of one
-  // per (chunk, channel tile)
-  f32x4 rv[K::NCHUNK][K::NCT][K::mtc(0)];
-#pragma unroll
-  for (int c = 0; c < K::NCHUNK; ++c)
-#pragma unroll
-    for (int j = 0; j < K::NCT; ++j) {
-      const int ch = 16 * (wave * K::NCT + j) + 4 * q;
-#pragma unroll
-      for (int t = 0; t < K::mtc(c); ++t) {
-        const int o = min(16 * t + l15, K::crows(c) * HW - 1);
-        const int off = ((r0 + K::crow0(c)) * HW + o) * C + ch;
-        rv[c][j][t] = p.has_res ? *(const f32x4*)(xin + off) : z;
-      }
-    }
+  // ---- epilogue: y = acc*s + b (+ x) straight from the accumulators ----
 #pragma unroll
   for (int c = 0; c < K::NCHUNK; ++c) {
 #pragma unroll
     for (int j = 0; j < K::NCT; ++j) {
       const int ch = 16 * (wave * K::NCT + j) + 4 * q;
-      const f32x4 ps = *(const f32x4*)(p.paff + ch);
-      const f32x4 pb = *(const f32x4*)(p.paff + C + ch);
 #pragma unroll
       for (int t = 0; t < K::mtc(c); ++t) {
         const int o = 16 * t + l15;
         const int off = ((r0 + K::crow0(c)) * HW + o) * C + ch;
-        const f32x4 v = pacc[K::tbase(c) + t][j] * ps + pb + rv[c][j][t];
+        const f32x4 v = pacc[K::tbase(c) + t][j] * ps[j] + pb[j] + rv[c][j][t];
         if (o < K::crows(c) * HW) *(f32x4*)(yout + off) = v;
       }
     }
@@ -546,10 +571,18 @@ __global__ __launch_bounds__(256, 3) void dwblock_x6q_kernel(DwbX6Args p) {
     }
   };
 
-  // E(s): both 16-channel tiles of the round for this wave's pixel tile (two accumulators)
+  // E(s): both 16-channel tiles of the round for this wave's pixel tile (two accumulators); the BN / PReLU parameters
+  // are requested before the first MFMA (see dwblock_x6_kernel)
   auto expand = [&](int s) {
     const float* Pc = Pl + (s & 1) * K::PL;
-    f32x4 acc0 = z, acc1 = z;
+    f32x4 es[2], eb[2], em[2];
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+      es[nt] = *(const f32x4*)&Pc[16 * nt + 4 * q];
+      eb[nt] = *(const f32x4*)&Pc[K::KCH + 16 * nt + 4 * q];
+      em[nt] = *(const f32x4*)&Pc[2 * K::KCH + 16 * nt + 4 * q] - f32x4{1.f, 1.f, 1.f, 1.f};
+    }
+    f32x4 acc[2] = {z, z};
     // steps g = (ks, nt): the weight fragment of step g + 1 is requested before the six MFMAs of step g (a chain on one
     // accumulator issues at the full rate: tools/lab/coexec_bf16_lab.hip)
     fp_frag3 wf[2];
@@ -565,19 +598,15 @@ __global__ __launch_bounds__(256, 3) void dwblock_x6q_kernel(DwbX6Args p) {
       if (g + 1 < 2 * KS) ldw(g + 1, wf[(g + 1) & 1]);
       const fp_frag3& w = wf[g & 1];
       const fp_frag3& xx = xf[g >> 1];
-      if (g & 1) acc1 = fp_mfma_x6(w.h, w.m, w.l, xx.h, xx.m, xx.l, acc1);
-      else acc0 = fp_mfma_x6(w.h, w.m, w.l, xx.h, xx.m, xx.l, acc0);
+      acc[g & 1] = fp_mfma_x6(w.h, w.m, w.l, xx.h, xx.m, xx.l, acc[g & 1]);
     }
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-      const f32x4 es = *(const f32x4*)&Pc[16 * nt + 4 * q];
-      const f32x4 eb = *(const f32x4*)&Pc[K::KCH + 16 * nt + 4 * q];
-      const f32x4 em = *(const f32x4*)&Pc[2 * K::KCH + 16 * nt + 4 * q] - f32x4{1.f, 1.f, 1.f, 1.f};
-      f32x4 v = (nt ? acc1 : acc0) * es + eb;
+      f32x4 v = acc[nt] * es[nt] + eb[nt];
       f32x4 neg;
 #pragma unroll
       for (int i = 0; i < 4; ++i) neg[i] = __builtin_fminf(v[i], 0.f);
-      v = neg * em + v;
+      v = neg * em[nt] + v;
       *(f32x4*)&El[eoff + 16 * nt] = v;
     }
   };
@@ -588,14 +617,11 @@ __global__ __launch_bounds__(256, 3) void dwblock_x6q_kernel(DwbX6Args p) {
   // v_pk_fma_f32 costs 22 cycles of issue against 2 x 8.7 for two v_fma_f32 (tools/lab/coexec_bf16_lab.hip), and one
   // channel per lane needs a third of the registers of the channel-pair form (three workgroups per CU need <= 168).
   // The three bf16 pieces are the upper halves of h, m, l: stored with ds_write_b16_d16_hi, no packing.
-  auto depthwise = [&](int s) {
-    const float* Pc = Pl + (s & 1) * K::PL;
+  auto depthwise = [&](const X6DwPar<float>& dp) {
     const int ch = tid & 31, col = tid >> 5;
     if (col < 7) {
-      float tap[9];
-#pragma unroll
-      for (int t = 0; t < 9; ++t) tap[t] = Pc[(3 + t) * K::KCH + ch];
-      const float dsc = Pc[12 * K::KCH + ch], dbi = Pc[13 * K::KCH + ch], dsl = Pc[14 * K::KCH + ch] - 1.f;
+      const float* tap = dp.tap;
+      const float dsc = dp.dsc, dbi = dp.dbi, dsl = dp.dsl;
       // grid slot (vr, vc) = vr*9 + vc; output (row, col) reads vr = row .. row + 2, vc = col .. col + 2
       const float* base = &El[col * K::LDE + ch];
       unsigned short* dst = Dl + (col * 32 + ch);
@@ -654,49 +680,71 @@ __global__ __launch_bounds__(256, 3) void dwblock_x6q_kernel(DwbX6Args p) {
   };
   auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
 
-  __syncthreads();
-  for (int s = 0; s < R; ++s) {
+  // epilogue operands: pixel o = 16 t + l15 of the tile (row o / 7, column o % 7), channels 16 (2 wave + j) + 4 q .. + 3;
+  // requested in the last round behind its expand phase, where the x fragments are dead (see dwblock_x6_kernel)
+  f32x4 rv[2][K::MTP], ps[2], pb[2];
+  int off[K::MTP];
+  auto request_tail = [&]() {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      ps[j] = *(const f32x4*)(p.paff + 16 * (wave * 2 + j) + 4 * q);
+      pb[j] = *(const f32x4*)(p.paff + C + 16 * (wave * 2 + j) + 4 * q);
+    }
+#pragma unroll
+    for (int t = 0; t < K::MTP; ++t) {
+      const int o = min(16 * t + l15, 48);
+      const int orow = o / 7, ocol = o - orow * 7;
+      off[t] = ((r0 + orow) * HW + c0 + ocol) * C + 32 * wave + 4 * q;
+    }
+    if (p.has_res) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int t = 0; t < K::MTP; ++t) rv[j][t] = *(const f32x4*)(xin + off[t] + 16 * j);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int t = 0; t < K::MTP; ++t) rv[j][t] = z;
+    }
+  };
+
+  auto round = [&](int s, auto last_c) {
+    constexpr bool last = decltype(last_c)::value;
     X6_STAMP(0);
     expand(s);
+    if (last) request_tail();
     X6_STAMP(1);
     __syncthreads();
     X6_STAMP(2);
+    const X6DwPar<float> dp = x6_dw_par<float, K::KCH>(Pl + (s & 1) * K::PL, tid & 31);
     load_pbw(s);
-    if (s + 1 < R) stage(s + 1);
+    if (!last) stage(s + 1);
     X6_DPRIO_ON();
-    depthwise(s);
+    depthwise(dp);
     X6_DPRIO_OFF();
     X6_STAMP(3);
     lds_barrier();
     X6_STAMP(4);
     project();
     X6_STAMP(5);
-    if (s + 1 < R) __syncthreads();
-  }
+    if (!last) __syncthreads();
+  };
+  __syncthreads();
+  for (int s = 0; s < R - 1; ++s) round(s, std::false_type());
+  round(R - 1, std::true_type());
   {
     [[maybe_unused]] const int s = R;
     X6_STAMP(0);
   }
 
-  // ---- epilogue: pixel o = 16 t + l15 of the tile (row o / 7, column o % 7), channels 16 (2 wave + j) + 4 q .. + 3 ----
+  // ---- epilogue ----
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const int ch = 16 * (wave * 2 + j) + 4 * q;
-    const f32x4 ps = *(const f32x4*)(p.paff + ch);
-    const f32x4 pb = *(const f32x4*)(p.paff + C + ch);
-    f32x4 rv[K::MTP];
-    int off[K::MTP];
 #pragma unroll
     for (int t = 0; t < K::MTP; ++t) {
-      const int o = min(16 * t + l15, 48);
-      const int orow = o / 7, ocol = o - orow * 7;
-      off[t] = ((r0 + orow) * HW + c0 + ocol) * C + ch;
-      rv[t] = p.has_res ? *(const f32x4*)(xin + off[t]) : z;
-    }
-#pragma unroll
-    for (int t = 0; t < K::MTP; ++t) {
-      const f32x4 v = pacc[t][j] * ps + pb + rv[t];
-      if (16 * t + l15 < 49) *(f32x4*)(yout + off[t]) = v;
+      const f32x4 v = pacc[t][j] * ps[j] + pb[j] + rv[j][t];
+      if (16 * t + l15 < 49) *(f32x4*)(yout + off[t] + 16 * j) = v;
     }
   }
 }
@@ -829,8 +877,16 @@ __global__ __launch_bounds__(256, 2) void dwblock_x6d_kernel(DwbX6Args p) {
     }
   };
 
+  // E(s): the BN / PReLU parameters are requested before the first MFMA group (see dwblock_x6_kernel)
   auto expand = [&](int s) {
     const float* Pc = Pl + (s & 1) * K::PL;
+    f32x4 es[2], eb[2], em[2];
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+      es[nt] = *(const f32x4*)&Pc[16 * nt + 4 * q];
+      eb[nt] = *(const f32x4*)&Pc[K::KCH + 16 * nt + 4 * q];
+      em[nt] = *(const f32x4*)&Pc[2 * K::KCH + 16 * nt + 4 * q] - f32x4{1.f, 1.f, 1.f, 1.f};
+    }
     f32x4 acc[K::NOWN][2];
 #pragma unroll
     for (int t = 0; t < K::NOWN; ++t) acc[t][0] = acc[t][1] = z;
@@ -852,16 +908,13 @@ __global__ __launch_bounds__(256, 2) void dwblock_x6d_kernel(DwbX6Args p) {
     }
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-      const f32x4 es = *(const f32x4*)&Pc[16 * nt + 4 * q];
-      const f32x4 eb = *(const f32x4*)&Pc[K::KCH + 16 * nt + 4 * q];
-      const f32x4 em = *(const f32x4*)&Pc[2 * K::KCH + 16 * nt + 4 * q] - f32x4{1.f, 1.f, 1.f, 1.f};
 #pragma unroll
       for (int t = 0; t < K::NOWN; ++t) {
-        f32x4 v = acc[t][nt] * es + eb;
+        f32x4 v = acc[t][nt] * es[nt] + eb[nt];
         f32x4 neg;
 #pragma unroll
         for (int i = 0; i < 4; ++i) neg[i] = __builtin_fminf(v[i], 0.f);
-        v = neg * em + v;
+        v = neg * em[nt] + v;
         *(f32x4*)&El[eoff[t] + 16 * nt] = v;
       }
     }
@@ -869,15 +922,10 @@ __global__ __launch_bounds__(256, 2) void dwblock_x6d_kernel(DwbX6Args p) {
 
   // D(s): lane = (channel pair c2, strip); strip = (row part, output column); output (r, c) reads E-image rows
   // 2r .. 2r + 2 and input columns 2c - 1 .. 2c + 1 = slots vr*ROWP + 2c + dx.  Consecutive outputs of a strip share a row.
-  auto depthwise = [&](int s) {
-    const float* Pc = Pl + (s & 1) * K::PL;
+  auto depthwise = [&](const X6DwPar<f32x2>& dp) {
     const int c2 = tid & 15;
-    f32x2 tap[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) tap[t] = *(const f32x2*)&Pc[(3 + t) * K::KCH + 2 * c2];
-    const f32x2 dsc = *(const f32x2*)&Pc[12 * K::KCH + 2 * c2];
-    const f32x2 dbi = *(const f32x2*)&Pc[13 * K::KCH + 2 * c2];
-    const f32x2 dsl = *(const f32x2*)&Pc[14 * K::KCH + 2 * c2] - f32x2{1.f, 1.f};
+    const f32x2* tap = dp.tap;
+    const f32x2 dsc = dp.dsc, dbi = dp.dbi, dsl = dp.dsl;
 #pragma unroll
     for (int ps = 0; ps < K::NPASS; ++ps) {
       const int strip = (tid >> 4) + 16 * ps;
@@ -951,10 +999,11 @@ __global__ __launch_bounds__(256, 2) void dwblock_x6d_kernel(DwbX6Args p) {
   for (int s = 0; s < R; ++s) {
     expand(s);
     __syncthreads();
+    const X6DwPar<f32x2> dp = x6_dw_par<f32x2, K::KCH>(Pl + (s & 1) * K::PL, 2 * (tid & 15));
     load_pbw(s);
     if (s + 1 < R) stage(s + 1);
     X6_DPRIO_ON();
-    depthwise(s);
+    depthwise(dp);
     X6_DPRIO_OFF();
     lds_barrier();
     project();

@@ -67,6 +67,12 @@ class FpFrameDesc(C.Structure):
     _fields_ = [("off", C.c_int64), ("h", C.c_int32), ("w", C.c_int32)]
 
 
+class FpTtaView(C.Structure):
+    """Mirror of struct fp_tta_view: one scaled view of the augmented inference (include/facepath.h)."""
+    _fields_ = [("content_h", C.c_int32), ("content_w", C.c_int32), ("padded_h", C.c_int32), ("padded_w", C.c_int32),
+                ("flip", C.c_int32), ("reserved", C.c_int32)]
+
+
 FRAME_MIN_W, FRAME_MAX_W, FRAME_MAX_H = 3, 32767, 65535   # fp_frame_desc sizes the ragged kernels take
 RAGGED_U8, RAGGED_F32_LUT = 0, 1                           # fp_resize_ragged output modes
 TOPK_MAX = 16                                              # FP_TOPK_MAX: largest k of fp_cosine_topk_x6
@@ -180,6 +186,8 @@ SIGNATURES = {
     "fp_blaze_decode": (_I, [_P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P]),
     "fp_blaze_weighted_nms": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P]),
     "fp_yolo_decode": (_I, [_P, _I, _I, _I, _I, _F, C.POINTER(_F), _P, _I64, _I64, _P]),
+    "fp_tta_views": (_I, [_P, _I, _I, _I, C.POINTER(FpTtaView), _P, _P, _F, _P]),
+    "fp_yolo_decode_view": (_I, [_P, _I, _I, _I, _I, _F, C.POINTER(_F), _P, _I64, _I64, _F, _I, _I, _I, _P]),
     "fp_yolo_nms": (_I, [_P, _I, _I, _F, _F, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
     "fp_yolo_nms_scratch_bytes": (_SZ, [_I, _I]),
     "fp_yolo_w_nms": (_I, [_P, _I, _I, _F, _F, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),

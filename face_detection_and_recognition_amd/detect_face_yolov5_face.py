@@ -2,7 +2,8 @@
 Entry point with the reference's flags (face_detection_and_extraction/detect_face_yolov5_face.py:13-66).  ``-o out.jpg`` also
 saves the image with the detections drawn on, ``--anonymize CELL`` pixelates the faces in it first (annotate.py).  ``--tile W H
 --merge_thr T`` (with ``--overlap``, ``--edge_px``, ``--no_full_frame``) runs the detector on overlapping tiles of the image as well and
-merges the detections on the device (tiling.py)."""
+merges the detections on the device (tiling.py).  ``--augment`` runs the reference's augmented inference: the image, the image
+mirrored and scaled by 0.83, and the image scaled by 0.67, behind one NMS (modules/yolov5_face/tta.py)."""
 import argparse
 import json
 import os
@@ -15,14 +16,15 @@ from .modules.yolov5_face.model import YOLOV5FaceModel
 from .tiling import add_tile_args, wrap_from_args
 
 
-def load_model(model_path: str, det_thres: float, bbox_area_thres: float, model_in_size: Tuple[int, int], device: str):
+def load_model(model_path: str, det_thres: float, bbox_area_thres: float, model_in_size: Tuple[int, int], device: str,
+               augment: bool = False):
     """detect_face_yolov5_face.py:13-38: .pt/.pth (state_dict) -> HIP network; .onnx sessions are out of scope."""
     _, fext = os.path.splitext(model_path)
     if fext in {".pt", ".pth"}:
         net = attempt_load(model_path, torch_device(device))
     else:
         raise NotImplementedError(f"[ERROR] model with extension {fext} not implemented")
-    return YOLOV5FaceModel(net, det_thres, bbox_area_thres, inference_pytorch_model_yolov5_face, model_in_size)
+    return YOLOV5FaceModel(net, det_thres, bbox_area_thres, inference_pytorch_model_yolov5_face, model_in_size, augment=augment)
 
 
 def build_parser():
@@ -36,6 +38,8 @@ def build_parser():
                         help="Write the image with its detections drawn on (box, landmarks, caption) to this JPEG file.")
     parser.add_argument("--anonymize", dest="anonymize", type=int, choices=[4, 8, 16, 32], default=argparse.SUPPRESS, metavar="CELL",
                         help="With -o: pixelate every detected face first, mosaic cells of CELL x CELL pixels (4, 8, 16 or 32).")
+    parser.add_argument("--augment", action="store_true", default=argparse.SUPPRESS,
+                        help="Augmented inference: also run the image mirrored at scale 0.83 and at scale 0.67, one NMS over all rows.")
     return add_tile_args(parser)
 
 
@@ -44,7 +48,7 @@ def main(argv=None):
     args = parser.parse_args(argv)
     print("Current Arguments: ", args)
     args.input_size = tuple(map(int, args.input_size))
-    net = load_model(args.model, args.det_thres, args.bbox_area_thres, args.input_size, args.device)
+    net = load_model(args.model, args.det_thres, args.bbox_area_thres, args.input_size, args.device, augment=getattr(args, "augment", False))
     net = wrap_from_args(net, args, parser.error)
     post = inference_img(net, args.input_src, save=getattr(args, "output", None), anonymize=getattr(args, "anonymize", 0))
     print(json.dumps({"boxes": post.boxes.tolist(), "confs": post.bbox_confs.tolist(), "areas": post.bbox_areas.tolist()}))

@@ -8,7 +8,8 @@ fast / slow, or the YOLOv5-face architecture name), ``--is W H`` the input size,
 per detector call.  ``--dets detections.json`` scores an existing COCO-format detection file without running a detector.
 ``--model synthetic`` runs seeded random weights (synth.py / workload.py).  ``--tile W H --merge_thr T`` (with ``--overlap``,
 ``--edge_px``, ``--no_full_frame``) scores the detector run on overlapping tiles of every image and on the whole image
-(tiling.TiledDetector; blazeface and yolov5_face, MTCNN refuses).  Writes annotations.json and detections.json in
+(tiling.TiledDetector; blazeface and yolov5_face, MTCNN refuses).  ``--augment`` scores YOLOv5-face with the reference's
+augmented inference (three views behind one NMS; yolov5_face only, any other model type is refused).  Writes annotations.json and detections.json in
 the reference's formats into ``--out`` (default: the current directory), prints the summary and returns the result.
 """
 import argparse
@@ -97,11 +98,13 @@ def load_detector(args, dev):
         size = tuple(args.input_size) if args.input_size else (640, 640)
         if synthetic:
             from ..workload import build_yolo_detector
-            return build_yolo_detector(dev, make_frames(4, dev), name=args.variant or "yolov5n", input_size=size)
+            det = build_yolo_detector(dev, make_frames(4, dev), name=args.variant or "yolov5n", input_size=size)
+            det.augment = bool(getattr(args, "augment", False))
+            return det
         from ..modules.yolov5_face import attempt_load, inference_pytorch_model_yolov5_face
         from ..modules.yolov5_face.model import YOLOV5FaceModel
         net = attempt_load(args.model, dev, cfg=args.variant)
-        return YOLOV5FaceModel(net, 0.4, 0.0, inference_pytorch_model_yolov5_face, size)
+        return YOLOV5FaceModel(net, 0.4, 0.0, inference_pytorch_model_yolov5_face, size, augment=getattr(args, "augment", False))
     if args.input_size:
         raise ValueError("--is applies to yolov5_face only")
     if args.model_type == "blazeface":
@@ -173,10 +176,15 @@ def main(argv=None):
     parser.add_argument("--dets", default=None, help="Score this COCO-format detections.json instead of running a detector.")
     parser.add_argument("--out", default=".", help="Directory for annotations.json (written in --dets mode too) and detections.json "
                                                   "(default: %(default)s).")
+    parser.add_argument("--augment", action="store_true",
+                        help="yolov5_face only: augmented inference (the image, mirrored at scale 0.83, at scale 0.67; one NMS).")
     add_tile_args(parser)
     args = parser.parse_args(argv)
     if args.batch < 1:
         parser.error("--batch must be positive")
+    if args.augment and args.model_type != "yolov5_face":
+        parser.error(f"--augment applies to yolov5_face only: {args.model_type} has no augmented inference "
+                     "(BlazeFace has a fixed input, MTCNN its own pyramid)")
 
     names, gt_boxes, gt_ids = parse_wider(args.ann, args.pics)
     os.makedirs(args.out, exist_ok=True)

@@ -42,7 +42,7 @@ class FrameFacesObj:
 
 def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=None, save_face=False,
                                      quality=95, align=False, quality_gate=None, tiled=None, tracker=None,
-                                     streams=None) -> List[FrameFacesObj]:
+                                     streams=None, augment=None) -> List[FrameFacesObj]:
     """frames: (B, H, W, 3) u8 BGR (numpy or CUDA tensor), a RaggedFrames, or a list of (h, w, 3) frames.  One FacePipeline
     step (no similarity filter needed); returns per-frame records with boxes (each frame's own pixels, rounded), confs,
     area fractions and embeddings.  A list whose frames share one size is stacked and takes the uniform path; otherwise it
@@ -56,12 +56,17 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
     tiled: dict(tile=(w, h), overlap=(ox, oy), merge_thr=t[, edge_px, full_frame, max_det]): for this call the pipeline's
     detector runs on overlapping tiles of every frame as well (tiling.TiledDetector over pipe.det; merge_thr has no default).
     tracker: a tracking.StreamTracker: for this call the step also tracks its faces (streams: the stream of every frame, None =
-    consecutive frames of stream 0) and every record carries track_ids, one per face; calls must come in video order."""
+    consecutive frames of stream 0) and every record carries track_ids, one per face; calls must come in video order.
+    augment: True / False: for this call the pipeline's YOLOv5-face detector runs with / without augmented inference (the
+    reference's three views behind one NMS; ValueError for a detector without it); None leaves the detector as it is."""
     if isinstance(frames, (list, tuple)) and not frames:
         return []
     frames = as_frames(frames, pipe.dev)
     B = len(frames)
     was = (pipe.det, pipe.align, pipe.tracker)
+    base_det, was_augment = pipe.det, getattr(pipe.det, "augment", None)
+    if augment is not None and was_augment is None:
+        raise ValueError(f"augment= needs a YOLOv5-face detector; {type(pipe.det).__name__} has no augmented inference")
     if tiled is not None:
         from ..tiling import TiledDetector
         key = tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in tiled.items()))
@@ -73,9 +78,13 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
     if tracker is not None:
         pipe.tracker = tracker
     try:
+        if augment is not None:
+            base_det.augment = bool(augment)
         res = pipe.step(frames, streams=streams)   # detect -> crops -> embed (+ the exact re-run on a detector overflow)
     finally:
         pipe.det, pipe.align, pipe.tracker = was
+        if augment is not None:
+            base_det.augment = was_augment
     n = res["n_faces"]
     emb = res["emb"].cpu().numpy()
     info = res["info"].cpu().numpy()
@@ -120,18 +129,18 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
 
 
 def extract_faces_from_images(pipe, paths, batch_size=256, entropy="host", save_face=False, quality=95,
-                              align=False, quality_gate=None, tiled=None) -> List[FrameFacesObj]:
+                              align=False, quality_gate=None, tiled=None, augment=None) -> List[FrameFacesObj]:
     """The reference's image media items (:400-407: one photo per item, any size, recorded as FrameFacesObj(1, 1, ...)) for a
     whole list of files: decode batch_size files at a time (modules/utils/jpeg.py imread_batch; entropy as there), then one
     pipeline step per batch -- frames of different sizes as one RaggedFrames.  Returns one record per path, in order; pass
-    each to save_extracted_faces under its file's media_root.  align, quality_gate, tiled: as extract_face_feat_conf_area_list."""
+    each to save_extracted_faces under its file's media_root.  align, quality_gate, tiled, augment: as extract_face_feat_conf_area_list."""
     from ..modules.utils.jpeg import imread_batch
     out = []
     for i in range(0, len(paths), int(batch_size)):
         chunk = paths[i:i + int(batch_size)]
         frames = imread_batch(chunk, pipe.dev, entropy=entropy)     # (B, H, W, 3) when the sizes agree, else a list
         recs = extract_face_feat_conf_area_list(pipe, frames, save_face=save_face, quality=quality, align=align,
-                                                quality_gate=quality_gate, tiled=tiled)
+                                                quality_gate=quality_gate, tiled=tiled, augment=augment)
         for r in recs:
             r.frame_num, r.time_sec = 1, 1
         out.extend(recs)

@@ -21,6 +21,7 @@ import torch.nn as nn
 from ... import _lib as L
 from ...plan import CompiledPlan, PlanBuilder, PlanCache, View, cpad, switch_key
 from ..params import BNParams, ConvParams, PlanCacheMixin, _NoCompute, bn_sb, npy
+from . import tta
 
 # Architecture specs of the reference's in-tree yamls (y5/models/yolov5n.yaml, yolov5s.yaml, yolov5n-0.5.yaml):
 # [from, number, module, args] rows, same meaning as upstream.
@@ -415,7 +416,8 @@ class Detect(_NoCompute):
 
 class Model(PlanCacheMixin, nn.Module):
     """yolo.py:116-257.  ``forward(x)``: (b, 3, H, W) float in [0, 1], H and W multiples of 32 ->
-    ``(z, heads)`` with z (b, sum(3*ny*nx), 16) decoded predictions, like the reference in eval mode."""
+    ``(z, heads)`` with z (b, sum(3*ny*nx), 16) decoded predictions, like the reference in eval mode.
+    ``forward(x, augment=True)``: ``(z, None)`` with the rows of the reference's three views (run_views)."""
 
     def __init__(self, cfg="yolov5s", ch=3, nc=None):
         super().__init__()
@@ -604,10 +606,14 @@ class Model(PlanCacheMixin, nn.Module):
         plan.n_rows = n_rows
         return plan
 
-    def plan_for(self, N, H=640, W=640, frame_hw=None):
+    def plan_for(self, N, H=640, W=640, frame_hw=None, slot=0):
+        """slot: a plan of its own for the same shape (the scaled views of run_views: a view whose padded size equals the
+        input's must not share the input's arena); 0 is the plan every other caller gets."""
         if self._device().type != "cuda":
             raise L.FacepathError("YOLOv5-face runs only on a HIP device (model.to('cuda')); there is no CPU path")
         key = (N, H, W, frame_hw, switch_key(PlanBuilder, Conv, StemBlock, C3, ShuffleV2Block, SPP, Concat, Model))
+        if slot:
+            key += (slot,)
         return self._plans.get(key, lambda cache: self._build(N, H, W, cache, frame_hw))
 
     def run_plan(self, plan):
@@ -627,11 +633,46 @@ class Model(PlanCacheMixin, nn.Module):
             row += det.na * ny * nx
         return plan.z
 
-    def forward(self, x, augment=False, profile=False):
+    def run_views(self, plan, landmarks="reference"):
+        """Augmented inference (yolo.py:156-175) from a view-1 plan whose fp32 input is filled: the plan itself, the inputs of
+        the mirrored 0.83 view and of the 0.67 view from its canvas (fp_tta_views), the same network at those two sizes, and
+        the three decodes with their un-mapping (fp_yolo_decode_view) into ONE (N, R1 + R2 + R3, 16) tensor, views in the
+        reference's order.  Everything goes on the current stream, in order.  landmarks: "reference" leaves columns 5..14
+        of views 2 and 3 in the view's own pixels, unmirrored, as the reference does; "mapped" maps them like the boxes.
+        The result is valid until the next run_views of this model."""
+        if plan.input is None:
+            raise L.FacepathError("run_views needs the fp32 canvas: a plan whose stem reads u8 frames has none")
+        if landmarks not in tta.LM_MODES:
+            raise ValueError(f"landmarks must be one of {sorted(tta.LM_MODES)}, not {landmarks!r}")
+        N, (H, W) = plan.N, plan.canvas_hw
+        views = tta.tta_views(H, W)
+        plans = [plan] + [self.plan_for(N, v[3][0], v[3][1], slot=i + 1) for i, v in enumerate(views[1:])]
+        rows = sum(p.n_rows for p in plans)
+        key = (N, rows, plan.arena.device)
+        if self._tta_z is None or self._tta_z[0] != key:
+            self._tta_z = (key, torch.empty((N, rows, 16), dtype=torch.float32, device=plan.arena.device))
+        z = self._tta_z[1]
+        plan.run()
+        tta.fill_views(plan.input, plans[1].input, plans[2].input)
+        plans[1].run()
+        plans[2].run()
+        det = self.model[-1]
+        row = 0
+        for p, (ratio, flip, _, _) in zip(plans, views):
+            row = tta.decode_view(det, p.heads, z, row, ratio, flip, W, landmarks)
+        self.last_view_plans = plans
+        return z
+
+    _tta_z = None            # (key, tensor): the concatenated rows of the last run_views
+    last_view_plans = None   # measurement / tests: the three plans of the last run_views
+
+    def forward(self, x, augment=False, profile=False, landmarks="reference"):
         b, _, H, W = x.shape
         plan = self.plan_for(b, H, W)
         plan.input[..., :3].copy_(x.to(self._device(), torch.float32).permute(0, 2, 3, 1))
         plan.input[..., 3:].zero_()
+        if augment:
+            return self.run_views(plan, landmarks).clone(), None      # yolo.py:172
         z = self.run_plan(plan).clone()              # plan.z / plan.heads are arena views the next call overwrites
         det = self.model[-1]
         heads = [h.view(b, h.shape[1], h.shape[2], det.na, det.no).permute(0, 3, 1, 2, 4).clone() for h in plan.heads]

@@ -590,6 +590,46 @@ int fp_yolo_w_nms(const float* pred, int B, int n_rows, float conf_thres, float 
                   float* out /*[B][max_out][7]*/, int32_t* out_count, int32_t* keep_idx, int32_t* overflow,
                   void* scratch, size_t scratch_bytes, void* stream);
 
+/*
+ * Augmented inference (y5/models/yolo.py:156-175, scale_img of y5/utils/torch_utils.py:230-240): the network runs on the
+ * input, on the input mirrored left-right and scaled by 0.83, and on the input scaled by 0.67; the rows of the three runs,
+ * mapped back to the input's pixels, go through one NMS.  Additions of ABI 15, csrc/tta.hip.
+ *
+ * fp_tta_views fills the inputs of the two scaled views in ONE launch.  canvas [N][H][W][4] fp32 is the view-1 input (channel
+ * 3 is zero and is not read for its value); out_a / out_b are [N][padded_h][padded_w][4] of views[0] / views[1].  Inside the
+ * content rectangle (content_h x content_w, top left) a pixel is F.interpolate(mode="bilinear", align_corners=False) of the
+ * canvas -- of the canvas mirrored left-right when flip is 1 --: scale = (float)in / content, src = max(fmaf(scale, dst + 0.5f,
+ * -0.5f), 0) (one fma, as torch's CPU build evaluates it), i0 = (int)src, i1 = min(i0 + 1, in - 1), l = src - i0, value = (a (1 - lx) + b lx)(1 - ly) + (c (1 - lx) + d lx)
+ * ly in that order, no fma.  Everywhere else channels 0..2 are pad_value (the reference pads with 0.447); channel 3 is 0 in every
+ * pixel.  Every float of both outputs is written, nothing else is.  Refusals before any launch: a NULL pointer, N < 0 or >
+ * 65535, a content size outside 1 .. min(padded, canvas) per axis, flip outside 0 / 1, 2^31 pixels or more in an image
+ * (FP_ERR_INVALID_ARG); a pointer not 16-byte aligned (FP_ERR_ALIGNMENT).  N == 0: FP_OK, nothing launched.  out_a / out_b must
+ * not overlap the canvas.
+ *
+ * fp_yolo_decode_view = fp_yolo_decode followed, in the same lane, by the view's un-mapping in the reference's order:
+ * columns 0..3 divided by si (an fp32 IEEE division by the float nearest the ratio, as torch's `/= si`; not a multiplication by
+ * a reciprocal: the rows feed NMS threshold decisions), then for flip = 1 cx = (float)img_w - cx.  lm_mode 0 leaves columns
+ * 5..14 as decoded -- the reference's behaviour: its landmarks of a scaled view stay in that view's pixels, unmirrored.
+ * lm_mode 1 divides every landmark coordinate by si and, for flip = 1, sets x = (float)img_w - x and exchanges points 0 <-> 1
+ * (eyes) and 3 <-> 4 (mouth corners), so that columns 5..14 mean the same in every row.  With si = 1, flip = 0 the rows equal
+ * fp_yolo_decode's bit for bit.  Refusals: fp_yolo_decode's, and si <= 0 or NaN, flip / lm_mode outside 0 / 1, img_w <= 0, a
+ * negative stride or offset (FP_ERR_INVALID_ARG); out not 16-byte aligned or out_image_stride % 4 (FP_ERR_ALIGNMENT).
+ */
+typedef struct fp_tta_view {
+  int32_t content_h, content_w;   /* (int)(h * ratio), (int)(w * ratio) */
+  int32_t padded_h, padded_w;     /* ceil(x * ratio / 32) * 32: the view's network input */
+  int32_t flip;                   /* 1: the view looks at the canvas mirrored left-right */
+  int32_t reserved;
+} fp_tta_view;
+
+int fp_tta_views(const float* canvas, int N, int H, int W, const fp_tta_view* views /*host [2]*/,
+                 float* out_a, float* out_b, float pad_value, void* stream);
+
+int fp_yolo_decode_view(const float* head, int B, int ny, int nx, int na,
+                        float stride, const float* anchors_px /*host [na][2]*/,
+                        float* out, int64_t out_image_stride /*floats*/, int64_t out_row_offset /*rows*/,
+                        float si, int flip, int img_w, int lm_mode, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* 5. Similarity filter                                                        */
 /* ------------------------------------------------------------------------- */

@@ -185,9 +185,10 @@ __global__ __launch_bounds__(256, 3) void blazeblock_wp_kernel(BlazeWpArgs p) {
 // workgroup barrier in the loop; the 1x1 weights of the whole block stay in LDS (shared by the four waves); the output
 // tile overwrites the A tile in LDS once the MFMAs have consumed it; the shortcut is re-read from the input (an L2 hit,
 // requested before the MFMAs) when the tile is stored, so no shortcut tile is kept.
-// Measured (batch 256): 48 -> 48 blocks 52 -> 41 us, 96 -> 96 blocks 44 (two kernels) -> 33 us.  A tile costs a wave
-// ~5 / ~8.5 us (C = 48 / 96) of mostly serial latency -- window round trip, depthwise, an MFMA phase with one or two
-// waves per SIMD -- so the grid gives every wave as few tiles as the resident workgroup count allows.
+// Measured (batch 256): 48 -> 48 blocks 52 -> 41 us, 96 -> 96 blocks 44 (two kernels) -> 33 us with this template (four
+// waves, one workgroup per CU at C = 96) -> 24 us with the eight-wave specialisation below, which is what C = 96 runs.  A
+// tile costs a wave ~5 / ~8.5 us (C = 48 / 96) of mostly serial latency -- window round trip, depthwise, an MFMA phase
+// with two waves per SIMD -- so the grid gives every wave as few tiles as the resident workgroup count allows.
 struct BlazeWpsArgs {
   const float* in;    // pixel (0, 0) of image 0, row-padded
   float* out;
@@ -201,6 +202,13 @@ struct BlazeWpsArgs {
   long in_ns, out_ns;
   fp_divisor tpi_div;
 };
+
+// Waves per workgroup: C = 48 runs four (this template, two workgroups per CU), C = 96 eight (the specialisation below, one
+// workgroup per CU).
+template <int C>
+constexpr int blaze_wps_waves = C > 48 ? 8 : 4;
+typedef __attribute__((address_space(3))) void* lds_ptr;
+typedef const __attribute__((address_space(1))) void* gbl_ptr;
 
 template <int C>
 __global__ __launch_bounds__(256, C <= 48 ? 2 : 1) void blazeblock_wps_kernel(BlazeWpsArgs p) {
@@ -248,7 +256,7 @@ __global__ __launch_bounds__(256, C <= 48 ? 2 : 1) void blazeblock_wps_kernel(Bl
   };
   // The windows of ALL channel passes of a tile are requested in one batch (one memory round trip per tile instead of
   // one per pass: these launches are latency bound), the next tile's right after this tile's depthwise phase, so they
-  // arrive under its MFMAs.  The register budget (72 VGPRs per pass) is why only 2 (C = 48) / 1 (C = 96) workgroups
+  // arrive under its MFMAs.  The register budget (72 VGPRs per pass) is why only 2 workgroups (C = 48: eight waves)
   // share a CU.
   f32x4 x[PASSES][3][6];
   auto issue_windows = [&](long ic) {
@@ -354,6 +362,202 @@ __global__ __launch_bounds__(256, C <= 48 ? 2 : 1) void blazeblock_wps_kernel(Bl
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// C = 96 (the seven blocks on the 16 x 16 map): EIGHT waves per workgroup, one workgroup per CU, two waves per SIMD.  At batch
+// 256 a launch has 2048 tiles = 256 CUs x 8 waves: every wave owns ONE tile, and one wave's MFMAs (144 per tile, 64 cycles
+// each) run under the loads and the depthwise phase of the other wave of its SIMD.  With four waves (the kernel above) a wave
+// ran two tiles in series with nothing beside it on its SIMD.  Same arithmetic per output value as the kernel above: the three
+// packed-FMA statements per tap row, the MFMAs in (kq, e, nb) order, bias, shortcut, ReLU; which wave computes a tile does not
+// matter.  What differs:
+//   * 140 KB of LDS: taps, bias, the 1x1 weights (shared by the eight waves) and eight wave regions;
+//   * 256 registers per wave, so the windows ROLL through two slots of 72 VGPRs: passes 0 and 1 are requested up front, pass
+//     p + 2 into the slot of pass p as soon as its depthwise has consumed it: passes 2 and 3 travel under the depthwise of
+//     passes 0 and 1.  Of a following tile, pass 0 is requested after the depthwise of pass 2 (under the MFMAs) and pass 1
+//     only once the accumulators are dead: 48 accumulators + 48 shortcut values + two full slots do not fit;
+//   * the 1x1 weights are staged by LDS-DMA (the packed layout is the LDS layout; 36 pieces of 1 KiB) while the taps and the
+//     bias travel through registers: one round trip, no 37 KB of loads and LDS writes in front of the barrier.
+// Requesting the first windows BEFORE the staging and the barrier (they need no LDS) measured nothing with eight waves and
+// cost 2.4 us per launch with four, so they are requested behind the barrier.
+// 240 VGPRs, 140 KB of LDS, no scratch.  Measured (batch 256, the detector plan of the two-stream benchmark, HIP events per op,
+// four alternating runs): 29.2-31.0 us per launch with the kernel above -> 23.5-27.2 us (FINDINGS.md finding 83).
+template <>
+__global__ __launch_bounds__(64 * blaze_wps_waves<96>, 1) void blazeblock_wps_kernel<96>(BlazeWpsArgs p) {
+  constexpr int C = 96, WAVES = blaze_wps_waves<C>;
+  constexpr int NB = C / 32, KG = C / 8, LDT = C + 4, PASSES = C / 24, C4T = C / 4, SLOTS = 2, TAPQ = 10 * C / 4;
+  constexpr int NST = (32 * C4T) / 64;                      // 16-byte stores per lane and tile
+  constexpr int PIECES = C * C * 4 / 1024;                  // LDS-DMA pieces of the 1x1 weights: 64 lanes x 16 bytes
+  static_assert(WAVES == 8 && PASSES % SLOTS == 0 && TAPQ <= 64 * WAVES && PIECES * 1024 == C * C * 4, "staging, slot refill");
+  static_assert(4 * (10 * C + C + C * C + WAVES * 32 * LDT) <= 160 * 1024, "LDS of a CU");
+  static_assert((16 * C4T) % 64 == 0, "a store does not straddle the two rows of a tile on a 16-wide map");
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* Ws = smem;                                         // [10][C] depthwise taps + bias
+  float* Bp = Ws + 10 * C;                                  // [C] pointwise bias
+  float* Bs = Bp + C;                                       // [C/4][C][4] pointwise weights
+  float* Wv = Bs + C * C;                                   // 8 wave regions [32][LDT]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lr = lane & 31, h = lane >> 5;
+
+  // depthwise item of this lane in every pass, as above
+  const bool dw_lane = lane < 48;
+  const int la = dw_lane ? lane : 0;
+  const int g = la / 6, c4 = la - g * 6;
+  const int gr = (4 * g) >> p.wshift, gx = (4 * g) & (p.W - 1);
+  unsigned voff_dw = (unsigned)(((gr * (p.W + 1) + gx) * C + 4 * c4) * 4);
+  const char* inb = (const char*)p.in;
+  char* outb = (char*)p.out;
+  const long in_rb = (long)p.in_rp * 4, out_rb = (long)p.out_rp * 4;
+  // the 64 float4s of store j lie in ONE row of the tile (a 16-wide map puts 16 C/4 = 64 NST/2 of them in a row): the row is
+  // scalar, and the lane offset within the row is the same for the shortcut load and the store
+  auto row_of = [&](int j) { return (long)((j * 64 / C4T) >> p.wshift); };
+
+  const int pos = (int)fp_xcd_block();
+  auto locate = [&](int t, long& ic, long& oo) {
+    const unsigned img = fp_fastdiv((unsigned)t, p.tpi_div), k = (unsigned)t - img * (unsigned)p.tiles_per_img;
+    const unsigned y0 = (k * 32u) >> p.wshift;
+    ic = fp_uniform(((long)img * p.in_ns + (long)y0 * p.in_rp) * 4);
+    oo = fp_uniform(((long)img * p.out_ns + (long)y0 * p.out_rp) * 4);
+  };
+  f32x4 x[SLOTS][3][6];
+  auto issue_pass = [&](long ic, int ps, int slot) {       // the window of channel pass ps of the tile at ic -> x[slot]
+    const long win = ic - in_rb - C * 4;                    // pixel (y0 - 1, -1)
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+      const char* rowp = inb + fp_uniform(win + ky * in_rb + ps * 96);
+#pragma unroll
+      for (int j = 0; j < 6; ++j) x[slot][ky][j] = *(const f32x4*)(rowp + voff_dw + j * C * 4);
+    }
+  };
+
+  int t = (pos * WAVES + wv) * p.per_wave;
+  const int t_end = min(t + p.per_wave, p.ntiles);
+  long in_ctr = 0, out_o = 0;
+
+  // ---- prologue: taps and bias -> registers, 1x1 weights by LDS-DMA: one round trip.  A wave whose run is empty stages its
+  // share, reaches the barrier and does nothing else. ----
+  f32x4 tapv = {0.f, 0.f, 0.f, 0.f};
+  float bpv = 0.f;
+  if (tid < TAPQ) tapv = (tid * 4 < 9 * C) ? *(const f32x4*)(p.wd + tid * 4) : *(const f32x4*)(p.bd + (tid * 4 - 9 * C));
+  if (tid < C) bpv = p.bp[tid];
+  {
+    const unsigned char* src = (const unsigned char*)p.wp + lane * 16;
+#pragma unroll
+    for (int j = 0; j < (PIECES + WAVES - 1) / WAVES; ++j) {
+      const int piece = j * WAVES + wv;
+      if (piece < PIECES)
+        __builtin_amdgcn_global_load_lds((gbl_ptr)(src + piece * 1024), (lds_ptr)((unsigned char*)Bs + piece * 1024), 16, 0, 0);
+    }
+  }
+  if (tid < TAPQ) *(f32x4*)&Ws[tid * 4] = tapv;
+  if (tid < C) Bp[tid] = bpv;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's LDS-DMA pieces have landed before it reaches the barrier
+  __syncthreads();                                          // the only workgroup barrier
+  if (t < t_end) {
+    locate(t, in_ctr, out_o);
+    issue_pass(in_ctr, 0, 0);
+    issue_pass(in_ctr, 1, 1);
+  }
+
+  float* At = Wv + wv * (32 * LDT);                         // A tile [32][LDT]; later the output tile [32][C]
+  float bias_n[NB];
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb) bias_n[nb] = Bp[nb * 32 + lr];
+
+  // one tile; more_v (a compile-time constant): another tile of this wave's run follows
+  auto tile = [&](auto more_v) {
+    constexpr bool more = decltype(more_v)::value;
+    long in_nx = 0, out_nx = 0;
+    if (more) locate(t + 1, in_nx, out_nx);
+    // Lane offsets are rebuilt per tile: hoisted out of the loop, `p.in + lane offset` becomes a 64-bit vector address per load
+    // and store (50 registers, and scratch); rebuilt, every access is `global_* v, v_offset32, s[base]`.
+    unsigned lane_t = (unsigned)lane;
+    asm volatile("" : "+v"(voff_dw), "+v"(lane_t));
+    // ---- depthwise, 24 channels per pass -> A tile; the slot a pass has consumed is refilled at once ----
+#pragma unroll
+    for (int ps = 0; ps < PASSES; ++ps) {
+      const int sl = ps % SLOTS;
+      const float* wl = &Ws[ps * 24 + 4 * c4];
+      const f32x4 dbias = *(const f32x4*)(wl + 9 * C);
+      f32x4 acc[4] = {dbias, dbias, dbias, dbias};
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky) {
+        const f32x4 w0 = *(const f32x4*)(wl + (ky * 3 + 0) * C);
+        const f32x4 w1 = *(const f32x4*)(wl + (ky * 3 + 1) * C);
+        const f32x4 w2 = *(const f32x4*)(wl + (ky * 3 + 2) * C);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {   // three statements: each contracts to one packed FMA on the accumulator
+          acc[q] += x[sl][ky][q] * w0;
+          acc[q] += x[sl][ky][q + 1] * w1;
+          acc[q] += x[sl][ky][q + 2] * w2;
+        }
+      }
+      if (dw_lane) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) *(f32x4*)&At[(4 * g + q) * LDT + ps * 24 + 4 * c4] = acc[q];
+      }
+      __builtin_amdgcn_sched_barrier(0);   // (a request hoisted above the FMAs would need a third slot)
+      if (ps + SLOTS < PASSES) issue_pass(in_ctr, ps + SLOTS, sl);
+      else if (more && ps + 1 < PASSES) issue_pass(in_nx, ps + SLOTS - PASSES, sl);
+    }
+    // ---- shortcut values of the float4s this lane will store: in flight during the MFMAs ----
+    f32x4 xc[NST];
+    unsigned ooff[NST];
+#pragma unroll
+    for (int j = 0; j < NST; ++j) {
+      const unsigned i = lane_t + 64u * j;
+      const unsigned px = i / C4T, cq = i - px * C4T;
+      ooff[j] = ((px & (unsigned)(p.W - 1)) * C + cq * 4) * 4u;
+      xc[j] = *(const f32x4*)(inb + fp_uniform(in_ctr + row_of(j) * in_rb) + ooff[j]);
+    }
+    const long out_cur = out_o;
+    in_ctr = in_nx;
+    out_o = out_nx;
+    __builtin_amdgcn_sched_barrier(0);     // the shortcut requests stay in front of the MFMAs
+    // ---- 1x1 on the MFMA pipe ----
+    f32x16 macc[NB];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) macc[nb][r] = 0.f;
+    const float* arow = &At[lr * LDT + 4 * h];
+#pragma unroll
+    for (int kq = 0; kq < KG; ++kq) {
+      const f32x4 a = *(const f32x4*)(arow + kq * 8);
+      f32x4 b[NB];
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) b[nb] = *(const f32x4*)&Bs[((kq * 2 + h) * C + nb * 32 + lr) * 4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) {
+          macc[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], b[nb][e], macc[nb], 0, 0, 0);
+          FP_MFMA_ORDER();
+        }
+    }
+    // ---- + bias -> output tile [32][C] over the A tile (this wave's MFMAs have consumed it) ----
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg)
+        At[((reg & 3) + 8 * (reg >> 2) + 4 * h) * C + nb * 32 + lr] = macc[nb][reg] + bias_n[nb];
+    // the accumulators are dead: the next tile's second slot, ahead of this tile's stores in the in-order vmcnt queue
+    if (more) issue_pass(in_ctr, SLOTS - 1, SLOTS - 1);
+    // ---- + shortcut, ReLU, 16-byte stores ----
+#pragma unroll
+    for (int j = 0; j < NST; ++j) {
+      const f32x4 v = *(const f32x4*)&At[(lane + 64 * j) * 4] + xc[j];
+      f32x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = v[e] > 0.f ? v[e] : 0.f;
+      *(f32x4*)(outb + fp_uniform(out_cur + row_of(j) * out_rb) + ooff[j]) = o;
+    }
+  };
+  // The last tile of a run is peeled.  Inside one loop body a slot that is refilled only `if (more)` stays live through the
+  // MFMAs on the other path (72 registers that hold nothing) and the kernel spills; and at batch 256 it is the only tile.
+  for (; t + 1 < t_end; ++t) tile(std::true_type{});
+  if (t < t_end) tile(std::false_type{});
+}
+
 }  // namespace
 
 // Wave-private kernel: stride 1, 24 -> 24 with the full shortcut, rows that split into 32-pixel tiles, row-padded input.
@@ -396,17 +600,19 @@ static int launch_blazeblock_wps(const fp_op& op, const fp_launch& L) {
   a.out_rp = (op.OW + ((op.flags & FP_OPF_OUT_ROWPAD) ? 1 : 0)) * C;
   a.in_ns = op.in_ns; a.out_ns = op.out_ns;
   a.tpi_div = fp_make_divisor((unsigned)a.tiles_per_img);
-  const size_t lds = 4 * ((size_t)10 * C + NPAD + (size_t)C * NPAD + 4 * (size_t)32 * (C + 4));
-  // persistent grid: 2 (C = 48) / 1 (C = 96: 92 KB of LDS) workgroups per CU, every wave a contiguous run of tiles
+  constexpr int WAVES = blaze_wps_waves<C>;
+  const size_t lds = 4 * ((size_t)10 * C + NPAD + (size_t)C * NPAD + WAVES * (size_t)32 * (C + 4));
+  // persistent grid: 2 (C = 48, four waves) / 1 (C = 96, eight waves: 140 KB of LDS) workgroups per CU, every wave a contiguous
+  // run of tiles
   const int max_wg = 256 * (C <= 48 ? 2 : 1);
-  a.per_wave = fp_ceil_div(a.ntiles, max_wg * 4);
-  const int G = fp_ceil_div(a.ntiles, 4 * a.per_wave);
+  a.per_wave = fp_ceil_div(a.ntiles, max_wg * WAVES);
+  const int G = fp_ceil_div(a.ntiles, WAVES * a.per_wave);
   hipError_t ae = hipFuncSetAttribute((const void*)blazeblock_wps_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (ae != hipSuccess) {
     fp_set_hip_error(ae);
     return FP_ERR_LAUNCH;
   }
-  hipLaunchKernelGGL((blazeblock_wps_kernel<C>), dim3(G), dim3(256), lds, s, a);
+  hipLaunchKernelGGL((blazeblock_wps_kernel<C>), dim3(G), dim3(64 * WAVES), lds, s, a);
   FP_CHECK_LAUNCH();
   return FP_OK;
 }

@@ -131,6 +131,7 @@ TRACK_SLOT_INTS, TRACK_SLOT_FLOATS = 5, 10                                # colu
 TRACK_MOTION_FLOATS = 20                  # FP_TRACK_MOTION_FLOATS: x, v, p00, p01, p11 of cx, cy, w, h per slot of `motion`
 TRACK_NEW, TRACK_BEST, TRACK_DEAD_ROW, TRACK_FULL, TRACK_NO_STREAM, TRACK_OVER = 1, 2, 4, 8, 16, 32   # track_flags bits
 MOT_MAX_ROWS, MOT_STATE_ROWS = 64, 6   # FP_MOT_MAX_ROWS: rows of one frame fp_mot_match takes; int32 rows of its per-id state
+HOTA_MAX_ALPHAS = 32                   # FP_HOTA_MAX_ALPHAS: localisation thresholds fp_hota_match takes
 
 
 class FpTrackState(C.Structure):
@@ -263,6 +264,11 @@ SIGNATURES = {
     "fp_mot_match": (_I, [_P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I64, _D, _P, _P, _P, _P, _P, _SZ, _P]),
     "fp_mot_match_emulate": (_I, [_P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I64, _D, _P, _P, _P, _P, _P,
                                   _SZ]),
+    "fp_hota_match_workspace": (_SZ, [_I64, _I64, _I64]),
+    "fp_hota_match": (_I, [_P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I64, _I64, _P, _I, _P, _P, _P, _P, _P,
+                           _SZ, _P]),
+    "fp_hota_match_emulate": (_I, [_P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I64, _I64, _P, _I, _P, _P, _P,
+                                   _P, _P, _SZ]),
 }
 
 _lib = None

@@ -11,7 +11,8 @@
 //      B. the whole workgroup fills sim[64][64] (fp64, 32 KiB of LDS) and adds the admissible pairs to the sequence's
 //         pot[G][H] in global memory: ids are unique inside a frame, so a cell has one writer per frame, and a sequence's
 //         matrix is touched by its own workgroup only -- no atomics;
-//      C. wave 0 runs the shortest-augmenting-path assignment with COLUMNS ON LANES: minv, way, v, used and the column's row
+//      C. wave 0 runs the shortest-augmenting-path assignment with COLUMNS ON LANES (wave_assign of motassign.h, which
+//         hota.hip shares; the score comes in as a functor): minv, way, v, used and the column's row
 //         p are lane-private, u sits on the lane of its row, the scan of a step is one LDS read and three fp64 operations per
 //         lane, delta / j1 come from a wave arg-min over (value, lane), lower lane on equal values (the minimum by DPP row
 //         steps and readlanes, then the lowest lane of the ballot of the lanes that hold it) -- the ascending scan with
@@ -29,12 +30,12 @@
 #include <vector>
 
 #include "common.h"
+#include "motassign.h"
 
 namespace {
 
-constexpr int MR = FP_MOT_MAX_ROWS;
+using namespace motassign;   // mot_iou, mot_reduced, mot_clamp, mot_frame; wave_assign and host_assign
 constexpr int TPB = 256;
-static_assert(MR == FP_WAVE, "one column of the assignment per lane; one 64-bit ballot of matched rows");
 
 // rows of the per-id state: state[k][n_gt_ids]
 enum { S_LAST = 0, S_CURH = 1, S_STAMP = 2, S_SEEN = 3, S_HIT = 4, S_RUNS = 5, S_ROWS = 6 };
@@ -64,39 +65,9 @@ struct MotArgs {
 };
 
 // ---------------------------------------------------------------------------------------- the decision code, host and device
-// xywh boxes, the operations of evaluation._iou_matrix in its order
-__host__ __device__ __forceinline__ double mot_iou(const double* a, const double* b) {
-  const double iw = fmin(a[0] + a[2], b[0] + b[2]) - fmax(a[0], b[0]);
-  const double ih = fmin(a[1] + a[3], b[1] + b[3]) - fmax(a[1], b[1]);
-  if (iw <= 0.0 || ih <= 0.0) return 0.0;
-  const double i = iw * ih;
-  const double u = a[2] * a[3] + b[2] * b[3] - i;
-  return i / u;
-}
-
 // prev_h: the hypothesis id the ground-truth id held in the previous frame, -1 for none
 __host__ __device__ __forceinline__ double mot_score(double sim, double thr, int prev_h, int h) {
   return sim >= thr ? sim + (prev_h == h ? 1000.0 : 0.0) : 0.0;
-}
-
-// C[i0][j] - u[i0] - v[j] with C = -score
-__host__ __device__ __forceinline__ double mot_reduced(double score, double u, double v) { return (-score - u) - v; }
-
-__host__ __device__ __forceinline__ long mot_clamp(long v, long lo, long hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// The rows of one frame: CSR offsets kept inside the arrays, at most MR rows taken (the caller refuses longer frames).
-struct MotFrame {
-  long g0, h0;
-  int n, m;
-};
-__host__ __device__ __forceinline__ MotFrame mot_frame(const MotArgs& p, long gf, int G, int H) {
-  MotFrame fr;
-  fr.g0 = mot_clamp(p.gt_off[gf], 0, p.n_gt);
-  fr.h0 = mot_clamp(p.hy_off[gf], 0, p.n_hy);
-  const long g1 = mot_clamp(p.gt_off[gf + 1], fr.g0, p.n_gt), h1 = mot_clamp(p.hy_off[gf + 1], fr.h0, p.n_hy);
-  fr.n = G > 0 ? (int)mot_clamp(g1 - fr.g0, 0, MR) : 0;
-  fr.m = H > 0 ? (int)mot_clamp(h1 - fr.h0, 0, MR) : 0;
-  return fr;
 }
 
 // The sequence's slice of the arrays; every index derived from device data is clamped into the arrays.
@@ -120,27 +91,6 @@ __host__ __device__ __forceinline__ MotSeq mot_seq(const MotArgs& p, int s) {
 }
 
 // ------------------------------------------------------------------------------------------------------------- the kernel
-// Wave-uniform lane indices: v_readlane instead of a shuffle through LDS.
-__device__ __forceinline__ int lane_i(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
-__device__ __forceinline__ double lane_d(double v, int lane) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
-// The minimum of a wave's values (no NaN among them), in every lane: quad_perm [1,0,3,2] and [2,3,0,1], row_half_mirror and
-// row_mirror give every lane the minimum of its row of 16, the four rows meet through readlanes.
-__device__ __forceinline__ double wave_min(double v) {
-  v = fmin(v, dpp_d<0xB1>(v));
-  v = fmin(v, dpp_d<0x4E>(v));
-  v = fmin(v, dpp_d<0x141>(v));
-  v = fmin(v, dpp_d<0x140>(v));
-  return fmin(fmin(lane_d(v, 0), lane_d(v, 16)), fmin(lane_d(v, 32), lane_d(v, 48)));
-}
-
 __global__ __launch_bounds__(TPB) void mot_match_kernel(MotArgs p) {
   __shared__ double s_sim[MR * MR];
   __shared__ double s_gb[MR * 4], s_hb[MR * 4];
@@ -154,7 +104,6 @@ __global__ __launch_bounds__(TPB) void mot_match_kernel(MotArgs p) {
   int* st = p.state + q.id0;
   int* pot = p.pot + q.pot0;
   const double thr = p.thr;
-  const double INF = __builtin_huge_val();
   long TP = 0, FN = 0, FP = 0, IDSW = 0;
   double acc = 0.0;
 
@@ -185,57 +134,15 @@ __global__ __launch_bounds__(TPB) void mot_match_kernel(MotArgs p) {
     }
     __syncthreads();
     if (wave == 0) {
-      // C. assignment: lane = column - 1 (v, minv, way, used, p_row) and lane = row - 1 (u, rowin)
+      // C. assignment (motassign.h): lane = column - 1 (v, minv, way, used, p_row) and lane = row - 1 (u, rowin)
       const int N = n > m ? n : m;
       const int hid = lane < m ? s_hid[lane] : -1;
-      int p_row = 0;
-      double u = 0.0, v = 0.0;
-      if (n > 0 && m > 0) {
-        for (int i = 1; i <= N; ++i) {
-          double minv = INF;
-          int way = 0, j0 = 0;
-          bool used = false, rowin = false, found = false;
-          for (int it = 0; it <= N; ++it) {                 // a step marks one more column used: N steps at most
-            if (lane == j0 - 1) used = true;
-            const int i0 = j0 == 0 ? i : lane_i(p_row, j0 - 1);
-            if (lane == i0 - 1) rowin = true;
-            const double ui0 = lane_d(u, i0 - 1);
-            const bool open = lane < N && !used;
-            if (open) {
-              const double sc = (i0 - 1 < n && lane < m) ? mot_score(s_sim[(i0 - 1) * MR + lane], thr, s_prev[i0 - 1], hid) : 0.0;
-              const double cur = mot_reduced(sc, ui0, v);
-              if (cur < minv) minv = cur, way = j0;
-            }
-            const double bv = open ? minv : INF;
-            const double mn = wave_min(bv);
-            if (!(mn < INF)) break;                         // no open column: cannot happen with finite scores
-            const int bl = __ffsll((long long)__ballot(bv == mn)) - 1;   // the lowest lane that holds the minimum
-            if (bl < 0) break;
-            const double delta = lane_d(bv, bl);
-            if (rowin) u += delta;
-            if (used) v -= delta;
-            else minv -= delta;
-            j0 = bl + 1;
-            if (lane_i(p_row, bl) == 0) {
-              found = true;
-              break;
-            }
-          }
-          if (!found) break;
-          for (int it = 0; it <= N && j0 != 0; ++it) {      // augment along way
-            const int j1 = lane_i(way, j0 - 1);
-            const int pn = j1 == 0 ? i : lane_i(p_row, j1 - 1);
-            if (lane == j0 - 1) p_row = pn;
-            j0 = j1;
-          }
-        }
-      }
+      const int p_row = wave_assign(n, m, lane, [&](int i0, double ui0, double v) {
+        const double sc = (i0 < n && lane < m) ? mot_score(s_sim[i0 * MR + lane], thr, s_prev[i0], hid) : 0.0;
+        return mot_reduced(sc, ui0, v);
+      });
       // D. lane = ground-truth row
-      int col = -1;
-      for (int c = 0; c < N; ++c) {
-        const int pr = lane_i(p_row, c);
-        if (pr == lane + 1) col = c;
-      }
+      const int col = wave_column_of_row(p_row, N, lane);
       bool matched = false, sw = false;
       double sv = 0.0;
       int h = -1;
@@ -323,12 +230,11 @@ void emulate_seq(const MotArgs& p, int s) {
   const long tg = p.n_gt_ids;
   int* st = p.state + q.id0;
   int* pot = p.pot + q.pot0;
-  const double INF = __builtin_huge_val();
   long TP = 0, FN = 0, FP = 0, IDSW = 0;
   double acc = 0.0;
-  std::vector<double> sim(MR * MR), u(MR + 1), v(MR + 1), minv(MR + 1);
-  std::vector<int> prow(MR + 1), way(MR + 1), gid(MR), hid(MR), prev(MR);
-  std::vector<char> used(MR + 1);
+  std::vector<double> sim(MR * MR);
+  std::vector<int> gid(MR), hid(MR), prev(MR);
+  HostAssign as;
   for (long gf = q.f0; gf < q.f1; ++gf) {
     const int f = (int)(gf - q.f0);
     const MotFrame fr = mot_frame(p, gf, G, H);
@@ -345,41 +251,10 @@ void emulate_seq(const MotArgs& p, int s) {
         if (sv >= p.thr) pot[(long)gid[i] * H + hid[j]] += 1;
       }
     auto score = [&](int i, int j) { return (i < n && j < m) ? mot_score(sim[i * MR + j], p.thr, prev[i], hid[j]) : 0.0; };
-    for (int j = 0; j <= N; ++j) u[j] = v[j] = 0.0, prow[j] = 0, way[j] = 0;
-    if (n > 0 && m > 0) {
-      for (int i = 1; i <= N; ++i) {
-        prow[0] = i;
-        int j0 = 0;
-        for (int j = 0; j <= N; ++j) minv[j] = INF, used[j] = 0;
-        do {
-          used[j0] = 1;
-          const int i0 = prow[j0];
-          double delta = INF;
-          int j1 = 0;
-          for (int j = 1; j <= N; ++j) {
-            if (used[j]) continue;
-            const double cur = mot_reduced(score(i0 - 1, j - 1), u[i0], v[j]);
-            if (cur < minv[j]) minv[j] = cur, way[j] = j0;
-            if (minv[j] < delta) delta = minv[j], j1 = j;
-          }
-          for (int j = 0; j <= N; ++j) {
-            if (used[j]) u[prow[j]] += delta, v[j] -= delta;
-            else minv[j] -= delta;
-          }
-          j0 = j1;                                          // 0: no open column, cannot happen with finite scores
-        } while (j0 != 0 && prow[j0] != 0);
-        do {
-          const int j1 = way[j0];
-          prow[j0] = prow[j1];
-          j0 = j1;
-        } while (j0);
-      }
-    }
+    host_assign(n, m, score, as);
     int k = 0;
     for (int i = 0; i < n; ++i) {
-      int col = -1;
-      for (int j = 1; j <= N; ++j)
-        if (prow[j] == i + 1) col = j - 1;
+      const int col = host_column_of_row(as, N, i);
       const bool matched = col >= 0 && col < m && score(i, col) > 0.0;
       int* e = st + gid[i];
       bool sw = false;

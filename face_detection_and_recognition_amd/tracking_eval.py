@@ -15,6 +15,10 @@ All three give the same integers, the same per-row outputs and a bit-equal sum_i
 the host (_idtp).  A single long sequence is a chain of dependent frames on one workgroup and is latency-bound; many
 sequences fill the device the way many streams fill fp_tracklets_step.
 
+hota_eval scores the same rows with HOTA (DetA, AssA, LocA over a family of localisation thresholds; DESIGN.md section 7
+"Tracker evaluation: HOTA"): the same three paths, fp_hota_match (csrc/hota.hip) on the device, everything per threshold
+derived on the host.
+
 Thresholds and max_age of tracking.py remain unmeasured on real video until somebody runs this on labelled footage.
 """
 import numpy as np
@@ -404,6 +408,264 @@ def mot_eval_emulate(*args, **kw) -> MotResult:
     return mot_eval(*args, device="cpu", _path="emulate", **kw)
 
 
+# ---- HOTA ----------------------------------------------------------------------------------------------------------------
+# DESIGN section 7 "Tracker evaluation: HOTA" and include/facepath.h are the specification.  The same three paths as above:
+# numpy, fp_hota_match (csrc/hota.hip) and fp_hota_match_emulate give the same integers and the same bits of gt_sim and gas;
+# everything per alpha is derived here, on the host, from their per-row outputs.
+
+MAX_ALPHAS = L.HOTA_MAX_ALPHAS
+DEFAULT_ALPHAS = np.arange(1, 20) / 20.0                 # 0.05 .. 0.95, computed once: every path compares against these bits
+HOTA_INT_KEYS = ("TP", "FN", "FP")
+HOTA_SUM_KEYS = ("loc_sum", "ass_num", "re_num", "pr_num")
+HOTA_KEYS = ("HOTA", "DetA", "AssA", "DetRe", "DetPr", "AssRe", "AssPr", "LocA")
+
+
+def _alphas(alphas):
+    a = DEFAULT_ALPHAS.copy() if alphas is None else np.array(alphas, dtype=np.float64).reshape(-1)
+    if alphas is not None and np.ndim(alphas) != 1:
+        raise ValueError("alphas: expected a one-dimensional array")
+    if not 1 <= a.shape[0] <= MAX_ALPHAS:
+        raise ValueError(f"alphas: expected 1 .. {MAX_ALPHAS} values, got {a.shape[0]}")
+    if not bool(np.all((a > 0.0) & (a <= 1.0))):
+        raise ValueError("alphas: every value must lie in (0, 1]")
+    if not bool(np.all(a[1:] > a[:-1])):
+        raise ValueError("alphas: not strictly ascending")
+    return np.ascontiguousarray(a)
+
+
+def _seq_sum(x):
+    """The sum of x in ascending index order, one fp64 addition each (np.sum adds pairwise)."""
+    x = np.asarray(x, np.float64)
+    return float(np.add.accumulate(x)[-1]) if x.shape[0] else 0.0
+
+
+class _HotaProblem(_Problem):
+    """_Problem with the localisation thresholds in place of thr, and the raw outputs of the HOTA paths: gt_match (sorted
+    hypothesis row) and gt_sim in sorted ground-truth order, levels (S, A + 1) int64, counts (S, 2) int64 = n_gt, n_hy; the
+    workspace = gas (sum G_s * H_s) fp64, then gtc (sum G_s) and hyc (sum H_s) int32."""
+
+    def __init__(self, gt_seq, gt_frame, gt_id, gt_boxes, hy_seq, hy_frame, hy_id, hy_boxes, n_frames, alphas, dev):
+        self.alphas = _alphas(alphas)
+        super().__init__(gt_seq, gt_frame, gt_id, gt_boxes, hy_seq, hy_frame, hy_id, hy_boxes, n_frames, 0.0, dev)
+        self.A = int(self.alphas.shape[0])
+        self.n_hy_ids = int(self.hy.id_base[-1])
+        self.hy_id_base32 = self.hy.id_base.to(torch.int32)
+        self.ws_ints = max(2 * self.n_pot + self.n_gt_ids + self.n_hy_ids, 2)
+
+    def outputs(self, dev):
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)   # noqa: E731
+        return dict(gt_match=z((self.Ng,), torch.int32), gt_sim=z((self.Ng,), torch.float64),
+                    levels=z((self.S, self.A + 1), torch.int64), counts=z((self.S, 2), torch.int64), ws=z((self.ws_ints,), torch.int32))
+
+    def call_args(self, out):
+        gt, hy = self.gt, self.hy
+        return ([L.ptr(gt.boxes), L.ptr(gt.dense), L.ptr(gt.off), self.Ng, L.ptr(hy.boxes), L.ptr(hy.dense), L.ptr(hy.off), self.Nh,
+                 L.ptr(self.frame_base32), L.ptr(self.gt_id_base32), L.ptr(self.hy_id_base32), L.ptr(self.pot_base), self.S,
+                 self.total, self.n_gt_ids, self.n_hy_ids, self.n_pot, self.alphas.ctypes.data, self.A] +
+                [L.ptr(out[k]) for k in ("gt_match", "gt_sim", "levels", "counts", "ws")] + [self.ws_ints * 4])
+
+    def raw(self, out):
+        ws = out["ws"].cpu().numpy()
+        k = 2 * self.n_pot
+        return dict(gt_match=out["gt_match"].cpu().numpy(), gt_sim=out["gt_sim"].cpu().numpy(), levels=out["levels"].cpu().numpy(),
+                    counts=out["counts"].cpu().numpy(), gas=ws[:k].view(np.float64).copy(),
+                    gtc=ws[k:k + self.n_gt_ids].copy(), hyc=ws[k + self.n_gt_ids:k + self.n_gt_ids + self.n_hy_ids].copy())
+
+
+def _hota_device(pb):
+    """One launch on the current stream of pb.dev; nothing is read back here."""
+    out = pb.outputs(pb.dev)
+    L.check(L.load().fp_hota_match(*pb.call_args(out), L.current_stream(pb.dev)), "fp_hota_match")
+    return out
+
+
+def _hota_emulate(pb):
+    out = pb.outputs(torch.device("cpu"))
+    L.check(L.load().fp_hota_match_emulate(*pb.call_args(out)), "fp_hota_match_emulate")
+    return out
+
+
+def _hota_numpy(pb):
+    """The procedure of DESIGN section 7 "Tracker evaluation: HOTA": the alignment march, the sweep, the matching march."""
+    gt, hy = pb.gt, pb.hy
+    gb, gd, goff = gt.boxes.numpy(), gt.dense.numpy(), gt.off.numpy()
+    hb, hd, hoff = hy.boxes.numpy(), hy.dense.numpy(), hy.off.numpy()
+    base, gidb, hidb, potb = pb.base.numpy(), gt.id_base.numpy(), hy.id_base.numpy(), pb.pot_base.numpy()
+    gt_match, gt_sim = -np.ones(pb.Ng, np.int32), np.zeros(pb.Ng)
+    levels, counts = np.zeros((pb.S, pb.A + 1), np.int64), np.zeros((pb.S, 2), np.int64)
+    gas_all, gtc_all, hyc_all = np.zeros(pb.n_pot), np.zeros(pb.n_gt_ids, np.int32), np.zeros(pb.n_hy_ids, np.int32)
+    for s in range(pb.S):
+        G, H = int(gidb[s + 1] - gidb[s]), int(hidb[s + 1] - hidb[s])
+        gtc, hyc = gtc_all[gidb[s]:gidb[s + 1]], hyc_all[hidb[s]:hidb[s + 1]]
+        pmc = np.zeros((G, H))
+        frames = []
+        for gf in range(base[s], base[s + 1]):
+            g0, g1, h0, h1 = goff[gf], goff[gf + 1], hoff[gf], hoff[gf + 1]
+            g, h = gd[g0:g1].astype(np.int64), hd[h0:h1].astype(np.int64)
+            sim = _iou_matrix(gb[g0:g1], hb[h0:h1]) if len(g) and len(h) else np.zeros((len(g), len(h)))
+            frames.append((g0, h0, g, h, sim))
+            gtc[g] += 1
+            hyc[h] += 1
+            if sim.size:
+                row = np.add.accumulate(sim, axis=1)[:, -1]           # ascending j, one addition each
+                col = np.add.accumulate(sim, axis=0)[-1, :]           # ascending i
+                den = (row[:, None] + col[None, :]) - sim
+                pos = sim > 0.0
+                pmc[np.ix_(g, h)] += np.divide(sim, den, out=np.zeros_like(sim), where=pos)
+        pos = pmc > 0.0
+        gas = np.divide(pmc, (gtc[:, None].astype(np.float64) + hyc[None, :].astype(np.float64)) - pmc, out=np.zeros_like(pmc),
+                        where=pos)
+        gas_all[potb[s]:potb[s + 1]] = gas.reshape(-1)
+        for g0, h0, g, h, sim in frames:
+            counts[s] += (len(g), len(h))
+            if not sim.size:
+                continue
+            score = gas[np.ix_(g, h)] * sim
+            col = assign_max(score)
+            for i in range(len(g)):
+                j = col[i]
+                if j < 0 or not score[i, j] > 0:
+                    continue
+                gt_match[g0 + i], gt_sim[g0 + i] = h0 + j, sim[i, j]
+                levels[s, int(np.count_nonzero(sim[i, j] >= pb.alphas))] += 1
+    return dict(gt_match=gt_match, gt_sim=gt_sim, levels=levels, counts=counts, gas=gas_all, gtc=gtc_all, hyc=hyc_all)
+
+
+def _mean(x):
+    return _seq_sum(x) / len(x) if len(x) else -1.0
+
+
+def derive_hota(c):
+    """The per-alpha arrays and headline means of a dict of TP / FN / FP (int64 arrays) and loc_sum / ass_num / re_num / pr_num
+    (fp64 arrays).  -1 where a Det* denominator is 0 (HOTA too); AssA = AssRe = AssPr = 0 and LocA = -1 where TP is 0 (TrackEval
+    reports 1 there).  The headline numbers are the means over the alphas, LocA over the alphas with TP > 0 (-1 without one)."""
+    TP, FN, FP = (c[k].astype(np.float64) for k in HOTA_INT_KEYS)
+    some = TP > 0
+
+    def ratio(num, den, empty):
+        return np.divide(num, den, out=np.full(TP.shape, float(empty)), where=den > 0)
+    pa = dict(DetA=ratio(TP, TP + FN + FP, -1), DetRe=ratio(TP, TP + FN, -1), DetPr=ratio(TP, TP + FP, -1),
+              AssA=ratio(c["ass_num"], TP, 0), AssRe=ratio(c["re_num"], TP, 0), AssPr=ratio(c["pr_num"], TP, 0),
+              LocA=ratio(c["loc_sum"], TP, -1))
+    pa["HOTA"] = np.where(pa["DetA"] >= 0, np.sqrt(np.maximum(pa["DetA"], 0.0) * pa["AssA"]), -1.0)
+    out = {k: _mean(pa[k]) for k in HOTA_KEYS if k != "LocA"}
+    out["LocA"] = _mean(pa["LocA"][some]) if some.any() else -1.0
+    out["per_alpha"] = pa
+    return out
+
+
+class HotaResult:
+    """alphas (A,) fp64.  sequences: one dict per sequence with TP / FN / FP (A,) int64, loc_sum / ass_num / re_num / pr_num
+    (A,) fp64, n_gt / n_hy, levels (A + 1,) int64, the headline means (HOTA_KEYS) and per_alpha: the same names as (A,) fp64
+    arrays; combined: the same keys from the integers and numerators summed in sequence order, then derived (so AssA combines
+    TP-weighted, as TrackEval's combined row).  gt_match (Ng,) int32: the caller's index of the hypothesis row matched to every
+    ground-truth row, -1 without one; gt_sim (Ng,) fp64: the IoU of that pair, 0 without one; levels (S, A + 1) int64: matched
+    pairs by the number of alphas their IoU reaches.  gas: per sequence the (G_s, H_s) fp64 global alignment scores, gtc / hyc
+    the frames every id occurs in, rows / columns in ascending order of the caller's ids (gt_ids[s], hy_ids[s]).  Attribute
+    access reaches the combined headline numbers: res.HOTA, res.DetA, ..."""
+
+    def __init__(self, alphas, sequences, combined, gt_match, gt_sim, levels, gas, gtc, hyc, gt_ids, hy_ids):
+        self.alphas, self.sequences, self.combined = alphas, sequences, combined
+        self.gt_match, self.gt_sim, self.levels, self.gas, self.gtc, self.hyc = gt_match, gt_sim, levels, gas, gtc, hyc
+        self.gt_ids, self.hy_ids = gt_ids, hy_ids
+
+    def __getattr__(self, name):
+        combined = self.__dict__.get("combined")
+        if combined is not None and name in combined:
+            return combined[name]
+        raise AttributeError(name)
+
+    def columns(self):
+        """The header and one string per sequence and for the combined row: HOTA_KEYS in summary()'s column format."""
+        return ["".join(f"{c:>10}" for c in HOTA_KEYS)] + ["".join(f" {row[c]:9.4f}" for c in HOTA_KEYS)
+                                                           for row in self.sequences + [self.combined]]
+
+    def summary(self, names=None):
+        """A header, one line per sequence and the combined line."""
+        cols = self.columns()
+        lines = [f"{'sequence':<16}" + cols[0]]
+        for k in range(len(self.sequences) + 1):
+            name = "COMBINED" if k == len(self.sequences) else (str(names[k]) if names is not None else f"seq{k}")
+            lines.append(f"{name:<16}" + cols[k + 1])
+        return "\n".join(lines)
+
+
+def _hota_finish(pb, raw):
+    gt, hy = pb.gt, pb.hy
+    A, alphas = pb.A, pb.alphas
+    gorder, horder = gt.order.cpu().numpy(), hy.order.cpu().numpy()
+    gm = raw["gt_match"].astype(np.int64)
+    gt_match, gt_sim = -np.ones(pb.Ng, np.int32), np.zeros(pb.Ng)
+    if pb.Ng:
+        gt_match[gorder] = np.where(gm >= 0, horder[np.clip(gm, 0, max(pb.Nh - 1, 0))] if pb.Nh else -1, -1)
+        gt_sim[gorder] = raw["gt_sim"]
+    gidb, hidb, potb = gt.id_base.cpu().numpy(), hy.id_base.cpu().numpy(), pb.pot_base.cpu().numpy()
+    gids, hids = gt.ids.cpu().numpy(), hy.ids.cpu().numpy()
+    gdense, hdense = gt.dense.cpu().numpy().astype(np.int64), hy.dense.cpu().numpy().astype(np.int64)
+    goff, base = gt.off.cpu().numpy(), pb.base.cpu().numpy()
+    sequences, gas_list, gtc_list, hyc_list, gt_ids, hy_ids = [], [], [], [], [], []
+    for s in range(pb.S):
+        G, H = int(gidb[s + 1] - gidb[s]), int(hidb[s + 1] - hidb[s])
+        gtc, hyc = raw["gtc"][gidb[s]:gidb[s + 1]].astype(np.int64), raw["hyc"][hidb[s]:hidb[s + 1]].astype(np.int64)
+        r0, r1 = int(goff[base[s]]), int(goff[base[s + 1]])               # the sequence's rows in sorted order
+        rows = np.arange(r0, r1)[gm[r0:r1] >= 0]
+        rows = rows[np.argsort(gorder[rows], kind="stable")]              # ascending caller row order
+        sim = raw["gt_sim"][rows]
+        key = gdense[rows] * H + hdense[np.clip(gm[rows], 0, max(pb.Nh - 1, 0))] if len(rows) else np.zeros(0, np.int64)
+        n_gt, n_hy = (int(v) for v in raw["counts"][s])
+        c = dict(TP=np.zeros(A, np.int64), loc_sum=np.zeros(A), ass_num=np.zeros(A), re_num=np.zeros(A), pr_num=np.zeros(A),
+                 n_gt=n_gt, n_hy=n_hy, levels=raw["levels"][s].astype(np.int64), n_gt_ids=G, n_hy_ids=H)
+        for a in range(A):
+            sel = sim >= alphas[a]
+            c["TP"][a] = int(sel.sum())
+            c["loc_sum"][a] = _seq_sum(sim[sel])
+            pair, mc = np.unique(key[sel], return_counts=True)            # the id pairs that occur, ascending (g, h)
+            g, h = pair // max(H, 1), pair % max(H, 1)
+            mcf = mc.astype(np.float64)
+            c["ass_num"][a] = _seq_sum(mcf * (mcf / np.maximum(1, gtc[g] + hyc[h] - mc)))
+            c["re_num"][a] = _seq_sum(mcf * (mcf / np.maximum(1, gtc[g])))
+            c["pr_num"][a] = _seq_sum(mcf * (mcf / np.maximum(1, hyc[h])))
+        c["FN"], c["FP"] = n_gt - c["TP"], n_hy - c["TP"]
+        sequences.append(c)
+        gas_list.append(raw["gas"][potb[s]:potb[s + 1]].reshape(G, H))
+        gtc_list.append(gtc)
+        hyc_list.append(hyc)
+        gt_ids.append(gids[gidb[s]:gidb[s + 1]])
+        hy_ids.append(hids[hidb[s]:hidb[s + 1]])
+    combined = {k: np.zeros(A, np.int64) for k in HOTA_INT_KEYS}
+    combined.update({k: np.zeros(A) for k in HOTA_SUM_KEYS})
+    combined.update(n_gt=0, n_hy=0, levels=np.zeros(A + 1, np.int64), n_gt_ids=0, n_hy_ids=0)
+    for c in sequences:                                                   # sequence order
+        for k in HOTA_INT_KEYS + HOTA_SUM_KEYS + ("n_gt", "n_hy", "levels", "n_gt_ids", "n_hy_ids"):
+            combined[k] = combined[k] + c[k]
+    for c in sequences + [combined]:
+        c.update(derive_hota(c))
+    return HotaResult(alphas, sequences, combined, gt_match, gt_sim, raw["levels"].astype(np.int64), gas_list, gtc_list, hyc_list,
+                      gt_ids, hy_ids)
+
+
+_HOTA_PATHS = {"numpy": _hota_numpy, "emulate": lambda pb: pb.raw(_hota_emulate(pb))}
+
+
+def hota_eval(gt_seq, gt_frame, gt_id, gt_boxes, hy_seq, hy_frame, hy_id, hy_boxes, n_frames, *, alphas=None, device=None,
+              _path=None) -> HotaResult:
+    """HOTA (DetA, AssA, LocA and their recalls / precisions) of hypothesis rows against ground-truth rows: the arguments and
+    ValueErrors of mot_eval, with alphas -- strictly ascending localisation thresholds inside (0, 1], at most 32, default
+    0.05 .. 0.95 -- in place of thr.  device None / "cpu": the numpy path; a HIP device: the kernel."""
+    dev = torch.device("cpu" if device is None else device)
+    if dev.type == "cpu":
+        pb = _HotaProblem(gt_seq, gt_frame, gt_id, gt_boxes, hy_seq, hy_frame, hy_id, hy_boxes, n_frames, alphas, dev)
+        return _hota_finish(pb, _HOTA_PATHS[_path or "numpy"](pb))
+    with torch.cuda.device(dev):
+        pb = _HotaProblem(gt_seq, gt_frame, gt_id, gt_boxes, hy_seq, hy_frame, hy_id, hy_boxes, n_frames, alphas, dev)
+        return _hota_finish(pb, pb.raw(_hota_device(pb)))
+
+
+def hota_eval_emulate(*args, **kw) -> HotaResult:
+    """hota_eval through fp_hota_match_emulate: the kernel's decision code on host memory (no GPU needed)."""
+    return hota_eval(*args, device="cpu", _path="emulate", **kw)
+
+
 class TrackingEvaluator:
     """Collects a tracker's rows step by step on the device (add() never synchronises with the host) and scores them against
     the ground truth given to set_ground_truth()."""
@@ -475,6 +737,13 @@ class TrackingEvaluator:
             raise ValueError("evaluate(): no ground truth; call set_ground_truth() first")
         gt_seq, gt_frame, gt_id, gt_boxes, n_frames = self._gt
         return mot_eval(gt_seq, gt_frame, gt_id, gt_boxes, *self.rows(), n_frames, thr=self.thr, device=self.device)
+
+    def evaluate_hota(self, alphas=None) -> HotaResult:
+        """hota_eval on the rows collected so far; evaluate() and its thr are not involved."""
+        if self._gt is None:
+            raise ValueError("evaluate_hota(): no ground truth; call set_ground_truth() first")
+        gt_seq, gt_frame, gt_id, gt_boxes, n_frames = self._gt
+        return hota_eval(gt_seq, gt_frame, gt_id, gt_boxes, *self.rows(), n_frames, alphas=alphas, device=self.device)
 
 
 # ---- MOTChallenge text rows ----------------------------------------------------------------------------------------------

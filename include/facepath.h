@@ -1545,7 +1545,7 @@ int fp_tracklets_step_motion_emulate(const fp_track_state* state, int n_streams,
  * IDFN = rows of ground truth - IDTP, IDFP = hypothesis rows - IDTP, IDF1 = IDTP / (IDTP + (IDFN + IDFP) / 2).  The combined
  * result sums the integers and sum_iou in sequence order, then derives.  -1 where a denominator is 0.
  * Known departures: parity with TrackEval / py-motmetrics is unpinned; every frame is processed (step 6 always runs, so a
- * target missed in a frame without any hypothesis starts a new run); admissibility is sim >= thr without an epsilon; no HOTA.
+ * target missed in a frame without any hypothesis starts a new run); admissibility is sim >= thr without an epsilon.  HOTA: below.
  *
  * fp_mot_match: one launch, one workgroup per sequence marching its frames; no global atomics, no scratch, no host
  * synchronisation; two runs are bit-identical.  A single long sequence is a chain of dependent frames: latency-bound.
@@ -1574,6 +1574,62 @@ int fp_mot_match_emulate(const double* gt_boxes, const int32_t* gt_id, const int
                          const int64_t* pot_base, int n_seqs, int64_t n_frames, int64_t n_gt_ids, int64_t n_pot, double thr,
                          int64_t* counts, double* sum_iou, int32_t* gt_match, uint8_t* gt_switch, void* workspace,
                          size_t ws_bytes);
+
+/*
+ * Tracker evaluation: HOTA (DetA, AssA, LocA; build-defined restatement of Luiten et al. 2020 as TrackEval computes it; DESIGN §7
+ * "Tracker evaluation: HOTA"; csrc/hota.hip; tracking_eval.py holds the numpy restatement and the host half).  Parity with
+ * TrackEval is unpinned: it is not installed.  All additive: ABI 15.
+ *
+ * Inputs.  Those of fp_mot_match (rows, n_frames, dense ids, at most FP_MOT_MAX_ROWS rows per side and frame, an id at most once
+ * per frame) without thr; in its place alphas: fp64, strictly ascending, every value in (0, 1], 1 .. FP_HOTA_MAX_ALPHAS = 32 of
+ * them (default in Python: numpy.arange(1, 20) / 20.0, passed as data).
+ * Pass 1, alignment, frames ascending, every frame, with n ground-truth and m hypothesis rows:
+ *   1. sim[i][j] = the fp64 IoU of fp_mot_match, the same operations and order.
+ *   2. row[i] = sum of sim[i][0 .. m-1] in ascending j, one fp64 addition each, from 0.0; col[j] the same over ascending i.
+ *   3. den = (row[i] + col[j]) - sim[i][j]; soft[i][j] = sim[i][j] > 0 ? sim[i][j] / den : 0.
+ *   4. pmc[g_i][h_j] += soft[i][j] (one fp64 addition per pair and frame).   5. gtc[g_i] += 1, hyc[h_j] += 1.
+ * After the last frame: gas[g][h] = pmc > 0 ? pmc / ((double(gtc[g]) + double(hyc[h])) - pmc) : 0.
+ * Pass 2, matching, frames ascending again:
+ *   1. score[i][j] = gas[g_i][h_j] * sim[i][j], one multiplication.
+ *   2. The assignment of fp_mot_match (step 4 there) on C = -score padded with zeros to N x N; matched pairs are the assigned
+ *      (i, j) with i < n, j < m, score > 0.
+ *   3. Per ground-truth row: gt_match = the index of the matched hypothesis row (in the order given to the call) or -1; gt_sim =
+ *      sim[i][j] of that pair or 0.0.
+ *   4. Per sequence: levels[t] += 1 for each matched pair, t = the number of alphas with gt_sim >= alpha (no epsilon);
+ *      n_gt += n, n_hy += m.
+ * Derived on the host in fp64 per alpha a (tracking_eval.py): a pair counts iff gt_sim >= alphas[a]; TP = their number (= sum of
+ * levels[t] over t > a), FN = n_gt - TP, FP = n_hy - TP, loc_sum = the sum of their gt_sim in ascending caller row order;
+ * mc[(g, h)] = pairs per id pair (sparse); ass = mc / max(1, gtc[g] + hyc[h] - mc); ass_num / re_num / pr_num = the sums over id
+ * pairs in ascending (g, h) of mc * ass, mc * mc / max(1, gtc[g]), mc * mc / max(1, hyc[h]); DetA = TP / (TP + FN + FP), DetRe,
+ * DetPr, AssA = ass_num / TP, AssRe, AssPr, LocA = loc_sum / TP, HOTA = sqrt(DetA * AssA); headline numbers = means over the
+ * alphas, LocA over the alphas with TP > 0.  The combined row sums TP, FN, FP and the numerators in sequence order, then derives.
+ * Known departures: where TP == 0, AssA = AssRe = AssPr = 0 and LocA = -1 (TrackEval reports 1); -1 where a Det* denominator is 0.
+ *
+ * fp_hota_match: ONE launch, one workgroup of 256 threads per sequence: pass 1, the sweep pmc -> gas and pass 2, ordered by
+ * workgroup barriers and fences; no global atomics, no scratch, no host synchronisation; two runs are byte-identical.  The row
+ * arrays, CSR offsets, frame_base, gt_id_base and pot_base are those of fp_mot_match; hy_id_base [n_seqs + 1] int32 = prefix
+ * sums of H_s, n_hy_ids its last entry.  alphas [n_alphas] is HOST memory (validated here, copied into the kernel arguments).
+ * Outputs (device): gt_match [n_gt] int32, gt_sim [n_gt] fp64, levels [n_seqs][n_alphas + 1] int64, counts [n_seqs][2] int64 =
+ * n_gt, n_hy.  workspace (fp_hota_match_workspace(n_gt_ids, n_hy_ids, n_pot) bytes, 8-byte aligned, zeroed here) is an output
+ * too: gas, n_pot fp64, and behind it gtc [n_gt_ids] and hyc [n_hy_ids] int32.  Indices read from device memory are clamped
+ * into the arrays.  Refusals as fp_mot_match, and FP_ERR_INVALID_ARG for alphas that are NULL, fewer than 1, more than 32, not
+ * strictly ascending or outside (0, 1].
+ * fp_hota_match_emulate: the same decision code serially on HOST memory (every pointer HOST), the same bits.
+ */
+#define FP_HOTA_MAX_ALPHAS 32
+size_t fp_hota_match_workspace(int64_t n_gt_ids, int64_t n_hy_ids, int64_t n_pot);
+int fp_hota_match(const double* gt_boxes, const int32_t* gt_id, const int32_t* gt_off, int64_t n_gt, const double* hy_boxes,
+                  const int32_t* hy_id, const int32_t* hy_off, int64_t n_hy, const int32_t* frame_base,
+                  const int32_t* gt_id_base, const int32_t* hy_id_base, const int64_t* pot_base, int n_seqs, int64_t n_frames,
+                  int64_t n_gt_ids, int64_t n_hy_ids, int64_t n_pot, const double* alphas /* HOST */, int n_alphas,
+                  int32_t* gt_match, double* gt_sim, int64_t* levels, int64_t* counts, void* workspace, size_t ws_bytes,
+                  void* stream);
+int fp_hota_match_emulate(const double* gt_boxes, const int32_t* gt_id, const int32_t* gt_off, int64_t n_gt,
+                          const double* hy_boxes, const int32_t* hy_id, const int32_t* hy_off, int64_t n_hy,
+                          const int32_t* frame_base, const int32_t* gt_id_base, const int32_t* hy_id_base,
+                          const int64_t* pot_base, int n_seqs, int64_t n_frames, int64_t n_gt_ids, int64_t n_hy_ids,
+                          int64_t n_pot, const double* alphas, int n_alphas, int32_t* gt_match, double* gt_sim, int64_t* levels,
+                          int64_t* counts, void* workspace, size_t ws_bytes);
 
 #ifdef __cplusplus
 }

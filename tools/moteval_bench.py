@@ -10,8 +10,13 @@ asserts that the device's integers, per-row outputs and the bits of sum_iou equa
 project's own numpy restatement, not against TrackEval or py-motmetrics, which are not installed and which nobody here has
 timed.  Prints one JSON line.
 
+`--hota` times tracking_eval.hota_eval next to it on the same rows in the same process: the fp_hota_match launch alternates with
+the fp_mot_match launch round by round (`hota.launch`, `hota.launch_over_mot_launch`), the read-back and the host derivation
+of the per-alpha numbers go by wall clock, and the numpy path runs once and must give the same integers and the same bits of
+gt_sim, gas and the numerators.
+
   python tools/moteval_bench.py [--seqs 256] [--frames 64] [--targets 8] [--long-frames 8192] [--rounds 5] [--round-s 0.25]
-                                [--no-numpy]"""
+                                [--no-numpy] [--hota]"""
 import argparse
 import json
 import math
@@ -83,7 +88,18 @@ def same(a, b):
     return ints, per_row, bits
 
 
-def run_layout(data, dev, rounds, round_s, with_numpy):
+def same_hota(a, b):
+    """Device HotaResult a against numpy's b: (integers equal, per-row outputs equal, fp64 bits equal)."""
+    rows = list(zip(a.sequences + [a.combined], b.sequences + [b.combined]))
+    ints = all(np.array_equal(x[k], y[k]) for x, y in rows for k in TE.HOTA_INT_KEYS + ("levels", "n_gt", "n_hy"))
+    per_row = bool(np.array_equal(a.gt_match, b.gt_match) and np.array_equal(a.levels, b.levels)
+                   and all(np.array_equal(p, q) for p, q in zip(a.gtc + a.hyc, b.gtc + b.hyc)))
+    bits = bool(a.gt_sim.tobytes() == b.gt_sim.tobytes() and all(p.tobytes() == q.tobytes() for p, q in zip(a.gas, b.gas))
+                and all(x[k].tobytes() == y[k].tobytes() for x, y in rows for k in TE.HOTA_SUM_KEYS))
+    return ints, per_row, bits
+
+
+def run_layout(data, dev, rounds, round_s, with_numpy, hota=False):
     keys = ("gt_seq", "gt_frame", "gt_id", "gt_boxes", "hy_seq", "hy_frame", "hy_id", "hy_boxes", "n_frames")
     t = [torch.from_numpy(np.ascontiguousarray(data[k])).to(dev) for k in keys]
     state = {}
@@ -94,6 +110,10 @@ def run_layout(data, dev, rounds, round_s, with_numpy):
     def launch():
         state["out"] = TE._match_device(state["pb"])
     variants = {"plumbing": plumbing, "launch": launch}
+    if hota:
+        state["hpb"] = TE._HotaProblem(*t, None, dev)
+        variants["hota_launch"] = lambda: state.update(hout=TE._hota_device(state["hpb"]))
+        variants["hota_launch"]()
     plumbing()
     launch()
     torch.cuda.synchronize()
@@ -108,9 +128,12 @@ def run_layout(data, dev, rounds, round_s, with_numpy):
     frames, longest = int(pb.total), int(pb.n_frames.max()) if pb.S else 0
     out = dict(sequences=pb.S, frames=frames, frames_longest=longest, gt_rows=pb.Ng, hy_rows=pb.Nh, gt_ids=pb.n_gt_ids,
                pot_cells=pb.n_pot)
+    summary = {}
     for name, v in times.items():
-        out[name] = dict(ms=round(float(np.median(v)), 4), min_ms=round(min(v), 4), max_ms=round(max(v), 4),
-                         calls_per_round=reps[name])
+        summary[name] = dict(ms=round(float(np.median(v)), 4), min_ms=round(min(v), 4), max_ms=round(max(v), 4),
+                             calls_per_round=reps[name])
+    hota_launch = summary.pop("hota_launch", None)
+    out.update(summary)
     out["launch_us_per_frame_of_longest"] = round(out["launch"]["ms"] * 1e3 / max(longest, 1), 3)
     out["launch_us_per_frame_overall"] = round(out["launch"]["ms"] * 1e3 / max(frames, 1), 4)
     t0 = time.perf_counter()
@@ -129,6 +152,26 @@ def run_layout(data, dev, rounds, round_s, with_numpy):
         out["numpy_over_device_total"] = round(out["numpy_once_s"] * 1e3 / device_total, 1)
         out["integers_equal"], out["rows_equal"], out["sum_iou_bit_equal"] = same(res, ref)
         assert out["integers_equal"] and out["rows_equal"] and out["sum_iou_bit_equal"], out
+    if hota:
+        hpb, h = state["hpb"], dict(launch=hota_launch)
+        h["launch_over_mot_launch"] = round(hota_launch["ms"] / out["launch"]["ms"], 3)
+        h["launch_us_per_frame_of_longest"] = round(hota_launch["ms"] * 1e3 / max(longest, 1), 3)
+        t0 = time.perf_counter()
+        raw = hpb.raw(state["hout"])
+        t1 = time.perf_counter()
+        hres = TE._hota_finish(hpb, raw)
+        h["readback_ms"] = round((t1 - t0) * 1e3, 3)
+        h["host_derivation_ms"] = round((time.perf_counter() - t1) * 1e3, 3)
+        h["alphas"] = int(hpb.A)
+        for key in TE.HOTA_KEYS:
+            h[key] = round(hres.combined[key], 6)
+        if with_numpy:
+            t0 = time.perf_counter()
+            href = TE.hota_eval(*(data[k] for k in keys))
+            h["numpy_once_s"] = round(time.perf_counter() - t0, 3)
+            h["integers_equal"], h["rows_equal"], h["fp64_bit_equal"] = same_hota(hres, href)
+            assert h["integers_equal"] and h["rows_equal"] and h["fp64_bit_equal"], h
+        out["hota"] = h
     return out
 
 
@@ -142,14 +185,16 @@ def main():
     ap.add_argument("--round-s", type=float, default=0.25)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-numpy", action="store_true")
+    ap.add_argument("--hota", action="store_true", help="time hota_eval next to mot_eval on the same rows")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("moteval_bench.py measures on the GPU; none is available")
     dev = torch.device("cuda:0")
     out = dict(bench="moteval", targets=a.targets)
     with torch.cuda.device(dev):
-        out["many_short"] = run_layout(synthetic(a.seqs, a.frames, a.targets, a.seed), dev, a.rounds, a.round_s, not a.no_numpy)
-        out["one_long"] = run_layout(synthetic(1, a.long_frames, a.targets, a.seed + 1), dev, a.rounds, a.round_s, not a.no_numpy)
+        out["many_short"] = run_layout(synthetic(a.seqs, a.frames, a.targets, a.seed), dev, a.rounds, a.round_s, not a.no_numpy,
+                                       a.hota)
+        out["one_long"] = run_layout(synthetic(1, a.long_frames, a.targets, a.seed + 1), dev, a.rounds, a.round_s, not a.no_numpy, a.hota)
     if not a.no_numpy:
         out["compared_against"] = "this project's numpy restatement (tracking_eval.py), not TrackEval / py-motmetrics"
     print(json.dumps(out))

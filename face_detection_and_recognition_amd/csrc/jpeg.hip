@@ -633,6 +633,54 @@ int fp_jpeg_parse(const uint8_t* data, size_t n, fp_jpeg_info* info) {
   return r < 0 ? (int)r : FP_OK;
 }
 
+// The Orientation tag (0x0112) of the first APP1 segment that starts with "Exif\0\0" in front of the first scan: TIFF header,
+// IFD0, the 12-byte entry of type SHORT.  Every offset is checked against the end of the TIFF block (tn) before the bytes
+// behind it are read; anything that does not fit is "no tag".
+int fp_jpeg_exif_orientation(const uint8_t* d, size_t n) {
+  if (!d || n < 4 || d[0] != 0xff || d[1] != 0xd8) return 1;
+  size_t pos = 2;
+  while (pos + 4 <= n) {
+    if (d[pos] != 0xff) return 1;
+    const unsigned m = d[pos + 1];
+    if (m == 0xff) {          // fill byte
+      ++pos;
+      continue;
+    }
+    pos += 2;
+    if (m == 0xd8 || (m >= 0xd0 && m <= 0xd7) || m == 0x01) continue;
+    if (m == 0xd9 || m == 0xda) return 1;        // EOI / the first scan: no Exif segment in front of it
+    if (pos + 2 > n) return 1;
+    const size_t len = be16(d + pos);
+    if (len < 2 || len > n - pos) return 1;
+    if (m != 0xe1 || len < 8 || memcmp(d + pos + 2, "Exif\0\0", 6) != 0) {
+      pos += len;
+      continue;
+    }
+    const uint8_t* t = d + pos + 8;              // the TIFF block: offsets inside it count from here
+    const size_t tn = len - 8;
+    if (tn < 8) return 1;
+    bool le;
+    if (t[0] == 'I' && t[1] == 'I' && t[2] == 0x2a && t[3] == 0) le = true;
+    else if (t[0] == 'M' && t[1] == 'M' && t[2] == 0 && t[3] == 0x2a) le = false;
+    else return 1;
+    auto u16 = [&](size_t o) { return le ? (unsigned)t[o] | ((unsigned)t[o + 1] << 8) : ((unsigned)t[o] << 8) | t[o + 1]; };
+    auto u32 = [&](size_t o) { return le ? (size_t)u16(o) | ((size_t)u16(o + 2) << 16) : ((size_t)u16(o) << 16) | u16(o + 2); };
+    const size_t ifd = u32(4);
+    if (ifd > tn - 2) return 1;                  // (tn >= 8; the entry count's two bytes lie inside)
+    const size_t cnt = u16(ifd);
+    if (cnt * 12 > tn - 2 - ifd) return 1;       // an entry count that runs past the segment
+    for (size_t i = 0; i < cnt; ++i) {
+      const size_t e = ifd + 2 + 12 * i;
+      if (u16(e) != 0x0112) continue;
+      if (u16(e + 2) != 3 || u32(e + 4) != 1) return 1;   // SHORT, one value: it sits in the entry's value field
+      const unsigned v = u16(e + 8);
+      return v >= 1 && v <= 8 ? (int)v : 1;
+    }
+    return 1;
+  }
+  return 1;
+}
+
 int fp_jpeg_entropy_decode(const uint8_t* data, size_t n, const fp_jpeg_info* info_in, int16_t* coefs) {
   if (!data || !info_in || !coefs) return FP_ERR_INVALID_ARG;
   fp_jpeg_info info;

@@ -9,7 +9,7 @@ import json
 
 from .modules.blazeface.model import BlazeFaceModel
 from .modules.utils.inference import inference_img
-from .modules.utils.parser import get_argparse, torch_device
+from .modules.utils.parser import add_read_args, get_argparse, read_kwargs, torch_device
 from .tiling import add_tile_args, wrap_from_args
 
 
@@ -24,7 +24,7 @@ def build_parser():
                         help="Write the image with its detections drawn on (box, landmarks, caption) to this JPEG file.")
     parser.add_argument("--anonymize", dest="anonymize", type=int, choices=[4, 8, 16, 32], default=argparse.SUPPRESS, metavar="CELL",
                         help="With -o: pixelate every detected face first, mosaic cells of CELL x CELL pixels (4, 8, 16 or 32).")
-    return add_tile_args(parser)
+    return add_read_args(add_tile_args(parser))
 
 
 def main(argv=None):
@@ -34,7 +34,8 @@ def main(argv=None):
     net = BlazeFaceModel(args.model, args.det_thres, args.bbox_area_thres, args.model_type,
                          torch_device(args.device))
     net = wrap_from_args(net, args, parser.error)
-    post = inference_img(net, args.input_src, save=getattr(args, "output", None), anonymize=getattr(args, "anonymize", 0))
+    post = inference_img(net, args.input_src, save=getattr(args, "output", None), anonymize=getattr(args, "anonymize", 0),
+                         **read_kwargs(args))
     print(json.dumps({"boxes": post.boxes.tolist(), "confs": post.bbox_confs.tolist(),
                       "areas": post.bbox_areas.tolist(), "landmarks": post.bbox_lmarks.tolist()}))
     return post

@@ -8,7 +8,7 @@ import json
 
 from .modules.mtcnn.model import SLOW_DEFAULTS, SLOW_WEIGHTS, MTCNNFastModel, MTCNNSlowModel
 from .modules.utils.inference import get_dets_bboxes_confs_lmarks_areas, load_image, save_annotated
-from .modules.utils.parser import get_argparse, torch_device
+from .modules.utils.parser import add_read_args, get_argparse, read_kwargs, torch_device
 from .tiling import add_tile_args
 
 
@@ -36,7 +36,7 @@ def build_parser():
                         help="Write the image with its detections drawn on (box, landmarks, caption) to this JPEG file.")
     parser.add_argument("--anonymize", dest="anonymize", type=int, choices=[4, 8, 16, 32], default=argparse.SUPPRESS, metavar="CELL",
                         help="With -o: pixelate every detected face first, mosaic cells of CELL x CELL pixels (4, 8, 16 or 32).")
-    return add_tile_args(parser)      # accepted so that the three entry points share their flags; MTCNN refuses --tile
+    return add_read_args(add_tile_args(parser))      # (tile flags:) accepted so that the three entry points share their flags; MTCNN refuses --tile
 
 
 def main(argv=None):
@@ -45,7 +45,7 @@ def main(argv=None):
     if getattr(args, "tile", None) is not None:
         parser.error("--tile: MTCNN scans its own image pyramid and is not tiled (tiling.TiledDetector refuses it)")
     print("Current Arguments: ", args)
-    image = load_image(args.input_src)
+    image = load_image(args.input_src, **read_kwargs(args))
     net = load_model(args.model_type, args.model, args.det_thres, args.bbox_area_thres, torch_device(args.device), image)
     h, w = image.shape[:2]
     dets = net(image)

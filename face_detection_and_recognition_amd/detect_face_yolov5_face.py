@@ -10,7 +10,7 @@ import os
 from typing import Tuple
 
 from .modules.utils.inference import inference_img
-from .modules.utils.parser import get_argparse, torch_device
+from .modules.utils.parser import add_read_args, get_argparse, read_kwargs, torch_device
 from .modules.yolov5_face import attempt_load, inference_pytorch_model_yolov5_face
 from .modules.yolov5_face.model import YOLOV5FaceModel
 from .tiling import add_tile_args, wrap_from_args
@@ -40,7 +40,7 @@ def build_parser():
                         help="With -o: pixelate every detected face first, mosaic cells of CELL x CELL pixels (4, 8, 16 or 32).")
     parser.add_argument("--augment", action="store_true", default=argparse.SUPPRESS,
                         help="Augmented inference: also run the image mirrored at scale 0.83 and at scale 0.67, one NMS over all rows.")
-    return add_tile_args(parser)
+    return add_read_args(add_tile_args(parser))
 
 
 def main(argv=None):
@@ -50,7 +50,8 @@ def main(argv=None):
     args.input_size = tuple(map(int, args.input_size))
     net = load_model(args.model, args.det_thres, args.bbox_area_thres, args.input_size, args.device, augment=getattr(args, "augment", False))
     net = wrap_from_args(net, args, parser.error)
-    post = inference_img(net, args.input_src, save=getattr(args, "output", None), anonymize=getattr(args, "anonymize", 0))
+    post = inference_img(net, args.input_src, save=getattr(args, "output", None), anonymize=getattr(args, "anonymize", 0),
+                         **read_kwargs(args))
     print(json.dumps({"boxes": post.boxes.tolist(), "confs": post.bbox_confs.tolist(), "areas": post.bbox_areas.tolist()}))
     return post
 

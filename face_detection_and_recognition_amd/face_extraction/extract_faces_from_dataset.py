@@ -129,16 +129,21 @@ def extract_face_feat_conf_area_list(pipe, frames, frame_nums=None, times_sec=No
 
 
 def extract_faces_from_images(pipe, paths, batch_size=256, entropy="host", save_face=False, quality=95,
-                              align=False, quality_gate=None, tiled=None, augment=None) -> List[FrameFacesObj]:
+                              align=False, quality_gate=None, tiled=None, augment=None, reduce=1,
+                              orientation=True) -> List[FrameFacesObj]:
     """The reference's image media items (:400-407: one photo per item, any size, recorded as FrameFacesObj(1, 1, ...)) for a
     whole list of files: decode batch_size files at a time (modules/utils/jpeg.py imread_batch; entropy as there), then one
     pipeline step per batch -- frames of different sizes as one RaggedFrames.  Returns one record per path, in order; pass
-    each to save_extracted_faces under its file's media_root.  align, quality_gate, tiled, augment: as extract_face_feat_conf_area_list."""
+    each to save_extracted_faces under its file's media_root.  align, quality_gate, tiled, augment: as extract_face_feat_conf_area_list.
+    reduce = 2 / 4 / 8: the JPEGs are decoded at 1/2, 1/4, 1/8 size (cv2's IMREAD_REDUCED_COLOR_*: frames of a quarter, a sixteenth,
+    a sixty-fourth of the bytes; boxes and crops are then in the reduced frame's pixels); orientation=False: the EXIF Orientation
+    tag is not applied (imread_batch)."""
     from ..modules.utils.jpeg import imread_batch
     out = []
     for i in range(0, len(paths), int(batch_size)):
         chunk = paths[i:i + int(batch_size)]
-        frames = imread_batch(chunk, pipe.dev, entropy=entropy)     # (B, H, W, 3) when the sizes agree, else a list
+        # (B, H, W, 3) when the sizes agree, else a list
+        frames = imread_batch(chunk, pipe.dev, entropy=entropy, reduce=reduce, orientation=orientation)
         recs = extract_face_feat_conf_area_list(pipe, frames, save_face=save_face, quality=quality, align=align,
                                                 quality_gate=quality_gate, tiled=tiled, augment=augment)
         for r in recs:

@@ -28,17 +28,20 @@ def get_dets_bboxes_confs_lmarks_areas(dets: np.ndarray, orig_size: Tuple[int, i
                                   bbox_lmarks=dets[:, 4:], bbox_labels=opt_labels)
 
 
-def load_image(path: str, device=None):
-    """BGR HWC u8 like cv2.imread (inference.py:68-76).  device = a HIP device: the frame is decoded there (baseline JPEGs:
-    host Huffman + device reconstruction, modules/utils/jpeg.py, byte-identical to libjpeg-turbo) and returned as a device
-    tensor; device = None: numpy array decoded by Pillow on the host (cv2 is not a dependency of this build)."""
+def load_image(path: str, device=None, reduce: int = 1, orientation: bool = True):
+    """BGR HWC u8 like cv2.imread (inference.py:68-76), upright by the file's EXIF Orientation tag as cv2.imread returns it
+    (orientation=False: IMREAD_IGNORE_ORIENTATION); reduce = 2 / 4 / 8: IMREAD_REDUCED_COLOR_2 / _4 / _8, libjpeg's reduced-size
+    decode of a JPEG.  device = a HIP device: the frame is decoded there (baseline JPEGs: host Huffman + device reconstruction,
+    modules/utils/jpeg.py, byte-identical to libjpeg-turbo) and returned as a device tensor; device = None: numpy array decoded
+    by Pillow on the host (cv2 is not a dependency of this build)."""
     if not os.path.exists(path):
         raise FileNotFoundError(f"{path} does not exist")
+    from .jpeg import _check_reduce, _pillow_decode, imread
+    _check_reduce(reduce)
     if device is not None:
-        from .jpeg import imread
-        return imread(path, device, bgr=True)
-    from PIL import Image
-    return np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB"))[..., ::-1])
+        return imread(path, device, bgr=True, reduce=reduce, orientation=orientation)
+    with open(path, "rb") as f:
+        return np.ascontiguousarray(_pillow_decode(f.read(), reduce, orientation)[..., ::-1])
 
 
 def save_annotated(path: str, image, post: PostProcessedDetection, anonymize: int = 0, device=None):
@@ -55,13 +58,15 @@ def save_annotated(path: str, image, post: PostProcessedDetection, anonymize: in
     return imwrite(path, frame)
 
 
-def inference_img(net: Model, img, waitKey_val: int = 0, save: Optional[str] = None, anonymize: int = 0) -> PostProcessedDetection:
+def inference_img(net: Model, img, waitKey_val: int = 0, save: Optional[str] = None, anonymize: int = 0, reduce: int = 1,
+                  orientation: bool = True) -> PostProcessedDetection:
     """inference.py:61-93; the drawing / imshow tail becomes: with `save`, the frame with its detections drawn on (faces
-    pixelated first with anonymize = a mosaic cell) is written to that path.  The return value does not depend on it."""
+    pixelated first with anonymize = a mosaic cell) is written to that path.  The return value does not depend on it.
+    reduce, orientation: how a file is read (load_image)."""
     # a net that takes device frames gets the file decoded ON its device (baseline JPEG: host Huffman + device IDCT / upsampling
     # / colour conversion, byte-identical to cv2.imread's libjpeg-turbo); everything else the host array, as the reference
     dev = net.net._device() if getattr(net, "accepts_device_frames", False) else None
-    image = load_image(img, dev if dev is not None and dev.type == "cuda" else None) if isinstance(img, str) else img
+    image = load_image(img, dev if dev is not None and dev.type == "cuda" else None, reduce, orientation) if isinstance(img, str) else img
     h, w = image.shape[:2]
     dets = net(image)
     labels = None

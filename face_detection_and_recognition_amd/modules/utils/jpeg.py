@@ -11,6 +11,17 @@ fde/face_extraction/extract_faces_from_dataset.py:393-420).
     imread(path, device)                      cv2.imread for the device: JPEGs (sequential and progressive) through the above;
                                               what the decoder does not take (CMYK / arithmetic-coded JPEGs, PNG, ...) is
                                               decoded by Pillow on the host -- file I/O, not the hot path -- and uploaded
+    orientation=True (all of the above)       the frame is turned upright by the file's EXIF Orientation tag (0x0112, read by
+                                              fp_jpeg_exif_orientation on the host), as cv2.imread does: tags 2 .. 8 are applied in
+                                              the colour kernel's addressing (csrc/jpegscale.hip), tags 5 .. 8 give a (W, H, 3)
+                                              frame.  cv2 parity of this is pinned through Pillow's ImageOps.exif_transpose, which
+                                              the host fallback applies too.  orientation=False: cv2's IMREAD_IGNORE_ORIENTATION
+    reduce=2 / 4 / 8 (all of the above)       cv2's IMREAD_REDUCED_COLOR_2 / _4 / _8 = libjpeg's scale_denom: the frame comes out
+                                              of 4 x 4 / 2 x 2 / 1 x 1 inverse DCTs at ceil(H / reduce) x ceil(W / reduce), no
+                                              resize; byte-identical to Pillow's draft() decode.  The orientation is applied after
+                                              scaling.  JPEGs only: a reduced PNG is a resize in cv2, which is not pinned here
+                                              (ValueError).  reduce=1 on a file without a tag (or with tag 1) is the unchanged
+                                              fp_jpeg_reconstruct call
 
     encode_jpeg_batch(images, ...)            JPEG ENCODE (csrc/jpegenc.hip): a list of (h, w, 3) u8 device images -> list of JPEG
                                               files (bytes), byte-identical to libjpeg-turbo's default compressor -- cv2.imwrite /
@@ -31,6 +42,7 @@ from ... import _lib as L
 
 FP_ERR_UNSUPPORTED = -3
 FP_ERR_INVALID_ARG = -1
+REDUCE = (1, 2, 4, 8)         # libjpeg's scale_denom values (cv2: IMREAD_REDUCED_COLOR_2 / _4 / _8)
 DEVICE_SUB_BITS = 1024        # entropy="device": bits per subsequence (one lane each)
 DEVICE_MAX_ROUNDS = 8         # entropy="device": synchronisation rounds before an image is left to the host path
 
@@ -60,9 +72,47 @@ def entropy_decode(data, pinned=False):
     return info, coefs
 
 
-def reconstruct(info, coefs_dev, device, bgr=True, out=None):
-    """The device half: coefficients (int16, on `device`) -> (H, W, 3) u8."""
+def _check_reduce(reduce):
+    if isinstance(reduce, bool) or reduce not in REDUCE:
+        raise ValueError(f"reduce must be 1, 2, 4 or 8 (libjpeg's scale_denom), not {reduce!r}")
+
+
+def exif_orientation(data):
+    """The EXIF Orientation tag (1 .. 8) of a JPEG file's bytes (fp_jpeg_exif_orientation, host only); 1 for no tag, a value
+    outside 1 .. 8 or a damaged segment."""
+    buf = (C.c_uint8 * len(data)).from_buffer_copy(data) if len(data) else (C.c_uint8 * 1)()
+    return int(L.load().fp_jpeg_exif_orientation(buf, len(data)))
+
+
+def scaled_size(info, reduce=1, orientation=1):
+    """(rows, columns) of the frame reconstruct(info, ..., reduce, orientation) writes."""
+    _check_reduce(reduce)
+    h, w = C.c_int(), C.c_int()
+    L.check(L.load().fp_jpeg_scaled_size(C.byref(info), reduce, int(orientation), C.byref(h), C.byref(w)), "fp_jpeg_scaled_size")
+    return h.value, w.value
+
+
+def reconstruct(info, coefs_dev, device, bgr=True, out=None, reduce=1, orientation=True):
+    """The device half: coefficients (int16, on `device`) -> (H, W, 3) u8.  reduce = 2 / 4 / 8: libjpeg's scale_denom, a
+    (ceil(H / reduce), ceil(W / reduce), 3) frame out of the reduced inverse DCTs.  orientation: there is no file here, so this
+    function takes the TAG ITSELF, 1 .. 8 (True counts as 1, as does False); the frame is turned upright by it after scaling,
+    tags 5 .. 8 give a (W', H', 3) frame.  reduce = 1 with tag 1 is fp_jpeg_reconstruct as before; everything else goes
+    through fp_jpeg_reconstruct_scaled (csrc/jpegscale.hip)."""
     lib = L.load()
+    _check_reduce(reduce)
+    tag = int(orientation) or 1
+    if not 1 <= tag <= 8:
+        raise ValueError(f"orientation tag {orientation!r}: 1 .. 8")
+    if reduce != 1 or tag != 1:
+        oh, ow = scaled_size(info, reduce, tag)
+        ws_bytes = int(lib.fp_jpeg_scaled_workspace_bytes(C.byref(info), reduce))
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
+        if out is None:
+            out = torch.empty((oh, ow, 3), dtype=torch.uint8, device=device)
+        assert out.is_contiguous() and tuple(out.shape) == (oh, ow, 3) and out.dtype == torch.uint8
+        L.check(lib.fp_jpeg_reconstruct_scaled(L.ptr(coefs_dev), C.byref(info), reduce, tag, L.ptr(ws), ws_bytes, L.ptr(out),
+                                               1 if bgr else 0, L.current_stream(device)), "fp_jpeg_reconstruct_scaled")
+        return out
     ws_bytes = int(lib.fp_jpeg_workspace_bytes(C.byref(info)))
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
     if out is None:
@@ -127,15 +177,23 @@ def device_entropy_decode(datas, device, sub_bits=None, max_rounds=None):
     return out
 
 
-def decode_jpeg(data, device, bgr=True, entropy="host"):
+def _tag(data, orientation):
+    return exif_orientation(data) if orientation else 1
+
+
+def decode_jpeg(data, device, bgr=True, entropy="host", reduce=1, orientation=True):
+    """One JPEG file's bytes -> (H, W, 3) u8 on `device`.  reduce = 2 / 4 / 8: cv2's IMREAD_REDUCED_COLOR_2 / _4 / _8 (libjpeg's
+    scale_denom).  orientation=True turns the frame upright by the file's EXIF Orientation tag, as cv2.imread does; False is
+    cv2's IMREAD_IGNORE_ORIENTATION."""
     device = torch.device(device)
     _check_entropy(entropy)
+    _check_reduce(reduce)
     if device.type != "cuda":
         raise L.FacepathError("decode_jpeg reconstructs on a HIP device; there is no CPU path")
     if entropy == "device":
-        return decode_jpeg_batch([data], device, bgr, entropy="device")[0]
+        return decode_jpeg_batch([data], device, bgr, entropy="device", reduce=reduce, orientation=orientation)[0]
     info, coefs = entropy_decode(data, pinned=True)
-    return reconstruct(info, coefs.to(device, non_blocking=True), device, bgr)
+    return reconstruct(info, coefs.to(device, non_blocking=True), device, bgr, reduce=reduce, orientation=_tag(data, orientation))
 
 
 def _host_entropy(d):
@@ -145,7 +203,7 @@ def _host_entropy(d):
         return e
 
 
-def _device_batch(datas, device, bgr, threads, missing):
+def _device_batch(datas, device, bgr, threads, missing, reduce=1, orientation=True):
     """entropy="device" for a batch: per file a frame, or missing(i, exception) for a file the host path raises on."""
     dev = device_entropy_decode(datas, device)
     rest = [i for i, r in enumerate(dev) if r is None]
@@ -160,14 +218,15 @@ def _device_batch(datas, device, bgr, threads, missing):
             if isinstance(r, Exception):
                 frames.append(missing(i, r))
                 continue
-            frames.append(reconstruct(r[0], r[1].to(device, non_blocking=True), device, bgr))
+            frames.append(reconstruct(r[0], r[1].to(device, non_blocking=True), device, bgr, reduce=reduce,
+                                      orientation=_tag(datas[i], orientation)))
         elif isinstance(r, int):
             try:
                 L.check(r, "fp_jpeg_entropy_decode")          # what the host path raises for this file
             except L.FacepathError as e:
                 frames.append(missing(i, e))
         else:
-            frames.append(reconstruct(r[0], r[1], device, bgr))
+            frames.append(reconstruct(r[0], r[1], device, bgr, reduce=reduce, orientation=_tag(datas[i], orientation)))
     return frames
 
 
@@ -181,45 +240,64 @@ def _unsupported_to_imread(i, e):
     raise e
 
 
-def decode_jpeg_batch(datas, device, bgr=True, threads=8, entropy="host"):
+def decode_jpeg_batch(datas, device, bgr=True, threads=8, entropy="host", reduce=1, orientation=True):
     """List of JPEG byte strings -> list of (H, W, 3) u8 tensors on `device` (sizes may differ).  entropy="device": the Huffman
     stage on the device for the sequential files it takes (one batch), the others through the host path; the first damaged or
-    unsupported file in order raises what the host path raises."""
+    unsupported file in order raises what the host path raises.  reduce, orientation: as decode_jpeg, per file."""
     device = torch.device(device)
     _check_entropy(entropy)
+    _check_reduce(reduce)
     if device.type != "cuda":
         raise L.FacepathError("decode_jpeg_batch reconstructs on a HIP device; there is no CPU path")
     if entropy == "device":
-        return _device_batch(datas, device, bgr, threads, _raise)
+        return _device_batch(datas, device, bgr, threads, _raise, reduce, orientation)
     with ThreadPoolExecutor(max_workers=max(1, min(threads, len(datas)))) as pool:
         # in order, as each frame's Huffman decode finishes: its copy and reconstruction run under the decodes still going
-        return [reconstruct(info, coefs.to(device, non_blocking=True), device, bgr)
-                for info, coefs in pool.map(lambda d: entropy_decode(d, pinned=True), datas)]
+        return [reconstruct(info, coefs.to(device, non_blocking=True), device, bgr, reduce=reduce, orientation=_tag(d, orientation))
+                for d, (info, coefs) in zip(datas, pool.map(lambda d: entropy_decode(d, pinned=True), datas))]
 
 
-def imread(path, device, bgr=True):
-    """cv2.imread(path) as a device tensor: (H, W, 3) u8, BGR by default."""
+def _pillow_decode(data, reduce, orientation):
+    """imread's host fallback (CMYK / arithmetic-coded JPEGs, other formats) -> (H, W, 3) u8 RGB array.  reduce > 1: libjpeg's
+    own scaled decode through draft() for a JPEG; cv2 RESIZES other formats, which cannot be pinned here: ValueError."""
+    import io
+    from PIL import Image, ImageOps
+    im = Image.open(io.BytesIO(data))
+    if reduce > 1:
+        if im.format != "JPEG":
+            raise ValueError(f"reduce={reduce} on a {im.format} file: only JPEGs are decoded at a reduced size")
+        w, h = im.size
+        im.draft(None, (max(1, w // reduce), max(1, h // reduce)))
+    if orientation:
+        im = ImageOps.exif_transpose(im)
+    return np.asarray(im.convert("RGB"))
+
+
+def imread(path, device, bgr=True, reduce=1, orientation=True):
+    """cv2.imread(path) as a device tensor: (H, W, 3) u8, BGR by default, upright by the EXIF Orientation tag unless
+    orientation=False (cv2's IMREAD_IGNORE_ORIENTATION); reduce = 2 / 4 / 8: IMREAD_REDUCED_COLOR_2 / _4 / _8 (JPEGs only)."""
+    _check_reduce(reduce)
     with open(path, "rb") as f:
         data = f.read()
     if data[:2] == b"\xff\xd8":
         try:
-            return decode_jpeg(data, device, bgr)
+            return decode_jpeg(data, device, bgr, reduce=reduce, orientation=orientation)
         except JpegUnsupported:
             pass
-    import io
-    from PIL import Image
-    rgb = np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+    rgb = _pillow_decode(data, reduce, orientation)
     arr = np.ascontiguousarray(rgb[..., ::-1] if bgr else rgb)
     return torch.from_numpy(arr).to(device)
 
 
-def imread_batch(paths, device, bgr=True, threads=8, entropy="host"):
+def imread_batch(paths, device, bgr=True, threads=8, entropy="host", reduce=1, orientation=True):
     """cv2.imread over a list of files (the dataset driver reads its media this way,
     fde/face_extraction/extract_faces_from_dataset.py:393-420) -> (B, H, W, 3) u8 on `device` when every frame has the same size,
     else a list of (H, W, 3) tensors.  Baseline JPEGs: Huffman decoding on a thread pool, everything else of the decode on the
-    device; other files through imread's host fallback."""
+    device; other files through imread's host fallback.  reduce, orientation: as imread, per file; the frames are stacked when
+    their OUTPUT shapes agree (a portrait file with tag 6 among landscape ones gives a list)."""
     device = torch.device(device)
     _check_entropy(entropy)
+    _check_reduce(reduce)
     datas = []
     for p in paths:
         with open(p, "rb") as f:
@@ -227,10 +305,10 @@ def imread_batch(paths, device, bgr=True, threads=8, entropy="host"):
     if entropy == "device":
         jpg = [i for i, d in enumerate(datas) if d[:2] == b"\xff\xd8"]
         frames = [None] * len(datas)
-        dec = _device_batch([datas[i] for i in jpg], device, bgr, threads, _unsupported_to_imread)
+        dec = _device_batch([datas[i] for i in jpg], device, bgr, threads, _unsupported_to_imread, reduce, orientation)
         for i, f in zip(jpg, dec):
             frames[i] = f
-        frames = [f if f is not None else imread(p, device, bgr) for f, p in zip(frames, paths)]
+        frames = [f if f is not None else imread(p, device, bgr, reduce, orientation) for f, p in zip(frames, paths)]
         if frames and all(f.shape == frames[0].shape for f in frames):
             return torch.stack(frames)
         return frames
@@ -243,8 +321,9 @@ def imread_batch(paths, device, bgr=True, threads=8, entropy="host"):
                 pass
         return None
     with ThreadPoolExecutor(max_workers=max(1, min(threads, len(datas)))) as pool:
-        frames = [reconstruct(h[0], h[1].to(device, non_blocking=True), device, bgr) if h is not None else imread(p, device, bgr)
-                  for h, p in zip(pool.map(host, datas), paths)]
+        frames = [reconstruct(h[0], h[1].to(device, non_blocking=True), device, bgr, reduce=reduce, orientation=_tag(d, orientation))
+                  if h is not None else imread(p, device, bgr, reduce, orientation)
+                  for h, p, d in zip(pool.map(host, datas), paths, datas)]
     if frames and all(f.shape == frames[0].shape for f in frames):
         return torch.stack(frames)
     return frames

@@ -43,6 +43,22 @@ def get_argparse(*args, **kwargs):
     return parser
 
 
+def add_read_args(parser):
+    """How the entry points read their images (modules/utils/jpeg.py imread): --reduce and --ignore_orientation.  Both are
+    absent from the namespace unless given (read_kwargs), so the reference's argument set stays as it is."""
+    parser.add_argument("--reduce", dest="reduce", type=int, choices=[1, 2, 4, 8], default=argparse.SUPPRESS,
+                        help="Decode JPEGs at 1/2, 1/4 or 1/8 size out of smaller inverse DCTs (cv2's IMREAD_REDUCED_COLOR_2 / _4 / "
+                             "_8): a sixteenth of the frame bytes at 4. (default: 1)")
+    parser.add_argument("--ignore_orientation", dest="ignore_orientation", action="store_true", default=argparse.SUPPRESS,
+                        help="Do not turn the image upright by its EXIF Orientation tag (cv2's IMREAD_IGNORE_ORIENTATION).")
+    return parser
+
+
+def read_kwargs(args):
+    """The reduce= / orientation= keywords of imread, load_image and inference_img from a parsed namespace."""
+    return dict(reduce=getattr(args, "reduce", 1), orientation=not getattr(args, "ignore_orientation", False))
+
+
 def torch_device(name: str):
     """'hip' / 'hip:N' / 'cuda[:N]' -> torch device string (ROCm exposes HIP devices as 'cuda')."""
     if name == "cpu":

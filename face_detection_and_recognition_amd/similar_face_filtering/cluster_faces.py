@@ -38,6 +38,10 @@ def get_parsed_args(argv=None):
                         help='measure every image (quality.face_quality over the whole image), keep the columns in clusters.npz '
                              'and copy each cluster\'s sharpest usable image to cluster_XXXX/best.jpg')
     parser.add_argument('-d', '--device', default="cuda")
+    parser.add_argument('--reduce', type=int, choices=[1, 2, 4, 8], default=1,
+                        help='decode the JPEGs at 1/2, 1/4 or 1/8 size out of smaller inverse DCTs (cv2\'s IMREAD_REDUCED_COLOR_*)')
+    parser.add_argument('--ignore_orientation', action="store_true",
+                        help='do not turn the images upright by their EXIF Orientation tag (the default applies it, as cv2.imread)')
     args = parser.parse_args(argv)
     if args.preprocess is None:
         args.preprocess = "tf_standardize" if args.net == "facenet" else "mobile_facenet"
@@ -84,7 +88,7 @@ def save_clusters(path, paths, labels, core, degree, centroids, medoid, quality=
 QUALITY_COLUMNS = ("flags", "step", "mean", "contrast", "dark_frac", "bright_frac", "sharpness", "side")
 
 
-def image_quality(paths, device, batch_size=32, entropy="host"):
+def image_quality(paths, device, batch_size=32, entropy="host", reduce=1, orientation=True):
     """quality.face_quality of every image as ONE whole-image rectangle (these images are face crops already) -> dict of
     host arrays, one row per path: stats (n, 8) and QUALITY_COLUMNS.  Decoded batch by batch as embed_images decodes them."""
     import torch
@@ -93,7 +97,7 @@ def image_quality(paths, device, batch_size=32, entropy="host"):
     from ..quality import face_quality
     cols = {k: [] for k in ("stats",) + QUALITY_COLUMNS}
     for i in range(0, len(paths), int(batch_size)):
-        decoded = imread_batch(paths[i:i + int(batch_size)], device, entropy=entropy)
+        decoded = imread_batch(paths[i:i + int(batch_size)], device, entropy=entropy, reduce=reduce, orientation=orientation)
         frames = as_frames(list(decoded) if isinstance(decoded, (list, tuple)) else decoded, device)
         rows = [[k, 0, 0, w, h, 0, 0, 0, 0] for k, (_, h, w) in enumerate(frame_layout(frames))]
         items = torch.tensor(rows, dtype=torch.int32, device=device)
@@ -127,14 +131,15 @@ def main(argv=None):
     paths = unlabelled_images(args.unlabelled_data_path)
     if not paths:
         raise Exception(f"no .jpg under {args.unlabelled_data_path}")
-    feats = embed_images(model, paths, args.batch_size, preprocess=args.preprocess)
+    read = dict(reduce=args.reduce, orientation=not args.ignore_orientation)
+    feats = embed_images(model, paths, args.batch_size, preprocess=args.preprocess, **read)
     res = dbscan_cosine(feats, args.tau, args.min_samples)
     summ = cluster_summary(feats, res["labels"])
     labels, medoid = res["labels"].cpu().numpy(), summ["medoid"].cpu().numpy()
     groups = group_files(paths, labels, medoid, args.unlabelled_data_path, args.target_data_path)
     quality = None
     if args.best_shot:
-        q = image_quality(paths, model._device(), args.batch_size)
+        q = image_quality(paths, model._device(), args.batch_size, **read)
         best = best_shots(q, labels, len(medoid))
         copy_best_shots(paths, best, args.target_data_path)
         quality = {f"quality_{k}": v for k, v in q.items()}

@@ -72,14 +72,15 @@ def read_and_preprocess_img(img_path: str, in_size=(160, 160), dct_method: str =
     return preprocess_tf_standardize(t, in_size)[0]
 
 
-def embed_images(model, paths, batch_size=32, preprocess="mobile_facenet", entropy="host"):
+def embed_images(model, paths, batch_size=32, preprocess="mobile_facenet", entropy="host", reduce=1, orientation=True):
     """Decode (Huffman stage on a host thread pool, the rest on the device: modules/utils/jpeg.py), then resize + normalise and
     embed on device, batch by batch.  preprocess:
     "mobile_facenet" = cv2-style resize of the whole image to the network's input size through its input LUT in its channel
     order (Mobile-FaceNet: 112x112, (x - 127.5) / 127.5, BGR, fde/modules/mobile_facenet/utils.py:13-17); "tf_standardize" =
     the reference filter's own TF preprocess (filter_faces_using_reference.py:60-68: RGB, [0,1], bilinear resize, per-image
     standardisation) at the network's input size (FaceNet: 160x160, the reference's own pairing).  entropy="device": the Huffman stage of the sequential JPEGs on the device as well
-    (modules/utils/jpeg.py imread_batch)."""
+    (modules/utils/jpeg.py imread_batch).  reduce, orientation: how the files are read (imread_batch: 1/2, 1/4, 1/8-size JPEG
+    decode; the EXIF Orientation tag applied unless orientation=False)."""
     if preprocess not in ("mobile_facenet", "tf_standardize"):
         raise ValueError(f"unknown preprocess {preprocess!r}")
     dev = model._device()
@@ -89,7 +90,8 @@ def embed_images(model, paths, batch_size=32, preprocess="mobile_facenet", entro
     for i in range(0, len(paths), batch_size):
         chunk = paths[i:i + batch_size]
         plan = model.plan_for(len(chunk))
-        decoded = imread_batch(chunk, dev, entropy=entropy)   # (B, H, W, 3) when the sizes agree, else a list
+        # (B, H, W, 3) when the sizes agree, else a list
+        decoded = imread_batch(chunk, dev, entropy=entropy, reduce=reduce, orientation=orientation)
         if preprocess == "tf_standardize":
             for j in range(len(chunk)):
                 rgb = decoded[j].unsqueeze(0).flip(-1).contiguous()

@@ -888,7 +888,32 @@ size_t fp_jpeg_workspace_bytes(const fp_jpeg_info* info);
 int fp_jpeg_reconstruct(const int16_t* coefs, const fp_jpeg_info* info, uint8_t* workspace, size_t ws_bytes, uint8_t* out,
                         int bgr, void* stream);
 
-#define FP_JPEG_DECODE_ON_HOST 1                 /* device status: decode this image with fp_jpeg_entropy_decode */
+/*
+ * EXIF orientation and reduced-size output (added within ABI 15: functions only, no struct changes).
+ * HOST.  fp_jpeg_exif_orientation: the Orientation tag (0x0112, type SHORT, IFD0) of the first APP1 segment that starts
+ * with "Exif\0\0" in front of the first scan: 1 .. 8; 1 for no tag, a value outside 1 .. 8, or a truncated or inconsistent
+ * segment.  Never reads outside data[0 .. n).
+ * fp_jpeg_reconstruct_scaled (csrc/jpegscale.hip): what libjpeg-turbo returns at scale_denom = 1 / 2 / 4 / 8 -- cv2.imread's
+ * IMREAD_REDUCED_COLOR_2 / _4 / _8 -- turned upright by the orientation tag afterwards, as cv2.imread does.  At scale_denom s
+ * the picture is ceil(width / s) x ceil(height / s) and comes out of reduced inverse DCTs, no resize: luma blocks of
+ * m = 8 / s samples (jidctred.c's 4 x 4 and 2 x 2 transforms, the DC term alone at 1 / 8), chroma blocks of up to 2m where
+ * jdmaster.c scales chroma up in the IDCT rather than by upsampling (4:2:0: no upsampling at all below full size), h2v1
+ * upsampling for 4:2:2 -- fancy only for m > 1 and a chroma plane more than 2 samples wide.  Orientation o maps the scaled
+ * H' x W' picture `in` to out[y][x] = in[y][x] (1), in[y][W'-1-x] (2), in[H'-1-y][W'-1-x] (3), in[H'-1-y][x] (4), in[x][y] (5),
+ * in[H'-1-x][y] (6), in[H'-1-x][W'-1-y] (7), in[x][W'-1-y] (8); 5 .. 8 give a W' x H' x 3 frame.  fp_jpeg_scaled_size writes
+ * the OUTPUT frame's rows and columns.  workspace: device, 8-byte aligned, fp_jpeg_scaled_workspace_bytes; out: device,
+ * 4-byte aligned.  Integer arithmetic only, no atomics: runs are bit-identical.  fp_jpeg_reconstruct_scaled_emulate runs the
+ * same __host__ __device__ arithmetic serially on the CPU (coefs, workspace, out: HOST memory).
+ */
+int fp_jpeg_exif_orientation(const uint8_t* data, size_t n);
+int fp_jpeg_scaled_size(const fp_jpeg_info* info, int scale_denom, int orientation, int* out_h, int* out_w);
+size_t fp_jpeg_scaled_workspace_bytes(const fp_jpeg_info* info, int scale_denom);
+int fp_jpeg_reconstruct_scaled(const int16_t* coefs, const fp_jpeg_info* info, int scale_denom, int orientation, uint8_t* workspace,
+                               size_t ws_bytes, uint8_t* out, int bgr, void* stream);
+int fp_jpeg_reconstruct_scaled_emulate(const int16_t* coefs, const fp_jpeg_info* info, int scale_denom, int orientation,
+                                       uint8_t* workspace, size_t ws_bytes, uint8_t* out, int bgr);
+
+#define FP_JPEG_DECODE_ON_HOST 1                /* device status: decode this image with fp_jpeg_entropy_decode */
 #define FP_JPEG_DEV_MAX_BYTES (64ll << 20)       /* scan data of one file the device path takes */
 #define FP_JPEG_DEV_MAX_BLOCKS (1 << 20)         /* 8 x 8 blocks of one image the device path takes */
 

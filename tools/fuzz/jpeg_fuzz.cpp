@@ -80,6 +80,8 @@ int main(int argc, char** argv) {
         }
       }
       fp_jpeg_info info;
+      const int tag = fp_jpeg_exif_orientation(d, len);   // the marker walk of the orientation reader on the same bytes (its own
+      if (tag < 1 || tag > 8) return 1;                   // campaign on the APP1 segment: jpeg_exif_fuzz.cpp)
       int rc = fp_jpeg_parse(d, len, &info);
       if (rc == 0) {
         if (info.n_coefs < 0 || info.n_coefs > (1L << 28)) { free(d); ++err; continue; }   // (a caller allocates this much)

@@ -218,6 +218,8 @@ SIGNATURES = {
     "fp_jpeg_entropy_decode": (_I, [_P, _SZ, C.POINTER(FpJpegInfo), _P]),
     "fp_jpeg_workspace_bytes": (_SZ, [C.POINTER(FpJpegInfo)]),
     "fp_jpeg_reconstruct": (_I, [_P, C.POINTER(FpJpegInfo), _P, _SZ, _P, _I, _P]),
+    "fp_jpeg_batch_workspace_bytes": (_SZ, [C.POINTER(FpJpegInfo), _I]),
+    "fp_jpeg_reconstruct_batch": (_I, [_P, _P, _P, C.POINTER(FpJpegInfo), _I, _P, _SZ, _P, _I, _P]),
     "fp_jpeg_exif_orientation": (_I, [_P, _SZ]),
     "fp_jpeg_scaled_size": (_I, [C.POINTER(FpJpegInfo), _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "fp_jpeg_scaled_workspace_bytes": (_SZ, [C.POINTER(FpJpegInfo), _I]),

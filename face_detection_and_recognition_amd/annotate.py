@@ -374,7 +374,9 @@ def post_dets_draw_list(post, h, w, line_thickness=None, text_bg_alpha=0.5, anon
     has_areas = post.bbox_areas is not None
     if has_areas:
         info[:, 6] = np.asarray(post.bbox_areas, np.float32)
-    lm = None if post.bbox_lmarks is None else np.asarray(post.bbox_lmarks, np.float32).reshape(n, -1)
+    lm = None if post.bbox_lmarks is None else np.asarray(post.bbox_lmarks, np.float32)
+    if lm is not None:                # (a frame without detections -- common in a video -- has nothing to infer a width from)
+        lm = lm.reshape(n, -1) if n else np.zeros((0, 0), np.float32)
     return face_draw_list(info, n, [(h, w)], lmarks=lm if lm is not None and lm.shape[1] >= 2 else None,
                           labels=post.bbox_labels, areas=has_areas, anonymize=anonymize, line_thickness=line_thickness,
                           text_bg_alpha=text_bg_alpha)

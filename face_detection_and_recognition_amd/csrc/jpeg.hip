@@ -16,11 +16,14 @@
 // byte for byte with Pillow's decode (libjpeg-turbo) of the reference's own test images (tests/golden/jpeg, tests/test_jpeg.py).
 // Scope: sequential (SOF0 / SOF1) and PROGRESSIVE (SOF2: spectral selection + successive approximation, jdphuff.c) Huffman
 // files, 8-bit, any number of scans, 1 or 3 components, luma sampling 1x1 / 2x1 / 2x2 with 1x1 chroma, restart intervals.
+// A sequential file without DHT segments (a Motion-JPEG frame) decodes with the Annex K.3 tables (std_huff_tables below).
 // Arithmetic-coded, lossless, 12-bit, CMYK and other sampling layouts are refused (FP_ERR_UNSUPPORTED): the caller falls back
 // to its host decoder for those.
 #include <string.h>
 
 #include "common.h"
+#include "jpegrecon.h"
+#include "jpegstd.h"
 
 namespace {
 
@@ -37,6 +40,7 @@ struct Huff {
   // (value << 8) | (run << 4) | bits consumed, 0 = take the two-step path (the same idea as stb_image's fast_ac)
   short fast[1024];
   bool present;
+  bool preset;              // installed by std_huff_tables, not by a DHT segment of the file
 };
 
 bool build_huff(Huff& h, const unsigned char* bits /*[1..16]*/, const unsigned char* vals, int nvals) {
@@ -186,6 +190,25 @@ inline int decode_block_seq(BitReader& br, const Huff& hd, const Huff& ha, int& 
   return FP_OK;
 }
 
+// The tables a SEQUENTIAL file starts with (jdhuff.c jinit_huff_decoder -> std_huff_tables): slots 0 and 1 of both classes
+// hold the Annex K.3 luminance and chrominance tables until a DHT segment overwrites them; slots 2 and 3 stay absent.
+// Motion-JPEG frames routinely carry no DHT at all.  libjpeg-turbo's progressive decoder (jdphuff.c) installs nothing and
+// refuses a scan whose table no DHT defined (JERR_NO_HUFF_TABLE); drop_preset_tables takes the presets out again for SOF2.
+void std_huff_tables(Huff* dc /*[4]*/, Huff* ac /*[4]*/) {
+  build_huff(dc[0], kDcLumaBits, kDcVals, 12);
+  build_huff(ac[0], kAcLumaBits, kAcLumaVals, 162);
+  build_huff(dc[1], kDcChromaBits, kDcVals, 12);
+  build_huff(ac[1], kAcChromaBits, kAcChromaVals, 162);
+  for (int i = 0; i < 2; ++i) dc[i].preset = ac[i].preset = true;
+}
+
+void drop_preset_tables(Huff* dc /*[4]*/, Huff* ac /*[4]*/) {
+  for (int i = 0; i < 2; ++i) {
+    if (dc[i].preset) dc[i].present = dc[i].preset = false;
+    if (ac[i].preset) ac[i].present = ac[i].preset = false;
+  }
+}
+
 inline unsigned be16(const unsigned char* p) { return ((unsigned)p[0] << 8) | p[1]; }
 
 struct Frame {               // what the frame header (SOF) and the tables in front of the first scan say
@@ -299,6 +322,7 @@ int read_sos(const unsigned char* s, unsigned len, const fp_jpeg_info& info, con
 long parse_headers(const unsigned char* d, size_t n, fp_jpeg_info& info, Frame& fr, Huff* dc /*[4]*/, Huff* ac /*[4]*/) {
   memset(&info, 0, sizeof(info));
   memset(&fr, 0, sizeof(fr));
+  std_huff_tables(dc, ac);
   if (n < 4 || d[0] != 0xff || d[1] != 0xd8) return FP_ERR_INVALID_ARG;
   size_t pos = 2;
   while (pos + 4 <= n) {
@@ -330,6 +354,7 @@ long parse_headers(const unsigned char* d, size_t n, fp_jpeg_info& info, Frame& 
         if (!fr.have_qt[fr.comp_tq[c]]) return FP_ERR_INVALID_ARG;
         memcpy(info.quant[c], fr.qt[fr.comp_tq[c]], 128);
       }
+      if (info.progressive) drop_preset_tables(dc, ac);
       return (long)pos;
     }
     if (rc) return rc;
@@ -462,135 +487,17 @@ int decode_scan(BitReader& br, const fp_jpeg_info& info, const Scan& sc, const H
 // ---------------------------------------------------------------------------------------------------------------------
 // device side
 
-struct JpegDevInfo {
-  int width, height, ncomp, hs0, vs0;
-  int blocks_w[3], blocks_h[3], comp_w[3], comp_h[3];
-  long coef_off[3], plane_off[3];
-  unsigned short quant[3][64];
-};
-
-// jidctint.c jpeg_idct_islow: CONST_BITS = 13, PASS1_BITS = 2
-#define JF_0_298631336 2446
-#define JF_0_390180644 3196
-#define JF_0_541196100 4433
-#define JF_0_765366865 6270
-#define JF_0_899976223 7373
-#define JF_1_175875602 9633
-#define JF_1_501321110 12299
-#define JF_1_847759065 15137
-#define JF_1_961570560 16069
-#define JF_2_053119869 16819
-#define JF_2_562915447 20995
-#define JF_3_072711026 25172
-
-__device__ __forceinline__ int jdescale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
-
-// one 1-D pass of the islow transform on eight values; SHIFT = the pass's descale
-template <int SHIFT, bool FIRST>
-__device__ __forceinline__ void idct8(const int in[8], int out[8]) {
-  // even part
-  int z2 = in[2], z3 = in[6];
-  int z1 = (z2 + z3) * JF_0_541196100;
-  const int tmp2 = z1 + z3 * (-JF_1_847759065);
-  const int tmp3 = z1 + z2 * JF_0_765366865;
-  z2 = in[0];
-  z3 = in[4];
-  const int tmp0 = (z2 + z3) << 13;
-  const int tmp1 = (z2 - z3) << 13;
-  const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-  // odd part
-  int t0 = in[7], t1 = in[5], t2 = in[3], t3 = in[1];
-  z1 = t0 + t3;
-  z2 = t1 + t2;
-  z3 = t0 + t2;
-  int z4 = t1 + t3;
-  const int z5 = (z3 + z4) * JF_1_175875602;
-  t0 *= JF_0_298631336;
-  t1 *= JF_2_053119869;
-  t2 *= JF_3_072711026;
-  t3 *= JF_1_501321110;
-  z1 *= -JF_0_899976223;
-  z2 *= -JF_2_562915447;
-  z3 *= -JF_1_961570560;
-  z4 *= -JF_0_390180644;
-  z3 += z5;
-  z4 += z5;
-  t0 += z1 + z3;
-  t1 += z2 + z4;
-  t2 += z2 + z3;
-  t3 += z1 + z4;
-  out[0] = jdescale(tmp10 + t3, SHIFT);
-  out[7] = jdescale(tmp10 - t3, SHIFT);
-  out[1] = jdescale(tmp11 + t2, SHIFT);
-  out[6] = jdescale(tmp11 - t2, SHIFT);
-  out[2] = jdescale(tmp12 + t1, SHIFT);
-  out[5] = jdescale(tmp12 - t1, SHIFT);
-  out[3] = jdescale(tmp13 + t0, SHIFT);
-  out[4] = jdescale(tmp13 - t0, SHIFT);
-}
+// (the arithmetic -- jpeg_idct_block, chroma_sample, jpeg_color_pixel -- stands in jpegrecon.h: csrc/jpegbatch.hip runs the same)
 
 // One thread per 8 x 8 block: dequantise, columns (descale 11), rows (descale 18), + 128, clamp -> the component's sample plane.
 __global__ __launch_bounds__(64) void jpeg_idct_kernel(const short* coefs, unsigned char* planes, JpegDevInfo info, long nblocks_total) {
   const long b = (long)blockIdx.x * 64 + threadIdx.x;
   if (b >= nblocks_total) return;
-  int c = 0;
   long bb = b;
-  while (c + 1 < info.ncomp && bb >= (long)info.blocks_w[c] * info.blocks_h[c]) bb -= (long)info.blocks_w[c] * info.blocks_h[c], ++c;
+  const int c = jpeg_block_component(info, bb);
   const int bx = (int)(bb % info.blocks_w[c]), by = (int)(bb / info.blocks_w[c]);
-  const short* src = coefs + info.coef_off[c] + bb * 64;
-  int ws[64];
-#pragma unroll
-  for (int col = 0; col < 8; ++col) {
-    int in[8], out[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) in[r] = (int)src[r * 8 + col] * (int)info.quant[c][r * 8 + col];
-    idct8<11, true>(in, out);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) ws[r * 8 + col] = out[r];
-  }
-  unsigned char* dst = planes + info.plane_off[c] + ((long)by * 8) * (info.blocks_w[c] * 8) + bx * 8;
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    int in[8], out[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) in[k] = ws[r * 8 + k];
-    idct8<18, false>(in, out);
-    unsigned long long packed = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int v = min(max(out[k] + 128, 0), 255);      // range_limit (jdmaster.c prepare_range_limit_table)
-      packed |= (unsigned long long)v << (8 * k);
-    }
-    *(unsigned long long*)(dst + (long)r * (info.blocks_w[c] * 8)) = packed;
-  }
-}
-
-// chroma sample for output pixel (oy, ox) by libjpeg's upsampling (jdsample.c); plane row pitch = pitch, the component's
-// true size = cw x ch (edges replicate inside it).  jinit_upsampler takes the fancy (triangle) filters only for
-// downsampled_width > 2; a component 1 or 2 samples wide gets plain replication (h2v1_upsample / h2v2_upsample), down as
-// well as across
-__device__ __forceinline__ int chroma_sample(const unsigned char* pl, int pitch, int cw, int ch, int oy, int ox, int hs0, int vs0) {
-  if (hs0 == 1) return pl[(long)oy * pitch + ox];                      // 4:4:4 (vs0 == 1 too)
-  const int cx = ox >> 1, hodd = ox & 1;
-  if (cw <= 2) return pl[(long)(vs0 == 1 ? oy : oy >> 1) * pitch + cx];   // h2v1_upsample / h2v2_upsample
-  if (vs0 == 1) {                                                      // h2v1_fancy_upsample
-    const unsigned char* r = pl + (long)oy * pitch;
-    const int cur = r[cx];
-    if (!hodd) return cx == 0 ? cur : (cur * 3 + r[cx - 1] + 1) >> 2;
-    return cx == cw - 1 ? cur : (cur * 3 + r[cx + 1] + 2) >> 2;
-  }
-  // h2v2_fancy_upsample: the nearer row counts 3/4, the further (above for even output rows, below for odd) 1/4
-  const int cy = oy >> 1;
-  const int cy1 = (oy & 1) ? min(cy + 1, ch - 1) : max(cy - 1, 0);
-  const unsigned char* r0 = pl + (long)cy * pitch;
-  const unsigned char* r1 = pl + (long)cy1 * pitch;
-  const int cur = r0[cx] * 3 + r1[cx];
-  if (!hodd) {
-    if (cx == 0) return (cur * 4 + 8) >> 4;
-    return (cur * 3 + (r0[cx - 1] * 3 + r1[cx - 1]) + 8) >> 4;
-  }
-  if (cx == cw - 1) return (cur * 4 + 7) >> 4;
-  return (cur * 3 + (r0[cx + 1] * 3 + r1[cx + 1]) + 7) >> 4;
+  const long pitch = info.blocks_w[c] * 8;
+  jpeg_idct_block(coefs + info.coef_off[c] + bb * 64, info.quant[c], planes + info.plane_off[c] + ((long)by * 8) * pitch + bx * 8, pitch);
 }
 
 // One thread per output pixel: upsample + ycc_rgb_convert (jdcolor.c: SCALEBITS 16) -> interleaved u8
@@ -598,25 +505,7 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const unsigned char* pl
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= (long)info.width * info.height) return;
   const int oy = (int)(i / info.width), ox = (int)(i - (long)oy * info.width);
-  const int y = planes[info.plane_off[0] + (long)oy * (info.blocks_w[0] * 8) + ox];
-  int r, g, b;
-  if (info.ncomp == 1) {
-    r = g = b = y;
-  } else {
-    const int cb = chroma_sample(planes + info.plane_off[1], info.blocks_w[1] * 8, info.comp_w[1], info.comp_h[1], oy, ox, info.hs0, info.vs0) - 128;
-    const int cr = chroma_sample(planes + info.plane_off[2], info.blocks_w[2] * 8, info.comp_w[2], info.comp_h[2], oy, ox, info.hs0, info.vs0) - 128;
-    // FIX(1.40200) = 91881, FIX(1.77200) = 116130, FIX(0.71414) = 46802, FIX(0.34414) = 22554, ONE_HALF = 32768
-    r = y + ((91881 * cr + 32768) >> 16);
-    b = y + ((116130 * cb + 32768) >> 16);
-    g = y + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
-    r = min(max(r, 0), 255);
-    g = min(max(g, 0), 255);
-    b = min(max(b, 0), 255);
-  }
-  unsigned char* o = out + i * 3;
-  o[0] = (unsigned char)(bgr ? b : r);
-  o[1] = (unsigned char)g;
-  o[2] = (unsigned char)(bgr ? r : b);
+  jpeg_color_pixel(planes, out + i * 3, info, oy, ox, bgr);
 }
 
 }  // namespace
@@ -837,25 +726,8 @@ int fp_jpeg_reconstruct(const int16_t* coefs, const fp_jpeg_info* info, uint8_t*
   if (ws_bytes < fp_jpeg_workspace_bytes(info)) return FP_ERR_BOUNDS;
   if (((uintptr_t)workspace) % 8 || ((uintptr_t)coefs) % 2) return FP_ERR_ALIGNMENT;
   JpegDevInfo d;
-  memset(&d, 0, sizeof(d));
-  d.width = info->width;
-  d.height = info->height;
-  d.ncomp = info->ncomp;
-  d.hs0 = info->hs[0];
-  d.vs0 = info->vs[0];
-  long nblocks = 0, poff = 0;
-  for (int c = 0; c < info->ncomp; ++c) {
-    if (info->blocks_w[c] <= 0 || info->blocks_h[c] <= 0) return FP_ERR_INVALID_ARG;
-    d.blocks_w[c] = info->blocks_w[c];
-    d.blocks_h[c] = info->blocks_h[c];
-    d.comp_w[c] = info->comp_w[c];
-    d.comp_h[c] = info->comp_h[c];
-    d.coef_off[c] = info->coef_off[c];
-    d.plane_off[c] = poff;
-    poff += (long)info->blocks_w[c] * 8 * info->blocks_h[c] * 8;
-    nblocks += (long)info->blocks_w[c] * info->blocks_h[c];
-    memcpy(d.quant[c], info->quant[c], 128);
-  }
+  long nblocks = 0, plane_bytes = 0;
+  if (!jpeg_dev_info(info, d, nblocks, plane_bytes)) return FP_ERR_INVALID_ARG;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((nblocks + 63) / 64)), dim3(64), 0, s, (const short*)coefs, workspace, d, nblocks);
   FP_CHECK_LAUNCH();

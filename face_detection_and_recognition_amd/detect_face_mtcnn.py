@@ -1,13 +1,15 @@
 """``python -m face_detection_and_recognition_amd.detect_face_mtcnn -i img.jpg --mt fast --md weights.npz``
-Entry point with the reference's flags (face_detection_and_extraction/detect_face_mtcnn.py).  Images only (the video /
-webcam GUI loops are out of scope); prints the detector's rows (15 numbers each: box, five landmarks, confidence, normalised
+Entry point with the reference's flags (face_detection_and_extraction/detect_face_mtcnn.py).  Images and Motion-JPEG video files
+(``-i clip.avi`` / ``clip.mjpeg``, modules/utils/video.py: one JSON record per frame, ``-o out.avi`` writes the annotated video; the
+webcam GUI loop is out of scope); for an image it prints the detector's rows (15 numbers each: box, five landmarks, confidence, normalised
 by the image size) and the post-processed detections as JSON.  ``-o out.jpg`` also saves the image with the detections drawn
 on, ``--anonymize CELL`` pixelates the faces in it first (annotate.py).  ``--md synthetic`` runs seeded random weights calibrated on the image (synth.py)."""
 import argparse
 import json
 
 from .modules.mtcnn.model import SLOW_DEFAULTS, SLOW_WEIGHTS, MTCNNFastModel, MTCNNSlowModel
-from .modules.utils.inference import get_dets_bboxes_confs_lmarks_areas, load_image, save_annotated
+from .modules.utils.files import get_file_type
+from .modules.utils.inference import get_dets_bboxes_confs_lmarks_areas, inference_vid, load_image, save_annotated
 from .modules.utils.parser import add_read_args, get_argparse, read_kwargs, torch_device
 from .tiling import add_tile_args
 
@@ -26,6 +28,25 @@ def load_model(model_type, model_path, det_thres, bbox_area_thres, device, image
     raise NotImplementedError(f"{model_type} is not supported")
 
 
+def video_main(args):
+    """-i clip.avi: inference_vid over the file; --md synthetic calibrates its heads on the first frame."""
+    first = None
+    if args.model == "synthetic":
+        import io
+        import numpy as np
+        from PIL import Image
+        from .modules.utils.video import VideoReader
+        with VideoReader(args.input_src) as reader:
+            first = np.ascontiguousarray(np.asarray(Image.open(io.BytesIO(reader.frame_bytes(0))).convert("RGB"))[..., ::-1])
+    net = load_model(args.model_type, args.model, args.det_thres, args.bbox_area_thres, torch_device(args.device), first)
+    posts = inference_vid(net, args.input_src, save=getattr(args, "output", None), anonymize=getattr(args, "anonymize", 0),
+                          reduce=getattr(args, "reduce", 1))
+    for frame, post in enumerate(posts):
+        print(json.dumps({"frame": frame, "boxes": post.boxes.tolist(), "confs": post.bbox_confs.tolist(),
+                          "areas": post.bbox_areas.tolist(), "landmarks": post.bbox_lmarks.tolist()}))
+    return posts
+
+
 def build_parser():
     parser = get_argparse(description="MTCNN face detection (MI355X HIP path)", conflict_handler='resolve')
     parser.add_argument("--md", "--model", dest="model", default=SLOW_WEIGHTS,
@@ -33,7 +54,8 @@ def build_parser():
     parser.add_argument("--mt", "--model_type", dest="model_type", default="fast", choices=["fast", "slow"],
                         help="MTCNN model type, fast or slow (default: %(default)s).")
     parser.add_argument("-o", "--output", dest="output", default=argparse.SUPPRESS,
-                        help="Write the image with its detections drawn on (box, landmarks, caption) to this JPEG file.")
+                        help="Write the image with its detections drawn on (box, landmarks, caption) to this JPEG file; for a video input, the "
+                             "annotated frames to this Motion-JPEG AVI file (AVI 1.0: below 2 GiB, OpenDML is out of scope).")
     parser.add_argument("--anonymize", dest="anonymize", type=int, choices=[4, 8, 16, 32], default=argparse.SUPPRESS, metavar="CELL",
                         help="With -o: pixelate every detected face first, mosaic cells of CELL x CELL pixels (4, 8, 16 or 32).")
     return add_read_args(add_tile_args(parser))      # (tile flags:) accepted so that the three entry points share their flags; MTCNN refuses --tile
@@ -45,6 +67,8 @@ def main(argv=None):
     if getattr(args, "tile", None) is not None:
         parser.error("--tile: MTCNN scans its own image pyramid and is not tiled (tiling.TiledDetector refuses it)")
     print("Current Arguments: ", args)
+    if get_file_type(args.input_src) == "video":
+        return video_main(args)
     image = load_image(args.input_src, **read_kwargs(args))
     net = load_model(args.model_type, args.model, args.det_thres, args.bbox_area_thres, torch_device(args.device), image)
     h, w = image.shape[:2]

@@ -1,5 +1,7 @@
 """``python -m face_detection_and_recognition_amd.detect_face_yolov5_face -i img.jpg --md yolov5n-face.pt``
-Entry point with the reference's flags (face_detection_and_extraction/detect_face_yolov5_face.py:13-66).  ``-o out.jpg`` also
+Entry point with the reference's flags (face_detection_and_extraction/detect_face_yolov5_face.py:13-66).  Images and Motion-JPEG
+video files (``-i clip.avi`` / ``clip.mjpeg``, modules/utils/video.py: one JSON record per frame, ``-o out.avi`` writes the annotated
+video; the webcam GUI loop is out of scope).  ``-o out.jpg`` also
 saves the image with the detections drawn on, ``--anonymize CELL`` pixelates the faces in it first (annotate.py).  ``--tile W H
 --merge_thr T`` (with ``--overlap``, ``--edge_px``, ``--no_full_frame``) runs the detector on overlapping tiles of the image as well and
 merges the detections on the device (tiling.py).  ``--augment`` runs the reference's augmented inference: the image, the image
@@ -9,7 +11,8 @@ import json
 import os
 from typing import Tuple
 
-from .modules.utils.inference import inference_img
+from .modules.utils.files import get_file_type
+from .modules.utils.inference import inference_img, inference_vid
 from .modules.utils.parser import add_read_args, get_argparse, read_kwargs, torch_device
 from .modules.yolov5_face import attempt_load, inference_pytorch_model_yolov5_face
 from .modules.yolov5_face.model import YOLOV5FaceModel
@@ -35,7 +38,8 @@ def build_parser():
     parser.add_argument("--is", "--input_size", dest="input_size", nargs=2, default=(640, 640),
                         help='Input images are resized to this size (width, height). (default: %(default)s).')
     parser.add_argument("-o", "--output", dest="output", default=argparse.SUPPRESS,
-                        help="Write the image with its detections drawn on (box, landmarks, caption) to this JPEG file.")
+                        help="Write the image with its detections drawn on (box, landmarks, caption) to this JPEG file; for a video input, the "
+                             "annotated frames to this Motion-JPEG AVI file (AVI 1.0: below 2 GiB, OpenDML is out of scope).")
     parser.add_argument("--anonymize", dest="anonymize", type=int, choices=[4, 8, 16, 32], default=argparse.SUPPRESS, metavar="CELL",
                         help="With -o: pixelate every detected face first, mosaic cells of CELL x CELL pixels (4, 8, 16 or 32).")
     parser.add_argument("--augment", action="store_true", default=argparse.SUPPRESS,
@@ -50,6 +54,13 @@ def main(argv=None):
     args.input_size = tuple(map(int, args.input_size))
     net = load_model(args.model, args.det_thres, args.bbox_area_thres, args.input_size, args.device, augment=getattr(args, "augment", False))
     net = wrap_from_args(net, args, parser.error)
+    if get_file_type(args.input_src) == "video":
+        posts = inference_vid(net, args.input_src, save=getattr(args, "output", None), anonymize=getattr(args, "anonymize", 0),
+                              reduce=getattr(args, "reduce", 1))
+        for frame, post in enumerate(posts):
+            print(json.dumps({"frame": frame, "boxes": post.boxes.tolist(), "confs": post.bbox_confs.tolist(),
+                              "areas": post.bbox_areas.tolist()}))
+        return posts
     post = inference_img(net, args.input_src, save=getattr(args, "output", None), anonymize=getattr(args, "anonymize", 0),
                          **read_kwargs(args))
     print(json.dumps({"boxes": post.boxes.tolist(), "confs": post.bbox_confs.tolist(), "areas": post.bbox_areas.tolist()}))

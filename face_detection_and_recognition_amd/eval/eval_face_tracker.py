@@ -7,7 +7,8 @@ section 7 "Tracker evaluation".  Build-defined: the reference calls no tracking 
 py-motmetrics is unpinned.
 
 ``data`` is a folder of sequences, each a folder with ``gt.txt`` (MOTChallenge rows ``frame,id,x,y,w,h,...``, frames 1-based)
-and ``frames/*.jpg`` (sorted by name = video order).  The hypotheses are either
+and ``frames/*.jpg`` (sorted by name = video order) or, in place of that folder, ``video.avi`` (Motion-JPEG,
+modules/utils/video.py).  The hypotheses are either
 
   * ``--tracks DIR``: ``DIR/<sequence>.txt`` in the same format (a sequence without a file has no hypotheses), or
   * a model plus ``--max_age`` (and ``--tau_near / --tau_far / --iou_min``): FacePipeline(tracker=StreamTracker) runs over the
@@ -37,7 +38,8 @@ SWEEP_KEYS = dict(max_age=int, tau_near=float, tau_far=float, iou_min=float, std
 
 
 def load_sequences(root):
-    """-> list of dict(name, gt (read_mot_txt), frames (sorted .jpg paths), n_frames) for every folder of root with a gt.txt.
+    """-> list of dict(name, gt (read_mot_txt), frames (sorted .jpg paths, or a VideoReader over video.avi), n_frames) for every
+    folder of root with a gt.txt.
     n_frames is the number of .jpg files, or without a frames folder the last labelled frame + 1."""
     seqs = []
     for name in sorted(os.listdir(root)):
@@ -46,6 +48,10 @@ def load_sequences(root):
             continue
         gt = read_mot_txt(gt_path)
         frames = sorted(glob.glob(os.path.join(root, name, "frames", "*.jpg")))
+        video = os.path.join(root, name, "video.avi")
+        if not frames and os.path.isfile(video):          # a Motion-JPEG file in place of the frames folder
+            from ..modules.utils.video import VideoReader
+            frames = VideoReader(video)
         n_frames = len(frames) if frames else (int(gt["frame"].max()) + 1 if len(gt["frame"]) else 0)
         if len(gt["frame"]) and (gt["frame"].min() < 0 or gt["frame"].max() >= n_frames):
             raise ValueError(f"{gt_path}: frame numbers outside 1 .. {n_frames}")
@@ -53,6 +59,13 @@ def load_sequences(root):
     if not seqs:
         raise ValueError(f"no sequence (a folder with gt.txt) under {root}")
     return seqs
+
+
+def close_sequences(seqs):
+    """Closes the video files load_sequences opened."""
+    for s in seqs:
+        if hasattr(s["frames"], "close"):
+            s["frames"].close()
 
 
 def stack_rows(per_seq):
@@ -93,20 +106,20 @@ def build_parts(seqs, args, dev):
     """(detector, embedder) on the synthetic weights, the detector's scores calibrated on the first frames; built once per
     sweep."""
     from .. import workload as W
-    from ..modules.utils.jpeg import imread_batch
+    from ..modules.utils.video import read_frames
     if args.model != "synthetic":
         raise ValueError("only --model synthetic is wired here; build a FacePipeline(..., tracker=StreamTracker(...)) for real "
                          "weights and feed a TrackingEvaluator from its steps")
     first = next((s["frames"] for s in seqs if s["frames"]), None)
     if first is None:
         raise ValueError("no frames/*.jpg in any sequence: nothing to run the tracker on (use --tracks)")
-    return W.build_detector(dev, imread_batch(first[:8], dev), cand_per_frame=48), W.build_embedder(dev)
+    return W.build_detector(dev, read_frames(first, 0, 8, dev), cand_per_frame=48), W.build_embedder(dev)
 
 
 def run_tracker(seqs, args, dev, parts):
     """The pipeline over every sequence's frames, batch by batch, one stream per sequence -> MotResult."""
     import torch
-    from ..modules.utils.jpeg import imread_batch
+    from ..modules.utils.video import read_frames
     from ..pipeline import FacePipeline
     from ..tracking import ConstantVelocity, StreamTracker
     det, emb = parts
@@ -117,9 +130,10 @@ def run_tracker(seqs, args, dev, parts):
     ev = TrackingEvaluator(len(seqs), dev, thr=args.thr).set_ground_truth(*ground_truth(seqs))
     for s, seq in enumerate(seqs):
         for lo in range(0, len(seq["frames"]), args.batch_size):
-            frames = imread_batch(seq["frames"][lo:lo + args.batch_size], dev)
-            if not isinstance(frames, torch.Tensor):
-                raise ValueError(f"{seq['name']}: the frames of a video share one size")
+            try:
+                frames = read_frames(seq["frames"], lo, lo + args.batch_size, dev)
+            except ValueError as e:
+                raise ValueError(f"{seq['name']}: {e}") from None
             B = int(frames.shape[0])
             res = pipe.step(frames, streams=[s] * B)
             n, info = res["n_faces"], res["info"]
@@ -156,7 +170,7 @@ def parse_sweep(text):
 def main(argv=None):
     import torch
     parser = argparse.ArgumentParser(description="Evaluate face trackers with CLEAR-MOT and IDF1 (MI355X HIP path)")
-    parser.add_argument("data", help="Folder of sequences: <sequence>/gt.txt and <sequence>/frames/*.jpg.")
+    parser.add_argument("data", help="Folder of sequences: <sequence>/gt.txt and <sequence>/frames/*.jpg (or <sequence>/video.avi, Motion-JPEG).")
     parser.add_argument("--tracks", default=None, help="Folder of hypothesis files <sequence>.txt; no tracker is run.")
     parser.add_argument("--model", default=None, help="'synthetic' (seeded random weights); trained weights: use the API.")
     parser.add_argument("--max_age", type=int, default=None, help="Required with --model unless swept: nothing has been measured.")
@@ -187,42 +201,45 @@ def main(argv=None):
             parser.error(str(e))
     device = None if args.device == "cpu" else torch.device(args.device.replace("hip", "cuda"))
     seqs = load_sequences(args.data)
-    names = [s["name"] for s in seqs]
-    if args.tracks is not None:
-        if args.sweep:
-            parser.error("--sweep needs a tracker to run: use --model")
-        if device is not None and not torch.cuda.is_available():
-            print("[WARNING] no HIP device: scoring the track files with the numpy path")
-            device = None
-        result = score_tracks(seqs, args.tracks, args.thr, device, args.hota, args.alphas)
-        print("\n".join(table(result, names)))
-        return result
-    if device is None:
-        raise NotImplementedError("the pipeline has no CPU path: use -d hip, or --tracks with -d cpu")
     try:
-        key, values = parse_sweep(args.sweep) if args.sweep else (None, [None])
-    except ValueError as e:
-        parser.error(str(e))
-    if args.max_age is None and key != "max_age":
-        parser.error("--max_age is required (it has no default: nothing has been measured)")
-    if key in ("std_pos", "std_vel") and args.motion is None:
-        parser.error(f"--sweep {key}= needs --motion STD_POS STD_VEL for the value that is not swept")
-    results, parts = [], build_parts(seqs, args, device)
-    for v in values:
-        if key in ("std_pos", "std_vel"):
-            args.motion[("std_pos", "std_vel").index(key)] = v
-        elif key is not None:
-            setattr(args, key, v)
-        result = run_tracker(seqs, args, device, parts)
-        results.append((v, result))
-        lines = table(result, names)
-        if key is None:
-            print("\n".join(lines))
-        else:
-            if len(results) == 1:
-                print(f"{key:<10}" + lines[0])
-            print(f"{v!s:<10}" + lines[-1])
-    return results[0][1] if key is None else results
+        names = [s["name"] for s in seqs]
+        if args.tracks is not None:
+            if args.sweep:
+                parser.error("--sweep needs a tracker to run: use --model")
+            if device is not None and not torch.cuda.is_available():
+                print("[WARNING] no HIP device: scoring the track files with the numpy path")
+                device = None
+            result = score_tracks(seqs, args.tracks, args.thr, device, args.hota, args.alphas)
+            print("\n".join(table(result, names)))
+            return result
+        if device is None:
+            raise NotImplementedError("the pipeline has no CPU path: use -d hip, or --tracks with -d cpu")
+        try:
+            key, values = parse_sweep(args.sweep) if args.sweep else (None, [None])
+        except ValueError as e:
+            parser.error(str(e))
+        if args.max_age is None and key != "max_age":
+            parser.error("--max_age is required (it has no default: nothing has been measured)")
+        if key in ("std_pos", "std_vel") and args.motion is None:
+            parser.error(f"--sweep {key}= needs --motion STD_POS STD_VEL for the value that is not swept")
+        results, parts = [], build_parts(seqs, args, device)
+        for v in values:
+            if key in ("std_pos", "std_vel"):
+                args.motion[("std_pos", "std_vel").index(key)] = v
+            elif key is not None:
+                setattr(args, key, v)
+            result = run_tracker(seqs, args, device, parts)
+            results.append((v, result))
+            lines = table(result, names)
+            if key is None:
+                print("\n".join(lines))
+            else:
+                if len(results) == 1:
+                    print(f"{key:<10}" + lines[0])
+                print(f"{v!s:<10}" + lines[-1])
+        return results[0][1] if key is None else results
+    finally:
+        close_sequences(seqs)
 
 
 if __name__ == "__main__":

@@ -14,7 +14,8 @@ directory follows the reference's driver (:395-409): <target>/faces/<class_name>
 
 The reference walks a dataset one frame at a time through a Net wrapper; this module is the SURVEY 8(f) rank-1
 "next" row: the same composition driven by pipeline.FacePipeline, so detection, cropping and embedding of all frames
-of a media item are three device-resident stages.  Directory walking / video decoding stay with the caller."""
+of a media item are three device-resident stages.  Directory walking / video decoding stay with the caller (a Motion-JPEG
+file's frames come batch by batch from modules/utils/video.py's VideoReader.batches)."""
 import os
 from dataclasses import dataclass, field
 from typing import List

@@ -1,6 +1,7 @@
-"""track_faces_in_frames: the faces of one video, given as a folder of its frames, grouped into tracks.
+"""track_faces_in_frames: the faces of one video, given as a folder of its frames or as a Motion-JPEG file, grouped into tracks.
 
-Every .jpg of --frames (sorted by name = video order) goes through FacePipeline (BlazeFace-back + Mobile-FaceNet) batch by
+Every .jpg of --frames (sorted by name = video order), or every frame of --video (a Motion-JPEG AVI or raw .mjpeg stream,
+modules/utils/video.py; exactly one of the two is given; tracks.json then names frames frame_000000.jpg ...), goes through FacePipeline (BlazeFace-back + Mobile-FaceNet) batch by
 batch with a tracking.StreamTracker behind the embedder: one fp_tracklets_step launch per batch assigns every face a track id
 (DESIGN section 7 "Tracklets").  A TrackBook collects, per track, its first and last frame, its hits and its best row (the
 highest detector confidence, or with --quality the sharpest crop); at the end <td>/tracks.json lists the tracks and
@@ -11,6 +12,9 @@ The thresholds default to the reference's numbers restated as cosines, unmeasure
 --motion STD_POS STD_VEL turns the tracker's constant-velocity prediction on (tracking.ConstantVelocity: the IoU gate takes the
 box a track is predicted at; no defaults, nothing has been measured).
 Build-defined: the reference labels faces frame by frame (face_tracker.py is that port).
+
+--video_out FILE writes every frame with its tracked faces' boxes and ` #<id>` captions (FacePipeline.annotate) to a
+Motion-JPEG AVI at the source's frame rate (25 where a folder or raw stream states none; below 2 GiB: OpenDML is out of scope).
 
 --mot_out FILE also writes every tracked face as a MOTChallenge row `frame,id,x,y,w,h,conf,-1,-1,-1` (frames 1-based in video
 order): a hypothesis file for eval/eval_face_tracker.py --tracks.  Nothing changes without it.
@@ -27,7 +31,13 @@ from ..tracking import BEST, IOU_MIN, TAU_FAR, TAU_NEAR, ConstantVelocity, Strea
 
 def get_parsed_args(argv=None):
     parser = argparse.ArgumentParser()
-    parser.add_argument('--frames', dest="frames_path", type=str, required=True, help="a folder of one video's frames as .jpg")
+    source = parser.add_mutually_exclusive_group(required=True)
+    source.add_argument('--frames', dest="frames_path", type=str, default=None, help="a folder of one video's frames as .jpg")
+    source.add_argument('--video', dest="video_path", type=str, default=None,
+                        help="a Motion-JPEG video file (AVI 1.0 or a raw .mjpeg stream) in place of --frames")
+    parser.add_argument('--video_out', type=str, default=None,
+                        help="write the frames with the tracked faces' boxes and ' #<id>' captions to this Motion-JPEG AVI "
+                             "(AVI 1.0: below 2 GiB, OpenDML is out of scope)")
     parser.add_argument('--td', '--target_data_path', dest="target_data_path", type=str, default="data/tracks")
     parser.add_argument('--model', default="synthetic", help="'synthetic' (seeded random weights); trained weights: use the API")
     parser.add_argument('--max_age', type=int, required=True,
@@ -62,17 +72,19 @@ def build_pipeline(args, dev, first_frames):
     return FacePipeline(det, emb, None, quality=True if args.quality else None, tracker=tracker), tracker
 
 
-def track_frames(pipe, paths, batch_size, jpeg_quality=95, mot_rows=None):
-    """-> (TrackBook, {(stream, id): JPEG bytes of the best row's crop}).  Frames of one size (a video's).  mot_rows: a list
-    that receives, per batch, (frame numbers, ids, xywh boxes, confidences) of the rows with a track id (numpy)."""
+def track_frames(pipe, paths, batch_size, jpeg_quality=95, mot_rows=None, writer=None):
+    """-> (TrackBook, {(stream, id): JPEG bytes of the best row's crop}).  Frames of one size (a video's).  paths: the sorted
+    .jpg files, or a VideoReader.  mot_rows: a list that receives, per batch, (frame numbers, ids, xywh boxes, confidences) of
+    the rows with a track id (numpy).  writer: a VideoWriter that receives every batch annotated (FacePipeline.annotate)."""
     import torch
-    from ..modules.utils.jpeg import encode_crops, imread_batch
+    from ..modules.utils.jpeg import encode_crops
+    from ..modules.utils.video import read_frames
     book, shots = TrackBook(), {}
     for lo in range(0, len(paths), int(batch_size)):
-        frames = imread_batch(paths[lo:lo + int(batch_size)], pipe.dev)
-        if not isinstance(frames, torch.Tensor):
-            raise ValueError("the frames of a video share one size")
+        frames = read_frames(paths, lo, lo + int(batch_size), pipe.dev)
         res = pipe.step(frames)
+        if writer is not None:
+            writer.write(pipe.annotate(frames, res))
         n, info = res["n_faces"], res["info"]
         score = res["quality"]["sharpness"] if "quality" in res else info[:, 5]
         sof = np.zeros((frames.shape[0],), np.int32)
@@ -123,16 +135,30 @@ def write_mot_rows(path, mot_rows):
 
 def main(argv=None):
     import torch
-    from ..modules.utils.jpeg import imread_batch
+    from ..modules.utils.video import VideoReader, VideoWriter, read_frames
     args = get_parsed_args(argv)
     print(args)
-    paths = frame_files(args.frames_path)
-    if not paths:
-        raise Exception(f"no .jpg under {args.frames_path}")
+    fps = None
+    if args.video_path is not None:
+        source = VideoReader(args.video_path)
+        if not len(source):
+            raise Exception(f"no frames in {args.video_path}")
+        paths, fps = [f"frame_{i:06d}.jpg" for i in range(len(source))], source.fps
+    else:
+        source = paths = frame_files(args.frames_path)
+        if not paths:
+            raise Exception(f"no .jpg under {args.frames_path}")
     dev = torch.device(args.device)
-    pipe, _ = build_pipeline(args, dev, imread_batch(paths[:8], dev))
+    pipe, _ = build_pipeline(args, dev, read_frames(source, 0, 8, dev))
     mot_rows = [] if args.mot_out else None
-    book, shots = track_frames(pipe, paths, args.batch_size, args.jpeg_quality, mot_rows=mot_rows)
+    writer = VideoWriter(args.video_out, fps if fps is not None else 25) if args.video_out else None
+    try:
+        book, shots = track_frames(pipe, source, args.batch_size, args.jpeg_quality, mot_rows=mot_rows, writer=writer)
+    finally:
+        if writer is not None:
+            writer.close()
+        if isinstance(source, VideoReader):
+            source.close()
     tracks = save_tracks(args.target_data_path, book, shots, paths)
     if args.mot_out:
         write_mot_rows(args.mot_out, mot_rows)

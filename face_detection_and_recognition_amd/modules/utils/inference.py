@@ -1,6 +1,7 @@
-"""Inference drivers (face_detection_and_extraction/modules/utils/inference.py).  The GUI loops
-(cv2.imshow / VideoCapture) are out of scope; ``inference_img`` keeps its signature, returns the
-post-processed detections and, instead of showing the drawn frame in a window, saves it when asked to (``save``)."""
+"""Inference drivers (face_detection_and_extraction/modules/utils/inference.py).  The GUI loops (cv2.imshow, the webcam's
+VideoCapture) are out of scope; ``inference_img`` keeps its signature, returns the post-processed detections and, instead of
+showing the drawn frame in a window, saves it when asked to (``save``).  ``inference_vid`` runs a Motion-JPEG video file
+(modules/utils/video.py) batch by batch and, instead of showing the frames, writes them annotated to an AVI when asked to."""
 import os
 from typing import Any, List, Optional, Tuple
 
@@ -76,3 +77,57 @@ def inference_img(net: Model, img, waitKey_val: int = 0, save: Optional[str] = N
     if save:
         save_annotated(save, image, post, anonymize, dev)
     return post
+
+
+def _batch_dets(net, frames, w, h):
+    """The net's rows for every frame of a decoded batch (device tensor, one size), each what net(frame) gives.  A net with a
+    batched path (predict_batch) takes the batch at once; a net whose rows are normalised by the frame (dets_fmt 2: the tiled
+    detector) gets its input_size set to the frames' (w, h) first, as its __call__ sets it per image.  Other nets go frame by
+    frame: on the device where they take device frames, else on host copies (YOLOV5FaceModel.__call__ takes numpy arrays)."""
+    if hasattr(net, "predict_batch"):
+        if getattr(net, "dets_fmt", None) == 2:
+            net.input_size = (w, h)
+        return net.predict_batch(frames)
+    if getattr(net, "accepts_device_frames", False):
+        return [net(f) for f in frames]
+    return [net(f) for f in frames.cpu().numpy()]
+
+
+def inference_vid(net: Model, vid: str, save: Optional[str] = None, batch: int = 64, anonymize: int = 0, entropy: str = "host",
+                  fps=None, reduce: int = 1) -> List[PostProcessedDetection]:
+    """inference.py:96-111 for a Motion-JPEG video file (AVI or a raw .mjpeg stream, modules/utils/video.py; every other codec
+    raises VideoUnsupported): one PostProcessedDetection per frame, what inference_img returns for that frame.  The file is
+    decoded `batch` frames at a time on the net's device (decode_video_batch: one launch sequence per chunk) and goes through
+    the net's batched path where it has one (predict_batch), else frame by frame (_batch_dets).  With `save`, the frames with
+    their detections drawn on (faces pixelated first with anonymize = a mosaic cell) are written to that path as a Motion-JPEG
+    AVI at the source's frame rate (VideoWriter; below 2 GiB).  fps: the rate to write where the source states none (a raw
+    stream).  reduce = 2 / 4 / 8: the frames are decoded at that fraction of their size, as load_image reads a file (AVI
+    carries no EXIF: there is no orientation to apply)."""
+    from .video import VideoReader, VideoWriter
+    if not hasattr(getattr(net, "net", None), "_device"):
+        raise NotImplementedError("inference_vid decodes the video on the net's device: a net on a HIP device is needed")
+    dev = net.net._device()
+    posts: List[PostProcessedDetection] = []
+    with VideoReader(vid) as reader:
+        rate = reader.fps if reader.fps is not None else fps
+        if save and rate is None:
+            raise ValueError(f"{vid} states no frame rate (a raw MJPEG stream): pass fps= to write {save}")
+        writer = VideoWriter(save, rate) if save else None
+        try:
+            for _, frames in reader.batches(batch, dev, entropy=entropy, reduce=reduce):
+                h, w = int(frames.shape[1]), int(frames.shape[2])
+                first = len(posts)
+                for dets in _batch_dets(net, frames, w, h):
+                    labels = None
+                    if net.returns_opt_labels:
+                        dets, labels = dets
+                    posts.append(get_dets_bboxes_confs_lmarks_areas(dets, (w, h), net.input_size, net.det_thres,
+                                                                    net.bbox_area_thres, labels))
+                if writer is not None:
+                    for i in range(frames.shape[0]):            # the decoded batch is this function's own: drawn on in place
+                        draw_bbox_on_image(frames[i], posts[first + i], anonymize=anonymize)
+                    writer.write(frames)
+        finally:
+            if writer is not None:
+                writer.close()
+    return posts

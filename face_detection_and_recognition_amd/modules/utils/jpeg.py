@@ -8,6 +8,11 @@ fde/face_extraction/extract_faces_from_dataset.py:393-420).
     entropy="device" (decode_jpeg / decode_jpeg_batch / imread_batch): the Huffman stage of sequential files runs on the
                                               device too (csrc/jpegdec.hip), one launch sequence per batch; files it does not take or
                                               leaves undecided go through the host path, bit-identical either way
+    decode_video_batch(datas, device)         the frames of a video (one size, one sampling) -> ONE (B, H, W, 3) tensor: the
+                                              device half in one launch sequence per chunk of frames (csrc/jpegbatch.hip), no
+                                              stacking copy; modules/utils/video.py reads and writes the Motion-JPEG containers.
+                                              Sequential files without Huffman tables (MJPEG frames) decode with the Annex K.3
+                                              tables, as libjpeg-turbo decodes them (all of the above)
     imread(path, device)                      cv2.imread for the device: JPEGs (sequential and progressive) through the above;
                                               what the decoder does not take (CMYK / arithmetic-coded JPEGs, PNG, ...) is
                                               decoded by Pillow on the host -- file I/O, not the hot path -- and uploaded
@@ -327,6 +332,174 @@ def imread_batch(paths, device, bgr=True, threads=8, entropy="host", reduce=1, o
     if frames and all(f.shape == frames[0].shape for f in frames):
         return torch.stack(frames)
     return frames
+
+
+# ---- frames of one geometry: a video ---------------------------------------------------------------------------------
+
+VIDEO_WS_BYTES = 64 << 20     # decode_video_batch: cap of one fp_jpeg_reconstruct_batch call's workspace (the sample planes of its
+                              # frames: 0.88 MB each at 576 x 1024 4:2:0, so 75 frames a call); a larger batch goes in chunks
+SAME_SIZE = "the frames of a video share one size"
+
+
+def _geometry(info):
+    return (info.width, info.height, info.ncomp, tuple(info.hs), tuple(info.vs))
+
+
+def reconstruct_batch(info, coefs_dev, coef_off, quant, device, out, bgr=True):
+    """The device half for len(coef_off) frames of info's geometry: fp_jpeg_reconstruct_batch.  coefs_dev: int16 on `device`;
+    coef_off: int64 elements into it, one per frame; quant: (n, 3, 64) uint16 -- both host numpy arrays, uploaded together in
+    one small copy.  out: contiguous (n, H, W, 3) u8 on `device`, written in place."""
+    lib = L.load()
+    n = len(coef_off)
+    assert out.is_contiguous() and tuple(out.shape) == (n, info.height, info.width, 3) and out.dtype == torch.uint8
+    # (pinned and asynchronous: a pageable copy would make the host wait for the coefficient copy queued in front of it, and
+    # with it the Huffman decoding of the next chunk)
+    side_host = torch.empty((n * 8 + n * 384,), dtype=torch.uint8, pin_memory=True)
+    side = side_host.numpy()
+    side[:n * 8] = np.ascontiguousarray(coef_off, dtype=np.int64).view(np.uint8)
+    side[n * 8:] = np.ascontiguousarray(quant, dtype=np.uint16).reshape(-1).view(np.uint8)
+    side_dev = side_host.to(device, non_blocking=True)
+    ws_bytes = int(lib.fp_jpeg_batch_workspace_bytes(C.byref(info), n))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
+    L.check(lib.fp_jpeg_reconstruct_batch(L.ptr(coefs_dev), side_dev.data_ptr(), side_dev.data_ptr() + n * 8, C.byref(info), n,
+                                          L.ptr(ws), ws_bytes, L.ptr(out), 1 if bgr else 0, L.current_stream(device)),
+            "fp_jpeg_reconstruct_batch")
+    return out
+
+
+def _quant_rows(infos):
+    return np.stack([np.frombuffer(i, dtype=np.uint16, count=192, offset=L.FpJpegInfo.quant.offset) for i in infos]).reshape(-1, 3, 64)
+
+
+def _host_submit(datas, info0, pool):
+    """Queues a chunk on the pool: every frame's headers are parsed and its scans Huffman-decoded into its slice of ONE pinned
+    arena.  The file's bytes go to the C functions as they are (no copy).  -> (arena, futures of (status, function, info))."""
+    lib = L.load()
+    nc, geo = int(info0.n_coefs), _geometry(info0)
+    arena = torch.empty((len(datas) * nc,), dtype=torch.int16, pin_memory=True)
+
+    def one(j):
+        base = arena.data_ptr()                       # (the closure holds the arena: it lives as long as a task may write to it)
+        d = datas[j]
+        info = L.FpJpegInfo()
+        rc = lib.fp_jpeg_parse(d, len(d), C.byref(info))
+        if rc:
+            return rc, "fp_jpeg_parse", None
+        if _geometry(info) != geo:
+            return None, None, None
+        return lib.fp_jpeg_entropy_decode(d, len(d), C.byref(info), C.c_void_p(base + 2 * j * nc)), "fp_jpeg_entropy_decode", info
+    return arena, [pool.submit(one, j) for j in range(len(datas))]
+
+
+def _host_finish(job, device):
+    """Waits for a chunk queued by _host_submit -- in order: the first frame that is damaged, unsupported or of another
+    geometry raises, as decode_jpeg_batch would --, then one host-to-device copy -> (device arena, the frames' infos)."""
+    arena, futures = job
+    infos = []
+    for f in futures:
+        rc, what, info = f.result()
+        if rc is None:
+            raise ValueError(SAME_SIZE)
+        if rc == FP_ERR_UNSUPPORTED and what == "fp_jpeg_parse":
+            raise JpegUnsupported("a JPEG this decoder does not take (arithmetic-coded / lossless / 12-bit / CMYK / unusual sampling)")
+        L.check(rc, what)
+        infos.append(info)
+    return arena.to(device, non_blocking=True), infos
+
+
+def _spans(n, step):
+    return [(s, min(n, s + step)) for s in range(0, n, step)]
+
+
+def _video_host(datas, info0, device, bgr, out, step, pool):
+    """entropy="host": chunk after chunk; the pool stays busy, because the next two chunks are queued before this one is
+    waited for: their Huffman decoding runs under this chunk's copy and kernels, which are asynchronous."""
+    nc = int(info0.n_coefs)
+    spans, jobs = _spans(len(datas), step), {}
+    for k, (s, e) in enumerate(spans):
+        for a in range(k, min(len(spans), k + 3)):
+            if a not in jobs:
+                jobs[a] = _host_submit(datas[spans[a][0]:spans[a][1]], info0, pool)
+        coefs, infos = _host_finish(jobs.pop(k), device)
+        reconstruct_batch(info0, coefs, np.arange(e - s, dtype=np.int64) * nc, _quant_rows(infos), device, out[s:e], bgr)
+
+
+def _video_device(datas, info0, device, bgr, out, step, pool):
+    """entropy="device": device_entropy_decode over the whole batch, as decode_jpeg_batch runs it (its fixed costs and its
+    synchronisation once); the frames it leaves undecided are Huffman-decoded on the host into a second arena.  Reconstruction
+    in chunks under the workspace cap; a chunk whose frames lie in both arenas is cut where the arena changes, so that every
+    fp_jpeg_reconstruct_batch call addresses one allocation."""
+    dev = device_entropy_decode(datas, device)
+    rest = [j for j, r in enumerate(dev) if r is None]
+    job = _host_submit([datas[j] for j in rest], info0, pool) if rest else None
+    geo, nc = _geometry(info0), int(info0.n_coefs)
+    bases = {}                                        # "device": the decoder's arena, "host": the second one
+    arena, offs, infos = [None] * len(datas), np.zeros(len(datas), np.int64), [None] * len(datas)
+    for j, r in enumerate(dev):                       # in order, with the host's frames: the first bad frame raises
+        if isinstance(r, int):
+            L.check(r, "fp_jpeg_entropy_decode")      # what the host path raises for this file
+        elif r is not None:
+            if _geometry(r[0]) != geo:
+                raise ValueError(SAME_SIZE)
+            bases.setdefault("device", r[1]._base if r[1]._base is not None else r[1])     # r[1] is a view of the arena
+            infos[j], arena[j], offs[j] = r[0], "device", r[1].storage_offset()
+        elif job is not None:                         # the host's frames are waited for at the first of them
+            host, host_infos = _host_finish(job, device)
+            job = None
+            bases["host"] = host
+            for k, i in enumerate(rest):
+                infos[i], arena[i], offs[i] = host_infos[k], "host", k * nc
+    quant = _quant_rows(infos)
+    for s, e in _spans(len(datas), step):
+        a = s
+        while a < e:
+            b = a + 1
+            while b < e and arena[b] == arena[a]:
+                b += 1
+            reconstruct_batch(info0, bases[arena[a]], offs[a:b], quant[a:b], device, out[a:b], bgr)
+            a = b
+
+
+def decode_video_batch(datas, device, bgr=True, threads=8, entropy="host", reduce=1, out=None, max_ws_bytes=None):
+    """The frames of a video -- JPEG byte strings that share width, height, components and sampling -> ONE (B, H, W, 3) u8 tensor
+    on `device`, reconstructed by fp_jpeg_reconstruct_batch (csrc/jpegbatch.hip): one launch sequence per chunk of frames and no
+    stacking copy, byte-identical to decode_jpeg(d, orientation=False) of each frame.  The headers are parsed on the thread pool
+    (the first frame's in front of it: it sizes the arena); a frame that disagrees with the first raises
+    ValueError("the frames of a video share one size").  entropy="host": chunk by chunk, the Huffman decoding on the pool into
+    one pinned arena per chunk, one copy to the device each.  entropy="device": device_entropy_decode over the batch, the frames
+    it leaves undecided through the host path.  The reconstruction is cut into chunks whose workspace stays under max_ws_bytes
+    (VIDEO_WS_BYTES = 64 MiB by default; a single frame over the cap goes alone).  The first damaged or unsupported frame in
+    order raises what decode_jpeg_batch raises for it.  reduce = 2 / 4 / 8: frame by frame through decode_jpeg_batch, stacked
+    (there is no batched kernel for the reduced sizes).  No EXIF orientation: a video's frames are taken as stored.  out: a
+    (B, H', W', 3) u8 tensor to fill."""
+    device = torch.device(device)
+    _check_entropy(entropy)
+    _check_reduce(reduce)
+    if device.type != "cuda":
+        raise L.FacepathError("decode_video_batch reconstructs on a HIP device; there is no CPU path")
+    datas = [d if isinstance(d, bytes) else bytes(d) for d in datas]
+    if not datas:
+        raise ValueError("decode_video_batch: no frames")
+    cap = VIDEO_WS_BYTES if max_ws_bytes is None else int(max_ws_bytes)
+    if cap < 1:
+        raise ValueError(f"max_ws_bytes must be positive, not {max_ws_bytes!r}")
+    info0 = parse(datas[0])[0]
+    oh, ow = scaled_size(info0, reduce, 1)
+    if out is None:
+        out = torch.empty((len(datas), oh, ow, 3), dtype=torch.uint8, device=device)
+    if not (out.is_contiguous() and tuple(out.shape) == (len(datas), oh, ow, 3) and out.dtype == torch.uint8 and out.device == device):
+        raise ValueError(f"out must be a contiguous ({len(datas)}, {oh}, {ow}, 3) uint8 tensor on {device}")
+    if reduce != 1:
+        frames = decode_jpeg_batch(datas, device, bgr, threads, entropy, reduce, orientation=False)
+        if any(f.shape != out.shape[1:] for f in frames):
+            raise ValueError(SAME_SIZE)
+        for i, f in enumerate(frames):
+            out[i].copy_(f)
+        return out
+    step = max(1, cap // max(1, int(L.load().fp_jpeg_workspace_bytes(C.byref(info0)))))
+    with ThreadPoolExecutor(max_workers=max(1, min(threads, len(datas)))) as pool:
+        (_video_host if entropy == "host" else _video_device)(datas, info0, device, bgr, out, step, pool)
+    return out
 
 
 # ---- encode ----------------------------------------------------------------------------------------------------------

@@ -50,7 +50,8 @@ def add_read_args(parser):
                         help="Decode JPEGs at 1/2, 1/4 or 1/8 size out of smaller inverse DCTs (cv2's IMREAD_REDUCED_COLOR_2 / _4 / "
                              "_8): a sixteenth of the frame bytes at 4. (default: 1)")
     parser.add_argument("--ignore_orientation", dest="ignore_orientation", action="store_true", default=argparse.SUPPRESS,
-                        help="Do not turn the image upright by its EXIF Orientation tag (cv2's IMREAD_IGNORE_ORIENTATION).")
+                        help="Do not turn the image upright by its EXIF Orientation tag (cv2's IMREAD_IGNORE_ORIENTATION).  A video's "
+                             "frames are taken as stored either way (AVI carries no EXIF); --reduce applies to them too.")
     return parser
 
 

@@ -889,6 +889,26 @@ int fp_jpeg_reconstruct(const int16_t* coefs, const fp_jpeg_info* info, uint8_t*
                         int bgr, void* stream);
 
 /*
+ * Frames of ONE geometry in one launch sequence (added within ABI 15: functions only; csrc/jpegbatch.hip) -- the frames of a
+ * Motion-JPEG video.  A SEQUENTIAL file that defines no Huffman table decodes with the tables of ITU T.81 Annex K.3 in slots 0
+ * (luminance) and 1 (chrominance) of both classes, as libjpeg-turbo's std_huff_tables installs them; DHT segments overwrite
+ * them, slots 2 and 3 stay absent (fp_jpeg_parse, fp_jpeg_entropy_decode, fp_jpeg_scan_prepare).  A progressive file gets no
+ * presets, as in libjpeg-turbo's jdphuff.c: a scan whose table no DHT defined is FP_ERR_INVALID_ARG.
+ * DEVICE.  fp_jpeg_reconstruct_batch: fp_jpeg_reconstruct for n_frames frames that all have info's width, height, components
+ * and sampling; info->quant is NOT read.  coefs: device; frame f's coefficients stand at coefs + coef_off[f] (int16 elements,
+ * laid out by info->coef_off as for one frame) -- the host path's arena and the device entropy decoder's padded arena both
+ * fit.  coef_off: DEVICE, n_frames int64.  quant: DEVICE, [n_frames][3][64] uint16, natural order: frame f's tables (rows
+ * behind ncomp are not read).  workspace: device, 8-byte aligned, fp_jpeg_batch_workspace_bytes (= n_frames x
+ * fp_jpeg_workspace_bytes).  out: device u8 [n_frames][height][width][3].  Two launches whatever n_frames is, 64-bit indices;
+ * out[f] equals fp_jpeg_reconstruct's frame byte for byte (the same device functions, csrc/jpegrecon.h).  The coefficient
+ * offsets live on the device and are not checked: the caller vouches that coef_off[f] + info->n_coefs stays inside coefs.
+ * FP_ERR_UNSUPPORTED: more than 2^31 - 1 workgroups in one launch (split the batch).  Full size, no orientation.
+ */
+size_t fp_jpeg_batch_workspace_bytes(const fp_jpeg_info* info, int n_frames);
+int fp_jpeg_reconstruct_batch(const int16_t* coefs, const int64_t* coef_off, const uint16_t* quant, const fp_jpeg_info* info,
+                              int n_frames, uint8_t* workspace, size_t ws_bytes, uint8_t* out, int bgr, void* stream);
+
+/*
  * EXIF orientation and reduced-size output (added within ABI 15: functions only, no struct changes).
  * HOST.  fp_jpeg_exif_orientation: the Orientation tag (0x0112, type SHORT, IFD0) of the first APP1 segment that starts
  * with "Exif\0\0" in front of the first scan: 1 .. 8; 1 for no tag, a value outside 1 .. 8, or a truncated or inconsistent

@@ -1,6 +1,8 @@
 """Case table, float64 references, write footprints and the product census for the generic fp32 plan ops of csrc/conv.hip
 (conv_igemm_kernel, dwconv_kernel, dwconv3_row_kernel, maxpool_kernel, maxpool_generic_kernel, upsample2x_kernel, copy_kernel,
-copy4_kernel, l2norm_kernel).  tests/test_generic_ops.py runs every case as a one-op plan.
+copy4_kernel, l2norm_kernel).  tests/test_generic_ops.py runs every case as a one-op plan.  The kernels that take an FP_OP_CONV
+away from conv_igemm_kernel have tables of their own: the split-bf16 convs tests/split_conv_cases.py, the stems (stem_conv_kernel,
+stemdw_kernel) and pws_kernel tests/stem_mfn_op_cases.py, which also holds the Mobile-FaceNet DWPW forms and the fp32 dwblock_kernel.
 
 * A Case says how to build the op with PlanBuilder (shapes, channel slices, image strides, flags), the kernel instance the
   launcher must pick for it and what the data look like.  build() emits the plan, inputs() draws the seeded data, reference()

@@ -8,9 +8,10 @@ outside the generic fp32 ops, the split-bf16 convs and conv3_kernel:
   FP_OP_DWPW + FP_OPF_SPLIT3    -> dwpwx6_kernel<4|8, 4, 1|2>              (csrc/dwpwx6.hip; <4, ...> with DWPW_X6_COUT = 64)
   FP_OP_DWPW without the flag   -> dwpw_kernel<2|4, 1|2|4, 1|2>, act2 = SiLU, with and without FP_RES_SHUFFLE2
 
-tests/test_yolo_ops.py runs every case as a one-op plan.  Out of scope here: the Mobile-FaceNet-only DWPW forms (output PReLU,
-dwpw_persist_kernel, dwpw_wp_kernel), pws_kernel and the fp32 dwblock_kernel; conv3_kernel (test_conv3_lds_image_kernel_vs_torch);
-the stems of csrc/stem.hip / stemdw.hip; the three head ops (EMBED_HEAD, POOL_LRN, CLS_HEAD).
+tests/test_yolo_ops.py runs every case as a one-op plan.  Out of scope here: the Mobile-FaceNet-only DWPW forms (act2 none, output
+PReLU, dwpw_persist_kernel, dwpw_wp_kernel), pws_kernel, the fp32 dwblock_kernel and the stems of csrc/stem.hip / stemdw.hip, which
+tests/stem_mfn_op_cases.py + tests/test_stem_mfn_ops.py pin the same way; conv3_kernel (test_conv3_lds_image_kernel_vs_torch); the
+three head ops (EMBED_HEAD, POOL_LRN, CLS_HEAD: float64 tests in test_facenet.py / test_age_gender.py).
 
 * A Case says how to build the op with PlanBuilder, the instance the launcher must pick and what the views look like.
   build() emits the plan, params() / inputs() draw the seeded data (He-scaled weights, affine scales in [0.5, 1.5], biases

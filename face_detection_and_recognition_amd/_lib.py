@@ -130,6 +130,7 @@ TRACK_SLOTS, TRACK_MAX_DETS, TRACK_MAX_DIM, TRACK_MAX_ROWS = 64, 64, 1024, 1 << 
 TRACK_SLOT_INTS, TRACK_SLOT_FLOATS = 5, 10                                # columns of fp_track_state.slot_i / slot_f
 TRACK_MOTION_FLOATS = 20                  # FP_TRACK_MOTION_FLOATS: x, v, p00, p01, p11 of cx, cy, w, h per slot of `motion`
 TRACK_NEW, TRACK_BEST, TRACK_DEAD_ROW, TRACK_FULL, TRACK_NO_STREAM, TRACK_OVER = 1, 2, 4, 8, 16, 32   # track_flags bits
+TRACK_LOST, TRACK_REVIVED = 64, 64        # FP_TRACK_LOST: parked tracks per stream of fp_track_lost; FP_TRACK_REVIVED: a track_flags bit
 MOT_MAX_ROWS, MOT_STATE_ROWS = 64, 6   # FP_MOT_MAX_ROWS: rows of one frame fp_mot_match takes; int32 rows of its per-id state
 HOTA_MAX_ALPHAS = 32                   # FP_HOTA_MAX_ALPHAS: localisation thresholds fp_hota_match takes
 
@@ -137,6 +138,12 @@ HOTA_MAX_ALPHAS = 32                   # FP_HOTA_MAX_ALPHAS: localisation thresh
 class FpTrackState(C.Structure):
     """Mirror of struct fp_track_state: the five state arrays of fp_tracklets_step (include/facepath.h "Tracklets")."""
     _fields_ = [("hdr", C.c_void_p), ("slot_i", C.c_void_p), ("slot_f", C.c_void_p), ("emb", C.c_void_p), ("best_emb", C.c_void_p)]
+
+
+class FpTrackLost(C.Structure):
+    """Mirror of struct fp_track_lost: the five pool arrays of fp_tracklets_step_reid ("Tracklets: re-identification")."""
+    _fields_ = [("lost_hdr", C.c_void_p), ("lost_i", C.c_void_p), ("lost_f", C.c_void_p), ("lost_emb", C.c_void_p),
+                ("lost_best_emb", C.c_void_p)]
 
 
 JPEG_DECODE_ON_HOST = 1          # fp_jpeg_entropy_decode_device status: decode this image with fp_jpeg_entropy_decode
@@ -267,6 +274,10 @@ SIGNATURES = {
                                       _P, _F, _F, _P, _P]),
     "fp_tracklets_step_motion_emulate": (_I, [C.POINTER(FpTrackState), _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _F, _F, _F, _P, _P,
                                               _P, _P, _P, _F, _F, _P]),
+    "fp_tracklets_step_reid": (_I, [C.POINTER(FpTrackState), C.POINTER(FpTrackLost), _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _F, _F,
+                                    _F, _P, _P, _P, _P, _F, _I, _P, _F, _F, _P, _P]),
+    "fp_tracklets_step_reid_emulate": (_I, [C.POINTER(FpTrackState), C.POINTER(FpTrackLost), _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I,
+                                            _F, _F, _F, _P, _P, _P, _P, _F, _I, _P, _F, _F, _P]),
     "fp_mot_match_workspace": (_SZ, [_I64, _I64]),
     "fp_mot_match": (_I, [_P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I64, _D, _P, _P, _P, _P, _P, _SZ, _P]),
     "fp_mot_match_emulate": (_I, [_P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I64, _D, _P, _P, _P, _P, _P,

@@ -15,27 +15,36 @@
 //    No global atomics, no scratch, no host synchronisation: two runs are bit-identical.
 // 2. fp_tracklets_step_emulate: the same __host__ __device__ decision code (liveness, dot product in the device's order, IoU,
 //    admissibility, key) run serially on host memory, std::sort for the keys (the order is total).
-// 3. fp_tracklets_step_motion / _emulate: the same kernel as tracklets_kernel<true> ("Tracklets: motion prediction" in
+// 3. fp_tracklets_step_motion / _emulate: the same kernel as tracklets_kernel<true, *> ("Tracklets: motion prediction" in
 //    include/facepath.h).  The slot's four constant-velocity filters (20 floats) and the predicted boxes sit in LDS beside the
 //    slot table; step 1b predicts one (slot, coordinate) per thread on the first 256 threads, the pair phase takes its IoU with
-//    the predicted box, wave 0 updates / opens the filters where it rewrites the slots.  tracklets_kernel<false> is the kernel
+//    the predicted box, wave 0 updates / opens the filters where it rewrites the slots.  tracklets_kernel<false, *> is the kernel
 //    of 1: no motion array is read, nothing of it is compiled in.
+// 4. fp_tracklets_step_reid / _emulate: tracklets_kernel<MOTION, true> ("Tracklets: re-identification" in include/facepath.h).
+//    The stream's pool of parked tracks (FP_TRACK_LOST slot rows, ints and floats) sits in LDS beside the slot table, their
+//    embeddings stay in global memory.  Every wave finds the expiring slots by a ballot of its own (64 slots, 64 lanes), wave 0
+//    moves their rows into the ring, the whole workgroup copies their embeddings.  Step 3b (the detections the walk left
+//    unmatched x the parked tracks) reuses key[], the sort and the walk, and runs only in a frame that has both: a frame with
+//    an empty pool pays one workgroup-uniform test, one with parked tracks and no unmatched detection one barrier more.
+//    tracklets_kernel<*, false> are the kernels of 1 and 3: nothing of the pool is read or compiled in.
 #include <limits.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
 
 namespace {
 
-constexpr int SLOTS = FP_TRACK_SLOTS, MAXD = FP_TRACK_MAX_DETS;
+constexpr int SLOTS = FP_TRACK_SLOTS, MAXD = FP_TRACK_MAX_DETS, LOST = FP_TRACK_LOST;
 constexpr int TPB = 512, NW = TPB / FP_WAVE;
 constexpr int GL = 16, NG = TPB / GL;   // lanes per pair, pairs in flight
 constexpr int MAXCH = 1024;             // row chunks whose frame range is kept in LDS
 constexpr int NI = FP_TRACK_SLOT_INTS, NF = FP_TRACK_SLOT_FLOATS, MF = FP_TRACK_MOTION_FLOATS;
 constexpr unsigned long long KEY_NONE = ~0ull;
 static_assert(SLOTS == 64 && MAXD == 64, "one 64-bit mask of tracks and one of detections; slot and position are key bytes");
+static_assert(LOST == 64, "one 64-bit mask of parked tracks, one lane of a wave each; the entry is a key byte");
 
 // slot_i columns / slot_f columns
 enum { I_ID = 0, I_FIRST = 1, I_LAST = 2, I_HITS = 3, I_BEST_CLOCK = 4 };
@@ -68,6 +77,20 @@ struct TrackArgs {
   float* motion;        // [S][SLOTS][MF]; null without motion prediction
   float std_pos, std_vel;
   float* o_pred;        // [n][4]
+};
+
+// re-identification: the pool and its parameters.  The kernels with a pool take ReidArgs, those without it TrackArgs as ever.
+struct LostArgs {
+  int* lhdr;            // [S][2] ring head, spare
+  int* li;              // [S][LOST][NI]
+  float* lf;            // [S][LOST][NF]
+  float* lemb;          // [S][LOST][D]
+  float* lbest;         // [S][LOST][D]
+  float tau_reid;
+  int lost_age;
+};
+struct ReidArgs : TrackArgs {
+  LostArgs l;
 };
 
 // ---------------------------------------------------------------------------------------- the decision code, host and device
@@ -219,15 +242,87 @@ __host__ __device__ __forceinline__ void tk_pred(const TrackArgs& p, long row, c
   for (int k = 0; k < 4; ++k) p.o_pred[row * 4 + k] = pb ? pb[k] : 0.f;
 }
 
+// ---------------------------------------------------------------------------- re-identification, host and device
+// a parked track takes part in step 3b
+__host__ __device__ __forceinline__ bool tk_parked(const int* li, const float* lf) { return li[I_ID] != 0 && tk_live(lf[F_INV]); }
+
+// A revived detection's slot continues the parked track: the entry's rows become the slot's, the entry is emptied, the slot is
+// then rewritten as by a match.  Returns the row's flags.
+__host__ __device__ __forceinline__ int tk_revive_slot(const TrackArgs& p, int* si, float* sf, int* li, const float* lf, long row,
+                                                       float inv, int clock) {
+  for (int k = 0; k < NI; ++k) si[k] = li[k];
+  for (int k = 0; k < NF; ++k) sf[k] = lf[k];
+  li[I_ID] = 0;
+  return tk_update_slot(p, si, sf, row, inv, false, clock, 0) | FP_TRACK_REVIVED;
+}
+
 // ------------------------------------------------------------------------------------------------------------ the kernel
-template <bool MOTION>
-__global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
+// bitonic sort of key[0, n_sort), n_sort a power of two, by the whole workgroup.  Returns the keys in front of the first KEY_NONE.
+__device__ __forceinline__ int tk_sort(unsigned long long* key, int n_sort, int tid) {
+  for (int k = 2; k <= n_sort; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < (n_sort >> 1); t += TPB) {
+        const int i = 2 * t - (t & (j - 1)), r = i + j;
+        const unsigned long long a = key[i], b = key[r];
+        if ((a > b) == ((i & k) == 0)) {
+          key[i] = b;
+          key[r] = a;
+        }
+      }
+      __syncthreads();
+    }
+  int n_valid = 0;
+  for (int step = n_sort; step > 0; step >>= 1)
+    if (n_valid + step <= n_sort && key[n_valid + step - 1] != KEY_NONE) n_valid += step;
+  return n_valid;
+}
+
+// One wave walks the sorted keys 64 at a time with a ballot per taken pair (two 64-bit masks: tracks and detections already
+// taken; at most `most` pairs).  Returns, on the lane that stands for a taken detection's position, the track it took; else -1.
+__device__ __forceinline__ int tk_walk(const unsigned long long* key, int n_valid, int most, int lane) {
+  int mine = -1;
+  unsigned long long t_taken = 0ull, d_taken = 0ull;
+  int taken = 0;
+  for (int i0 = 0; i0 < n_valid && taken < most; i0 += FP_WAVE) {
+    const int i = i0 + lane;
+    const bool have = i < n_valid;
+    const unsigned long long kk = have ? key[i] : 0ull;
+    const int k_slot = tk_key_slot(kk), k_pos = tk_key_pos(kk);
+    bool alive = have && !((t_taken >> k_slot) & 1ull) && !((d_taken >> k_pos) & 1ull);
+    unsigned long long live = __ballot(alive);
+    while (live) {
+      const int l = __ffsll((long long)live) - 1;   // the first pair of the batch still free is taken
+      const int w_slot = __shfl(k_slot, l), w_pos = __shfl(k_pos, l);
+      t_taken |= 1ull << w_slot;
+      d_taken |= 1ull << w_pos;
+      ++taken;
+      if (lane == w_pos) mine = w_slot;
+      if (alive && (k_slot == w_slot || k_pos == w_pos)) alive = false;
+      live = __ballot(alive);
+    }
+  }
+  return mine;
+}
+
+// the r-th set bit of m (r < popcount)
+__device__ __forceinline__ int tk_nth_bit(unsigned long long m, int r) {
+  for (int k = 0; k < r; ++k) m &= m - 1ull;
+  return __ffsll((long long)m) - 1;
+}
+
+template <bool MOTION, bool REID>
+__global__ __launch_bounds__(TPB) void tracklets_kernel(std::conditional_t<REID, ReidArgs, TrackArgs> a) {
+  const TrackArgs& p = a;
   __shared__ unsigned long long key[SLOTS * MAXD];   // 32 KB
   __shared__ int cmin[MAXCH], cmax[MAXCH];
   __shared__ int s_i[SLOTS][NI];
   __shared__ float s_f[SLOTS][NF];
-  __shared__ float s_m[MOTION ? SLOTS : 1][MF];      // <true> only: the filters and the predicted boxes
+  __shared__ float s_m[MOTION ? SLOTS : 1][MF];      // <true, *> only: the filters and the predicted boxes
   __shared__ float s_pb[MOTION ? SLOTS : 1][4];
+  __shared__ int l_i[REID ? LOST : 1][NI];           // <*, true> only: the parked tracks' rows
+  __shared__ float l_f[REID ? LOST : 1][NF];
+  __shared__ int le[REID ? LOST : 1], lu[REID ? MAXD : 1], det_ent[REID ? MAXD : 1];   // parked entries / unmatched positions, ascending
+  __shared__ int s_nU;
   __shared__ int det_row[MAXD], det_slot[MAXD], det_flag[MAXD];
   __shared__ float det_inv[MAXD];                    // 0 = a dead row
   __shared__ int lt[SLOTS], ld[MAXD];                // the live slots / the positions of the live detections, ascending
@@ -246,6 +341,10 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
   }
   for (int i = tid; i < SLOTS * NI; i += TPB) (&s_i[0][0])[i] = p.si[(long)s * SLOTS * NI + i];
   for (int i = tid; i < SLOTS * NF; i += TPB) (&s_f[0][0])[i] = p.sf[(long)s * SLOTS * NF + i];
+  if constexpr (REID) {
+    for (int i = tid; i < LOST * NI; i += TPB) (&l_i[0][0])[i] = a.l.li[(long)s * LOST * NI + i];
+    for (int i = tid; i < LOST * NF; i += TPB) (&l_f[0][0])[i] = a.l.lf[(long)s * LOST * NF + i];
+  }
   __syncthreads();
 
   // first pass over the rows: frame range of every chunk; the untracked rows of the groups this workgroup owns
@@ -267,6 +366,14 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
   float* semb = p.semb + (long)s * SLOTS * D;
   float* sbest = p.sbest + (long)s * SLOTS * D;
   bool owned = false;   // MOTION: the stream has a frame in this step, its filters are in s_m
+  int head = 0;         // REID: where the ring parks next, kept by every thread
+  float* lemb = nullptr;
+  float* lbest = nullptr;
+  if constexpr (REID) {
+    head = a.l.lhdr[2 * s];   // taken modulo LOST wherever it is used
+    lemb = a.l.lemb + (long)s * LOST * D;
+    lbest = a.l.lbest + (long)s * LOST * D;
+  }
 
   for (int f0 = 0; f0 < p.B; f0 += TPB) {
     const bool mine = f0 + tid < p.B && p.sof[f0 + tid] == s;
@@ -288,6 +395,8 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
 
         // ---- 1. the clock, expiry
         clock += 1;
+        unsigned long long exm = 0ull;   // REID: the slots that expire in this frame, found by every wave for itself
+        if constexpr (REID) exm = __ballot(s_i[lane][I_ID] != 0 && clock - s_i[lane][I_LAST] > p.max_age);
         // ---- 1b. thread 4 * slot + c moves coordinate c of a slot that survives the expiry; the scale is read first
         const int m_slot = tid >> 2, m_c = tid & 3;
         float m_H = 1.f;
@@ -299,7 +408,29 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
           }
           __syncthreads();
         }
-        if (tid < SLOTS && s_i[tid][I_ID] != 0 && clock - s_i[tid][I_LAST] > p.max_age) s_i[tid][I_ID] = 0;
+        if constexpr (REID) {
+          // ---- 1a. the pool forgets; 1. the expiring slots are parked: the r-th of them, ascending, in entry (head + r) % LOST
+          if (tid < LOST && l_i[tid][I_ID] != 0 && clock - l_i[tid][I_LAST] > a.l.lost_age) l_i[tid][I_ID] = 0;
+          if (exm != 0ull) {   // every wave holds the same mask
+            if constexpr (!MOTION) __syncthreads();   // every wave has read the slots (MOTION: the barrier above)
+            const int n_ex = __popcll(exm);
+            if (wave == 0 && ((exm >> lane) & 1ull)) {
+              const int e = (head + __popcll(exm & lane_lt)) & (LOST - 1);
+              for (int k = 0; k < NI; ++k) l_i[e][k] = s_i[lane][k];
+              for (int k = 0; k < NF; ++k) l_f[e][k] = s_f[lane][k];
+              s_i[lane][I_ID] = 0;
+            }
+            for (int idx = tid; idx < n_ex * D4; idx += TPB) {
+              const int r = idx / D4, k = idx % D4, slot = tk_nth_bit(exm, r), e = (head + r) & (LOST - 1);
+              ((f32x4*)(lemb + (long)e * D))[k] = ((const f32x4*)(semb + (long)slot * D))[k];
+              ((f32x4*)(lbest + (long)e * D))[k] = ((const f32x4*)(sbest + (long)slot * D))[k];
+            }
+            head = (head + n_ex) & (LOST - 1);
+            __threadfence_block();   // the barriers of step 2 stand between these copies and step 3b
+          }
+        } else {
+          if (tid < SLOTS && s_i[tid][I_ID] != 0 && clock - s_i[tid][I_LAST] > p.max_age) s_i[tid][I_ID] = 0;
+        }
         if constexpr (MOTION) {
           if (tid < 4 * SLOTS) {   // whole waves: the centre lanes (c < 2) fetch their extent from lane + 2
             const float x = m_live ? tk_motion_predict(p, &s_m[m_slot][m_c * MC], m_H) : 0.f;
@@ -343,6 +474,8 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
         const int nd = min(base, MAXD);
         __syncthreads();
         if (nd == 0) continue;
+        unsigned long long pm = 0ull;   // REID: the parked tracks that can pair, found by every wave for itself
+        if constexpr (REID) pm = __ballot(tk_parked(l_i[lane], l_f[lane]));
 
         // ---- live slots and live detections, ascending
         if (wave == 0) {
@@ -357,6 +490,7 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
           if (lane == 0) s_nD = __popcll(dm);
           det_slot[lane] = -1;
           det_flag[lane] = 0;
+          if constexpr (REID) det_ent[lane] = -1;
         }
         __syncthreads();
         const int nT = s_nT, nD = s_nD, np = nT * nD;
@@ -401,28 +535,76 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
             if (n_valid + step <= n_sort && key[n_valid + step - 1] != KEY_NONE) n_valid += step;
         }
 
+        // ---- 3 (walk) with a pool: wave 0 alone, then 3b by everybody.  (Steps 3 to 5 without a pool stand below as they always
+        // did, sort and walk written out: moving them into the functions of 3b changed the schedule of tracklets_kernel<*, false>.)
+        int walked = -1, my_ent = -1;
+        if constexpr (REID)
+          if (wave == 0) walked = tk_walk(key, n_valid, min(nT, nD), lane);
+
+        // ---- 3b. the live detections the walk left unmatched x the parked tracks: cosine alone, the same key, sort and walk
+        if constexpr (REID) {
+          if (pm != 0ull) {   // workgroup-uniform: a frame with an empty pool goes straight on
+            if (wave == 0) {
+              const bool un = lane < nd && det_inv[lane] > 0.f && walked < 0;
+              const unsigned long long um = __ballot(un);
+              if (un) lu[__popcll(um & lane_lt)] = lane;
+              if (lane == 0) s_nU = __popcll(um);
+            } else if (wave == 1) {
+              if ((pm >> lane) & 1ull) le[__popcll(pm & lane_lt)] = lane;
+            }
+            __syncthreads();   // wave 0 is through with the keys of step 3
+            const int nU = s_nU, nE = __popcll(pm), nq = nE * nU;
+            if (nq > 0) {
+              int n_sort = 2;
+              while (n_sort < nq) n_sort <<= 1;
+              const int grp = tid / GL, gl = tid % GL;
+              for (int q0 = 0; q0 < nq; q0 += NG) {
+                const int q = min(q0 + grp, nq - 1);
+                const int ent = le[q / nU], pos = lu[q % nU];
+                float v = tk_partial(lemb + (long)ent * D, p.emb + (long)det_row[pos] * D, D, gl);
+                v += __shfl_xor(v, 8);
+                v += __shfl_xor(v, 4);
+                v += __shfl_xor(v, 2);
+                v += __shfl_xor(v, 1);
+                if (gl == 0 && q0 + grp < nq) {
+                  const float c = tk_cos(v, l_f[ent][F_INV], det_inv[pos]);
+                  key[q] = c > a.l.tau_reid ? tk_key(c, ent, pos) : KEY_NONE;
+                }
+              }
+              for (int i = nq + tid; i < n_sort; i += TPB) key[i] = KEY_NONE;
+              __syncthreads();
+              const int n_valid_b = tk_sort(key, n_sort, tid);
+              if (wave == 0) my_ent = tk_walk(key, n_valid_b, min(nE, nU), lane);
+            }
+          }
+        }
+
         // ---- 3 (walk), 4, 5: wave 0; lane j stands for the detection at position j
         if (wave == 0) {
           int my_slot = -1;
-          unsigned long long t_taken = 0ull, d_taken = 0ull;
-          const int most = min(nT, nD);
-          int taken = 0;
-          for (int i0 = 0; i0 < n_valid && taken < most; i0 += FP_WAVE) {
-            const int i = i0 + lane;
-            const bool have = i < n_valid;
-            const unsigned long long kk = have ? key[i] : 0ull;
-            const int k_slot = tk_key_slot(kk), k_pos = tk_key_pos(kk);
-            bool alive = have && !((t_taken >> k_slot) & 1ull) && !((d_taken >> k_pos) & 1ull);
-            unsigned long long live = __ballot(alive);
-            while (live) {
-              const int l = __ffsll((long long)live) - 1;   // the first pair of the batch still free is taken
-              const int w_slot = __shfl(k_slot, l), w_pos = __shfl(k_pos, l);
-              t_taken |= 1ull << w_slot;
-              d_taken |= 1ull << w_pos;
-              ++taken;
-              if (lane == w_pos) my_slot = w_slot;
-              if (alive && (k_slot == w_slot || k_pos == w_pos)) alive = false;
-              live = __ballot(alive);
+          if constexpr (REID) {
+            my_slot = walked;
+          } else {
+            unsigned long long t_taken = 0ull, d_taken = 0ull;
+            const int most = min(nT, nD);
+            int taken = 0;
+            for (int i0 = 0; i0 < n_valid && taken < most; i0 += FP_WAVE) {
+              const int i = i0 + lane;
+              const bool have = i < n_valid;
+              const unsigned long long kk = have ? key[i] : 0ull;
+              const int k_slot = tk_key_slot(kk), k_pos = tk_key_pos(kk);
+              bool alive = have && !((t_taken >> k_slot) & 1ull) && !((d_taken >> k_pos) & 1ull);
+              unsigned long long live = __ballot(alive);
+              while (live) {
+                const int l = __ffsll((long long)live) - 1;   // the first pair of the batch still free is taken
+                const int w_slot = __shfl(k_slot, l), w_pos = __shfl(k_pos, l);
+                t_taken |= 1ull << w_slot;
+                d_taken |= 1ull << w_pos;
+                ++taken;
+                if (lane == w_pos) my_slot = w_slot;
+                if (alive && (k_slot == w_slot || k_pos == w_pos)) alive = false;
+                live = __ballot(alive);
+              }
             }
           }
           // the unmatched live detections open tracks in the lowest free slots, in row order
@@ -439,12 +621,19 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
               unsigned long long fm = freem;
               for (int r = 0; r < rank; ++r) fm &= fm - 1ull;
               my_slot = __ffsll((long long)fm) - 1;
-              new_id = next_id + rank;
+              if constexpr (!REID) new_id = next_id + rank;
             } else {
               flags = FP_TRACK_FULL;
+              if constexpr (REID) my_ent = -1;   // no slot: the parked track stays parked
             }
           }
-          next_id += min(__popcll(needm), n_free);
+          if constexpr (REID) {   // ids go to the true openings alone, by their rank among themselves
+            const unsigned long long openm = __ballot(need && my_slot >= 0 && my_ent < 0);
+            new_id = next_id + __popcll(openm & lane_lt);
+            next_id += __popcll(openm);
+          } else {
+            next_id += min(__popcll(needm), n_free);
+          }
           if (lane < nd) {
             const long row = det_row[lane];
             if constexpr (MOTION) {
@@ -457,7 +646,12 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
             } else if (my_slot < 0) {
               tk_out(p, row, 0, 0, clock, flags);
             } else {
-              flags = tk_update_slot(p, s_i[my_slot], s_f[my_slot], row, det_inv[lane], !matched, clock, new_id);
+              if (REID && my_ent >= 0) {
+                flags = tk_revive_slot(p, s_i[my_slot], s_f[my_slot], l_i[my_ent], l_f[my_ent], row, det_inv[lane], clock);
+                det_ent[lane] = my_ent;
+              } else {
+                flags = tk_update_slot(p, s_i[my_slot], s_f[my_slot], row, det_inv[lane], !matched, clock, new_id);
+              }
               tk_out(p, row, s_i[my_slot][I_ID], s_i[my_slot][I_HITS], clock, flags);
               det_slot[lane] = my_slot;
               det_flag[lane] = flags;
@@ -472,7 +666,12 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
           if (slot < 0) continue;
           const f32x4 v = ((const f32x4*)(p.emb + (long)det_row[pos] * D))[k];
           ((f32x4*)(semb + (long)slot * D))[k] = v;
-          if (det_flag[pos] & FP_TRACK_BEST) ((f32x4*)(sbest + (long)slot * D))[k] = v;
+          if (det_flag[pos] & FP_TRACK_BEST) {
+            ((f32x4*)(sbest + (long)slot * D))[k] = v;
+          } else if constexpr (REID) {   // a revived track that keeps its best shot keeps that shot's embedding
+            const int ent = det_ent[pos];
+            if (ent >= 0) ((f32x4*)(sbest + (long)slot * D))[k] = ((const f32x4*)(lbest + (long)ent * D))[k];
+          }
         }
         __threadfence_block();
         __syncthreads();   // the rewritten embeddings are what the next frame's pairs read
@@ -486,6 +685,11 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
   if constexpr (MOTION)
     if (owned)
       for (int i = tid; i < SLOTS * MF; i += TPB) p.motion[(long)s * SLOTS * MF + i] = (&s_m[0][0])[i];
+  if constexpr (REID) {
+    for (int i = tid; i < LOST * NI; i += TPB) a.l.li[(long)s * LOST * NI + i] = (&l_i[0][0])[i];
+    for (int i = tid; i < LOST * NF; i += TPB) a.l.lf[(long)s * LOST * NF + i] = (&l_f[0][0])[i];
+    if (tid == 0) a.l.lhdr[2 * s] = head;
+  }
   if (tid == 0) {
     p.hdr[2 * s] = clock;
     p.hdr[2 * s + 1] = next_id;
@@ -531,20 +735,61 @@ TrackArgs track_args(const fp_track_state* st, int n_streams, int D, const int32
   return a;
 }
 
+ReidArgs with_reid(const TrackArgs& t, const fp_track_lost* lost, float tau_reid, int lost_age) {
+  ReidArgs a;
+  static_cast<TrackArgs&>(a) = t;
+  a.l.lhdr = lost ? lost->lost_hdr : nullptr;
+  a.l.li = lost ? lost->lost_i : nullptr;
+  a.l.lf = lost ? lost->lost_f : nullptr;
+  a.l.lemb = lost ? lost->lost_emb : nullptr;
+  a.l.lbest = lost ? lost->lost_best_emb : nullptr;
+  a.l.tau_reid = tau_reid; a.l.lost_age = lost_age;
+  return a;
+}
+
+// the re-identification entry points: check_track's refusals (check_motion's with a motion array) and their own
+int check_reid(const ReidArgs& a, const fp_track_state* st, const fp_track_lost* lost) {
+  const int rc = a.motion ? check_motion(a, st) : check_track(a, st);
+  if (rc != FP_OK) return rc;
+  if (!a.motion && a.o_pred) return FP_ERR_INVALID_ARG;   // track_pred is null iff motion is
+  if (!lost || !a.l.lhdr || !a.l.li || !a.l.lf || !a.l.lemb || !a.l.lbest) return FP_ERR_INVALID_ARG;
+  if (((uintptr_t)a.l.lemb | (uintptr_t)a.l.lbest) % 16 != 0) return FP_ERR_INVALID_ARG;   // float4 rows
+  if (!tk_finite(a.l.tau_reid) || a.l.lost_age <= a.max_age) return FP_ERR_INVALID_ARG;
+  return FP_OK;
+}
+
 TrackArgs with_motion(TrackArgs a, float* motion, float std_pos, float std_vel, float* track_pred) {
   a.motion = motion; a.std_pos = std_pos; a.std_vel = std_vel; a.o_pred = track_pred;
   return a;
 }
 
 // ---------------------------------------------------------------------------------------------------------- the host twin
-void emulate_frame(const TrackArgs& p, int s, int f, int& clock, int& next_id, std::vector<unsigned long long>& key) {
+void emulate_frame(const TrackArgs& p, const LostArgs* lo, int s, int f, int& clock, int& next_id,
+                   std::vector<unsigned long long>& key) {
   int* si = p.si + (long)s * SLOTS * NI;
   float* sf = p.sf + (long)s * SLOTS * NF;
   float* semb = p.semb + (long)s * SLOTS * p.D;
   float* sbest = p.sbest + (long)s * SLOTS * p.D;
   clock += 1;
+  int* li = lo ? lo->li + (long)s * LOST * NI : nullptr;   // the pool; null without re-identification
+  float* lf = lo ? lo->lf + (long)s * LOST * NF : nullptr;
+  float* lemb = lo ? lo->lemb + (long)s * LOST * p.D : nullptr;
+  float* lbest = lo ? lo->lbest + (long)s * LOST * p.D : nullptr;
+  for (int e = 0; li && e < LOST; ++e)   // step 1a
+    if (li[e * NI + I_ID] != 0 && clock - li[e * NI + I_LAST] > lo->lost_age) li[e * NI + I_ID] = 0;
   for (int t = 0; t < SLOTS; ++t)
-    if (si[t * NI + I_ID] != 0 && clock - si[t * NI + I_LAST] > p.max_age) si[t * NI + I_ID] = 0;
+    if (si[t * NI + I_ID] != 0 && clock - si[t * NI + I_LAST] > p.max_age) {
+      if (li) {   // parked in the ring before the slot is freed
+        int& head = lo->lhdr[2 * s];
+        const int e = head & (LOST - 1);
+        std::copy(si + t * NI, si + (t + 1) * NI, li + e * NI);
+        std::copy(sf + t * NF, sf + (t + 1) * NF, lf + e * NF);
+        std::copy(semb + (long)t * p.D, semb + (long)(t + 1) * p.D, lemb + (long)e * p.D);
+        std::copy(sbest + (long)t * p.D, sbest + (long)(t + 1) * p.D, lbest + (long)e * p.D);
+        head = (e + 1) & (LOST - 1);
+      }
+      si[t * NI + I_ID] = 0;
+    }
   float* sm = p.motion ? p.motion + (long)s * SLOTS * MF : nullptr;
   float pbox[SLOTS][4];   // step 1b: the predicted boxes of the live slots
   for (int t = 0; sm && t < SLOTS; ++t) {
@@ -594,11 +839,38 @@ void emulate_frame(const TrackArgs& p, int s, int f, int& clock, int& next_id, s
     d_taken |= 1ull << k_pos;
     my_slot[k_pos] = k_slot;
   }
-  int slot_of[MAXD], flag_of[MAXD];
+  int my_ent[MAXD];   // step 3b: the parked track an unmatched detection revives
+  for (int j = 0; j < MAXD; ++j) my_ent[j] = -1;
+  if (li) {
+    key.clear();
+    for (int e = 0; e < LOST; ++e) {
+      if (!tk_parked(li + e * NI, lf + e * NF)) continue;
+      for (int j = 0; j < nd; ++j) {
+        if (!(det_inv[j] > 0.f) || my_slot[j] >= 0) continue;
+        float part[GL];
+        for (int gl = 0; gl < GL; ++gl) part[gl] = tk_partial(lemb + (long)e * p.D, p.emb + det_row[j] * p.D, p.D, gl);
+        for (int off = GL / 2; off > 0; off >>= 1)
+          for (int l = 0; l < off; ++l) part[l] = part[l] + part[l + off];
+        const float c = tk_cos(part[0], lf[e * NF + F_INV], det_inv[j]);
+        if (c > lo->tau_reid) key.push_back(tk_key(c, e, j));
+      }
+    }
+    std::sort(key.begin(), key.end());
+    unsigned long long e_taken = 0ull, u_taken = 0ull;
+    for (size_t i = 0; i < key.size(); ++i) {
+      const int k_ent = tk_key_slot(key[i]), k_pos = tk_key_pos(key[i]);
+      if (((e_taken >> k_ent) & 1ull) || ((u_taken >> k_pos) & 1ull)) continue;
+      e_taken |= 1ull << k_ent;
+      u_taken |= 1ull << k_pos;
+      my_ent[k_pos] = k_ent;
+    }
+  }
+  int slot_of[MAXD], flag_of[MAXD], ent_of[MAXD];
   for (int j = 0; j < nd; ++j) {
     const long row = det_row[j];
     slot_of[j] = -1;
     flag_of[j] = 0;
+    ent_of[j] = -1;
     if (sm) tk_pred(p, row, my_slot[j] >= 0 ? pbox[my_slot[j]] : nullptr);
     if (!(det_inv[j] > 0.f)) {
       tk_out(p, row, 0, 0, clock, FP_TRACK_DEAD_ROW);
@@ -614,11 +886,18 @@ void emulate_frame(const TrackArgs& p, int s, int f, int& clock, int& next_id, s
         tk_out(p, row, 0, 0, clock, FP_TRACK_FULL);
         continue;
       }
-      new_id = next_id++;
+      if (my_ent[j] < 0) new_id = next_id++;   // a revived track brings its id along
     }
     if (sm && matched) tk_motion_update(p, sm + slot * MF, p.box + row * 4);
     if (sm && !matched) tk_motion_init(p, sm + slot * MF, p.box + row * 4);
-    const int flags = tk_update_slot(p, si + slot * NI, sf + slot * NF, row, det_inv[j], !matched, clock, new_id);
+    int flags;
+    if (my_ent[j] >= 0) {
+      const int e = my_ent[j];
+      flags = tk_revive_slot(p, si + slot * NI, sf + slot * NF, li + e * NI, lf + e * NF, row, det_inv[j], clock);
+      ent_of[j] = e;
+    } else {
+      flags = tk_update_slot(p, si + slot * NI, sf + slot * NF, row, det_inv[j], !matched, clock, new_id);
+    }
     tk_out(p, row, si[slot * NI + I_ID], si[slot * NI + I_HITS], clock, flags);
     slot_of[j] = slot;
     flag_of[j] = flags;
@@ -628,10 +907,11 @@ void emulate_frame(const TrackArgs& p, int s, int f, int& clock, int& next_id, s
     const float* e = p.emb + det_row[j] * p.D;
     std::copy(e, e + p.D, semb + (long)slot_of[j] * p.D);
     if (flag_of[j] & FP_TRACK_BEST) std::copy(e, e + p.D, sbest + (long)slot_of[j] * p.D);
+    else if (ent_of[j] >= 0) std::copy(lbest + (long)ent_of[j] * p.D, lbest + (long)(ent_of[j] + 1) * p.D, sbest + (long)slot_of[j] * p.D);
   }
 }
 
-void emulate_step(const TrackArgs& p) {
+void emulate_step(const TrackArgs& p, const LostArgs* lo = nullptr) {
   for (long i = 0; i < p.n; ++i)
     if (tk_untracked(p, p.frame[i])) {
       tk_out(p, i, 0, 0, 0, FP_TRACK_NO_STREAM);
@@ -641,7 +921,7 @@ void emulate_step(const TrackArgs& p) {
   for (int f = 0; f < p.B; ++f) {   // streams are independent: batch order is every stream's own order
     const int s = p.sof[f];
     if (s < 0 || s >= p.S) continue;
-    emulate_frame(p, s, f, p.hdr[2 * s], p.hdr[2 * s + 1], key);
+    emulate_frame(p, lo, s, f, p.hdr[2 * s], p.hdr[2 * s + 1], key);
   }
 }
 
@@ -657,7 +937,7 @@ int fp_tracklets_step(const fp_track_state* state, int n_streams, int D, const i
                                  tau_far, iou_min, track_id, track_hits, track_clock, track_flags);
   const int rc = check_track(a, state);
   if (rc != FP_OK || (B == 0 && n == 0)) return rc;
-  hipLaunchKernelGGL(tracklets_kernel<false>, dim3((unsigned)n_streams), dim3(TPB), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL((tracklets_kernel<false, false>), dim3((unsigned)n_streams), dim3(TPB), 0, (hipStream_t)stream, a);
   FP_CHECK_LAUNCH();
   return FP_OK;
 }
@@ -684,7 +964,7 @@ int fp_tracklets_step_motion(const fp_track_state* state, int n_streams, int D, 
                                   motion, std_pos, std_vel, track_pred);
   const int rc = check_motion(a, state);
   if (rc != FP_OK || (B == 0 && n == 0)) return rc;
-  hipLaunchKernelGGL(tracklets_kernel<true>, dim3((unsigned)n_streams), dim3(TPB), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL((tracklets_kernel<true, false>), dim3((unsigned)n_streams), dim3(TPB), 0, (hipStream_t)stream, a);
   FP_CHECK_LAUNCH();
   return FP_OK;
 }
@@ -700,6 +980,41 @@ int fp_tracklets_step_motion_emulate(const fp_track_state* state, int n_streams,
   const int rc = check_motion(p, state);
   if (rc != FP_OK) return rc;
   emulate_step(p);
+  return FP_OK;
+}
+
+int fp_tracklets_step_reid(const fp_track_state* state, const fp_track_lost* lost, int n_streams, int D, const int32_t* frame,
+                           const float* box, const float* emb, const float* xinv, const float* score, int n,
+                           const int32_t* stream_of_frame, int B, int max_age, float tau_near, float tau_far, float iou_min,
+                           int32_t* track_id, int32_t* track_hits, int32_t* track_clock, int32_t* track_flags, float tau_reid,
+                           int lost_age, float* motion, float std_pos, float std_vel, float* track_pred, void* stream) {
+  TrackArgs t = track_args(state, n_streams, D, frame, box, emb, xinv, score, n, stream_of_frame, B, max_age, tau_near, tau_far,
+                           iou_min, track_id, track_hits, track_clock, track_flags);
+  if (motion) t = with_motion(t, motion, std_pos, std_vel, track_pred);
+  else t.o_pred = track_pred;   // refused unless null
+  const ReidArgs a = with_reid(t, lost, tau_reid, lost_age);
+  const int rc = check_reid(a, state, lost);
+  if (rc != FP_OK || (B == 0 && n == 0)) return rc;
+  if (motion) hipLaunchKernelGGL((tracklets_kernel<true, true>), dim3((unsigned)n_streams), dim3(TPB), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((tracklets_kernel<false, true>), dim3((unsigned)n_streams), dim3(TPB), 0, (hipStream_t)stream, a);
+  FP_CHECK_LAUNCH();
+  return FP_OK;
+}
+
+int fp_tracklets_step_reid_emulate(const fp_track_state* state, const fp_track_lost* lost, int n_streams, int D,
+                                   const int32_t* frame, const float* box, const float* emb, const float* xinv, const float* score,
+                                   int n, const int32_t* stream_of_frame, int B, int max_age, float tau_near, float tau_far,
+                                   float iou_min, int32_t* track_id, int32_t* track_hits, int32_t* track_clock,
+                                   int32_t* track_flags, float tau_reid, int lost_age, float* motion, float std_pos, float std_vel,
+                                   float* track_pred) {
+  TrackArgs t = track_args(state, n_streams, D, frame, box, emb, xinv, score, n, stream_of_frame, B, max_age, tau_near, tau_far,
+                           iou_min, track_id, track_hits, track_clock, track_flags);
+  if (motion) t = with_motion(t, motion, std_pos, std_vel, track_pred);
+  else t.o_pred = track_pred;
+  const ReidArgs p = with_reid(t, lost, tau_reid, lost_age);
+  const int rc = check_reid(p, state, lost);
+  if (rc != FP_OK) return rc;
+  emulate_step(p, &p.l);
   return FP_OK;
 }
 

@@ -1,5 +1,5 @@
 """``python -m face_detection_and_recognition_amd.eval.eval_face_tracker data/ --tracks hyp/`` or
-``... data/ --model synthetic --max_age 30 [--motion STD_POS STD_VEL] [--sweep max_age=5,15,30] [--hota [--alphas a,b,...]]``
+``... data/ --model synthetic --max_age 30 [--motion STD_POS STD_VEL] [--reid TAU LOST_AGE] [--sweep max_age=5,15,30] [--hota [--alphas a,b,...]]``
 
 Scores a face tracker on labelled video with CLEAR-MOT (MOTA, MOTP, IDSW, Frag, MT / PT / ML) and the identity measures
 (IDF1, IDP, IDR): tracking_eval.py, the kernel of csrc/moteval.hip on a HIP device, numpy with ``-d cpu``; DESIGN.md
@@ -16,7 +16,11 @@ modules/utils/video.py).  The hypotheses are either
 
 ``--motion STD_POS STD_VEL`` turns the tracker's constant-velocity prediction on (tracking.ConstantVelocity; DESIGN section 7
 "Tracklets: motion prediction"): no defaults, nothing has been measured; DeepSORT publishes 0.05 and 0.00625.
-``--sweep key=v1,v2,...`` (key: max_age, tau_near, tau_far, iou_min, or with --motion std_pos / std_vel) repeats the run per
+``--reid TAU LOST_AGE`` turns re-identification on (tracking.LostPool; DESIGN section 7 "Tracklets: re-identification"): an
+ended track is remembered for LOST_AGE frames (an integer > max_age) and a returning face whose cosine to its last embedding
+exceeds TAU continues it; no defaults, nothing has been measured on real video.
+``--sweep key=v1,v2,...`` (key: max_age, tau_near, tau_far, iou_min, with --motion std_pos / std_vel, with --reid tau_reid /
+lost_age) repeats the run per
 value and prints one combined row each.  Prints the table (one line per sequence and the combined line) and returns the result
 (a list of (value, result) under --sweep).  The thresholds' defaults are the reference's numbers restated as cosines; max_age
 has no default.
@@ -34,7 +38,8 @@ import numpy as np
 from ..tracking import IOU_MIN, TAU_FAR, TAU_NEAR
 from ..tracking_eval import TrackingEvaluator, hota_eval, mot_eval, read_mot_txt
 
-SWEEP_KEYS = dict(max_age=int, tau_near=float, tau_far=float, iou_min=float, std_pos=float, std_vel=float)
+SWEEP_KEYS = dict(max_age=int, tau_near=float, tau_far=float, iou_min=float, std_pos=float, std_vel=float, tau_reid=float,
+                  lost_age=int)
 
 
 def load_sequences(root):
@@ -121,11 +126,11 @@ def run_tracker(seqs, args, dev, parts):
     import torch
     from ..modules.utils.video import read_frames
     from ..pipeline import FacePipeline
-    from ..tracking import ConstantVelocity, StreamTracker
+    from ..tracking import ConstantVelocity, LostPool, StreamTracker
     det, emb = parts
     motion = None if args.motion is None else ConstantVelocity(*args.motion)
     tracker = StreamTracker(len(seqs), emb.embedding_size, args.max_age, args.tau_near, args.tau_far, args.iou_min, device=dev,
-                            motion=motion)
+                            motion=motion, reid=None if args.reid is None else LostPool(*args.reid))
     pipe = FacePipeline(det, emb, None, tracker=tracker)
     ev = TrackingEvaluator(len(seqs), dev, thr=args.thr).set_ground_truth(*ground_truth(seqs))
     for s, seq in enumerate(seqs):
@@ -179,8 +184,11 @@ def main(argv=None):
     parser.add_argument("--iou_min", type=float, default=IOU_MIN)
     parser.add_argument("--motion", type=float, nargs=2, default=None, metavar=("STD_POS", "STD_VEL"),
                         help="Constant-velocity prediction for the IoU gate: noise as fractions of the box height (no defaults).")
+    parser.add_argument("--reid", type=float, nargs=2, default=None, metavar=("TAU", "LOST_AGE"),
+                        help="Re-identification of ended tracks: the cosine a returning face must exceed and the frames a track is "
+                             "remembered, an integer > max_age (no defaults).")
     parser.add_argument("--sweep", default=None, help="key=v1,v2,...: repeat the run per value of max_age / tau_near / tau_far / iou_min "
-                                                      "/ std_pos / std_vel (the last two with --motion).")
+                                                      "/ std_pos / std_vel (with --motion) / tau_reid / lost_age (with --reid).")
     parser.add_argument("--thr", type=float, default=0.5, help="IoU threshold of a match (default: %(default)s).")
     parser.add_argument("--hota", action="store_true", help="Append HOTA, DetA, AssA, DetRe, DetPr, AssRe, AssPr, LocA to every row.")
     parser.add_argument("--alphas", default=None, help="a,b,...: HOTA's localisation thresholds, ascending inside (0, 1] "
@@ -222,10 +230,14 @@ def main(argv=None):
             parser.error("--max_age is required (it has no default: nothing has been measured)")
         if key in ("std_pos", "std_vel") and args.motion is None:
             parser.error(f"--sweep {key}= needs --motion STD_POS STD_VEL for the value that is not swept")
+        if key in ("tau_reid", "lost_age") and args.reid is None:
+            parser.error(f"--sweep {key}= needs --reid TAU LOST_AGE for the value that is not swept")
         results, parts = [], build_parts(seqs, args, device)
         for v in values:
             if key in ("std_pos", "std_vel"):
                 args.motion[("std_pos", "std_vel").index(key)] = v
+            elif key in ("tau_reid", "lost_age"):
+                args.reid[("tau_reid", "lost_age").index(key)] = v
             elif key is not None:
                 setattr(args, key, v)
             result = run_tracker(seqs, args, device, parts)

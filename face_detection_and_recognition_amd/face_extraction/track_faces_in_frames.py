@@ -11,6 +11,9 @@ highest detector confidence, or with --quality the sharpest crop); at the end <t
 The thresholds default to the reference's numbers restated as cosines, unmeasured on real video; --max_age has no default.
 --motion STD_POS STD_VEL turns the tracker's constant-velocity prediction on (tracking.ConstantVelocity: the IoU gate takes the
 box a track is predicted at; no defaults, nothing has been measured).
+--reid TAU LOST_AGE turns re-identification on (tracking.LostPool: a track that ends is remembered for LOST_AGE frames and a
+returning face whose cosine to its last embedding exceeds TAU continues it -- one track_XXXX/ folder and one id instead of
+two; no defaults, nothing has been measured on real video).
 Build-defined: the reference labels faces frame by frame (face_tracker.py is that port).
 
 --video_out FILE writes every frame with its tracked faces' boxes and ` #<id>` captions (FacePipeline.annotate) to a
@@ -26,7 +29,7 @@ import os
 
 import numpy as np
 
-from ..tracking import BEST, IOU_MIN, TAU_FAR, TAU_NEAR, ConstantVelocity, StreamTracker, TrackBook
+from ..tracking import BEST, IOU_MIN, TAU_FAR, TAU_NEAR, ConstantVelocity, LostPool, StreamTracker, TrackBook
 
 
 def get_parsed_args(argv=None):
@@ -47,12 +50,20 @@ def get_parsed_args(argv=None):
     parser.add_argument('--iou_min', type=float, default=IOU_MIN)
     parser.add_argument('--motion', type=float, nargs=2, default=None, metavar=("STD_POS", "STD_VEL"),
                         help="constant-velocity prediction for the IoU gate: noise as fractions of the box height (no defaults)")
+    parser.add_argument('--reid', type=float, nargs=2, default=None, metavar=("TAU", "LOST_AGE"),
+                        help="re-identification of ended tracks: the cosine a returning face must exceed and the frames a track "
+                             "is remembered, an integer > max_age (no defaults)")
     parser.add_argument('--quality', action="store_true", help="best shot by crop sharpness instead of detector confidence")
     parser.add_argument('-b', '--batch_size', type=int, default=256)
     parser.add_argument('--jpeg_quality', type=int, default=95)
     parser.add_argument('-d', '--device', default="cuda:0")
     parser.add_argument('--mot_out', type=str, default=None, help="also write the tracked rows as MOTChallenge text to this file")
     return parser.parse_args(argv)
+
+
+def lost_pool(args):
+    """--reid as a tracking.LostPool, or None (ValueError for a LOST_AGE that is no integer)."""
+    return None if args.reid is None else LostPool(args.reid[0], args.reid[1])
 
 
 def frame_files(folder):
@@ -68,7 +79,8 @@ def build_pipeline(args, dev, first_frames):
     det = W.build_detector(dev, first_frames, cand_per_frame=48)
     emb = W.build_embedder(dev)
     motion = None if args.motion is None else ConstantVelocity(*args.motion)
-    tracker = StreamTracker(1, emb.embedding_size, args.max_age, args.tau_near, args.tau_far, args.iou_min, device=dev, motion=motion)
+    tracker = StreamTracker(1, emb.embedding_size, args.max_age, args.tau_near, args.tau_far, args.iou_min, device=dev, motion=motion,
+                            reid=lost_pool(args))
     return FacePipeline(det, emb, None, quality=True if args.quality else None, tracker=tracker), tracker
 
 

@@ -36,7 +36,9 @@ class FacePipeline:
     mask, which compacts nothing (as the cosine filter's keep); side stream as the attributes.
     tracker: a StreamTracker (tracking.py) whose feat_dim is the embedder's: step results then also carry track_id, track_hits,
     track_clock and track_flags (n,) int32, rows in the order of emb, from one fp_tracklets_step launch behind the embedder (side
-    stream as the attributes); a tracker built with motion= adds track_pred (n, 4) fp32, the predicted box of every matched row.  step / step_overlapped take streams = the stream of every frame ((B,) ints, -1: not tracked;
+    stream as the attributes); a tracker built with motion= adds track_pred (n, 4) fp32, the predicted box of every matched row; one built with reid= (a
+    tracking.LostPool) gives a returning face its old id back, and that row's track_flags carry tracking.REVIVED (64) where an
+    opening row carries NEW: the flags pass through unchanged.  step / step_overlapped take streams = the stream of every frame ((B,) ints, -1: not tracked;
     None: the batch is consecutive frames of stream 0).  The score of the best shot is the conf column of info, or
     quality["sharpness"] with quality on.  Steps must reach the tracker in order: it carries state from step to step."""
 

@@ -19,6 +19,14 @@ and every matched row also reports that box (track_pred).  fp_tracklets_step_mot
 prediction"; the filter is float32 in the written order on all three paths, so it adds nothing to the agreement condition.
 Without motion= nothing changes.  Rows for coasting tracks, Mahalanobis gating and camera-motion compensation are not part of
 this, and no value of std_pos / std_vel has been measured.
+
+Re-identification is opt-in too: reid=LostPool(tau_reid, lost_age) parks a track that expires in a ring of L.TRACK_LOST entries
+per stream instead of dropping it, and a face that no live track takes is compared (cosine alone, against the parked track's LAST
+embedding) with the parked tracks before it opens a new one; above tau_reid it continues the old track -- id, hits, first clock,
+best shot -- and its row carries REVIVED instead of NEW.  fp_tracklets_step_reid, include/facepath.h "Tracklets:
+re-identification"; the state gains the five lost_* arrays.  Without reid= nothing changes.  Neither parameter has a default and
+neither has been measured on real video; re-identification across streams, pools beyond 64 tracks and a best-shot descriptor are
+not part of this.
 """
 import ctypes as C
 
@@ -30,6 +38,8 @@ from . import _lib as L
 SLOTS, MAX_DETS = L.TRACK_SLOTS, L.TRACK_MAX_DETS
 NEW, BEST, DEAD_ROW, FULL, NO_STREAM, OVER = (L.TRACK_NEW, L.TRACK_BEST, L.TRACK_DEAD_ROW, L.TRACK_FULL, L.TRACK_NO_STREAM,
                                               L.TRACK_OVER)
+REVIVED, LOST = L.TRACK_REVIVED, L.TRACK_LOST
+LOST_KEYS = ("lost_hdr", "lost_i", "lost_f", "lost_emb", "lost_best_emb")
 TAU_NEAR, TAU_FAR, IOU_MIN = 0.5, 0.7408, 0.1        # the reference's 1.0 / 0.72 L2 thresholds as cosines, and its IoU gate
 I_ID, I_FIRST, I_LAST, I_HITS, I_BEST_CLOCK = range(5)      # slot_i columns
 F_BOX, F_INV, F_BEST_SCORE, F_BEST_BOX = 0, 4, 5, 6         # slot_f columns
@@ -55,6 +65,54 @@ class ConstantVelocity:
 
     def __repr__(self):
         return f"ConstantVelocity(std_pos={self.std_pos}, std_vel={self.std_vel})"
+
+
+class LostPool:
+    """The parameters of the tracker's re-identification: tau_reid, the cosine a returning face must exceed against a parked
+    track's last embedding (finite, ValueError otherwise), and lost_age, the frames after its last sighting for which an expired
+    track stays parked (an int; the tracker wants lost_age > max_age).  No defaults: nothing has been measured here."""
+
+    def __init__(self, tau_reid, lost_age):
+        self.tau_reid = float(tau_reid)
+        if not np.isfinite(np.float32(self.tau_reid)):
+            raise ValueError(f"tau_reid must be finite, got {tau_reid}")
+        if isinstance(lost_age, bool) or int(lost_age) != lost_age:
+            raise ValueError(f"lost_age must be an int, got {lost_age!r}")
+        self.lost_age = int(lost_age)
+
+    def check(self, max_age):
+        if not self.lost_age > int(max_age):
+            raise ValueError(f"lost_age must be > max_age, got lost_age {self.lost_age}, max_age {max_age}")
+
+    def __repr__(self):
+        return f"LostPool(tau_reid={self.tau_reid}, lost_age={self.lost_age})"
+
+
+def new_lost_state(n_streams, feat_dim):
+    """A fresh pool: dict of zero numpy arrays in the layout of fp_track_lost (every entry empty, every ring head 0)."""
+    S, D = int(n_streams), int(feat_dim)
+    return dict(lost_hdr=np.zeros((S, 2), np.int32), lost_i=np.zeros((S, LOST, L.TRACK_SLOT_INTS), np.int32),
+                lost_f=np.zeros((S, LOST, L.TRACK_SLOT_FLOATS), np.float32), lost_emb=np.zeros((S, LOST, D), np.float32),
+                lost_best_emb=np.zeros((S, LOST, D), np.float32))
+
+
+def _reid_args(reid, lost_state, S, D, max_age):
+    """None without reid; else the checked pool dict."""
+    if reid is None:
+        if lost_state is not None:
+            raise ValueError("lost_state without reid=")
+        return None
+    if not isinstance(reid, LostPool):
+        raise TypeError(f"reid must be None or a LostPool, got {type(reid).__name__}")
+    reid.check(max_age)
+    fresh = new_lost_state(1, D)
+    ok = isinstance(lost_state, dict) and all(
+        isinstance(lost_state.get(k), np.ndarray) and lost_state[k].dtype == fresh[k].dtype
+        and lost_state[k].shape == (S,) + fresh[k].shape[1:] and lost_state[k].flags.c_contiguous and lost_state[k].flags.writeable
+        for k in LOST_KEYS)
+    if not ok:
+        raise ValueError(f"lost_state must be a dict of the writable C-contiguous arrays of new_lost_state({S}, {D})")
+    return lost_state
 
 
 def new_motion_state(n_streams):
@@ -185,14 +243,18 @@ def _iou_f32(t, d):
 
 
 def track_step_numpy(state, frame, boxes, emb, xinv, stream_of_frame, max_age, tau_near=TAU_NEAR, tau_far=TAU_FAR,
-                     iou_min=IOU_MIN, score=None, cosines=None, motion=None, motion_state=None):
+                     iou_min=IOU_MIN, score=None, cosines=None, motion=None, motion_state=None, reid=None, lost_state=None,
+                     reid_cosines=None):
     """fp_tracklets_step in numpy on a host state (new_state; updated IN PLACE).  IoU in float32 in the written order, the
     cosine in float64: (dot * inv_t) * inv_d with float64 products of the float32 values.  -> dict of the four per-row int32
     arrays.  cosines: a list that receives, per frame with live tracks and live detections, (frame, slots, rows, c (T, K)
     float64, iou (T, K) float32, the tracks' stored rows (T, D)) -- what the tests' gap condition looks at.
     motion: a ConstantVelocity, with motion_state = the streams' `motion` array (new_motion_state; updated IN PLACE): the filter
     of "Tracklets: motion prediction" in np.float32 scalars, the IoU taken with the predicted boxes, and the result also
-    carries track_pred (n, 4) float32."""
+    carries track_pred (n, 4) float32.
+    reid: a LostPool, with lost_state = the streams' pool (new_lost_state; updated IN PLACE): steps 1a, 1 (parking), 3b and 4 of
+    "Tracklets: re-identification", the reid cosine in float64 like step 2's.  reid_cosines: a list that receives, per frame
+    with unmatched live detections and parked tracks, (frame, entries, rows, c (E, K) float64)."""
     frame, boxes, emb, xinv, score, sof = _row_inputs(frame, boxes, emb, xinv, score, stream_of_frame)
     n, B = frame.shape[0], sof.shape[0]
     S, D = state["hdr"].shape[0], state["emb"].shape[2]
@@ -200,6 +262,8 @@ def track_step_numpy(state, frame, boxes, emb, xinv, stream_of_frame, max_age, t
     f32 = np.float32
     tn, tf, im = float(f32(tau_near)), float(f32(tau_far)), f32(iou_min)
     sp, sv, mstate = _motion_args(motion, motion_state, S)
+    pool = _reid_args(reid, lost_state, S, D, max_age)
+    tr = None if pool is None else float(f32(reid.tau_reid))
     out = {k: np.zeros((n,), np.int32) for k in OUT_KEYS}
     if motion is not None:
         out["track_pred"] = np.zeros((n, 4), np.float32)
@@ -218,7 +282,16 @@ def track_step_numpy(state, frame, boxes, emb, xinv, stream_of_frame, max_age, t
             hdr, si, sf = state["hdr"][s], state["slot_i"][s], state["slot_f"][s]
             hdr[0] += 1
             clock = int(hdr[0])
-            si[(si[:, I_ID] != 0) & (clock - si[:, I_LAST] > max_age), I_ID] = 0
+            expiring = (si[:, I_ID] != 0) & (clock - si[:, I_LAST] > max_age)
+            if pool is not None:
+                lh, li, lf = pool["lost_hdr"][s], pool["lost_i"][s], pool["lost_f"][s]
+                li[(li[:, I_ID] != 0) & (clock - li[:, I_LAST] > reid.lost_age), I_ID] = 0          # step 1a
+                for t in np.nonzero(expiring)[0]:                                                    # step 1: parked, then freed
+                    e = int(lh[0]) & (LOST - 1)
+                    li[e], lf[e] = si[t], sf[t]
+                    pool["lost_emb"][s][e], pool["lost_best_emb"][s][e] = state["emb"][s][t], state["best_emb"][s][t]
+                    lh[0] = (e + 1) & (LOST - 1)
+            si[expiring, I_ID] = 0
             if motion is not None:                          # step 1b: every live slot, rows or not
                 pbox = {int(t): _motion_predict(mstate[s, t], sp, sv) for t in np.nonzero(si[:, I_ID] != 0)[0]}
             rows = np.nonzero(frame == f)[0]
@@ -248,18 +321,44 @@ def track_step_numpy(state, frame, boxes, emb, xinv, stream_of_frame, max_age, t
                     t_used.add(t)
                     d_used.add(d)
                     taken[int(dets[d])] = int(slots[t])
+            revived = {}                                    # detection row -> pool entry (step 3b)
+            if pool is not None:
+                un = np.array([i for i in dets if int(i) not in taken], np.int64)
+                with np.errstate(all="ignore"):
+                    ents = np.nonzero((li[:, I_ID] != 0) & np.isfinite(lf[:, F_INV]) & (lf[:, F_INV] > 0))[0]
+                if len(un) and len(ents):
+                    le, de = pool["lost_emb"][s][ents].astype(np.float64), emb[un].astype(np.float64)
+                    dot = (le[:, None, :] * de[None, :, :]).sum(axis=2)
+                    c = (dot * lf[ents, F_INV].astype(np.float64)[:, None]) * xinv[un].astype(np.float64)[None, :]
+                    if reid_cosines is not None:
+                        reid_cosines.append((f, ents.copy(), un.copy(), c.copy()))
+                    ei, dj = np.nonzero(c > tr)
+                    order = np.lexsort((dj, ei, -c[ei, dj]))   # c descending, then entry, then row
+                    e_used, d_used = set(), set()
+                    for q in order:
+                        e, d = int(ei[q]), int(dj[q])
+                        if e in e_used or d in d_used:
+                            continue
+                        e_used.add(e)
+                        d_used.add(d)
+                        revived[int(un[d])] = int(ents[e])
             for i in dets:
                 i = int(i)
-                slot, is_new = taken.get(i), False
+                slot, is_new, ent = taken.get(i), False, None
                 if slot is None:
                     free = np.nonzero(si[:, I_ID] == 0)[0]
-                    if not len(free):
+                    if not len(free):                       # a revived detection too: its entry stays parked
                         out["track_clock"][i], out["track_flags"][i] = clock, FULL
                         continue
-                    slot, is_new = int(free[0]), True
-                    si[slot, I_ID], si[slot, I_FIRST], si[slot, I_HITS] = hdr[1], clock, 0
-                    hdr[1] += 1
-                if motion is not None and is_new:
+                    slot, ent = int(free[0]), revived.get(i)
+                    if ent is None:
+                        is_new = True
+                        si[slot, I_ID], si[slot, I_FIRST], si[slot, I_HITS] = hdr[1], clock, 0
+                        hdr[1] += 1
+                    else:                                   # the slot continues the parked track
+                        si[slot], sf[slot] = li[ent], lf[ent]
+                        li[ent, I_ID] = 0
+                if motion is not None and (is_new or ent is not None):
                     _motion_init(mstate[s, slot], boxes[i], sp, sv)
                 elif motion is not None:
                     out["track_pred"][i] = pbox[slot]
@@ -268,11 +367,13 @@ def track_step_numpy(state, frame, boxes, emb, xinv, stream_of_frame, max_age, t
                 si[slot, I_HITS] += 1
                 si[slot, I_LAST] = clock
                 sf[slot, F_BOX:F_BOX + 4], sf[slot, F_INV] = boxes[i], xinv[i]
-                flags = NEW if is_new else 0
+                flags = NEW if is_new else (0 if ent is None else REVIVED)
                 if is_new or sc > sf[slot, F_BEST_SCORE]:
                     sf[slot, F_BEST_SCORE], si[slot, I_BEST_CLOCK] = sc, clock
                     sf[slot, F_BEST_BOX:F_BEST_BOX + 4] = boxes[i]
                     flags |= BEST
+                elif ent is not None:                       # the carried best shot keeps its embedding
+                    state["best_emb"][s][slot] = pool["lost_best_emb"][s][ent]
                 out["track_id"][i], out["track_hits"][i] = si[slot, I_ID], si[slot, I_HITS]
                 out["track_clock"][i], out["track_flags"][i] = clock, flags
             for i in dets:                                  # after the frame's pairs were scored against the old embeddings
@@ -293,10 +394,15 @@ def _state_struct(arrays, pointer):
     return L.FpTrackState(*[pointer(arrays[k]) for k in STATE_KEYS])
 
 
+def _lost_struct(arrays, pointer):
+    return L.FpTrackLost(*[pointer(arrays[k]) for k in LOST_KEYS])
+
+
 def track_step_emulate(state, frame, boxes, emb, xinv, stream_of_frame, max_age, tau_near=TAU_NEAR, tau_far=TAU_FAR,
-                       iou_min=IOU_MIN, score=None, motion=None, motion_state=None):
+                       iou_min=IOU_MIN, score=None, motion=None, motion_state=None, reid=None, lost_state=None):
     """fp_tracklets_step_emulate on a host state (new_state; updated IN PLACE): track_step_numpy's arguments and results; with
-    motion= and motion_state=, fp_tracklets_step_motion_emulate.  Raises FacepathError on a refusal.  Needs no GPU."""
+    motion= and motion_state=, fp_tracklets_step_motion_emulate; with reid= and lost_state= (with or without motion),
+    fp_tracklets_step_reid_emulate.  Raises FacepathError on a refusal.  Needs no GPU."""
     lib = L.load()
     frame, boxes, emb, xinv, score, sof = _row_inputs(frame, boxes, emb, xinv, score, stream_of_frame)
     n, B = frame.shape[0], sof.shape[0]
@@ -313,9 +419,21 @@ def track_step_emulate(state, frame, boxes, emb, xinv, stream_of_frame, max_age,
         aligned[...] = emb
         emb = aligned
     sp, sv, mstate = _motion_args(motion, motion_state, S)
+    pool = _reid_args(reid, lost_state, S, D, max_age)
     out = {k: np.zeros((n,), np.int32) for k in OUT_KEYS}
     p = lambda a: None if a is None else C.c_void_p(a.ctypes.data)          # noqa: E731
     st = _state_struct(state, p)
+    if pool is not None:
+        pred = None if motion is None else np.zeros((n, 4), np.float32)
+        lost = _lost_struct(pool, p)
+        L.check(lib.fp_tracklets_step_reid_emulate(C.byref(st), C.byref(lost), S, D, p(frame), p(boxes), p(emb), p(xinv), p(score), n,
+                                                   p(sof), B, int(max_age), float(tau_near), float(tau_far), float(iou_min),
+                                                   *[p(out[k]) for k in OUT_KEYS], reid.tau_reid, reid.lost_age, p(mstate),
+                                                   0.0 if motion is None else float(sp), 0.0 if motion is None else float(sv),
+                                                   p(pred)), "fp_tracklets_step_reid_emulate")
+        if motion is not None:
+            out["track_pred"] = pred
+        return out
     if motion is not None:
         pred = np.zeros((n, 4), np.float32)
         L.check(lib.fp_tracklets_step_motion_emulate(C.byref(st), S, D, p(frame), p(boxes), p(emb), p(xinv), p(score), n, p(sof),
@@ -335,14 +453,20 @@ class StreamTracker:
     max_age: a track unseen for more than max_age frames of its stream is freed (required: nothing to restate).  The
     thresholds default to the reference's numbers as cosines (module docstring); tau_far < tau_near is a ValueError.
     motion: None, or a ConstantVelocity: the IoU gate takes the predicted box (fp_tracklets_step_motion), the state gains
-    "motion" (n_streams, SLOTS, MOTION_FLOATS) and step() also returns track_pred."""
+    "motion" (n_streams, SLOTS, MOTION_FLOATS) and step() also returns track_pred.
+    reid: None, or a LostPool with lost_age > max_age (ValueError otherwise): expired tracks are parked and a returning face
+    takes its old id back (fp_tracklets_step_reid; its row carries REVIVED); the state gains the five LOST_KEYS arrays."""
 
     def __init__(self, n_streams, feat_dim, max_age, tau_near=TAU_NEAR, tau_far=TAU_FAR, iou_min=IOU_MIN, device="cuda:0",
-                 motion=None):
+                 motion=None, reid=None):
         check_params(n_streams, feat_dim, max_age, tau_near, tau_far, iou_min)
         if motion is not None and not isinstance(motion, ConstantVelocity):
             raise TypeError(f"motion must be None or a ConstantVelocity, got {type(motion).__name__}")
-        self.motion = motion
+        if reid is not None and not isinstance(reid, LostPool):
+            raise TypeError(f"reid must be None or a LostPool, got {type(reid).__name__}")
+        if reid is not None:
+            reid.check(max_age)
+        self.motion, self.reid = motion, reid
         self.S, self.D, self.max_age = int(n_streams), int(feat_dim), int(max_age)
         self.tau_near, self.tau_far, self.iou_min = float(tau_near), float(tau_far), float(iou_min)
         self.dev = torch.device(device)
@@ -350,10 +474,13 @@ class StreamTracker:
         self._struct = _state_struct(self.state, L.ptr)
         if motion is not None:
             self.state["motion"] = torch.from_numpy(new_motion_state(self.S)).to(self.dev)
+        if reid is not None:
+            self.state.update({k: torch.from_numpy(v).to(self.dev) for k, v in new_lost_state(self.S, self.D).items()})
+            self._lost = _lost_struct(self.state, L.ptr)
 
     @property
     def state_keys(self):
-        return STATE_KEYS + (("motion",) if self.motion is not None else ())
+        return STATE_KEYS + (("motion",) if self.motion is not None else ()) + (LOST_KEYS if self.reid is not None else ())
 
     def step(self, frame, boxes, emb, stream_of_frame, score=None, n=None, xinv=None):
         """One launch on the current stream.  frame (n,) int32 batch index of every face row, boxes (n, 4) fp32 (the
@@ -361,7 +488,8 @@ class StreamTracker:
         or None; n: use the first n rows only (default: all); xinv: (n,) fp32 inverse norms of the rows of emb when the caller
         has them (default: fp_row_inv_norm here).  Device tensors; a frames / boxes tensor with a row stride (a
         column slice of info) is made contiguous.  -> dict(track_id, track_hits, track_clock, track_flags), (n,) int32 each;
-        with motion= also track_pred (n, 4) fp32: the box a matched row's track was predicted at, zeros for every other row."""
+        with motion= also track_pred (n, 4) fp32: the box a matched row's track was predicted at, zeros for every other row.
+        With reid= a row that continues a parked track carries REVIVED in track_flags (never NEW) and the track's old id."""
         n = int(emb.shape[0] if n is None else n)
         f32c = lambda t: t[:n].to(self.dev, torch.float32).contiguous()      # noqa: E731
         frame = frame[:n].to(self.dev, torch.int32).contiguous()
@@ -383,10 +511,17 @@ class StreamTracker:
             L.check(lib.fp_row_inv_norm(L.ptr(emb), n, self.D, L.ptr(xinv), L.current_stream(self.dev)), "fp_row_inv_norm")
         rows = (C.byref(self._struct), self.S, self.D, L.ptr(frame), L.ptr(boxes), L.ptr(emb), L.ptr(xinv), L.ptr(score), n,
                 L.ptr(sof), sof.shape[0], self.max_age, self.tau_near, self.tau_far, self.iou_min, *[L.ptr(out[k]) for k in OUT_KEYS])
+        if self.motion is not None:
+            out["track_pred"] = torch.empty((n, 4), dtype=torch.float32, device=self.dev)
+        if self.reid is not None:
+            tail = ((None, 0.0, 0.0, None) if self.motion is None else
+                    (L.ptr(self.state["motion"]), self.motion.std_pos, self.motion.std_vel, L.ptr(out["track_pred"])))
+            L.check(lib.fp_tracklets_step_reid(rows[0], C.byref(self._lost), *rows[1:], self.reid.tau_reid, self.reid.lost_age,
+                                               *tail, L.current_stream(self.dev)), "fp_tracklets_step_reid")
+            return out
         if self.motion is None:
             L.check(lib.fp_tracklets_step(*rows, L.current_stream(self.dev)), "fp_tracklets_step")
             return out
-        out["track_pred"] = torch.empty((n, 4), dtype=torch.float32, device=self.dev)
         L.check(lib.fp_tracklets_step_motion(*rows, L.ptr(self.state["motion"]), self.motion.std_pos, self.motion.std_vel,
                                              L.ptr(out["track_pred"]), L.current_stream(self.dev)), "fp_tracklets_step_motion")
         return out
@@ -413,6 +548,20 @@ class StreamTracker:
             t["velocity"] = m[:, :, M_V].copy()
         return t
 
+    def lost(self, stream):
+        """The parked tracks of one stream (a host read; ValueError without reid=): dict of numpy arrays entry, id, first_clock,
+        last_clock, hits, best_score, best_box, best_emb, in entry order."""
+        if self.reid is None:
+            raise ValueError("this tracker has no lost-track pool (reid=)")
+        s = int(stream)
+        if not 0 <= s < self.S:
+            raise ValueError(f"stream {stream} outside 0 .. {self.S - 1}")
+        li, lf = (self.state[k][s].cpu().numpy() for k in ("lost_i", "lost_f"))
+        e = np.nonzero(li[:, I_ID] != 0)[0]
+        return dict(entry=e, id=li[e, I_ID], first_clock=li[e, I_FIRST], last_clock=li[e, I_LAST], hits=li[e, I_HITS],
+                    best_score=lf[e, F_BEST_SCORE], best_box=lf[e, F_BEST_BOX:F_BEST_BOX + 4],
+                    best_emb=self.state["lost_best_emb"][s].cpu().numpy()[e])
+
     def reset(self, streams=None):
         """Forget the tracks, clocks and ids of `streams` (an iterable of stream indices; None: all)."""
         fresh = new_state(1, self.D)
@@ -421,6 +570,9 @@ class StreamTracker:
             self.state[k][idx] = torch.from_numpy(fresh[k][0]).to(self.dev)
         if self.motion is not None:
             self.state["motion"][idx] = 0
+        if self.reid is not None:
+            for k in LOST_KEYS:
+                self.state[k][idx] = 0
 
     def state_dict(self):
         """A copy of the device state and the parameters (host tensors)."""
@@ -429,12 +581,14 @@ class StreamTracker:
                            tau_far=self.tau_far, iou_min=self.iou_min)
         if self.motion is not None:
             d["params"].update(std_pos=self.motion.std_pos, std_vel=self.motion.std_vel)
+        if self.reid is not None:
+            d["params"].update(tau_reid=self.reid.tau_reid, lost_age=self.reid.lost_age)
         return d
 
     def load_state_dict(self, d):
         """The arrays of a state_dict of a tracker with the same n_streams and feat_dim (ValueError otherwise), copied into
         this tracker's own buffers; the parameters stay this tracker's.  A tracker with motion= needs the "motion" array too
-        (KeyError without it); one without ignores it."""
+        (KeyError without it); one without ignores it.  The same holds for the five LOST_KEYS arrays and reid=."""
         for k in self.state_keys:
             if tuple(d[k].shape) != tuple(self.state[k].shape):
                 raise ValueError(f"state_dict[{k!r}] has shape {tuple(d[k].shape)}, this tracker {tuple(self.state[k].shape)}")
@@ -442,8 +596,8 @@ class StreamTracker:
             self.state[k].copy_(torch.as_tensor(d[k]).to(self.state[k].dtype))
 
     def host_state(self):
-        """The state as a dict of numpy arrays (new_state's layout, plus "motion" with motion=): what track_step_numpy /
-        track_step_emulate continue from."""
+        """The state as a dict of numpy arrays (new_state's layout, plus "motion" with motion= and the LOST_KEYS arrays with
+        reid=): what track_step_numpy / track_step_emulate continue from."""
         return {k: self.state[k].detach().cpu().numpy().copy() for k in self.state_keys}
 
 

@@ -1550,6 +1550,79 @@ int fp_tracklets_step_motion_emulate(const fp_track_state* state, int n_streams,
                                      int32_t* track_flags, float* motion, float std_pos, float std_vel, float* track_pred);
 
 /*
+ * Tracklets: re-identification (build-defined; DESIGN §7 "Tracklets: re-identification"; csrc/tracklets.hip,
+ * tracklets_kernel<MOTION, true>).  Opt-in: fp_tracklets_step, fp_tracklets_step_motion and their state are untouched.  All
+ * additive: ABI 15.
+ *
+ * A track that expires is PARKED instead of dropped, and a face that no live track takes is compared with the parked tracks of
+ * its stream before it opens a new one: a returning face gets its old id back.  Two parameters: tau_reid, a cosine (finite),
+ * and lost_age > max_age, the number of frames after its last sighting for which a track is remembered.  Neither has a default:
+ * nothing has been measured on real video.
+ * State, owned by the caller beside the five arrays of "Tracklets" (fp_track_lost: five more, zero-filled for a fresh
+ * tracker), per stream s a ring of FP_TRACK_LOST = 64 entries; a parked track is literally its slot row:
+ *   lost_hdr      [S][2] int32                       ring head (used modulo FP_TRACK_LOST), spare
+ *   lost_i        [S][FP_TRACK_LOST][5] int32        the slot's slot_i row (id 0 = empty entry)
+ *   lost_f        [S][FP_TRACK_LOST][10] fp32        the slot's slot_f row
+ *   lost_emb      [S][FP_TRACK_LOST][D] fp32         the slot's last embedding;  lost_best_emb likewise: its best row's
+ * Per frame of stream s, numbered against the steps of "Tracklets":
+ *   1a. After clock += 1, every entry with id != 0 and clock - last_clock > lost_age is emptied (id = 0).
+ *   1.  The slots that expire (clock - last_clock > max_age) are parked, then freed: in ascending slot order the r-th of them goes
+ *       to entry (head + r) % 64, then head = (head + count) % 64.  The entry receives the slot's slot_i and slot_f rows, emb[slot]
+ *       and best_emb[slot]; what it held is overwritten (it is the oldest parked track).  A track parked in a frame can be revived
+ *       in that same frame.
+ *   2, 3. Unchanged (with motion, 1b too: a parked track has no filter).
+ *   3b. For every live detection d that the walk of step 3 left unmatched and every entry e with id != 0 whose stored inverse
+ *       norm is live: c = (dot(lost_emb_e, emb_d) * inv_e) * inv_d, the dot product in step 2's order; inv_e is the parked row's
+ *       inverse norm, so the pool compares LAST embeddings (a slot keeps no norm for best_emb).  The pair is admissible when
+ *       c > tau_reid (false for a NaN); there is no IoU gate, the person has moved.  Admissible pairs in the order of step 3 (c
+ *       descending, then lower entry, then lower position), walked the same greedy one-to-one way.
+ *   4.  Every live detection that step 3 left unmatched, revived or not, takes the lowest free slot by its rank among them in row
+ *       order, as before; one without a free slot gets id 0 and FP_TRACK_FULL, and the entry it had taken stays parked.  A
+ *       revived detection with a slot: the slot's slot_i and slot_f rows become the entry's (id, first_clock, hits, best_score,
+ *       best_clock and the best box continue), the entry is emptied, and the slot is then rewritten as by a match (hits + 1,
+ *       last_clock, last box, inverse norm, last embedding).  Step 5 holds for it as for a match: FP_TRACK_BEST only when score
+ *       is strictly greater than the carried best_score, otherwise best_emb[slot] = lost_best_emb[entry].  Its flags gain
+ *       FP_TRACK_REVIVED and never FP_TRACK_NEW.  next_id advances for true openings only: the k-th opening detection of the
+ *       frame, in row order, gets id next_id + k.
+ *   Motion.  With a motion array a revived slot's filters are initialised from the detection's box as at an opening, and its
+ *       track_pred row is zeros.
+ * As for the parent: a step equals the same frames split anywhere, interleaved streams equal each stream alone, scattered rows
+ * equal contiguous rows, two runs are bit-identical; the device and the emulator share every bit, another implementation agrees
+ * wherever no c of step 2 or 3b lies within D * 2^-24 of its threshold or of another c.
+ * Out of scope: re-identification across streams, pools of more than 64 tracks, a best-shot descriptor in place of the last
+ * embedding, and any measured value of tau_reid / lost_age.
+ *
+ * fp_tracklets_step_reid: fp_tracklets_step's launch shape and promises (one launch, one workgroup per stream; the pool's rows in
+ * LDS beside the slot table; no global atomics, no scratch, no host synchronisation).  Step 3b runs only in a frame that has
+ * both an unmatched live detection and a parked track.  motion NULL: the kernel of fp_tracklets_step plus the pool (std_pos,
+ * std_vel are ignored, track_pred must be NULL); motion not NULL: that of fp_tracklets_step_motion plus the pool.  Refusals before
+ * any launch: everything fp_tracklets_step (with motion: fp_tracklets_step_motion) refuses, a NULL lost or pool array, a pool
+ * embedding array not 16-byte aligned, lost_age <= max_age, a tau_reid that is not finite, a track_pred without motion.
+ * fp_tracklets_step_reid_emulate: the same decision code serially on HOST memory (every pointer HOST), the same bits.
+ */
+#define FP_TRACK_LOST 64
+#define FP_TRACK_REVIVED 64
+typedef struct fp_track_lost {
+  int32_t* lost_hdr;
+  int32_t* lost_i;
+  float* lost_f;
+  float* lost_emb;
+  float* lost_best_emb;
+} fp_track_lost;
+int fp_tracklets_step_reid(const fp_track_state* state /*host struct*/, const fp_track_lost* lost /*host struct*/, int n_streams,
+                           int D, const int32_t* frame, const float* box, const float* emb, const float* xinv,
+                           const float* score /* or NULL */, int n, const int32_t* stream_of_frame /* B */, int B, int max_age,
+                           float tau_near, float tau_far, float iou_min, int32_t* track_id, int32_t* track_hits,
+                           int32_t* track_clock, int32_t* track_flags, float tau_reid, int lost_age, float* motion /* or NULL */,
+                           float std_pos, float std_vel, float* track_pred /* n x 4, NULL iff motion is */, void* stream);
+int fp_tracklets_step_reid_emulate(const fp_track_state* state, const fp_track_lost* lost, int n_streams, int D,
+                                   const int32_t* frame, const float* box, const float* emb, const float* xinv,
+                                   const float* score, int n, const int32_t* stream_of_frame, int B, int max_age, float tau_near,
+                                   float tau_far, float iou_min, int32_t* track_id, int32_t* track_hits, int32_t* track_clock,
+                                   int32_t* track_flags, float tau_reid, int lost_age, float* motion, float std_pos,
+                                   float std_vel, float* track_pred);
+
+/*
  * Tracker evaluation: CLEAR-MOT and IDF1 (build-defined, the reference calls no tracking scorer; DESIGN §7 "Tracker
  * evaluation"; csrc/moteval.hip; tracking_eval.py holds the numpy restatement and the host half).  All additive: ABI 14.
  *

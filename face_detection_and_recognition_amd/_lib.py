@@ -204,6 +204,7 @@ SIGNATURES = {
     "fp_split3_bytes": (_SZ, [_I, _I]),
     "fp_split3_rows": (_I, [_P, _I, _I, _P, _P]),
     "fp_cosine_filter_x6": (_I, [_P, _P, _I64, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P]),
+    "fp_cosine_filter_x6_tile_rows": (_I, [_I64, _I]),
     "fp_cosine_topk_workspace": (_SZ, [_I64, _I, _I, _I]),
     "fp_cosine_topk_x6": (_I, [_P, _P, _I64, _P, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "fp_quant_i8_bytes": (_SZ, [_I, _I]),

@@ -510,12 +510,24 @@ int fp_split3_rows(const float* R, int Nr, int D, void* out, void* stream) {
   return FP_OK;
 }
 
+// 256-row tiles (two workgroups per CU) when they fill several rounds of workgroups, else 128-row tiles (three per CU).  The one
+// place where fp_cosine_filter_x6's form is chosen; 0: a grid the launcher refuses.
+int fp_cosine_filter_x6_tile_rows(int64_t M, int Nr) {
+  if (M < 0 || Nr <= 0) return 0;
+  const long nchunk = fp_round_up(Nr, CW_NC) / CW_NC;
+  const long big = (M + 255) / 256 * nchunk;
+  if (big >= (1L << 31)) return 0;
+  return big >= 2048 ? 256 : 128;
+}
+
 int fp_cosine_filter_x6(const float* G, const float* ginv, int64_t M, const void* R3, const float* rinv, int Nr, int D,
                         float tau, float* best, int32_t* arg, uint8_t* keep, uint64_t* packed, void* stream) {
   if (!G || !ginv || !R3 || !rinv || !best || !arg || !keep || !packed) return FP_ERR_INVALID_ARG;
   if (M < 0 || Nr <= 0 || D <= 0) return FP_ERR_INVALID_ARG;
   if (D % 32 || ((uintptr_t)G) % 16 || ((uintptr_t)R3) % 16 || ((uintptr_t)rinv) % 16) return FP_ERR_ALIGNMENT;
   if (M == 0) return FP_OK;
+  const int tile_rows = fp_cosine_filter_x6_tile_rows(M, Nr);
+  if (!tile_rows) return FP_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(packed, 0, (size_t)M * sizeof(uint64_t), s) != hipSuccess) {
     fp_set_hip_error(hipGetLastError());
@@ -523,14 +535,11 @@ int fp_cosine_filter_x6(const float* G, const float* ginv, int64_t M, const void
   }
   const int Npad = (int)fp_round_up(Nr, CW_NC);
   const long nchunk = Npad / CW_NC;
-  // 256-row tiles (two workgroups per CU) when they fill several rounds of workgroups, else 128-row tiles (three per CU)
-  const long big = (M + 255) / 256 * nchunk;
-  if (big >= 2048) {
-    if (big >= (1L << 31)) return FP_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((cosine_x6_kernel<4>), dim3((unsigned)big), dim3(256), CW_LDS, s, G, ginv, (long)M, (const unsigned short*)R3, rinv,
+  const long tiles = (M + tile_rows - 1) / tile_rows * nchunk;
+  if (tile_rows == 256) {
+    hipLaunchKernelGGL((cosine_x6_kernel<4>), dim3((unsigned)tiles), dim3(256), CW_LDS, s, G, ginv, (long)M, (const unsigned short*)R3, rinv,
                        Nr, Npad, D, (unsigned long long*)packed);
   } else {
-    const long tiles = (M + 127) / 128 * nchunk;
     hipLaunchKernelGGL((cosine_x6_kernel<2>), dim3((unsigned)tiles), dim3(256), CW_LDS, s, G, ginv, (long)M, (const unsigned short*)R3, rinv,
                        Nr, Npad, D, (unsigned long long*)packed);
   }

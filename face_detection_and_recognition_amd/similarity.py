@@ -39,7 +39,12 @@ def split3_rows(R):
 def cosine_filter(G, R, tau, ginv=None, rinv=None, r3=None, x6=None):
     """G (M, D) gallery, R (Nr, D) reference -> best (M,), arg (M,) int32, keep (M,) bool.
     The M x Nr score matrix is never materialised.  x6 (default: PlanBuilder.X6 and D a multiple of 32): S = G R^T on the
-    bf16 matrix cores with fp32-equivalent split arithmetic (r3 = split3_rows(R), computed here when not passed in)."""
+    bf16 matrix cores with fp32-equivalent split arithmetic (r3 = split3_rows(R), computed here when not passed in).
+    score = <G[m], R[j]> * ginv[m] * rinv[j]; on equal scores the lowest j.  Zero rows and masks (pinned by
+    tests/test_similarity_ops.py): an all-zero gallery row has ginv = inf, every score of it is NaN and it gives best = NaN,
+    arg = -1, keep = False; an all-zero reference row has rinv = inf, its scores are NaN and it never wins.  An explicitly
+    passed rinv of 0 is NOT a mask here, unlike ginv in cosine_topk: that column scores exactly 0 (+0 or -0) in every row and
+    wins wherever the other scores are negative.  To exclude a reference row, leave it out of R."""
     from .plan import PlanBuilder
     G, R = _f32c(G), _f32c(R)
     M, D = G.shape

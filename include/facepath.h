@@ -653,7 +653,11 @@ int fp_cosine_filter(const float* G, const float* ginv, int64_t M,
  * [D / 32][3][round_up(Nr, 128)][32] bf16, zero rows in the padding; D a multiple of 32), then every gallery batch runs
  * fp_cosine_filter_x6 against them.  Same results within fp32 rounding (best: 1e-6; arg: equal unless two scores tie within
  * it), 2x the rate of the fp32-MFMA kernel at 1 M x 10 k x 512.  rinv must be 16-byte aligned.
+ * fp_cosine_filter_x6_tile_rows (host only; added within ABI 15: a function only): the gallery rows of a workgroup's tile that
+ * fp_cosine_filter_x6 chooses for M x Nr -- 256 when ceil(M / 256) * ceil(Nr / 128) >= 2048, else 128; 0 for M < 0, Nr <= 0 and
+ * a grid of 2^31 workgroups or more, which the launcher refuses.  The launcher asks this function; results do not depend on it.
  */
+int fp_cosine_filter_x6_tile_rows(int64_t M, int Nr);
 size_t fp_split3_bytes(int Nr, int D);
 int fp_split3_rows(const float* R, int Nr, int D, void* out, void* stream);
 int fp_cosine_filter_x6(const float* G, const float* ginv, int64_t M,

@@ -158,6 +158,11 @@ _SZ = C.c_size_t
 _I64 = C.c_int64
 _D = C.c_double
 
+# the six fp_tracklets_step* entry points: [state(, lost)] + rows (+ reid tail) (+ motion tail) (+ stream on the device path)
+_TK_ROWS = [_I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P]   # n_streams .. track_flags
+_TK_MOTION = [_P, _F, _F, _P]                                                         # motion, std_pos, std_vel, track_pred
+_TK_REID = [_F, _I]                                                                   # tau_reid, lost_age
+
 # name -> (restype, argtypes); every symbol declared in include/facepath.h
 SIGNATURES = {
     "fp_abi_version": (_I, []),
@@ -268,17 +273,12 @@ SIGNATURES = {
     "fp_merge_views": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _F, _I, _P, _P, _P, _P]),
     "fp_merge_views_emulate": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _F, _I, _P, _P, _P]),
     "fp_gather_tiles": (_I, [_P, _SZ, _P, _I, _P, _I, _I, _I, _P, _P]),
-    "fp_tracklets_step": (_I, [C.POINTER(FpTrackState), _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P]),
-    "fp_tracklets_step_emulate": (_I, [C.POINTER(FpTrackState), _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _F, _F, _F, _P, _P, _P,
-                                       _P]),
-    "fp_tracklets_step_motion": (_I, [C.POINTER(FpTrackState), _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P,
-                                      _P, _F, _F, _P, _P]),
-    "fp_tracklets_step_motion_emulate": (_I, [C.POINTER(FpTrackState), _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _F, _F, _F, _P, _P,
-                                              _P, _P, _P, _F, _F, _P]),
-    "fp_tracklets_step_reid": (_I, [C.POINTER(FpTrackState), C.POINTER(FpTrackLost), _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _F, _F,
-                                    _F, _P, _P, _P, _P, _F, _I, _P, _F, _F, _P, _P]),
-    "fp_tracklets_step_reid_emulate": (_I, [C.POINTER(FpTrackState), C.POINTER(FpTrackLost), _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I,
-                                            _F, _F, _F, _P, _P, _P, _P, _F, _I, _P, _F, _F, _P]),
+    "fp_tracklets_step": (_I, [C.POINTER(FpTrackState)] + _TK_ROWS + [_P]),
+    "fp_tracklets_step_emulate": (_I, [C.POINTER(FpTrackState)] + _TK_ROWS),
+    "fp_tracklets_step_motion": (_I, [C.POINTER(FpTrackState)] + _TK_ROWS + _TK_MOTION + [_P]),
+    "fp_tracklets_step_motion_emulate": (_I, [C.POINTER(FpTrackState)] + _TK_ROWS + _TK_MOTION),
+    "fp_tracklets_step_reid": (_I, [C.POINTER(FpTrackState), C.POINTER(FpTrackLost)] + _TK_ROWS + _TK_REID + _TK_MOTION + [_P]),
+    "fp_tracklets_step_reid_emulate": (_I, [C.POINTER(FpTrackState), C.POINTER(FpTrackLost)] + _TK_ROWS + _TK_REID + _TK_MOTION),
     "fp_mot_match_workspace": (_SZ, [_I64, _I64]),
     "fp_mot_match": (_I, [_P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I64, _D, _P, _P, _P, _P, _P, _SZ, _P]),
     "fp_mot_match_emulate": (_I, [_P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I64, _D, _P, _P, _P, _P, _P,

@@ -2,35 +2,36 @@
 // (DESIGN §7 "Tracklets"; include/facepath.h states the procedure; tracker.hip stays the port of the reference's per-frame
 // first-match rule).  Build with -ffp-contract=off: the IoU gate and the cosine are the same bits on device and host emulator.
 //
-// 1. fp_tracklets_step: ONE launch, one workgroup per stream; a workgroup whose stream owns no frame of the step leaves after
-//    the first pass.  That pass reads frame[] once: the min / max frame index of every chunk of rows goes to LDS (so a frame's
-//    rows are later looked for only in the chunks that can hold them: one or two when the rows come in frame order, all of
-//    them at worst), and the rows nobody tracks get their NO_STREAM outputs from the workgroup that owns their chunk.  Then
-//    the workgroup marches over its frames in ascending batch index with the stream's slot table in LDS:
-//      expiry -> the frame's rows by ballot compaction in row order -> live tracks x live detections, one pair per 16 lanes
-//      (float4 loads, xor-shuffle sum) -> 64-bit keys in LDS (~ord(c) << 32 | slot << 8 | position: ascending = c descending,
-//      lower slot, lower row) -> bitonic sort -> wave 0 walks the keys 64 at a time with a ballot per taken pair (two 64-bit
-//      masks: tracks and detections already taken) -> the unmatched detections open tracks in the lowest free slots by rank
-//      -> slot fields in LDS, embeddings copied in global memory by the whole workgroup.
-//    No global atomics, no scratch, no host synchronisation: two runs are bit-identical.
-// 2. fp_tracklets_step_emulate: the same __host__ __device__ decision code (liveness, dot product in the device's order, IoU,
-//    admissibility, key) run serially on host memory, std::sort for the keys (the order is total).
-// 3. fp_tracklets_step_motion / _emulate: the same kernel as tracklets_kernel<true, *> ("Tracklets: motion prediction" in
-//    include/facepath.h).  The slot's four constant-velocity filters (20 floats) and the predicted boxes sit in LDS beside the
-//    slot table; step 1b predicts one (slot, coordinate) per thread on the first 256 threads, the pair phase takes its IoU with
-//    the predicted box, wave 0 updates / opens the filters where it rewrites the slots.  tracklets_kernel<false, *> is the kernel
-//    of 1: no motion array is read, nothing of it is compiled in.
-// 4. fp_tracklets_step_reid / _emulate: tracklets_kernel<MOTION, true> ("Tracklets: re-identification" in include/facepath.h).
-//    The stream's pool of parked tracks (FP_TRACK_LOST slot rows, ints and floats) sits in LDS beside the slot table, their
-//    embeddings stay in global memory.  Every wave finds the expiring slots by a ballot of its own (64 slots, 64 lanes), wave 0
-//    moves their rows into the ring, the whole workgroup copies their embeddings.  Step 3b (the detections the walk left
-//    unmatched x the parked tracks) reuses key[], the sort and the walk, and runs only in a frame that has both: a frame with
-//    an empty pool pays one workgroup-uniform test, one with parked tracks and no unmatched detection one barrier more.
-//    tracklets_kernel<*, false> are the kernels of 1 and 3: nothing of the pool is read or compiled in.
+// One kernel, tracklets_kernel<MOTION, REID>, one host twin, emulate_step, and one argument struct, TrackArgs, whose motion and
+// pool pointers are null where the caller has neither.  The six fp_tracklets_step* entry points build the arguments and hand
+// them to run(), which checks them (before any HIP call), then launches the instantiation the arguments name or calls the twin.
+//
+// The kernel: ONE launch, one workgroup per stream; a workgroup whose stream owns no frame of the step leaves after the first
+// pass.  That pass reads frame[] once: the min / max frame index of every chunk of rows goes to LDS (so a frame's rows are later
+// looked for only in the chunks that can hold them: one or two when the rows come in frame order, all of them at worst), and
+// the rows nobody tracks get their NO_STREAM outputs from the workgroup that owns their chunk.  Then the workgroup marches over
+// its frames in ascending batch index with the stream's slot table in LDS:
+//   1.  expiry.  REID: every wave finds the expiring slots by a ballot of its own, wave 0 moves their rows into the pool's ring
+//       (the stream's FP_TRACK_LOST parked tracks, ints and floats in LDS, embeddings in global memory), everybody copies their
+//       embeddings.  1b, MOTION: the slot's four constant-velocity filters and the predicted boxes sit in LDS beside the slot
+//       table; one (slot, coordinate) per thread on the first 256 threads.
+//   2.  the frame's rows by ballot compaction in row order.
+//   3.  live tracks x live detections, one pair per 16 lanes (tk_dot16: float4 loads, xor-shuffle sum; IoU with the predicted
+//       box under MOTION) -> 64-bit keys in LDS (~ord(c) << 32 | slot << 8 | position: ascending = c descending, lower slot,
+//       lower row) -> tk_sort (bitonic) -> tk_walk: wave 0 takes the keys 64 at a time with a ballot per taken pair.
+//       (<true, false> alone carries the text of the two written out, for a measured 0.9 %: WRITTEN_OUT in the kernel.)
+//   3b. REID, only in a frame that has parked tracks and unmatched detections: those x those through the same tk_dot16, key[],
+//       tk_sort and tk_walk, the cosine alone deciding.  An empty pool costs one workgroup-uniform test.
+//   4,5 the unmatched detections open tracks in the lowest free slots by rank (or continue the parked track they took) -> slot
+//       fields in LDS, filters updated / opened by wave 0, embeddings copied in global memory by the whole workgroup.
+// No global atomics, no scratch, no host synchronisation: two runs are bit-identical.  What an instantiation does not use is
+// not compiled into it: <false, *> reads no motion array, <*, false> nothing of the pool.
+//
+// The twin runs the same __host__ __device__ decision code (liveness, dot product in the device's order, IoU, admissibility,
+// key, filters, slot rewrite) serially on host memory, std::sort for the keys (the order is total).
 #include <limits.h>
 
 #include <algorithm>
-#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -77,20 +78,13 @@ struct TrackArgs {
   float* motion;        // [S][SLOTS][MF]; null without motion prediction
   float std_pos, std_vel;
   float* o_pred;        // [n][4]
-};
-
-// re-identification: the pool and its parameters.  The kernels with a pool take ReidArgs, those without it TrackArgs as ever.
-struct LostArgs {
-  int* lhdr;            // [S][2] ring head, spare
+  int* lhdr;            // [S][2] ring head, spare; the five pool arrays are null without re-identification
   int* li;              // [S][LOST][NI]
   float* lf;            // [S][LOST][NF]
   float* lemb;          // [S][LOST][D]
   float* lbest;         // [S][LOST][D]
   float tau_reid;
   int lost_age;
-};
-struct ReidArgs : TrackArgs {
-  LostArgs l;
 };
 
 // ---------------------------------------------------------------------------------------- the decision code, host and device
@@ -304,6 +298,17 @@ __device__ __forceinline__ int tk_walk(const unsigned long long* key, int n_vali
   return mine;
 }
 
+// The dot product of a track-side row and a detection's row by one group of 16 lanes (gl: the lane within the group): the
+// partials, then xor 8, 4, 2, 1, so every lane of the group returns the same sum.
+__device__ __forceinline__ float tk_dot16(const float* t, const float* d, int D, int gl) {
+  float v = tk_partial(t, d, D, gl);
+  v += __shfl_xor(v, 8);
+  v += __shfl_xor(v, 4);
+  v += __shfl_xor(v, 2);
+  v += __shfl_xor(v, 1);
+  return v;
+}
+
 // the r-th set bit of m (r < popcount)
 __device__ __forceinline__ int tk_nth_bit(unsigned long long m, int r) {
   for (int k = 0; k < r; ++k) m &= m - 1ull;
@@ -311,8 +316,12 @@ __device__ __forceinline__ int tk_nth_bit(unsigned long long m, int r) {
 }
 
 template <bool MOTION, bool REID>
-__global__ __launch_bounds__(TPB) void tracklets_kernel(std::conditional_t<REID, ReidArgs, TrackArgs> a) {
-  const TrackArgs& p = a;
+__global__ __launch_bounds__(TPB) void tracklets_kernel(TrackArgs p) {
+  // <true, false> alone keeps the text of tk_sort and tk_walk written out in step 3.  Measured (FINDINGS 87): through the calls
+  // that one instantiation marched 0.9 % slower on 256 frames x 2 faces (1.360 against 1.348 ms) and 0.9 % slower on 256 x 8
+  // (6.034 against 5.978 ms), same VGPRs, 2 042 instructions against 2 043; written out it is at the old time again.  The other
+  // three go through the calls and are as fast or 1 - 1.5 % faster.  A change of the sort or the walk is made in both places.
+  constexpr bool WRITTEN_OUT = MOTION && !REID;
   __shared__ unsigned long long key[SLOTS * MAXD];   // 32 KB
   __shared__ int cmin[MAXCH], cmax[MAXCH];
   __shared__ int s_i[SLOTS][NI];
@@ -342,8 +351,8 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(std::conditional_t<REID,
   for (int i = tid; i < SLOTS * NI; i += TPB) (&s_i[0][0])[i] = p.si[(long)s * SLOTS * NI + i];
   for (int i = tid; i < SLOTS * NF; i += TPB) (&s_f[0][0])[i] = p.sf[(long)s * SLOTS * NF + i];
   if constexpr (REID) {
-    for (int i = tid; i < LOST * NI; i += TPB) (&l_i[0][0])[i] = a.l.li[(long)s * LOST * NI + i];
-    for (int i = tid; i < LOST * NF; i += TPB) (&l_f[0][0])[i] = a.l.lf[(long)s * LOST * NF + i];
+    for (int i = tid; i < LOST * NI; i += TPB) (&l_i[0][0])[i] = p.li[(long)s * LOST * NI + i];
+    for (int i = tid; i < LOST * NF; i += TPB) (&l_f[0][0])[i] = p.lf[(long)s * LOST * NF + i];
   }
   __syncthreads();
 
@@ -370,9 +379,9 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(std::conditional_t<REID,
   float* lemb = nullptr;
   float* lbest = nullptr;
   if constexpr (REID) {
-    head = a.l.lhdr[2 * s];   // taken modulo LOST wherever it is used
-    lemb = a.l.lemb + (long)s * LOST * D;
-    lbest = a.l.lbest + (long)s * LOST * D;
+    head = p.lhdr[2 * s];   // taken modulo LOST wherever it is used
+    lemb = p.lemb + (long)s * LOST * D;
+    lbest = p.lbest + (long)s * LOST * D;
   }
 
   for (int f0 = 0; f0 < p.B; f0 += TPB) {
@@ -410,7 +419,7 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(std::conditional_t<REID,
         }
         if constexpr (REID) {
           // ---- 1a. the pool forgets; 1. the expiring slots are parked: the r-th of them, ascending, in entry (head + r) % LOST
-          if (tid < LOST && l_i[tid][I_ID] != 0 && clock - l_i[tid][I_LAST] > a.l.lost_age) l_i[tid][I_ID] = 0;
+          if (tid < LOST && l_i[tid][I_ID] != 0 && clock - l_i[tid][I_LAST] > p.lost_age) l_i[tid][I_ID] = 0;
           if (exm != 0ull) {   // every wave holds the same mask
             if constexpr (!MOTION) __syncthreads();   // every wave has read the slots (MOTION: the barrier above)
             const int n_ex = __popcll(exm);
@@ -505,11 +514,7 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(std::conditional_t<REID,
             const int q = min(q0 + grp, np - 1);
             const int slot = lt[q / nD], pos = ld[q % nD];
             const long row = det_row[pos];
-            float v = tk_partial(semb + (long)slot * D, p.emb + row * D, D, gl);
-            v += __shfl_xor(v, 8);
-            v += __shfl_xor(v, 4);
-            v += __shfl_xor(v, 2);
-            v += __shfl_xor(v, 1);
+            const float v = tk_dot16(semb + (long)slot * D, p.emb + row * D, D, gl);
             if (gl == 0 && q0 + grp < np) {
               const float c = tk_cos(v, s_f[slot][F_INV], det_inv[pos]);
               const float iou = tk_iou(MOTION ? s_pb[slot] : &s_f[slot][F_BOX], p.box + row * 4);
@@ -518,34 +523,61 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(std::conditional_t<REID,
           }
           for (int i = np + tid; i < n_sort; i += TPB) key[i] = KEY_NONE;
           __syncthreads();
-
-          for (int k = 2; k <= n_sort; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-              for (int t = tid; t < (n_sort >> 1); t += TPB) {
-                const int i = 2 * t - (t & (j - 1)), r = i + j;
-                const unsigned long long a = key[i], b = key[r];
-                if ((a > b) == ((i & k) == 0)) {
-                  key[i] = b;
-                  key[r] = a;
+          if constexpr (!WRITTEN_OUT) {
+            n_valid = tk_sort(key, n_sort, tid);
+          } else {   // tk_sort's text
+            for (int k = 2; k <= n_sort; k <<= 1)
+              for (int j = k >> 1; j > 0; j >>= 1) {
+                for (int t = tid; t < (n_sort >> 1); t += TPB) {
+                  const int i = 2 * t - (t & (j - 1)), r = i + j;
+                  const unsigned long long a = key[i], b = key[r];
+                  if ((a > b) == ((i & k) == 0)) {
+                    key[i] = b;
+                    key[r] = a;
+                  }
                 }
+                __syncthreads();
               }
-              __syncthreads();
-            }
-          for (int step = n_sort; step > 0; step >>= 1)   // the keys in front of the first KEY_NONE
-            if (n_valid + step <= n_sort && key[n_valid + step - 1] != KEY_NONE) n_valid += step;
+            for (int step = n_sort; step > 0; step >>= 1)
+              if (n_valid + step <= n_sort && key[n_valid + step - 1] != KEY_NONE) n_valid += step;
+          }
         }
 
-        // ---- 3 (walk) with a pool: wave 0 alone, then 3b by everybody.  (Steps 3 to 5 without a pool stand below as they always
-        // did, sort and walk written out: moving them into the functions of 3b changed the schedule of tracklets_kernel<*, false>.)
-        int walked = -1, my_ent = -1;
-        if constexpr (REID)
-          if (wave == 0) walked = tk_walk(key, n_valid, min(nT, nD), lane);
+        // ---- 3 (walk): wave 0; lane j stands for the detection at position j
+        int my_slot = -1, my_ent = -1;
+        if (wave == 0) {
+          if constexpr (!WRITTEN_OUT) {
+            my_slot = tk_walk(key, n_valid, min(nT, nD), lane);
+          } else {   // tk_walk's text
+            unsigned long long t_taken = 0ull, d_taken = 0ull;
+            const int most = min(nT, nD);
+            int taken = 0;
+            for (int i0 = 0; i0 < n_valid && taken < most; i0 += FP_WAVE) {
+              const int i = i0 + lane;
+              const bool have = i < n_valid;
+              const unsigned long long kk = have ? key[i] : 0ull;
+              const int k_slot = tk_key_slot(kk), k_pos = tk_key_pos(kk);
+              bool alive = have && !((t_taken >> k_slot) & 1ull) && !((d_taken >> k_pos) & 1ull);
+              unsigned long long live = __ballot(alive);
+              while (live) {
+                const int l = __ffsll((long long)live) - 1;
+                const int w_slot = __shfl(k_slot, l), w_pos = __shfl(k_pos, l);
+                t_taken |= 1ull << w_slot;
+                d_taken |= 1ull << w_pos;
+                ++taken;
+                if (lane == w_pos) my_slot = w_slot;
+                if (alive && (k_slot == w_slot || k_pos == w_pos)) alive = false;
+                live = __ballot(alive);
+              }
+            }
+          }
+        }
 
         // ---- 3b. the live detections the walk left unmatched x the parked tracks: cosine alone, the same key, sort and walk
         if constexpr (REID) {
           if (pm != 0ull) {   // workgroup-uniform: a frame with an empty pool goes straight on
             if (wave == 0) {
-              const bool un = lane < nd && det_inv[lane] > 0.f && walked < 0;
+              const bool un = lane < nd && det_inv[lane] > 0.f && my_slot < 0;
               const unsigned long long um = __ballot(un);
               if (un) lu[__popcll(um & lane_lt)] = lane;
               if (lane == 0) s_nU = __popcll(um);
@@ -561,14 +593,10 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(std::conditional_t<REID,
               for (int q0 = 0; q0 < nq; q0 += NG) {
                 const int q = min(q0 + grp, nq - 1);
                 const int ent = le[q / nU], pos = lu[q % nU];
-                float v = tk_partial(lemb + (long)ent * D, p.emb + (long)det_row[pos] * D, D, gl);
-                v += __shfl_xor(v, 8);
-                v += __shfl_xor(v, 4);
-                v += __shfl_xor(v, 2);
-                v += __shfl_xor(v, 1);
+                const float v = tk_dot16(lemb + (long)ent * D, p.emb + (long)det_row[pos] * D, D, gl);
                 if (gl == 0 && q0 + grp < nq) {
                   const float c = tk_cos(v, l_f[ent][F_INV], det_inv[pos]);
-                  key[q] = c > a.l.tau_reid ? tk_key(c, ent, pos) : KEY_NONE;
+                  key[q] = c > p.tau_reid ? tk_key(c, ent, pos) : KEY_NONE;
                 }
               }
               for (int i = nq + tid; i < n_sort; i += TPB) key[i] = KEY_NONE;
@@ -579,35 +607,8 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(std::conditional_t<REID,
           }
         }
 
-        // ---- 3 (walk), 4, 5: wave 0; lane j stands for the detection at position j
+        // ---- 4, 5: wave 0.  The unmatched live detections open tracks in the lowest free slots, in row order
         if (wave == 0) {
-          int my_slot = -1;
-          if constexpr (REID) {
-            my_slot = walked;
-          } else {
-            unsigned long long t_taken = 0ull, d_taken = 0ull;
-            const int most = min(nT, nD);
-            int taken = 0;
-            for (int i0 = 0; i0 < n_valid && taken < most; i0 += FP_WAVE) {
-              const int i = i0 + lane;
-              const bool have = i < n_valid;
-              const unsigned long long kk = have ? key[i] : 0ull;
-              const int k_slot = tk_key_slot(kk), k_pos = tk_key_pos(kk);
-              bool alive = have && !((t_taken >> k_slot) & 1ull) && !((d_taken >> k_pos) & 1ull);
-              unsigned long long live = __ballot(alive);
-              while (live) {
-                const int l = __ffsll((long long)live) - 1;   // the first pair of the batch still free is taken
-                const int w_slot = __shfl(k_slot, l), w_pos = __shfl(k_pos, l);
-                t_taken |= 1ull << w_slot;
-                d_taken |= 1ull << w_pos;
-                ++taken;
-                if (lane == w_pos) my_slot = w_slot;
-                if (alive && (k_slot == w_slot || k_pos == w_pos)) alive = false;
-                live = __ballot(alive);
-              }
-            }
-          }
-          // the unmatched live detections open tracks in the lowest free slots, in row order
           const bool dl = lane < nd && det_inv[lane] > 0.f;
           const bool matched = my_slot >= 0;
           const unsigned long long freem = __ballot(s_i[lane][I_ID] == 0);
@@ -686,9 +687,9 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(std::conditional_t<REID,
     if (owned)
       for (int i = tid; i < SLOTS * MF; i += TPB) p.motion[(long)s * SLOTS * MF + i] = (&s_m[0][0])[i];
   if constexpr (REID) {
-    for (int i = tid; i < LOST * NI; i += TPB) a.l.li[(long)s * LOST * NI + i] = (&l_i[0][0])[i];
-    for (int i = tid; i < LOST * NF; i += TPB) a.l.lf[(long)s * LOST * NF + i] = (&l_f[0][0])[i];
-    if (tid == 0) a.l.lhdr[2 * s] = head;
+    for (int i = tid; i < LOST * NI; i += TPB) p.li[(long)s * LOST * NI + i] = (&l_i[0][0])[i];
+    for (int i = tid; i < LOST * NF; i += TPB) p.lf[(long)s * LOST * NF + i] = (&l_f[0][0])[i];
+    if (tid == 0) p.lhdr[2 * s] = head;
   }
   if (tid == 0) {
     p.hdr[2 * s] = clock;
@@ -696,30 +697,13 @@ __global__ __launch_bounds__(TPB) void tracklets_kernel(std::conditional_t<REID,
   }
 }
 
-int check_track(const TrackArgs& a, const fp_track_state* st) {
-  if (!st || !a.hdr || !a.si || !a.sf || !a.semb || !a.sbest) return FP_ERR_INVALID_ARG;
-  if (a.S < 1 || a.D < 4 || a.D % 4 != 0 || a.D > FP_TRACK_MAX_DIM || a.n < 0 || a.n > FP_TRACK_MAX_ROWS || a.B < 0 || a.max_age < 0) return FP_ERR_INVALID_ARG;
-  if (a.B > 0 && !a.sof) return FP_ERR_INVALID_ARG;
-  if (a.n > 0 && (!a.frame || !a.box || !a.emb || !a.xinv || !a.o_id || !a.o_hits || !a.o_clock || !a.o_flags))
-    return FP_ERR_INVALID_ARG;
-  if (((uintptr_t)a.semb | (uintptr_t)a.sbest | (uintptr_t)a.emb) % 16 != 0) return FP_ERR_INVALID_ARG;   // float4 rows
-  if (!(a.tau_far >= a.tau_near) || a.iou_min != a.iou_min) return FP_ERR_INVALID_ARG;
-  return FP_OK;
-}
-
-// the motion entry points: check_track's refusals and their own
-int check_motion(const TrackArgs& a, const fp_track_state* st) {
-  const int rc = check_track(a, st);
-  if (rc != FP_OK) return rc;
-  if (!a.motion || (a.n > 0 && !a.o_pred)) return FP_ERR_INVALID_ARG;
-  if (!(a.std_pos > 0.f && tk_finite(a.std_pos) && a.std_vel > 0.f && tk_finite(a.std_vel))) return FP_ERR_INVALID_ARG;
-  return FP_OK;
-}
-
+// ------------------------------------------------------------------------------------------ arguments: one builder, one checker
+// The tails an entry point does not have stay at their defaults: no motion array, no pool.
 TrackArgs track_args(const fp_track_state* st, int n_streams, int D, const int32_t* frame, const float* box, const float* emb,
                      const float* xinv, const float* score, int n, const int32_t* stream_of_frame, int B, int max_age,
                      float tau_near, float tau_far, float iou_min, int32_t* track_id, int32_t* track_hits, int32_t* track_clock,
-                     int32_t* track_flags) {
+                     int32_t* track_flags, float* motion = nullptr, float std_pos = 0.f, float std_vel = 0.f,
+                     float* track_pred = nullptr, const fp_track_lost* lost = nullptr, float tau_reid = 0.f, int lost_age = 0) {
   TrackArgs a;
   a.hdr = st ? st->hdr : nullptr;
   a.si = st ? st->slot_i : nullptr;
@@ -731,56 +715,86 @@ TrackArgs track_args(const fp_track_state* st, int n_streams, int D, const int32
   a.sof = stream_of_frame; a.B = B;
   a.max_age = max_age; a.tau_near = tau_near; a.tau_far = tau_far; a.iou_min = iou_min;
   a.o_id = track_id; a.o_hits = track_hits; a.o_clock = track_clock; a.o_flags = track_flags;
-  a.motion = nullptr; a.std_pos = a.std_vel = 0.f; a.o_pred = nullptr;
+  a.motion = motion; a.std_pos = std_pos; a.std_vel = std_vel; a.o_pred = track_pred;
+  a.lhdr = lost ? lost->lost_hdr : nullptr;
+  a.li = lost ? lost->lost_i : nullptr;
+  a.lf = lost ? lost->lost_f : nullptr;
+  a.lemb = lost ? lost->lost_emb : nullptr;
+  a.lbest = lost ? lost->lost_best_emb : nullptr;
+  a.tau_reid = tau_reid; a.lost_age = lost_age;
   return a;
 }
 
-ReidArgs with_reid(const TrackArgs& t, const fp_track_lost* lost, float tau_reid, int lost_age) {
-  ReidArgs a;
-  static_cast<TrackArgs&>(a) = t;
-  a.l.lhdr = lost ? lost->lost_hdr : nullptr;
-  a.l.li = lost ? lost->lost_i : nullptr;
-  a.l.lf = lost ? lost->lost_f : nullptr;
-  a.l.lemb = lost ? lost->lost_emb : nullptr;
-  a.l.lbest = lost ? lost->lost_best_emb : nullptr;
-  a.l.tau_reid = tau_reid; a.l.lost_age = lost_age;
-  return a;
-}
+// what an entry point requires of the two optional parts
+enum NeedMotion { MOTION_ABSENT, MOTION_OPTIONAL, MOTION_REQUIRED };
+struct Needs {
+  NeedMotion motion;
+  bool pool;
+};
 
-// the re-identification entry points: check_track's refusals (check_motion's with a motion array) and their own
-int check_reid(const ReidArgs& a, const fp_track_state* st, const fp_track_lost* lost) {
-  const int rc = a.motion ? check_motion(a, st) : check_track(a, st);
-  if (rc != FP_OK) return rc;
-  if (!a.motion && a.o_pred) return FP_ERR_INVALID_ARG;   // track_pred is null iff motion is
-  if (!lost || !a.l.lhdr || !a.l.li || !a.l.lf || !a.l.lemb || !a.l.lbest) return FP_ERR_INVALID_ARG;
-  if (((uintptr_t)a.l.lemb | (uintptr_t)a.l.lbest) % 16 != 0) return FP_ERR_INVALID_ARG;   // float4 rows
-  if (!tk_finite(a.l.tau_reid) || a.l.lost_age <= a.max_age) return FP_ERR_INVALID_ARG;
+int check_args(const TrackArgs& a, Needs need) {
+  if (!a.hdr || !a.si || !a.sf || !a.semb || !a.sbest) return FP_ERR_INVALID_ARG;   // a null state struct gave five nulls
+  if (a.S < 1 || a.D < 4 || a.D % 4 != 0 || a.D > FP_TRACK_MAX_DIM || a.n < 0 || a.n > FP_TRACK_MAX_ROWS || a.B < 0 || a.max_age < 0) return FP_ERR_INVALID_ARG;
+  if (a.B > 0 && !a.sof) return FP_ERR_INVALID_ARG;
+  if (a.n > 0 && (!a.frame || !a.box || !a.emb || !a.xinv || !a.o_id || !a.o_hits || !a.o_clock || !a.o_flags))
+    return FP_ERR_INVALID_ARG;
+  if (((uintptr_t)a.semb | (uintptr_t)a.sbest | (uintptr_t)a.emb) % 16 != 0) return FP_ERR_INVALID_ARG;   // float4 rows
+  if (!(a.tau_far >= a.tau_near) || a.iou_min != a.iou_min) return FP_ERR_INVALID_ARG;
+  if (a.motion ? need.motion == MOTION_ABSENT : need.motion == MOTION_REQUIRED) return FP_ERR_INVALID_ARG;
+  if (a.motion) {
+    if (a.n > 0 && !a.o_pred) return FP_ERR_INVALID_ARG;
+    if (!(a.std_pos > 0.f && tk_finite(a.std_pos) && a.std_vel > 0.f && tk_finite(a.std_vel))) return FP_ERR_INVALID_ARG;
+  } else if (a.o_pred) {   // track_pred is null iff motion is; std_pos / std_vel are not looked at
+    return FP_ERR_INVALID_ARG;
+  }
+  if (need.pool) {
+    if (!a.lhdr || !a.li || !a.lf || !a.lemb || !a.lbest) return FP_ERR_INVALID_ARG;   // a null pool struct gave five nulls
+    if (((uintptr_t)a.lemb | (uintptr_t)a.lbest) % 16 != 0) return FP_ERR_INVALID_ARG;   // float4 rows
+    if (!tk_finite(a.tau_reid) || a.lost_age <= a.max_age) return FP_ERR_INVALID_ARG;
+  }
   return FP_OK;
 }
 
-TrackArgs with_motion(TrackArgs a, float* motion, float std_pos, float std_vel, float* track_pred) {
-  a.motion = motion; a.std_pos = std_pos; a.std_vel = std_vel; a.o_pred = track_pred;
-  return a;
+// ---------------------------------------------------------------------------------------------------------- the host twin
+// the cosine of one pair: the 16 partials, then the xor-shuffle sum as lane 0 sees it
+float emu_cos(const float* t, const float* d, int D, float inv_t, float inv_d) {
+  float part[GL];
+  for (int gl = 0; gl < GL; ++gl) part[gl] = tk_partial(t, d, D, gl);
+  for (int off = GL / 2; off > 0; off >>= 1)
+    for (int l = 0; l < off; ++l) part[l] = part[l] + part[l + off];
+  return tk_cos(part[0], inv_t, inv_d);
 }
 
-// ---------------------------------------------------------------------------------------------------------- the host twin
-void emulate_frame(const TrackArgs& p, const LostArgs* lo, int s, int f, int& clock, int& next_id,
-                   std::vector<unsigned long long>& key) {
+// the keys in ascending order, each taken unless its track-side partner or its position is: partner[position], -1 where none
+void emu_greedy(std::vector<unsigned long long>& key, int* partner) {
+  std::sort(key.begin(), key.end());
+  for (int j = 0; j < MAXD; ++j) partner[j] = -1;
+  unsigned long long t_taken = 0ull, d_taken = 0ull;
+  for (size_t i = 0; i < key.size(); ++i) {
+    const int k_slot = tk_key_slot(key[i]), k_pos = tk_key_pos(key[i]);
+    if (((t_taken >> k_slot) & 1ull) || ((d_taken >> k_pos) & 1ull)) continue;
+    t_taken |= 1ull << k_slot;
+    d_taken |= 1ull << k_pos;
+    partner[k_pos] = k_slot;
+  }
+}
+
+void emulate_frame(const TrackArgs& p, int s, int f, int& clock, int& next_id, std::vector<unsigned long long>& key) {
   int* si = p.si + (long)s * SLOTS * NI;
   float* sf = p.sf + (long)s * SLOTS * NF;
   float* semb = p.semb + (long)s * SLOTS * p.D;
   float* sbest = p.sbest + (long)s * SLOTS * p.D;
   clock += 1;
-  int* li = lo ? lo->li + (long)s * LOST * NI : nullptr;   // the pool; null without re-identification
-  float* lf = lo ? lo->lf + (long)s * LOST * NF : nullptr;
-  float* lemb = lo ? lo->lemb + (long)s * LOST * p.D : nullptr;
-  float* lbest = lo ? lo->lbest + (long)s * LOST * p.D : nullptr;
+  int* li = p.li ? p.li + (long)s * LOST * NI : nullptr;   // the pool; null without re-identification
+  float* lf = li ? p.lf + (long)s * LOST * NF : nullptr;
+  float* lemb = li ? p.lemb + (long)s * LOST * p.D : nullptr;
+  float* lbest = li ? p.lbest + (long)s * LOST * p.D : nullptr;
   for (int e = 0; li && e < LOST; ++e)   // step 1a
-    if (li[e * NI + I_ID] != 0 && clock - li[e * NI + I_LAST] > lo->lost_age) li[e * NI + I_ID] = 0;
+    if (li[e * NI + I_ID] != 0 && clock - li[e * NI + I_LAST] > p.lost_age) li[e * NI + I_ID] = 0;
   for (int t = 0; t < SLOTS; ++t)
     if (si[t * NI + I_ID] != 0 && clock - si[t * NI + I_LAST] > p.max_age) {
       if (li) {   // parked in the ring before the slot is freed
-        int& head = lo->lhdr[2 * s];
+        int& head = p.lhdr[2 * s];
         const int e = head & (LOST - 1);
         std::copy(si + t * NI, si + (t + 1) * NI, li + e * NI);
         std::copy(sf + t * NF, sf + (t + 1) * NF, lf + e * NF);
@@ -814,57 +828,28 @@ void emulate_frame(const TrackArgs& p, const LostArgs* lo, int s, int f, int& cl
       if (sm) tk_pred(p, i, nullptr);
     }
   }
+  int my_slot[MAXD], my_ent[MAXD];   // step 3: the live track a detection takes; step 3b: the parked track an unmatched one revives
   key.clear();
   for (int t = 0; t < SLOTS; ++t) {
     if (si[t * NI + I_ID] == 0) continue;
     for (int j = 0; j < nd; ++j) {
       if (!(det_inv[j] > 0.f)) continue;
-      float part[GL];
-      for (int gl = 0; gl < GL; ++gl) part[gl] = tk_partial(semb + (long)t * p.D, p.emb + det_row[j] * p.D, p.D, gl);
-      for (int off = GL / 2; off > 0; off >>= 1)   // the xor-shuffle sum as lane 0 sees it
-        for (int l = 0; l < off; ++l) part[l] = part[l] + part[l + off];
-      const float c = tk_cos(part[0], sf[t * NF + F_INV], det_inv[j]);
+      const float c = emu_cos(semb + (long)t * p.D, p.emb + det_row[j] * p.D, p.D, sf[t * NF + F_INV], det_inv[j]);
       const float iou = tk_iou(sm ? pbox[t] : sf + t * NF + F_BOX, p.box + det_row[j] * 4);
       if (tk_admissible(p, c, iou)) key.push_back(tk_key(c, t, j));
     }
   }
-  std::sort(key.begin(), key.end());
-  int my_slot[MAXD];
-  for (int j = 0; j < MAXD; ++j) my_slot[j] = -1;
-  unsigned long long t_taken = 0ull, d_taken = 0ull;
-  for (size_t i = 0; i < key.size(); ++i) {
-    const int k_slot = tk_key_slot(key[i]), k_pos = tk_key_pos(key[i]);
-    if (((t_taken >> k_slot) & 1ull) || ((d_taken >> k_pos) & 1ull)) continue;
-    t_taken |= 1ull << k_slot;
-    d_taken |= 1ull << k_pos;
-    my_slot[k_pos] = k_slot;
-  }
-  int my_ent[MAXD];   // step 3b: the parked track an unmatched detection revives
-  for (int j = 0; j < MAXD; ++j) my_ent[j] = -1;
-  if (li) {
-    key.clear();
-    for (int e = 0; e < LOST; ++e) {
-      if (!tk_parked(li + e * NI, lf + e * NF)) continue;
-      for (int j = 0; j < nd; ++j) {
-        if (!(det_inv[j] > 0.f) || my_slot[j] >= 0) continue;
-        float part[GL];
-        for (int gl = 0; gl < GL; ++gl) part[gl] = tk_partial(lemb + (long)e * p.D, p.emb + det_row[j] * p.D, p.D, gl);
-        for (int off = GL / 2; off > 0; off >>= 1)
-          for (int l = 0; l < off; ++l) part[l] = part[l] + part[l + off];
-        const float c = tk_cos(part[0], lf[e * NF + F_INV], det_inv[j]);
-        if (c > lo->tau_reid) key.push_back(tk_key(c, e, j));
-      }
-    }
-    std::sort(key.begin(), key.end());
-    unsigned long long e_taken = 0ull, u_taken = 0ull;
-    for (size_t i = 0; i < key.size(); ++i) {
-      const int k_ent = tk_key_slot(key[i]), k_pos = tk_key_pos(key[i]);
-      if (((e_taken >> k_ent) & 1ull) || ((u_taken >> k_pos) & 1ull)) continue;
-      e_taken |= 1ull << k_ent;
-      u_taken |= 1ull << k_pos;
-      my_ent[k_pos] = k_ent;
+  emu_greedy(key, my_slot);
+  key.clear();
+  for (int e = 0; li && e < LOST; ++e) {
+    if (!tk_parked(li + e * NI, lf + e * NF)) continue;
+    for (int j = 0; j < nd; ++j) {
+      if (!(det_inv[j] > 0.f) || my_slot[j] >= 0) continue;
+      const float c = emu_cos(lemb + (long)e * p.D, p.emb + det_row[j] * p.D, p.D, lf[e * NF + F_INV], det_inv[j]);
+      if (c > p.tau_reid) key.push_back(tk_key(c, e, j));
     }
   }
+  emu_greedy(key, my_ent);
   int slot_of[MAXD], flag_of[MAXD], ent_of[MAXD];
   for (int j = 0; j < nd; ++j) {
     const long row = det_row[j];
@@ -911,7 +896,7 @@ void emulate_frame(const TrackArgs& p, const LostArgs* lo, int s, int f, int& cl
   }
 }
 
-void emulate_step(const TrackArgs& p, const LostArgs* lo = nullptr) {
+void emulate_step(const TrackArgs& p) {
   for (long i = 0; i < p.n; ++i)
     if (tk_untracked(p, p.frame[i])) {
       tk_out(p, i, 0, 0, 0, FP_TRACK_NO_STREAM);
@@ -921,8 +906,24 @@ void emulate_step(const TrackArgs& p, const LostArgs* lo = nullptr) {
   for (int f = 0; f < p.B; ++f) {   // streams are independent: batch order is every stream's own order
     const int s = p.sof[f];
     if (s < 0 || s >= p.S) continue;
-    emulate_frame(p, lo, s, f, p.hdr[2 * s], p.hdr[2 * s + 1], key);
+    emulate_frame(p, s, f, p.hdr[2 * s], p.hdr[2 * s + 1], key);
   }
+}
+
+// Every entry point ends here.  The refusals come before any HIP call; the emulate path makes none at all.
+int run(const TrackArgs& a, Needs need, bool emulate, void* stream) {
+  const int rc = check_args(a, need);
+  if (rc != FP_OK) return rc;
+  if (emulate) {
+    emulate_step(a);
+    return FP_OK;
+  }
+  if (a.B == 0 && a.n == 0) return FP_OK;
+  void (*const kernel)(TrackArgs) = !a.li ? (!a.motion ? tracklets_kernel<false, false> : tracklets_kernel<true, false>)
+                                          : (a.motion ? tracklets_kernel<true, true> : tracklets_kernel<false, true>);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)a.S), dim3(TPB), 0, (hipStream_t)stream, a);
+  FP_CHECK_LAUNCH();
+  return FP_OK;
 }
 
 }  // namespace
@@ -933,25 +934,18 @@ int fp_tracklets_step(const fp_track_state* state, int n_streams, int D, const i
                       const float* emb, const float* xinv, const float* score, int n, const int32_t* stream_of_frame, int B,
                       int max_age, float tau_near, float tau_far, float iou_min, int32_t* track_id, int32_t* track_hits,
                       int32_t* track_clock, int32_t* track_flags, void* stream) {
-  const TrackArgs a = track_args(state, n_streams, D, frame, box, emb, xinv, score, n, stream_of_frame, B, max_age, tau_near,
-                                 tau_far, iou_min, track_id, track_hits, track_clock, track_flags);
-  const int rc = check_track(a, state);
-  if (rc != FP_OK || (B == 0 && n == 0)) return rc;
-  hipLaunchKernelGGL((tracklets_kernel<false, false>), dim3((unsigned)n_streams), dim3(TPB), 0, (hipStream_t)stream, a);
-  FP_CHECK_LAUNCH();
-  return FP_OK;
+  return run(track_args(state, n_streams, D, frame, box, emb, xinv, score, n, stream_of_frame, B, max_age, tau_near, tau_far,
+                        iou_min, track_id, track_hits, track_clock, track_flags),
+             {MOTION_ABSENT, false}, false, stream);
 }
 
 int fp_tracklets_step_emulate(const fp_track_state* state, int n_streams, int D, const int32_t* frame, const float* box,
                               const float* emb, const float* xinv, const float* score, int n, const int32_t* stream_of_frame,
                               int B, int max_age, float tau_near, float tau_far, float iou_min, int32_t* track_id,
                               int32_t* track_hits, int32_t* track_clock, int32_t* track_flags) {
-  const TrackArgs p = track_args(state, n_streams, D, frame, box, emb, xinv, score, n, stream_of_frame, B, max_age, tau_near,
-                                 tau_far, iou_min, track_id, track_hits, track_clock, track_flags);
-  const int rc = check_track(p, state);
-  if (rc != FP_OK) return rc;
-  emulate_step(p);
-  return FP_OK;
+  return run(track_args(state, n_streams, D, frame, box, emb, xinv, score, n, stream_of_frame, B, max_age, tau_near, tau_far,
+                        iou_min, track_id, track_hits, track_clock, track_flags),
+             {MOTION_ABSENT, false}, true, nullptr);
 }
 
 int fp_tracklets_step_motion(const fp_track_state* state, int n_streams, int D, const int32_t* frame, const float* box,
@@ -959,14 +953,9 @@ int fp_tracklets_step_motion(const fp_track_state* state, int n_streams, int D, 
                              int B, int max_age, float tau_near, float tau_far, float iou_min, int32_t* track_id,
                              int32_t* track_hits, int32_t* track_clock, int32_t* track_flags, float* motion, float std_pos,
                              float std_vel, float* track_pred, void* stream) {
-  const TrackArgs a = with_motion(track_args(state, n_streams, D, frame, box, emb, xinv, score, n, stream_of_frame, B, max_age,
-                                             tau_near, tau_far, iou_min, track_id, track_hits, track_clock, track_flags),
-                                  motion, std_pos, std_vel, track_pred);
-  const int rc = check_motion(a, state);
-  if (rc != FP_OK || (B == 0 && n == 0)) return rc;
-  hipLaunchKernelGGL((tracklets_kernel<true, false>), dim3((unsigned)n_streams), dim3(TPB), 0, (hipStream_t)stream, a);
-  FP_CHECK_LAUNCH();
-  return FP_OK;
+  return run(track_args(state, n_streams, D, frame, box, emb, xinv, score, n, stream_of_frame, B, max_age, tau_near, tau_far,
+                        iou_min, track_id, track_hits, track_clock, track_flags, motion, std_pos, std_vel, track_pred),
+             {MOTION_REQUIRED, false}, false, stream);
 }
 
 int fp_tracklets_step_motion_emulate(const fp_track_state* state, int n_streams, int D, const int32_t* frame, const float* box,
@@ -974,13 +963,9 @@ int fp_tracklets_step_motion_emulate(const fp_track_state* state, int n_streams,
                                      const int32_t* stream_of_frame, int B, int max_age, float tau_near, float tau_far,
                                      float iou_min, int32_t* track_id, int32_t* track_hits, int32_t* track_clock,
                                      int32_t* track_flags, float* motion, float std_pos, float std_vel, float* track_pred) {
-  const TrackArgs p = with_motion(track_args(state, n_streams, D, frame, box, emb, xinv, score, n, stream_of_frame, B, max_age,
-                                             tau_near, tau_far, iou_min, track_id, track_hits, track_clock, track_flags),
-                                  motion, std_pos, std_vel, track_pred);
-  const int rc = check_motion(p, state);
-  if (rc != FP_OK) return rc;
-  emulate_step(p);
-  return FP_OK;
+  return run(track_args(state, n_streams, D, frame, box, emb, xinv, score, n, stream_of_frame, B, max_age, tau_near, tau_far,
+                        iou_min, track_id, track_hits, track_clock, track_flags, motion, std_pos, std_vel, track_pred),
+             {MOTION_REQUIRED, false}, true, nullptr);
 }
 
 int fp_tracklets_step_reid(const fp_track_state* state, const fp_track_lost* lost, int n_streams, int D, const int32_t* frame,
@@ -988,17 +973,10 @@ int fp_tracklets_step_reid(const fp_track_state* state, const fp_track_lost* los
                            const int32_t* stream_of_frame, int B, int max_age, float tau_near, float tau_far, float iou_min,
                            int32_t* track_id, int32_t* track_hits, int32_t* track_clock, int32_t* track_flags, float tau_reid,
                            int lost_age, float* motion, float std_pos, float std_vel, float* track_pred, void* stream) {
-  TrackArgs t = track_args(state, n_streams, D, frame, box, emb, xinv, score, n, stream_of_frame, B, max_age, tau_near, tau_far,
-                           iou_min, track_id, track_hits, track_clock, track_flags);
-  if (motion) t = with_motion(t, motion, std_pos, std_vel, track_pred);
-  else t.o_pred = track_pred;   // refused unless null
-  const ReidArgs a = with_reid(t, lost, tau_reid, lost_age);
-  const int rc = check_reid(a, state, lost);
-  if (rc != FP_OK || (B == 0 && n == 0)) return rc;
-  if (motion) hipLaunchKernelGGL((tracklets_kernel<true, true>), dim3((unsigned)n_streams), dim3(TPB), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL((tracklets_kernel<false, true>), dim3((unsigned)n_streams), dim3(TPB), 0, (hipStream_t)stream, a);
-  FP_CHECK_LAUNCH();
-  return FP_OK;
+  return run(track_args(state, n_streams, D, frame, box, emb, xinv, score, n, stream_of_frame, B, max_age, tau_near, tau_far,
+                        iou_min, track_id, track_hits, track_clock, track_flags, motion, std_pos, std_vel, track_pred, lost,
+                        tau_reid, lost_age),
+             {MOTION_OPTIONAL, true}, false, stream);
 }
 
 int fp_tracklets_step_reid_emulate(const fp_track_state* state, const fp_track_lost* lost, int n_streams, int D,
@@ -1007,15 +985,10 @@ int fp_tracklets_step_reid_emulate(const fp_track_state* state, const fp_track_l
                                    float iou_min, int32_t* track_id, int32_t* track_hits, int32_t* track_clock,
                                    int32_t* track_flags, float tau_reid, int lost_age, float* motion, float std_pos, float std_vel,
                                    float* track_pred) {
-  TrackArgs t = track_args(state, n_streams, D, frame, box, emb, xinv, score, n, stream_of_frame, B, max_age, tau_near, tau_far,
-                           iou_min, track_id, track_hits, track_clock, track_flags);
-  if (motion) t = with_motion(t, motion, std_pos, std_vel, track_pred);
-  else t.o_pred = track_pred;
-  const ReidArgs p = with_reid(t, lost, tau_reid, lost_age);
-  const int rc = check_reid(p, state, lost);
-  if (rc != FP_OK) return rc;
-  emulate_step(p, &p.l);
-  return FP_OK;
+  return run(track_args(state, n_streams, D, frame, box, emb, xinv, score, n, stream_of_frame, B, max_age, tau_near, tau_far,
+                        iou_min, track_id, track_hits, track_clock, track_flags, motion, std_pos, std_vel, track_pred, lost,
+                        tau_reid, lost_age),
+             {MOTION_OPTIONAL, true}, true, nullptr);
 }
 
 }  // extern "C"

@@ -398,12 +398,29 @@ def _lost_struct(arrays, pointer):
     return L.FpTrackLost(*[pointer(arrays[k]) for k in LOST_KEYS])
 
 
+def _step_call(st, lost, rows, motion_tail, reid, emulate, stream):
+    """The one call of a tracker step: picks among the six fp_tracklets_step* entry points and lays out their arguments.
+    st: FpTrackState; lost: FpTrackLost or None; rows: n_streams .. track_flags; motion_tail: (motion, std_pos, std_vel,
+    track_pred) or None; reid: a LostPool or None (with lost); emulate: the host twin, which takes no stream."""
+    name = "fp_tracklets_step" + ("_reid" if reid is not None else "_motion" if motion_tail is not None else "")
+    args = (C.byref(st),) + rows
+    if reid is not None:
+        args = (args[0], C.byref(lost)) + rows + (reid.tau_reid, reid.lost_age) + (motion_tail or (None, 0.0, 0.0, None))
+    elif motion_tail is not None:
+        args += motion_tail
+    if emulate:
+        name += "_emulate"
+    else:
+        args += (stream,)
+    L.check(getattr(L.load(), name)(*args), name)
+
+
 def track_step_emulate(state, frame, boxes, emb, xinv, stream_of_frame, max_age, tau_near=TAU_NEAR, tau_far=TAU_FAR,
                        iou_min=IOU_MIN, score=None, motion=None, motion_state=None, reid=None, lost_state=None):
     """fp_tracklets_step_emulate on a host state (new_state; updated IN PLACE): track_step_numpy's arguments and results; with
     motion= and motion_state=, fp_tracklets_step_motion_emulate; with reid= and lost_state= (with or without motion),
     fp_tracklets_step_reid_emulate.  Raises FacepathError on a refusal.  Needs no GPU."""
-    lib = L.load()
+    L.load()                                                 # a library that is not built is what is reported first
     frame, boxes, emb, xinv, score, sof = _row_inputs(frame, boxes, emb, xinv, score, stream_of_frame)
     n, B = frame.shape[0], sof.shape[0]
     S, D = state["hdr"].shape[0], state["emb"].shape[2]
@@ -422,29 +439,13 @@ def track_step_emulate(state, frame, boxes, emb, xinv, stream_of_frame, max_age,
     pool = _reid_args(reid, lost_state, S, D, max_age)
     out = {k: np.zeros((n,), np.int32) for k in OUT_KEYS}
     p = lambda a: None if a is None else C.c_void_p(a.ctypes.data)          # noqa: E731
-    st = _state_struct(state, p)
-    if pool is not None:
-        pred = None if motion is None else np.zeros((n, 4), np.float32)
-        lost = _lost_struct(pool, p)
-        L.check(lib.fp_tracklets_step_reid_emulate(C.byref(st), C.byref(lost), S, D, p(frame), p(boxes), p(emb), p(xinv), p(score), n,
-                                                   p(sof), B, int(max_age), float(tau_near), float(tau_far), float(iou_min),
-                                                   *[p(out[k]) for k in OUT_KEYS], reid.tau_reid, reid.lost_age, p(mstate),
-                                                   0.0 if motion is None else float(sp), 0.0 if motion is None else float(sv),
-                                                   p(pred)), "fp_tracklets_step_reid_emulate")
-        if motion is not None:
-            out["track_pred"] = pred
-        return out
+    rows = (S, D, p(frame), p(boxes), p(emb), p(xinv), p(score), n, p(sof), B, int(max_age), float(tau_near), float(tau_far),
+            float(iou_min), *[p(out[k]) for k in OUT_KEYS])
+    tail = None
     if motion is not None:
-        pred = np.zeros((n, 4), np.float32)
-        L.check(lib.fp_tracklets_step_motion_emulate(C.byref(st), S, D, p(frame), p(boxes), p(emb), p(xinv), p(score), n, p(sof),
-                                                     B, int(max_age), float(tau_near), float(tau_far), float(iou_min),
-                                                     *[p(out[k]) for k in OUT_KEYS], p(mstate), float(sp), float(sv), p(pred)),
-                "fp_tracklets_step_motion_emulate")
-        out["track_pred"] = pred
-        return out
-    L.check(lib.fp_tracklets_step_emulate(C.byref(st), S, D, p(frame), p(boxes), p(emb), p(xinv), p(score), n, p(sof), B,
-                                          int(max_age), float(tau_near), float(tau_far), float(iou_min),
-                                          *[p(out[k]) for k in OUT_KEYS]), "fp_tracklets_step_emulate")
+        out["track_pred"] = np.zeros((n, 4), np.float32)
+        tail = (p(mstate), float(sp), float(sv), p(out["track_pred"]))
+    _step_call(_state_struct(state, p), None if pool is None else _lost_struct(pool, p), rows, tail, reid, True, None)
     return out
 
 
@@ -509,21 +510,14 @@ class StreamTracker:
         elif n:
             xinv = torch.empty((n,), dtype=torch.float32, device=self.dev)
             L.check(lib.fp_row_inv_norm(L.ptr(emb), n, self.D, L.ptr(xinv), L.current_stream(self.dev)), "fp_row_inv_norm")
-        rows = (C.byref(self._struct), self.S, self.D, L.ptr(frame), L.ptr(boxes), L.ptr(emb), L.ptr(xinv), L.ptr(score), n,
-                L.ptr(sof), sof.shape[0], self.max_age, self.tau_near, self.tau_far, self.iou_min, *[L.ptr(out[k]) for k in OUT_KEYS])
+        rows = (self.S, self.D, L.ptr(frame), L.ptr(boxes), L.ptr(emb), L.ptr(xinv), L.ptr(score), n, L.ptr(sof), sof.shape[0],
+                self.max_age, self.tau_near, self.tau_far, self.iou_min, *[L.ptr(out[k]) for k in OUT_KEYS])
+        tail = None
         if self.motion is not None:
             out["track_pred"] = torch.empty((n, 4), dtype=torch.float32, device=self.dev)
-        if self.reid is not None:
-            tail = ((None, 0.0, 0.0, None) if self.motion is None else
-                    (L.ptr(self.state["motion"]), self.motion.std_pos, self.motion.std_vel, L.ptr(out["track_pred"])))
-            L.check(lib.fp_tracklets_step_reid(rows[0], C.byref(self._lost), *rows[1:], self.reid.tau_reid, self.reid.lost_age,
-                                               *tail, L.current_stream(self.dev)), "fp_tracklets_step_reid")
-            return out
-        if self.motion is None:
-            L.check(lib.fp_tracklets_step(*rows, L.current_stream(self.dev)), "fp_tracklets_step")
-            return out
-        L.check(lib.fp_tracklets_step_motion(*rows, L.ptr(self.state["motion"]), self.motion.std_pos, self.motion.std_vel,
-                                             L.ptr(out["track_pred"]), L.current_stream(self.dev)), "fp_tracklets_step_motion")
+            tail = (L.ptr(self.state["motion"]), self.motion.std_pos, self.motion.std_vel, L.ptr(out["track_pred"]))
+        _step_call(self._struct, self._lost if self.reid is not None else None, rows, tail, self.reid, False,
+                   L.current_stream(self.dev))
         return out
 
     def tracks(self, stream):

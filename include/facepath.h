@@ -1506,7 +1506,7 @@ int fp_tracklets_step_emulate(const fp_track_state* state, int n_streams, int D,
 
 /*
  * Tracklets: motion prediction (build-defined; DESIGN §7 "Tracklets: motion prediction"; csrc/tracklets.hip,
- * tracklets_kernel<true>).  Opt-in: fp_tracklets_step and its state are untouched.  All additive: ABI 14.
+ * tracklets_kernel<true, REID>).  Opt-in: fp_tracklets_step and its state are untouched.  All additive: ABI 14.
  *
  * Each slot carries four independent two-state filters, one per coordinate c of the centre form (cx, cy, w, h): the
  * decomposition that DeepSORT's 8-state constant-velocity filter has anyway, its covariance never couples two coordinates.  Per

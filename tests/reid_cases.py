@@ -362,6 +362,19 @@ def crafted_cases():
     return [fn(D) for fn in CRAFTED for D in DIMS]
 
 
+def track_cases_in_every_configuration():
+    """The crafted cases of track_cases.py (sorts of up to 2048 keys, 64 full slots, 65 rows, ties) made runnable by run_case with
+    reid= and motion= on or off: DeepSORT's motion constants and a pool at tau_reid 0.6 that outlives the case's max_age.  The ids
+    differ between the configurations (the pool revives where the plain tracker opens), so the cases' own `expect` is not called
+    on them: what is compared is one path against another within a configuration."""
+    cv = T.ConstantVelocity(T.ConstantVelocity.DEEPSORT_STD_POS, T.ConstantVelocity.DEEPSORT_STD_VEL)
+    return [dict(c, reid=T.LostPool(0.6, c["max_age"] + 50), lost_init=None, motion=cv) for c in TC.crafted_cases()]
+
+
+CONFIGS = [(False, False), (True, False), (False, True), (True, True)]      # (motion, reid)
+CONFIG_IDS = ["plain", "motion", "reid", "motion+reid"]
+
+
 # ------------------------------------------------------------------------------------------------ the batch of the properties
 
 def busy(D, seed=5, n_streams=4, spare_streams=1):

@@ -20,6 +20,7 @@ from face_detection_and_recognition_amd import tracking_eval as TE
 CASES = RC.crafted_cases()
 BUSY = [RC.busy(D) for D in RC.DIMS]
 BY_NAME = {c["name"]: c for c in CASES + BUSY}
+TRACK = RC.track_cases_in_every_configuration()
 STEP_FNS = pytest.mark.parametrize("step_fn", [T.track_step_numpy, T.track_step_emulate], ids=["numpy", "emulate"])
 
 
@@ -44,6 +45,15 @@ def test_crafted_case_numpy_equals_emulator_and_states_its_outcome(case, motion,
         assert not (o["track_flags"][rev] & T.NEW).any() and (o["track_id"][rev] > 0).all()
         if motion:
             assert (o["track_pred"][rev] == 0).all()
+
+
+@pytest.mark.parametrize("motion,reid", RC.CONFIGS, ids=RC.CONFIG_IDS)
+@pytest.mark.parametrize("case", TRACK, ids=[c["name"] for c in TRACK])
+def test_track_case_numpy_equals_emulator_in_every_configuration(case, motion, reid):
+    """The crafted cases of track_cases.py through all four kernels' host twin: the one sort, walk and pair scorer at 2048 keys,
+    64 full slots, 65 rows and ties, under the gap condition of steps 2 and 3b."""
+    want = RC.assert_gap(case, reid=reid, motion=motion)[:4]
+    RC.assert_same(RC.run_case(case, T.track_step_emulate, reid=reid, motion=motion), want, case["name"])
 
 
 @pytest.mark.parametrize("D", RC.DIMS)

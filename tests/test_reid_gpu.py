@@ -18,6 +18,7 @@ pytestmark = pytest.mark.gpu
 CASES = RC.crafted_cases()
 BUSY = [RC.busy(D) for D in RC.DIMS]
 BY_NAME = {c["name"]: c for c in CASES + BUSY}
+TRACK = RC.track_cases_in_every_configuration()
 
 
 @pytest.fixture(scope="module")
@@ -64,6 +65,17 @@ def test_crafted_case_device_equals_numpy(case, motion, numpy_runs, dev):
     if motion and "expect_motion" in case:
         case["expect_motion"](*got[:3])
     RC.assert_same(got, numpy_runs[case["name"], motion], case["name"])
+
+
+@pytest.mark.parametrize("motion,reid", RC.CONFIGS, ids=RC.CONFIG_IDS)
+@pytest.mark.parametrize("case", TRACK, ids=[c["name"] for c in TRACK])
+def test_track_case_device_equals_emulator_in_every_configuration(case, motion, reid, dev):
+    """The crafted cases of track_cases.py through each of the four kernels: all of them sort, walk and score pairs through the
+    same functions, and these cases are the ones with 2048 and 1024 keys, 64 full slots, 65 rows and ties.  Device and emulator
+    share every bit (outputs, state, motion, pool), so no gap condition is needed here; test_reid_cpu.py holds the emulator to
+    numpy on the same matrix."""
+    got = RC.run_case(case, device_step(dev), reid=reid, motion=motion)
+    RC.assert_same(got, RC.run_case(case, T.track_step_emulate, reid=reid, motion=motion), case["name"])
 
 
 @pytest.mark.parametrize("D", RC.DIMS)

@@ -258,7 +258,8 @@ __global__ __launch_bounds__(256) void coarse_scale_kernel(float* __restrict__ s
 // One wave per query row.  Candidate j (indexed mode: row cand[m][j] of G; compact mode: row m * pool + j of `rows`) gets
 // score = dot * qinv[m] * ginv[cand], dot = every lane's products summed in feature order, then the xor butterfly: a fixed
 // order.  -1 / out-of-range entries and masked rows (ginv == 0) carry no key.  Lane j then holds the key of candidate j; its
-// rank among the keys (larger first; keys of distinct rows are distinct) is its output slot.
+// rank among the keys (larger first; keys of distinct rows are distinct, a row that the list names again keeps its first
+// entry only) is its output slot.
 __global__ __launch_bounds__(256) void rerank_topk_kernel(const float* __restrict__ Q, const float* __restrict__ qinv, long M,
                                                           int D, const int* __restrict__ cand, int pool,
                                                           const float* __restrict__ G, const float* __restrict__ rows,
@@ -297,11 +298,15 @@ __global__ __launch_bounds__(256) void rerank_topk_kernel(const float* __restric
     const float sc = s * qi * gi;
     if (lane == j && sc == sc) mine = cw_key(sc, (unsigned)g);
   }
-  int rank = 0;
+  // a gallery row that the list names again has the key of its first entry (the same row, the same sum): it counts once
+  bool again = false;
   for (int j = 0; j < pool; ++j) {
     const u64 o = __shfl(mine, j);
-    rank += (o > mine || (o == mine && j < lane)) ? 1 : 0;
+    again |= o == mine && j < lane;
   }
+  if (again) mine = 0;
+  int rank = 0;
+  for (int j = 0; j < pool; ++j) rank += __shfl(mine, j) > mine ? 1 : 0;
   const int valid = __popcll(__ballot(mine != 0));
   if (mine && rank < k) {
     scores[m * k + rank] = cw_key_score(mine);

@@ -209,7 +209,7 @@ def cosine_topk_i8_numpy(qq, u, qg, w, pool):
 
 def rerank_topk(Q, cand, k, G=None, ginv=None, qinv=None, rows=None):
     """The exact scores of a candidate list.  Q (M, D) fp32, cand (M, pool) int32 gallery rows (-1 and rows whose ginv is 0 are
-    skipped), ginv (N,) -> scores (M, k) descending, idx (M, k) int32 gallery rows, -inf / -1 behind the valid ones.  The fp32
+    skipped, a row named more than once counts once), ginv (N,) -> scores (M, k) descending, idx (M, k) int32 gallery rows, -inf / -1 behind the valid ones.  The fp32
     rows come from G (N, D64) on the device, or from rows (M, pool, D64): the candidates' rows gathered in the order of cand
     (a gallery whose rows live on the host).  score = <Q, row> * qinv * ginv in fp32 with a fixed summation order: both
     modes and every run give the same bits.  D64: the features zero-padded to a multiple of 64 (pad_features64)."""

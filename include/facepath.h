@@ -704,7 +704,8 @@ int fp_cosine_topk_x6(const float* Q, const float* qinv, int64_t M, const void* 
  * holds intermediate values until the call's last kernel has run); the result is that of one pass.
  *
  * fp_rerank_topk: the exact scores of the candidates.  cand [M][pool] int32 gallery rows; -1 (or any index outside 0 .. N-1)
- * and rows with ginv == 0 are skipped, the others are distinct.  score = dot_fp32(Q[m], row) * qinv[m] * ginv[cand], the dot
+ * and rows with ginv == 0 are skipped; a list is a SET of rows: an index it names more than once counts once (its first
+ * entry), so no gallery row comes back twice.  score = dot_fp32(Q[m], row) * qinv[m] * ginv[cand], the dot
  * summed in a fixed order (two runs agree bit for bit); the k best by (score descending, index ascending) to scores [M][k],
  * idx [M][k] (gallery rows), -inf / -1 behind them.  The fp32 rows come from G [N][D] (rows == NULL) or, for a gallery whose
  * rows stay on the host, from the compact block rows [M][pool][D] gathered in the order of cand (G == NULL); exactly one of

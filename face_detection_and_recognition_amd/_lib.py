@@ -131,6 +131,8 @@ TRACK_SLOT_INTS, TRACK_SLOT_FLOATS = 5, 10                                # colu
 TRACK_MOTION_FLOATS = 20                  # FP_TRACK_MOTION_FLOATS: x, v, p00, p01, p11 of cx, cy, w, h per slot of `motion`
 TRACK_NEW, TRACK_BEST, TRACK_DEAD_ROW, TRACK_FULL, TRACK_NO_STREAM, TRACK_OVER = 1, 2, 4, 8, 16, 32   # track_flags bits
 TRACK_LOST, TRACK_REVIVED = 64, 64        # FP_TRACK_LOST: parked tracks per stream of fp_track_lost; FP_TRACK_REVIVED: a track_flags bit
+TRACK_POOL = 128                          # FP_TRACK_POOL: template entries per stream of fp_track_templates
+TRACK_TPL_EVICTED, TRACK_TPL_RESTART = 1, 2   # FP_TRACK_TPL_*: track_emb_flags bits
 MOT_MAX_ROWS, MOT_STATE_ROWS = 64, 6   # FP_MOT_MAX_ROWS: rows of one frame fp_mot_match takes; int32 rows of its per-id state
 HOTA_MAX_ALPHAS = 32                   # FP_HOTA_MAX_ALPHAS: localisation thresholds fp_hota_match takes
 
@@ -144,6 +146,11 @@ class FpTrackLost(C.Structure):
     """Mirror of struct fp_track_lost: the five pool arrays of fp_tracklets_step_reid ("Tracklets: re-identification")."""
     _fields_ = [("lost_hdr", C.c_void_p), ("lost_i", C.c_void_p), ("lost_f", C.c_void_p), ("lost_emb", C.c_void_p),
                 ("lost_best_emb", C.c_void_p)]
+
+
+class FpTrackTemplates(C.Structure):
+    """Mirror of struct fp_track_templates: the three table arrays of fp_track_pool_step ("Tracklets: templates")."""
+    _fields_ = [("tpl_i", C.c_void_p), ("tpl_w", C.c_void_p), ("tpl_sum", C.c_void_p)]
 
 
 JPEG_DECODE_ON_HOST = 1          # fp_jpeg_entropy_decode_device status: decode this image with fp_jpeg_entropy_decode
@@ -162,6 +169,9 @@ _D = C.c_double
 _TK_ROWS = [_I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P]   # n_streams .. track_flags
 _TK_MOTION = [_P, _F, _F, _P]                                                         # motion, std_pos, std_vel, track_pred
 _TK_REID = [_F, _I]                                                                   # tau_reid, lost_age
+
+# fp_track_pool_step*: [tpl] + n_streams .. track_emb_flags (+ workspace, workspace_bytes, stream on the device path)
+_TP_ROWS = [_I, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P]
 
 # name -> (restype, argtypes); every symbol declared in include/facepath.h
 SIGNATURES = {
@@ -279,6 +289,9 @@ SIGNATURES = {
     "fp_tracklets_step_motion_emulate": (_I, [C.POINTER(FpTrackState)] + _TK_ROWS + _TK_MOTION),
     "fp_tracklets_step_reid": (_I, [C.POINTER(FpTrackState), C.POINTER(FpTrackLost)] + _TK_ROWS + _TK_REID + _TK_MOTION + [_P]),
     "fp_tracklets_step_reid_emulate": (_I, [C.POINTER(FpTrackState), C.POINTER(FpTrackLost)] + _TK_ROWS + _TK_REID + _TK_MOTION),
+    "fp_track_pool_workspace_bytes": (_SZ, [_I]),
+    "fp_track_pool_step": (_I, [C.POINTER(FpTrackTemplates)] + _TP_ROWS + [_P, _SZ, _P]),
+    "fp_track_pool_step_emulate": (_I, [C.POINTER(FpTrackTemplates)] + _TP_ROWS),
     "fp_mot_match_workspace": (_SZ, [_I64, _I64]),
     "fp_mot_match": (_I, [_P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I64, _D, _P, _P, _P, _P, _P, _SZ, _P]),
     "fp_mot_match_emulate": (_I, [_P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _I, _I64, _I64, _I64, _D, _P, _P, _P, _P, _P,

@@ -316,14 +316,16 @@ def face_draw_list(info, n, sizes, lmarks=None, labels=None, areas=True, colors=
 
 def step_labels(result, names=None):
     """One caption suffix per face of a FacePipeline.step result, or None when it carries nothing to say: the gallery name of
-    `identity` (names[identity], a dict or a sequence; nothing for -1), the arg-max gender / age classes and, for a step with a
-    tracker, " #<track_id>" (nothing for id 0)."""
+    `identity` (names[identity], a dict or a sequence; nothing for -1) -- of `track_identity`, the track's name, when the result
+    carries it (FacePipeline(identify_tracks=True)) --, the arg-max gender / age classes and, for a step with a tracker,
+    " #<track_id>" (nothing for id 0)."""
     n = result["n_faces"]
     parts = [""] * n
     said = False
-    if "identity" in result and names is not None:
+    who = "track_identity" if "track_identity" in result else "identity"
+    if who in result and names is not None:
         said = True
-        for i, k in enumerate(result["identity"][:n].tolist()):
+        for i, k in enumerate(result[who][:n].tolist()):
             if k >= 0:
                 parts[i] += " " + str(names.get(k, k) if isinstance(names, dict) else names[k])
     if "age_probs" in result:

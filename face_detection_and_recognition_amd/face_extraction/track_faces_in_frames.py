@@ -14,6 +14,11 @@ box a track is predicted at; no defaults, nothing has been measured).
 --reid TAU LOST_AGE turns re-identification on (tracking.LostPool: a track that ends is remembered for LOST_AGE frames and a
 returning face whose cosine to its last embedding exceeds TAU continues it -- one track_XXXX/ folder and one id instead of
 two; no defaults, nothing has been measured on real video).
+--templates [--weighted] keeps a template per track on the device (tracking.Templates: the sum of the track's normalised
+embeddings, with --weighted each weighed by its score): tracks.json gains template_rows and <td>/tracks.npz holds the templates
+(ids, templates, template_rows).  --gallery FILE [--identify_tau T] (a FaceGallery.save file; needs --templates) names every
+track from its template (FacePipeline(identify_tracks=True)): tracks.json gains identity (the gallery's name, null for nobody)
+and identity_score, and the captions of --video_out carry the track's name.  What either gains on real video is unmeasured.
 Build-defined: the reference labels faces frame by frame (face_tracker.py is that port).
 
 --video_out FILE writes every frame with its tracked faces' boxes and ` #<id>` captions (FacePipeline.annotate) to a
@@ -29,7 +34,7 @@ import os
 
 import numpy as np
 
-from ..tracking import BEST, IOU_MIN, TAU_FAR, TAU_NEAR, ConstantVelocity, LostPool, StreamTracker, TrackBook
+from ..tracking import BEST, IOU_MIN, TAU_FAR, TAU_NEAR, ConstantVelocity, LostPool, StreamTracker, Templates, TrackBook
 
 
 def get_parsed_args(argv=None):
@@ -53,6 +58,12 @@ def get_parsed_args(argv=None):
     parser.add_argument('--reid', type=float, nargs=2, default=None, metavar=("TAU", "LOST_AGE"),
                         help="re-identification of ended tracks: the cosine a returning face must exceed and the frames a track "
                              "is remembered, an integer > max_age (no defaults)")
+    parser.add_argument('--templates', action="store_true",
+                        help="keep a template per track (the sum of its normalised embeddings) and write them to tracks.npz")
+    parser.add_argument('--weighted', action="store_true", help="with --templates: weigh every row by its score")
+    parser.add_argument('--gallery', type=str, default=None,
+                        help="a FaceGallery.save file: name every track from its template (needs --templates)")
+    parser.add_argument('--identify_tau', type=float, default=None, help="with --gallery: the cosine a name needs (default 0.3)")
     parser.add_argument('--quality', action="store_true", help="best shot by crop sharpness instead of detector confidence")
     parser.add_argument('-b', '--batch_size', type=int, default=256)
     parser.add_argument('--jpeg_quality', type=int, default=95)
@@ -79,15 +90,23 @@ def build_pipeline(args, dev, first_frames):
     det = W.build_detector(dev, first_frames, cand_per_frame=48)
     emb = W.build_embedder(dev)
     motion = None if args.motion is None else ConstantVelocity(*args.motion)
+    if (args.weighted or args.gallery) and not args.templates:
+        raise ValueError("--weighted and --gallery need --templates")
     tracker = StreamTracker(1, emb.embedding_size, args.max_age, args.tau_near, args.tau_far, args.iou_min, device=dev, motion=motion,
-                            reid=lost_pool(args))
-    return FacePipeline(det, emb, None, quality=True if args.quality else None, tracker=tracker), tracker
+                            reid=lost_pool(args), templates=Templates(args.weighted) if args.templates else None)
+    kw = {}
+    if args.gallery:
+        from ..gallery import FaceGallery
+        kw = dict(gallery=FaceGallery.load(args.gallery, device=dev), identify_tau=args.identify_tau, identify_tracks=True)
+    return FacePipeline(det, emb, None, quality=True if args.quality else None, tracker=tracker, **kw), tracker
 
 
 def track_frames(pipe, paths, batch_size, jpeg_quality=95, mot_rows=None, writer=None):
     """-> (TrackBook, {(stream, id): JPEG bytes of the best row's crop}).  Frames of one size (a video's).  paths: the sorted
     .jpg files, or a VideoReader.  mot_rows: a list that receives, per batch, (frame numbers, ids, xywh boxes, confidences) of
-    the rows with a track id (numpy).  writer: a VideoWriter that receives every batch annotated (FacePipeline.annotate)."""
+    the rows with a track id (numpy).  writer: a VideoWriter that receives every batch annotated (FacePipeline.annotate).
+    With a tracker that keeps templates the book's records carry template / template_rows, and with identify_tracks also
+    identity / identity_score: the track's latest."""
     import torch
     from ..modules.utils.jpeg import encode_crops
     from ..modules.utils.video import read_frames
@@ -101,8 +120,14 @@ def track_frames(pipe, paths, batch_size, jpeg_quality=95, mot_rows=None, writer
         score = res["quality"]["sharpness"] if "quality" in res else info[:, 5]
         sof = np.zeros((frames.shape[0],), np.int32)
         out = {k: res[k] for k in pipe.TRACK_KEYS}
-        book.update(out, info[:n, 0].to(torch.int32), info[:n, 1:5], sof, emb=res["emb"], score=score[:n], frame_base=lo)
+        book.update(out, info[:n, 0].to(torch.int32), info[:n, 1:5], sof, emb=res["emb"], score=score[:n], frame_base=lo,
+                    track_emb=res.get("track_emb"), track_emb_rows=res.get("track_emb_rows"))
         flags, ids = res["track_flags"].cpu().numpy(), res["track_id"].cpu().numpy()
+        if "track_identity" in res:
+            who, how = res["track_identity"].cpu().numpy(), res["track_identity_score"].cpu().numpy()
+            for i in range(n):
+                if ids[i] > 0:
+                    book[(0, int(ids[i]))].update(identity=int(who[i]), identity_score=float(how[i]))
         if mot_rows is not None:
             rows = info[:n].cpu().numpy().astype(np.float64)
             keep = ids[:n] > 0
@@ -117,10 +142,12 @@ def track_frames(pipe, paths, batch_size, jpeg_quality=95, mot_rows=None, writer
     return book, shots
 
 
-def save_tracks(target, book, shots, paths):
-    """<target>/tracks.json and <target>/track_XXXX/best.jpg.  -> the list written to tracks.json."""
+def save_tracks(target, book, shots, paths, names=None):
+    """<target>/tracks.json and <target>/track_XXXX/best.jpg; with templates in the book also <target>/tracks.npz (ids,
+    templates, template_rows, in the order of tracks.json).  names: the gallery's {label: name}.  -> the list written to
+    tracks.json."""
     os.makedirs(target, exist_ok=True)
-    tracks = []
+    tracks, templates = [], []
     for r in book.rows():
         name = f"track_{r['id']:04d}"
         rec = dict(id=r["id"], first_frame=os.path.basename(paths[r["first_clock"] - 1]),
@@ -132,7 +159,18 @@ def save_tracks(target, book, shots, paths):
             with open(os.path.join(target, name, "best.jpg"), "wb") as f:
                 f.write(data)
             rec["best_jpg"] = f"{name}/best.jpg"
+        if "template" in r:
+            rec["template_rows"] = r["template_rows"]
+            templates.append(r["template"])
+        if "identity" in r:
+            k = r["identity"]
+            rec["identity"] = None if k < 0 else str((names or {}).get(k, k))
+            rec["identity_score"] = r["identity_score"]
         tracks.append(rec)
+    if templates:
+        np.savez(os.path.join(target, "tracks.npz"), ids=np.array([t["id"] for t in tracks], np.int32),
+                 templates=np.stack(templates).astype(np.float32),
+                 template_rows=np.array([t["template_rows"] for t in tracks], np.int32))
     with open(os.path.join(target, "tracks.json"), "w") as f:
         json.dump(dict(frames=len(paths), tracks=tracks), f, indent=1)
     return tracks
@@ -171,7 +209,7 @@ def main(argv=None):
             writer.close()
         if isinstance(source, VideoReader):
             source.close()
-    tracks = save_tracks(args.target_data_path, book, shots, paths)
+    tracks = save_tracks(args.target_data_path, book, shots, paths, names=pipe.gallery.names if pipe.gallery is not None else None)
     if args.mot_out:
         write_mot_rows(args.mot_out, mot_rows)
     print(f"{len(tracks)} tracks in {len(paths)} frames -> {os.path.join(args.target_data_path, 'tracks.json')}")

@@ -40,7 +40,13 @@ class FacePipeline:
     tracking.LostPool) gives a returning face its old id back, and that row's track_flags carry tracking.REVIVED (64) where an
     opening row carries NEW: the flags pass through unchanged.  step / step_overlapped take streams = the stream of every frame ((B,) ints, -1: not tracked;
     None: the batch is consecutive frames of stream 0).  The score of the best shot is the conf column of info, or
-    quality["sharpness"] with quality on.  Steps must reach the tracker in order: it carries state from step to step."""
+    quality["sharpness"] with quality on.  Steps must reach the tracker in order: it carries state from step to step.  A tracker
+    built with templates= adds track_emb (n, D) fp32, track_emb_rows and track_emb_flags (n,) int32: the template of every row's
+    track after the row (tracking.py; the row's own embedding where it has no track).
+    identify_tracks: needs a gallery and a tracker with templates= (ValueError otherwise): step results then also carry
+    track_identity, track_identity_score, track_top_scores and track_top_idx, the gallery's answer for track_emb (same top_k,
+    identify_tau and vote), searched behind the tracker: who the TRACK is, which one turned or blurred frame does not change,
+    beside the per-row identity keys, which stay.  What that gains on real video has not been measured."""
 
     # embed(): a batch a little above a multiple of ROUND_CROPS crops is run as that multiple + the remainder on a side stream
     ROUND_CROPS = 512     # crops whose tiles fill whole rounds of workgroups in every Depth_Wise kernel (2 / 4 / 7 tiles per crop, 512 slots)
@@ -49,11 +55,14 @@ class FacePipeline:
 
     def __init__(self, detector, embedder, reference=None, tau=0.3, max_faces_per_frame=8, bucket=8, two_streams=False,
                  split_tail=True, align=False, attributes=None, gallery=None, top_k=5, identify_tau=None, vote="top1",
-                 quality=None, tracker=None):
+                 quality=None, tracker=None, identify_tracks=False):
         self.det = detector
         if tracker is not None and tracker.D != embedder.embedding_size:
             raise ValueError(f"tracker feat_dim {tracker.D} is not the embedder's {embedder.embedding_size}")
         self.tracker = tracker
+        self.identify_tracks = bool(identify_tracks)
+        if self.identify_tracks and (gallery is None or tracker is None or getattr(tracker, "templates_opt", None) is None):
+            raise ValueError("identify_tracks needs gallery= and a tracker built with templates=")
         if not (quality is None or quality is True or isinstance(quality, Q.QualityGate)):
             raise ValueError(f"quality must be None, True or a QualityGate, got {quality!r}")
         self.quality = quality
@@ -319,7 +328,9 @@ class FacePipeline:
             out["quality_keep"] = self.quality.mask(out["quality"])
 
     TRACK_KEYS = ("track_id", "track_hits", "track_clock", "track_flags")
-    TRACK_RESULT_KEYS = TRACK_KEYS + ("track_pred",)      # track_pred: only from a tracker with motion=
+    TRACK_IDENTITY_KEYS = ("track_top_scores", "track_top_idx", "track_identity", "track_identity_score")
+    # track_pred: only from a tracker with motion=; track_emb*: with templates=; the last four: with identify_tracks
+    TRACK_RESULT_KEYS = TRACK_KEYS + ("track_pred", "track_emb", "track_emb_rows", "track_emb_flags") + TRACK_IDENTITY_KEYS
 
     def _stream_of_frame(self, B, streams):
         """(B,) int32 on the device: zeros for None (small cache by B), else the caller's streams."""
@@ -338,6 +349,17 @@ class FacePipeline:
         n, info = out["n_faces"], out["info"]
         score = out["quality"]["sharpness"] if self.quality is not None else info[:, 5]
         out.update(self.tracker.step(info[:, 0], info[:, 1:5], out["emb"], self._stream_of_frame(B, streams), score=score, n=n))
+        if self.identify_tracks:
+            k = self.top_k
+            if n == 0:
+                out.update(track_top_scores=torch.zeros((0, k), device=self.dev),
+                           track_top_idx=torch.zeros((0, k), dtype=torch.int32, device=self.dev),
+                           track_identity=torch.zeros((0,), dtype=torch.int32, device=self.dev),
+                           track_identity_score=torch.zeros((0,), device=self.dev))
+                return
+            r = self.gallery.identify(out["track_emb"], k=k, tau=self.identify_tau, vote=self.vote)
+            out.update(track_top_scores=r["top_scores"], track_top_idx=r["top_idx"], track_identity=r["label"],
+                       track_identity_score=r["score"])
 
     @staticmethod
     def _add_align(out, al, n):

@@ -27,6 +27,15 @@ best shot -- and its row carries REVIVED instead of NEW.  fp_tracklets_step_reid
 re-identification"; the state gains the five lost_* arrays.  Without reid= nothing changes.  Neither parameter has a default and
 neither has been measured on real video; re-identification across streams, pools beyond 64 tracks and a best-shot descriptor are
 not part of this.
+
+Templates are opt-in as well: templates=Templates(weighted=False) keeps, per stream, a table of L.TRACK_POOL entries with the
+weighted sum of the normalised embeddings of every row of a track (fp_track_pool_step, csrc/trackpool.hip, two launches after
+the tracker's, nothing read back; include/facepath.h "Tracklets: templates"), and step() also returns track_emb (n, D): the
+sum of the row's track after the row, the row's own embedding where it has no track.  A gallery search on track_emb answers "who
+is this track" (FacePipeline(identify_tracks=True)).  The state gains tpl_i, tpl_w, tpl_sum.  track_pool_numpy restates the
+procedure in numpy float32, track_pool_emulate runs the kernel's own arithmetic on the host; there is no reduction, so the
+three agree on every bit without a gap condition.  weighted=True weighs a row by the step's score; keep is lost_age with reid=,
+else max_age.  Neither choice, nor any gain on real video, has been measured here.  Without templates= nothing changes.
 """
 import ctypes as C
 
@@ -46,6 +55,10 @@ F_BOX, F_INV, F_BEST_SCORE, F_BEST_BOX = 0, 4, 5, 6         # slot_f columns
 STATE_KEYS = ("hdr", "slot_i", "slot_f", "emb", "best_emb")
 OUT_KEYS = ("track_id", "track_hits", "track_clock", "track_flags")
 MOTION_FLOATS = L.TRACK_MOTION_FLOATS
+POOL, TPL_EVICTED, TPL_RESTART = L.TRACK_POOL, L.TRACK_TPL_EVICTED, L.TRACK_TPL_RESTART
+TEMPLATE_KEYS = ("tpl_i", "tpl_w", "tpl_sum")
+TEMPLATE_OUT_KEYS = ("track_emb", "track_emb_rows", "track_emb_flags")
+P_ID, P_LAST, P_ROWS = range(3)                             # tpl_i columns
 M_X, M_V, M_P00, M_P01, M_P11, M_COLS = 0, 1, 2, 3, 4, 5    # columns of one coordinate (cx, cy, w, h) of a slot of `motion`
 
 
@@ -113,6 +126,127 @@ def _reid_args(reid, lost_state, S, D, max_age):
     if not ok:
         raise ValueError(f"lost_state must be a dict of the writable C-contiguous arrays of new_lost_state({S}, {D})")
     return lost_state
+
+
+class Templates:
+    """The tracker keeps a template per track (module docstring).  weighted: a row's weight is the step's score (a row whose
+    score is not finite and > 0 adds nothing), else every row weighs 1.  Which of the two serves real video is unmeasured."""
+
+    def __init__(self, weighted=False):
+        self.weighted = bool(weighted)
+
+    def __repr__(self):
+        return f"Templates(weighted={self.weighted})"
+
+
+def new_template_state(n_streams, feat_dim):
+    """A fresh template table: dict of zero numpy arrays in the layout of fp_track_templates (every entry free)."""
+    S, D = int(n_streams), int(feat_dim)
+    return dict(tpl_i=np.zeros((S, POOL, 3), np.int32), tpl_w=np.zeros((S, POOL), np.float32),
+                tpl_sum=np.zeros((S, POOL, D), np.float32))
+
+
+def _template_args(tstate, frame, emb, xinv, stream_of_frame, track_id, track_clock, track_flags, keep, weight):
+    """The checked, contiguous host arguments of track_pool_numpy / track_pool_emulate."""
+    fresh = new_template_state(1, 4)
+    ok = isinstance(tstate, dict) and all(
+        isinstance(tstate.get(k), np.ndarray) and tstate[k].dtype == fresh[k].dtype and tstate[k].ndim == fresh[k].ndim
+        and tstate[k].flags.c_contiguous and tstate[k].flags.writeable for k in TEMPLATE_KEYS)
+    if ok:
+        S, D = tstate["tpl_sum"].shape[0], tstate["tpl_sum"].shape[2]
+        ok = tstate["tpl_i"].shape == (S, POOL, 3) and tstate["tpl_w"].shape == (S, POOL) and tstate["tpl_sum"].shape[1] == POOL
+    if not ok:
+        raise ValueError("the template state must be a dict of the writable C-contiguous arrays of new_template_state")
+    if S < 1 or D < 4 or D % 4 or D > L.TRACK_MAX_DIM:
+        raise ValueError(f"need n_streams >= 1 and feat_dim a multiple of 4 in 4 .. {L.TRACK_MAX_DIM}, got {S}, {D}")
+    if isinstance(keep, bool) or int(keep) != keep or int(keep) < 0:
+        raise ValueError(f"keep must be an int >= 0, got {keep!r}")
+    frame = np.ascontiguousarray(frame, np.int32).reshape(-1)
+    n = frame.shape[0]
+    emb = np.ascontiguousarray(emb, np.float32).reshape(n, D)
+    xinv = np.ascontiguousarray(xinv, np.float32).reshape(n)
+    sof = np.ascontiguousarray(stream_of_frame, np.int32).reshape(-1)
+    ids, clocks, flags = (np.ascontiguousarray(a, np.int32).reshape(n) for a in (track_id, track_clock, track_flags))
+    weight = None if weight is None else np.ascontiguousarray(weight, np.float32).reshape(n)
+    return S, D, n, frame, emb, xinv, sof, ids, clocks, flags, weight
+
+
+def track_pool_numpy(tstate, frame, emb, xinv, stream_of_frame, track_id, track_clock, track_flags, keep, weight=None):
+    """fp_track_pool_step in numpy float32 on a host table (new_template_state; updated IN PLACE): include/facepath.h
+    "Tracklets: templates", step by step.  track_id / track_clock / track_flags: a tracker step's per-row results, or crafted.
+    -> dict(track_emb (n, D) float32, track_emb_rows (n,) int32, track_emb_flags (n,) int32)."""
+    S, D, n, frame, emb, xinv, sof, ids, clocks, flags, weight = _template_args(
+        tstate, frame, emb, xinv, stream_of_frame, track_id, track_clock, track_flags, keep, weight)
+    B, keep = sof.shape[0], int(keep)
+    out = dict(track_emb=emb.copy(), track_emb_rows=np.zeros((n,), np.int32), track_emb_flags=np.zeros((n,), np.int32))
+    with np.errstate(all="ignore"):
+        for f in range(B):
+            s = int(sof[f])
+            if s < 0 or s >= S:
+                continue
+            ti, tw, ts = tstate["tpl_i"][s], tstate["tpl_w"][s], tstate["tpl_sum"][s]
+            for i in np.nonzero(frame == f)[0]:
+                tid, c = int(ids[i]), int(clocks[i])
+                if tid <= 0:
+                    continue
+                is_new, oflags = bool(flags[i] & NEW), 0
+                found = np.nonzero(ti[:, P_ID] == tid)[0]
+                take = bool(len(found)) and is_new
+                if len(found):
+                    e = int(found[0])
+                else:
+                    cand = np.nonzero((ti[:, P_ID] == 0) | (c - ti[:, P_LAST].astype(np.int64) > keep))[0]
+                    if len(cand):
+                        e = int(cand[0])
+                    else:
+                        e = int(np.argmin(ti[:, P_LAST]))       # the first of the smallest
+                        oflags |= TPL_EVICTED
+                    take = True
+                    if not is_new:
+                        oflags |= TPL_RESTART
+                if take:
+                    ts[e], tw[e] = 0, 0
+                    ti[e, P_ID], ti[e, P_ROWS] = tid, 0
+                w = np.float32(1) if weight is None else weight[i]
+                if np.isfinite(w) and w > 0:
+                    ts[e] = ts[e] + ((emb[i] * xinv[i]) * w)
+                    tw[e] = tw[e] + w
+                    ti[e, P_ROWS] += 1
+                ti[e, P_LAST] = c
+                out["track_emb_flags"][i] = oflags
+                if ti[e, P_ROWS] > 0:
+                    out["track_emb"][i], out["track_emb_rows"][i] = ts[e], ti[e, P_ROWS]
+    return out
+
+
+def _aligned_like(a):
+    """a, or a 16-byte aligned copy of it (numpy aligns what it allocates; a view may start anywhere)."""
+    if a.ctypes.data % 16 == 0:
+        return a
+    buf = np.empty((a.size + 4,), a.dtype)
+    off = (-buf.ctypes.data % 16) // 4
+    out = buf[off:off + a.size].reshape(a.shape)
+    out[...] = a
+    return out
+
+
+def track_pool_emulate(tstate, frame, emb, xinv, stream_of_frame, track_id, track_clock, track_flags, keep, weight=None):
+    """fp_track_pool_step_emulate on a host table (updated IN PLACE): track_pool_numpy's arguments and results.  Raises
+    FacepathError on a refusal.  Needs no GPU."""
+    lib = L.load()
+    S, D, n, frame, emb, xinv, sof, ids, clocks, flags, weight = _template_args(
+        tstate, frame, emb, xinv, stream_of_frame, track_id, track_clock, track_flags, keep, weight)
+    if tstate["tpl_sum"].ctypes.data % 16:
+        raise ValueError("tpl_sum must be 16-byte aligned")
+    emb = _aligned_like(emb)
+    out = dict(track_emb=_aligned_like(np.zeros((n, D), np.float32)), track_emb_rows=np.zeros((n,), np.int32),
+               track_emb_flags=np.zeros((n,), np.int32))
+    p = lambda a: None if a is None else C.c_void_p(a.ctypes.data)          # noqa: E731
+    st = L.FpTrackTemplates(*[p(tstate[k]) for k in TEMPLATE_KEYS])
+    L.check(lib.fp_track_pool_step_emulate(C.byref(st), S, D, p(frame), p(emb), p(xinv), p(weight), n, p(sof), sof.shape[0],
+                                           p(ids), p(clocks), p(flags), int(keep), *[p(out[k]) for k in TEMPLATE_OUT_KEYS]),
+            "fp_track_pool_step_emulate")
+    return out
 
 
 def new_motion_state(n_streams):
@@ -456,10 +590,12 @@ class StreamTracker:
     motion: None, or a ConstantVelocity: the IoU gate takes the predicted box (fp_tracklets_step_motion), the state gains
     "motion" (n_streams, SLOTS, MOTION_FLOATS) and step() also returns track_pred.
     reid: None, or a LostPool with lost_age > max_age (ValueError otherwise): expired tracks are parked and a returning face
-    takes its old id back (fp_tracklets_step_reid; its row carries REVIVED); the state gains the five LOST_KEYS arrays."""
+    takes its old id back (fp_tracklets_step_reid; its row carries REVIVED); the state gains the five LOST_KEYS arrays.
+    templates: None, or a Templates: a template per track (fp_track_pool_step after the tracker's launch); the state gains the
+    three TEMPLATE_KEYS arrays and step() also returns track_emb, track_emb_rows and track_emb_flags."""
 
     def __init__(self, n_streams, feat_dim, max_age, tau_near=TAU_NEAR, tau_far=TAU_FAR, iou_min=IOU_MIN, device="cuda:0",
-                 motion=None, reid=None):
+                 motion=None, reid=None, templates=None):
         check_params(n_streams, feat_dim, max_age, tau_near, tau_far, iou_min)
         if motion is not None and not isinstance(motion, ConstantVelocity):
             raise TypeError(f"motion must be None or a ConstantVelocity, got {type(motion).__name__}")
@@ -467,7 +603,9 @@ class StreamTracker:
             raise TypeError(f"reid must be None or a LostPool, got {type(reid).__name__}")
         if reid is not None:
             reid.check(max_age)
-        self.motion, self.reid = motion, reid
+        if templates is not None and not isinstance(templates, Templates):
+            raise TypeError(f"templates must be None or a Templates, got {type(templates).__name__}")
+        self.motion, self.reid, self.templates_opt = motion, reid, templates
         self.S, self.D, self.max_age = int(n_streams), int(feat_dim), int(max_age)
         self.tau_near, self.tau_far, self.iou_min = float(tau_near), float(tau_far), float(iou_min)
         self.dev = torch.device(device)
@@ -478,10 +616,20 @@ class StreamTracker:
         if reid is not None:
             self.state.update({k: torch.from_numpy(v).to(self.dev) for k, v in new_lost_state(self.S, self.D).items()})
             self._lost = _lost_struct(self.state, L.ptr)
+        if templates is not None:
+            self.state.update({k: torch.from_numpy(v).to(self.dev) for k, v in new_template_state(self.S, self.D).items()})
+            self._tpl = L.FpTrackTemplates(*[L.ptr(self.state[k]) for k in TEMPLATE_KEYS])
+            self._tpl_ws = None
+
+    @property
+    def keep(self):
+        """The clocks a template outlives its track's last row: lost_age with reid=, else max_age."""
+        return self.reid.lost_age if self.reid is not None else self.max_age
 
     @property
     def state_keys(self):
-        return STATE_KEYS + (("motion",) if self.motion is not None else ()) + (LOST_KEYS if self.reid is not None else ())
+        return (STATE_KEYS + (("motion",) if self.motion is not None else ()) + (LOST_KEYS if self.reid is not None else ())
+                + (TEMPLATE_KEYS if self.templates_opt is not None else ()))
 
     def step(self, frame, boxes, emb, stream_of_frame, score=None, n=None, xinv=None):
         """One launch on the current stream.  frame (n,) int32 batch index of every face row, boxes (n, 4) fp32 (the
@@ -490,7 +638,9 @@ class StreamTracker:
         has them (default: fp_row_inv_norm here).  Device tensors; a frames / boxes tensor with a row stride (a
         column slice of info) is made contiguous.  -> dict(track_id, track_hits, track_clock, track_flags), (n,) int32 each;
         with motion= also track_pred (n, 4) fp32: the box a matched row's track was predicted at, zeros for every other row.
-        With reid= a row that continues a parked track carries REVIVED in track_flags (never NEW) and the track's old id."""
+        With reid= a row that continues a parked track carries REVIVED in track_flags (never NEW) and the track's old id.
+        With templates= also track_emb (n, D) fp32, track_emb_rows and track_emb_flags (n,) int32: the template of the row's
+        track after the row (the row's own embedding and 0 rows where it has no track), two more launches."""
         n = int(emb.shape[0] if n is None else n)
         f32c = lambda t: t[:n].to(self.dev, torch.float32).contiguous()      # noqa: E731
         frame = frame[:n].to(self.dev, torch.int32).contiguous()
@@ -518,7 +668,34 @@ class StreamTracker:
             tail = (L.ptr(self.state["motion"]), self.motion.std_pos, self.motion.std_vel, L.ptr(out["track_pred"]))
         _step_call(self._struct, self._lost if self.reid is not None else None, rows, tail, self.reid, False,
                    L.current_stream(self.dev))
+        if self.templates_opt is not None:
+            out["track_emb"] = torch.empty((n, self.D), dtype=torch.float32, device=self.dev)
+            out["track_emb_rows"] = torch.empty((n,), dtype=torch.int32, device=self.dev)
+            out["track_emb_flags"] = torch.empty((n,), dtype=torch.int32, device=self.dev)
+            need = lib.fp_track_pool_workspace_bytes(n)
+            if self._tpl_ws is None or self._tpl_ws.numel() < need:
+                self._tpl_ws = torch.empty((need,), dtype=torch.uint8, device=self.dev)
+            weight = score if self.templates_opt.weighted else None
+            if self.templates_opt.weighted and score is None:
+                raise ValueError("Templates(weighted=True) needs the step's score")
+            L.check(lib.fp_track_pool_step(C.byref(self._tpl), self.S, self.D, L.ptr(frame), L.ptr(emb), L.ptr(xinv), L.ptr(weight),
+                                           n, L.ptr(sof), sof.shape[0], L.ptr(out["track_id"]), L.ptr(out["track_clock"]),
+                                           L.ptr(out["track_flags"]), self.keep, *[L.ptr(out[k]) for k in TEMPLATE_OUT_KEYS],
+                                           L.ptr(self._tpl_ws), self._tpl_ws.numel(), L.current_stream(self.dev)),
+                    "fp_track_pool_step")
         return out
+
+    def templates(self, stream):
+        """The templates of one stream (a host read; ValueError without templates=): dict of numpy arrays entry, id, rows, wsum,
+        last_clock and sum (k, D), in entry order."""
+        if self.templates_opt is None:
+            raise ValueError("this tracker keeps no templates (templates=)")
+        s = int(stream)
+        if not 0 <= s < self.S:
+            raise ValueError(f"stream {stream} outside 0 .. {self.S - 1}")
+        ti, tw, ts = (self.state[k][s].cpu().numpy() for k in TEMPLATE_KEYS)
+        e = np.nonzero(ti[:, P_ID] != 0)[0]
+        return dict(entry=e, id=ti[e, P_ID], rows=ti[e, P_ROWS], wsum=tw[e], last_clock=ti[e, P_LAST], sum=ts[e])
 
     def tracks(self, stream):
         """The live slots of one stream (a host read): dict of numpy arrays slot, id, first_clock, last_clock, hits, box,
@@ -567,6 +744,9 @@ class StreamTracker:
         if self.reid is not None:
             for k in LOST_KEYS:
                 self.state[k][idx] = 0
+        if self.templates_opt is not None:
+            for k in TEMPLATE_KEYS:
+                self.state[k][idx] = 0
 
     def state_dict(self):
         """A copy of the device state and the parameters (host tensors)."""
@@ -582,7 +762,8 @@ class StreamTracker:
     def load_state_dict(self, d):
         """The arrays of a state_dict of a tracker with the same n_streams and feat_dim (ValueError otherwise), copied into
         this tracker's own buffers; the parameters stay this tracker's.  A tracker with motion= needs the "motion" array too
-        (KeyError without it); one without ignores it.  The same holds for the five LOST_KEYS arrays and reid=."""
+        (KeyError without it); one without ignores it.  The same holds for the five LOST_KEYS arrays and reid=, and for the
+        three TEMPLATE_KEYS arrays and templates=."""
         for k in self.state_keys:
             if tuple(d[k].shape) != tuple(self.state[k].shape):
                 raise ValueError(f"state_dict[{k!r}] has shape {tuple(d[k].shape)}, this tracker {tuple(self.state[k].shape)}")
@@ -591,7 +772,8 @@ class StreamTracker:
 
     def host_state(self):
         """The state as a dict of numpy arrays (new_state's layout, plus "motion" with motion= and the LOST_KEYS arrays with
-        reid=): what track_step_numpy / track_step_emulate continue from."""
+        reid= and the TEMPLATE_KEYS arrays with templates=): what track_step_numpy / track_step_emulate and track_pool_numpy /
+        track_pool_emulate continue from."""
         return {k: self.state[k].detach().cpu().numpy().copy() for k in self.state_keys}
 
 
@@ -603,12 +785,14 @@ class TrackBook:
     def __init__(self):
         self.records = {}
 
-    def update(self, out, frame, boxes, stream_of_frame, emb=None, score=None, frame_base=0):
+    def update(self, out, frame, boxes, stream_of_frame, emb=None, score=None, frame_base=0, track_emb=None, track_emb_rows=None):
         """out: a step's four per-row arrays (dict; tensors or numpy); frame / boxes / emb / score / stream_of_frame: the
-        step's inputs.  -> the keys (stream, id) the step touched."""
+        step's inputs.  track_emb / track_emb_rows: the step's templates (a tracker with templates=); a record then keeps the
+        latest of its track as `template` (D,) float32 and `template_rows`.  -> the keys (stream, id) the step touched."""
         host = lambda t: None if t is None else (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t))  # noqa: E731
         ids, hits, clocks, flags = (host(out[k]) for k in OUT_KEYS)
         frame, boxes, emb, score, sof = host(frame), host(boxes), host(emb), host(score), host(stream_of_frame)
+        track_emb, track_emb_rows = host(track_emb), host(track_emb_rows)
         touched = []
         for i in range(len(ids)):
             if ids[i] <= 0:
@@ -624,6 +808,9 @@ class TrackBook:
                 rec["best_frame"], rec["best_clock"] = int(frame_base) + int(frame[i]), int(clocks[i])
                 rec["best_box"] = [float(v) for v in boxes[i]]
                 rec["best_emb"] = None if emb is None else np.array(emb[i], np.float32)
+            if track_emb is not None:
+                rec["template"] = np.array(track_emb[i], np.float32)
+                rec["template_rows"] = 0 if track_emb_rows is None else int(track_emb_rows[i])
             touched.append(key)
         return touched
 

@@ -1628,6 +1628,77 @@ int fp_tracklets_step_reid_emulate(const fp_track_state* state, const fp_track_l
                                    float std_vel, float* track_pred);
 
 /*
+ * Tracklets: templates (build-defined; DESIGN §7 "Tracklets: templates"; csrc/trackpool.hip).  Opt-in: the tracker kernels,
+ * their state and every result of theirs are untouched.  All additive; FP_ABI_VERSION stays 15.
+ *
+ * A TEMPLATE sums up a sighting: the weighted sum of the normalised embeddings of every row of a track, kept per stream on the
+ * device and handed back with every row, so that a gallery search can ask "who is this track" instead of "who is this row".
+ * The entry points take the tracker's per-row results as DATA and read nothing of the tracker's state.
+ * State, owned by the caller (fp_track_templates: three arrays, zero-filled for a fresh table), per stream s a table of
+ * FP_TRACK_POOL = 128 entries (FP_TRACK_SLOTS + FP_TRACK_LOST: one for every live and every parked track):
+ *   tpl_i    [S][FP_TRACK_POOL][3] int32     id (0 = free), last_clock, rows
+ *   tpl_w    [S][FP_TRACK_POOL] fp32         the sum of the weights of the rows that were added
+ *   tpl_sum  [S][FP_TRACK_POOL][D] fp32      the sum itself
+ * Inputs of a step: frame, emb, xinv, stream_of_frame, B as for "Tracklets"; track_id, track_clock, track_flags as
+ * fp_tracklets_step* wrote them (or crafted); weight [n] fp32, or NULL for 1.0 everywhere; keep >= 0, the clocks an entry
+ * outlives its last row (the tracker's lost_age with re-identification, else its max_age).
+ * Order: the rows of a stream in the tracker's order -- its frames in ascending batch index, the rows of a frame in row order
+ * (they need not be contiguous); streams are independent.  A row TAKES PART when its frame has a stream (frame[i] in [0, B),
+ * stream_of_frame in [0, n_streams)) and track_id[i] > 0.  For such a row, with c = track_clock[i]:
+ *   1. The entry of the stream whose id is track_id[i] is looked up (the lowest index, should a crafted table hold it twice).
+ *   2. Found, and the row carries FP_TRACK_NEW: the id is being given out again; the entry is cleared (5) and reused.
+ *   3. Not found: the lowest-index entry that is free (id 0) or stale (c - last_clock > keep, in 64-bit integers) is taken.
+ *   4. None free or stale: the entry with the smallest last_clock is taken, the lowest index on ties, and the row is flagged
+ *      FP_TRACK_TPL_EVICTED.
+ *   5. An entry cleared or taken: rows = 0, its weight sum and its D sums = +0, id = track_id[i].
+ *   6. A row that is neither NEW nor found is flagged FP_TRACK_TPL_RESTART: the track goes on, its template starts again.
+ *   7. w = weight[i] if that is finite and > 0, else 0 (NULL weight: 1).
+ *   8. If w > 0: for every j, sum[j] = sum[j] + ((emb[i][j] * xinv[i]) * w) -- fp32, three roundings, in that order, no
+ *      contraction --, the weight sum = the weight sum + w, rows += 1.
+ *   9. last_clock = c, whether or not the row added.
+ * Per-row outputs: track_emb[i] [D] = the entry's sum after the row (unnormalised: nothing divides, a cosine does not mind the
+ * scale); track_emb_rows[i] = the entry's rows after the row; track_emb_flags[i] (TPL_EVICTED, TPL_RESTART).  A row that does
+ * not take part, or whose entry has rows == 0 after it, gets its own emb[i] bit for bit and track_emb_rows = 0 (a face without a
+ * track is its own template, a dead row stays dead for a search); a row that does not take part has flags 0.
+ * There is no reduction: the device, the host twin and numpy float32 share every bit of every output and of the state.  (One
+ * exception no caller meets through the tracker: where a sum turns NaN, all three hold a NaN, of the machine's own sign and
+ * payload.)  A step equals the same frames split anywhere with the state carried; two runs are bit-identical.
+ * Out of scope: decaying or windowed templates, vote ledgers, templates across streams, tables of more than 128 entries, and
+ * any measured value of `weight` or `keep`, or of the gain on real video.
+ *
+ * fp_track_pool_step: two launches, nothing read back, no global atomics.  The directory launch, one wave per stream and
+ * integers only, resolves every row's entry and flags and writes, per (stream, entry) SEGMENT -- a run of rows on one entry
+ * between two clearings; an entry evicted in the middle of a step yields two --, the ordered list of its rows to the workspace.
+ * The accumulate launch runs one workgroup of D / 4 lanes per touched entry, a float4 of the running sum in each lane's
+ * registers along its segments; tpl_sum is read at most once and written once per touched entry.  workspace: device memory of
+ * fp_track_pool_workspace_bytes(n) bytes, 4-byte aligned, contents irrelevant before and after.  Every pointer but `tpl` itself
+ * (a HOST struct of device pointers) is device memory the host does not read.  Refusals before any launch
+ * (FP_ERR_INVALID_ARG): a NULL tpl or table array, n_streams < 1, D not a multiple of 4, D < 4 or D > FP_TRACK_MAX_DIM, n < 0
+ * or n > FP_TRACK_MAX_ROWS, B < 0, keep < 0, a NULL stream_of_frame with B > 0, a NULL row input or output with n > 0 (weight
+ * may be NULL), emb, track_emb or tpl_sum not 16-byte aligned, with n > 0 a NULL or too small workspace.  n == 0: FP_OK, nothing
+ * launched, nothing changed (a frame without rows moves no template).  B == 0 with n > 0: every row passes through.
+ * fp_track_pool_step_emulate: the same tests and the same arithmetic serially on HOST memory (every pointer HOST), the same bits.
+ */
+#define FP_TRACK_POOL 128
+#define FP_TRACK_TPL_EVICTED 1
+#define FP_TRACK_TPL_RESTART 2
+typedef struct fp_track_templates {
+  int32_t* tpl_i;
+  float* tpl_w;
+  float* tpl_sum;
+} fp_track_templates;
+size_t fp_track_pool_workspace_bytes(int n);
+int fp_track_pool_step(const fp_track_templates* tpl /*host struct*/, int n_streams, int D, const int32_t* frame, const float* emb,
+                       const float* xinv, const float* weight /* or NULL */, int n, const int32_t* stream_of_frame /* B */, int B,
+                       const int32_t* track_id, const int32_t* track_clock, const int32_t* track_flags, int keep,
+                       float* track_emb /* n x D */, int32_t* track_emb_rows, int32_t* track_emb_flags, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int fp_track_pool_step_emulate(const fp_track_templates* tpl, int n_streams, int D, const int32_t* frame, const float* emb,
+                               const float* xinv, const float* weight, int n, const int32_t* stream_of_frame, int B,
+                               const int32_t* track_id, const int32_t* track_clock, const int32_t* track_flags, int keep,
+                               float* track_emb, int32_t* track_emb_rows, int32_t* track_emb_flags);
+
+/*
  * Tracker evaluation: CLEAR-MOT and IDF1 (build-defined, the reference calls no tracking scorer; DESIGN §7 "Tracker
  * evaluation"; csrc/moteval.hip; tracking_eval.py holds the numpy restatement and the host half).  All additive: ABI 14.
  *

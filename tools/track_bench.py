@@ -16,12 +16,18 @@ motion_cost_us_per_frame = their medians' difference over the frames one workgro
 The reid leg, likewise: a StreamTracker with reid=LostPool (fp_tracklets_step_reid) on the same rows, alternated with the plain
 one: reid_off_ms, reid_on_ms, reid_on_over_off and reid_cost_us_per_frame.  In layouts a to c nothing ever expires: the pool
 stays empty and the leg prices the kernel with the pool compiled in; layout d prices parking and step 3b.
+The templates leg (--templates only): a StreamTracker with templates=Templates() (fp_track_pool_step behind the tracker's launch)
+on the same rows, alternated with the plain one: templates_off_ms, templates_on_ms, templates_cost_ms; and pool_ms, the two
+launches of fp_track_pool_step alone on the rows and the ids of a finished step, beside its two yardsticks of the same run:
+pool_over_tracklets (against tracklets_ms, the tracker's launch on the same rows) and pool_floor_bytes = 4 * n * D * 4 (emb read,
+track_emb written, twice over for the state and the lists' slack) with pool_gbps = those bytes over pool_ms.  With --templates
+the pipeline block gains the kind "templates".
 Then the pipeline: FacePipeline.step on 256 synthetic frames without tracker=, with it, with a tracker with motion= and with one
 with reid=, and
 step_overlapped with two_streams (the tracker on the side stream) likewise.  Timed with device events after warm-up, `--iters` calls per round,
 `--rounds` rounds; median with min .. max.  Prints one JSON line.  No pass / fail threshold.
 
-  python tools/track_bench.py [--iters 10] [--rounds 5] [--small] [--no-pipeline]
+  python tools/track_bench.py [--iters 10] [--rounds 5] [--small] [--no-pipeline] [--templates]
 
 --small: 8 frames per layout, 1 iteration, 2 rounds."""
 import argparse
@@ -38,7 +44,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from face_detection_and_recognition_amd import workload as W  # noqa: E402
 from face_detection_and_recognition_amd.face_extraction.face_tracker import FaceTracker  # noqa: E402
 from face_detection_and_recognition_amd.pipeline import FacePipeline  # noqa: E402
-from face_detection_and_recognition_amd.tracking import REVIVED, ConstantVelocity, LostPool, StreamTracker  # noqa: E402
+from face_detection_and_recognition_amd.tracking import REVIVED, ConstantVelocity, LostPool, StreamTracker, Templates  # noqa: E402
 
 D = 512
 REID = LostPool(0.6, 1 << 20)      # sightings of one identity have cosines of about 0.9, two identities of about 0
@@ -131,7 +137,48 @@ def measure_layout(name, rows, max_age, args, dev):
     rec["reid_on_over_off"] = round(rec["reid_on_ms"]["median"] / rec["reid_off_ms"]["median"], 4)
     rec["reid_cost_us_per_frame"] = round((rec["reid_on_ms"]["median"] - rec["reid_off_ms"]["median"]) * 1000.0
                                           / (rows["B"] // rows["n_streams"]), 3)
+    if args.templates:
+        measure_templates(rec, rows, max_age, step, args, dev)
     return rec
+
+
+def measure_templates(rec, rows, max_age, step, args, dev):
+    """The templates leg of one layout (module docstring), written into rec."""
+    import ctypes as C
+
+    from face_detection_and_recognition_amd import _lib as L
+    from face_detection_and_recognition_amd import tracking as T
+    trt = StreamTracker(rows["n_streams"], D, max_age, device=dev, templates=Templates())
+    tstep = lambda: trt.step(rows["frame"], rows["boxes"], rows["emb"], rows["sof"])   # noqa: E731
+    tstep()
+    tout = tstep()
+    torch.cuda.synchronize()
+    rec["template_entries"] = int((trt.state["tpl_i"][:, :, 0] != 0).sum().item())
+    rec["template_rows_max"] = int(tout["track_emb_rows"].max().item())
+    off, on = [], []
+    for _ in range(args.rounds):
+        off.append(timed(step, args.iters, dev))
+        on.append(timed(tstep, args.iters, dev))
+    rec["templates_off_ms"], rec["templates_on_ms"] = summary(off), summary(on)
+    rec["templates_cost_ms"] = round(rec["templates_on_ms"]["median"] - rec["templates_off_ms"]["median"], 4)
+    # the pool's two launches alone, on the rows and the results of the finished step
+    lib, n = L.load(), int(rows["frame"].shape[0])
+    xinv = torch.empty((n,), dtype=torch.float32, device=dev)
+    L.check(lib.fp_row_inv_norm(L.ptr(rows["emb"]), n, D, L.ptr(xinv), L.current_stream(dev)), "fp_row_inv_norm")
+    ws = torch.empty((lib.fp_track_pool_workspace_bytes(n),), dtype=torch.uint8, device=dev)
+    outs = [tout[k] for k in T.TEMPLATE_OUT_KEYS]
+
+    def pool():
+        L.check(lib.fp_track_pool_step(C.byref(trt._tpl), trt.S, D, L.ptr(rows["frame"]), L.ptr(rows["emb"]), L.ptr(xinv), None, n,
+                                       L.ptr(rows["sof"]), rows["B"], L.ptr(tout["track_id"]), L.ptr(tout["track_clock"]),
+                                       L.ptr(tout["track_flags"]), trt.keep, *[L.ptr(t) for t in outs], L.ptr(ws), ws.numel(),
+                                       L.current_stream(dev)), "fp_track_pool_step")
+    pool()
+    torch.cuda.synchronize()
+    rec["pool_ms"] = summary([timed(pool, args.iters, dev) for _ in range(args.rounds)])
+    rec["pool_over_tracklets"] = round(rec["pool_ms"]["median"] / rec["tracklets_ms"]["median"], 4)
+    rec["pool_floor_bytes"] = 4 * n * D * 4
+    rec["pool_gbps"] = round(rec["pool_floor_bytes"] / (rec["pool_ms"]["median"] * 1e-3) / 1e9, 2)
 
 
 def measure_pipeline(n_frames, args, dev):
@@ -141,9 +188,10 @@ def measure_pipeline(n_frames, args, dev):
     ref = W.make_reference(256, dev)
     rec = dict(frames=n_frames)
     for two in (False, True):
-        for kind in ("plain", "tracker", "motion", "reid"):
+        for kind in ("plain", "tracker", "motion", "reid") + (("templates",) if args.templates else ()):
             tr = None if kind == "plain" else StreamTracker(1, D, 8, device=dev, motion=MOTION if kind == "motion" else None,
-                                                            reid=REID if kind == "reid" else None)
+                                                            reid=REID if kind == "reid" else None,
+                                                            templates=Templates() if kind == "templates" else None)
             pipe = FacePipeline(det, emb, ref, tau=0.0, two_streams=two, tracker=tr)
             if two:
                 def fn():
@@ -165,6 +213,8 @@ def measure_pipeline(n_frames, args, dev):
         rec[k + "_tracker_cost_ms"] = round(rec[k + "_tracker_ms"]["median"] - rec[k + "_plain_ms"]["median"], 4)
         rec[k + "_motion_cost_ms"] = round(rec[k + "_motion_ms"]["median"] - rec[k + "_tracker_ms"]["median"], 4)
         rec[k + "_reid_cost_ms"] = round(rec[k + "_reid_ms"]["median"] - rec[k + "_tracker_ms"]["median"], 4)
+        if args.templates:
+            rec[k + "_templates_cost_ms"] = round(rec[k + "_templates_ms"]["median"] - rec[k + "_tracker_ms"]["median"], 4)
     return rec
 
 
@@ -174,6 +224,7 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--small", action="store_true")
     ap.add_argument("--no-pipeline", dest="pipeline", action="store_false")
+    ap.add_argument("--templates", action="store_true", help="add the templates leg (fp_track_pool_step)")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     if args.small:
